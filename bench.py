@@ -12,7 +12,9 @@ all-gather: RCCL over xGMI) whose R@K / MR must equal the single-rank result.
 (option dual_stream, bit-identical results).  The `roofline*` objects and `stage_ms_per_step` time the kernels on ONE stream
 (a kernel's roofline is a property of the kernel running alone); `single_stream` repeats the timed loop in that mode.
 
-Usage: python bench.py [--gpus N --steps K --warmup W]
+Usage: python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]
+  --dump-outputs DIR: rank 0 writes what the LAST timed step returned (the (clips,150,512) fp32 gesture embeddings) to
+  DIR/gesture_embeddings.npy; the inputs are seeded, so two builds run with the same arguments can be compared output for output.
   N > 1 without a torchrun environment: this process starts N fresh rank processes itself (it makes no GPU
   call before or after doing so) and relays rank 0's JSON line.  Under `python -m torch.distributed.run
   --nproc-per-node N bench.py --gpus N ...` the ranks come from the environment; WORLD_SIZE != N is an error.
@@ -30,6 +32,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 CLIPS, FRAMES = 32, 150
+DUMP_MAX_BYTES = 64 << 20          # --dump-outputs: larger outputs are cut to a seeded sample of whole clips
 # ---- algorithmic work per clip (never padded K or tile waste).  SURVEY counts 170 window-de-duplicated
 # conv positions per 150-frame clip; the engine evaluates the 154 DISTINCT ones (positions 0..8 and T+11..T+19 of the
 # edge-padded clip see five copies of one frame), and every utilisation figure below is priced on those 154.
@@ -207,6 +210,19 @@ def config3(eng, jg, dev, steps, warmup=3, clips=64):
                     "word pooling (host segment logic included) + fusion / align MLPs"}
 
 
+def dump_outputs(path, emb):
+    """Write the timed path's output (numpy float32, clips first) as path/gesture_embeddings.npy.  Over DUMP_MAX_BYTES a fixed
+    seeded sample of clips is written instead, with their indices in path/gesture_embeddings_clip_index.npy (float64)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    per_clip = emb[0].nbytes
+    if emb.nbytes > DUMP_MAX_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(emb.shape[0], DUMP_MAX_BYTES // per_clip, replace=False))
+        emb = emb[keep]
+        np.save(os.path.join(path, "gesture_embeddings_clip_index.npy"), keep.astype(np.float64))
+    np.save(os.path.join(path, "gesture_embeddings.npy"), np.ascontiguousarray(emb, dtype=np.float32))
+
+
 def launch_ranks(args, argv, timeout_s=1800.0):
     """--gpus N > 1 outside torchrun: start N fresh rank processes (one per GPU).  This parent never touches the GPU.
     Watchdog: the children are polled; when one exits non-zero (e.g. before the rendezvous) the others are terminated instead
@@ -274,8 +290,12 @@ def main():
                     help="testing aid: allow more ranks than GPUs (ranks share devices round-robin; forces backend gloo; flagged in the output)")
     ap.add_argument("--extra-streams", type=int, default=0, help="robustness experiment: the application owns this many other (used) streams before the engine exists")
     ap.add_argument("--opt", action="append", default=[], help="engine option name=int (tuning experiments)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's embeddings (rank 0) to DIR/gesture_embeddings.npy, float32, at most 64 MB")
     ap.add_argument("--only", default=None, choices=["config3"], help="run just one secondary measurement (for rocprofv3 summaries) and print its object")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     env_world = os.environ.get("WORLD_SIZE")
     if args.gpus > 1 and env_world is None:
@@ -360,6 +380,8 @@ def main():
     dt = timed_loop(args.steps)
     per_rank_ms = [v / args.steps * 1e3 for v in timed_loop.per_rank_s]
     assert torch.isfinite(out).all(), "non-finite embeddings"
+    # the measurements below reuse `out`: keep the last timed step's result now
+    timed_out = out.cpu().numpy() if args.dump_outputs and rank == 0 else None
 
     # ---- per-kernel timing with HIP events on the launch stream (dominant kernel: conv1)
     # (1) the dominant kernel alone: only the conv1 launch carries events, the rest of the step runs back to back as in the
@@ -722,6 +744,8 @@ def main():
             res["cpu_baseline"] = cpu_baseline(frames_host[:2])
         else:
             res["cpu_baseline"] = None
+        if timed_out is not None:
+            dump_outputs(args.dump_outputs, timed_out)
         print(json.dumps(res))
     jdist.barrier()
     if world > 1:
