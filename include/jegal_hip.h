@@ -107,7 +107,11 @@ int jg_set_chunk(jg_handle* h, int clips_per_chunk);
  *   "gemm_timeline"   1: print a per-tile phase timeline of every GEMM launch to stderr (debug)
  *   "jegal_fp32_ends" 1 (default): the two ends of the JEGAL gesture branch (proj_ip_rgb; final norm + proj_op_rgb + proj_op_align_gesture) and
  *                     of the content path (proj_op_text, fusion / align MLPs) keep fp32 activations and run on the split-operand GEMM
- *                     (three fp16 MFMAs per tile: fp32-grade products); 0: the round-5 arithmetic (fp16 activations, hi+lo weights).  DESIGN.md section 3
+ *                     (three fp16 MFMAs per tile: fp32-grade products); 0: the round-5 arithmetic (fp16 activations, hi+lo weights).  DESIGN.md section 3.
+ *                     "fp32-grade" holds for activation rows of rms >= ~2^-7 and |a| < 65520: below |a| ~ 2^-3 the lo half of the split is an fp16
+ *                     subnormal with an absolute quantum of 2^-24.  At these call sites the activations have row rms 0.69 .. ~9 and |a| <= 42 over
+ *                     the six synthetic weight families (tools/x3_operand_range.py, profiles/x3_operand_range.json); tests/test_gpu_kernels_fp64.py
+ *                     holds the kernel to the fp32 bound for operand row rms 2^-6 / sqrt 3 .. 2^10 / sqrt 3
  *   "jegal_ffn_x3"    0 (default) / 1: the six feed-forward sub-layers of the JEGAL gesture branch on the split-operand GEMM as well (gesture error
  *                     3.5e-4 -> 2.5e-4 on the Gaussian draw for +3 % step time)
  *   "conv_round_diffuse" 1 (default; before jg_finalize_weights): conv weights are rounded to fp16 with error diffusion across the taps of each
@@ -175,6 +179,47 @@ int jg_gestsync_clip_ragged(jg_handle* h, const void* frames, int frames_dtype, 
 /* Kernel-level check point: conv1+BN+ReLU+maxpool (gestsync.py:36-46) only.  frames (B,T,270,480,3) u8,
  * pad = temporal edge padding (12 for clips, 0 for a raw 25-frame window) -> out (B*(T+2*pad-4),43,78,64) fp16 NHWC. */
 int jg_debug_conv1_pool(jg_handle* h, const void* frames_u8, int B, int T, int pad, void* out_f16);
+/* Kernel check points (tests/test_gpu_kernels_fp64.py): each runs exactly ONE launch of a production launcher on caller operands.  The
+ * handle's options (gemm_tile, gemm_small_tile, gemm_big_tile, gemm_persistent, num_cu, gemm_counted, gemm_stagger, gemm_glds, attn_mfma,
+ * stream_fp16 via the operands passed) pick the kernel instance exactly as in production, and the handle's precision picks the build: under
+ * JG_PREC_BF16 every 16-bit operand and output is bf16, otherwise fp16.  All pointers are device buffers the caller owns, leading
+ * dimensions are in elements.  A shape or argument set the launcher rejects returns JG_ERR_ARG and launches nothing.  Asynchronous.
+ * Linear GEMM (launch_gemm, GemmArgs in jegal_amd/csrc/common.h):
+ *   out[m][n] = act( sum_k A[m][k] (Wh[n][k] + Wl[n][k]) * scale[n] + bias[n] + res[m % res_mod][n] ),  act: relu 0 none / 1 ReLU / 2 GELU;
+ *   bias_clip [nclips][N]: row m takes bias_clip[min(m / rpc, nclips - 1)] instead of bias (fp16 out16 alone);
+ *   ln_w != NULL: residual + LayerNorm fused (N = 512, M >= 1024): out16 (+ out8) = LN(acc + bias + res16 (+ res8)) in the tiled token order;
+ *   ln_mode 1 / 2: the implicit-LayerNorm consumer / producer epilogues (ln_stats, xres_hi / xres_lo, out_lo, stat_out as in GemmArgs). */
+typedef struct jg_gemm_check {
+    const void* A; int64_t lda;                   /* [M][lda] 16-bit */
+    const void* Wh; const void* Wl; int64_t ldw;  /* [N][ldw] 16-bit; Wl NULL: single weights */
+    int M, N, K;
+    const float* scale; const float* bias;        /* per n, or NULL */
+    const float* bias_clip; int rpc, nclips;
+    const float* res; int64_t ldr; int res_mod;   /* fp32 residual, row m % res_mod (0: m) */
+    int relu;
+    float* out32; void* out16; int64_t ldc;       /* either or both */
+    const float* ln_w; const float* ln_b; const void* res16; const void* res8; void* out8;
+    int ln_mode; const float* ln_stats; const void* xres_hi; const void* xres_lo; void* out_lo; float* stat_out;
+} jg_gemm_check;
+int jg_debug_gemm_check(jg_handle* h, const jg_gemm_check* c);
+/* fp32 GEMM of the audit mode (launch_gemm32): out = act(A W^T * scale + bias + res[m % res_mod]), act 0 / 1 ReLU / 2 exact GELU. */
+int jg_debug_gemm32(jg_handle* h, const float* A, int64_t lda, const float* W, int64_t ldw, int M, int N, int K, const float* scale,
+                    const float* bias, const float* res, int64_t ldr, int res_mod, int act, float* out, int64_t ldc);
+/* Split-operand GEMM (launch_gemm_x3, option jegal_fp32_ends): fp32 A, fp16 Wh + Wl, fp32 out = relu?(A W^T + bias + res[m % res_mod]).
+ * fp16 weights in every precision mode.  K % 256 == 0, N % 128 == 0. */
+int jg_debug_gemm_x3(jg_handle* h, const float* A, int64_t lda, const void* Wh, const void* Wl, int64_t ldw, int M, int N, int K,
+                     const float* bias, const float* res, int64_t ldr, int res_mod, int relu, float* out, int64_t ldc);
+/* softmax(q k^T / sqrt(dk), masked_fill(keymask == 0, -1e9)) v per (sequence, head) (launch_attention): qkv [B*S][3*H*dk] 16-bit (q | k | v),
+ * keymask (B,S) fp32 or NULL, out [B*S][H*dk] 16-bit. */
+int jg_debug_attention(jg_handle* h, const void* qkv, const float* keymask, int B, int S, int H, int dk, void* out);
+/* The layer-0 gather form (launch_attention_gather, fp16 build only; dk = 64, S <= 32): token j of window b = (clip b / Twin, frame b % Twin)
+ * is row clip * P + clamp(b % Twin + j - shift, 0, P - 1) of qkv_pos [.][3*H*64] plus row j of pe_qkv [S][3*H*64]. */
+int jg_debug_attention_gather(jg_handle* h, const void* qkv_pos, const void* pe_qkv, int Twin, int P, int shift, int B, int S, int H, void* out);
+/* fp32 attention of the audit mode (launch_attention32): as jg_debug_attention with fp32 qkv / out. */
+int jg_debug_attention32(jg_handle* h, const float* qkv, const float* keymask, int B, int S, int H, int dk, float* out);
+/* Name of the kernel instance the last check point launched, with its template arguments (e.g. "gemm_glds_kernel<1,0,4,4,2,0,0,0,0>";
+ * empty if it launched nothing).  Host only, no synchronisation. */
+int jg_debug_last_kernel(jg_handle* h, char* buf, int len);
 /* Check point for "conv2_row_skip": the MINIMUM over the positions of the last conv stack of the leading conv2 output rows that
  * were read from the const chain instead of computed (every position skips its own count: jg_debug_conv_rows);
  * 0: none, or the option is off.  Synchronises the stream. */

@@ -20,6 +20,17 @@ STAGES = ["stack_frames", "conv1", "maxpool", "conv2-fc6+audio_cnn", "gemm", "at
 
 _P = ctypes.c_void_p
 _I = ctypes.c_int
+_L = ctypes.c_int64
+JG_ERR_ARG = -1
+
+
+class GemmCheck(ctypes.Structure):
+    """struct jg_gemm_check (include/jegal_hip.h): operands of one jg_debug_gemm_check launch."""
+    _fields_ = [("A", _P), ("lda", _L), ("Wh", _P), ("Wl", _P), ("ldw", _L), ("M", _I), ("N", _I), ("K", _I),
+                ("scale", _P), ("bias", _P), ("bias_clip", _P), ("rpc", _I), ("nclips", _I),
+                ("res", _P), ("ldr", _L), ("res_mod", _I), ("relu", _I), ("out32", _P), ("out16", _P), ("ldc", _L),
+                ("ln_w", _P), ("ln_b", _P), ("res16", _P), ("res8", _P), ("out8", _P),
+                ("ln_mode", _I), ("ln_stats", _P), ("xres_hi", _P), ("xres_lo", _P), ("out_lo", _P), ("stat_out", _P)]
 _SIGS = {
     "jg_create": [_I, ctypes.POINTER(_P)],
     "jg_destroy": [_P],
@@ -39,6 +50,13 @@ _SIGS = {
     "jg_debug_gemm": [_P, _I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_double)],
     "jg_debug_gemm_ex": [_P, _P, _P, _I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_double)],
     "jg_debug_conv2_rowskip": [_P, ctypes.POINTER(ctypes.c_int)],
+    "jg_debug_gemm_check": [_P, _P],
+    "jg_debug_gemm32": [_P, _P, _L, _P, _L, _I, _I, _I, _P, _P, _P, _L, _I, _I, _P, _L],
+    "jg_debug_gemm_x3": [_P, _P, _L, _P, _P, _L, _I, _I, _I, _P, _P, _L, _I, _I, _P, _L],
+    "jg_debug_attention": [_P, _P, _P, _I, _I, _I, _I, _P],
+    "jg_debug_attention_gather": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "jg_debug_attention32": [_P, _P, _P, _I, _I, _I, _I, _P],
+    "jg_debug_last_kernel": [_P, ctypes.c_char_p, _I],
     "jg_debug_conv_rows": [_P, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)],
     "jg_jegal_gestures": [_P, _P, _P, _I, _I, _I, _P],
     "jg_jegal_audio": [_P, _P, _I, _I, _P],
@@ -98,7 +116,9 @@ def load_library():
 
 
 class JegalError(RuntimeError):
-    pass
+    def __init__(self, msg, code=None):
+        super().__init__(msg)
+        self.code = code
 
 
 def _ptr(t):
@@ -146,7 +166,7 @@ class Engine:
 
     def _ck(self, rc):
         if rc != 0:
-            raise JegalError(f"libjegal_hip error {rc}: {self.lib.jg_last_error(self.h).decode()}")
+            raise JegalError(f"libjegal_hip error {rc}: {self.lib.jg_last_error(self.h).decode()}", rc)
 
     def _bind_stream(self):
         self._ck(self.lib.jg_set_stream(self.h, _P(torch.cuda.current_stream(self.device).cuda_stream)))
@@ -263,6 +283,47 @@ class Engine:
                 raise ValueError(f"debug_gemm operand must be a contiguous fp16 {shp} tensor on {self.device}")
         self._ck(self.lib.jg_debug_gemm_ex(self.h, _ptr(a16), _ptr(w16), M, N, K, mode, iters, ctypes.byref(ms)))
         return ms.value
+
+    # ---- kernel check points (include/jegal_hip.h): one production launch on caller-owned device tensors, asynchronous on the
+    # engine's stream; a shape the launcher rejects raises JegalError with .code == JG_ERR_ARG.  debug_last_kernel() names the instance.
+    def debug_gemm_check(self, **kw):
+        """Linear GEMM (launch_gemm): keyword arguments are the fields of jg_gemm_check; tensors are passed by pointer."""
+        self._bind_stream()
+        c = GemmCheck()
+        for k, v in kw.items():
+            if isinstance(v, torch.Tensor):
+                if v.device != self.device:
+                    raise ValueError(f"debug_gemm_check: {k} must be on {self.device}")
+                v = v.data_ptr()
+            setattr(c, k, v)
+        self._ck(self.lib.jg_debug_gemm_check(self.h, ctypes.byref(c)))
+
+    def debug_gemm32(self, A, lda, W, ldw, M, N, K, out, ldc, scale=None, bias=None, res=None, ldr=0, res_mod=0, act=0):
+        self._bind_stream()
+        self._ck(self.lib.jg_debug_gemm32(self.h, _ptr(A), lda, _ptr(W), ldw, M, N, K, _ptr(scale), _ptr(bias), _ptr(res), ldr, res_mod, act,
+                                          _ptr(out), ldc))
+
+    def debug_gemm_x3(self, A, lda, Wh, Wl, ldw, M, N, K, out, ldc, bias=None, res=None, ldr=0, res_mod=0, relu=0):
+        self._bind_stream()
+        self._ck(self.lib.jg_debug_gemm_x3(self.h, _ptr(A), lda, _ptr(Wh), _ptr(Wl), ldw, M, N, K, _ptr(bias), _ptr(res), ldr, res_mod, relu,
+                                           _ptr(out), ldc))
+
+    def debug_attention(self, qkv, keymask, B, S, H, dk, out):
+        self._bind_stream()
+        self._ck(self.lib.jg_debug_attention(self.h, _ptr(qkv), _ptr(keymask), B, S, H, dk, _ptr(out)))
+
+    def debug_attention_gather(self, qkv_pos, pe_qkv, Twin, P, shift, B, S, H, out):
+        self._bind_stream()
+        self._ck(self.lib.jg_debug_attention_gather(self.h, _ptr(qkv_pos), _ptr(pe_qkv), Twin, P, shift, B, S, H, _ptr(out)))
+
+    def debug_attention32(self, qkv, keymask, B, S, H, dk, out):
+        self._bind_stream()
+        self._ck(self.lib.jg_debug_attention32(self.h, _ptr(qkv), _ptr(keymask), B, S, H, dk, _ptr(out)))
+
+    def debug_last_kernel(self):
+        buf = ctypes.create_string_buffer(128)
+        self._ck(self.lib.jg_debug_last_kernel(self.h, buf, 128))
+        return buf.value.decode()
 
     def debug_conv2_rowskip(self):
         """Leading conv2 output rows per image that the last conv stack copied instead of computing ("conv2_row_skip")."""

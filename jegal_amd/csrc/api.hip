@@ -169,6 +169,7 @@ struct jg_handle {
     std::vector<void*>* wallocs = &wallocs_gs;   // list the model being finalized allocates into
     int cur_model = 1;
     EngineOpts opts;               // per-handle tuning switches + per-device resources (common.h)
+    char kname[KNAME_LEN] = {0};   // instance the last kernel check point launched (jg_debug_last_kernel)
     Arena ws;
     bool prof = false;
     int prof_only = -1;            // >= 0: only this stage is bracketed with events (jg_profile_enable(h, 2 + stage))
@@ -2388,6 +2389,111 @@ int jg_debug_gemm_ex(jg_handle* h, const void* a16, const void* w16, int M, int 
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
     *ms = t / iters;
+    return JG_OK;
+}
+
+// ---- kernel check points: one launch of a production launcher on the caller's operands, with the handle's options (which pick
+// the instance exactly as in production) and the handle's build (fp16 or bf16).  The launcher's own shape rules decide what is
+// valid: its hipErrorInvalidValue comes back as JG_ERR_ARG, and nothing was launched then.
+// (They live here rather than in a translation unit of their own because they need the handle's internals -- options, stream, build
+// switch, error slot -- and the LAUNCH dispatch between the fp16 and bf16 builds, all private to this file.)
+namespace {
+// options of the handle + the name slot the launchers write
+void check_opts(jg_handle* h, EngineOpts& o) {
+    o = h->opts;
+    o.kname = h->kname;
+}
+int check_result(jg_handle* h, hipError_t e, const char* what) {
+    if (e == hipErrorInvalidValue) JG_FAIL(h, JG_ERR_ARG, "%s: the launcher rejects this shape / argument set", what);
+    if (e != hipSuccess) JG_FAIL(h, JG_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
+    return JG_OK;
+}
+}  // namespace
+
+int jg_debug_gemm_check(jg_handle* h, const jg_gemm_check* c) {
+    ENTER(h);
+    h->kname[0] = 0;
+    if (!c || !c->A || !c->Wh || c->M <= 0 || c->N <= 0 || c->K <= 0 || c->lda < c->K || c->ldw < c->K || (!c->out32 && !c->out16) ||
+        ((c->out32 || (c->out16 && !c->ln_w)) && c->ldc < c->N) || (c->res && (c->ldr < c->N || c->res_mod < 0)) ||
+        (c->bias_clip && (c->rpc <= 0 || c->nclips <= 0)) || c->relu < 0 || c->relu > 2 || c->ln_mode < 0 || c->ln_mode > 2)
+        JG_FAIL(h, JG_ERR_ARG, "jg_debug_gemm_check: bad arguments");
+    GemmArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.A = static_cast<const f16*>(c->A); a.lda = c->lda;
+    a.Wh = static_cast<const f16*>(c->Wh); a.Wl = static_cast<const f16*>(c->Wl); a.ldw = c->ldw;
+    a.M = c->M; a.N = c->N; a.K = c->K;
+    a.scale = c->scale; a.bias = c->bias;
+    a.bias_clip = c->bias_clip; a.rpc = c->rpc; a.nclips = c->nclips;
+    a.res = c->res; a.ldr = c->ldr; a.res_mod = c->res_mod; a.relu = c->relu;
+    a.out32 = c->out32; a.out16 = static_cast<f16*>(c->out16); a.ldc = c->ldc;
+    a.ln_w = c->ln_w; a.ln_b = c->ln_b; a.ln_flavour = LN_STD;
+    a.res16 = static_cast<const f16*>(c->res16); a.res8 = static_cast<const signed char*>(c->res8); a.out8 = static_cast<signed char*>(c->out8);
+    a.ln_mode = c->ln_mode; a.ln_stats = c->ln_stats;
+    a.xres_hi = static_cast<const f16*>(c->xres_hi); a.xres_lo = static_cast<const f16*>(c->xres_lo);
+    a.out_lo = static_cast<f16*>(c->out_lo); a.stat_out = c->stat_out;
+    EngineOpts o;
+    check_opts(h, o);
+    return check_result(h, LAUNCH(h, launch_gemm, a, false, o, h->stream), "launch_gemm");
+}
+
+int jg_debug_gemm32(jg_handle* h, const float* A, int64_t lda, const float* W, int64_t ldw, int M, int N, int K, const float* scale,
+                    const float* bias, const float* res, int64_t ldr, int res_mod, int act, float* out, int64_t ldc) {
+    ENTER(h);
+    h->kname[0] = 0;
+    if (!A || !W || !out || M <= 0 || N <= 0 || K <= 0 || lda < K || ldw < K || ldc < N || (res && (ldr < N || res_mod < 0)) || act < 0 || act > 2)
+        JG_FAIL(h, JG_ERR_ARG, "jg_debug_gemm32: bad arguments");
+    Gemm32Args a;
+    std::memset(&a, 0, sizeof(a));
+    a.A = A; a.lda = lda; a.W = W; a.ldw = ldw; a.M = M; a.N = N; a.K = K;
+    a.scale = scale; a.bias = bias; a.res = res; a.ldr = ldr; a.res_mod = res_mod; a.out = out; a.ldc = ldc; a.act = act;
+    return check_result(h, launch_gemm32(a, h->stream, h->kname), "launch_gemm32");
+}
+
+int jg_debug_gemm_x3(jg_handle* h, const float* A, int64_t lda, const void* Wh, const void* Wl, int64_t ldw, int M, int N, int K,
+                     const float* bias, const float* res, int64_t ldr, int res_mod, int relu, float* out, int64_t ldc) {
+    ENTER(h);
+    h->kname[0] = 0;
+    if (!A || !Wh || !Wl || !out || M <= 0 || N <= 0 || K <= 0 || lda < K || ldw < K || ldc < N || (res && (ldr < N || res_mod < 0)) ||
+        relu < 0 || relu > 1)
+        JG_FAIL(h, JG_ERR_ARG, "jg_debug_gemm_x3: bad arguments");
+    GemmX3Args a;
+    std::memset(&a, 0, sizeof(a));
+    a.A = A; a.lda = lda; a.Wh = static_cast<const f16*>(Wh); a.Wl = static_cast<const f16*>(Wl); a.ldw = ldw; a.M = M; a.N = N; a.K = K;
+    a.bias = bias; a.res = res; a.ldr = ldr; a.res_mod = res_mod; a.out = out; a.ldc = ldc; a.relu = relu;
+    return check_result(h, launch_gemm_x3(a, h->stream, h->kname), "launch_gemm_x3");
+}
+
+int jg_debug_attention(jg_handle* h, const void* qkv, const float* keymask, int B, int S, int H, int dk, void* out) {
+    ENTER(h);
+    h->kname[0] = 0;
+    if (!qkv || !out || B <= 0 || S <= 0 || H <= 0 || (dk != 64 && dk != 96)) JG_FAIL(h, JG_ERR_ARG, "jg_debug_attention: bad arguments");
+    EngineOpts o;
+    check_opts(h, o);
+    return check_result(h, LAUNCH(h, launch_attention, static_cast<const f16*>(qkv), keymask, B, S, H, dk, static_cast<f16*>(out), o, h->stream),
+                        "launch_attention");
+}
+
+int jg_debug_attention_gather(jg_handle* h, const void* qkv_pos, const void* pe_qkv, int Twin, int P, int shift, int B, int S, int H, void* out) {
+    ENTER(h);
+    h->kname[0] = 0;
+    if (!qkv_pos || !pe_qkv || !out || B <= 0 || S <= 0 || H <= 0 || Twin <= 0 || P <= 0 || B % Twin)
+        JG_FAIL(h, JG_ERR_ARG, "jg_debug_attention_gather: bad arguments (B must be a multiple of Twin)");
+    if (h->bf16) JG_FAIL(h, JG_ERR_STATE, "jg_debug_attention_gather: the gather form is an fp16-build kernel (the clip path's layer 0)");
+    const AttnGather g{static_cast<const f16*>(pe_qkv), Twin, P, shift};
+    return check_result(h, launch_attention_gather(static_cast<const f16*>(qkv_pos), g, B, S, H, static_cast<f16*>(out), h->stream, h->kname),
+                        "launch_attention_gather");
+}
+
+int jg_debug_attention32(jg_handle* h, const float* qkv, const float* keymask, int B, int S, int H, int dk, float* out) {
+    ENTER(h);
+    h->kname[0] = 0;
+    if (!qkv || !out || B <= 0 || S <= 0 || H <= 0) JG_FAIL(h, JG_ERR_ARG, "jg_debug_attention32: bad arguments");
+    return check_result(h, launch_attention32(qkv, keymask, B, S, H, dk, out, h->stream, h->kname), "launch_attention32");
+}
+
+int jg_debug_last_kernel(jg_handle* h, char* buf, int len) {
+    if (!h || !buf || len <= 0) return JG_ERR_ARG;
+    snprintf(buf, (size_t)len, "%s", h->kname);
     return JG_OK;
 }
 

@@ -645,11 +645,12 @@ static hipError_t launch_attn_mfma(const f16* qkv, const float* keymask, long np
 
 // Layer-0 attention of the GestSync transformer from per-position projections (see attn_mfma_s32_kernel<true>):
 // B = windows (nclip * g.Twin), S <= 32 tokens, dk = 64.
-hipError_t launch_attention_gather(const f16* qkv_pos, const AttnGather& g, int B, int S, int H, f16* out, hipStream_t s) {
+hipError_t launch_attention_gather(const f16* qkv_pos, const AttnGather& g, int B, int S, int H, f16* out, hipStream_t s, char* kname) {
     if (B <= 0 || S <= 0) return hipSuccess;
     const long npairs = (long)B * H;
     if (S > 32 || npairs >= (1L << 31) || g.Twin <= 0 || g.P <= 0 || !g.pe_qkv) return hipErrorInvalidValue;
     const unsigned blocks = (unsigned)((npairs + 3) / 4);
+    record_kernel(kname, "attn_mfma_s32_kernel<1,%d>", S <= 24 ? 24 : 32);
     if (S <= 24) hipLaunchKernelGGL((attn_mfma_s32_kernel<true, 24>), dim3((blocks + 7) / 8 * 8), dim3(256), 0, s, qkv_pos, (int)npairs, S, H, out, g);
     else hipLaunchKernelGGL((attn_mfma_s32_kernel<true, 32>), dim3((blocks + 7) / 8 * 8), dim3(256), 0, s, qkv_pos, (int)npairs, S, H, out, g);
     return hipGetLastError();
@@ -659,11 +660,13 @@ hipError_t launch_attention(const f16* qkv, const float* keymask, int B, int S, 
     if (B <= 0 || S <= 0) return hipSuccess;
     const long npairs = (long)B * H;
     if (o.attn_mfma && S <= 32 && dk == 64 && !keymask && npairs < (1L << 31)) {
+        record_kernel(o.kname, "attn_mfma_s32_kernel<0,%d>", S <= 24 ? 24 : 32);
         if (S <= 24) hipLaunchKernelGGL((attn_mfma_s32_kernel<false, 24>), dim3((unsigned)((npairs + 3) / 4)), dim3(256), 0, s, qkv, (int)npairs, S, H, out, AttnGather{});
         else hipLaunchKernelGGL((attn_mfma_s32_kernel<false, 32>), dim3((unsigned)((npairs + 3) / 4)), dim3(256), 0, s, qkv, (int)npairs, S, H, out, AttnGather{});
         return hipGetLastError();
     }
     if (o.attn_mfma && S <= 160 && dk == 64 && npairs < (1L << 31)) {      // S <= 32 with a key mask: one query block
+        record_kernel(o.kname, "attn_mfma_kernel<%d>", (S + 31) / 32 < 5 ? (S + 31) / 32 : 5);
         switch ((S + 31) / 32) {
             case 1: return launch_attn_mfma<1>(qkv, keymask, npairs, S, H, out, s);
             case 2: return launch_attn_mfma<2>(qkv, keymask, npairs, S, H, out, s);
@@ -673,7 +676,8 @@ hipError_t launch_attention(const f16* qkv, const float* keymask, int B, int S, 
         }
     }
     // everything else on the matrix cores too: dk = 64 beyond 160 keys, dk = 96 (text encoder) at any length
-    if (o.attn_mfma && npairs < (1L << 31)) {
+    if (o.attn_mfma && npairs < (1L << 31) && (dk == 64 || dk == 96)) {
+        record_kernel(o.kname, "attn_mfma_flash_kernel<%d>", dk);
         if (dk == 64) return launch_attn_flash<64>(qkv, keymask, npairs, S, H, out, s);
         if (dk == 96) return launch_attn_flash<96>(qkv, keymask, npairs, S, H, out, s);
     }
@@ -688,6 +692,7 @@ hipError_t launch_attention(const f16* qkv, const float* keymask, int B, int S, 
         grid = dim3((unsigned)npairs, (S + 255) / 256);
         block = dim3(256);
     }
+    if (dk == 64 || dk == 96) record_kernel(o.kname, "attn_kernel<%d>", dk);
     if (dk == 64) hipLaunchKernelGGL(attn_kernel<64>, grid, block, 0, s, qkv, keymask, B, S, H, G, out);
     else if (dk == 96) hipLaunchKernelGGL(attn_kernel<96>, grid, block, 0, s, qkv, keymask, B, S, H, G, out);
     else return hipErrorInvalidValue;

@@ -428,34 +428,39 @@ inline int grid_for(long total) { return (int)((total + 255) / 256 < 65536 * 4 ?
 }  // namespace
 
 template <int BT>
-static hipError_t launch_gemm32_bt(const Gemm32Args& a, hipStream_t s) {
+static hipError_t launch_gemm32_bt(const Gemm32Args& a, hipStream_t s, char* kname) {
     const long mt = (a.M + BT - 1) / BT, nt = (a.N + BT - 1) / BT;
     const dim3 grid((unsigned)(mt * nt)), block(256);
     const bool walign = (a.ldw & 3) == 0 && ((uintptr_t)a.W & 15) == 0 && ((uintptr_t)a.A & 15) == 0;
     if (a.conv) {
         if ((1 << a.g.cshift) != a.g.C || a.g.rowmap || a.g.const_in) return hipErrorInvalidValue;
-        if (walign && (a.g.C & 3) == 0) hipLaunchKernelGGL((gemm32_kernel<true, true, BT>), grid, block, 0, s, a);
+        const bool v4 = walign && (a.g.C & 3) == 0;
+        record_kernel(kname, "gemm32_kernel<1,%d,%d>", (int)v4, BT);
+        if (v4) hipLaunchKernelGGL((gemm32_kernel<true, true, BT>), grid, block, 0, s, a);
         else hipLaunchKernelGGL((gemm32_kernel<true, false, BT>), grid, block, 0, s, a);
     } else {
-        if (walign && (a.lda & 3) == 0 && (a.K & 3) == 0) hipLaunchKernelGGL((gemm32_kernel<false, true, BT>), grid, block, 0, s, a);
+        const bool v4 = walign && (a.lda & 3) == 0 && (a.K & 3) == 0;
+        record_kernel(kname, "gemm32_kernel<0,%d,%d>", (int)v4, BT);
+        if (v4) hipLaunchKernelGGL((gemm32_kernel<false, true, BT>), grid, block, 0, s, a);
         else hipLaunchKernelGGL((gemm32_kernel<false, false, BT>), grid, block, 0, s, a);
     }
     return hipGetLastError();
 }
 
-hipError_t launch_gemm32(const Gemm32Args& a, hipStream_t s) {
+hipError_t launch_gemm32(const Gemm32Args& a, hipStream_t s, char* kname) {
     if (a.M <= 0 || a.N <= 0) return hipSuccess;
     if (a.K <= 0 || !a.A || !a.W || !a.out) return hipErrorInvalidValue;
     // fewer than ~1.5 rounds of 128 x 128 tiles on 256 CUs: 64 x 64 tiles (the small-M launches of the JEGAL branch)
     const long tiles128 = (long)((a.M + 127) / 128) * ((a.N + 127) / 128);
-    if (tiles128 < 384) return launch_gemm32_bt<64>(a, s);
-    return launch_gemm32_bt<128>(a, s);
+    if (tiles128 < 384) return launch_gemm32_bt<64>(a, s, kname);
+    return launch_gemm32_bt<128>(a, s, kname);
 }
 
-hipError_t launch_attention32(const float* qkv, const float* keymask, int B, int S, int H, int dk, float* out, hipStream_t s) {
+hipError_t launch_attention32(const float* qkv, const float* keymask, int B, int S, int H, int dk, float* out, hipStream_t s, char* kname) {
     if (B <= 0 || S <= 0) return hipSuccess;
     const int threads = S >= 256 ? 256 : (S + 63) / 64 * 64;
     const dim3 grid((unsigned)(B * H), (unsigned)((S + threads - 1) / threads));
+    if (dk == 64 || dk == 96) record_kernel(kname, "attention32_kernel<%d>", dk);
     if (dk == 64) hipLaunchKernelGGL(attention32_kernel<64>, grid, dim3(threads), 0, s, qkv, keymask, S, H, out);
     else if (dk == 96) hipLaunchKernelGGL(attention32_kernel<96>, grid, dim3(threads), 0, s, qkv, keymask, S, H, out);
     else return hipErrorInvalidValue;
@@ -497,12 +502,13 @@ hipError_t launch_zero_tail32(float* x, const int* valid, int halvings, int B, i
     return hipGetLastError();
 }
 
-hipError_t launch_gemm_x3(const GemmX3Args& a, hipStream_t s) {
+hipError_t launch_gemm_x3(const GemmX3Args& a, hipStream_t s, char* kname) {
     if (a.M <= 0) return hipSuccess;
     if (!a.A || !a.Wh || !a.Wl || !a.out || a.K <= 0 || a.K % 256 || a.N <= 0 || a.N % 128 || (a.lda & 3) || (a.ldw & 7) || (a.ldc & 3) || (a.res && (a.ldr & 3)) ||
         ((uintptr_t)a.A & 15))
         return hipErrorInvalidValue;
     const long tiles = (long)((a.M + 31) / 32) * (a.N / 128);
+    record_kernel(kname, "%s", "gemm_x3_kernel");
     hipLaunchKernelGGL(gemm_x3_kernel, dim3((unsigned)tiles), dim3(256), 0, s, a);
     return hipGetLastError();
 }

@@ -6,6 +6,7 @@
 // included) sits in namespace bf.  api.hip includes this header twice and dispatches per handle (LAUNCH in api.hip).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <cstdio>
 
 #if (defined(JG_BF16) && !defined(JG_COMMON_BF16_INCLUDED)) || (!defined(JG_BF16) && !defined(JG_COMMON_FP16_INCLUDED))
 #undef JG_NS_BEGIN
@@ -202,7 +203,15 @@ struct EngineOpts {
     bool attn_mfma = true;
     bool conv1_zero_skip = true;
     bool conv1_mfma16 = true;            // conv1_direct_kernel's MFMA waves on 16x16x32 MFMAs (false: 32x32x16, the round-1/2 form)
+    char* kname = nullptr;               // kernel check points (jg_debug_last_kernel): the launchers write the name of the instance they
+                                         // launch here, with its template arguments (KNAME_LEN bytes; nullptr: not recorded)
 };
+constexpr int KNAME_LEN = 96;
+// printf-style into kname (if any): host side of a launcher
+template <class... T>
+inline void record_kernel(char* kname, const char* fmt, T... v) {
+    if (kname) snprintf(kname, KNAME_LEN, fmt, v...);
+}
 hipError_t engine_opts_init(EngineOpts& o, int device);      // queries the CU count, allocates the zero page (current device = `device`)
 void engine_opts_release(EngineOpts& o);
 void engine_opts_set_timeline(EngineOpts& o, bool on);
@@ -246,7 +255,7 @@ struct AttnGather {
     const f16* pe_qkv;    // [S][3D]: W_qkv pe[j] + b
     int Twin, P, shift;   // windows per clip, conv positions per clip, window_gather's shift
 };
-hipError_t launch_attention_gather(const f16* qkv_pos, const AttnGather& g, int B, int S, int H, f16* out, hipStream_t s);
+hipError_t launch_attention_gather(const f16* qkv_pos, const AttnGather& g, int B, int S, int H, f16* out, hipStream_t s, char* kname = nullptr);
 // pe_qkv[j][n] = sum_k W[n][k] pe[j][k] + bias[n]  (W = Wh (+ Wl), [N][K] fp16; pe [S][K] fp32): 21 x 1536 outputs
 hipError_t launch_pe_project(const float* pe, int S, const f16* Wh, const f16* Wl, const float* bias, int N, int K, f16* out, hipStream_t s);
 hipError_t launch_group_mean(const f16* in, int groups, int L, int D, f16* out, hipStream_t s);

@@ -1149,6 +1149,7 @@ static hipError_t launch_glds_cfg(const GemmArgs& a, const EngineOpts& o, hipStr
     const int last_round = tiles % o.num_cu;
     const int stagger = o.gemm_stagger < 0 ? 0 : o.gemm_stagger > 0 ? o.gemm_stagger
                         : (!CONV && !o.lanes_active && tiles > o.num_cu && 2 * last_round < o.num_cu ? 300 : 0);
+    record_kernel(o.kname, "gemm_glds_kernel<%d,%d,%d,%d,%d,0,%d,%d,%d>", (int)W2, (int)CONV, MI, WM, WN, (int)SPR, XE, (int)C32);
     hipLaunchKernelGGL((gemm_glds_kernel<W2, CONV, MI, WM, WN, false, SPR, XE, C32>), dim3((unsigned)grid), dim3(512), lds, s, a, nt, tiles, o.zeros,
                        o.gemm_counted | (stagger << 8), o.gemm_tl);
     if (o.gemm_tl) dump_timeline(o, s, CONV ? "conv" : "linear");
@@ -1176,6 +1177,7 @@ static hipError_t launch_glds_ln(const GemmArgs& a, const EngineOpts& o, hipStre
     const int last_round = tiles % o.num_cu;
     const int auto_stagger = tiles > o.num_cu && 2 * last_round < o.num_cu ? (a.K <= 1024 ? 500 : 1400) : 0;
     const int stagger = o.gemm_stagger < 0 ? 0 : o.gemm_stagger > 0 ? o.gemm_stagger : auto_stagger;
+    record_kernel(o.kname, "gemm_glds_kernel<0,%d,8,1,8,1,0,0,0>", (int)CONV);
     hipLaunchKernelGGL((gemm_glds_kernel<false, CONV, 8, 1, 8, true>), dim3((unsigned)grid), dim3(512), lds, s, a, 1, tiles, o.zeros,
                        o.gemm_counted | (stagger << 8), o.gemm_tl);
     if (o.gemm_tl) dump_timeline(o, s, "linear+LN");
@@ -1263,8 +1265,9 @@ static hipError_t launch_glds(const GemmArgs& a, const EngineOpts& o, hipStream_
 }
 
 template <int WM, int WN, bool CONV, bool W2>
-static hipError_t launch_variant(const GemmArgs& a, hipStream_t s) {
+static hipError_t launch_variant(const GemmArgs& a, const EngineOpts& o, hipStream_t s) {
     constexpr int BM = 64 * WM, BN = 64 * WN;
+    record_kernel(o.kname, "gemm_kernel<%d,%d,%d,%d>", WM, WN, (int)CONV, (int)W2);
     const long mt = (a.M + BM - 1) / BM, nt = (a.N + BN - 1) / BN;
     const size_t lds = (size_t)(BM + BN * (W2 ? 2 : 1)) * 128;
     hipLaunchKernelGGL((gemm_kernel<WM, WN, CONV, W2>), dim3((unsigned)(mt * nt)), dim3(256), lds, s, a);
@@ -1304,15 +1307,23 @@ hipError_t launch_gemm(const GemmArgs& a, bool conv, const EngineOpts& o, hipStr
         if (o.gemm_glds && !w2 && a.N == 64 && a.g.C == 32 && a.K % 32 == 0 && a.K == a.g.KH * a.g.KW * 32 && !a.g.tap_table && !a.g.rowmap && a.M >= 256 &&
             coords_ok && a.out16 && !a.out32 && (a.ldc & 7) == 0 && (a.ldw & 7) == 0)
             return launch_glds_cfg<false, true, 2, 8, 1, false, 0, true>(a, o, s);
-        if (narrow) return w2 ? launch_variant<4, 1, true, true>(a, s) : launch_variant<4, 1, true, false>(a, s);
+        if (narrow) return w2 ? launch_variant<4, 1, true, true>(a, o, s) : launch_variant<4, 1, true, false>(a, o, s);
         if (o.gemm_glds && a.M >= 256 && a.g.C % 64 == 0 && a.N % 128 == 0 && coords_ok) return w2 ? launch_glds<true, true>(a, o, s) : launch_glds<false, true>(a, o, s);
         if (a.g.rowmap) return hipErrorInvalidValue;          // only the LDS-DMA kernel knows the compaction
-        return w2 ? launch_variant<2, 2, true, true>(a, s) : launch_variant<2, 2, true, false>(a, s);
+        return w2 ? launch_variant<2, 2, true, true>(a, o, s) : launch_variant<2, 2, true, false>(a, o, s);
     }
-    if (narrow) return w2 ? launch_variant<4, 1, false, true>(a, s) : launch_variant<4, 1, false, false>(a, s);
+    // every epilogue stores 4 columns per lane (16 / 8 bytes) and reads the residual the same way; the register-staged kernel below
+    // also loads A and W in 8-element (16-byte) pieces and only masks whole pieces against K: anything else would read columns >= K
+    if (a.N % 4 || a.ldc % 4 || (a.res && a.ldr % 4)) return hipErrorInvalidValue;
+    const bool staged_ok = a.K % 8 == 0 && a.lda % 8 == 0 && a.ldw % 8 == 0;
+    if (narrow) {
+        if (!staged_ok) return hipErrorInvalidValue;
+        return w2 ? launch_variant<4, 1, false, true>(a, o, s) : launch_variant<4, 1, false, false>(a, o, s);
+    }
     if (o.gemm_glds && a.K % 64 == 0 && a.M >= 128 && a.lda % 8 == 0 && a.ldw % 8 == 0 && a.N % 128 == 0)
         return w2 ? launch_glds<true, false>(a, o, s) : launch_glds<false, false>(a, o, s);
-    return w2 ? launch_variant<2, 2, false, true>(a, s) : launch_variant<2, 2, false, false>(a, s);
+    if (!staged_ok) return hipErrorInvalidValue;
+    return w2 ? launch_variant<2, 2, false, true>(a, o, s) : launch_variant<2, 2, false, false>(a, o, s);
 }
 
 JG_NS_END
