@@ -82,8 +82,6 @@ int jg_set_chunk(jg_handle* h, int clips_per_chunk);
  *                     positional rows (linearity of W(conv + pe) + b); the attention kernel gathers and sums the rows
  *   "edge_dedup"      1: evaluate only the T+4 distinct padded-clip positions
  *   "fuse_ln"         1: residual + LayerNorm fused into the GestSync projection GEMMs (tiled token stream)
- *   "stream_fp16"     1: that token stream is the fp16 plane alone (post-norm: the LayerNorm output is rounded to fp16 as the next GEMM's
- *                     operand anyway; -1.5 % per step); 0: fp16 + one e4m3 byte of correction per element (rounds 2-4)
  *   "attn_mfma"       1: MFMA attention kernels for S <= 160, dk = 64
  *   "gemm_glds", "gemm_big_tile", "gemm_small_tile", "gemm_tall_tile", "gemm_persistent", "gemm_counted",
  *   "gemm_stagger":   tile / pipeline choices of the LDS-DMA GEMM (tests/test_gpu_options_scale_multirank.py flips every one of them)
@@ -99,12 +97,10 @@ int jg_set_chunk(jg_handle* h, int clips_per_chunk);
  *                     streams).  High-priority lanes only compete with the application's own high-priority streams.  (A host-streaming pipeline around the engine -- GestureStreamer's
  *                     H2D / D2H / compute streams -- in a process that owns further streams is the one measured case where 0 was faster:
  *                     tools/experiments/stream_queue_sweep.sh)
- *   "gesture_lanes"   0 (default): two lanes ("dual_split"); 3 / 4: that many EQUAL lanes (experiment: slower, tools/experiments/README.md)
  *   "xlmr_lanes"      2 (default), 1 .. 4: jg_xlmr_encode runs a batch as that many equal parts on as many streams (the first two are the
  *                     lane streams of "dual_stream" / "lane_priority")
  *   "ws_poison"       1 (test aid, default 0): the workspace is filled with 0xff bytes (fp16/fp32 NaN) before every clip chunk, so a
  *                     kernel that reads a row nobody wrote (the row / band skips leave rows unwritten on purpose) shows up as NaN
- *   "gemm_timeline"   1: print a per-tile phase timeline of every GEMM launch to stderr (debug)
  *   "jegal_fp32_ends" 1 (default): the two ends of the JEGAL gesture branch (proj_ip_rgb; final norm + proj_op_rgb + proj_op_align_gesture) and
  *                     of the content path (proj_op_text, fusion / align MLPs) keep fp32 activations and run on the split-operand GEMM
  *                     (three fp16 MFMAs per tile: fp32-grade products); 0: the round-5 arithmetic (fp16 activations, hi+lo weights).  DESIGN.md section 3.
@@ -112,12 +108,8 @@ int jg_set_chunk(jg_handle* h, int clips_per_chunk);
  *                     subnormal with an absolute quantum of 2^-24.  At these call sites the activations have row rms 0.69 .. ~9 and |a| <= 42 over
  *                     the six synthetic weight families (tools/x3_operand_range.py, profiles/x3_operand_range.json); tests/test_gpu_kernels_fp64.py
  *                     holds the kernel to the fp32 bound for operand row rms 2^-6 / sqrt 3 .. 2^10 / sqrt 3
- *   "jegal_ffn_x3"    0 (default) / 1: the six feed-forward sub-layers of the JEGAL gesture branch on the split-operand GEMM as well (gesture error
- *                     3.5e-4 -> 2.5e-4 on the Gaussian draw for +3 % step time)
  *   "conv_round_diffuse" 1 (default; before jg_finalize_weights): conv weights are rounded to fp16 with error diffusion across the taps of each
  *                     (output channel, input slot) pair instead of round-to-nearest per weight (the pixel-independent part of the rounding error vanishes)
- *   "rc_layers"       measurement only: mask of the GestSync Linear types that get JG_PREC_FP16_RC's run-time correction (1 qkv, 2 out_proj,
- *                     4 linear1 / ff_vid.0, 8 linear2; default 15); the others run single fp16 WITHOUT a correction
  *   "audit_jegal_parts" measurement only (needs audit_weights): parts of the fp16 JEGAL gesture branch on the fp32 kernels (1 input projection,
  *                     2 attention sub-layers, 4 feed-forward sub-layers, 8 final norm + output projections)
  *   "audit_weights"   1 (before jg_finalize_weights): the fp32 matrices are kept next to the packed fp16 ones (always in JG_PREC_FP32)
@@ -180,14 +172,14 @@ int jg_gestsync_clip_ragged(jg_handle* h, const void* frames, int frames_dtype, 
  * pad = temporal edge padding (12 for clips, 0 for a raw 25-frame window) -> out (B*(T+2*pad-4),43,78,64) fp16 NHWC. */
 int jg_debug_conv1_pool(jg_handle* h, const void* frames_u8, int B, int T, int pad, void* out_f16);
 /* Kernel check points (tests/test_gpu_kernels_fp64.py): each runs exactly ONE launch of a production launcher on caller operands.  The
- * handle's options (gemm_tile, gemm_small_tile, gemm_big_tile, gemm_persistent, num_cu, gemm_counted, gemm_stagger, gemm_glds, attn_mfma,
- * stream_fp16 via the operands passed) pick the kernel instance exactly as in production, and the handle's precision picks the build: under
+ * handle's options (gemm_tile, gemm_small_tile, gemm_big_tile, gemm_persistent, num_cu, gemm_counted, gemm_stagger, gemm_glds, attn_mfma)
+ * pick the kernel instance exactly as in production, and the handle's precision picks the build: under
  * JG_PREC_BF16 every 16-bit operand and output is bf16, otherwise fp16.  All pointers are device buffers the caller owns, leading
  * dimensions are in elements.  A shape or argument set the launcher rejects returns JG_ERR_ARG and launches nothing.  Asynchronous.
  * Linear GEMM (launch_gemm, GemmArgs in jegal_amd/csrc/common.h):
  *   out[m][n] = act( sum_k A[m][k] (Wh[n][k] + Wl[n][k]) * scale[n] + bias[n] + res[m % res_mod][n] ),  act: relu 0 none / 1 ReLU / 2 GELU;
  *   bias_clip [nclips][N]: row m takes bias_clip[min(m / rpc, nclips - 1)] instead of bias (fp16 out16 alone);
- *   ln_w != NULL: residual + LayerNorm fused (N = 512, M >= 1024): out16 (+ out8) = LN(acc + bias + res16 (+ res8)) in the tiled token order;
+ *   ln_w != NULL: residual + LayerNorm fused (N = 512, M >= 1024): out16 = LN(acc + bias + res16) in the tiled token order;
  *   ln_mode 1 / 2: the implicit-LayerNorm consumer / producer epilogues (ln_stats, xres_hi / xres_lo, out_lo, stat_out as in GemmArgs). */
 typedef struct jg_gemm_check {
     const void* A; int64_t lda;                   /* [M][lda] 16-bit */
@@ -198,7 +190,7 @@ typedef struct jg_gemm_check {
     const float* res; int64_t ldr; int res_mod;   /* fp32 residual, row m % res_mod (0: m) */
     int relu;
     float* out32; void* out16; int64_t ldc;       /* either or both */
-    const float* ln_w; const float* ln_b; const void* res16; const void* res8; void* out8;
+    const float* ln_w; const float* ln_b; const void* res16;
     int ln_mode; const float* ln_stats; const void* xres_hi; const void* xres_lo; void* out_lo; float* stat_out;
 } jg_gemm_check;
 int jg_debug_gemm_check(jg_handle* h, const jg_gemm_check* c);

@@ -29,7 +29,7 @@ class GemmCheck(ctypes.Structure):
     _fields_ = [("A", _P), ("lda", _L), ("Wh", _P), ("Wl", _P), ("ldw", _L), ("M", _I), ("N", _I), ("K", _I),
                 ("scale", _P), ("bias", _P), ("bias_clip", _P), ("rpc", _I), ("nclips", _I),
                 ("res", _P), ("ldr", _L), ("res_mod", _I), ("relu", _I), ("out32", _P), ("out16", _P), ("ldc", _L),
-                ("ln_w", _P), ("ln_b", _P), ("res16", _P), ("res8", _P), ("out8", _P),
+                ("ln_w", _P), ("ln_b", _P), ("res16", _P),
                 ("ln_mode", _I), ("ln_stats", _P), ("xres_hi", _P), ("xres_lo", _P), ("out_lo", _P), ("stat_out", _P)]
 _SIGS = {
     "jg_create": [_I, ctypes.POINTER(_P)],

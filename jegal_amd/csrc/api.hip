@@ -59,7 +59,6 @@ struct Lin {            // packed Linear / folded conv:  [N][K] fp16 hi (+lo), f
     // run-time corrected mode (JG_PREC_FP16_RC; GestSync transformer Linears): single fp16 `wh` + a per-clip bias built from the clip's own
     // rows and the lo part (`wl_calib`), see gemm(); wherever that epilogue is not available the GEMM runs hi+lo instead
     bool rc = false;
-    int rc_type = 0;            // which GestSync Linear this is for option rc_layers: 1 qkv, 2 out_proj, 4 linear1 / ff_vid.0, 8 linear2
     bool bc_pending = false;    // LK_XLMR: no calibration yet -- the run-time GEMM keeps using hi+lo (wl == wl_calib); jg_calibrate_xlmr clears it
     f16* wl_calib = nullptr;
     float* mu = nullptr;        // device [K]: column sums of the A operand seen during calibration
@@ -153,7 +152,6 @@ struct jg_handle {
     std::vector<Lin*> bc_layers;   // bias-corrected layers of both models (entries of a model are dropped on its re-finalize)
     int chunk = 32;                // clips per GestSync pass: ~14 GB of workspace per lane at 150 frames; 288 GB of HBM make the whole BASELINE batch one pass
     bool fuse_ln = true;           // residual + LayerNorm in the GEMM epilogue (GestSync post-norm layers)
-    bool stream8 = false;          // option "stream_fp16" = 0: the fused transformer's token stream carries an 8-bit correction plane next to the fp16 plane
     bool edge_dedup = true;        // skip the 16 duplicated edge positions of a padded clip
     bool conv1_direct = true;      // fused u8 conv1 kernel (false: stack_frames + implicit GEMM)
     f16* gs_qpe = nullptr;         // [21][1536]: layer-0 W_qkv pe[j] + b (Qkv0); recomputed when weights or bias corrections change
@@ -218,9 +216,7 @@ struct jg_handle {
     bool dual_stream = true;
     int dual_split = 4;            // the first lane gets dual_split/8 of the batch.  Round 6: equal halves (rounds 3-5: 3/8; with the run-time correction's
                                    // small launches and the split-operand GEMMs in the mix the sweep reads 12.77 ms at 12:20, 12.57 at 14:18, 12.53-12.61 at 16:16,
-                                   // 12.57-12.66 at 17:15 / 18:14, 12.66-12.73 at 20:12 -- tools/dual_split_sweep.py)
-    int dual_split32 = 0;          // option "dual_split32" (experiments): the first lane gets this many 32nds of the batch instead (0: use dual_split)
-    int gesture_lanes = 0;         // option "gesture_lanes" (experiments): 3 / 4 = the gesture path runs as that many EQUAL parts (0: two lanes, dual_split)
+                                   // 12.57-12.66 at 17:15 / 18:14, 12.66-12.73 at 20:12 -- tools/experiments/README.md)
     std::map<hipStream_t, Arena> ws_parked;      // arenas of the other streams this handle has been bound to (jg_set_stream)
     static constexpr int MAX_LANES = 4;
     hipStream_t lane_stream[MAX_LANES] = {};
@@ -231,9 +227,6 @@ struct jg_handle {
     // 4 XLM-RoBERTa; JG_PREC_FP32 = all of them) -- the stage boundaries are fp32 tensors in every mode, so stages can be mixed
     // round 6: the two ends of the JEGAL gesture branch -- proj_ip_rgb and final norm + proj_op_rgb + the align MLP, five
     // small GEMMs that carry two thirds of the branch's fp16 error -- run on the fp32 kernel in the fp16 contract modes
-    int rc_layers = 15;            // experiment (option "rc_layers"): which Linear types of the GestSync transformer get the run-time correction
-                                   // (mask of Lin::rc_type); the others run single fp16 WITHOUT a correction -- measurement only
-    bool jegal_ffn_x3 = false;     // option "jegal_ffn_x3": the JEGAL gesture branch's feed-forward sub-layers on the split-operand kernel too (measured, not default)
     bool jegal_fp32_ends = true;
     bool conv_round_diffuse = true;      // conv weights rounded with per-channel error diffusion across the taps (pack_matrix)
     bool audit_weights = false;
@@ -616,9 +609,7 @@ int finalize_gestsync(jg_handle* h) {
         RET(make_linear(h, p + ".linear2.weight", p + ".linear2.bias", 512, 2048, &L->ff2));
         RET(make_ln(h, p + ".norm1.weight", p + ".norm1.bias", 512, &L->n1));
         RET(make_ln(h, p + ".norm2.weight", p + ".norm2.bias", 512, &L->n2));
-        L->qkv.rc_type = 1; L->out.rc_type = 2; L->ff1.rc_type = 4; L->ff2.rc_type = 8;
     }
-    h->ff0.rc_type = 4;
     h->gs_ready = true;
     return JG_OK;
 }
@@ -678,8 +669,6 @@ struct Epi {
     int ln_flavour = LN_STD;
     // tiled token stream of the fused GestSync transformer (common.h): residual in / LayerNorm out planes, tiled A operand
     const f16* res16 = nullptr;
-    const signed char* res8 = nullptr;
-    signed char* out8 = nullptr;
     int a_tiled = 0;
     int no_bias = 0;              // the layer's bias is applied elsewhere (layer-0 qkv by linearity: it rides in the projected PE rows)
     // implicit LayerNorm (GemmArgs::ln_mode): ln_stats = (mean, rstd) of the LayerNorm's input rows.  Mode 1: the layer is a folded
@@ -704,9 +693,7 @@ int gemm(jg_handle* h, int stage, const f16* A, long lda, int M, const Lin& L, c
     if (g) a.g = *g;
     a.Wh = L.wh; a.Wl = (h->calib && L.bc) ? L.wl_calib : L.wl; a.ldw = L.K;
     const bool conv = g != nullptr;
-    if (L.rc && L.rc_type && !(h->rc_layers & L.rc_type)) {
-        // experiment (option rc_layers): this Linear type runs single fp16 without its correction
-    } else if (L.rc) {
+    if (L.rc) {
         // run-time correction: bias_clip = bias + lo . (mean of a sample of the clip's own rows), two small launches in front of the GEMM;
         // only the LDS-DMA kernel's fp16-row and LayerNorm-fused epilogues take it (launch_gemm), everything else runs hi+lo
         const bool ln_fused = e.ln && e.res16;
@@ -729,7 +716,7 @@ int gemm(jg_handle* h, int stage, const f16* A, long lda, int M, const Lin& L, c
     a.out32 = e.out32; a.out16 = e.out16; a.ldc = e.ldc ? e.ldc : L.N;
     a.relu = e.relu;
     if (e.ln) { a.ln_w = e.ln->w; a.ln_b = e.ln->b; a.ln_flavour = e.ln_flavour; }
-    a.res16 = e.res16; a.res8 = e.res8; a.out8 = e.out8; a.a_tiled = e.a_tiled;
+    a.res16 = e.res16; a.a_tiled = e.a_tiled;
     if (e.ln_mode == 1) {
         if (!L.c1h || !L.c1f) JG_FAIL(h, JG_ERR_STATE, "implicit LayerNorm on a layer that was not packed for it");
         a.ln_mode = 1; a.ln_stats = e.ln_stats; a.scale = a.Wl ? L.c1f : L.c1h;
@@ -915,7 +902,7 @@ int gs_build_const_chain(jg_handle* h) {
 // kernel), and the per-clip bias needs rows_per_clip >= 256 (gemm(): `can`): shorter clips (T <= 12) and launches without clip structure
 // take the unfused plan, whose GEMMs run hi+lo (such batches used to fail with hipErrorInvalidValue).
 bool gs_fused_plan(const jg_handle* h, int M, int rows_per_clip) {
-    if (!h->fuse_ln || !h->opts.gemm_glds || h->calib || M < 1024 || h->bf16) return false;     // (the token stream's codec is fp16 + fp8)      // the tiled token stream is read by LDS-DMA only
+    if (!h->fuse_ln || !h->opts.gemm_glds || h->calib || M < 1024 || h->bf16) return false;     // (the token stream is fp16)      // the tiled token stream is read by LDS-DMA only
     if (h->precision == JG_PREC_FP16_RC && rows_per_clip < 256) return false;
     for (int l = 0; l < 6; ++l)
         if (h->gs_layers[l].out.wl || h->gs_layers[l].ff2.wl) return false;
@@ -923,8 +910,8 @@ bool gs_fused_plan(const jg_handle* h, int M, int rows_per_clip) {
 }
 inline size_t pad128(size_t rows) { return (rows + 127) / 128 * 128; }
 
-// x32/x16 hold pad128(M) rows.  With `tiled` (gs_fused_plan) the token stream is the tiled fp16 plane x16 plus the 8-bit
-// correction plane stored in x32's memory (launch_window_gather(..., tiled = 1)); otherwise fp32 rows + fp16 rows.
+// x32/x16 hold pad128(M) rows.  With `tiled` (gs_fused_plan) the token stream is the tiled fp16 plane x16 alone (x32 is not
+// used); otherwise fp32 rows + fp16 rows.
 // Layer 0's qkv projection by linearity (clip path): token j of window (clip c, frame i) is conv[c][clamp(i+j-shift)] + pe[j],
 // so W x + b = W conv[c][p] + (W pe[j] + b).  The projection then runs over the nclip*P distinct conv positions (154 per clip
 // instead of 150 * 21 tokens) plus the 21 positional rows, and the attention kernel gathers and sums the operand rows
@@ -943,7 +930,6 @@ int gs_transformer(jg_handle* h, float* x32, f16* x16, int nseq, int S, bool til
     RET(wsalloc(h, (size_t)M * 1536, &qkv));
     RET(wsalloc(h, (size_t)M * 512, &att));
     RET(wsalloc(h, (size_t)M * 2048, &hid));
-    signed char* d8 = reinterpret_cast<signed char*>(x32);
     for (int l = 0; l < 6; ++l) {
         const EncLayer& L = h->gs_layers[l];
         if (l == 0 && q0) {
@@ -968,12 +954,11 @@ int gs_transformer(jg_handle* h, float* x32, f16* x16, int nseq, int S, bool til
             RET(timed(h, JG_ST_ATTN, [&] { return LAUNCH(h, launch_attention, qkv, nullptr, nseq, S, 8, 64, att, h->opts, h->stream); }));
         }
         // out_proj / linear2 with the residual add and the post-norm LayerNorm fused into the epilogue (row-wide
-        // 128x512 tiles, tiled fp16 + 8-bit token stream) when gs_fused_plan() says so; otherwise GEMM + LayerNorm kernel.
+        // 128x512 tiles, tiled fp16 token stream) when gs_fused_plan() says so; otherwise GEMM + LayerNorm kernel.
         auto proj_ln = [&](const f16* A, long lda, const Lin& W, const LNp& ln) -> int {
             Epi r;
             if (tiled) {
                 r.res16 = x16; r.out16 = x16; r.ln = &ln; r.ln_flavour = LN_STD;
-                if (h->stream8) { r.res8 = d8; r.out8 = d8; }
                 r.rc_rpc = rc_rpc; r.rc_clips = rc_clips; r.rc_valid = rc_valid;
                 return gemm(h, JG_ST_GEMM, A, lda, M, W, r);
             }
@@ -1132,7 +1117,7 @@ int annotated_encoder32(jg_handle* h, const EncLayer* layers, int nl, const LNp&
 
 // ONE sub-layer of a pre-norm encoder layer on the fp32 kernels, in place on the fp32 residual stream (which = 1: x += out(attn(qkv(LN1 x))),
 // 2: x += ff2(relu(ff1(LN2 x)))); scratch: M * (D + 3 D + D + Dff) floats.  (Diagnosis: annotated_encoder's `parts`.)
-int encoder_sublayers32(jg_handle* h, const EncLayer& L, int which, float* x32, float* scratch, const float* mask, int B, int S, int D, int Dff, bool x3 = false) {
+int encoder_sublayers32(jg_handle* h, const EncLayer& L, int which, float* x32, float* scratch, const float* mask, int B, int S, int D, int Dff) {
     const int M = B * S, H = 8, dk = D / H;
     float* n32 = scratch;
     float* qkv = n32 + (size_t)M * D;
@@ -1147,10 +1132,6 @@ int encoder_sublayers32(jg_handle* h, const EncLayer& L, int which, float* x32, 
     }
     Epi32 f; f.act = 1;
     RET(timed(h, JG_ST_NORM, [&] { return launch_layernorm(x32, L.n2.w, L.n2.b, M, D, LN_ANNOTATED, 0, n32, nullptr, h->stream); }));
-    if (x3) {          // option jegal_ffn_x3: fp32 activations, split in the loader, three fp16 MFMAs per tile (gemm_x3)
-        RET(gemm_x3(h, JG_ST_GEMM, n32, D, M, L.ff1, hid, f));
-        return gemm_x3(h, JG_ST_GEMM, hid, Dff, M, L.ff2, x32, r);
-    }
     RET(gemm32(h, JG_ST_GEMM, n32, D, M, L.ff1, hid, f));
     return gemm32(h, JG_ST_GEMM, hid, Dff, M, L.ff2, x32, r);
 }
@@ -1186,23 +1167,13 @@ int jegal_tail32(jg_handle* h, const float* n32, int M, int align, float* out, b
 
 int jegal_gestures_impl32(jg_handle* h, const float* feats, const float* mask, int B, int T, int align, float* out) {
     const int M = B * T;
-    float *t32, *t2, *x32, *n32, *g32, *a32;
+    float *t32, *x32, *n32;
     RET(wsalloc(h, (size_t)M * 512, &t32));
-    RET(wsalloc(h, (size_t)M * 512, &t2));
     RET(wsalloc(h, (size_t)M * 512, &x32));
     RET(wsalloc(h, (size_t)M * 512, &n32));
-    RET(gemm32(h, JG_ST_GEMM, feats, 1024, M, h->ip0, t32));
-    RET(timed(h, JG_ST_NORM, [&] { return launch_layernorm(t32, h->ip_ln.w, h->ip_ln.b, M, 512, LN_STD, 1, t2, nullptr, h->stream); }));
-    Epi32 p; p.res = h->rgb_pe; p.ldr = 512; p.res_mod = T;
-    RET(gemm32(h, JG_ST_GEMM, t2, 512, M, h->ip3, x32, p));
+    RET(jegal_input32(h, feats, M, T, t32, x32, false));
     RET(annotated_encoder32(h, h->rgb_layers, 6, h->rgb_norm, x32, n32, mask, B, T, 512, 2048));
-    if (!align) return gemm32(h, JG_ST_GEMM, n32, 512, M, h->op_rgb, out);
-    RET(wsalloc(h, (size_t)M * 512, &g32));
-    RET(wsalloc(h, (size_t)M * 512, &a32));
-    RET(gemm32(h, JG_ST_GEMM, n32, 512, M, h->op_rgb, g32));
-    Epi32 f; f.act = 1;
-    RET(gemm32(h, JG_ST_GEMM, g32, 512, M, h->al_g0, a32, f));
-    return gemm32(h, JG_ST_GEMM, a32, 512, M, h->al_g2, out);
+    return jegal_tail32(h, n32, M, align, out, false);
 }
 
 int jegal_audio_impl32(jg_handle* h, const float* mel, int B, int Tm, const int32_t* valid_host, float* out) {
@@ -1365,7 +1336,7 @@ int gestsync_clip_impl(jg_handle* h, const void* frames, int dtype, int B, int T
         }
         RET(wsalloc(h, pad128(M) * 512, &x32));
         RET(wsalloc(h, pad128(M) * 512, &x16));
-        RET(timed(h, JG_ST_MISC, [&] { return LAUNCH(h, launch_window_gather, conv, h->gs_pe, nb, P, T, S, 512, 12 - PAD, tiled ? (h->stream8 ? 1 : 2) : 0, x32, x16, h->stream); }));
+        RET(timed(h, JG_ST_MISC, [&] { return LAUNCH(h, launch_window_gather, conv, h->gs_pe, nb, P, T, S, 512, 12 - PAD, tiled, x32, x16, h->stream); }));
         const Qkv0 q0 = {conv16, nb, P, T, 12 - PAD};
         RET(gs_transformer(h, x32, x16, nseq, S, tiled, lin0 ? &q0 : nullptr, nb, rc_valid));
         RET(wsalloc(h, (size_t)M * 512, &hid));
@@ -1414,7 +1385,7 @@ int gestsync_windows_impl(jg_handle* h, const float* x, int N, float* out, float
         const bool tiled = gs_fused_plan(h, M, 0);
         RET(wsalloc(h, pad128(M) * 512, &x32));
         RET(wsalloc(h, pad128(M) * 512, &x16));
-        RET(timed(h, JG_ST_MISC, [&] { return LAUNCH(h, launch_window_gather, conv, h->gs_pe, nb, S, 1, S, 512, 0, tiled ? (h->stream8 ? 1 : 2) : 0, x32, x16, h->stream); }));
+        RET(timed(h, JG_ST_MISC, [&] { return LAUNCH(h, launch_window_gather, conv, h->gs_pe, nb, S, 1, S, 512, 0, tiled, x32, x16, h->stream); }));
         RET(gs_transformer(h, x32, x16, nb, S, tiled));
         RET(wsalloc(h, (size_t)M * 512, &hid));
         RET(wsalloc(h, (size_t)M * 1024, &full));
@@ -1453,7 +1424,7 @@ int annotated_encoder(jg_handle* h, const EncLayer* layers, int nl, const LNp& f
             RET(gemm(h, JG_ST_GEMM, att, D, M, L.out, r));
         }
         if (parts & 4) {
-            RET(encoder_sublayers32(h, L, 2, x32, scr32, mask, B, S, D, Dff, (parts & 16) != 0));
+            RET(encoder_sublayers32(h, L, 2, x32, scr32, mask, B, S, D, Dff));
         } else {
             RET(timed(h, JG_ST_NORM, [&] { return LAUNCH(h, launch_layernorm, x32, L.n2.w, L.n2.b, M, D, LN_ANNOTATED, 0, nullptr, n16, h->stream); }));
             Epi f; f.relu = 1; f.out16 = hid;
@@ -1472,9 +1443,7 @@ int jegal_gestures_impl(jg_handle* h, const float* feats, const float* mask, int
     const int M = B * T;
     // the branch's two ends on the fp32 kernel (option jegal_fp32_ends; not in the plain-fp16 / bf16 reported modes, not while calibrating)
     const bool ends32 = h->jegal_fp32_ends && !h->calib && h->precision != JG_PREC_FP16 && h->precision != JG_PREC_BF16 && h->ip0.b32d && h->al_g2.b32d;
-    // option jegal_ffn_x3 (default off; DESIGN.md section 3 prices it): the six feed-forward sub-layers with fp32 activations on the split-operand kernel
-    const bool ffn_x3 = ends32 && h->jegal_ffn_x3 && !(h->audit_jegal_parts & 4) && (h->rgb_layers[0].ff1.wl || h->rgb_layers[0].ff1.wl_calib) && (h->rgb_layers[0].ff2.wl || h->rgb_layers[0].ff2.wl_calib);
-    const int parts = h->audit_jegal_parts | (ends32 ? 9 : 0) | (ffn_x3 ? 4 | 16 : 0);
+    const int parts = h->audit_jegal_parts | (ends32 ? 9 : 0);
     const bool ends_x3 = ends32 && !(h->audit_jegal_parts & 9);          // production: split operands on the fp16 matrix cores; diagnosis: fp32 MFMA
     f16 *f16in, *t16, *n16, *g16, *a16;
     float *t32, *x32, *n32 = nullptr;
@@ -1954,7 +1923,7 @@ int run_in_lanes(jg_handle* h, int B, int T, F&& run_part, int equal_lanes = 0) 
     const int nl = equal_lanes ? equal_lanes : 2;
     int start[jg_handle::MAX_LANES + 1];
     start[0] = 0;
-    for (int l = 1; l <= nl; ++l) start[l] = equal_lanes ? (int)((long)B * l / nl) : (l == 1 ? (h->dual_split32 ? (B * h->dual_split32 + 16) / 32 : (B * h->dual_split + 4) / 8) : B);
+    for (int l = 1; l <= nl; ++l) start[l] = equal_lanes ? (int)((long)B * l / nl) : (l == 1 ? (B * h->dual_split + 4) / 8 : B);
     int smallest = B;
     for (int l = 0; l < nl; ++l) smallest = std::min(smallest, start[l + 1] - start[l]);
     if (!h->dual_stream || h->calib || nl < 2 || B < 8 || (long)smallest * T < 256 || audit_mask(h)) return run_part(0, B);
@@ -2103,14 +2072,11 @@ int jg_set_option(jg_handle* h, const char* name, int value) {
     EngineOpts& o = h->opts;
     if (!std::strcmp(name, "conv1_direct")) { h->conv1_direct = value != 0; return JG_OK; }
     if (!std::strcmp(name, "fuse_ln")) { h->fuse_ln = value != 0; return JG_OK; }
-    if (!std::strcmp(name, "stream_fp16")) { h->stream8 = value == 0; return JG_OK; }
     if (!std::strcmp(name, "edge_dedup")) { h->edge_dedup = value != 0; return JG_OK; }
     if (!std::strcmp(name, "conv1_mfma16")) { o.conv1_mfma16 = value != 0; return JG_OK; }
     if (!std::strcmp(name, "conv1_zero_skip")) { o.conv1_zero_skip = value != 0; return JG_OK; }
     if (!std::strcmp(name, "conv2_row_skip")) { h->conv2_row_skip = value != 0; return JG_OK; }
     if (!std::strcmp(name, "ws_poison")) { h->ws_poison = value != 0; return JG_OK; }
-    if (!std::strcmp(name, "rc_layers")) { h->rc_layers = value & 15; return JG_OK; }
-    if (!std::strcmp(name, "jegal_ffn_x3")) { h->jegal_ffn_x3 = value != 0; return JG_OK; }
     if (!std::strcmp(name, "jegal_fp32_ends")) { h->jegal_fp32_ends = value != 0; return JG_OK; }
     if (!std::strcmp(name, "conv_round_diffuse")) {
         if (h->gs_ready || h->jg_ready) JG_FAIL(h, JG_ERR_STATE, "set conv_round_diffuse before jg_finalize_weights");
@@ -2140,22 +2106,12 @@ int jg_set_option(jg_handle* h, const char* name, int value) {
         o.num_cu = value;
         return JG_OK;
     }
-    if (!std::strcmp(name, "gesture_lanes")) {
-        if (value != 0 && (value < 2 || value > jg_handle::MAX_LANES)) JG_FAIL(h, JG_ERR_ARG, "gesture_lanes must be 0 or 2..%d", jg_handle::MAX_LANES);
-        h->gesture_lanes = value;
-        return JG_OK;
-    }
     if (!std::strcmp(name, "xlmr_lanes")) {
         if (value < 1 || value > jg_handle::MAX_LANES) JG_FAIL(h, JG_ERR_ARG, "xlmr_lanes must be 1..%d", jg_handle::MAX_LANES);
         h->xl_lanes = value;
         return JG_OK;
     }
     if (!std::strcmp(name, "xlmr_fold")) { h->xl_fold_opt = value != 0; return JG_OK; }       // takes effect at the next jg_finalize_weights(h, 4)
-    if (!std::strcmp(name, "dual_split32")) {
-        if (value < 0 || value > 31) JG_FAIL(h, JG_ERR_ARG, "dual_split32 must be 0..31 (32nds of the batch on the first lane; 0 = use dual_split)");
-        h->dual_split32 = value;
-        return JG_OK;
-    }
     if (!std::strcmp(name, "lane_priority")) {
         if (value < 0 || value > 3) JG_FAIL(h, JG_ERR_ARG, "lane_priority must be 0..3");
         if (value != h->lane_priority) {
@@ -2186,7 +2142,6 @@ int jg_set_option(jg_handle* h, const char* name, int value) {
     if (!std::strcmp(name, "gemm_counted")) { o.gemm_counted = value != 0; return JG_OK; }
     if (!std::strcmp(name, "gemm_persistent")) { o.gemm_persistent = value != 0; return JG_OK; }
     if (!std::strcmp(name, "gemm_stagger")) { o.gemm_stagger = value; return JG_OK; }
-    if (!std::strcmp(name, "gemm_timeline")) { DeviceGuard dg(h->device); engine_opts_set_timeline(o, value != 0); return JG_OK; }
     JG_FAIL(h, JG_ERR_ARG, "unknown option '%s'", name);
 }
 
@@ -2359,7 +2314,6 @@ int jg_debug_gemm_ex(jg_handle* h, const void* a16, const void* w16, int M, int 
     if (mode & 8) {      // residual + LayerNorm fused (N = 512): gamma/beta = the zero bias vector, timing only
         a.res = nullptr; a.out32 = nullptr;
         a.res16 = o16; a.out16 = o16;
-        if (h->stream8) { a.res8 = reinterpret_cast<signed char*>(x32); a.out8 = reinterpret_cast<signed char*>(x32); }      // (option stream_fp16 = 0)
         a.ln_w = bias; a.ln_b = bias; a.ln_flavour = LN_STD;
     }
     if (mode & 48) {     // implicit LayerNorm, timing only: 16 = consumer (ln_mode 1), 32 = producer (ln_mode 2); statistics / planes = the scratch buffers
@@ -2427,7 +2381,7 @@ int jg_debug_gemm_check(jg_handle* h, const jg_gemm_check* c) {
     a.res = c->res; a.ldr = c->ldr; a.res_mod = c->res_mod; a.relu = c->relu;
     a.out32 = c->out32; a.out16 = static_cast<f16*>(c->out16); a.ldc = c->ldc;
     a.ln_w = c->ln_w; a.ln_b = c->ln_b; a.ln_flavour = LN_STD;
-    a.res16 = static_cast<const f16*>(c->res16); a.res8 = static_cast<const signed char*>(c->res8); a.out8 = static_cast<signed char*>(c->out8);
+    a.res16 = static_cast<const f16*>(c->res16);
     a.ln_mode = c->ln_mode; a.ln_stats = c->ln_stats;
     a.xres_hi = static_cast<const f16*>(c->xres_hi); a.xres_lo = static_cast<const f16*>(c->xres_lo);
     a.out_lo = static_cast<f16*>(c->out_lo); a.stat_out = c->stat_out;
@@ -2620,7 +2574,7 @@ int jg_extract_gesture(jg_handle* h, const void* frames, int dtype, int B, int T
         RET(jegal_gestures_impl(h, feats, nullptr, nb, T, 1, emb));
         return timed(h, JG_ST_MISC, [&] { return launch_l2norm(emb, emb, nb * T, 512, h->stream); });
     };
-    return run_in_lanes(h, B, T, run_part, h->gesture_lanes);
+    return run_in_lanes(h, B, T, run_part);
 }
 
 int jg_pool_mean(jg_handle* h, const float* x, const int32_t* off, int n, int D, float* out) {

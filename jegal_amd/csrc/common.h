@@ -116,12 +116,10 @@ struct GemmArgs {
     const float* ln_w;    // nullptr: no LayerNorm
     const float* ln_b;
     int ln_flavour;       // LN_STD / LN_ANNOTATED
-    // Tiled token stream of the fused GestSync transformer (see res_* below): with ln_w the residual comes from
-    // (res16, res8) and the LayerNorm output goes to (out16, out8), all in the tiled order; a_tiled: the A operand
-    // of a plain GEMM (K == 512) is such a tiled fp16 plane.
+    // Tiled token stream of the fused GestSync transformer (see below): with ln_w the residual comes from res16 and the
+    // LayerNorm output goes to out16, both in the tiled order; a_tiled: the A operand of a plain GEMM (K == 512) is such
+    // a tiled fp16 plane.
     const f16* res16;
-    const signed char* res8;
-    signed char* out8;
     int a_tiled;
     // Implicit LayerNorm (XLM-RoBERTa's post-norm layers, api.hip:xlmr_encode_impl): the token stream holds the UN-normalised rows
     // x = hi + lo (two fp16 planes; the hi plane is the next GEMM's A operand) and per row (mean, rstd) of x; LN(x) itself is never
@@ -145,40 +143,15 @@ struct GemmArgs {
 };
 
 // ---- tiled token stream (N = 512 columns, row tiles of 128) -----------------------------------------------------
-// The residual stream of the fused transformer is kept as fp16 + an 8-bit correction instead of fp32 (3 instead of
-// 4 bytes per element to read, 3 instead of 6 to write next to the fp16 copy the next GEMM needs anyway):
-//   x  =  x16 + c * 2^-13,   c = e4m3( clamp((x - x16) * 2^13, +-448) )   (one OCP fp8 byte, v_cvt_pk_fp8_f32 / v_cvt_pk_f32_fp8)
-// |x - x16| <= ulp(x16)/2 and e4m3 keeps 4 significant bits of it: relative error <= 2^-16 per LayerNorm output (rms ~ 5e-6;
-// 12 of them per forward pass; the embedding tolerance is 1e-3, the path measures 6e-4 with or without it).  The scale 2^13
-// keeps c normal for |x| between 2^-4 and 128 (below: the absolute error is < 2^-23; above: c saturates and the element
-// degrades towards plain fp16).  Round 2 stored round((x - x16) * 256/ulp(x16)) as a biased byte (2^-19): three more bits
-// that the error budget never saw, for 17 VALU instructions per element in the LayerNorm epilogue instead of 5.
-// Both planes are stored in the MFMA fragment order of the 128x512 LN kernel:
+// The residual stream of the fused transformer is one fp16 plane: in a post-norm transformer the LayerNorm output is
+// rounded to fp16 as the next GEMM's operand anyway, and carrying the residual at that precision costs 1-5 % of the
+// feature error (oracle/precision_families.py) for no extra bytes and no codec arithmetic.
+// The plane is stored in the MFMA fragment order of the 128x512 LN kernel:
 //   x16t element (m, n): R*65536 + (n>>6)*8192 + ((m&127)>>4)*1024 + ((n&63)>>4)*256 + (m&15)*16 + (n&15),  R = m>>7
 //        (a wave's 8-byte accesses of one (j, i) block are one contiguous 512 B; a 64-wide k-tile of a 128-row
 //         panel is one contiguous 16 KB -> the consumer GEMMs' LDS-DMA reads it with a_tiled addressing)
-//   d8t  byte    (m, n): R*65536 + (n>>6)*8192 + ((m&127)>>4)*1024 + lane*16 + ((n&63)>>4)*4 + (n&3),
-//        lane = ((n&15)>>2)*16 + (m&15)   (one 16-byte access per lane and 16-row block)
 #ifdef __HIPCC__
 typedef float f32x2_t __attribute__((ext_vector_type(2)));
-constexpr float RES_SCALE = 8192.f, RES_INV_SCALE = 1.220703125e-4f;      // 2^13, 2^-13
-// h01 / h23: two packed fp16 pairs (elements 0,1 and 2,3), dw: their four corrections
-__device__ __forceinline__ f32x4 res_dec4(unsigned h01, unsigned h23, unsigned dw) {
-    const f32x2_t c01 = __builtin_amdgcn_cvt_pk_f32_fp8((int)dw, false), c23 = __builtin_amdgcn_cvt_pk_f32_fp8((int)dw, true);
-    const f16x2 a = __builtin_bit_cast(f16x2, h01), b = __builtin_bit_cast(f16x2, h23);
-    return f32x4{__builtin_fmaf(c01.x, RES_INV_SCALE, (float)a.x), __builtin_fmaf(c01.y, RES_INV_SCALE, (float)a.y),
-                 __builtin_fmaf(c23.x, RES_INV_SCALE, (float)b.x), __builtin_fmaf(c23.y, RES_INV_SCALE, (float)b.y)};
-}
-// four corrections packed into one dword
-__device__ __forceinline__ unsigned res_enc4(float y0, float y1, float y2, float y3, f16 h0, f16 h1, f16 h2, f16 h3) {
-    auto t = [](float y, f16 h) -> float {        // (y - h) * 2^13: v_mul + v_fma_mix (the fp16 operand is read as such), clamped to e4m3's range
-        return __builtin_amdgcn_fmed3f(__builtin_fmaf(-(float)h, RES_SCALE, y * RES_SCALE), -448.f, 448.f);
-    };
-    int w = 0;
-    w = __builtin_amdgcn_cvt_pk_fp8_f32(t(y0, h0), t(y1, h1), w, false);
-    w = __builtin_amdgcn_cvt_pk_fp8_f32(t(y2, h2), t(y3, h3), w, true);
-    return (unsigned)w;
-}
 #endif
 
 enum { LN_STD = 0, LN_ANNOTATED = 1 };
@@ -199,7 +172,6 @@ struct EngineOpts {
     int gemm_stagger = 0;                // 10-ns ticks per phase (0: default policy, -1: off)
     bool lanes_active = false;           // the launch is part of a two-lane batch (api.hip, run_in_lanes): the other lane's kernels already
                                          // spread the store bursts, the default de-phasing only costs time there (12.22 -> 12.16 ms per step)
-    unsigned long long* gemm_tl = nullptr;   // debug timeline buffer (option gemm_timeline)
     bool attn_mfma = true;
     bool conv1_zero_skip = true;
     bool conv1_mfma16 = true;            // conv1_direct_kernel's MFMA waves on 16x16x32 MFMAs (false: 32x32x16, the round-1/2 form)
@@ -214,7 +186,6 @@ inline void record_kernel(char* kname, const char* fmt, T... v) {
 }
 hipError_t engine_opts_init(EngineOpts& o, int device);      // queries the CU count, allocates the zero page (current device = `device`)
 void engine_opts_release(EngineOpts& o);
-void engine_opts_set_timeline(EngineOpts& o, bool on);
 
 // ---- launchers (each returns hipGetLastError()) -----------------------------------------
 hipError_t launch_gemm(const GemmArgs& a, bool conv, const EngineOpts& o, hipStream_t s);
@@ -244,7 +215,8 @@ size_t conv1_edge_elems(long positions);
 // s2 / in_op / const_in as in ConvGeom: input rows of image n below conv_skip_decode(s2[n], in_op) come from the const image
 hipError_t launch_maxpool3x3s2(const f16* in, f16* out, int N, int H, int W, int C, hipStream_t s, const int* s2 = nullptr,
                                int in_op = 0, const f16* const_in = nullptr);
-hipError_t launch_window_gather(const float* conv, const float* pe, int B, int P, int Twin, int L, int D, int shift, int tiled,
+// tiled: x16 is the tiled token stream (D = 512; x32 unused); otherwise row-major x32 (+ x16 unless nullptr)
+hipError_t launch_window_gather(const float* conv, const float* pe, int B, int P, int Twin, int L, int D, int shift, bool tiled,
                                 float* x32, f16* x16, hipStream_t s);
 hipError_t launch_layernorm(const float* in, const float* w, const float* b, int rows, int D, int flavour,
                             int relu, float* out32, f16* out16, hipStream_t s);

@@ -57,7 +57,6 @@ struct Conv1Args {
     f16* dump;            // [gridDim.x][256][8]: scratch slots for stores of lanes that have no output (behind `edge`)
     int nstrips;          // nclip * P * 5
     float invP;           // 1/P for the position -> (clip, frame) split
-    unsigned long long* tl;   // debug timeline (env JG_CONV1_TL): 100 MHz stamps of workgroup 0, waves 0 and 4
     int zskip;            // 1: all-zero input tiles (the face-mask rows) run only the two bias slots
     const unsigned* zmask;    // [nclip*P] per POSITION: bit rt = input band rt is zero in all five frames of the position
                               // (conv1_zero_scan_kernel + conv1_skip_mask_kernel); tile rt is skipped outright when bits rt and
@@ -65,8 +64,6 @@ struct Conv1Args {
     const f16* zconst;        // [64] relu(bias) per channel as fp16: the value of every conv1 output whose patch is all zero
     int fill_partial;         // 1: conv2 honours the per-position row skip (common.h, ConvGeom::rowmap): it reads pooled rows >= 2 s2 of a
                               // position only (s2 from the position's own skip mask), and the constant fill leaves the rows above unwritten
-    int dbg;              // ablation switch (env JG_CONV1_DBG): 1 = loaders idle, 2 = MFMA waves idle, 4 = no pooling,
-                          // 8 = no u8->fp16 conversion / LDS fill (timing experiments only)
 };
 
 namespace {
@@ -113,16 +110,12 @@ __device__ __forceinline__ int conv1_s2_of_mask(unsigned sk) {
     return rs < C2_OH ? rs : C2_OH - 1;
 }
 
-// DBG: the timeline stamps (JG_CONV1_TL) and the ablation switches (JG_CONV1_DBG) exist only in the <true> instantiation: in the
-// loader waves every extra scalar compare-and-branch per tile is on the critical path (one wave per SIMD, ~9 cycles per
-// instruction next to the MFMA wave).
 // M16: the MFMA waves run v_mfma_f32_16x16x32_f16 (two pixel slots per k-step) instead of 32x32x16 (one slot): the same FLOPs per
 // cycle, but the chip holds a higher clock on the 16x16x32 shape (MI355X_MICROARCH.md "DVFS give-back" item 7; tools/mfma_rate.hip
 // on this part, random data, registers only: 19.7 ns per 32x32x16 = 1.70 PFLOP/s against 8.2-9.2 ns per 16x16x32 = 1.8-2.05),
 // and the MFMA waves are this kernel's critical role.  See the M16 block below for the k-step pairing and the LDS addressing.
-template <bool DBG, bool M16>
+template <bool M16>
 __global__ __launch_bounds__(512, 2) void conv1_direct_kernel(Conv1Args a) {
-    const int dbg = DBG ? a.dbg : 0;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -138,7 +131,7 @@ __global__ __launch_bounds__(512, 2) void conv1_direct_kernel(Conv1Args a) {
     // local tile t of this workgroup -> strip s_lo + (t/22)*GX, row tile t%22
     // All of this index math is 32-bit and incremental: the first version decoded every tile id with 64-bit
     // divisions (t/22, strip/5, nf/P) in both issue() and pool() -- ~1.2 us of VALU per tile on the loader waves,
-    // which made THEM the critical path (tools/conv1_ablate.py, JG_CONV1_TL=1).
+    // which made THEM the critical path.
     const int G32 = (int)G;
     const int xcd = blockIdx.x & 7, xidx = blockIdx.x >> 3;
     const int GX = (G32 + 7 - xcd) >> 3;                                 // workgroups on this XCD
@@ -202,7 +195,6 @@ __global__ __launch_bounds__(512, 2) void conv1_direct_kernel(Conv1Args a) {
         walk_next(q, on_strip);
         return q;
     };
-    auto no_fill = [](int, unsigned) {};
 
     if (!(s_lo < r_hi && GX > 0)) return;      // a workgroup without a strip (launches of fewer strips than CUs): nothing to do, for either role
     if (use_skip) {
@@ -267,11 +259,6 @@ __global__ __launch_bounds__(512, 2) void conv1_direct_kernel(Conv1Args a) {
                 const uint8_t* fbu = reinterpret_cast<const uint8_t*>(((uintptr_t)fb0_lo | ((uintptr_t)fb0_hi << 32)) + fdelta[dt]);
                 // s_nop 4: the base may come straight out of a v_readfirstlane, and hipcc pads no hazard for an operand of an asm
                 // statement (VALU-written SGPR -> VMEM address: 5 wait states; cdna_hip_programming.md 5.7 item 2)
-                if (DBG && (dbg & 32)) {            // debugging aid: compiler-visible loads
-                    R.w[0][dt] = *reinterpret_cast<const u32x3*>(fbu + o0);
-                    R.w[1][dt] = *reinterpret_cast<const u32x3*>(fbu + o1);
-                    continue;
-                }
                 asm volatile("s_nop 4\n\tglobal_load_dwordx3 %0, %1, %2" : "=v"(R.w[0][dt]) : "v"(o0), "s"(fbu) : "memory");
                 asm volatile("global_load_dwordx3 %0, %1, %2" : "=v"(R.w[1][dt]) : "v"(o1), "s"(fbu) : "memory");
             }
@@ -281,7 +268,7 @@ __global__ __launch_bounds__(512, 2) void conv1_direct_kernel(Conv1Args a) {
         // the integer-valued formulation times 2^-24 exactly; the epilogue scale carries the 2^24 (a power of two:
         // bit-identical results).  One v_perm_b32 places two bytes -> 8 VALU ops per 16-element pixel slot instead
         // of ~40 (cvt_f32_ubyte + cvt_f16_f32 + pack); the loader waves share their SIMDs with the MFMA waves and
-        // their VALU time is what the tile time was waiting for (JG_CONV1_TL=1).
+        // their VALU time is what the tile time was waiting for.
         // slot element k = 3*dt + c (dt = frame 0..4, c = channel), k = 15: the bias lane, 2^-24 (= 1.0 * 2^-24).
         // Zero tiles: the reference blanks the face region of every frame (inference_embs.py:264,270: rows 0..y2+15,
         // ~40 % of the crop).  A tile whose 16 x 100 x 5 source pixels are all zero contributes nothing but the bias
@@ -439,14 +426,6 @@ __global__ __launch_bounds__(512, 2) void conv1_direct_kernel(Conv1Args a) {
         };
 
         int* live = reinterpret_cast<int*>(smem + OFF_LIVE);
-        int tli = 0;
-        auto mark = [&]() {
-            if (DBG && a.tl && blockIdx.x == 0 && wave == 4 && tli < 2000) {
-                const unsigned long long c = wall_clock64();
-                if (lane == 0) a.tl[2048 + tli] = c;
-                ++tli;
-            }
-        };
         C1Regs RA, RB;
         // ONE walk, the issue walk (it runs three tiles ahead of the loop); the tiles the other steps of an iteration work on are
         // its last positions, kept in a small history: hA = tile t+2, hB = t+1 (image written this iteration), hC = t (the
@@ -475,18 +454,6 @@ __global__ __launch_bounds__(512, 2) void conv1_direct_kernel(Conv1Args a) {
             walk_next(qi, on_strip);
         };
         if (ltid == 0) { live[0] = qi.done ? 0 : 1; live[1] = 0; }
-        if (DBG && (dbg & 1)) {
-            Walk q = qi;
-            int t = 0;
-            while (!q.done) {
-                __syncthreads();
-                walk_next(q, no_fill);
-                if (ltid == 0) live[(t + 1) & 1] = q.done ? 0 : 1;
-                ++t;
-            }
-            __syncthreads();
-            return;
-        }
         const bool any_tile = !qi.done;
         issue_next(RA);                         // tile 0 (or nothing: the loads are harmless)
         if (any_tile) {
@@ -515,30 +482,22 @@ __global__ __launch_bounds__(512, 2) void conv1_direct_kernel(Conv1Args a) {
         };
         int t = 0;
         while (!hC.done) {                      // hC = tile t
-            mark();
             __syncthreads();
-            mark();
             const bool zc0 = tile_is_zero(t);          // before cvt_write reuses the other slot; this slot is rewritten at t+1
             if (ltid == 0) live[(t + 1) & 1] = hB.done ? 0 : 1;
-            wait_frames(RB, (t >= 2 && !dbg) ? 2 : 1);
-            if (!hB.done && !(dbg & 8)) cvt_write(RB, smem + ((t + 1) & 1) * TILE_BYTES, (t + 1) & 1, hB.zero);
-            mark();
-            if (t > 0 && !(dbg & 4)) pool_step(t - 1);          // hD = tile t-1; its stores go BEFORE the loads (wait_frames)
-            mark();
+            wait_frames(RB, t >= 2 ? 2 : 1);
+            if (!hB.done) cvt_write(RB, smem + ((t + 1) & 1) * TILE_BYTES, (t + 1) & 1, hB.zero);
+            if (t > 0) pool_step(t - 1);          // hD = tile t-1; its stores go BEFORE the loads (wait_frames)
             issue_next(RB);                     // tile t+3; the history shifts: hC = t+1, hD = t
             z2 = z1; z1 = zc0;
             ++t;
             if (hC.done) break;
-            mark();
             __syncthreads();
-            mark();
             const bool zc1 = tile_is_zero(t);
             if (ltid == 0) live[(t + 1) & 1] = hB.done ? 0 : 1;
-            wait_frames(RA, (t >= 2 && !dbg) ? 2 : 1);
-            if (!hB.done && !(dbg & 8)) cvt_write(RA, smem + ((t + 1) & 1) * TILE_BYTES, (t + 1) & 1, hB.zero);
-            mark();
-            if (!(dbg & 4)) pool_step(t - 1);
-            mark();
+            wait_frames(RA, t >= 2 ? 2 : 1);
+            if (!hB.done) cvt_write(RA, smem + ((t + 1) & 1) * TILE_BYTES, (t + 1) & 1, hB.zero);
+            pool_step(t - 1);
             issue_next(RA);
             z2 = z1; z1 = zc1;
             ++t;
@@ -548,7 +507,7 @@ __global__ __launch_bounds__(512, 2) void conv1_direct_kernel(Conv1Args a) {
         // of the final pool().  Drain them first.
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();                       // the MFMA waves have finished the last tile (hD = tile t-1)
-        if (t > 0 && !(dbg & 4)) pool_step(t - 1);
+        if (t > 0) pool_step(t - 1);
         return;
     }
 
@@ -593,23 +552,12 @@ __global__ __launch_bounds__(512, 2) void conv1_direct_kernel(Conv1Args a) {
         const int lb = 112 * colp + 16 * half;
         const int lb_row = lb + sel * ROW_PITCH, lb_32 = lb + sel * 32, lb_224 = lb + sel * 224;
         constexpr int DEPTH = 4;                             // patch fragments in flight per wave (2 steps x 2 column blocks; 6 spill)
-        int tli = 0;
-        auto mark = [&]() {
-            if (DBG && a.tl && blockIdx.x == 0 && wave == 0 && tli < 2000) {
-                const unsigned long long c = wall_clock64();
-                if (lane == 0) a.tl[tli] = c;
-                ++tli;
-            }
-        };
 #ifdef JG_CLOCK_STAMPS
         const unsigned long long ck0 = __builtin_amdgcn_s_memtime(), rt0 = __builtin_amdgcn_s_memrealtime();
 #endif
         for (int t = 0;; ++t) {
-            mark();
             __syncthreads();
-            mark();
             if (__builtin_amdgcn_readfirstlane(*reinterpret_cast<const int*>(smem + OFF_LIVE + (t & 1) * 4)) == 0) break;
-            if (dbg & 2) continue;
             const char* cur = smem + (t & 1) * TILE_BYTES + 3 * mb0 * ROW_PITCH;
             char* cbuf = smem + OFF_CONV + (t & 1) * CONV_BYTES;
             const char* p_row = cur + lb_row;
@@ -699,21 +647,10 @@ __global__ __launch_bounds__(512, 2) void conv1_direct_kernel(Conv1Args a) {
     //   (3*mb+kh)*ROW_PITCH + 32*x + 16*(x/3) + 16*h = [112*r + 16*h] + [kh*ROW_PITCH + 32*kw + 16*(kw/3)]
     const int lbase = 112 * r + 16 * h;
     constexpr int DEPTH = 6;                             // patch fragments in flight per wave
-    int tli = 0;
-    auto mark = [&]() {
-        if (DBG && a.tl && blockIdx.x == 0 && wave == 0 && tli < 2000) {
-            const unsigned long long c = wall_clock64();
-            if (lane == 0) a.tl[tli] = c;
-            ++tli;
-        }
-    };
     for (int t = 0;; ++t) {
-        mark();
         __syncthreads();
-        mark();
         // live[t & 1]: written by the loaders before this barrier; 0 = the workgroup's tiles are done (this was the final barrier)
         if (__builtin_amdgcn_readfirstlane(*reinterpret_cast<const int*>(smem + OFF_LIVE + (t & 1) * 4)) == 0) break;
-        if (dbg & 2) continue;
         const char* cur = smem + (t & 1) * TILE_BYTES;
         char* cbuf = smem + OFF_CONV + (t & 1) * CONV_BYTES;
         // The two blocks of a tile form ONE stream of 98 (block, slot) steps with DEPTH fragments in
@@ -985,8 +922,7 @@ hipError_t launch_conv1_direct(const uint8_t* src, int nclip, int T, int pad, co
     if (o.device < 0 || o.device >= 64) return hipErrorInvalidDevice;
     const int num_cu = o.num_cu;
     if (!attr_set[o.device]) {
-        const void* ks[3] = {reinterpret_cast<const void*>(conv1_direct_kernel<false, false>), reinterpret_cast<const void*>(conv1_direct_kernel<true, false>),
-                             reinterpret_cast<const void*>(conv1_direct_kernel<false, true>)};
+        const void* ks[2] = {reinterpret_cast<const void*>(conv1_direct_kernel<false>), reinterpret_cast<const void*>(conv1_direct_kernel<true>)};
         for (const void* kf : ks) {
             hipError_t e = hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
             if (e != hipSuccess) return e;
@@ -1000,8 +936,6 @@ hipError_t launch_conv1_direct(const uint8_t* src, int nclip, int T, int pad, co
     if ((long)nclip * a.P >= (1L << 24)) return hipErrorInvalidValue;     // decode() splits positions with a float reciprocal
     a.nstrips = nclip * a.P * COL_TILES;
     a.invP = 1.0f / (float)a.P;
-    static const int dbg = getenv("JG_CONV1_DBG") ? atoi(getenv("JG_CONV1_DBG")) : 0;
-    a.dbg = dbg;
     a.zskip = o.conv1_zero_skip ? 1 : 0;
     a.zmask = nullptr;
     a.zconst = nullptr;
@@ -1012,33 +946,10 @@ hipError_t launch_conv1_direct(const uint8_t* src, int nclip, int T, int pad, co
         a.zconst = reinterpret_cast<const f16*>(zscratch);
         if (!fill_all) a.fill_partial = 1;
     }
-    static unsigned long long* tl = nullptr;
-    static const bool want_tl = getenv("JG_CONV1_TL") != nullptr;
-    if (want_tl && !tl && hipHostMalloc(&tl, 4096 * sizeof(unsigned long long), hipHostMallocMapped) != hipSuccess) tl = nullptr;
-    a.tl = tl;
-    if (tl) {
-        (void)hipStreamSynchronize(s);
-        std::memset(tl, 0, 4096 * sizeof(unsigned long long));
-    }
     if (a.nstrips <= 0) return hipSuccess;
     const unsigned grid = (unsigned)(a.nstrips < num_cu ? a.nstrips : num_cu);
-    // (the timeline / ablation build exists for the 32x32x16 form only)
-    if (a.dbg || a.tl) hipLaunchKernelGGL((conv1_direct_kernel<true, false>), dim3(grid), dim3(512), LDS_BYTES, s, a);
-    else if (o.conv1_mfma16) hipLaunchKernelGGL((conv1_direct_kernel<false, true>), dim3(grid), dim3(512), LDS_BYTES, s, a);
-    else hipLaunchKernelGGL((conv1_direct_kernel<false, false>), dim3(grid), dim3(512), LDS_BYTES, s, a);
-    if (tl) {
-        (void)hipStreamSynchronize(s);
-        // MFMA wave 0: per tile [arrive, pass]; loader wave 4: per tile [arrive, pass, loads issued, pooled]
-        double wait = 0, work = 0; int n = 0;
-        for (int i = 0; i + 2 < 2000 && tl[i + 2]; i += 2, ++n) { wait += (tl[i + 1] - tl[i]) * 0.01; work += (tl[i + 2] - tl[i + 1]) * 0.01; }
-        if (n) std::fprintf(stderr, "[conv1 timeline] MFMA wave: %d tiles, barrier wait %.2f us, MFMA+epilogue %.2f us per tile\n", n, wait / n, work / n);
-        double w2 = 0, is = 0, po = 0, cv = 0; n = 0;
-        const unsigned long long* q = tl + 2048;
-        for (int i = 0; i + 4 < 2000 && q[i + 4]; i += 4, ++n) {
-            w2 += (q[i + 1] - q[i]) * 0.01; is += (q[i + 2] - q[i + 1]) * 0.01; po += (q[i + 3] - q[i + 2]) * 0.01; cv += (q[i + 4] - q[i + 3]) * 0.01;
-        }
-        if (n) std::fprintf(stderr, "[conv1 timeline] loader wave: %d tiles, barrier wait %.2f us, convert+fill %.2f us, issue loads %.2f us, pool %.2f us per tile\n", n, w2 / n, is / n, po / n, cv / n);
-    }
+    if (o.conv1_mfma16) hipLaunchKernelGGL((conv1_direct_kernel<true>), dim3(grid), dim3(512), LDS_BYTES, s, a);
+    else hipLaunchKernelGGL((conv1_direct_kernel<false>), dim3(grid), dim3(512), LDS_BYTES, s, a);
     return hipGetLastError();
 }
 

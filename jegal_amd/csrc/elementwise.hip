@@ -144,13 +144,12 @@ __global__ void window_gather_kernel(const float* __restrict__ conv, const float
     }
 }
 
-// Tiled variant (token stream of the fused GEMM+LayerNorm kernel, layouts and res_enc in common.h; x32 is the 8-bit
-// correction plane): one wave per 16-row x 64-column block, lane = (column quad ng, row m15) exactly as in the LN epilogue
-// of gemm_glds_kernel -- a lane holds columns 16q + 4ng .. +3 (q = 0..3) of its row, so every store instruction of the wave
-// covers a contiguous 512 B (fp16 plane, one per q) or 1 KB (correction plane).  (The element-per-thread kernel above wrote
-// 32-byte pieces 512 B apart: 67 us for the 155 MB of a 32-clip chunk.)
+// Tiled variant (token stream of the fused GEMM+LayerNorm kernel, layout in common.h): one wave per 16-row x 64-column
+// block, lane = (column quad ng, row m15) exactly as in the LN epilogue of gemm_glds_kernel -- a lane holds columns
+// 16q + 4ng .. +3 (q = 0..3) of its row, so every store instruction of the wave covers a contiguous 512 B (one per q).
+// (The element-per-thread kernel above wrote 32-byte pieces 512 B apart: 67 us for the 155 MB of a 32-clip chunk.)
 __global__ __launch_bounds__(256) void window_gather_tiled_kernel(const float* __restrict__ conv, const float* __restrict__ pe, int B, int P, int Twin,
-                                                                  int L, int shift, signed char* __restrict__ d8, f16* __restrict__ x16) {
+                                                                  int L, int shift, f16* __restrict__ x16) {
     const long M = (long)B * Twin * L;
     const long nblk = ((M + 15) >> 4) * 8;
     const long blk = blockIdx.x * 4L + (threadIdx.x >> 6);
@@ -173,28 +172,22 @@ __global__ __launch_bounds__(256) void window_gather_tiled_kernel(const float* _
     const float* src = conv + ((long)b * P + pp) * 512 + cb * 64 + 4 * ng;
     const float* pes = pe + (long)j * 512 + cb * 64 + 4 * ng;
     const long base = (rb >> 3) * 65536 + (long)cb * 8192 + (rb & 7) * 1024;
-    unsigned dq[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         f32x4 v = *reinterpret_cast<const f32x4*>(src + 16 * q);
         v += *reinterpret_cast<const f32x4*>(pes + 16 * q);
         const f16x4 h = {(f16)v.x, (f16)v.y, (f16)v.z, (f16)v.w};
         if (live) __builtin_nontemporal_store(h, reinterpret_cast<f16x4*>(x16 + base + q * 256 + m15 * 16 + 4 * ng));
-        if (d8) dq[q] = res_enc4(v.x, v.y, v.z, v.w, h[0], h[1], h[2], h[3]);
     }
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    // (d8 == nullptr: the token stream is the fp16 plane alone, option stream_fp16)
-    if (live && d8) __builtin_nontemporal_store(u32x4{dq[0], dq[1], dq[2], dq[3]}, reinterpret_cast<u32x4*>(d8 + base + lane * 16));
 }
 
-hipError_t launch_window_gather(const float* conv, const float* pe, int B, int P, int Twin, int L, int D, int shift, int tiled,
+hipError_t launch_window_gather(const float* conv, const float* pe, int B, int P, int Twin, int L, int D, int shift, bool tiled,
                                 float* x32, f16* x16, hipStream_t s) {
     if (tiled && D != 512) return hipErrorInvalidValue;
     if (tiled) {
         if ((long)B * Twin * L >= (1L << 31)) return hipErrorInvalidValue;
         const long nblk = (((long)B * Twin * L + 15) >> 4) * 8;
-        hipLaunchKernelGGL(window_gather_tiled_kernel, dim3((unsigned)((nblk + 3) / 4)), dim3(256), 0, s, conv, pe, B, P, Twin, L, shift,
-                           tiled == 2 ? nullptr : reinterpret_cast<signed char*>(x32), x16);          // tiled == 2: no correction plane
+        hipLaunchKernelGGL(window_gather_tiled_kernel, dim3((unsigned)((nblk + 3) / 4)), dim3(256), 0, s, conv, pe, B, P, Twin, L, shift, x16);
         return hipGetLastError();
     }
     const long total = (long)B * Twin * L * (D / 4);

@@ -229,7 +229,7 @@ template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_
 // MI = 16-row MFMA tiles per wave along m (4: 64x64 wave tile, 8: 128x64); WM x WN waves.
 //   <4,4,2>: 256x128 block tile (hi+lo weights fit two LDS stages);  <8,2,4>: 256x256 block tile for single-fp16
 //   weights -- 1.5x fewer L2->LDS bytes per FLOP, which is what bounds the 256x128 kernel once the lo MFMAs are gone.
-// LNF: row-wide 128x512 tile with the residual add and the LayerNorm in the epilogue (tiled fp16 + 8-bit token stream).
+// LNF: row-wide 128x512 tile with the residual add and the LayerNorm in the epilogue (tiled fp16 token stream).
 // SPR: plain GEMM -- the next k-tile's DMA pieces are spread over the MFMA schedule (K <= 1024 instances);
 //      CONV -- the loader can read the producer's left-out leading rows from a const image (ConvGeom::in_op / const_in).
 // Every CONV instance honours ConvGeom::rowmap on its output side (compacted row index, row_full()).
@@ -241,7 +241,7 @@ template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_
 //      is then TWO taps x 32 channels, so a lane's tap depends on which half of the 128-B row its 16-B chunk sits in (one select per
 //      piece); with WN = 1 (N = 64) every wave stages ONE weight piece.
 template <bool W2, bool CONV, int MI, int WM, int WN, bool LNF = false, bool SPR = false, int XE = 0, bool C32 = false>
-__global__ __launch_bounds__(512) void gemm_glds_kernel(GemmArgs a, int n_tiles, int total_tiles, const f16* zeros, int counted_ok, unsigned long long* tl) {
+__global__ __launch_bounds__(512) void gemm_glds_kernel(GemmArgs a, int n_tiles, int total_tiles, const f16* zeros, int counted_ok) {
     static_assert(WM * WN == 8, "8 waves");
     static_assert(!C32 || (CONV && !SPR && !W2), "C32: plain conv instance, single fp16 weights");
     static_assert(!LNF || (WM == 1 && !W2), "fused LayerNorm needs a row-wide tile: all 8 waves side by side along n");
@@ -465,44 +465,25 @@ src = xsrc[i] + ((!XE && a.a_tiled) ? (long)sk0 * 128 : (long)sk0);        // ti
         }
     }
     counted_ok &= 1;
-    // debug timeline (gemm_timeline option): wave 0 of workgroup 0 / G-1 stamps s_memrealtime at the phase edges
-    int tli = 0;
-    const bool tl_on = tl != nullptr && wave == 0 && (blockIdx.x == 0 || blockIdx.x == G - 1);
-    unsigned long long* tlp = tl + (blockIdx.x == 0 ? 0 : 512);
-    auto mark = [&]() {
-        if (tl_on && tli < 512) {
-            const unsigned long long c = wall_clock64();
-            if (lane == 0) tlp[tli] = c;
-            ++tli;
-        }
-    };
-    // LNF: the accumulators start from the residual.  The token stream is the tiled fp16 + 8-bit pair of common.h
-    // (res_dec / res_enc): its raw bits are loaded one tile ahead (4 x 8 B + 16 B per 16-row block and lane, every
-    // access a contiguous 512 B / 1 KB per wave instruction) and expanded to fp32 right before the k loop.
-    // The raw bits of a 16-row block (4 x 8 B of fp16, 16 B of corrections = 12 registers) are parked IN the 16
-    // accumulator registers of that block, which are dead between the block's stores and the next tile's k loop:
-    //   acc[0][j] = {x16 i=0 (2 regs), x16 i=3 (2 regs)},  acc[1][j].xy = x16 i=1,  acc[2][j].xy = x16 i=2,  acc[3][j] = d8.
+    // LNF: the accumulators start from the residual.  The token stream is the tiled fp16 plane of common.h: its raw bits
+    // are loaded one tile ahead (4 x 8 B per 16-row block and lane, every access a contiguous 512 B per wave instruction)
+    // and expanded to fp32 right before the k loop.
+    // The raw bits of a 16-row block (4 x 8 B of fp16 = 8 registers) are parked IN the 16 accumulator registers of that
+    // block, which are dead between the block's stores and the next tile's k loop:
+    //   acc[0][j] = {x16 i=0 (2 regs), x16 i=3 (2 regs)},  acc[1][j].xy = x16 i=1,  acc[2][j].xy = x16 i=2.
     // (As separate arrays hipcc spilled every loaded value to scratch right behind its load.)
     f32x4 acc[4][MI];
     auto x16t_off = [&](int tm0) -> long { return (long)(tm0 / BM) * 65536 + (long)wn * 8192 + frow * 16 + fq * 4; };     // + j*1024 + i*256
-    auto d8t_off = [&](int tm0) -> long { return (long)(tm0 / BM) * 65536 + (long)wn * 8192 + lane * 16; };               // + j*1024
     auto asf = [](unsigned v) -> float { return __builtin_bit_cast(float, v); };
     auto load_stream = [&](int tm0, int j) __attribute__((always_inline)) {
         const f16* xp = a.res16 + x16t_off(tm0) + j * 1024;
         typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-        typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
         // read-once stream: nontemporal, so it does not push the weights out of L2
         const u32x2 r0 = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(xp)), r1 = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(xp + 256));
         const u32x2 r2 = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(xp + 512)), r3 = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(xp + 768));
-        // res8 == nullptr (option stream_fp16 = 1, the default since round 5): the token stream is the fp16 plane alone -- in a post-norm transformer the
-        // LayerNorm output is rounded to fp16 as the next GEMM's operand anyway, and carrying the residual at that precision costs
-        // 1-5 % of the feature error (oracle/precision_families.py) for a third fewer stream bytes and no codec arithmetic
-        u32x4 dq = {0u, 0u, 0u, 0u};
-        if (a.res8) dq = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(a.res8 + d8t_off(tm0) + j * 1024));
         acc[0][j] = f32x4{asf(r0.x), asf(r0.y), asf(r3.x), asf(r3.y)};
         acc[1][j] = f32x4{asf(r1.x), asf(r1.y), 0.f, 0.f};
         acc[2][j] = f32x4{asf(r2.x), asf(r2.y), 0.f, 0.f};
-        acc[3][j] = f32x4{asf(dq.x), asf(dq.y), asf(dq.z), asf(dq.w)};
     };
     if constexpr (LNF) {
 #pragma unroll
@@ -524,11 +505,9 @@ src = xsrc[i] + ((!XE && a.a_tiled) ? (long)sk0 * 128 : (long)sk0);        // ti
             case 40: wait_vmcnt<40>(); break;
             case 48: wait_vmcnt<48>(); break;
             case 56: wait_vmcnt<56>(); break;
-            case 60: wait_vmcnt<60>(); break;
             default: wait_vmcnt<0>(); break;
         }
         __builtin_amdgcn_s_barrier();
-        mark();     // 0: tile start (first k-tile landed)
         const int cn0 = n0, cm0 = m0;
         // interior: the fast epilogues apply.  A tile that is only partial along M (the last row tile: M = 4800 is 18.75 tiles of
         // 256 rows) takes them too, with its stores masked by row (m_full false): the generic per-element path below costs such a
@@ -552,15 +531,18 @@ src = xsrc[i] + ((!XE && a.a_tiled) ? (long)sk0 * 128 : (long)sk0);        // ti
             }
 
         if constexpr (LNF) {
-            // expand the parked token-stream bits of this tile into fp32 accumulators (res_dec4, common.h)
-            auto asu = [](float v) -> unsigned { return __builtin_bit_cast(unsigned, v); };
+            // expand the parked fp16 bits of this tile into fp32 accumulators (from acc[3] down: 229 instead of 246 VGPRs)
+            auto unpack = [](float lo, float hi) -> f32x4 {
+                const f16x2 p = __builtin_bit_cast(f16x2, lo), q = __builtin_bit_cast(f16x2, hi);
+                return f32x4{(float)p.x, (float)p.y, (float)q.x, (float)q.y};
+            };
 #pragma unroll
             for (int j = 0; j < MI; ++j) {
-                const f32x4 a0 = acc[0][j], a1 = acc[1][j], a2 = acc[2][j], a3 = acc[3][j];
-                const unsigned xw[4][2] = {{asu(a0.x), asu(a0.y)}, {asu(a1.x), asu(a1.y)}, {asu(a2.x), asu(a2.y)}, {asu(a0.z), asu(a0.w)}};
-                const unsigned dw[4] = {asu(a3.x), asu(a3.y), asu(a3.z), asu(a3.w)};
-#pragma unroll
-                for (int i = 0; i < 4; ++i) acc[i][j] = res_dec4(xw[i][0], xw[i][1], dw[i]);
+                const f32x4 a0 = acc[0][j], a1 = acc[1][j], a2 = acc[2][j];
+                acc[3][j] = unpack(a0.z, a0.w);
+                acc[2][j] = unpack(a2.x, a2.y);
+                acc[1][j] = unpack(a1.x, a1.y);
+                acc[0][j] = unpack(a0.x, a0.y);
             }
         }
         // LNF: this tile's bias row(s) / gamma / beta -- one element per thread (BN == 512 threads), loaded under the LAST k-tile's MFMAs
@@ -646,7 +628,6 @@ src = xsrc[i] + ((!XE && a.a_tiled) ? (long)sk0 * 128 : (long)sk0);        // ti
             __syncthreads();     // drains the LDS-DMA of tile kt+1 (vmcnt(0)) and fences the reads of tile kt
         }
 
-        mark();     // 1: k loop done
         // fp16-only outputs (qkv, linear1, the conv layers) leave through the row-transposing epilogue below
         constexpr int TP16 = 144;                        // row pitch: 16-B aligned, 36 banks -> conflict-free b64 writes
         constexpr bool ROWS_OK = STAGE / 8 >= 16 * TP16;
@@ -685,14 +666,13 @@ src = xsrc[i] + ((!XE && a.a_tiled) ? (long)sk0 * 128 : (long)sk0);        // ti
         __builtin_amdgcn_sched_barrier(0);
         if (nbid >= 0 && !LNF) stage(0, 0);
         __builtin_amdgcn_sched_barrier(0);       // keep the DMA older than the stores (the counted wait relies on it)
-        if (!LNF) mark();     // 2: next tile's first DMA issued (LNF: statistics done, see below)
 
         if constexpr (LNF) {
             // ---- fused residual + LayerNorm epilogue (gestsync.py:20: LN(x + sublayer(x)), eps 1e-5).
             // The tile spans the whole row (BN == N == 512, wave wn owns columns wn*64..+63): row statistics are a
             // shuffle over the 4 lanes of a row inside the wave plus an 8-way exchange through LDS (stage 1 is idle
             // here).  Two-pass (mean, then centred variance) like nn.LayerNorm.
-            // Input and output token stream: the tiled fp16 + 8-bit pair (common.h) in this kernel's own fragment
+            // Input and output token stream: the tiled fp16 plane (common.h) in this kernel's own fragment
             // order, normally in place.  As soon as the 16-row block j of this tile has been stored, the raw bits of
             // block j of the NEXT tile are loaded (no spare registers are needed for a whole tile of residual, the
             // HBM latency hides behind the rest of the epilogue); that tile's first DMA goes in front of block JD and
@@ -751,9 +731,7 @@ src = xsrc[i] + ((!XE && a.a_tiled) ? (long)sk0 * 128 : (long)sk0);        // ti
                 for (int j = 0; j < MI; ++j) red[(8 + wn) * BM + j * 16 + frow] = rsq[j];
             }
             __syncthreads();
-            mark();     // 2 (LNF): row statistics done, the store / reload phase starts
             f16* o16 = a.out16 + x16t_off(cm0);
-            signed char* o8 = a.out8 ? a.out8 + d8t_off(cm0) : nullptr;
 #pragma unroll
             for (int j = 0; j < MI; ++j) {
                 if (j == JD) {
@@ -766,25 +744,18 @@ src = xsrc[i] + ((!XE && a.a_tiled) ? (long)sk0 * 128 : (long)sk0);        // ti
                 for (int w = 0; w < 8; ++w) tq += red[(8 + w) * BM + j * 16 + frow];
                 const float inv = a.ln_flavour == LN_STD ? 1.f / sqrtf(tq * (1.f / BN) + 1e-5f)
                                                          : 1.f / (sqrtf(tq * (1.f / (BN - 1))) + 1e-6f);
-                uint4 dq;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     const f32x4 y = acc[i][j] * inv * *reinterpret_cast<const f32x4*>(lnp + BN + ncol + i * 16) +
                                     *reinterpret_cast<const f32x4*>(lnp + 2 * BN + ncol + i * 16);
                     const f16x4 hv = {(f16)y.x, (f16)y.y, (f16)y.z, (f16)y.w};
                     *reinterpret_cast<f16x4*>(o16 + j * 1024 + i * 256) = hv;
-                    if (o8) {
-                        const unsigned dw = res_enc4(y.x, y.y, y.z, y.w, hv[0], hv[1], hv[2], hv[3]);
-                        if (i == 0) dq.x = dw; else if (i == 1) dq.y = dw; else if (i == 2) dq.z = dw; else dq.w = dw;
-                    }
                 }
-                if (o8) *reinterpret_cast<uint4*>(o8 + j * 1024) = dq;
                 if (nbid >= 0) load_stream(m0, j);                        // m0 is already the next tile's
             }
-            mark();     // 3: epilogue issued
             if (nbid < 0) break;
             // the loop-top barrier fences red[] / lnp[] against the next tile's k-tile 1 (staged after it)
-            pending = counted_ok ? (MI - JD) * (o8 ? 10 : 8) : 0;
+            pending = counted_ok ? (MI - JD) * 8 : 0;
             continue;
         }
         // ---- epilogue: lane holds D[n = 4*fq + r][m = frow] of each 16x16 tile.
@@ -794,7 +765,7 @@ src = xsrc[i] + ((!XE && a.a_tiled) ? (long)sk0 * 128 : (long)sk0);        // ti
         // fp16-only outputs (qkv, linear1, the conv layers): transpose the tile through LDS so that every store
         // instruction writes 8 rows x 128 contiguous bytes.  In the MFMA fragment layout a store instruction covers
         // 16 rows x 32 B, and the CU's write path retires those at ~17 GB/s: 8-9 us per 256x256 tile, as long as the
-        // whole k loop at K = 512 (tools/store_pattern.hip, tools/gemm_timeline.py).  The scratch is this wave's
+        // whole k loop at K = 512 (tools/store_pattern.hip, profiles/r5_gemm_timeline.txt).  The scratch is this wave's
         // slice of LDS stage 1, idle until the next tile's k-tile 1 is staged (after the barrier at the loop top);
         // a wave's LDS instructions execute in order, so consecutive 16-row blocks reuse the same 2.3 KB.
         constexpr bool xdone = XE == 2;
@@ -1055,7 +1026,6 @@ src = xsrc[i] + ((!XE && a.a_tiled) ? (long)sk0 * 128 : (long)sk0);        // ti
                 }
             }
         }
-        mark();     // 3: epilogue issued
         if (nbid < 0) break;
         pending = !(interior && m_full && counted_ok) || xdone ? 0 : rows16 ? 2 * MI : (a.out32 ? 4 * MI : 0) + (a.out16 ? 4 * MI : 0);
     }
@@ -1070,26 +1040,6 @@ src = xsrc[i] + ((!XE && a.a_tiled) ? (long)sk0 * 128 : (long)sk0);        // ti
 // ---- host side.  Every tuning switch and per-device resource lives in the caller's EngineOpts (one per jg_handle):
 // nothing here is process-global except the "dynamic LDS attribute set" flags, which are per (kernel, device).
 constexpr int MAX_DEV = 64;
-
-void engine_opts_set_timeline(EngineOpts& o, bool on) {
-    if (on && !o.gemm_tl) {
-        if (hipHostMalloc(&o.gemm_tl, 1024 * sizeof(unsigned long long), hipHostMallocMapped) != hipSuccess) o.gemm_tl = nullptr;
-    } else if (!on && o.gemm_tl) {
-        (void)hipHostFree(o.gemm_tl);
-        o.gemm_tl = nullptr;
-    }
-}
-static void dump_timeline(const EngineOpts& o, hipStream_t s, const char* what) {
-    (void)hipStreamSynchronize(s);
-    for (int b = 0; b < 2; ++b) {
-        const unsigned long long* t = o.gemm_tl + b * 512;
-        std::fprintf(stderr, "[gemm timeline %s wg %s] (100 MHz ticks -> us)\n", what, b ? "last" : "0");
-        for (int i = 0; i + 3 < 512 && t[i + 3]; i += 4) {
-            std::fprintf(stderr, "  tile %2d: kloop %6.2f  setup+dma-issue %5.2f  epilogue %5.2f  wait-next %5.2f\n", i / 4, (t[i + 1] - t[i]) * 0.01,
-                         (t[i + 2] - t[i + 1]) * 0.01, (t[i + 3] - t[i + 2]) * 0.01, t[i + 4] ? (t[i + 4] - t[i + 3]) * 0.01 : 0.0);
-        }
-    }
-}
 
 hipError_t engine_opts_init(EngineOpts& o, int device) {
     o.device = device;
@@ -1109,7 +1059,6 @@ hipError_t engine_opts_init(EngineOpts& o, int device) {
 void engine_opts_release(EngineOpts& o) {
     if (o.zeros) (void)hipFree(const_cast<f16*>(o.zeros));
     o.zeros = nullptr;
-    engine_opts_set_timeline(o, false);
 }
 
 template <class K>
@@ -1134,10 +1083,6 @@ static hipError_t launch_glds_cfg(const GemmArgs& a, const EngineOpts& o, hipStr
     const int mt = (a.M + BM - 1) / BM, nt = (a.N + BN - 1) / BN;
     const int tiles = mt * nt;
     const int grid = o.gemm_persistent ? (tiles < o.num_cu ? tiles : o.num_cu) : tiles;
-    if (o.gemm_tl) {
-        (void)hipStreamSynchronize(s);
-        std::memset(o.gemm_tl, 0, 1024 * sizeof(unsigned long long));
-    }
     // De-phasing the workgroups (4 phases, 2 us apart; the last phase falls on the workgroups that run one tile fewer):
     // once the outputs were nontemporal the epilogues became HBM-write-burst bound (every CU stores its 128 KB at the
     // same moment) and spreading them pays: qkv 157 -> 146 us.  Only for long plain GEMMs (>= 4 rounds); the LN-fused
@@ -1151,8 +1096,7 @@ static hipError_t launch_glds_cfg(const GemmArgs& a, const EngineOpts& o, hipStr
                         : (!CONV && !o.lanes_active && tiles > o.num_cu && 2 * last_round < o.num_cu ? 300 : 0);
     record_kernel(o.kname, "gemm_glds_kernel<%d,%d,%d,%d,%d,0,%d,%d,%d>", (int)W2, (int)CONV, MI, WM, WN, (int)SPR, XE, (int)C32);
     hipLaunchKernelGGL((gemm_glds_kernel<W2, CONV, MI, WM, WN, false, SPR, XE, C32>), dim3((unsigned)grid), dim3(512), lds, s, a, nt, tiles, o.zeros,
-                       o.gemm_counted | (stagger << 8), o.gemm_tl);
-    if (o.gemm_tl) dump_timeline(o, s, CONV ? "conv" : "linear");
+                       o.gemm_counted | (stagger << 8));
     return hipGetLastError();
 }
 
@@ -1165,10 +1109,6 @@ static hipError_t launch_glds_ln(const GemmArgs& a, const EngineOpts& o, hipStre
     if (!o.zeros) return hipErrorInvalidValue;
     const int tiles = (a.M + 127) / 128;
     const int grid = tiles < o.num_cu ? tiles : o.num_cu;
-    if (o.gemm_tl) {
-        (void)hipStreamSynchronize(s);
-        std::memset(o.gemm_tl, 0, 1024 * sizeof(unsigned long long));
-    }
     // De-phasing (see launch_glds_cfg), round 3: in this kernel every workgroup reaches its store / reload phase at the same moment
     // and that phase is an HBM burst (100 MB per round in ~10 us) while the k loops leave HBM idle.  Four start phases spread it;
     // the delay is free when the last round is less than half full, because the highest block ids - the ones delayed longest -
@@ -1179,14 +1119,13 @@ static hipError_t launch_glds_ln(const GemmArgs& a, const EngineOpts& o, hipStre
     const int stagger = o.gemm_stagger < 0 ? 0 : o.gemm_stagger > 0 ? o.gemm_stagger : auto_stagger;
     record_kernel(o.kname, "gemm_glds_kernel<0,%d,8,1,8,1,0,0,0>", (int)CONV);
     hipLaunchKernelGGL((gemm_glds_kernel<false, CONV, 8, 1, 8, true>), dim3((unsigned)grid), dim3(512), lds, s, a, 1, tiles, o.zeros,
-                       o.gemm_counted | (stagger << 8), o.gemm_tl);
-    if (o.gemm_tl) dump_timeline(o, s, "linear+LN");
+                       o.gemm_counted | (stagger << 8));
     return hipGetLastError();
 }
 
 bool gemm_ln_fusable(const GemmArgs& a) {
     return a.Wl == nullptr && a.N == 512 && a.K % 64 == 0 && a.M >= 1024 && a.lda % 8 == 0 && a.ldw % 8 == 0 && !a.relu && !a.scale &&
-           !a.res && !a.out32 && a.res16 && a.out16 && (a.res8 != nullptr) == (a.out8 != nullptr) && !a.a_tiled;
+           !a.res && !a.out32 && a.res16 && a.out16 && !a.a_tiled;
 }
 
 template <bool W2, bool CONV>

@@ -227,9 +227,9 @@ def test_audit_full_length_clip_vs_oracle(fp32, oracle_sd):
 
 
 def test_split_operand_options_reduce_the_error(oracle_sd):
-    """Options jegal_fp32_ends (default on) and jegal_ffn_x3 (default off: +3 % step time) move GEMMs of the JEGAL branch to fp32 activations on
-    the split-operand kernel; conv_round_diffuse (default on) rounds conv weights with error diffusion across the taps.  Each must stay
-    inside the contract and the more exact arrangement must not be worse (T = 64, two clips; DESIGN.md section 3 has the T = 150 table)."""
+    """Option jegal_fp32_ends (default on) moves GEMMs of the JEGAL branch to fp32 activations on the split-operand kernel;
+    conv_round_diffuse (default on) rounds conv weights with error diffusion across the taps.  Each must stay inside the contract and
+    the more exact arrangement must not be worse (T = 64, two clips; DESIGN.md section 3 has the T = 150 table)."""
     from jegal_amd._lib import Engine, PREC_FP16_RC
     from jegal_amd.gestsync import GestSync
     from jegal_amd.jegal import JEGAL
@@ -243,7 +243,7 @@ def test_split_operand_options_reduce_the_error(oracle_sd):
             f = O.gestsync_clip_feats(gsd, torch.from_numpy(frames[b].astype(np.float32) / np.float32(255.0)))
             refs.append(O.l2_normalize(O.jegal_forward_inference(jsd, visual_feats=f[None], visual_mask=torch.ones(1, T))[0]).numpy())
     errs = {}
-    for tag, opts in (("round5", {"jegal_fp32_ends": 0, "conv_round_diffuse": 0}), ("default", {}), ("ffn_x3", {"jegal_ffn_x3": 1})):
+    for tag, opts in (("round5", {"jegal_fp32_ends": 0, "conv_round_diffuse": 0}), ("default", {})):
         e = Engine(0, precision=PREC_FP16_RC)
         try:
             for k, v in opts.items():
@@ -255,4 +255,4 @@ def test_split_operand_options_reduce_the_error(oracle_sd):
             e.close()
         errs[tag] = max(rel(emb[b], refs[b]) for b in range(B))
     print("\ngesture rel-L2 (T = 64): " + "  ".join(f"{k} {v:.2e}" for k, v in errs.items()), end="")
-    assert errs["round5"] < 1e-3 and errs["default"] < 0.8 * errs["round5"] and errs["ffn_x3"] < 0.9 * errs["default"], errs
+    assert errs["round5"] < 1e-3 and errs["default"] < 0.8 * errs["round5"], errs

@@ -254,8 +254,8 @@ GEMM_CASES = [
 ]
 
 
-def ln_fused_case(M, stream8, clip=None, seed=1):
-    """Residual + LayerNorm fused (N = 512): the token planes in the tiled order of common.h, built here from that description."""
+def ln_fused_case(M, clip=None, seed=1):
+    """Residual + LayerNorm fused (N = 512): the token plane in the tiled order of common.h, built here from that description."""
     N, K = 512, 512
     g = torch.Generator().manual_seed(seed)
     e = engine()
@@ -267,9 +267,7 @@ def ln_fused_case(M, stream8, clip=None, seed=1):
     m = np.arange(R * 128)[:, None]
     n = np.arange(N)[None, :]
     off16 = (m >> 7) * 65536 + (n >> 6) * 8192 + ((m & 127) >> 4) * 1024 + ((n & 63) >> 4) * 256 + (m & 15) * 16 + (n & 15)
-    lane = ((n & 15) >> 2) * 16 + (m & 15)
-    off8 = (m >> 7) * 65536 + (n >> 6) * 8192 + ((m & 127) >> 4) * 1024 + lane * 16 + ((n & 63) >> 4) * 4 + (n & 3)
-    assert np.unique(off16).size == off16.size == R * 65536 and np.unique(off8).size == R * 65536
+    assert np.unique(off16).size == off16.size == R * 65536
     r16 = urnd(g, (R * 128, N), -2, 2).half()
     r16[M:] = float("nan")                                   # rows past M in the last tile: read, never part of a valid row
     res = r16.double()
@@ -278,16 +276,6 @@ def ln_fused_case(M, stream8, clip=None, seed=1):
     plane16[R * 65536:] = float("nan")
     kw = dict(A=operand(a, K, torch.float16), lda=K, Wh=operand(wh, K, torch.float16), ldw=K, M=M, N=N, K=K, bias=bias.to(DEV),
               ln_w=gam.to(DEV), ln_b=bet.to(DEV), res16=plane16.to(DEV))
-    if stream8:
-        codes = torch.randint(0, 256, (R * 128, N), generator=g, dtype=torch.uint8)
-        codes[(codes & 0x7F) == 0x7F] = 0                    # no e4m3 NaN
-        c = codes.view(torch.float8_e4m3fn).double()
-        res = res + c * 2.0 ** -13
-        p8 = torch.zeros(R * 65536 + 65536, dtype=torch.uint8)
-        p8[torch.from_numpy(off8.ravel())] = codes.ravel()
-        kw["res8"] = p8.to(DEV)
-        out8 = torch.full((R * 65536 + 65536,), 0x5A, dtype=torch.uint8, device=DEV)
-        kw["out8"] = out8
     out16 = torch.full((R * 65536 + 65536,), SENT16, dtype=torch.int16, device=DEV).view(torch.float16)
     kw["out16"] = out16
     rows = torch.arange(M)
@@ -318,19 +306,10 @@ def ln_fused_case(M, stream8, clip=None, seed=1):
     fails = []
     if not bool((o16.view(torch.int16)[R * 65536:] == SENT16).all()):
         fails.append("ln_fused: guard tile of out16 overwritten")
-    if stream8:
-        o8 = out8.cpu()
-        c8 = o8[torch.from_numpy(off8[:M].ravel())].view(M, N).view(torch.float8_e4m3fn).double()
-        y8 = got + c8 * 2.0 ** -13
-        # the correction byte keeps 4 significant bits of y - fp16(y) (|.| <= ulp/2): 2^-5 ulp, or the e4m3 subnormal step 2^-22
-        r8 = float(((y8 - y).abs() / (ey + ulp16(y) * 2.0 ** -4 + 2.0 ** -21)).max())
-        ratio = max(ratio, r8)
-        if not bool((o8[R * 65536:] == 0x5A).all()):
-            fails.append("ln_fused: guard tile of out8 overwritten")
     note("ln_fused", ratio)
-    print(f"ln_fused M={M} stream8={stream8} clip={clip} {kname} observed/bound {ratio:.3f}")
+    print(f"ln_fused M={M} clip={clip} {kname} observed/bound {ratio:.3f}")
     if ratio > 1:
-        fails.append(f"ln_fused M={M} stream8={stream8} clip={clip}: observed/bound {ratio:.3f}")
+        fails.append(f"ln_fused M={M} clip={clip}: observed/bound {ratio:.3f}")
     return fails
 
 
@@ -407,8 +386,8 @@ def test_linear_gemm_kernels_vs_fp64_and_instance_coverage():
     fails = []
     for name, M, N, K, kw in GEMM_CASES:
         fails += gemm_case(name, M, N, K, **kw)
-    for M, s8, clip in ((1029, False, None), (1029, True, None), (1153, False, (300, 3)), (1100, True, (256, 4))):
-        fails += ln_fused_case(M, s8, clip)
+    for M, clip in ((1029, None), (1153, (300, 3)), (1100, (256, 4))):
+        fails += ln_fused_case(M, clip)
     for mode in (1, 2):
         for w2, tile in ((True, 1), (True, 2), (False, 1), (False, 3)):
             fails += implicit_ln_case(mode, 257, 512, 512, w2, tile)
@@ -515,8 +494,8 @@ def test_gemm_x3_vs_fp64():
 # an ABSOLUTE quantum of 2^-24 (error <= 2^-25 per element), so the norm-wise error of a row is ~2^-25 / rms(a): within the 2 sqrt(K) u
 # bound while the rows' rms is >= ~2^-7 at K = 512; |a| >= 65520 overflows the hi half.
 # The activations at the engine's gemm_x3 call sites (proj_ip_rgb on the GestSync features, the LayerNorm / ReLU outputs in front of
-# proj_ip_rgb.3, proj_op_rgb, proj_op_text and the align MLPs, the fusion / align MLPs of the content path, and the encoder feed-forward
-# Linears of option jegal_ffn_x3), measured on the CPU oracle over the six weight families by tools/x3_operand_range.py
+# proj_ip_rgb.3, proj_op_rgb, proj_op_text and the align MLPs, the fusion / align MLPs of the content path; the measured set also
+# takes in the encoder feed-forward Linears as a wider envelope), measured on the CPU oracle over the six weight families by tools/x3_operand_range.py
 # (profiles/x3_operand_range.json): per-row rms 0.69 .. ~9, max |a| 42.3; the split itself costs at most 0.018 of the bound there.
 # The grid below -- uniform operands in +-2^s, row rms 2^s / sqrt 3 -- spans rms 0.009 .. 591 and |a| up to 1024, i.e. that range with
 # margin on both sides, and holds the kernel to the fp32 bound over all of it.  No pre-scale of the split is needed at these call sites.

@@ -69,7 +69,7 @@ def test_rc_result_of_a_clip_does_not_depend_on_the_batch(rc):
         rc.set_option("dual_stream", 1)
 
 
-@pytest.mark.parametrize("opt", ["fuse_ln", "gemm_glds", "qkv0_linear", "stream_fp16", "gemm_big_tile", "dual_stream"])
+@pytest.mark.parametrize("opt", ["fuse_ln", "gemm_glds", "qkv0_linear", "gemm_big_tile", "dual_stream"])
 def test_rc_options_fall_back_to_hi_lo_or_stay_within_tolerance(rc, opt):
     """Where the per-clip epilogue is not available (unfused LayerNorm, register-staged GEMM) the run-time corrected layers run hi+lo:
     never single fp16 without its correction."""

@@ -1,4 +1,4 @@
-"""Activation range at the split-operand GEMM's call sites (gemm_x3, option jegal_fp32_ends / jegal_ffn_x3), on the CPU oracle.
+"""Activation range at the split-operand GEMM's call sites (gemm_x3, option jegal_fp32_ends), on the CPU oracle.
 
 gemm_x3 splits its fp32 A in the loader as hi = fp16(a), lo = fp16(a - hi).  Below |a| ~ 2^-3 the lo half is an fp16 subnormal with an
 absolute quantum of 2^-24, so how close the split is to fp32 depends on the activations' scale.  This tool runs the oracle's JEGAL
@@ -28,7 +28,7 @@ from jegal_amd import synth  # noqa: E402
 
 FAMILIES = [("gauss", 0), ("gauss", 1), ("gauss", 2), ("heavy", 0), ("sharp2", 0), ("sharp", 0)]
 # Linears on gemm_x3 in the fp16 modes (api.hip: jegal_input32 / jegal_tail32 / jegal_text_impl / fuse_content_impl); the encoder
-# feed-forward ones only with option jegal_ffn_x3 (default 0)
+# feed-forward ones are not, and are measured as a wider envelope (rows marked ffn_x3_only, summary "with_ffn")
 X3_SITES = ["proj_ip_rgb.0", "proj_ip_rgb.3", "proj_op_rgb", "proj_op_align_gesture.0", "proj_op_align_gesture.2", "proj_op_text",
             "proj_op_fusion_content.0", "proj_op_fusion_content.2", "proj_op_align_content.0", "proj_op_align_content.2"]
 FFN_SITES = [f"encoder_rgb.layers.{l}.feed_forward.w_{i}" for l in range(6) for i in (1, 2)]
