@@ -4,15 +4,21 @@ Workload (BASELINE.json configs[1]): per GPU a batch of 32 s
 150 frames x 270x480x3 uint8 (face rows zeroed), resident in HBM; one step = frames -> GestSync
 (conv stack de-duplicated over windows, transformer, ff_vid, mean) -> JEGAL gesture encoder ->
 align MLP -> L2-normalise -> (32,150,512).  Weak scaling: every rank has its own 32 clips, no
-collective on the data path.  After the timed loop every rank takes part in ONE config-4 retrieval
-evaluation (seed-1237 gallery of 10 000 clips, queries sharded ceil(N/G) per rank, gallery assembled by an
-all-gather: RCCL over xGMI) whose R@K / MR must equal the single-rank result.
+collective on the data path.
 
 `value` is measured with the engine's default scheduling: every batch runs as two parts on two internal HIP streams
-(option dual_stream, bit-identical results).  The `roofline*` objects and `stage_ms_per_step` time the kernels on ONE stream
-(a kernel's roofline is a property of the kernel running alone); `single_stream` repeats the timed loop in that mode.
+(option dual_stream, bit-identical results).
 
-Usage: python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, --dump-outputs, the JSON line.  --full
+measures everything else after the timed loop, in the same process: the `roofline*` objects and `stage_ms_per_step` (HIP events
+around the kernels of steps on ONE stream: a kernel's roofline is a property of the kernel running alone), the secondary
+measurements (--no-extras leaves them out: live parity against the fp32 audit engine, dense / mask-jitter / sustained /
+`single_stream` loops, the config-4 retrieval evaluation -- seed-1237 gallery of 10 000 clips, queries sharded ceil(N/G) per rank,
+gallery assembled by an all-gather: RCCL over xGMI -- and config-5 spotting, whose results must equal the single-rank ones,
+config 3, the PCIe-inclusive legs, the other precision modes in fresh child processes) and the CPU baseline (--no-cpu-baseline
+leaves it out).
+
+Usage: python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full [--no-extras] [--no-cpu-baseline]]
   --dump-outputs DIR: rank 0 writes what the LAST timed step returned (the (clips,150,512) fp32 gesture embeddings) to
   DIR/gesture_embeddings.npy; the inputs are seeded, so two builds run with the same arguments can be compared output for output.
   N > 1 without a torchrun environment: this process starts N fresh rank processes itself (it makes no GPU
@@ -283,8 +289,10 @@ def main():
     ap.add_argument("--clips", type=int, default=CLIPS)
     ap.add_argument("--chunk", type=int, default=32)
     ap.add_argument("--precision", type=int, default=5, help="0 fp16, 1 hi+lo Linear weights, 2 hi+lo everywhere, 3 bias-corrected fp16 (opt-in: needs a calibration), 4 bf16 (reported mode: outside the 1e-3 contract), 5 run-time corrected fp16 (the library default: calibration-free), 6 fp32 audit mode (~50 clips/s: use --steps 2 --warmup 1)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary measurements (dense conv1, sustained loop, PCIe stream, retrieval)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed loop also measure the roofline / per-stage figures, the secondary measurements and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the secondary measurements (dense conv1, sustained loop, PCIe stream, retrieval)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL; gloo only for --oversubscribe)")
     ap.add_argument("--oversubscribe", action="store_true",
                     help="testing aid: allow more ranks than GPUs (ranks share devices round-robin; forces backend gloo; flagged in the output)")
@@ -383,7 +391,7 @@ def main():
     # the measurements below reuse `out`: keep the last timed step's result now
     timed_out = out.cpu().numpy() if args.dump_outputs and rank == 0 else None
 
-    # ---- per-kernel timing with HIP events on the launch stream (dominant kernel: conv1)
+    # ---- --full: per-kernel timing with HIP events on the launch stream (dominant kernel: conv1)
     # (1) the dominant kernel alone: only the conv1 launch carries events, the rest of the step runs back to back as in the
     # timed loop; (2) every launch bracketed, for the per-stage table (each bracket adds ~10 us of idle time around its launch).
     # Each block starts with untimed steps: the all-reduce / host work since the timed loop left the GPU idle for milliseconds,
@@ -410,13 +418,15 @@ def main():
         eng.set_option("dual_stream", 1 if dual else 0)
         return p
 
-    c1_ms, c1_n = profiled(only="conv1")["conv1"]
-    prof = profiled()
-    conv2_rows_skipped = eng.debug_conv2_rowskip()          # min over the positions, of 20 output rows ("conv2_row_skip", bit-identical)
-    conv_rows, conv_rows_full = eng.debug_conv_rows()       # output pixels conv2 .. conv5 computed / would compute without the skip
+    if args.full:
+        c1_ms, c1_n = profiled(only="conv1")["conv1"]
+        prof = profiled()
+        conv2_rows_skipped = eng.debug_conv2_rowskip()          # min over the positions, of 20 output rows ("conv2_row_skip", bit-identical)
+        conv_rows, conv_rows_full = eng.debug_conv_rows()       # output pixels conv2 .. conv5 computed / would compute without the skip
 
     extras = {}
-    if not args.no_extras and rank == 0 and args.precision != 6:
+    extras_on = args.full and not args.no_extras
+    if extras_on and rank == 0 and args.precision != 6:
         # Parity of THIS run's embeddings, measured live (round 6): two of the timed clips once more on a JG_PREC_FP32 audit engine (exact-fp32
         # MFMAs, fp32 activations: the reference's CPU arithmetic on the device, itself 1e-6 from the CPU oracle -- tests/test_gpu_audit_fp32.py,
         # and from the cpu_baseline port below on the same clips) and the rel-L2 / max-abs of the timed mode against it
@@ -441,7 +451,7 @@ def main():
                 e32.close()
         except Exception as exc:  # noqa: BLE001
             extras["audit"] = {"error": repr(exc)[:200]}
-    if not args.no_extras:
+    if extras_on:
         # the same step on frames with no zero rows (timing only): every conv1 tile is computed
         dense = torch.randint(0, 256, frames.shape, dtype=torch.uint8, device=dev)
         dprof = profiled(only="conv1", src=dense)
@@ -593,7 +603,7 @@ def main():
         # The same timed loop in the other precision treatments a driver can select: `value` is the calibration-FREE
         # run-time corrected mode (5: per-clip E[x] from the clip's own rows -- what the CLI drivers give a checkpoint they have never
         # seen); 3 = corrections folded into the biases by a calibration pass (the library default for the seeded weights), 1 = hi+lo
-        # Linear weights.  Each mode runs this very script in a FRESH child process (--no-extras: weights, warm-up, the timed loop, the
+        # Linear weights.  Each mode runs this very script in a FRESH child process (--full --no-extras: weights, warm-up, the timed loop, the
         # bracketed stage table): a second engine inside this process would share the runtime's hardware queues with the streams the
         # measurements above created, and its two lanes then serialise (measured: 13.8 ms instead of 11.9 for mode 3).
         if world == 1:
@@ -601,7 +611,7 @@ def main():
             for mode, name in ((5, "rc"), (3, "bc"), (1, "w2")):
                 if mode == args.precision:
                     continue
-                cmd = [sys.executable, os.path.abspath(__file__), "--precision", str(mode), "--no-extras", "--no-cpu-baseline", "--steps", str(args.steps),
+                cmd = [sys.executable, os.path.abspath(__file__), "--precision", str(mode), "--full", "--no-extras", "--no-cpu-baseline", "--steps", str(args.steps),
                        "--warmup", str(max(3, args.warmup)), "--clips", str(args.clips), "--chunk", str(args.chunk)]
                 for o in args.opt:
                     cmd += ["--opt", o]
@@ -619,72 +629,75 @@ def main():
     if rank == 0:
         clips_total = args.clips * world * args.steps
         value = clips_total / dt
-        c1_avg_s = (c1_ms / max(c1_n, 1)) * 1e-3
-        clips_per_launch = args.clips * nprof / max(c1_n, 1)
         zskip = not any(o.replace(" ", "") == "conv1_zero_skip=0" for o in args.opt)
-        exec_frac = CONV1_EXECUTED_TILE_FRACTION if zskip else 1.0
-        achieved = CONV1_GFLOP_PER_CLIP * exec_frac * clips_per_launch / c1_avg_s / 1e3 if c1_avg_s > 0 else 0.0
-        traffic, traffic_note = load_traffic()
-        # executed share of conv2 .. conv5: every position leaves out its own position-independent leading rows (ConvGeom::rowmap)
-        cfrac = [conv_rows[l] / conv_rows_full[l] if conv_rows_full[l] else 1.0 for l in range(4)]
-        layer_gflop = [CONV2_GFLOP_PER_CLIP, CONV3_GFLOP_PER_CLIP, CONV4_GFLOP_PER_CLIP, CONV5_GFLOP_PER_CLIP]
-        conv_rest_exec = CONV_REST_GFLOP_PER_CLIP - sum(g * (1.0 - f) for g, f in zip(layer_gflop, cfrac))
-        exec_gflop_clip = CONV1_GFLOP_PER_CLIP * exec_frac + conv_rest_exec + LINEAR_GFLOP_PER_CLIP
-        pooled_rows_written = 43 - 2 * max(int(conv2_rows_skipped or 0), 0) if zskip else 43
-        exec_bytes_launch = (FRAMES * 270 * 480 * 3 * exec_frac + 2 * POS_EXEC * pooled_rows_written * 78 * 64) * clips_per_launch
-        stage = {k: v[0] / nprof for k, v in prof.items()}
-        conv_ms = stage["conv1"] + stage["conv1_aux"] + stage["maxpool"] + stage["conv2-fc6+audio_cnn"] + stage["stack_frames"]
-        lin_ms = stage["gemm"] + stage["attention"] + stage["layernorm"]
         res = {
             "metric": "clips/sec (T=150 frames, 270x480) embedding extraction", "value": value, "unit": "clips/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
             "ms_per_step_per_rank": [round(v, 4) for v in per_rank_ms],
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "bf16" if args.precision == 4 else ("f32" if args.precision == 6 else "f16"),
-            "data": "synthetic",
+            "data": "synthetic", "full": args.full,
             "config": {"workload": "BASELINE configs[1]: synthetic batch=32 gesture-only (GestSync conv + JEGAL gesture encoder), "
                                    "uint8 150x270x480x3 clips resident in HBM, seeded synthetic weights",
                        "clips_per_gpu": args.clips, "frames": FRAMES, "precision_mode": args.precision, "chunk": args.chunk,
                        "conv1_zero_tile_skip": zskip, "dual_stream": dual,
                        "parallelism": f"clip-sharded x{world}, no data-path collective" + (" (OVERSUBSCRIBED: ranks share GPUs, gloo)" if oversub else "")},
-            "roofline": {"bound": "mfma", "kernel": "conv1_direct_kernel (u8 frames -> conv1+BN+ReLU+maxpool, 154 distinct positions/clip)",
-                         "achieved": achieved, "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": achieved / MFMA_PEAK_TFLOPS,
-                         "traffic": traffic * clips_per_launch / 32.0 if traffic else None, "traffic_note": traffic_note,
-                         # bytes the launch has to move for the work it EXECUTES: the frame rows of the executed input tiles (the all-zero
-                         # bands are read by the scan kernel, not by this one) + the pooled rows conv2 will read (conv2's row skip leaves
-                         # the first 2 x s2 pooled rows of every position unwritten); `traffic` / this >= 1 is the re-read / write amplification
-                         "algorithmic_bytes_per_launch": exec_bytes_launch,
-                         "algorithmic_bytes_per_launch_unskipped": CONV1_ALGO_BYTES_PER_CLIP * clips_per_launch,
-                         "traffic_over_algorithmic": (traffic * clips_per_launch / 32.0) / exec_bytes_launch if traffic else None,
-                         "hbm_frac_of_peak": exec_bytes_launch / c1_avg_s / 1e9 / HBM_PEAK_GBS if c1_avg_s > 0 else None,
-                         "launch_ms": c1_avg_s * 1e3, "launches_per_step": c1_n / nprof,
-                         "counters": load_sq_counters(),
-                         "executed_tile_fraction": exec_frac,
-                         "timing_note": "the kernel timed ALONE: these steps run on one stream (dual_stream=0, one launch = all clips); in the timed "
-                                        "loop the batch runs as two parts on two streams and its two conv1 launches share the CUs with the other part's kernels",
-                         "flops_note": "achieved = EXECUTED algorithmic FLOPs / launch time (HIP events on the launch stream, mean of "
-                                       f"{c1_n} launches): all-zero input tiles (the face-mask rows, 8 of 22 row tiles of the synthetic clips) are not counted",
-                         # whole path, priced consistently on executed work (154 positions, executed conv1 tiles)
-                         "whole_path": {"executed_gflop_per_clip": exec_gflop_clip,
-                                        "frac": value / world * exec_gflop_clip / 1e3 / MFMA_PEAK_TFLOPS}},
-            # SURVEY 8d asks for BOTH fractions on the conv extractor: algorithmic HBM bytes of the whole conv stack / its time
-            "roofline_conv_stack": {"bound": "mfma", "ms_per_step": conv_ms,
-                                    "mfma_frac": (CONV1_GFLOP_PER_CLIP * exec_frac + conv_rest_exec) * args.clips / max(conv_ms, 1e-9) / MFMA_PEAK_TFLOPS,
-                                    "conv2_rows_skipped_min": conv2_rows_skipped,
-                                    "computed_row_fraction": {f"conv{l + 2}": round(cfrac[l], 4) for l in range(4)},
-                                    "flops_note": "executed FLOPs: conv1 tiles over all-zero input and the leading conv2 .. conv5 output rows that do "
-                                                  "not depend on the position (read from images computed once per weight load) are not counted",
-                                    "algorithmic_bytes_per_step": CONV_ALGO_BYTES_PER_CLIP * args.clips,
-                                    "achieved_gbs": CONV_ALGO_BYTES_PER_CLIP * args.clips / max(conv_ms, 1e-9) / 1e6,
-                                    "hbm_frac": CONV_ALGO_BYTES_PER_CLIP * args.clips / max(conv_ms, 1e-9) / 1e6 / HBM_PEAK_GBS,
-                                    "note": "the conv stack is MFMA-bound (620 FLOP/B): the HBM fraction is reported because north_star asks for it, not because it is the roof"},
-            # attention + MLP blocks: every Linear GEMM, attention and LayerNorm launch of a step (algorithmic FLOPs only:
-            # the hi+lo weight split of precision mode 1 is NOT counted as work)
-            "roofline_linear_gemms": {"bound": "mfma", "kernel": "all Linear GEMM + attention + LayerNorm launches of one step",
-                                      "achieved": LINEAR_GFLOP_PER_CLIP * args.clips / max(lin_ms, 1e-9), "peak": MFMA_PEAK_TFLOPS,
-                                      "unit": "TFLOP/s", "frac": LINEAR_GFLOP_PER_CLIP * args.clips / max(lin_ms, 1e-9) / MFMA_PEAK_TFLOPS,
-                                      "ms_per_step": lin_ms, "gemm_only_ms": stage["gemm"], "launches_per_step": prof["gemm"][1] / nprof},
-            "stage_ms_per_step": {k: round(v, 3) for k, v in stage.items()},
         }
+        if args.full:
+            c1_avg_s = (c1_ms / max(c1_n, 1)) * 1e-3
+            clips_per_launch = args.clips * nprof / max(c1_n, 1)
+            exec_frac = CONV1_EXECUTED_TILE_FRACTION if zskip else 1.0
+            achieved = CONV1_GFLOP_PER_CLIP * exec_frac * clips_per_launch / c1_avg_s / 1e3 if c1_avg_s > 0 else 0.0
+            traffic, traffic_note = load_traffic()
+            # executed share of conv2 .. conv5: every position leaves out its own position-independent leading rows (ConvGeom::rowmap)
+            cfrac = [conv_rows[l] / conv_rows_full[l] if conv_rows_full[l] else 1.0 for l in range(4)]
+            layer_gflop = [CONV2_GFLOP_PER_CLIP, CONV3_GFLOP_PER_CLIP, CONV4_GFLOP_PER_CLIP, CONV5_GFLOP_PER_CLIP]
+            conv_rest_exec = CONV_REST_GFLOP_PER_CLIP - sum(g * (1.0 - f) for g, f in zip(layer_gflop, cfrac))
+            exec_gflop_clip = CONV1_GFLOP_PER_CLIP * exec_frac + conv_rest_exec + LINEAR_GFLOP_PER_CLIP
+            pooled_rows_written = 43 - 2 * max(int(conv2_rows_skipped or 0), 0) if zskip else 43
+            exec_bytes_launch = (FRAMES * 270 * 480 * 3 * exec_frac + 2 * POS_EXEC * pooled_rows_written * 78 * 64) * clips_per_launch
+            stage = {k: v[0] / nprof for k, v in prof.items()}
+            conv_ms = stage["conv1"] + stage["conv1_aux"] + stage["maxpool"] + stage["conv2-fc6+audio_cnn"] + stage["stack_frames"]
+            lin_ms = stage["gemm"] + stage["attention"] + stage["layernorm"]
+            res.update({
+                "roofline": {"bound": "mfma", "kernel": "conv1_direct_kernel (u8 frames -> conv1+BN+ReLU+maxpool, 154 distinct positions/clip)",
+                             "achieved": achieved, "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": achieved / MFMA_PEAK_TFLOPS,
+                             "traffic": traffic * clips_per_launch / 32.0 if traffic else None, "traffic_note": traffic_note,
+                             # bytes the launch has to move for the work it EXECUTES: the frame rows of the executed input tiles (the all-zero
+                             # bands are read by the scan kernel, not by this one) + the pooled rows conv2 will read (conv2's row skip leaves
+                             # the first 2 x s2 pooled rows of every position unwritten); `traffic` / this >= 1 is the re-read / write amplification
+                             "algorithmic_bytes_per_launch": exec_bytes_launch,
+                             "algorithmic_bytes_per_launch_unskipped": CONV1_ALGO_BYTES_PER_CLIP * clips_per_launch,
+                             "traffic_over_algorithmic": (traffic * clips_per_launch / 32.0) / exec_bytes_launch if traffic else None,
+                             "hbm_frac_of_peak": exec_bytes_launch / c1_avg_s / 1e9 / HBM_PEAK_GBS if c1_avg_s > 0 else None,
+                             "launch_ms": c1_avg_s * 1e3, "launches_per_step": c1_n / nprof,
+                             "counters": load_sq_counters(),
+                             "executed_tile_fraction": exec_frac,
+                             "timing_note": "the kernel timed ALONE: these steps run on one stream (dual_stream=0, one launch = all clips); in the timed "
+                                            "loop the batch runs as two parts on two streams and its two conv1 launches share the CUs with the other part's kernels",
+                             "flops_note": "achieved = EXECUTED algorithmic FLOPs / launch time (HIP events on the launch stream, mean of "
+                                           f"{c1_n} launches): all-zero input tiles (the face-mask rows, 8 of 22 row tiles of the synthetic clips) are not counted",
+                             # whole path, priced consistently on executed work (154 positions, executed conv1 tiles)
+                             "whole_path": {"executed_gflop_per_clip": exec_gflop_clip,
+                                            "frac": value / world * exec_gflop_clip / 1e3 / MFMA_PEAK_TFLOPS}},
+                # SURVEY 8d asks for BOTH fractions on the conv extractor: algorithmic HBM bytes of the whole conv stack / its time
+                "roofline_conv_stack": {"bound": "mfma", "ms_per_step": conv_ms,
+                                        "mfma_frac": (CONV1_GFLOP_PER_CLIP * exec_frac + conv_rest_exec) * args.clips / max(conv_ms, 1e-9) / MFMA_PEAK_TFLOPS,
+                                        "conv2_rows_skipped_min": conv2_rows_skipped,
+                                        "computed_row_fraction": {f"conv{l + 2}": round(cfrac[l], 4) for l in range(4)},
+                                        "flops_note": "executed FLOPs: conv1 tiles over all-zero input and the leading conv2 .. conv5 output rows that do "
+                                                      "not depend on the position (read from images computed once per weight load) are not counted",
+                                        "algorithmic_bytes_per_step": CONV_ALGO_BYTES_PER_CLIP * args.clips,
+                                        "achieved_gbs": CONV_ALGO_BYTES_PER_CLIP * args.clips / max(conv_ms, 1e-9) / 1e6,
+                                        "hbm_frac": CONV_ALGO_BYTES_PER_CLIP * args.clips / max(conv_ms, 1e-9) / 1e6 / HBM_PEAK_GBS,
+                                        "note": "the conv stack is MFMA-bound (620 FLOP/B): the HBM fraction is reported because north_star asks for it, not because it is the roof"},
+                # attention + MLP blocks: every Linear GEMM, attention and LayerNorm launch of a step (algorithmic FLOPs only:
+                # the hi+lo weight split of precision mode 1 is NOT counted as work)
+                "roofline_linear_gemms": {"bound": "mfma", "kernel": "all Linear GEMM + attention + LayerNorm launches of one step",
+                                          "achieved": LINEAR_GFLOP_PER_CLIP * args.clips / max(lin_ms, 1e-9), "peak": MFMA_PEAK_TFLOPS,
+                                          "unit": "TFLOP/s", "frac": LINEAR_GFLOP_PER_CLIP * args.clips / max(lin_ms, 1e-9) / MFMA_PEAK_TFLOPS,
+                                          "ms_per_step": lin_ms, "gemm_only_ms": stage["gemm"], "launches_per_step": prof["gemm"][1] / nprof},
+                "stage_ms_per_step": {k: round(v, 3) for k, v in stage.items()},
+            })
         if "dense_ms" in extras:
             d1 = extras["dense_ms"] / max(extras["dense_n"], 1) * 1e-3
             da = CONV1_GFLOP_PER_CLIP * clips_per_launch / d1 / 1e3 if d1 > 0 else 0.0
@@ -740,7 +753,7 @@ def main():
                     "what": "decoder-resolution frames (228x314 as in the reference's samples/sample1.avi), only the source rows below each frame's mask "
                             "cross the link (GestureStreamer(source_hw=...)); face mask + cv2-style bilinear resize to 270x480 on the device "
                             "(jg_mask_resize_packed); bit-identical to load_rgb_masked_frames + the resident path"}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             res["cpu_baseline"] = cpu_baseline(frames_host[:2])
         else:
             res["cpu_baseline"] = None

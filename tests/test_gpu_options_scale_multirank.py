@@ -618,7 +618,7 @@ def test_bench_launcher_starts_ranks(tmp_path):
     the launcher is exercised with --oversubscribe (ranks share the GPU, gloo)."""
     import json
     args = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--clips", "4",
-            "--no-cpu-baseline"]
+            "--full", "--no-cpu-baseline"]
     if torch.cuda.device_count() < 2:
         args.append("--oversubscribe")
     r = subprocess.run(args, capture_output=True, text=True, timeout=900)

@@ -12,10 +12,10 @@ OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 run() { local name=$1; shift; rocprofv3 "$@" --output-format csv -d "$OUT/$name" -o "$name" -- python3 "$ROOT/bench.py" --no-cpu-baseline "${EXTRA[@]}" > "$OUT/$name.json" 2> "$OUT/$name.err"; }
-EXTRA=(--no-extras);                                  run dual --kernel-trace --stats
-EXTRA=(--no-extras --opt dual_stream=0);              run single --kernel-trace --stats
-EXTRA=(--no-extras --steps 1 --warmup 1 --opt dual_stream=0); run fetch --kernel-trace --pmc FETCH_SIZE
-EXTRA=(--no-extras --steps 1 --warmup 1 --opt dual_stream=0); run write --kernel-trace --pmc WRITE_SIZE
+EXTRA=(--full --no-extras);                           run dual --kernel-trace --stats
+EXTRA=(--full --no-extras --opt dual_stream=0);       run single --kernel-trace --stats
+EXTRA=(--full --no-extras --steps 1 --warmup 1 --opt dual_stream=0); run fetch --kernel-trace --pmc FETCH_SIZE
+EXTRA=(--full --no-extras --steps 1 --warmup 1 --opt dual_stream=0); run write --kernel-trace --pmc WRITE_SIZE
 EXTRA=(--only config3 --steps 5);                     run vta --kernel-trace --stats
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/xlmr" -o xlmr -- python3 "$ROOT/tools/xlmr_bench.py" 256 64 > "$OUT/xlmr.txt" 2> "$OUT/xlmr.err"
 cd "$ROOT"

@@ -14,7 +14,7 @@ ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$ROOT/gpurun_out/sq_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-EXTRA=(--no-cpu-baseline --no-extras --steps 1 --warmup 1 --opt dual_stream=0 "$@")
+EXTRA=(--full --no-cpu-baseline --no-extras --steps 1 --warmup 1 --opt dual_stream=0 "$@")
 run() { local name=$1; shift; rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d "$OUT/$name" -o "$name" -- python3 "$ROOT/bench.py" "${EXTRA[@]}" > "$OUT/$name.json" 2> "$OUT/$name.err"; echo "$name rc=$?"; }
 run mfma SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_INSTS_MFMA SQ_WAVE_CYCLES SQ_BUSY_CU_CYCLES GRBM_GUI_ACTIVE
 run lds SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_LDS_ADDR_CONFLICT SQ_LDS_UNALIGNED_STALL SQ_WAIT_INST_LDS SQ_INSTS_LDS SQ_ACTIVE_INST_LDS GRBM_GUI_ACTIVE

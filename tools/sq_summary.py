@@ -94,7 +94,7 @@ def main():
         if e:
             res[k] = e
     res["_note"] = ("counters summed over instances by rocprofv3: SQ_VALU_MFMA_BUSY_CYCLES / 1024 SIMDs, GRBM_GUI_ACTIVE / 8 XCDs; one "
-                    "one-stream 32-clip step of `bench.py --no-extras --steps 1 --warmup 1 --opt dual_stream=0`; durations and clocks are those of "
+                    "one-stream 32-clip step of `bench.py --full --no-extras --steps 1 --warmup 1 --opt dual_stream=0`; durations and clocks are those of "
                     "the profiled passes (slower than un-profiled runs); SQ_WAVE_CYCLES / SQ_WAIT_* / SQ_ACTIVE_INST_* count quad-cycles")
     out = os.path.join(ROOT, "profiles", f"{tag}_sq_summary.json")
     json.dump(res, open(out, "w"), indent=1)
