@@ -1,0 +1,206 @@
+// libjegal_hip: the jg_debug_* entry points -- kernel check points, GEMM timing, what the last conv stack did.  Host code only.
+#include "engine.h"
+
+using namespace engine;
+
+// ---- kernel check points: one launch of a production launcher on the caller's operands, with the handle's options (which pick
+// the instance exactly as in production) and the handle's build (fp16 or bf16).  The launcher's own shape rules decide what is
+// valid: its hipErrorInvalidValue comes back as JG_ERR_ARG, and nothing was launched then.  (Handle internals and LAUNCH: engine.h.)
+namespace {
+int check_result(jg_handle* h, hipError_t e, const char* what) {
+    if (e == hipErrorInvalidValue) JG_FAIL(h, JG_ERR_ARG, "%s: the launcher rejects this shape / argument set", what);
+    if (e != hipSuccess) JG_FAIL(h, JG_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
+    return JG_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int jg_debug_conv2_rowskip(jg_handle* h, int* rows) {
+    ENTER(h);
+    if (!rows) JG_FAIL(h, JG_ERR_ARG, "rows is NULL");
+    *rows = 0;
+    if (!h->last_rowskip) return JG_OK;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpy(rows, h->last_rowskip, sizeof(int), hipMemcpyDeviceToHost));
+    return JG_OK;
+}
+
+int jg_debug_conv_rows(jg_handle* h, int64_t* computed, int64_t* full) {
+    ENTER(h);
+    if (!computed || !full) JG_FAIL(h, JG_ERR_ARG, "null buffer");
+    for (int l = 0; l < 4; ++l) computed[l] = full[l] = 0;
+    if (!h->last_conv_totals) return JG_OK;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    int t[4];
+    HIPCHK(h, hipMemcpy(t, h->last_conv_totals, sizeof(t), hipMemcpyDeviceToHost));
+    for (int l = 0; l < 4; ++l) { computed[l] = t[l]; full[l] = h->last_conv_full[l]; }
+    return JG_OK;
+}
+
+int jg_debug_conv1_pool(jg_handle* h, const void* frames_u8, int B, int T, int pad, void* out_f16) {
+    ENTER(h);
+    if (!h->gs.m.ready) JG_FAIL(h, JG_ERR_STATE, "GestSync weights not finalized");
+    if (!frames_u8 || !out_f16 || B <= 0 || pad < 0 || pad > 12 || T + 2 * pad < 5)      // conv1's skip-mask area is sized for pad <= 12
+        JG_FAIL(h, JG_ERR_ARG, "bad arguments (need 0 <= pad <= 12 and T + 2*pad >= 5)");
+    h->ws.reset();
+    const long sw = 3, sh = (long)FW * 3, st = (long)FH * FW * 3, sb = (long)T * st;
+    unsigned* zscr;
+    return gs_conv1_stage(h, frames_u8, 1, sb, st, sh, sw, 1, B, T, pad, static_cast<f16*>(out_f16), true, &zscr);
+}
+
+// Tuning aid: time `iters` launches of the production GEMM on garbage operands of a given shape.
+// mode bit 0: hi+lo weights, bit 1: fp32 residual in/out (else fp16 out), bit 2: ReLU.  Returns ms per launch in *ms.
+int jg_debug_gemm(jg_handle* h, int M, int N, int K, int mode, int iters, double* ms) {
+    return jg_debug_gemm_ex(h, nullptr, nullptr, M, N, K, mode, iters, ms);
+}
+
+// a16 / w16: caller-supplied fp16 operands ([M][K] and [N][K], e.g. random data: constant operands let the chip hold a higher
+// clock than real data does, MI355X_MICROARCH.md "DVFS give-back"); NULL: constant fill
+int jg_debug_gemm_ex(jg_handle* h, const void* a16, const void* w16, int M, int N, int K, int mode, int iters, double* ms) {
+    if (!h || !ms || M <= 0 || N <= 0 || K <= 0 || iters <= 0) return JG_ERR_ARG;
+    ENTER(h);
+    h->ws.reset();
+    f16 *A, *Wh, *Wl, *o16;
+    float *bias, *x32;
+    RET(wsalloc(h, (size_t)M * K, &A));
+    RET(wsalloc(h, (size_t)N * K, &Wh));
+    RET(wsalloc(h, (size_t)N * K, &Wl));
+    RET(wsalloc(h, pad128(M) * N, &o16));
+    RET(wsalloc(h, pad128(M) * N, &x32));
+    RET(wsalloc(h, (size_t)N, &bias));
+    if (a16) HIPCHK(h, hipMemcpyAsync(A, a16, (size_t)M * K * 2, hipMemcpyDeviceToDevice, h->stream));
+    else HIPCHK(h, hipMemsetAsync(A, 0x3c, (size_t)M * K * 2, h->stream));
+    if (w16) HIPCHK(h, hipMemcpyAsync(Wh, w16, (size_t)N * K * 2, hipMemcpyDeviceToDevice, h->stream));
+    else HIPCHK(h, hipMemsetAsync(Wh, 0x2c, (size_t)N * K * 2, h->stream));
+    HIPCHK(h, hipMemsetAsync(Wl, 0x1c, (size_t)N * K * 2, h->stream));
+    HIPCHK(h, hipMemsetAsync(bias, 0, (size_t)N * 4, h->stream));
+    HIPCHK(h, hipMemsetAsync(x32, 0, (size_t)M * N * 4, h->stream));
+    GemmArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.A = A; a.lda = K; a.Wh = Wh; a.Wl = (mode & 1) ? Wl : nullptr; a.ldw = K;
+    a.M = M; a.N = N; a.K = K; a.bias = bias; a.ldc = N; a.relu = (mode >> 2) & 1;
+    if (mode & 2) { a.res = x32; a.ldr = N; a.out32 = x32; } else { a.out16 = o16; }
+    if (mode & 8) {      // residual + LayerNorm fused (N = 512): gamma/beta = the zero bias vector, timing only
+        a.res = nullptr; a.out32 = nullptr;
+        a.res16 = o16; a.out16 = o16;
+        a.ln_w = bias; a.ln_b = bias; a.ln_flavour = LN_STD;
+    }
+    if (mode & 48) {     // implicit LayerNorm, timing only: 16 = consumer (ln_mode 1), 32 = producer (ln_mode 2); statistics / planes = the scratch buffers
+        float* stats;
+        RET(wsalloc(h, (size_t)pad128(M) * 2, &stats));
+        HIPCHK(h, hipMemsetAsync(stats, 0, (size_t)M * 2 * 4, h->stream));
+        a.res = nullptr; a.out32 = nullptr; a.scale = bias; a.ln_stats = stats;
+        if (mode & 16) { a.ln_mode = 1; a.out16 = o16; }
+        else {
+            f16* lo;
+            float* part;
+            RET(wsalloc(h, pad128(M) * N, &lo));
+            RET(wsalloc(h, (size_t)pad128(M) * (N / 64) * 2, &part));
+            a.ln_mode = 2; a.relu = 0; a.xres_hi = o16; a.xres_lo = lo; a.out16 = o16; a.out_lo = lo; a.stat_out = part;
+        }
+    }
+    hipEvent_t e0, e1;
+    HIPCHK(h, hipEventCreate(&e0));
+    HIPCHK(h, hipEventCreate(&e1));
+    HIPCHK(h, LAUNCH(h, launch_gemm, a, false, h->opts, h->stream));
+    HIPCHK(h, hipEventRecord(e0, h->stream));
+    for (int i = 0; i < iters; ++i) HIPCHK(h, LAUNCH(h, launch_gemm, a, false, h->opts, h->stream));
+    HIPCHK(h, hipEventRecord(e1, h->stream));
+    HIPCHK(h, hipEventSynchronize(e1));
+    float t = 0.f;
+    HIPCHK(h, hipEventElapsedTime(&t, e0, e1));
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    *ms = t / iters;
+    return JG_OK;
+}
+
+int jg_debug_gemm_check(jg_handle* h, const jg_gemm_check* c) {
+    ENTER(h);
+    h->kname[0] = 0;
+    if (!c || !c->A || !c->Wh || c->M <= 0 || c->N <= 0 || c->K <= 0 || c->lda < c->K || c->ldw < c->K || (!c->out32 && !c->out16) ||
+        ((c->out32 || (c->out16 && !c->ln_w)) && c->ldc < c->N) || (c->res && (c->ldr < c->N || c->res_mod < 0)) ||
+        (c->bias_clip && (c->rpc <= 0 || c->nclips <= 0)) || c->relu < 0 || c->relu > 2 || c->ln_mode < 0 || c->ln_mode > 2)
+        JG_FAIL(h, JG_ERR_ARG, "jg_debug_gemm_check: bad arguments");
+    GemmArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.A = static_cast<const f16*>(c->A); a.lda = c->lda;
+    a.Wh = static_cast<const f16*>(c->Wh); a.Wl = static_cast<const f16*>(c->Wl); a.ldw = c->ldw;
+    a.M = c->M; a.N = c->N; a.K = c->K;
+    a.scale = c->scale; a.bias = c->bias;
+    a.bias_clip = c->bias_clip; a.rpc = c->rpc; a.nclips = c->nclips;
+    a.res = c->res; a.ldr = c->ldr; a.res_mod = c->res_mod; a.relu = c->relu;
+    a.out32 = c->out32; a.out16 = static_cast<f16*>(c->out16); a.ldc = c->ldc;
+    a.ln_w = c->ln_w; a.ln_b = c->ln_b; a.ln_flavour = LN_STD;
+    a.res16 = static_cast<const f16*>(c->res16);
+    a.ln_mode = c->ln_mode; a.ln_stats = c->ln_stats;
+    a.xres_hi = static_cast<const f16*>(c->xres_hi); a.xres_lo = static_cast<const f16*>(c->xres_lo);
+    a.out_lo = static_cast<f16*>(c->out_lo); a.stat_out = c->stat_out;
+    EngineOpts o = h->opts;
+    o.kname = h->kname;          // the name slot the launchers write
+    return check_result(h, LAUNCH(h, launch_gemm, a, false, o, h->stream), "launch_gemm");
+}
+
+int jg_debug_gemm32(jg_handle* h, const float* A, int64_t lda, const float* W, int64_t ldw, int M, int N, int K, const float* scale,
+                    const float* bias, const float* res, int64_t ldr, int res_mod, int act, float* out, int64_t ldc) {
+    ENTER(h);
+    h->kname[0] = 0;
+    if (!A || !W || !out || M <= 0 || N <= 0 || K <= 0 || lda < K || ldw < K || ldc < N || (res && (ldr < N || res_mod < 0)) || act < 0 || act > 2)
+        JG_FAIL(h, JG_ERR_ARG, "jg_debug_gemm32: bad arguments");
+    Gemm32Args a;
+    std::memset(&a, 0, sizeof(a));
+    a.A = A; a.lda = lda; a.W = W; a.ldw = ldw; a.M = M; a.N = N; a.K = K;
+    a.scale = scale; a.bias = bias; a.res = res; a.ldr = ldr; a.res_mod = res_mod; a.out = out; a.ldc = ldc; a.act = act;
+    return check_result(h, launch_gemm32(a, h->stream, h->kname), "launch_gemm32");
+}
+
+int jg_debug_gemm_x3(jg_handle* h, const float* A, int64_t lda, const void* Wh, const void* Wl, int64_t ldw, int M, int N, int K,
+                     const float* bias, const float* res, int64_t ldr, int res_mod, int relu, float* out, int64_t ldc) {
+    ENTER(h);
+    h->kname[0] = 0;
+    if (!A || !Wh || !Wl || !out || M <= 0 || N <= 0 || K <= 0 || lda < K || ldw < K || ldc < N || (res && (ldr < N || res_mod < 0)) ||
+        relu < 0 || relu > 1)
+        JG_FAIL(h, JG_ERR_ARG, "jg_debug_gemm_x3: bad arguments");
+    GemmX3Args a;
+    std::memset(&a, 0, sizeof(a));
+    a.A = A; a.lda = lda; a.Wh = static_cast<const f16*>(Wh); a.Wl = static_cast<const f16*>(Wl); a.ldw = ldw; a.M = M; a.N = N; a.K = K;
+    a.bias = bias; a.res = res; a.ldr = ldr; a.res_mod = res_mod; a.out = out; a.ldc = ldc; a.relu = relu;
+    return check_result(h, launch_gemm_x3(a, h->stream, h->kname), "launch_gemm_x3");
+}
+
+int jg_debug_attention(jg_handle* h, const void* qkv, const float* keymask, int B, int S, int H, int dk, void* out) {
+    ENTER(h);
+    h->kname[0] = 0;
+    if (!qkv || !out || B <= 0 || S <= 0 || H <= 0 || (dk != 64 && dk != 96)) JG_FAIL(h, JG_ERR_ARG, "jg_debug_attention: bad arguments");
+    EngineOpts o = h->opts;
+    o.kname = h->kname;          // the name slot the launchers write
+    return check_result(h, LAUNCH(h, launch_attention, static_cast<const f16*>(qkv), keymask, B, S, H, dk, static_cast<f16*>(out), o, h->stream),
+                        "launch_attention");
+}
+
+int jg_debug_attention_gather(jg_handle* h, const void* qkv_pos, const void* pe_qkv, int Twin, int P, int shift, int B, int S, int H, void* out) {
+    ENTER(h);
+    h->kname[0] = 0;
+    if (!qkv_pos || !pe_qkv || !out || B <= 0 || S <= 0 || H <= 0 || Twin <= 0 || P <= 0 || B % Twin)
+        JG_FAIL(h, JG_ERR_ARG, "jg_debug_attention_gather: bad arguments (B must be a multiple of Twin)");
+    if (h->bf16) JG_FAIL(h, JG_ERR_STATE, "jg_debug_attention_gather: the gather form is an fp16-build kernel (the clip path's layer 0)");
+    const AttnGather g{static_cast<const f16*>(pe_qkv), Twin, P, shift};
+    return check_result(h, launch_attention_gather(static_cast<const f16*>(qkv_pos), g, B, S, H, static_cast<f16*>(out), h->stream, h->kname),
+                        "launch_attention_gather");
+}
+
+int jg_debug_attention32(jg_handle* h, const float* qkv, const float* keymask, int B, int S, int H, int dk, float* out) {
+    ENTER(h);
+    h->kname[0] = 0;
+    if (!qkv || !out || B <= 0 || S <= 0 || H <= 0) JG_FAIL(h, JG_ERR_ARG, "jg_debug_attention32: bad arguments");
+    return check_result(h, launch_attention32(qkv, keymask, B, S, H, dk, out, h->stream, h->kname), "launch_attention32");
+}
+
+int jg_debug_last_kernel(jg_handle* h, char* buf, int len) {
+    if (!h || !buf || len <= 0) return JG_ERR_ARG;
+    snprintf(buf, (size_t)len, "%s", h->kname);
+    return JG_OK;
+}
+
+}  // extern "C"

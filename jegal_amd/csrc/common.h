@@ -3,7 +3,7 @@
 // Two builds of the kernels live in the library: the default one with fp16 operands and, for precision mode JG_PREC_BF16, a
 // second one of gemm.hip / attention.hip / elementwise.hip compiled with -DJG_BF16: there `f16` -- the 16-bit operand /
 // activation type of every kernel -- is __bf16, the MFMA macros below name the bf16 instructions, and everything (this header
-// included) sits in namespace bf.  api.hip includes this header twice and dispatches per handle (LAUNCH in api.hip).
+// included) sits in namespace bf.  engine.h includes this header twice and dispatches per handle (LAUNCH in engine.h).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <cstdio>
@@ -45,13 +45,13 @@ struct ConvGeom {
     // p = kh*KW + kw when tap_table == 0.  Strided layers list their taps by parity class (kh % SH, kw % SW):
     // consecutive taps of a class touch the same input pixels shifted by whole output positions, so the re-reads
     // of a k-loop hit the L2 instead of thrashing it (conv2: 25 taps, 4 classes of 9/6/6/4).  The packed weights
-    // use the same order (api.hip:make_conv).
+    // use the same order (linear.hip:make_conv).
     unsigned long long taps[4];
     int tap_table;
-    // ---- position-independent leading rows (LDS-DMA conv kernels ONLY: api.hip sets these for launches that take that path).
+    // ---- position-independent leading rows (LDS-DMA conv kernels ONLY: gestsync.hip sets these for launches that take that path).
     // Behind conv1's zero-band skip (conv1.hip) the first rows of every layer's output do not depend on the position at all:
     // they are what the layer computes from an all-constant input image, and the engine keeps those images per weight load
-    // ("const chain", api.hip).  PER POSITION (image) p, conv2 leaves its first s2[p] output rows out and every deeper layer the
+    // ("const chain", gestsync.hip).  PER POSITION (image) p, conv2 leaves its first s2[p] output rows out and every deeper layer the
     // count conv_skip_decode(s2[p], op) derived from it; a consumer reads the input rows its producer left out from the const
     // image of its input instead.  The computed rows of a launch are COMPACTED: the kernel runs over m' = 0 .. *rows_total - 1 and
     //   rowmap[m'] = (full output row = (img*OH + oh)*OW + ow) | s2[img] << 24
@@ -121,7 +121,7 @@ struct GemmArgs {
     // a tiled fp16 plane.
     const f16* res16;
     int a_tiled;
-    // Implicit LayerNorm (XLM-RoBERTa's post-norm layers, api.hip:xlmr_encode_impl): the token stream holds the UN-normalised rows
+    // Implicit LayerNorm (XLM-RoBERTa's post-norm layers, xlmr.hip:xlmr_encode_folded): the token stream holds the UN-normalised rows
     // x = hi + lo (two fp16 planes; the hi plane is the next GEMM's A operand) and per row (mean, rstd) of x; LN(x) itself is never
     // materialised.  ln_mode 1 (consumer: the Linear behind the LayerNorm, weights pre-multiplied by gamma):
     //     out = rstd[m] * (acc - mean[m] * scale[n]) + bias[n]      scale = column sums of the folded weights, bias = b + W beta
@@ -158,7 +158,7 @@ enum { LN_STD = 0, LN_ANNOTATED = 1 };
 
 
 // ---- per-handle engine state shared with the launchers ---------------------------------------------------------
-// Tuning / A-B switches and the per-device resources a launch needs.  One instance per jg_handle (api.hip), passed to
+// Tuning / A-B switches and the per-device resources a launch needs.  One instance per jg_handle (engine.h), passed to
 // the launchers: two handles -- on one device or on two -- never see each other's settings.
 struct EngineOpts {
     int device = 0;
@@ -242,7 +242,6 @@ hipError_t launch_audio_conv0(const float* mel, int B, int Tm, int F, const f16*
 hipError_t launch_zero_tail(f16* x, const int* valid, int halvings, int B, int H, long row_elems, hipStream_t s);
 hipError_t launch_segment_mean(const float* seq, int D, const int32_t* seg, int n, f16* dst16, float* dst32,
                                int dst_ld, int dst_col, hipStream_t s);
-hipError_t launch_fill_f16(f16* p, long n, hipStream_t s);
 hipError_t launch_xlmr_embed(const int32_t* ids, int B, int L, int D, int pad_id, int vocab, int maxpos, const float* word, const float* pos,
                              const float* type, float* out, hipStream_t s);
 // implicit-LayerNorm token stream (GemmArgs::ln_mode): embeddings as un-normalised hi / lo planes + per-64-column (sum, sum of squares)
@@ -252,7 +251,6 @@ hipError_t launch_xlmr_embed_planes(const int32_t* ids, int B, int L, int D, int
 hipError_t launch_ln_stats(const float* part, int rows, int P, float* stats, hipStream_t s);
 // out32 = LayerNorm(hi + lo) (nn.LayerNorm, eps 1e-5), D = 768: the explicit LayerNorm at the end of the implicit chain
 hipError_t launch_layernorm_planes(const f16* hi, const f16* lo, const float* w, const float* b, int rows, int D, float* out32, hipStream_t s);
-hipError_t launch_gelu(const float* in, f16* out, long n, hipStream_t s);
 hipError_t launch_mask_i32_f32(const int32_t* in, float* out, long n, hipStream_t s);
 hipError_t launch_broadcast_channels(const f16* v, int C, f16* out, long pixels, hipStream_t s);
 hipError_t launch_logmel(const float* wav, int B, int n_samples, const float* mel_basis, float* out, hipStream_t s);

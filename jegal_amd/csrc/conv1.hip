@@ -785,7 +785,7 @@ __global__ __launch_bounds__(256) void conv1_zero_scan_kernel(const uint8_t* __r
 // rows (2rt-1: carry of the tile above and its own row 0; 2rt: its rows 0..2) are then the constant.  Its own carry is the
 // constant as well, which the tile below -- if that one runs -- takes from cz instead of LDS (pool(), carry_const).
 // It also writes s2[nf], conv2's position-independent leading output rows of the position (conv1_s2_of_mask): the conv2 GEMM
-// computes rows >= s2[nf] of that position only, and so on down the stack (ConvGeom::rowmap, the const chain of api.hip).
+// computes rows >= s2[nf] of that position only, and so on down the stack (ConvGeom::rowmap, the const chain of gestsync.hip).
 // *rowskip_min = min over the launch (a debug word: jg_debug_conv2_rowskip).
 __global__ void conv1_skip_mask_kernel(const unsigned* __restrict__ fz, int nclip, int T, int pad, int P, unsigned* __restrict__ skip,
                                        int* __restrict__ s2, int* __restrict__ rowskip_min) {

@@ -593,21 +593,6 @@ hipError_t launch_layernorm_planes(const f16* hi, const f16* lo, const float* w,
     hipLaunchKernelGGL(layernorm_planes_kernel<3>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, hi, lo, w, b, rows, out32);
     return hipGetLastError();
 }
-// exact GELU (erf form, the HF "gelu"): fp32 in -> fp16 out
-__global__ void gelu_kernel(const float* __restrict__ in, f16* __restrict__ out, long n4) {
-    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(in + i * 4);
-        auto g = [](float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f)); };
-        const f16x4 h = {(f16)g(v.x), (f16)g(v.y), (f16)g(v.z), (f16)g(v.w)};
-        *reinterpret_cast<f16x4*>(out + i * 4) = h;
-    }
-}
-hipError_t launch_gelu(const float* in, f16* out, long n, hipStream_t s) {
-    if (n % 4) return hipErrorInvalidValue;
-    const long n4 = n / 4;
-    hipLaunchKernelGGL(gelu_kernel, dim3((unsigned)((n4 + 255) / 256 < 65536 ? (n4 + 255) / 256 : 65536)), dim3(256), 0, s, in, out, n4);
-    return hipGetLastError();
-}
 // int attention mask (1 = token, 0 = padding) -> the float key mask the attention kernels take
 __global__ void mask_i32_f32_kernel(const int32_t* __restrict__ in, float* __restrict__ out, long n) {
     const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
@@ -626,10 +611,6 @@ hipError_t launch_broadcast_channels(const f16* v, int C, f16* out, long pixels,
     const long total = pixels * C;
     hipLaunchKernelGGL(broadcast_channels_kernel, dim3((unsigned)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096)), dim3(256), 0, s, v, C, out, total);
     return hipGetLastError();
-}
-
-hipError_t launch_fill_f16(f16* p, long n, hipStream_t s) {
-    return hipMemsetAsync(p, 0, n * sizeof(f16), s);
 }
 
 // Temporal mean of ragged (rows,D) blocks: out[i] = mean(x[offsets[i]:offsets[i+1]])

@@ -1,0 +1,393 @@
+// libjegal_hip host side: the handle, the packed model state and the helpers the host units share (api.hip, linear.hip,
+// gestsync.hip, jegal.hip, xlmr.hip, checks.hip).  Host code only; the kernel units do not include it.
+#pragma once
+#include "common.h"
+#define JG_BF16                  // the bf16 build's declarations (namespace bf): same launchers, f16 = __bf16
+#include "common.h"
+#undef JG_BF16
+#include "../../include/jegal_hip.h"
+#include "audit32.h"
+
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <map>
+#include <string>
+#include <vector>
+
+namespace engine {
+
+// ---- dispatch between the two kernel builds.  LAUNCH(h, launch_x, args...) calls launch_x of the fp16 build or bf::launch_x of
+// the bf16 build (precision mode JG_PREC_BF16): same argument lists, the 16-bit pointers and the structs that carry them are
+// layout-identical in both builds and simply re-typed.
+[[maybe_unused]] inline const bf::f16* to_bf(const f16* p) { return reinterpret_cast<const bf::f16*>(p); }
+inline bf::f16* to_bf(f16* p) { return reinterpret_cast<bf::f16*>(p); }
+inline const bf::GemmArgs& to_bf(const GemmArgs& a) { return reinterpret_cast<const bf::GemmArgs&>(a); }
+inline const bf::EngineOpts& to_bf(const EngineOpts& o) { return reinterpret_cast<const bf::EngineOpts&>(o); }
+static_assert(sizeof(bf::GemmArgs) == sizeof(GemmArgs) && sizeof(bf::EngineOpts) == sizeof(EngineOpts), "the two builds share their argument structs");
+template <class T> inline T to_bf(T v) { return v; }
+template <class F, class G, class... A>
+inline hipError_t dispatch_build(bool bf16, F f, G g, A... a) { return bf16 ? g(to_bf(a)...) : f(a...); }
+#define LAUNCH(h, fn, ...) engine::dispatch_build((h)->bf16, fn, bf::fn, __VA_ARGS__)
+
+struct HostTensor {
+    std::vector<float> v;
+    std::vector<int64_t> shape;
+    mutable bool used = false;      // consumed by a finalize (find / need): erased when that finalize is done
+    int64_t numel() const { int64_t n = 1; for (auto s : shape) n *= s; return n; }
+};
+
+struct Lin {            // packed Linear / folded conv:  [N][K] fp16 hi (+lo), fp32 bias
+    f16* wh = nullptr;
+    f16* wl = nullptr;          // lo part used at run time (W2 modes) or nullptr
+    float* bias = nullptr;
+    int N = 0, K = 0;
+    // bias-corrected mode (JG_PREC_FP16_BC): run-time weights are the single fp16 `wh`; the systematic part of
+    // the weight-rounding error, (w - fp16(w)) . E[x], is folded into `bias` after a calibration pass that runs
+    // with hi+lo weights (wl_calib) and records the per-channel mean of this layer's input (mu).
+    bool bc = false;
+    // run-time corrected mode (JG_PREC_FP16_RC; GestSync transformer Linears): single fp16 `wh` + a per-clip bias built from the clip's own
+    // rows and the lo part (`wl_calib`), see gemm(); wherever that epilogue is not available the GEMM runs hi+lo instead
+    bool rc = false;
+    bool bc_pending = false;    // LK_XLMR: no calibration yet -- the run-time GEMM keeps using hi+lo (wl == wl_calib); jg_calibrate_xlmr clears it
+    f16* wl_calib = nullptr;
+    float* mu = nullptr;        // device [K]: column sums of the A operand seen during calibration
+    long mu_rows = 0;
+    std::vector<float> w32, b32;
+    // Linear behind an IMPLICIT LayerNorm (GemmArgs::ln_mode 1): w32 / wh / wl hold W . diag(gamma), b32 / bias hold b + W beta, and
+    // c1h / c1f [N] the column sums of the packed weights -- of `wh` alone (single-fp16 runs: the GEMM then is exactly
+    // sum_k wh[n][k] (x[k] - mean) rstd, and the bias correction covers the lo part) and of wh + lo (hi+lo runs)
+    float* c1h = nullptr;
+    float* c1f = nullptr;
+    // fp32 audit path (JG_PREC_FP32 / option audit_weights; audit32.hip): the fp32 matrix [N][K] as packed (BatchNorm folded, same k order as
+    // wh) and the layer's own fp32 bias (`bias` above may carry a calibration's correction)
+    float* w32d = nullptr;
+    float* b32d = nullptr;
+};
+struct LNp { float* w = nullptr; float* b = nullptr; };
+
+struct EncLayer { Lin qkv, out, ff1, ff2; LNp n1, n2; };
+
+struct Arena {          // stream-ordered bump allocator over persistent chunks
+    struct Chunk { char* p; size_t cap; };
+    std::vector<Chunk> chunks;
+    size_t cur = 0, off = 0;
+    void reset() { cur = 0; off = 0; }
+    unsigned long tick = 0;         // jg_set_stream: when this arena was last parked (least recently used goes first)
+    size_t total() const { size_t t = 0; for (auto& c : chunks) t += c.cap; return t; }
+    void* alloc(size_t bytes, hipError_t* err) {
+        bytes = (bytes + 255) & ~size_t(255);
+        while (cur < chunks.size()) {
+            if (off + bytes <= chunks[cur].cap) { void* r = chunks[cur].p + off; off += bytes; return r; }
+            ++cur; off = 0;
+        }
+        size_t cap = bytes > (size_t(1) << 30) ? bytes : (size_t(1) << 30);
+        char* p = nullptr;
+        hipError_t e = hipMalloc(&p, cap);
+        if (e != hipSuccess) { *err = e; return nullptr; }
+        chunks.push_back({p, cap});
+        cur = chunks.size() - 1; off = bytes;
+        return p;
+    }
+    void release() { for (auto& c : chunks) (void)hipFree(c.p); chunks.clear(); reset(); }
+};
+
+struct ProfRec { int stage; hipEvent_t e0, e1; };
+
+// What each model's finalize owns besides its layers (the drivers reload the state_dict on every command: drop_model)
+struct Model {
+    int id = 0;                    // 1 GestSync, 2 JEGAL, 3 XLM-RoBERTa: bit id - 1 of a `which` / `models` mask
+    bool ready = false;
+    std::vector<void*> allocs;     // device weights and the buffers derived from them (walloc)
+    std::vector<Lin*> bc;          // bias-corrected layers (calibration passes)
+};
+
+struct GestSyncModel {
+    Model m{1};
+    Lin c1, c2, c3, c4, c5, fc6, ff0, ff2;
+    EncLayer layers[6];
+    float* pe = nullptr;
+    // const chain: what conv2 / conv3 / conv4 compute from an all-constant pooled image (relu(bias1) everywhere) -- the rows of
+    // their outputs that the zero-band skip makes position-independent are read from here (ConvGeom::const_in); 4 copies each
+    f16 *c2C = nullptr, *c3C = nullptr, *c4C = nullptr, *c5C = nullptr;
+    float* c1_scale255 = nullptr;
+    f16* c1_direct = nullptr;      // conv1 weights, slot-major [49][64][16] for the direct kernel
+    f16* qpe = nullptr;            // [21][1536]: layer-0 W_qkv pe[j] + b (Qkv0); recomputed when weights or bias corrections change
+    bool qpe_valid = false;
+};
+
+struct JegalModel {
+    Model m{2};
+    Lin ip0, ip3, op_rgb, al_g0, al_g2, fu0, fu2, al_c0, al_c2, op_text, op_audio;
+    Lin a0, a3, a6, a9, a12, a15;  // audio CNN
+    LNp ip_ln, rgb_norm, text_norm;
+    float* rgb_pe = nullptr;
+    EncLayer rgb_layers[6], text_layers[3];
+};
+
+// XLM-RoBERTa text front end (third-party transformers.XLMRobertaModel, call site jegal.py:116-129)
+struct XlmrModel {
+    Model m{3};
+    int vocab = 0, maxpos = 0;
+    float *word = nullptr, *pos = nullptr, *type = nullptr;
+    LNp emb_ln;
+    std::vector<EncLayer> layers;
+    bool folded = false;           // packed for the implicit-LayerNorm pass (option xlmr_fold at finalize, xlmr_encode_folded)
+};
+
+}  // namespace engine
+
+struct jg_handle {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    hipStream_t own_stream = nullptr;
+    std::string err;
+    int precision = JG_PREC_FP16_RC;      // the calibration-free mode (round 5; rounds 1-4: JG_PREC_FP16_BC)
+    bool bf16 = false;             // precision == JG_PREC_BF16: every launcher comes from the bf16 build (namespace bf)
+    bool calib = false;            // calibration pass in progress (bc layers use hi+lo and record input means)
+    int chunk = 32;                // clips per GestSync pass: ~14 GB of workspace per lane at 150 frames; 288 GB of HBM make the whole BASELINE batch one pass
+    bool fuse_ln = true;           // residual + LayerNorm in the GEMM epilogue (GestSync post-norm layers)
+    bool edge_dedup = true;        // skip the 16 duplicated edge positions of a padded clip
+    bool conv1_direct = true;      // fused u8 conv1 kernel (false: stack_frames + implicit GEMM)
+    bool qkv0_linear = true;       // layer-0 qkv projection over the distinct conv positions + gather in the attention kernel
+    bool ws_poison = false;        // option "ws_poison": fill the workspace with 0xff before every clip chunk (tests)
+    bool conv2_row_skip = true;    // conv2 leaves out the leading output rows that the zero-band scan proves to be copies of one row
+    const int* last_rowskip = nullptr;   // device word: min over the last conv stack's positions of conv2's row skip (jg_debug_conv2_rowskip)
+    const int* last_conv_totals = nullptr;   // device [4]: rows conv2 .. conv5 of the last conv stack computed (jg_debug_conv_rows)
+    long last_conv_full[4] = {0, 0, 0, 0};   // ... of these many
+    std::map<std::string, engine::HostTensor> host;
+    EngineOpts opts;               // per-handle tuning switches + per-device resources (common.h)
+    char kname[KNAME_LEN] = {0};   // instance the last kernel check point launched (jg_debug_last_kernel)
+    engine::Arena ws;
+    bool prof = false;
+    int prof_only = -1;            // >= 0: only this stage is bracketed with events (jg_profile_enable(h, 2 + stage))
+    std::vector<engine::ProfRec> recs;
+    double prof_ms[JG_ST_COUNT] = {0};
+    int64_t prof_n[JG_ST_COUNT] = {0};
+
+    engine::GestSyncModel gs;
+    engine::JegalModel jg;
+    engine::XlmrModel xl;
+    // implicit LayerNorm (option "xlmr_fold", read when the XLM-R weights are finalized): the 25 LayerNorms of a pass are never
+    // materialised -- see xlmr_encode_folded
+    bool xl_fold_opt = true;
+    float* feats = nullptr;
+    size_t feats_cap = 0;
+    // Small host -> device uploads that a call enqueues on its stream (per-clip lengths): a ring of PINNED staging slots, each guarded by
+    // an event recorded behind its copy, so a slot is re-used only once that copy has run (pageable vectors kept "alive for
+    // seven more parts" relied on the runtime staging pageable copies synchronously and on no caller enqueueing more than eight parts ahead)
+    struct StageSlot { int32_t* host = nullptr; size_t cap = 0; hipEvent_t ev = nullptr; bool pending = false; };
+    StageSlot stage_ring[16];
+    unsigned stage_next = 0;
+    // jg_extract_gesture on two lanes (option "dual_stream"): the batch is split in two (dual_split) and the parts run concurrently on two
+    // internal streams with their own workspaces, so that one part's next kernel fills the partly empty last round of the
+    // other's (persistent kernels run in rounds of one tile per CU: 788 LayerNorm tiles on 256 CUs are 3.08 rounds)
+    bool dual_stream = true;
+    int dual_split = 4;            // the first lane gets dual_split/8 of the batch.  Round 6: equal halves (rounds 3-5: 3/8; with the run-time correction's
+                                   // small launches and the split-operand GEMMs in the mix the sweep reads 12.77 ms at 12:20, 12.57 at 14:18, 12.53-12.61 at 16:16,
+                                   // 12.57-12.66 at 17:15 / 18:14, 12.66-12.73 at 20:12 -- tools/experiments/README.md)
+    std::map<hipStream_t, engine::Arena> ws_parked;      // arenas of the other streams this handle has been bound to (jg_set_stream)
+    static constexpr int MAX_LANES = 4;
+    hipStream_t lane_stream[MAX_LANES] = {};
+    engine::Arena lane_ws[MAX_LANES];
+    hipEvent_t lane_ev[MAX_LANES + 1] = {};      // [0]: the caller's stream at entry, [1 + l]: end of lane l
+    // fp32 audit path (audit32.hip).  audit_weights: finalize also keeps every matrix in fp32 (always in JG_PREC_FP32); audit_stages: which
+    // stages of the path run in fp32 (bit 0 conv stack, 1 GestSync transformer + ff_vid, 2 JEGAL gesture branch, 3 JEGAL content path,
+    // 4 XLM-RoBERTa; JG_PREC_FP32 = all of them) -- the stage boundaries are fp32 tensors in every mode, so stages can be mixed
+    // round 6: the two ends of the JEGAL gesture branch -- proj_ip_rgb and final norm + proj_op_rgb + the align MLP, five
+    // small GEMMs that carry two thirds of the branch's fp16 error -- run on the fp32 kernel in the fp16 contract modes
+    bool jegal_fp32_ends = true;
+    bool conv_round_diffuse = true;      // conv weights rounded with per-channel error diffusion across the taps (pack_matrix)
+    bool audit_weights = false;
+    int audit_stages = 0;
+    // diagnosis inside the fp16 JEGAL gesture branch (option "audit_jegal_parts", needs audit_weights): 1 input projection, 2 attention
+    // sub-layers, 4 feed-forward sub-layers, 8 final norm + output / align projections run on the fp32 kernels (the residual stream
+    // between them is fp32 in every mode)
+    int audit_jegal_parts = 0;
+    void* comm = nullptr;          // ncclComm_t of this rank (jg_comm_init) or nullptr
+    int comm_rank = 0, comm_world = 1;
+    // option "xlmr_lanes": jg_xlmr_encode runs a batch as this many equal parts (1..4) on as many streams (default 2).  Round 6 ran it with 1 for
+    // a while: with two parts in flight the implicit-LayerNorm pass returned ~1e-2 errors on some sequences of one part in 10-40 % of the runs.
+    // Root cause (tools/experiments/xlmr_race/, tools/experiments/pk_opsel_mfma/repro.hip): on this GPU a v_pk_fma_f32 whose low half selects
+    // the HIGH register of its second operand (op_sel:[0,1,0], the consumer epilogue's `acc * rstd`) reads that operand as 0 in lanes 48-63
+    // while waves of another kernel issue MFMAs on the same SIMD.  The library is built without packed-fp32 instructions since (Makefile, NOPK).
+    int xl_lanes = 2;
+    // option "lane_priority": 0 = lane streams of normal priority; 1 / 2 = lane 1 / lane 0 of high priority; 3 = both
+    // (default since round 6).  The runtime deals streams onto hardware queues per PRIORITY LEVEL (four queues each, in creation order): with
+    // normal priority the two lanes can land on ONE queue and then run in turn -- measured with five other streams in the application:
+    // 2 076 instead of 2 510 clips/s (tools/experiments/lane_queue_sweep.sh) -- high-priority lanes get queues of their own whatever the
+    // application's normal-priority streams are doing (2 503-2 526 clips/s with 0 / 1 / 2 / 3 / 5 / 8 other streams)
+    int lane_priority = 3;
+};
+
+namespace engine {
+
+#define JG_FAIL(h, code, ...) do { char _b[512]; snprintf(_b, sizeof(_b), __VA_ARGS__); (h)->err = _b; return (code); } while (0)
+#define HIPCHK(h, expr) do { hipError_t _e = (expr); if (_e != hipSuccess) JG_FAIL(h, JG_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); } while (0)
+#define RET(expr) do { int _r = (expr); if (_r != JG_OK) return _r; } while (0)
+
+// Every entry point runs on the handle's device whatever the caller's current device is, and restores it afterwards:
+// workspace allocations, kernel launches and hipFuncSetAttribute all act on the CURRENT device.
+struct DeviceGuard {
+    int prev = -1;
+    bool ok = true;
+    explicit DeviceGuard(int dev) {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        if (prev != dev) ok = hipSetDevice(dev) == hipSuccess; else prev = -1;
+    }
+    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
+};
+#define ENTER(h) if (!(h)) return JG_ERR_ARG; engine::DeviceGuard _dg((h)->device); if (!_dg.ok) JG_FAIL(h, JG_ERR_HIP, "hipSetDevice(%d) failed", (h)->device)
+
+// env JG_DEBUG_SYNC, read once per process: synchronise (and report) after every launch
+inline bool debug_sync() {
+    static const bool on = getenv("JG_DEBUG_SYNC") != nullptr;
+    return on;
+}
+
+// run a launcher under optional event timing
+template <class F>
+int timed(jg_handle* h, int stage, F&& f) {
+    ProfRec r{stage, nullptr, nullptr};
+    const bool prof = h->prof && (h->prof_only < 0 || h->prof_only == stage);
+    if (prof) {
+        HIPCHK(h, hipEventCreate(&r.e0));
+        HIPCHK(h, hipEventCreate(&r.e1));
+        HIPCHK(h, hipEventRecord(r.e0, h->stream));
+    }
+    hipError_t e = f();
+    if (e != hipSuccess) JG_FAIL(h, JG_ERR_HIP, "kernel launch failed (stage %s): %s", jg_stage_name(stage), hipGetErrorString(e));
+    if (debug_sync()) {                          // fault hunting (env JG_DEBUG_SYNC): name the launch a memory fault belongs to
+        static long n = 0;
+        std::fprintf(stderr, "[jg] launch %ld (stage %s) ...", ++n, jg_stage_name(stage));
+        e = hipStreamSynchronize(h->stream);
+        std::fprintf(stderr, " %s\n", e == hipSuccess ? "done" : hipGetErrorString(e));
+        if (e != hipSuccess) JG_FAIL(h, JG_ERR_HIP, "launch %ld (stage %s) failed at its synchronisation: %s", n, jg_stage_name(stage), hipGetErrorString(e));
+    }
+    if (prof) {
+        HIPCHK(h, hipEventRecord(r.e1, h->stream));
+        h->recs.push_back(r);
+    }
+    return JG_OK;
+}
+
+template <class T>
+int walloc(jg_handle* h, Model& m, size_t n, T** out) {
+    void* p = nullptr;
+    HIPCHK(h, hipMalloc(&p, n * sizeof(T) + 256));
+    m.allocs.push_back(p);
+    *out = reinterpret_cast<T*>(p);
+    return JG_OK;
+}
+
+template <class T>
+int upload(jg_handle* h, Model& m, const std::vector<T>& v, T** out) {
+    RET(walloc<T>(h, m, v.size(), out));
+    HIPCHK(h, hipMemcpy(*out, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    return JG_OK;
+}
+
+// Re-finalizing a model (the drivers reload the state_dict on every command) frees that model's previous device
+// weights and drops its bias-corrected layers first.
+template <class M>
+void drop_model(jg_handle* h, M& model) {
+    (void)hipStreamSynchronize(h->stream);
+    for (void* p : model.m.allocs) (void)hipFree(p);
+    model = M();
+}
+
+template <class T>
+int wsalloc(jg_handle* h, size_t n, T** out) {
+    hipError_t e = hipSuccess;
+    void* p = h->ws.alloc(n * sizeof(T), &e);
+    if (!p) JG_FAIL(h, JG_ERR_HIP, "workspace allocation of %zu bytes failed: %s", n * sizeof(T), hipGetErrorString(e));
+    *out = reinterpret_cast<T*>(p);
+    return JG_OK;
+}
+
+constexpr int FH = 270, FW = 480;
+inline size_t pad128(size_t rows) { return (rows + 127) / 128 * 128; }
+
+// fp32 audit stages (audit32.hip, JG_PREC_FP32 and option audit_stages on a handle finalized with audit_weights)
+enum { AUD_CONV = 1, AUD_GS = 2, AUD_JG = 4, AUD_CONTENT = 8, AUD_XLMR = 16, AUD_ALL = 31 };
+inline int audit_mask(const jg_handle* h) { return h->precision == JG_PREC_FP32 ? AUD_ALL : h->audit_stages; }
+
+// ------------------------------------------------------------------------------------ GEMM calls (linear.hip)
+struct Epi {
+    const float* scale = nullptr;
+    const float* res = nullptr;
+    long ldr = 0;
+    int res_mod = 0;
+    float* out32 = nullptr;
+    f16* out16 = nullptr;
+    long ldc = 0;
+    int relu = 0;
+    const LNp* ln = nullptr;      // fused residual + LayerNorm epilogue (when the GEMM can: see gemm_ln_fusable)
+    int ln_flavour = LN_STD;
+    // tiled token stream of the fused GestSync transformer (common.h): residual in / LayerNorm out planes, tiled A operand
+    const f16* res16 = nullptr;
+    int a_tiled = 0;
+    int no_bias = 0;              // the layer's bias is applied elsewhere (layer-0 qkv by linearity: it rides in the projected PE rows)
+    // implicit LayerNorm (GemmArgs::ln_mode): ln_stats = (mean, rstd) of the LayerNorm's input rows.  Mode 1: the layer is a folded
+    // consumer (Lin::c1h / c1f).  Mode 2: x_hi / x_lo = the token stream's planes (residual in, new rows out, in place),
+    // ln_gamma = that LayerNorm's weight (its bias is already part of the layer's packed bias), stat_out = the new rows' partial sums.
+    int ln_mode = 0;
+    const float* ln_stats = nullptr;
+    f16* x_hi = nullptr;
+    f16* x_lo = nullptr;
+    const float* ln_gamma = nullptr;
+    float* stat_out = nullptr;
+    int calib_rows = 0;           // calibration pass: only the first calib_rows rows of A are real (0: all M) -- short XLM-R batches are padded to 128 rows
+    // JG_PREC_FP16_RC: the M rows are rc_clips clips of rc_rpc rows each (0: no clip structure -> a run-time corrected layer runs hi+lo)
+    int rc_rpc = 0, rc_clips = 0;
+    const int* rc_valid = nullptr;    // device [rc_clips]: rows of each clip that are its own (jg_gestsync_clip_ragged) or nullptr
+};
+
+struct Epi32 {
+    const float* res = nullptr;
+    long ldr = 0;
+    int res_mod = 0;
+    int act = 0;          // 0 none, 1 ReLU, 2 exact GELU
+};
+
+int gemm(jg_handle* h, int stage, const f16* A, long lda, int M, const Lin& L, const Epi& e, const ConvGeom* g = nullptr);
+int gemm32(jg_handle* h, int stage, const float* A, long lda, int M, const Lin& L, float* out, const Epi32& e = Epi32(), const ConvGeom* g = nullptr);
+int gemm_x3(jg_handle* h, int stage, const float* A, long lda, int M, const Lin& L, float* out, const Epi32& e = Epi32());
+ConvGeom geom(int H, int W, int C, int KH, int KW, int SH, int SW, int PH, int PW, bool reorder = false);
+int post_norm_layer32(jg_handle* h, const EncLayer& L, float* x32, float* t32, float* qkv, float* att, float* hid, const float* mask, int B, int S,
+                      int H, int D, int Dff, int act, float* out);
+
+// ------------------------------------------------------------------------------------ weight packing (linear.hip)
+// layer kinds: which precision treatment a matrix gets under the handle's mode
+enum { LK_CONV = 0, LK_GESTURE = 1, LK_CONTENT = 2, LK_XLMR = 3 };      // LK_XLMR: bias-corrected like the gesture path (calibrated on token ids)
+const HostTensor* find(jg_handle* h, const std::string& name);
+int need(jg_handle* h, const std::string& name, int64_t numel, const HostTensor** out);
+int pack_matrix(jg_handle* h, Model& m, const std::vector<float>& w, const std::vector<float>& bias, int N, int K, int kind, Lin* L,
+                bool ln_consumer = false, bool keep32 = false, int diffuse_group = 0);
+int make_linear(jg_handle* h, Model& m, const std::string& wname, const std::string& bname, int N, int K, Lin* L, int kind = LK_GESTURE, bool keep32 = false);
+int make_ln(jg_handle* h, Model& m, const std::string& wname, const std::string& bname, int D, LNp* p);
+int make_conv(jg_handle* h, Model& m, const std::string& conv, const std::string& bn, int O, int I, int KT, int KH, int KW,
+              int slot, int kpad, Lin* L, int SH = 1, int SW = 1, bool reorder = false);
+int make_annotated_layer(jg_handle* h, Model& m, const std::string& p, int D, int Dff, EncLayer* L, int kind);
+int calibrate_gesture(jg_handle* h, const void* frames, int dtype, int B, int T, int models);
+int calibrate_xlmr(jg_handle* h, const int32_t* ids_dev, const int32_t* mask_dev, int B, int L);
+
+// ------------------------------------------------------------------------------------ models (gestsync.hip, jegal.hip, xlmr.hip)
+int finalize_gestsync(jg_handle* h);
+int gs_conv1_stage(jg_handle* h, const void* src, int src_u8, long sb, long st, long sh, long sw, long sc, int nclip, int T, int pad,
+                   f16* pooled, bool fill_all, unsigned** zscr);
+int gestsync_clip_impl(jg_handle* h, const void* frames, int dtype, int B, int T, float* out_feats, const int32_t* valid_host = nullptr);
+int gestsync_windows_impl(jg_handle* h, const float* x, int N, float* out, float* out_conv);
+int finalize_jegal(jg_handle* h);
+int jegal_gestures_impl(jg_handle* h, const float* feats, const float* mask, int B, int T, int align, float* out);
+int jegal_audio_impl(jg_handle* h, const float* mel, int B, int Tm, const int32_t* valid_host, float* out);
+int jegal_text_impl(jg_handle* h, const float* states, const float* mask, int B, int L, float* out);
+int fuse_content_impl(jg_handle* h, const float* fused, int rows, float* out);
+int finalize_xlmr(jg_handle* h);
+int xlmr_encode_impl(jg_handle* h, const int32_t* ids, const int32_t* amask, int B, int L, float* out);
+
+// n int32 values from the host into `dst` (device) on the handle's stream, through the pinned staging ring (api.hip)
+int upload_i32_async(jg_handle* h, const int32_t* src, size_t n, int32_t* dst);
+
+}  // namespace engine

@@ -1,7 +1,7 @@
 """Frames -> embedding parity against the oracle on inputs that are NOT uniform noise.
 
 Every frames -> embedding oracle comparison of rounds 1-3 drew its clips from synth.synth_frames (noise under a 110-row mask) -- the
-distribution the default precision mode's bias corrections are calibrated on (api.hip, calibrate_impl).  The reference's inputs
+distribution the default precision mode's bias corrections are calibrated on (linear.hip, calibrate_gesture).  The reference's inputs
 are natural crops (inference_embs.py:235-286): smooth, low contrast, saturated regions, a mask that follows the chin per frame.
 Three seeded families (synth.synth_frames_structured), two full-length clips each, in JG_PREC_FP16_BC (calibrated on the built-in
 noise clips), the calibration-free JG_PREC_FP16_W2 and the run-time corrected default JG_PREC_FP16_RC, measured errors printed."""

@@ -68,7 +68,7 @@ def test_jegal_gesture_long_clips(models, oracle_sd, T):
     assert r0 < TOL and r1 < TOL
     # The reference also computes the PADDED query rows of clip 1 (zero feature rows; the caller strips them): held to the
     # same 1e-3.  (Round 2 allowed 2e-3: the bias correction (w - fp16(w)).E[x] of the default mode is pure error on x = 0;
-    # the input projection proj_ip_rgb now keeps hi+lo weights in that mode, api.hip finalize_jegal.)
+    # the input projection proj_ip_rgb now keeps hi+lo weights in that mode, jegal.hip finalize_jegal.)
     assert rel(out[1], ref[1]) < TOL and rel(out[1, valid:], ref[1, valid:]) < TOL
 
 

@@ -75,7 +75,7 @@ def test_xlmr_properties_and_errors(xlmr):
 
 def test_xlmr_implicit_layernorm_and_lanes(xlmr):
     """Round 4: the default pass never materialises a LayerNorm (option xlmr_fold: un-normalised hi + lo token planes, LayerNorm
-    folded into the consumer GEMMs / recomputed in the producer epilogues, api.hip:xlmr_encode_folded) and runs a batch as two
+    folded into the consumer GEMMs / recomputed in the producer epilogues, xlmr.hip:xlmr_encode_folded) and runs a batch as two
     half batches on two streams.  Both against the explicit-LayerNorm pass (xlmr_fold=0) and the fp32 restatement; the lanes
     must not change a bit; hi+lo (default) and single-fp16 (calibrated) weights alike."""
     from jegal_amd._lib import Engine
