@@ -194,6 +194,16 @@ typedef struct jg_gemm_check {
     int ln_mode; const float* ln_stats; const void* xres_hi; const void* xres_lo; void* out_lo; float* stat_out;
 } jg_gemm_check;
 int jg_debug_gemm_check(jg_handle* h, const jg_gemm_check* c);
+/* The GEMM planner's answer for an argument set, without a handle, a device or a launch: which kernel instance launch_gemm would run
+ * (jegal_amd/csrc/gemm_plan.h).  Of `c` only the sizes and the null-ness of the pointers are read.  conv (optional): the launch is an
+ * implicit-GEMM convolution of this geometry (rowmap / const_in: whether ConvGeom's pointers are set).  a_tiled: the A operand is the
+ * tiled token plane.  num_cu: compute units of the device; lanes_active: the launch is part of a two-lane batch.  opt_names / opt_values:
+ * n_opts options as for jg_set_option ("gemm_*"; the defaults otherwise).  name receives the instance as jg_debug_last_kernel reports it,
+ * or "rejected" (launch_gemm would return an error and launch nothing; grid = lds = stagger = 0 then); grid = workgroups, lds = dynamic
+ * LDS bytes, stagger = de-phasing delay in 10-ns ticks.  Returns JG_ERR_ARG for bad arguments or an unknown option. */
+typedef struct jg_conv_shape { int H, W, C, KH, KW, PH, PW, tap_table, rowmap, const_in; } jg_conv_shape;
+int jg_debug_gemm_plan(const jg_gemm_check* c, const jg_conv_shape* conv, int a_tiled, int num_cu, int lanes_active, const char* const* opt_names,
+                       const int* opt_values, int n_opts, char* name, int name_len, int* grid, int* lds, int* stagger);
 /* fp32 GEMM of the audit mode (launch_gemm32): out = act(A W^T * scale + bias + res[m % res_mod]), act 0 / 1 ReLU / 2 exact GELU. */
 int jg_debug_gemm32(jg_handle* h, const float* A, int64_t lda, const float* W, int64_t ldw, int M, int N, int K, const float* scale,
                     const float* bias, const float* res, int64_t ldr, int res_mod, int act, float* out, int64_t ldc);

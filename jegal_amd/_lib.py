@@ -31,6 +31,11 @@ class GemmCheck(ctypes.Structure):
                 ("res", _P), ("ldr", _L), ("res_mod", _I), ("relu", _I), ("out32", _P), ("out16", _P), ("ldc", _L),
                 ("ln_w", _P), ("ln_b", _P), ("res16", _P),
                 ("ln_mode", _I), ("ln_stats", _P), ("xres_hi", _P), ("xres_lo", _P), ("out_lo", _P), ("stat_out", _P)]
+class ConvShape(ctypes.Structure):
+    """struct jg_conv_shape (include/jegal_hip.h): the part of a conv geometry the GEMM planner reads."""
+    _fields_ = [(k, _I) for k in ("H", "W", "C", "KH", "KW", "PH", "PW", "tap_table", "rowmap", "const_in")]
+
+
 _SIGS = {
     "jg_create": [_I, ctypes.POINTER(_P)],
     "jg_destroy": [_P],
@@ -51,6 +56,8 @@ _SIGS = {
     "jg_debug_gemm_ex": [_P, _P, _P, _I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_double)],
     "jg_debug_conv2_rowskip": [_P, ctypes.POINTER(ctypes.c_int)],
     "jg_debug_gemm_check": [_P, _P],
+    "jg_debug_gemm_plan": [_P, _P, _I, _I, _I, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(_I), _I, ctypes.c_char_p, _I,
+                           ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I)],
     "jg_debug_gemm32": [_P, _P, _L, _P, _L, _I, _I, _I, _P, _P, _P, _L, _I, _I, _P, _L],
     "jg_debug_gemm_x3": [_P, _P, _L, _P, _P, _L, _I, _I, _I, _P, _P, _L, _I, _I, _P, _L],
     "jg_debug_attention": [_P, _P, _P, _I, _I, _I, _I, _P],
@@ -113,6 +120,31 @@ def load_library():
     lib.jg_workspace_bytes.restype = ctypes.c_int64
     _lib = lib
     return lib
+
+
+def gemm_plan(num_cu=256, lanes_active=False, opts=None, conv=None, a_tiled=False, **fields):
+    """The GEMM planner's answer (jg_debug_gemm_plan) -> (instance name or "rejected", grid, lds bytes, stagger).  Needs no Engine and no
+    GPU.  fields: those of jg_gemm_check, as for Engine.debug_gemm_check; of a pointer field only its presence counts, so a tensor or
+    True stands for "set" (None / False / 0: NULL).  opts: engine options (gemm_*; "num_cu" overrides num_cu); conv: dict of the jg_conv_shape fields."""
+    lib = load_library()
+    c = GemmCheck()
+    ptr_fields = {k for k, t in GemmCheck._fields_ if t is _P}
+    for k, v in fields.items():
+        if k in ptr_fields:
+            v = 1 if isinstance(v, torch.Tensor) or bool(v) else None
+        setattr(c, k, v)
+    opts = dict(opts or {})
+    num_cu = opts.pop("num_cu", num_cu)
+    names = (ctypes.c_char_p * max(len(opts), 1))(*[k.encode() for k in opts])
+    values = (_I * max(len(opts), 1))(*[int(v) for v in opts.values()])
+    cs = ConvShape(**{k: int(v) for k, v in conv.items()}) if conv is not None else None
+    name = ctypes.create_string_buffer(128)
+    grid, lds, stagger = _I(), _I(), _I()
+    rc = lib.jg_debug_gemm_plan(ctypes.byref(c), ctypes.byref(cs) if cs is not None else None, int(bool(a_tiled)), int(num_cu), int(bool(lanes_active)),
+                                names, values, len(opts), name, 128, ctypes.byref(grid), ctypes.byref(lds), ctypes.byref(stagger))
+    if rc != 0:
+        raise JegalError(f"jg_debug_gemm_plan: bad arguments or unknown option ({rc})", rc)
+    return name.value.decode(), grid.value, lds.value, stagger.value
 
 
 class JegalError(RuntimeError):

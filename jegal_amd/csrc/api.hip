@@ -229,11 +229,10 @@ int jg_set_chunk(jg_handle* h, int c) {
 int jg_set_option(jg_handle* h, const char* name, int value) {
     if (!h || !name) return JG_ERR_ARG;
     EngineOpts& o = h->opts;
+    if (engine_opts_set(o, name, value)) return JG_OK;      // the launchers' own switches (gemm_*, attn_mfma, conv1_mfma16, conv1_zero_skip)
     if (!std::strcmp(name, "conv1_direct")) { h->conv1_direct = value != 0; return JG_OK; }
     if (!std::strcmp(name, "fuse_ln")) { h->fuse_ln = value != 0; return JG_OK; }
     if (!std::strcmp(name, "edge_dedup")) { h->edge_dedup = value != 0; return JG_OK; }
-    if (!std::strcmp(name, "conv1_mfma16")) { o.conv1_mfma16 = value != 0; return JG_OK; }
-    if (!std::strcmp(name, "conv1_zero_skip")) { o.conv1_zero_skip = value != 0; return JG_OK; }
     if (!std::strcmp(name, "conv2_row_skip")) { h->conv2_row_skip = value != 0; return JG_OK; }
     if (!std::strcmp(name, "ws_poison")) { h->ws_poison = value != 0; return JG_OK; }
     if (!std::strcmp(name, "jegal_fp32_ends")) { h->jegal_fp32_ends = value != 0; return JG_OK; }
@@ -292,15 +291,6 @@ int jg_set_option(jg_handle* h, const char* name, int value) {
         return JG_OK;
     }
     if (!std::strcmp(name, "qkv0_linear")) { h->qkv0_linear = value != 0; return JG_OK; }
-    if (!std::strcmp(name, "attn_mfma")) { o.attn_mfma = value != 0; return JG_OK; }
-    if (!std::strcmp(name, "gemm_glds")) { o.gemm_glds = value != 0; return JG_OK; }
-    if (!std::strcmp(name, "gemm_tall_tile")) { o.gemm_tall_tile = value != 0; return JG_OK; }
-    if (!std::strcmp(name, "gemm_small_tile")) { o.gemm_small_tile = value != 0; return JG_OK; }
-    if (!std::strcmp(name, "gemm_big_tile")) { o.gemm_big_tile = value != 0; return JG_OK; }
-    if (!std::strcmp(name, "gemm_tile")) { o.gemm_tile = value; return JG_OK; }
-    if (!std::strcmp(name, "gemm_counted")) { o.gemm_counted = value != 0; return JG_OK; }
-    if (!std::strcmp(name, "gemm_persistent")) { o.gemm_persistent = value != 0; return JG_OK; }
-    if (!std::strcmp(name, "gemm_stagger")) { o.gemm_stagger = value; return JG_OK; }
     JG_FAIL(h, JG_ERR_ARG, "unknown option '%s'", name);
 }
 

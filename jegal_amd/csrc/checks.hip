@@ -6,11 +6,30 @@ using namespace engine;
 // ---- kernel check points: one launch of a production launcher on the caller's operands, with the handle's options (which pick
 // the instance exactly as in production) and the handle's build (fp16 or bf16).  The launcher's own shape rules decide what is
 // valid: its hipErrorInvalidValue comes back as JG_ERR_ARG, and nothing was launched then.  (Handle internals and LAUNCH: engine.h.)
+// jg_debug_gemm_plan asks the GEMM planner (gemm_plan.h) the same question without a handle, a device or a launch.
 namespace {
 int check_result(jg_handle* h, hipError_t e, const char* what) {
     if (e == hipErrorInvalidValue) JG_FAIL(h, JG_ERR_ARG, "%s: the launcher rejects this shape / argument set", what);
     if (e != hipSuccess) JG_FAIL(h, JG_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
     return JG_OK;
+}
+// the GemmArgs of a jg_gemm_check
+GemmArgs gemm_check_args(const jg_gemm_check* c) {
+    GemmArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.A = static_cast<const f16*>(c->A); a.lda = c->lda;
+    a.Wh = static_cast<const f16*>(c->Wh); a.Wl = static_cast<const f16*>(c->Wl); a.ldw = c->ldw;
+    a.M = c->M; a.N = c->N; a.K = c->K;
+    a.scale = c->scale; a.bias = c->bias;
+    a.bias_clip = c->bias_clip; a.rpc = c->rpc; a.nclips = c->nclips;
+    a.res = c->res; a.ldr = c->ldr; a.res_mod = c->res_mod; a.relu = c->relu;
+    a.out32 = c->out32; a.out16 = static_cast<f16*>(c->out16); a.ldc = c->ldc;
+    a.ln_w = c->ln_w; a.ln_b = c->ln_b; a.ln_flavour = LN_STD;
+    a.res16 = static_cast<const f16*>(c->res16);
+    a.ln_mode = c->ln_mode; a.ln_stats = c->ln_stats;
+    a.xres_hi = static_cast<const f16*>(c->xres_hi); a.xres_lo = static_cast<const f16*>(c->xres_lo);
+    a.out_lo = static_cast<f16*>(c->out_lo); a.stat_out = c->stat_out;
+    return a;
 }
 }  // namespace
 
@@ -123,23 +142,33 @@ int jg_debug_gemm_check(jg_handle* h, const jg_gemm_check* c) {
         ((c->out32 || (c->out16 && !c->ln_w)) && c->ldc < c->N) || (c->res && (c->ldr < c->N || c->res_mod < 0)) ||
         (c->bias_clip && (c->rpc <= 0 || c->nclips <= 0)) || c->relu < 0 || c->relu > 2 || c->ln_mode < 0 || c->ln_mode > 2)
         JG_FAIL(h, JG_ERR_ARG, "jg_debug_gemm_check: bad arguments");
-    GemmArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.A = static_cast<const f16*>(c->A); a.lda = c->lda;
-    a.Wh = static_cast<const f16*>(c->Wh); a.Wl = static_cast<const f16*>(c->Wl); a.ldw = c->ldw;
-    a.M = c->M; a.N = c->N; a.K = c->K;
-    a.scale = c->scale; a.bias = c->bias;
-    a.bias_clip = c->bias_clip; a.rpc = c->rpc; a.nclips = c->nclips;
-    a.res = c->res; a.ldr = c->ldr; a.res_mod = c->res_mod; a.relu = c->relu;
-    a.out32 = c->out32; a.out16 = static_cast<f16*>(c->out16); a.ldc = c->ldc;
-    a.ln_w = c->ln_w; a.ln_b = c->ln_b; a.ln_flavour = LN_STD;
-    a.res16 = static_cast<const f16*>(c->res16);
-    a.ln_mode = c->ln_mode; a.ln_stats = c->ln_stats;
-    a.xres_hi = static_cast<const f16*>(c->xres_hi); a.xres_lo = static_cast<const f16*>(c->xres_lo);
-    a.out_lo = static_cast<f16*>(c->out_lo); a.stat_out = c->stat_out;
+    const GemmArgs a = gemm_check_args(c);
     EngineOpts o = h->opts;
     o.kname = h->kname;          // the name slot the launchers write
     return check_result(h, LAUNCH(h, launch_gemm, a, false, o, h->stream), "launch_gemm");
+}
+
+int jg_debug_gemm_plan(const jg_gemm_check* c, const jg_conv_shape* conv, int a_tiled, int num_cu, int lanes_active, const char* const* opt_names,
+                       const int* opt_values, int n_opts, char* name, int name_len, int* grid, int* lds, int* stagger) {
+    if (!c || c->M <= 0 || c->N <= 0 || c->K <= 0 || num_cu <= 0 || n_opts < 0 || (n_opts && (!opt_names || !opt_values)) || !name || name_len <= 0 ||
+        !grid || !lds || !stagger)
+        return JG_ERR_ARG;
+    GemmShape s = gemm_shape(gemm_check_args(c), false);
+    s.a_tiled = a_tiled != 0;
+    if (conv) {
+        s.conv = true;
+        s.H = conv->H; s.W = conv->W; s.C = conv->C; s.KH = conv->KH; s.KW = conv->KW; s.PH = conv->PH; s.PW = conv->PW;
+        s.tap_table = conv->tap_table; s.rowmap = conv->rowmap != 0; s.const_in = conv->const_in != 0;
+    }
+    EngineOpts o;
+    o.num_cu = num_cu;
+    o.lanes_active = lanes_active != 0;
+    for (int i = 0; i < n_opts; ++i)
+        if (!opt_names[i] || !engine_opts_set(o, opt_names[i], opt_values[i])) return JG_ERR_ARG;
+    const GemmPlan p = plan_gemm(s, o);
+    snprintf(name, (size_t)name_len, "%s", p.name);
+    *grid = (int)p.grid; *lds = (int)p.lds; *stagger = p.stagger;
+    return JG_OK;
 }
 
 int jg_debug_gemm32(jg_handle* h, const float* A, int64_t lda, const float* W, int64_t ldw, int M, int N, int K, const float* scale,

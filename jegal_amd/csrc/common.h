@@ -137,7 +137,7 @@ struct GemmArgs {
     float* stat_out;           // mode 2: [M][N / 64][2]
     // Per-clip bias (precision mode JG_PREC_FP16_RC, launch_rc_bias): row m takes bias_clip[min(m / rpc, nclips - 1)][n] instead of
     // bias[n].  LDS-DMA kernel only, through the fp16 row-transposing epilogue (out16 alone, no residual) or the LayerNorm-fused one;
-    // launch_gemm rejects anything else -- there is no path that would quietly drop the correction.
+    // the planner (gemm_plan.hip) rejects anything else -- there is no path that would quietly drop the correction.
     const float* bias_clip;    // [nclips][N] (the layer's bias already inside) or nullptr
     int rpc, nclips;
 };
@@ -167,7 +167,7 @@ struct EngineOpts {
     bool gemm_glds = true;               // LDS-DMA GEMM kernels (false: register-staged gemm_kernel everywhere)
     bool gemm_persistent = true;
     bool gemm_big_tile = true, gemm_small_tile = true, gemm_tall_tile = true;
-    int gemm_tile = 0;                   // plain GEMMs: 0 = pick by the cost estimate (launch_glds), 1 / 2 / 3 = force the 128x128 / 256x128 / 256x256 tile
+    int gemm_tile = 0;                   // plain GEMMs: 0 = pick by the cost estimate (plan_gemm), 1 / 2 / 3 = force the 128x128 / 256x128 / 256x256 tile
     int gemm_counted = 1;                // counted s_waitcnt between a tile's epilogue stores and the next tile's first DMA
     int gemm_stagger = 0;                // 10-ns ticks per phase (0: default policy, -1: off)
     bool lanes_active = false;           // the launch is part of a two-lane batch (api.hip, run_in_lanes): the other lane's kernels already
@@ -188,8 +188,8 @@ hipError_t engine_opts_init(EngineOpts& o, int device);      // queries the CU c
 void engine_opts_release(EngineOpts& o);
 
 // ---- launchers (each returns hipGetLastError()) -----------------------------------------
+// which instance a launch gets and which argument sets are accepted: plan_gemm (gemm_plan.h); a rejected set returns hipErrorInvalidValue
 hipError_t launch_gemm(const GemmArgs& a, bool conv, const EngineOpts& o, hipStream_t s);
-bool gemm_ln_fusable(const GemmArgs& a);
 // packed_bytes >= 0: frames whose metadata points outside [0, packed_bytes) or is misaligned come out zero instead of being read
 hipError_t launch_unpack_masked(const uint8_t* packed, const int* row0, const long long* offs, int n_frames, uint8_t* dst, hipStream_t s,
                                 long long packed_bytes = -1);
@@ -263,6 +263,8 @@ size_t col_sum_scratch_elems(int K);
 hipError_t launch_rc_bias(const f16* A, long lda, int tiled, int nclips, int rpc, const int* valid_rows, const f16* lo, const float* bias, int N, int K,
                           float* scratch, float* out, hipStream_t s);
 size_t rc_scratch_elems(int nclips, int K);
+// the shapes launch_rc_bias takes (its kernels' own limits; the GEMM that consumes the result has its rules in plan_gemm)
+inline bool rc_bias_ok(int N, int K, int tiled) { return (K == 512 || K == 2048) && (!tiled || K == 512) && !(N & 31); }
 hipError_t launch_ragged_mean(const float* x, const int32_t* offsets, int n, int D, float* out, hipStream_t s);
 hipError_t launch_sim_rank(const float* e1, const float* e2, int n_local, int n_total, int row_offset, int D,
                            int32_t* rank, int32_t* ties, hipStream_t s);

@@ -789,7 +789,7 @@ size_t rc_scratch_elems(int nclips, int K) { return (size_t)nclips * K; }
 hipError_t launch_rc_bias(const f16* A, long lda, int tiled, int nclips, int rpc, const int* valid_rows, const f16* lo, const float* bias, int N, int K,
                           float* scratch, float* out, hipStream_t s) {
     if (nclips <= 0 || rpc <= 0) return hipSuccess;
-    if ((K != 512 && K != 2048) || (tiled && K != 512) || (N & 31)) return hipErrorInvalidValue;
+    if (!rc_bias_ok(N, K, tiled)) return hipErrorInvalidValue;
     f16* mean16 = reinterpret_cast<f16*>(scratch);
     hipLaunchKernelGGL(rc_col_mean_kernel, dim3(nclips, K / 64), dim3(256), 0, s, A, lda, tiled, rpc, valid_rows, K, mean16);
     hipLaunchKernelGGL(rc_gemv_kernel, dim3(N / 32, (nclips + 31) / 32), dim3(256), 0, s, mean16, lo, bias, nclips, N, K, out);

@@ -5,6 +5,7 @@
 #define JG_BF16                  // the bf16 build's declarations (namespace bf): same launchers, f16 = __bf16
 #include "common.h"
 #undef JG_BF16
+#include "gemm_plan.h"
 #include "../../include/jegal_hip.h"
 #include "audit32.h"
 
@@ -323,7 +324,7 @@ struct Epi {
     f16* out16 = nullptr;
     long ldc = 0;
     int relu = 0;
-    const LNp* ln = nullptr;      // fused residual + LayerNorm epilogue (when the GEMM can: see gemm_ln_fusable)
+    const LNp* ln = nullptr;      // fused residual + LayerNorm epilogue (when the GEMM can: plan_gemm, gemm_plan.hip)
     int ln_flavour = LN_STD;
     // tiled token stream of the fused GestSync transformer (common.h): residual in / LayerNorm out planes, tiled A operand
     const f16* res16 = nullptr;

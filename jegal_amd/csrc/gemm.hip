@@ -16,7 +16,10 @@
 //   rounding, not activation rounding, dominates the end-to-end error (precision).
 // * CONV: the activation "row" m is an output pixel (img,oh,ow) of an NHWC tensor and
 //   k = (kh,kw,c); out-of-image taps are zero-filled at staging time.
+// * Host side (end of the file): launch_gemm asks the planner (gemm_plan.h / gemm_plan.hip) which instance a launch gets and
+//   launches that entry of one table of thunks; no admission rule and no tile choice lives in this file.
 #include "common.h"
+#include "gemm_plan.h"
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -273,7 +276,7 @@ __global__ __launch_bounds__(512) void gemm_glds_kernel(GemmArgs a, int n_tiles,
             total_tiles = ((Mrows + BM - 1) / BM) * n_tiles;
         }
     }
-    // ConvGeom::in_op / const_in (conv instances with SPR, which has no other meaning for CONV: launch_glds picks them when
+    // ConvGeom::in_op / const_in (conv instances with SPR, which has no other meaning for CONV: plan_gemm picks them when
     // const_in is set): input rows 0..rin-1 of an image were left out by the producer because they do not depend on the
     // position; the loader reads them from the const image of the input instead (same pixel, other base).  rin =
     // conv_skip_decode(s2[img], in_op) is per row (it rides in the low byte of xpix).
@@ -1037,8 +1040,9 @@ src = xsrc[i] + ((!XE && a.a_tiled) ? (long)sk0 * 128 : (long)sk0);        // ti
 #endif
 }
 
-// ---- host side.  Every tuning switch and per-device resource lives in the caller's EngineOpts (one per jg_handle):
-// nothing here is process-global except the "dynamic LDS attribute set" flags, which are per (kernel, device).
+// ---- host side: engine_opts_init / release, the launch thunks and launch_gemm.  Every tuning switch and per-device resource lives
+// in the caller's EngineOpts (one per jg_handle): nothing here is process-global except the "dynamic LDS attribute set" flags, which
+// are per (kernel instance, device).  The choice of the instance is the planner's (gemm_plan.hip).
 constexpr int MAX_DEV = 64;
 
 hipError_t engine_opts_init(EngineOpts& o, int device) {
@@ -1061,208 +1065,51 @@ void engine_opts_release(EngineOpts& o) {
     o.zeros = nullptr;
 }
 
-template <class K>
-static hipError_t ensure_lds_attr(K kernel, size_t lds, int device, bool* flags) {
-    if (device < 0 || device >= MAX_DEV) return hipErrorInvalidDevice;
-    if (!flags[device]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+// One launch thunk per entry of the instance table (gemm_plan.h): it owns the instance's "dynamic LDS attribute set" flags and
+// launches with the plan's figures.  Nothing is chosen here.
+using GemmThunk = hipError_t (*)(const GemmArgs&, const GemmPlan&, const EngineOpts&, hipStream_t);
+
+template <bool W2, bool CONV, int MI, int WM, int WN, bool LNF, bool SPR, int XE, bool C32>
+static hipError_t run_glds(const GemmArgs& a, const GemmPlan& p, const EngineOpts& o, hipStream_t s) {
+    static bool attr_set[MAX_DEV] = {};
+    if (o.device < 0 || o.device >= MAX_DEV) return hipErrorInvalidDevice;
+    if (!attr_set[o.device]) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_glds_kernel<W2, CONV, MI, WM, WN, LNF, SPR, XE, C32>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
         if (e != hipSuccess) return e;
-        flags[device] = true;
+        attr_set[o.device] = true;
     }
-    return hipSuccess;
-}
-
-template <bool W2, bool CONV, int MI, int WM, int WN, bool SPR = false, int XE = 0, bool C32 = false>
-static hipError_t launch_glds_cfg(const GemmArgs& a, const EngineOpts& o, hipStream_t s) {
-    static bool attr_set[MAX_DEV] = {};
-    constexpr int BM = 16 * MI * WM, BN = 64 * WN;
-    constexpr size_t lds = 2 * (size_t)(BM * 128 + BN * 128 * (W2 ? 2 : 1));
-    hipError_t e = ensure_lds_attr(gemm_glds_kernel<W2, CONV, MI, WM, WN, false, SPR, XE, C32>, lds, o.device, attr_set);
-    if (e != hipSuccess) return e;
     if (!o.zeros) return hipErrorInvalidValue;
-    const int mt = (a.M + BM - 1) / BM, nt = (a.N + BN - 1) / BN;
-    const int tiles = mt * nt;
-    const int grid = o.gemm_persistent ? (tiles < o.num_cu ? tiles : o.num_cu) : tiles;
-    // De-phasing the workgroups (4 phases, 2 us apart; the last phase falls on the workgroups that run one tile fewer):
-    // once the outputs were nontemporal the epilogues became HBM-write-burst bound (every CU stores its 128 KB at the
-    // same moment) and spreading them pays: qkv 157 -> 146 us.  Only for long plain GEMMs (>= 4 rounds); the LN-fused
-    // and conv kernels and short launches measured neutral or slower.  Option gemm_stagger: ticks of 10 ns, -1 = off.
-    // Round 3: the delay only pays when the last round is less than half full - the highest block ids, delayed longest, then run one
-    // tile fewer (ff0, 3.08 rounds: 79 -> 75 us; N = 1024, 6.16 rounds: 129 -> 117 us; qkv 9.23: 175 -> 170; with a nearly full last
-    // round it costs 2-3 %), short launches included (round 2: >= 4 rounds).  Inside the two-lane batches the plain GEMMs stay
-    // un-staggered: the other lane's kernels already spread the store bursts and the delay only costs (+0.8 % per step measured).
-    const int last_round = tiles % o.num_cu;
-    const int stagger = o.gemm_stagger < 0 ? 0 : o.gemm_stagger > 0 ? o.gemm_stagger
-                        : (!CONV && !o.lanes_active && tiles > o.num_cu && 2 * last_round < o.num_cu ? 300 : 0);
-    record_kernel(o.kname, "gemm_glds_kernel<%d,%d,%d,%d,%d,0,%d,%d,%d>", (int)W2, (int)CONV, MI, WM, WN, (int)SPR, XE, (int)C32);
-    hipLaunchKernelGGL((gemm_glds_kernel<W2, CONV, MI, WM, WN, false, SPR, XE, C32>), dim3((unsigned)grid), dim3(512), lds, s, a, nt, tiles, o.zeros,
-                       o.gemm_counted | (stagger << 8));
+    record_kernel(o.kname, "%s", p.name);
+    hipLaunchKernelGGL((gemm_glds_kernel<W2, CONV, MI, WM, WN, LNF, SPR, XE, C32>), dim3(p.grid), dim3(512), p.lds, s, a, p.n_tiles, p.total_tiles, o.zeros,
+                       o.gemm_counted | (p.stagger << 8));
     return hipGetLastError();
-}
-
-template <bool CONV>
-static hipError_t launch_glds_ln(const GemmArgs& a, const EngineOpts& o, hipStream_t s) {
-    static bool attr_set[MAX_DEV] = {};
-    constexpr size_t lds = 2 * (size_t)(128 * 128 + 512 * 128);          // 160 KiB: the whole LDS
-    hipError_t e = ensure_lds_attr(gemm_glds_kernel<false, CONV, 8, 1, 8, true>, lds, o.device, attr_set);
-    if (e != hipSuccess) return e;
-    if (!o.zeros) return hipErrorInvalidValue;
-    const int tiles = (a.M + 127) / 128;
-    const int grid = tiles < o.num_cu ? tiles : o.num_cu;
-    // De-phasing (see launch_glds_cfg), round 3: in this kernel every workgroup reaches its store / reload phase at the same moment
-    // and that phase is an HBM burst (100 MB per round in ~10 us) while the k loops leave HBM idle.  Four start phases spread it;
-    // the delay is free when the last round is less than half full, because the highest block ids - the ones delayed longest -
-    // run one tile fewer: out_proj 108 -> 94 us, linear2 265 -> 256 us at M = 100 800 (3.08 rounds), 52 -> 48 us at 1.15 rounds;
-    // with a nearly full last round it costs what it delays (1.92 rounds: 58 -> 61 us), so it is off there.
-    const int last_round = tiles % o.num_cu;
-    const int auto_stagger = tiles > o.num_cu && 2 * last_round < o.num_cu ? (a.K <= 1024 ? 500 : 1400) : 0;
-    const int stagger = o.gemm_stagger < 0 ? 0 : o.gemm_stagger > 0 ? o.gemm_stagger : auto_stagger;
-    record_kernel(o.kname, "gemm_glds_kernel<0,%d,8,1,8,1,0,0,0>", (int)CONV);
-    hipLaunchKernelGGL((gemm_glds_kernel<false, CONV, 8, 1, 8, true>), dim3((unsigned)grid), dim3(512), lds, s, a, 1, tiles, o.zeros,
-                       o.gemm_counted | (stagger << 8));
-    return hipGetLastError();
-}
-
-bool gemm_ln_fusable(const GemmArgs& a) {
-    return a.Wl == nullptr && a.N == 512 && a.K % 64 == 0 && a.M >= 1024 && a.lda % 8 == 0 && a.ldw % 8 == 0 && !a.relu && !a.scale &&
-           !a.res && !a.out32 && a.res16 && a.out16 && !a.a_tiled;
-}
-
-template <bool W2, bool CONV>
-static hipError_t launch_glds(const GemmArgs& a, const EngineOpts& o, hipStream_t s) {
-    // small problems (the JEGAL branch: M = B*T = 4800 tokens) would leave most CUs idle with 256-row tiles:
-    // 128x128 tiles (32x64 wave tiles) give 4x the workgroups
-    const long tiles256 = (long)((a.M + 255) / 256) * ((a.N + 127) / 128);
-    const long tiles_big = (long)((a.M + 255) / 256) * ((a.N + 255) / 256);        // 256x256 tiles: fewer than CUs -> under-filled
-    if constexpr (CONV) {
-        if (a.g.rowmap && a.g.const_in) {   // consumer of a row-skipping producer: the instances whose loader can read the const image
-            if (o.gemm_small_tile && (tiles256 < 200 || tiles_big < 224)) return launch_glds_cfg<W2, true, 2, 4, 2, true>(a, o, s);
-            if constexpr (!W2) {
-                if (o.gemm_big_tile && a.N >= 256 && a.N % 256 == 0) return launch_glds_cfg<false, true, 8, 2, 4, true>(a, o, s);
-            }
-            return launch_glds_cfg<W2, true, 4, 4, 2, true>(a, o, s);
-        }
-    }
-    if constexpr (!CONV) {
-        // Plain GEMMs: pick the tile by a cost estimate, rounds of one tile per CU x (k-tiles x time per k-tile + epilogue), with
-        // the per-tile figures measured on the box (tools/gemm_tiles.py; us, L2-resident operands): bigger tiles move fewer
-        // bytes per FLOP through the CU's LDS-DMA path but fill fewer CUs / leave emptier last rounds.  Every instance
-        // accumulates k in the same order, so the choice never changes a bit of the result.  (Round 2 took the 128x128 tile
-        // whenever fewer than 224 of the 256x256 tiles existed: M = 4800 x N = 2048 ran three rounds of small tiles instead of
-        // one round of 152 big ones, and XLM-R's N = 768 layers likewise.)
-        const int nk = (a.K + 63) / 64;
-        auto est = [&](int bm, int bn, double kt_us, double epi_us) {
-            const long tiles = (long)((a.M + bm - 1) / bm) * ((a.N + bn - 1) / bn);
-            return (double)((tiles + o.num_cu - 1) / o.num_cu) * (nk * kt_us + epi_us);
-        };
-        if (a.ln_mode) {
-            // implicit-LayerNorm epilogues (XE instances): single fp16 weights -> 256x256 or 128x128, hi+lo -> 256x128 or 128x128, by the
-            // same cost estimate
-            auto go = [&](auto xe) -> hipError_t {
-                constexpr int X = decltype(xe)::value;
-                if constexpr (W2) {
-                    if (est(128, 128, 1.25, 1.0) < est(256, 128, 1.6, 1.6) && o.gemm_tile != 2) return launch_glds_cfg<true, false, 2, 4, 2, false, X>(a, o, s);
-                    return launch_glds_cfg<true, false, 4, 4, 2, false, X>(a, o, s);
-                } else {
-                    const bool big_ok = a.N % 256 == 0;
-                    if (!big_ok || (est(128, 128, 0.95, 1.0) < est(256, 256, 1.45, 2.7) && o.gemm_tile != 3) || o.gemm_tile == 1)
-                        return launch_glds_cfg<false, false, 2, 4, 2, false, X>(a, o, s);
-                    if (a.K <= 1024) return launch_glds_cfg<false, false, 8, 2, 4, true, X>(a, o, s);
-                    return launch_glds_cfg<false, false, 8, 2, 4, false, X>(a, o, s);
-                }
-            };
-            return a.ln_mode == 1 ? go(std::integral_constant<int, 1>{}) : go(std::integral_constant<int, 2>{});
-        }
-        const bool can_big = !W2 && o.gemm_big_tile && a.N >= 256 && a.N % 256 == 0;
-        const double e_small = o.gemm_small_tile ? est(128, 128, W2 ? 1.25 : 0.95, 1.0) : 1e30;
-        const double e_mid = est(256, 128, W2 ? 1.6 : 1.2, 1.6);
-        const double e_big = can_big ? est(256, 256, 1.45, 2.7) : 1e30;
-        int pick = e_big <= e_mid && e_big <= e_small ? 3 : (e_mid <= e_small ? 2 : 1);
-        if (o.gemm_tile >= 1 && o.gemm_tile <= 3 && (o.gemm_tile != 3 || can_big)) pick = o.gemm_tile;
-        if (pick == 1) return launch_glds_cfg<W2, false, 2, 4, 2>(a, o, s);
-        if constexpr (!W2) {
-            if (pick == 3) {
-                if (a.K <= 1024) return launch_glds_cfg<false, false, 8, 2, 4, true>(a, o, s);       // short k loops: spread DMA issue
-                return launch_glds_cfg<false, false, 8, 2, 4>(a, o, s);
-            }
-        }
-        return launch_glds_cfg<W2, false, 4, 4, 2>(a, o, s);
-    }
-    if (o.gemm_small_tile && (tiles256 < 200 || tiles_big < 224)) return launch_glds_cfg<W2, CONV, 2, 4, 2>(a, o, s);
-    if constexpr (!W2) {
-        if (o.gemm_big_tile && a.N >= 256 && a.N % 256 == 0) {
-            if (!CONV && a.K <= 1024) return launch_glds_cfg<false, CONV, 8, 2, 4, !CONV>(a, o, s);       // short k loops: spread DMA issue
-            return launch_glds_cfg<false, CONV, 8, 2, 4>(a, o, s);
-        }
-        // N = 128 (conv2): 512x128 block tile, the whole 160 KiB of LDS -- the activation side dominates the
-        // L2->LDS traffic there, a taller tile halves the weight re-reads per activation byte
-        if constexpr (CONV) {
-            if (o.gemm_tall_tile && a.N == 128 && a.M >= 512 * 256) return launch_glds_cfg<false, true, 8, 4, 2>(a, o, s);
-        }
-    }
-    return launch_glds_cfg<W2, CONV, 4, 4, 2>(a, o, s);
 }
 
 template <int WM, int WN, bool CONV, bool W2>
-static hipError_t launch_variant(const GemmArgs& a, const EngineOpts& o, hipStream_t s) {
-    constexpr int BM = 64 * WM, BN = 64 * WN;
-    record_kernel(o.kname, "gemm_kernel<%d,%d,%d,%d>", WM, WN, (int)CONV, (int)W2);
-    const long mt = (a.M + BM - 1) / BM, nt = (a.N + BN - 1) / BN;
-    const size_t lds = (size_t)(BM + BN * (W2 ? 2 : 1)) * 128;
-    hipLaunchKernelGGL((gemm_kernel<WM, WN, CONV, W2>), dim3((unsigned)(mt * nt)), dim3(256), lds, s, a);
+static hipError_t run_staged(const GemmArgs& a, const GemmPlan& p, const EngineOpts& o, hipStream_t s) {
+    record_kernel(o.kname, "%s", p.name);
+    hipLaunchKernelGGL((gemm_kernel<WM, WN, CONV, W2>), dim3(p.grid), dim3(256), p.lds, s, a);
     return hipGetLastError();
 }
 
+static constexpr GemmThunk GEMM_THUNKS[] = {
+#define X(W2, CONV, MI, WM, WN, LNF, SPR, XE, C32) run_glds<W2, CONV, MI, WM, WN, LNF, SPR, XE, C32>,
+    JG_GEMM_GLDS_INSTANCES(X)
+#undef X
+#define X(WM, WN, CONV, W2) run_staged<WM, WN, CONV, W2>,
+    JG_GEMM_STAGED_INSTANCES(X)
+#undef X
+};
+static_assert(sizeof(GEMM_THUNKS) / sizeof(GEMM_THUNKS[0]) == GEMM_NUM_INSTANCES, "one thunk per table entry");
+
+// shape of the arguments -> plan (gemm_plan.hip: every rule lives there) -> the table
 hipError_t launch_gemm(const GemmArgs& a, bool conv, const EngineOpts& o, hipStream_t s) {
     if (a.M <= 0) return hipSuccess;
-    if (a.ln_w) {
-        if (conv || !gemm_ln_fusable(a) || (a.bias_clip && (a.rpc < 128 || a.nclips <= 0))) return hipErrorInvalidValue;
-        return launch_glds_ln<false>(a, o, s);
-    }
-    const bool w2 = a.Wl != nullptr;
-    const bool narrow = a.N <= 64;
-    if (a.bias_clip) {
-        // per-clip bias: only the LDS-DMA kernel's fp16 row epilogue knows it (the LayerNorm-fused launch returned above); rpc >= 256
-        // keeps a tile within two clips' reach of the straddle path's per-block lookup
-        const bool ok = !conv && !a.ln_mode && o.gemm_glds && a.rpc >= 256 && a.nclips > 0 && a.K % 64 == 0 && a.M >= 128 && a.lda % 8 == 0 && a.ldw % 8 == 0 &&
-                        a.N % 128 == 0 && a.out16 && !a.out32 && !a.res && (a.ldc & 7) == 0 && !narrow;
-        if (!ok) return hipErrorInvalidValue;
-    }
-    if (a.ln_mode) {
-        // implicit LayerNorm: LDS-DMA instances with the fast epilogues only (whole tiles along n, 16-byte rows); anything else is a
-        // caller error -- there is no slow path that would quietly ignore the statistics
-        const bool shape_ok = !conv && o.gemm_glds && a.K % 64 == 0 && a.M >= 128 && a.lda % 8 == 0 && a.ldw % 8 == 0 && a.N % 128 == 0 && a.ldc % 8 == 0;
-        const bool mode1_ok = a.ln_mode == 1 && a.ln_stats && a.scale && a.bias && a.out16 && !a.out32 && !a.res;
-        const bool mode2_ok = a.ln_mode == 2 && a.ln_stats && a.scale && a.bias && a.out16 && a.out_lo && a.xres_hi && a.xres_lo && a.stat_out &&
-                              !a.out32 && !a.res && !a.relu;
-        if (!shape_ok || !(mode1_ok || mode2_ok) || a.ln_w || a.a_tiled) return hipErrorInvalidValue;
-        return w2 ? launch_glds<true, false>(a, o, s) : launch_glds<false, false>(a, o, s);
-    }
-    if (a.a_tiled && (conv || narrow || !o.gemm_glds || a.K != 512 || a.M < 128 || a.N % 128)) return hipErrorInvalidValue;   // LDS-DMA kernel only
-    if (conv) {
-        if (a.res) return hipErrorInvalidValue;          // the conv instances are compiled without the residual path
-        const bool coords_ok = a.g.H + a.g.PH < 2048 && a.g.W + a.g.PW < 2048 && a.M < (1 << 24);      // packed pixel coordinates / rowmap entries
-        // C = 32 -> N = 64 (the second audio conv): its own LDS-DMA instance, 256x64 tiles (round 5; before: the register-staged kernel)
-        if (o.gemm_glds && !w2 && a.N == 64 && a.g.C == 32 && a.K % 32 == 0 && a.K == a.g.KH * a.g.KW * 32 && !a.g.tap_table && !a.g.rowmap && a.M >= 256 &&
-            coords_ok && a.out16 && !a.out32 && (a.ldc & 7) == 0 && (a.ldw & 7) == 0)
-            return launch_glds_cfg<false, true, 2, 8, 1, false, 0, true>(a, o, s);
-        if (narrow) return w2 ? launch_variant<4, 1, true, true>(a, o, s) : launch_variant<4, 1, true, false>(a, o, s);
-        if (o.gemm_glds && a.M >= 256 && a.g.C % 64 == 0 && a.N % 128 == 0 && coords_ok) return w2 ? launch_glds<true, true>(a, o, s) : launch_glds<false, true>(a, o, s);
-        if (a.g.rowmap) return hipErrorInvalidValue;          // only the LDS-DMA kernel knows the compaction
-        return w2 ? launch_variant<2, 2, true, true>(a, o, s) : launch_variant<2, 2, true, false>(a, o, s);
-    }
-    // every epilogue stores 4 columns per lane (16 / 8 bytes) and reads the residual the same way; the register-staged kernel below
-    // also loads A and W in 8-element (16-byte) pieces and only masks whole pieces against K: anything else would read columns >= K
-    if (a.N % 4 || a.ldc % 4 || (a.res && a.ldr % 4)) return hipErrorInvalidValue;
-    const bool staged_ok = a.K % 8 == 0 && a.lda % 8 == 0 && a.ldw % 8 == 0;
-    if (narrow) {
-        if (!staged_ok) return hipErrorInvalidValue;
-        return w2 ? launch_variant<4, 1, false, true>(a, o, s) : launch_variant<4, 1, false, false>(a, o, s);
-    }
-    if (o.gemm_glds && a.K % 64 == 0 && a.M >= 128 && a.lda % 8 == 0 && a.ldw % 8 == 0 && a.N % 128 == 0)
-        return w2 ? launch_glds<true, false>(a, o, s) : launch_glds<false, false>(a, o, s);
-    if (!staged_ok) return hipErrorInvalidValue;
-    return w2 ? launch_variant<2, 2, false, true>(a, o, s) : launch_variant<2, 2, false, false>(a, o, s);
+    // (the planner reads the options through the fp16 build's EngineOpts; the two builds' structs are layout-identical, engine.h)
+    const GemmPlan p = plan_gemm(gemm_shape(a, conv), reinterpret_cast<const ::EngineOpts&>(o));
+    if (!p.ok()) return hipErrorInvalidValue;
+    return GEMM_THUNKS[p.instance](a, p, o, s);
 }
 
 JG_NS_END

@@ -1,0 +1,112 @@
+// The GEMM launch policy of libjegal_hip: which kernel instance a launch gets and which argument sets the GEMM accepts.
+//
+// plan_gemm() (gemm_plan.hip) is the ONE place that decides.  launch_gemm (gemm.hip) derives a GemmShape from its GemmArgs, asks, and
+// launches the instance the plan names; the host units ask the same function before they commit to a form (linear.hip: the run-time
+// corrected form of a call; gestsync.hip: the fused transformer plan and the row-skipping conv chain), and jg_debug_gemm_plan
+// (checks.hip) shows the answer on a machine without a GPU.  The choice does not depend on the 16-bit operand type, so this header
+// is included once and is not part of the fp16 / bf16 double include of common.h: there is one planner in the library.
+#pragma once
+#include <cstddef>
+
+struct EngineOpts;      // common.h, the fp16 build's (the bf16 build's struct is layout-identical: engine.h)
+
+// ---- the instance table: every gemm_glds_kernel / gemm_kernel instantiation the library holds per build, each exactly once.
+// gemm_glds_kernel<W2, CONV, MI, WM, WN, LNF, SPR, XE, C32> (LDS-DMA; block tile 16 MI WM x 64 WN) ...
+#define JG_GEMM_GLDS_INSTANCES(X)                                                                                                  \
+    /* plain Linear: 128x128, 256x128 (single / hi+lo weights), 256x256 (SPR: K <= 1024) */                                        \
+    X(0, 0, 2, 4, 2, 0, 0, 0, 0) X(1, 0, 2, 4, 2, 0, 0, 0, 0) X(0, 0, 4, 4, 2, 0, 0, 0, 0) X(1, 0, 4, 4, 2, 0, 0, 0, 0)            \
+    X(0, 0, 8, 2, 4, 0, 1, 0, 0) X(0, 0, 8, 2, 4, 0, 0, 0, 0)                                                                      \
+    /* residual + LayerNorm fused, 128x512: the whole LDS */                                                                       \
+    X(0, 0, 8, 1, 8, 1, 0, 0, 0)                                                                                                   \
+    /* implicit-LayerNorm consumer (XE = 1) and producer (XE = 2) epilogues */                                                     \
+    X(0, 0, 2, 4, 2, 0, 0, 1, 0) X(1, 0, 2, 4, 2, 0, 0, 1, 0) X(1, 0, 4, 4, 2, 0, 0, 1, 0) X(0, 0, 8, 2, 4, 0, 1, 1, 0)            \
+    X(0, 0, 8, 2, 4, 0, 0, 1, 0)                                                                                                   \
+    X(0, 0, 2, 4, 2, 0, 0, 2, 0) X(1, 0, 2, 4, 2, 0, 0, 2, 0) X(1, 0, 4, 4, 2, 0, 0, 2, 0) X(0, 0, 8, 2, 4, 0, 1, 2, 0)            \
+    X(0, 0, 8, 2, 4, 0, 0, 2, 0)                                                                                                   \
+    /* conv: 128x128, 256x128, 256x256, the tall 512x128 tile (conv2) and the C = 32 instance (256x64) */                          \
+    X(0, 1, 2, 4, 2, 0, 0, 0, 0) X(1, 1, 2, 4, 2, 0, 0, 0, 0) X(0, 1, 4, 4, 2, 0, 0, 0, 0) X(1, 1, 4, 4, 2, 0, 0, 0, 0)            \
+    X(0, 1, 8, 2, 4, 0, 0, 0, 0) X(0, 1, 8, 4, 2, 0, 0, 0, 0) X(0, 1, 2, 8, 1, 0, 0, 0, 1)                                         \
+    /* conv behind a row-skipping producer (SPR: the loader reads ConvGeom::const_in) */                                           \
+    X(0, 1, 2, 4, 2, 0, 1, 0, 0) X(1, 1, 2, 4, 2, 0, 1, 0, 0) X(0, 1, 4, 4, 2, 0, 1, 0, 0) X(1, 1, 4, 4, 2, 0, 1, 0, 0)            \
+    X(0, 1, 8, 2, 4, 0, 1, 0, 0)
+// ... and gemm_kernel<WM, WN, CONV, W2> (register-staged; block tile 64 WM x 64 WN)
+#define JG_GEMM_STAGED_INSTANCES(X)                                                                                                \
+    X(4, 1, 0, 0) X(4, 1, 0, 1) X(2, 2, 0, 0) X(2, 2, 0, 1) X(4, 1, 1, 0) X(4, 1, 1, 1) X(2, 2, 1, 0) X(2, 2, 1, 1)
+
+struct GemmInstance {
+    const char* name;       // what record_kernel writes (jg_debug_last_kernel)
+    int key[10];            // {LDS-DMA kernel (512 threads) or register-staged (256), W2, CONV, MI, WM, WN, LNF, SPR, XE, C32}
+};
+constexpr GemmInstance GEMM_INSTANCES[] = {
+#define X(W2, CONV, MI, WM, WN, LNF, SPR, XE, C32) \
+    {"gemm_glds_kernel<" #W2 "," #CONV "," #MI "," #WM "," #WN "," #LNF "," #SPR "," #XE "," #C32 ">", {1, W2, CONV, MI, WM, WN, LNF, SPR, XE, C32}},
+    JG_GEMM_GLDS_INSTANCES(X)
+#undef X
+#define X(WM, WN, CONV, W2) {"gemm_kernel<" #WM "," #WN "," #CONV "," #W2 ">", {0, W2, CONV, 4, WM, WN, 0, 0, 0, 0}},
+    JG_GEMM_STAGED_INSTANCES(X)
+#undef X
+};
+constexpr int GEMM_NUM_INSTANCES = sizeof(GEMM_INSTANCES) / sizeof(GEMM_INSTANCES[0]);
+
+// ---- minimum row counts of the routes (the planner's own rules use them; the host pads or asks, it does not restate them)
+constexpr int GEMM_GLDS_MIN_ROWS = 128;         // a Linear launch reaches the LDS-DMA kernel from this many rows (shorter batches: pad with zero rows)
+constexpr int GEMM_GLDS_CONV_MIN_ROWS = 256;    // ... and a conv launch from this many output pixels
+constexpr int GEMM_LN_FUSED_MIN_ROWS = 1024;    // residual + LayerNorm fused (row-wide 128x512 tiles)
+constexpr int GEMM_CLIP_MIN_RPC = 256;          // per-clip bias through the fp16 row epilogue: rows per clip (a tile stays within two clips' reach)
+constexpr int GEMM_LN_CLIP_MIN_RPC = 128;       // ... through the LayerNorm-fused epilogue (128-row tiles)
+
+// Everything the choice depends on and nothing it does not: sizes, which operands / outputs are present, plain values.  No pointers.
+struct GemmShape {
+    long M;
+    int N, K;
+    long lda, ldw, ldc, ldr;
+    bool w2;                                    // lo weights present
+    bool out16, out32, res, scale, bias, bias_clip, ln_w, res16, a_tiled;
+    bool ln_stats, xres_hi, xres_lo, out_lo, stat_out;      // ln_mode 2's planes and the statistics
+    int relu, ln_mode, rpc, nclips;
+    bool conv;                                  // implicit-GEMM convolution: the geometry below counts
+    int H, W, C, KH, KW, PH, PW, tap_table;
+    bool rowmap, const_in;
+
+    template <class Geom>
+    void set_geom(const Geom& g) {
+        conv = true;
+        H = g.H; W = g.W; C = g.C; KH = g.KH; KW = g.KW; PH = g.PH; PW = g.PW; tap_table = g.tap_table;
+        rowmap = g.rowmap != nullptr; const_in = g.const_in != nullptr;
+    }
+};
+
+// The shape of a GemmArgs (either build's)
+template <class Args>
+inline GemmShape gemm_shape(const Args& a, bool conv) {
+    GemmShape s = {};
+    s.M = a.M; s.N = a.N; s.K = a.K; s.lda = a.lda; s.ldw = a.ldw; s.ldc = a.ldc; s.ldr = a.ldr;
+    s.w2 = a.Wl != nullptr;
+    s.out16 = a.out16 != nullptr; s.out32 = a.out32 != nullptr; s.res = a.res != nullptr; s.scale = a.scale != nullptr;
+    s.bias = a.bias != nullptr; s.bias_clip = a.bias_clip != nullptr; s.ln_w = a.ln_w != nullptr; s.res16 = a.res16 != nullptr;
+    s.a_tiled = a.a_tiled != 0;
+    s.ln_stats = a.ln_stats != nullptr; s.xres_hi = a.xres_hi != nullptr; s.xres_lo = a.xres_lo != nullptr; s.out_lo = a.out_lo != nullptr;
+    s.stat_out = a.stat_out != nullptr;
+    s.relu = a.relu; s.ln_mode = a.ln_mode; s.rpc = a.rpc; s.nclips = a.nclips;
+    if (conv) s.set_geom(a.g);
+    return s;
+}
+
+// The verdict: rejected (instance < 0: launch_gemm returns hipErrorInvalidValue and launches nothing), or one entry of GEMM_INSTANCES
+// with its launch figures.
+struct GemmPlan {
+    int instance = -1;
+    const char* name = "rejected";
+    unsigned grid = 0;
+    size_t lds = 0;
+    int n_tiles = 0, total_tiles = 0;           // tiles along n / in all (the LDS-DMA kernels' arguments)
+    int stagger = 0;                            // de-phasing delay in 10-ns ticks per phase (LDS-DMA kernels; 0: none)
+    bool ok() const { return instance >= 0; }
+    bool glds() const { return instance >= 0 && GEMM_INSTANCES[instance].key[0]; }
+};
+
+// Pure: no HIP call, dereferences nothing, keeps no state.  Reads the gemm_* options, num_cu and lanes_active of `o`.
+GemmPlan plan_gemm(const GemmShape& s, const EngineOpts& o);
+
+// The EngineOpts half of jg_set_option ("gemm_*", "attn_mfma", "conv1_mfma16", "conv1_zero_skip"): true if `name` is one of them
+bool engine_opts_set(EngineOpts& o, const char* name, int value);

@@ -19,6 +19,8 @@ static void gs_conv_geoms(ConvGeom g[5]) {
 static int gs_build_const_chain(jg_handle* h) {
     GestSyncModel& gs = h->gs;
     gs.c2C = gs.c3C = gs.c4C = gs.c5C = nullptr;
+    // (option gemm_glds is the policy here -- the chain is built before any launch shape is known; which launches then reach the LDS-DMA
+    // conv kernel is plan_gemm's answer, gs_conv_stack)
     if (!h->opts.gemm_glds || h->bf16) return JG_OK;      // the chain starts from conv1_direct's constant (fp16 build only)
     constexpr int NC = 4;
     f16 *zc, *poolC, *c2C, *c3C, *c4C, *c5C;
@@ -160,9 +162,17 @@ static int gs_conv_stack(jg_handle* h, const void* src, int src_u8, long sb, lon
     // Position-independent leading rows (common.h, ConvGeom::rowmap): the zero-band scan of the direct conv1 leaves every position's
     // count s2 in zscr; conv2 .. conv5 leave those rows out PER POSITION (compacted row maps built on the device) and conv3 .. conv5 and
     // the last max-pool read them from the const chain.  Only the LDS-DMA conv kernel knows how, so every layer of the chain must
-    // take that path.
-    const bool rowskip = h->opts.conv1_zero_skip && h->conv2_row_skip && h->opts.gemm_glds && gs.c2C && NF * 10 * 10 >= 256 &&
-                         NF * 20 * 37 < (1L << 24);
+    // take that path: the planner is asked about conv2 .. conv5 of this launch with a row map.
+    const Lin* cl[4] = {&gs.c2, &gs.c3, &gs.c4, &gs.c5};
+    bool rowskip = h->opts.conv1_zero_skip && h->conv2_row_skip && gs.c2C;
+    for (int l = 0; l < 4 && rowskip; ++l) {
+        GemmShape q = {};
+        q.set_geom(g[l + 1]);
+        q.rowmap = true; q.const_in = l > 0;
+        q.M = NF * g[l + 1].OH * g[l + 1].OW; q.N = cl[l]->N; q.K = q.ldw = cl[l]->K; q.ldc = cl[l]->N;
+        q.w2 = cl[l]->wl != nullptr; q.bias = q.out16 = true; q.relu = 1;
+        rowskip = plan_gemm(q, h->opts).glds();
+    }
     unsigned* zscr;
     RET(gs_conv1_stage(h, src, src_u8, sb, st, sh, sw, sc, nclip, T, pad, p1, !rowskip, &zscr));
     if (zscr && rowskip) {
@@ -202,14 +212,25 @@ static int gs_conv_stack(jg_handle* h, const void* src, int src_u8, long sb, lon
 // fp32 residual stream in its own tiled order (gemm.hip), so fused and unfused layers cannot be mixed.
 // rows_per_clip: rows of one clip in the launch (T * 21 on the clip path; 0: no clip structure, e.g. forward_vid windows).  In the
 // run-time corrected mode the LayerNorm-fused projections exist with the per-clip bias only (there is no hi+lo instance of that
-// kernel), and the per-clip bias needs rows_per_clip >= 256 (gemm(): `can`): shorter clips (T <= 12) and launches without clip structure
-// take the unfused plan, whose GEMMs run hi+lo (such batches used to fail with hipErrorInvalidValue).
+// kernel), so there the questions are asked in the per-clip-bias form: clips too short for it (T <= 12) and launches without clip
+// structure take the unfused plan, whose GEMMs run hi+lo (such batches used to fail with hipErrorInvalidValue).
+// Policy here: the option, not calibrating, the fp16 build (the token stream is fp16), no lo weights behind a fused LayerNorm.
+// Shape: the planner accepts all four GEMM kinds of a layer at this M -- qkv and linear1 on the tiled token plane, out_proj and
+// linear2 with the LayerNorm fused.
 static bool gs_fused_plan(const jg_handle* h, int M, int rows_per_clip) {
-    if (!h->fuse_ln || !h->opts.gemm_glds || h->calib || M < 1024 || h->bf16) return false;     // (the token stream is fp16)      // the tiled token stream is read by LDS-DMA only
-    if (h->precision == JG_PREC_FP16_RC && rows_per_clip < 256) return false;
+    if (!h->fuse_ln || h->calib || h->bf16) return false;
     for (int l = 0; l < 6; ++l)
         if (h->gs.layers[l].out.wl || h->gs.layers[l].ff2.wl) return false;
-    return true;
+    const bool clip_bias = h->precision == JG_PREC_FP16_RC;
+    auto plans = [&](int N, int K, bool ln, int relu) {
+        GemmShape q = {};
+        q.M = M; q.N = q.ldc = N; q.K = q.lda = q.ldw = K;
+        q.bias = q.out16 = true; q.relu = relu;
+        q.a_tiled = !ln; q.ln_w = q.res16 = ln;
+        if (clip_bias) { q.bias_clip = true; q.rpc = rows_per_clip; q.nclips = rows_per_clip > 0 ? M / rows_per_clip : 0; }
+        return plan_gemm(q, h->opts).ok();
+    };
+    return plans(1536, 512, false, 0) && plans(512, 512, true, 0) && plans(2048, 512, false, 1) && plans(512, 2048, true, 0);
 }
 
 // x32/x16 hold pad128(M) rows.  With `tiled` (gs_fused_plan) the token stream is the tiled fp16 plane x16 alone (x32 is not

@@ -219,13 +219,29 @@ int gemm(jg_handle* h, int stage, const f16* A, long lda, int M, const Lin& L, c
     if (g) a.g = *g;
     a.Wh = L.wh; a.Wl = (h->calib && L.bc) ? L.wl_calib : L.wl; a.ldw = L.K;
     const bool conv = g != nullptr;
+    a.M = M; a.N = L.N; a.K = L.K;
+    a.scale = e.scale; a.bias = e.no_bias ? nullptr : L.bias;
+    a.res = e.res; a.ldr = e.ldr; a.res_mod = e.res_mod;
+    a.out32 = e.out32; a.out16 = e.out16; a.ldc = e.ldc ? e.ldc : L.N;
+    a.relu = e.relu;
+    if (e.ln) { a.ln_w = e.ln->w; a.ln_b = e.ln->b; a.ln_flavour = e.ln_flavour; }
+    a.res16 = e.res16; a.a_tiled = e.a_tiled;
+    if (e.ln_mode == 1) {
+        if (!L.c1h || !L.c1f) JG_FAIL(h, JG_ERR_STATE, "implicit LayerNorm on a layer that was not packed for it");
+        a.ln_mode = 1; a.ln_stats = e.ln_stats; a.scale = L.c1h;
+    } else if (e.ln_mode == 2) {
+        a.ln_mode = 2; a.ln_stats = e.ln_stats; a.scale = e.ln_gamma;
+        a.xres_hi = e.x_hi; a.xres_lo = e.x_lo; a.out16 = e.x_hi; a.out_lo = e.x_lo; a.stat_out = e.stat_out;
+    }
     if (L.rc) {
-        // run-time correction: bias_clip = bias + lo . (mean of a sample of the clip's own rows), two small launches in front of the GEMM;
-        // only the LDS-DMA kernel's fp16-row and LayerNorm-fused epilogues take it (launch_gemm), everything else runs hi+lo
-        const bool ln_fused = e.ln && e.res16;
-        const bool rows16 = e.out16 && !e.out32 && !e.res && !e.ln;
-        const bool can = !conv && !e.ln_mode && !e.no_bias && h->opts.gemm_glds && e.rc_rpc >= 256 && e.rc_clips > 0 && (long)e.rc_rpc * e.rc_clips == M &&
-                         M >= 1024 && (L.K == 512 || L.K == 2048) && L.N % 128 == 0 && (ln_fused || rows16) && (!e.a_tiled || L.K == 512);
+        // run-time correction: bias_clip = bias + lo . (mean of a sample of the clip's own rows), two small launches in front of the GEMM.
+        // Whether the GEMM takes the corrected form of this call (per-clip bias, single fp16 weights) is the planner's answer for that
+        // form; everything else runs hi+lo.  Particular to this call site: the clips must tile the rows, the layer's bias rides in the
+        // per-clip vector, and launches of fewer than 1024 rows stay hi+lo (stricter than the planner's own minimum for the two
+        // non-fused GEMMs).  Decided before the scratch buffers are allocated: a refused call leaves the workspace layout alone.
+        GemmShape q = gemm_shape(a, conv);
+        q.bias_clip = true; q.rpc = e.rc_rpc; q.nclips = e.rc_clips;
+        const bool can = !e.no_bias && (long)e.rc_rpc * e.rc_clips == M && M >= 1024 && rc_bias_ok(L.N, L.K, e.a_tiled) && plan_gemm(q, h->opts).ok();
         if (can) {
             float *scr, *bc;
             RET(wsalloc(h, rc_scratch_elems(e.rc_clips, L.K), &scr));
@@ -236,20 +252,7 @@ int gemm(jg_handle* h, int stage, const f16* A, long lda, int M, const Lin& L, c
             a.Wl = L.wl_calib;
         }
     }
-    a.M = M; a.N = L.N; a.K = L.K;
-    a.scale = e.scale; a.bias = e.no_bias ? nullptr : L.bias;
-    a.res = e.res; a.ldr = e.ldr; a.res_mod = e.res_mod;
-    a.out32 = e.out32; a.out16 = e.out16; a.ldc = e.ldc ? e.ldc : L.N;
-    a.relu = e.relu;
-    if (e.ln) { a.ln_w = e.ln->w; a.ln_b = e.ln->b; a.ln_flavour = e.ln_flavour; }
-    a.res16 = e.res16; a.a_tiled = e.a_tiled;
-    if (e.ln_mode == 1) {
-        if (!L.c1h || !L.c1f) JG_FAIL(h, JG_ERR_STATE, "implicit LayerNorm on a layer that was not packed for it");
-        a.ln_mode = 1; a.ln_stats = e.ln_stats; a.scale = a.Wl ? L.c1f : L.c1h;
-    } else if (e.ln_mode == 2) {
-        a.ln_mode = 2; a.ln_stats = e.ln_stats; a.scale = e.ln_gamma;
-        a.xres_hi = e.x_hi; a.xres_lo = e.x_lo; a.out16 = e.x_hi; a.out_lo = e.x_lo; a.stat_out = e.stat_out;
-    }
+    if (a.ln_mode == 1 && a.Wl) a.scale = L.c1f;      // column sums of the weights the GEMM runs with (Lin::c1h / c1f)
     if (h->calib && L.bc && !conv) {
         // column sums ACCUMULATE over every call of a calibration pass (chunks of a large calibration batch, the six
         // layers' shared shapes are separate Lin objects): calibration_pass zeroes mu / mu_rows once at its start

@@ -30,8 +30,9 @@ int finalize_xlmr(jg_handle* h) {
     // Implicit LayerNorm (xlmr_encode_folded): the Linear BEHIND a LayerNorm(gamma, beta) is packed as W diag(gamma) with bias
     // b + W beta (fold_consumer), the Linear whose output is ADDED to that LayerNorm's output takes beta into its bias (the
     // gamma (x - mean) rstd part is recomputed from the un-normalised stream in its epilogue).
-    // (the implicit-LayerNorm epilogues exist in the LDS-DMA kernel only; the fp32 audit path runs the explicit LayerNorms on the
-    // un-folded matrices, so audit weights switch the folding off)
+    // (the implicit-LayerNorm epilogues exist in the LDS-DMA kernel only -- plan_gemm, gemm_plan.hip; the option is the policy here, the
+    // packing happens before any shape is known.  The fp32 audit path runs the explicit LayerNorms on the un-folded matrices, so audit
+    // weights switch the folding off)
     const bool fold = h->xl_fold_opt && h->opts.gemm_glds && !h->audit_weights && h->precision != JG_PREC_FP32;
     const HostTensor *pg, *pb;          // the LayerNorm in front of the current sub-layer
     RET(need(h, "xlmr.embeddings.LayerNorm.weight", D, &pg));
@@ -138,7 +139,7 @@ static int xlmr_encode_folded(jg_handle* h, const int32_t* ids, const int32_t* a
     const XlmrModel& xl = h->xl;
     constexpr int P = D / 64;
     const int M = B * L;
-    const int Mp = M < 128 ? 128 : M;             // the LDS-DMA GEMMs want >= 128 rows: short batches carry zero rows behind the tokens
+    const int Mp = M < GEMM_GLDS_MIN_ROWS ? GEMM_GLDS_MIN_ROWS : M;      // the LDS-DMA GEMMs' minimum (gemm_plan.h): short batches carry zero rows behind the tokens
     float *part, *stats, *mk = nullptr;
     f16 *xh, *xlo, *qkv, *att, *hid;
     RET(wsalloc(h, (size_t)Mp * D, &xh));
@@ -185,7 +186,7 @@ int xlmr_encode_impl(jg_handle* h, const int32_t* ids, const int32_t* amask, int
     if (!xl.m.ready) JG_FAIL(h, JG_ERR_STATE, "XLM-RoBERTa weights not finalized (jg_finalize_weights(h, 4))");
     if (B <= 0 || L <= 0 || L > xl.maxpos - 2) JG_FAIL(h, JG_ERR_ARG, "need B > 0 and 0 < L <= %d", xl.maxpos - 2);
     if (audit_mask(h) & AUD_XLMR) return xlmr_encode_impl32(h, ids, amask, B, L, out);
-    if (xl.folded && !h->opts.gemm_glds)
+    if (xl.folded && !h->opts.gemm_glds)      // (plan_gemm would reject every implicit-LayerNorm launch: say why up front)
         JG_FAIL(h, JG_ERR_STATE, "the XLM-RoBERTa weights were packed for the implicit-LayerNorm pass, which needs the LDS-DMA GEMM: set option "
                                  "gemm_glds=0 (or xlmr_fold=0) BEFORE jg_finalize_weights(h, 4)");
     if (xl.folded) return xlmr_encode_folded(h, ids, amask, B, L, out);

@@ -114,7 +114,7 @@ def nrm_ratio(got, ref):
 
 
 # ---- Linear GEMM (launch_gemm) ---------------------------------------------------------------------------------------------------
-# every non-conv Linear instance launch_gemm can reach (gemm.hip): gemm_glds_kernel<W2,CONV,MI,WM,WN,LNF,SPR,XE,C32>, gemm_kernel<WM,WN,CONV,W2>
+# every non-conv Linear instance launch_gemm can reach (the instance table of jegal_amd/csrc/gemm_plan.h): gemm_glds_kernel<W2,CONV,MI,WM,WN,LNF,SPR,XE,C32>, gemm_kernel<WM,WN,CONV,W2>
 LINEAR_INSTANCES = {
     "gemm_glds_kernel<0,0,2,4,2,0,0,0,0>", "gemm_glds_kernel<1,0,2,4,2,0,0,0,0>",          # 128x128
     "gemm_glds_kernel<0,0,4,4,2,0,0,0,0>", "gemm_glds_kernel<1,0,4,4,2,0,0,0,0>",          # 256x128
@@ -129,6 +129,12 @@ LINEAR_INSTANCES = {
     "gemm_kernel<4,1,0,0>", "gemm_kernel<4,1,0,1>", "gemm_kernel<2,2,0,0>", "gemm_kernel<2,2,0,1>",
 }
 SEEN = set()
+
+
+def planned(kw, opts=None):
+    """The GEMM planner's answer for one debug_gemm_check argument set under these engine options: asked without a launch."""
+    from jegal_amd._lib import gemm_plan
+    return gemm_plan(num_cu=torch.cuda.get_device_properties(0).multi_processor_count, opts=opts, **kw)[0]
 
 
 def gemm_case(name, M, N, K, *, w2=False, out="f32", lda=None, ldw=None, ldc=None, scale=False, bias=True, res=False, res_mod=0,
@@ -175,6 +181,7 @@ def gemm_case(name, M, N, K, *, w2=False, out="f32", lda=None, ldw=None, ldc=Non
     e.debug_gemm_check(**kw)
     torch.cuda.synchronize()
     kname = e.debug_last_kernel()
+    assert kname == planned(kw, opts), f"{name}: launched {kname}, the planner says {planned(kw, opts)}"
     SEEN.add(kname)
 
     acc = a @ weff.T
@@ -289,6 +296,7 @@ def ln_fused_case(M, clip=None, seed=1):
     e.debug_gemm_check(**kw)
     torch.cuda.synchronize()
     kname = e.debug_last_kernel()
+    assert kname == planned(kw), f"ln_fused M={M}: launched {kname}, the planner says {planned(kw)}"
     SEEN.add(kname)
     x = a @ wh.T + badd + res[:M]
     mu = x.mean(1, keepdim=True)
@@ -357,6 +365,7 @@ def implicit_ln_case(mode, M, N, K, w2, tile, seed=2):
     e.debug_gemm_check(**kw)
     torch.cuda.synchronize()
     kname = e.debug_last_kernel()
+    assert kname == planned(kw, dict(gemm_tile=tile)), f"ln_mode {mode}: launched {kname}, the planner says {planned(kw, dict(gemm_tile=tile))}"
     SEEN.add(kname)
     hi = out16[:M, :N].double().cpu()
     ratio = float(((hi - v).abs() / (eb + ulp16(v))).max()) if hi.isfinite().all() else float("inf")
@@ -431,6 +440,7 @@ def test_gemm_launcher_rejections():
     for kw in bad:
         assert rejects(e.debug_gemm_check, **kw), kw
         assert e.debug_last_kernel() == ""
+        assert planned(kw) == "rejected", kw
     assert rejects(e.debug_gemm_x3, z32, 200, z16, z16, 200, 64, 128, 200, z32, 128)          # x3: K % 256 != 0
     assert rejects(e.debug_gemm_x3, z32, 256, z16, z16, 256, 64, 64, 256, z32, 64)            # x3: N % 128 != 0
     assert rejects(e.debug_attention_gather, z16, z16, 4, 8, 2, 8, 33, 8, z16)               # gather: S > 32

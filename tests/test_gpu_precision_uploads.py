@@ -210,7 +210,7 @@ def test_conv1_launches_with_fewer_strips_than_cus(nclip, T):
 
 
 def test_gemm_tile_choice_never_changes_a_bit():
-    """launch_glds picks the plain GEMMs' tile (128x128 / 256x128 / 256x256) by a cost estimate; every instance accumulates k in
+    """plan_gemm (gemm_plan.hip) picks the plain GEMMs' tile (128x128 / 256x128 / 256x256) by a cost estimate; every instance accumulates k in
     the same order, so forcing any of them (option gemm_tile) must reproduce the default bit for bit - on the gesture path (M-partial
     last tiles: 3 x 60 x 21 tokens, 180 JEGAL tokens) and on the XLM-R front end."""
     from jegal_amd._lib import Engine

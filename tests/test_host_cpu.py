@@ -31,6 +31,43 @@ def test_library_exports_every_declared_symbol():
     assert set(_lib.EXPORTS) == set(declared)
 
 
+def test_gemm_planner_matches_the_recorded_choices(golden_dir):
+    """The GEMM planner (jegal_amd/csrc/gemm_plan.hip, asked through jg_debug_gemm_plan: no handle, no device) against a table of
+    argument sets with the instance, grid, LDS bytes and stagger that launch_gemm chose for them BEFORE the choice moved into the
+    planner -- recorded from that commit's launcher with the launch itself stubbed out, never from the planner.  The table holds every
+    launch of tests/test_gpu_kernels_fp64.py's Linear cases with their options, the GEMM and conv shapes of a BASELINE config-2 step
+    (32 clips x 150 frames, one stream and two lanes), of the config-3 content path and of an XLM-RoBERTa pass (B = 256, L = 64) in
+    the default precision mode and in modes 1, 3 and 4, and argument sets that must stay rejected; it reaches every kernel instance
+    of the library."""
+    import json
+
+    import __graft_entry__ as G
+    G.build()
+    from jegal_amd._lib import gemm_plan
+    from test_gpu_kernels_fp64 import LINEAR_INSTANCES
+    conv = {f"gemm_glds_kernel<{w2},1,{t},0,{spr},0,0>" for w2 in (0, 1) for t in ("2,4,2", "4,4,2") for spr in (0, 1)}
+    conv |= {"gemm_glds_kernel<0,1,8,2,4,0,0,0,0>", "gemm_glds_kernel<0,1,8,2,4,0,1,0,0>", "gemm_glds_kernel<0,1,8,4,2,0,0,0,0>",
+             "gemm_glds_kernel<0,1,2,8,1,0,0,0,1>"}
+    conv |= {f"gemm_kernel<{t},1,{w2}>" for t in ("4,1", "2,2") for w2 in (0, 1)}
+    instances = LINEAR_INSTANCES | conv
+    assert len(instances) == 37                  # 29 gemm_glds_kernel + 8 gemm_kernel instances per build
+    cases = json.load(open(os.path.join(golden_dir, "gemm_plan_cases.json")))
+    assert len(cases) >= 300
+    wrong, seen = [], set()
+    for c in cases:
+        got = gemm_plan(num_cu=c["num_cu"], lanes_active=c["lanes"], opts=c.get("opts"), conv=c.get("conv"), a_tiled=c.get("a_tiled", 0),
+                        **c["fields"])
+        seen.add(got[0])
+        if list(got) != c["want"]:
+            wrong.append((c["tag"], c["fields"], c.get("opts"), c["want"], got))
+    assert not wrong, wrong[:5]
+    rejected = [c for c in cases if c["tag"] == "rejected"]
+    assert len(rejected) >= 12 and all(c["want"][0] == "rejected" for c in rejected)
+    assert seen - {"rejected"} == instances, (sorted(instances - seen), sorted(seen - instances - {"rejected"}))
+    with pytest.raises(RuntimeError):            # an option the planner does not know is an error, not a default
+        gemm_plan(M=256, N=256, K=512, lda=512, ldw=512, ldc=256, out16=True, opts=dict(gemm_no_such_option=1))
+
+
 def test_hot_kernels_do_not_spill():
     """the LN-fused GEMM carried 6 VGPR spills (28 B scratch), the 512x128 conv instance 8.  Read
     .vgpr_spill_count of every kernel from the gfx950 code objects inside libjegal_hip.so so that cannot come back."""

@@ -1,5 +1,5 @@
 """Per-tile-shape timing of the plain LDS-DMA GEMM on the small-M shapes (JEGAL branch, XLM-R): calibrates the cost estimate of
-launch_glds (gemm.hip).  Usage: python tools/gemm_tiles.py"""
+plan_gemm (gemm_plan.hip).  Usage: python tools/gemm_tiles.py"""
 import os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
