@@ -204,6 +204,14 @@ int jg_debug_gemm_check(jg_handle* h, const jg_gemm_check* c);
 typedef struct jg_conv_shape { int H, W, C, KH, KW, PH, PW, tap_table, rowmap, const_in; } jg_conv_shape;
 int jg_debug_gemm_plan(const jg_gemm_check* c, const jg_conv_shape* conv, int a_tiled, int num_cu, int lanes_active, const char* const* opt_names,
                        const int* opt_values, int n_opts, char* name, int name_len, int* grid, int* lds, int* stagger);
+/* Which weights a packed layer's GEMM runs with (jegal_amd/csrc/weight_form.h), without a handle or a device.  precision: JG_PREC_*;
+ * kind: 0 conv, 1 gesture-path Linear, 2 content-path Linear, 3 XLM-RoBERTa Linear; model: 1 GestSync, 2 JEGAL, 3 XLM-RoBERTa; keep32: the
+ * layer also runs on the split-operand kernel.  form: 0 single, 1 hi+lo split, 2 single + calibrated bias, 3 single + per-clip run-time
+ * bias; lo_kept: the lo matrix stays on the device; uncalibrated: the layer runs hi+lo until a calibration has been applied. */
+int jg_debug_weight_form(int precision, int kind, int model, int keep32, int* form, int* lo_kept, int* uncalibrated);
+/* ... and whether a GEMM on a layer of that form takes the lo operand: uncalibrated as above, calibrating: a calibration pass is in
+ * progress, clip_bias: the call takes the per-clip bias (a run-time corrected layer runs hi+lo in every call that cannot). */
+int jg_debug_gemm_runs_lo(int form, int uncalibrated, int calibrating, int clip_bias, int* lo);
 /* fp32 GEMM of the audit mode (launch_gemm32): out = act(A W^T * scale + bias + res[m % res_mod]), act 0 / 1 ReLU / 2 exact GELU. */
 int jg_debug_gemm32(jg_handle* h, const float* A, int64_t lda, const float* W, int64_t ldw, int M, int N, int K, const float* scale,
                     const float* bias, const float* res, int64_t ldr, int res_mod, int act, float* out, int64_t ldc);

@@ -58,6 +58,8 @@ _SIGS = {
     "jg_debug_gemm_check": [_P, _P],
     "jg_debug_gemm_plan": [_P, _P, _I, _I, _I, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(_I), _I, ctypes.c_char_p, _I,
                            ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I)],
+    "jg_debug_weight_form": [_I, _I, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I)],
+    "jg_debug_gemm_runs_lo": [_I, _I, _I, _I, ctypes.POINTER(_I)],
     "jg_debug_gemm32": [_P, _P, _L, _P, _L, _I, _I, _I, _P, _P, _P, _L, _I, _I, _P, _L],
     "jg_debug_gemm_x3": [_P, _P, _L, _P, _P, _L, _I, _I, _I, _P, _P, _L, _I, _I, _P, _L],
     "jg_debug_attention": [_P, _P, _P, _I, _I, _I, _I, _P],
@@ -145,6 +147,28 @@ def gemm_plan(num_cu=256, lanes_active=False, opts=None, conv=None, a_tiled=Fals
     if rc != 0:
         raise JegalError(f"jg_debug_gemm_plan: bad arguments or unknown option ({rc})", rc)
     return name.value.decode(), grid.value, lds.value, stagger.value
+
+
+WEIGHT_FORMS = ["single", "split", "bias_corrected", "runtime_corrected"]       # enum WeightForm (jegal_amd/csrc/weight_form.h)
+
+
+def weight_form(precision, kind, model, keep32=False):
+    """Which weights a packed layer's GEMM runs with (jg_debug_weight_form) -> (form name, lo kept on the device, starts uncalibrated).
+    kind: 0 conv, 1 gesture, 2 content, 3 XLM-R; model: 1 GestSync, 2 JEGAL, 3 XLM-R.  Needs no Engine and no GPU."""
+    form, lo, unc = _I(), _I(), _I()
+    rc = load_library().jg_debug_weight_form(int(precision), int(kind), int(model), int(bool(keep32)), ctypes.byref(form), ctypes.byref(lo), ctypes.byref(unc))
+    if rc != 0:
+        raise JegalError(f"jg_debug_weight_form: bad arguments ({rc})", rc)
+    return WEIGHT_FORMS[form.value], bool(lo.value), bool(unc.value)
+
+
+def gemm_runs_lo(form, uncalibrated=False, calibrating=False, clip_bias=False):
+    """Whether a GEMM on a layer of this form (a name of WEIGHT_FORMS) takes the lo operand (jg_debug_gemm_runs_lo)."""
+    lo = _I()
+    rc = load_library().jg_debug_gemm_runs_lo(WEIGHT_FORMS.index(form), int(bool(uncalibrated)), int(bool(calibrating)), int(bool(clip_bias)), ctypes.byref(lo))
+    if rc != 0:
+        raise JegalError(f"jg_debug_gemm_runs_lo: bad arguments ({rc})", rc)
+    return bool(lo.value)
 
 
 class JegalError(RuntimeError):

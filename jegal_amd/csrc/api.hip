@@ -325,8 +325,8 @@ int jg_finalize_weights(jg_handle* h, int which) {
     if (which & 1) RET(finalize_gestsync(h));
     if (which & 2) RET(finalize_jegal(h));
     if (which & 4) RET(finalize_xlmr(h));
-    // The fp32 host copies this finalize consumed are no longer needed (packed device weights + the w32/b32 of the
-    // bias-corrected layers carry everything).  Tensors staged for a model that is finalized LATER stay staged; what no
+    // The fp32 host copies this finalize consumed are no longer needed (packed device weights + the w32 / b32 of the
+    // bias-corrected layers' calibration records carry everything).  Tensors staged for a model that is finalized LATER stay staged; what no
     // finalize consumes (the unused audio/LSTM tensors of gestsync.py:23-32) stays until jg_clear_staged_tensors / jg_destroy.
     for (auto it = h->host.begin(); it != h->host.end();) it = it->second.used ? h->host.erase(it) : std::next(it);
     // Built-in calibration only for the gesture models finalized by THIS call (XLM-R has no bias-corrected layers): the bias

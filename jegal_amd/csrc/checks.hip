@@ -6,7 +6,8 @@ using namespace engine;
 // ---- kernel check points: one launch of a production launcher on the caller's operands, with the handle's options (which pick
 // the instance exactly as in production) and the handle's build (fp16 or bf16).  The launcher's own shape rules decide what is
 // valid: its hipErrorInvalidValue comes back as JG_ERR_ARG, and nothing was launched then.  (Handle internals and LAUNCH: engine.h.)
-// jg_debug_gemm_plan asks the GEMM planner (gemm_plan.h) the same question without a handle, a device or a launch.
+// jg_debug_gemm_plan asks the GEMM planner (gemm_plan.h) the same question without a handle, a device or a launch, and
+// jg_debug_weight_form / jg_debug_gemm_runs_lo show which weights a layer's GEMM runs with (weight_form.h) in the same way.
 namespace {
 int check_result(jg_handle* h, hipError_t e, const char* what) {
     if (e == hipErrorInvalidValue) JG_FAIL(h, JG_ERR_ARG, "%s: the launcher rejects this shape / argument set", what);
@@ -168,6 +169,21 @@ int jg_debug_gemm_plan(const jg_gemm_check* c, const jg_conv_shape* conv, int a_
     const GemmPlan p = plan_gemm(s, o);
     snprintf(name, (size_t)name_len, "%s", p.name);
     *grid = (int)p.grid; *lds = (int)p.lds; *stagger = p.stagger;
+    return JG_OK;
+}
+
+int jg_debug_weight_form(int precision, int kind, int model, int keep32, int* form, int* lo_kept_out, int* uncalibrated) {
+    if (precision < JG_PREC_FP16 || precision > JG_PREC_FP32 || kind < LK_CONV || kind > LK_XLMR || model < 1 || model > 3 || !form || !lo_kept_out ||
+        !uncalibrated)
+        return JG_ERR_ARG;
+    const WeightForm f = weight_form(precision, kind, model);
+    *form = f; *lo_kept_out = lo_kept(f, keep32 != 0); *uncalibrated = starts_uncalibrated(f, kind);
+    return JG_OK;
+}
+
+int jg_debug_gemm_runs_lo(int form, int uncalibrated, int calibrating, int clip_bias, int* lo) {
+    if (form < WF_SINGLE || form > WF_RUNTIME_CORRECTED || !lo) return JG_ERR_ARG;
+    *lo = runs_with_lo((WeightForm)form, uncalibrated != 0, calibrating != 0, clip_bias != 0);
     return JG_OK;
 }
 

@@ -6,6 +6,7 @@
 #include "common.h"
 #undef JG_BF16
 #include "gemm_plan.h"
+#include "weight_form.h"
 #include "../../include/jegal_hip.h"
 #include "audit32.h"
 
@@ -13,6 +14,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <deque>
 #include <map>
 #include <string>
 #include <vector>
@@ -39,24 +41,16 @@ struct HostTensor {
     int64_t numel() const { int64_t n = 1; for (auto s : shape) n *= s; return n; }
 };
 
-struct Lin {            // packed Linear / folded conv:  [N][K] fp16 hi (+lo), fp32 bias
+struct BiasCalib;
+struct Lin {            // packed Linear / folded conv:  [N][K] fp16 hi (+lo), fp32 bias.  Read-only once packed, but for `uncalibrated`
     f16* wh = nullptr;
-    f16* wl = nullptr;          // lo part used at run time (W2 modes) or nullptr
+    f16* lo = nullptr;          // the lo half, or nullptr when it is not kept (lo_kept).  Whether a GEMM runs with it: run_lo() below
     float* bias = nullptr;
     int N = 0, K = 0;
-    // bias-corrected mode (JG_PREC_FP16_BC): run-time weights are the single fp16 `wh`; the systematic part of
-    // the weight-rounding error, (w - fp16(w)) . E[x], is folded into `bias` after a calibration pass that runs
-    // with hi+lo weights (wl_calib) and records the per-channel mean of this layer's input (mu).
-    bool bc = false;
-    // run-time corrected mode (JG_PREC_FP16_RC; GestSync transformer Linears): single fp16 `wh` + a per-clip bias built from the clip's own
-    // rows and the lo part (`wl_calib`), see gemm(); wherever that epilogue is not available the GEMM runs hi+lo instead
-    bool rc = false;
-    bool bc_pending = false;    // LK_XLMR: no calibration yet -- the run-time GEMM keeps using hi+lo (wl == wl_calib); jg_calibrate_xlmr clears it
-    f16* wl_calib = nullptr;
-    float* mu = nullptr;        // device [K]: column sums of the A operand seen during calibration
-    long mu_rows = 0;
-    std::vector<float> w32, b32;
-    // Linear behind an IMPLICIT LayerNorm (GemmArgs::ln_mode 1): w32 / wh / wl hold W . diag(gamma), b32 / bias hold b + W beta, and
+    WeightForm form = WF_SINGLE;        // which weights the layer's GEMM runs with (weight_form.h)
+    bool uncalibrated = false;          // starts_uncalibrated: hi+lo until apply_bias_corrections (jg_calibrate_xlmr) clears it
+    BiasCalib* cal = nullptr;           // WF_BIAS_CORRECTED: the layer's calibration record (owned by Model::bc)
+    // Linear behind an IMPLICIT LayerNorm (GemmArgs::ln_mode 1): wh / lo / BiasCalib::w32 hold W . diag(gamma), bias / BiasCalib::b32 hold b + W beta, and
     // c1h / c1f [N] the column sums of the packed weights -- of `wh` alone (single-fp16 runs: the GEMM then is exactly
     // sum_k wh[n][k] (x[k] - mean) rstd, and the bias correction covers the lo part) and of wh + lo (hi+lo runs)
     float* c1h = nullptr;
@@ -65,6 +59,13 @@ struct Lin {            // packed Linear / folded conv:  [N][K] fp16 hi (+lo), f
     // wh) and the layer's own fp32 bias (`bias` above may carry a calibration's correction)
     float* w32d = nullptr;
     float* b32d = nullptr;
+};
+// What a calibration pass records for one bias-corrected layer and what apply_bias_corrections needs to fold it into the layer's bias
+struct BiasCalib {
+    Lin* layer = nullptr;
+    float* mu = nullptr;        // device [K]: column sums of the A operand seen during calibration
+    long mu_rows = 0;
+    std::vector<float> w32, b32;        // the matrix and the bias as packed, fp32
 };
 struct LNp { float* w = nullptr; float* b = nullptr; };
 
@@ -101,7 +102,7 @@ struct Model {
     int id = 0;                    // 1 GestSync, 2 JEGAL, 3 XLM-RoBERTa: bit id - 1 of a `which` / `models` mask
     bool ready = false;
     std::vector<void*> allocs;     // device weights and the buffers derived from them (walloc)
-    std::vector<Lin*> bc;          // bias-corrected layers (calibration passes)
+    std::deque<BiasCalib> bc;      // calibration records of the bias-corrected layers (a deque: Lin::cal points into it)
 };
 
 struct GestSyncModel {
@@ -146,7 +147,7 @@ struct jg_handle {
     std::string err;
     int precision = JG_PREC_FP16_RC;      // the calibration-free mode (round 5; rounds 1-4: JG_PREC_FP16_BC)
     bool bf16 = false;             // precision == JG_PREC_BF16: every launcher comes from the bf16 build (namespace bf)
-    bool calib = false;            // calibration pass in progress (bc layers use hi+lo and record input means)
+    bool calib = false;            // calibration pass in progress (bias-corrected layers run hi+lo and record input means: runs_with_lo, gemm())
     int chunk = 32;                // clips per GestSync pass: ~14 GB of workspace per lane at 150 frames; 288 GB of HBM make the whole BASELINE batch one pass
     bool fuse_ln = true;           // residual + LayerNorm in the GEMM epilogue (GestSync post-norm layers)
     bool edge_dedup = true;        // skip the 16 duplicated edge positions of a padded clip
@@ -314,6 +315,12 @@ inline size_t pad128(size_t rows) { return (rows + 127) / 128 * 128; }
 enum { AUD_CONV = 1, AUD_GS = 2, AUD_JG = 4, AUD_CONTENT = 8, AUD_XLMR = 16, AUD_ALL = 31 };
 inline int audit_mask(const jg_handle* h) { return h->precision == JG_PREC_FP32 ? AUD_ALL : h->audit_stages; }
 
+// The lo operand a GEMM on layer L runs with on this handle, or nullptr (weight_form.h, runs_with_lo).  clip_bias: the call takes the
+// per-clip bias of a run-time corrected layer
+inline const f16* run_lo(const jg_handle* h, const Lin& L, bool clip_bias) {
+    return runs_with_lo(L.form, L.uncalibrated, h->calib, clip_bias) ? L.lo : nullptr;
+}
+
 // ------------------------------------------------------------------------------------ GEMM calls (linear.hip)
 struct Epi {
     const float* scale = nullptr;
@@ -360,8 +367,7 @@ int post_norm_layer32(jg_handle* h, const EncLayer& L, float* x32, float* t32, f
                       int H, int D, int Dff, int act, float* out);
 
 // ------------------------------------------------------------------------------------ weight packing (linear.hip)
-// layer kinds: which precision treatment a matrix gets under the handle's mode
-enum { LK_CONV = 0, LK_GESTURE = 1, LK_CONTENT = 2, LK_XLMR = 3 };      // LK_XLMR: bias-corrected like the gesture path (calibrated on token ids)
+// (layer kinds LK_* and the form each gets under the handle's mode: weight_form.h)
 const HostTensor* find(jg_handle* h, const std::string& name);
 int need(jg_handle* h, const std::string& name, int64_t numel, const HostTensor** out);
 int pack_matrix(jg_handle* h, Model& m, const std::vector<float>& w, const std::vector<float>& bias, int N, int K, int kind, Lin* L,

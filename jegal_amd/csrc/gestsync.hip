@@ -170,7 +170,7 @@ static int gs_conv_stack(jg_handle* h, const void* src, int src_u8, long sb, lon
         q.set_geom(g[l + 1]);
         q.rowmap = true; q.const_in = l > 0;
         q.M = NF * g[l + 1].OH * g[l + 1].OW; q.N = cl[l]->N; q.K = q.ldw = cl[l]->K; q.ldc = cl[l]->N;
-        q.w2 = cl[l]->wl != nullptr; q.bias = q.out16 = true; q.relu = 1;
+        q.w2 = run_lo(h, *cl[l], false) != nullptr; q.bias = q.out16 = true; q.relu = 1;
         rowskip = plan_gemm(q, h->opts).glds();
     }
     unsigned* zscr;
@@ -214,13 +214,14 @@ static int gs_conv_stack(jg_handle* h, const void* src, int src_u8, long sb, lon
 // run-time corrected mode the LayerNorm-fused projections exist with the per-clip bias only (there is no hi+lo instance of that
 // kernel), so there the questions are asked in the per-clip-bias form: clips too short for it (T <= 12) and launches without clip
 // structure take the unfused plan, whose GEMMs run hi+lo (such batches used to fail with hipErrorInvalidValue).
-// Policy here: the option, not calibrating, the fp16 build (the token stream is fp16), no lo weights behind a fused LayerNorm.
+// Policy here: the option, not calibrating, the fp16 build (the token stream is fp16), no lo operand behind a fused LayerNorm (asked
+// in the per-clip-bias form, the one these launches take: a run-time corrected layer answers "none").
 // Shape: the planner accepts all four GEMM kinds of a layer at this M -- qkv and linear1 on the tiled token plane, out_proj and
 // linear2 with the LayerNorm fused.
 static bool gs_fused_plan(const jg_handle* h, int M, int rows_per_clip) {
     if (!h->fuse_ln || h->calib || h->bf16) return false;
     for (int l = 0; l < 6; ++l)
-        if (h->gs.layers[l].out.wl || h->gs.layers[l].ff2.wl) return false;
+        if (run_lo(h, h->gs.layers[l].out, true) || run_lo(h, h->gs.layers[l].ff2, true)) return false;
     const bool clip_bias = h->precision == JG_PREC_FP16_RC;
     auto plans = [&](int N, int K, bool ln, int relu) {
         GemmShape q = {};
@@ -266,7 +267,7 @@ static int gs_transformer(jg_handle* h, float* x32, f16* x16, int nseq, int S, b
             e.out16 = qpos; e.no_bias = 1;
             RET(gemm(h, JG_ST_GEMM, q0->conv16, 512, q0->nclip * q0->P, L.qkv, e));
             if (!gs.qpe_valid) {
-                RET(timed(h, JG_ST_GEMM, [&] { return launch_pe_project(gs.pe, S, L.qkv.wh, L.qkv.rc ? L.qkv.wl_calib : L.qkv.wl, L.qkv.bias, 1536, 512, qpe, h->stream); }));
+                RET(timed(h, JG_ST_GEMM, [&] { return launch_pe_project(gs.pe, S, L.qkv.wh, run_lo(h, L.qkv, false), L.qkv.bias, 1536, 512, qpe, h->stream); }));
                 HIPCHK(h, hipStreamSynchronize(h->stream));      // once per weight load: later calls may come on another stream
                 gs.qpe_valid = true;
             }

@@ -40,10 +40,10 @@ int finalize_jegal(jg_handle* h) {
 }
 
 // Option jegal_fp32_ends: these ends of a JEGAL path keep fp32 activations and run on gemm_x3 -- not in the plain-fp16
-// / bf16 reported modes, not while calibrating, and only where every one of them was packed with its lo half
+// / bf16 reported modes, not while calibrating, and only where every one of them keeps its lo half on the device (lo_kept, weight_form.h)
 static bool split_ends(const jg_handle* h, std::initializer_list<const Lin*> ends) {
     if (!h->jegal_fp32_ends || h->calib || h->precision == JG_PREC_FP16 || h->precision == JG_PREC_BF16) return false;
-    for (const Lin* L : ends) if (!L->wl && !L->wl_calib) return false;
+    for (const Lin* L : ends) if (!L->lo) return false;
     return true;
 }
 
@@ -314,7 +314,7 @@ int jegal_audio_impl(jg_handle* h, const float* mel, int B, int Tm, const int32_
         return timed(h, JG_ST_MISC, [&] { return LAUNCH(h, launch_zero_tail, x, a.valid, halvings, B, g.OH, (long)g.OW * C, h->stream); });
     };
     // cnn.0 + BN + ReLU straight from the mel frames (round 2: im2col + a K = 32 GEMM on the register-staged kernel)
-    RET(timed(h, JG_ST_CONV, [&] { return LAUNCH(h, launch_audio_conv0, mel, B, Tm, F, jg.a0.wh, jg.a0.wl, jg.a0.bias, c0, a.valid, h->stream); }));
+    RET(timed(h, JG_ST_CONV, [&] { return LAUNCH(h, launch_audio_conv0, mel, B, Tm, F, jg.a0.wh, run_lo(h, jg.a0, false), jg.a0.bias, c0, a.valid, h->stream); }));
     Epi e; e.relu = 1;
     e.out16 = c3; RET(gemm(h, JG_ST_CONV, c0, 0, B * a.g3.OH * a.g3.OW, jg.a3, e, &a.g3));
     RET(tail(c3, 1, a.g3, 64));

@@ -36,24 +36,16 @@ int need(jg_handle* h, const std::string& name, int64_t numel, const HostTensor*
 // that averages out over pixels.  No calibration, no run-time cost (measured with tools/precision_floor.py).
 int pack_matrix(jg_handle* h, Model& m, const std::vector<float>& w, const std::vector<float>& bias, int N, int K, int kind, Lin* L, bool ln_consumer,
                 bool keep32, int diffuse_group) {
-    const int mode = h->precision;
-    // JG_PREC_FP16_RC: GestSync's Linears are run-time corrected; the JEGAL gesture branch (M = B*T rows: launch-bound, a
-    // 256-row tile meets several clips) and the content path keep hi+lo; XLM-RoBERTa as in JG_PREC_FP16_BC (hi+lo until calibrated)
-    const bool rcm = mode == JG_PREC_FP16_RC;
-    const bool rc = rcm && kind == LK_GESTURE && m.id == 1;
-    const bool bc = (mode == JG_PREC_FP16_BC && (kind == LK_GESTURE || kind == LK_XLMR)) || (rcm && kind == LK_XLMR);
-    const bool split = kind == LK_CONV ? mode == JG_PREC_FP16_W2_ALL
-                                       : (mode == JG_PREC_FP16_W2 || mode == JG_PREC_FP16_W2_ALL || (mode == JG_PREC_FP16_BC && kind == LK_CONTENT) ||
-                                          (rcm && !rc && kind != LK_XLMR));
+    const WeightForm form = weight_form(h->precision, kind, m.id);
+    const bool want_lo = lo_kept(form, keep32);
     std::vector<f16> hi((size_t)N * K), lo;
-    const bool want_lo = split || bc || rc || keep32;
     if (want_lo) lo.resize((size_t)N * K);
     if (h->bf16) {                       // JG_PREC_BF16: single bf16 weights (the 16-bit container is re-typed by the bf16 build)
         for (size_t i = 0; i < hi.size(); ++i) {
             const uint16_t b = bf16_bits(w[i]);
             std::memcpy(&hi[i], &b, 2);
         }
-    } else if (diffuse_group > 0 && K % diffuse_group == 0 && !(split || bc || rc)) {
+    } else if (diffuse_group > 0 && K % diffuse_group == 0 && form == WF_SINGLE) {
         const int taps = K / diffuse_group;
         for (int n = 0; n < N; ++n)
             for (int sl = 0; sl < diffuse_group; ++sl) {
@@ -101,28 +93,22 @@ int pack_matrix(jg_handle* h, Model& m, const std::vector<float>& w, const std::
         RET(upload(h, m, c1f, &L->c1f));
     }
     RET(upload(h, m, hi, &L->wh));
-    L->wl = nullptr;
-    if (split) RET(upload(h, m, lo, &L->wl));
     RET(upload(h, m, bias, &L->bias));
     L->w32d = L->b32d = nullptr;
     if (h->audit_weights || h->precision == JG_PREC_FP32 || keep32) {
         RET(upload(h, m, w, &L->w32d));
         RET(upload(h, m, bias, &L->b32d));
     }
-    L->bc = bc;
-    L->rc = rc;
-    L->bc_pending = false;
-    if (rc) RET(upload(h, m, lo, &L->wl_calib));
-    if (keep32 && !split && !bc && !rc) RET(upload(h, m, lo, &L->wl_calib));      // the lo half for the split-operand kernel (gemm_x3)
-    if (bc) {
-        RET(upload(h, m, lo, &L->wl_calib));
-        RET(walloc<float>(h, m, (size_t)K, &L->mu));
-        L->w32 = w;
-        L->b32 = bias;
-        m.bc.push_back(L);
-        // XLM-RoBERTa: calibration-free hi+lo until jg_calibrate_xlmr has seen the caller's token ids (the released checkpoint has
-        // strong outlier activation dimensions; bias corrections recorded on made-up ids were never validated for it)
-        if (kind == LK_XLMR) { L->wl = L->wl_calib; L->bc_pending = true; }
+    L->lo = nullptr;
+    if (want_lo) RET(upload(h, m, lo, &L->lo));       // for the form's own GEMMs and / or the split-operand kernel (gemm_x3, keep32)
+    L->form = form;
+    L->uncalibrated = starts_uncalibrated(form, kind);
+    L->cal = nullptr;
+    if (form == WF_BIAS_CORRECTED) {
+        float* mu;
+        RET(walloc<float>(h, m, (size_t)K, &mu));
+        m.bc.push_back({L, mu, 0, w, bias});
+        L->cal = &m.bc.back();
     }
     return JG_OK;
 }
@@ -217,7 +203,7 @@ int gemm(jg_handle* h, int stage, const f16* A, long lda, int M, const Lin& L, c
     std::memset(&a, 0, sizeof(a));
     a.A = A; a.lda = lda;
     if (g) a.g = *g;
-    a.Wh = L.wh; a.Wl = (h->calib && L.bc) ? L.wl_calib : L.wl; a.ldw = L.K;
+    a.Wh = L.wh; a.Wl = run_lo(h, L, true); a.ldw = L.K;      // (a run-time corrected layer: the per-clip-bias form, unless that is refused below)
     const bool conv = g != nullptr;
     a.M = M; a.N = L.N; a.K = L.K;
     a.scale = e.scale; a.bias = e.no_bias ? nullptr : L.bias;
@@ -233,7 +219,7 @@ int gemm(jg_handle* h, int stage, const f16* A, long lda, int M, const Lin& L, c
         a.ln_mode = 2; a.ln_stats = e.ln_stats; a.scale = e.ln_gamma;
         a.xres_hi = e.x_hi; a.xres_lo = e.x_lo; a.out16 = e.x_hi; a.out_lo = e.x_lo; a.stat_out = e.stat_out;
     }
-    if (L.rc) {
+    if (L.form == WF_RUNTIME_CORRECTED) {
         // run-time correction: bias_clip = bias + lo . (mean of a sample of the clip's own rows), two small launches in front of the GEMM.
         // Whether the GEMM takes the corrected form of this call (per-clip bias, single fp16 weights) is the planner's answer for that
         // form; everything else runs hi+lo.  Particular to this call site: the clips must tile the rows, the layer's bias rides in the
@@ -246,24 +232,23 @@ int gemm(jg_handle* h, int stage, const f16* A, long lda, int M, const Lin& L, c
             float *scr, *bc;
             RET(wsalloc(h, rc_scratch_elems(e.rc_clips, L.K), &scr));
             RET(wsalloc(h, (size_t)e.rc_clips * L.N, &bc));
-            RET(timed(h, JG_ST_GEMM, [&] { return launch_rc_bias(A, lda, e.a_tiled, e.rc_clips, e.rc_rpc, e.rc_valid, L.wl_calib, L.bias, L.N, L.K, scr, bc, h->stream); }));
+            RET(timed(h, JG_ST_GEMM, [&] { return launch_rc_bias(A, lda, e.a_tiled, e.rc_clips, e.rc_rpc, e.rc_valid, L.lo, L.bias, L.N, L.K, scr, bc, h->stream); }));
             a.bias_clip = bc; a.rpc = e.rc_rpc; a.nclips = e.rc_clips;
         } else {
-            a.Wl = L.wl_calib;
+            a.Wl = run_lo(h, L, false);
         }
     }
     if (a.ln_mode == 1 && a.Wl) a.scale = L.c1f;      // column sums of the weights the GEMM runs with (Lin::c1h / c1f)
-    if (h->calib && L.bc && !conv) {
-        // column sums ACCUMULATE over every call of a calibration pass (chunks of a large calibration batch, the six
-        // layers' shared shapes are separate Lin objects): calibration_pass zeroes mu / mu_rows once at its start
-        Lin& Lm = const_cast<Lin&>(L);
+    if (h->calib && L.cal && !conv) {
+        // column sums ACCUMULATE in the layer's record over every call of a calibration pass (chunks of a large calibration batch, the
+        // six layers' shared shapes are separate Lin objects): calibration_pass zeroes mu / mu_rows once at its start
         float* part;
         RET(wsalloc(h, col_sum_scratch_elems(L.K), &part));
         // (a folded consumer's effective input is the NORMALISED row: the correction term is (w' - fp16(w')) . E[(x - mean) rstd])
         // (padding rows behind the caller's tokens would be averaged into E[x]: ADVICE r4)
         const int rows = e.calib_rows > 0 && e.calib_rows < M ? e.calib_rows : M;
-        RET(timed(h, JG_ST_MISC, [&] { return launch_col_sum(A, lda, rows, L.K, part, Lm.mu, h->stream, e.ln_mode == 1 ? e.ln_stats : nullptr); }));
-        Lm.mu_rows += rows;
+        RET(timed(h, JG_ST_MISC, [&] { return launch_col_sum(A, lda, rows, L.K, part, L.cal->mu, h->stream, e.ln_mode == 1 ? e.ln_stats : nullptr); }));
+        L.cal->mu_rows += rows;
     }
     return timed(h, stage, [&] { return LAUNCH(h, launch_gemm, a, conv, h->opts, h->stream); });
 }
@@ -322,11 +307,10 @@ int post_norm_layer32(jg_handle* h, const EncLayer& L, float* x32, float* t32, f
 
 // The same product on the fp16 matrix cores with split operands (audit32.h, GemmX3Args): A fp32, W = hi + lo, three MFMAs per fragment pair
 int gemm_x3(jg_handle* h, int stage, const float* A, long lda, int M, const Lin& L, float* out, const Epi32& e) {
-    const f16* lo = L.wl ? L.wl : L.wl_calib;
-    if (!L.wh || !lo) JG_FAIL(h, JG_ERR_STATE, "split-operand GEMM on a layer that was packed without its lo half");
+    if (!L.wh || !L.lo) JG_FAIL(h, JG_ERR_STATE, "split-operand GEMM on a layer that was packed without its lo half");
     GemmX3Args a;
     std::memset(&a, 0, sizeof(a));
-    a.A = A; a.lda = lda; a.Wh = L.wh; a.Wl = lo; a.ldw = L.K;
+    a.A = A; a.lda = lda; a.Wh = L.wh; a.Wl = L.lo; a.ldw = L.K;
     a.M = M; a.N = L.N; a.K = L.K;
     a.bias = L.b32d ? L.b32d : L.bias;
     a.res = e.res; a.ldr = e.ldr; a.res_mod = e.res_mod;
@@ -346,22 +330,23 @@ static int apply_bias_corrections(jg_handle* h, int models) {
     HIPCHK(h, hipStreamSynchronize(h->stream));
     std::vector<float> mu;
     for (Model* m : {&h->gs.m, &h->jg.m, &h->xl.m})
-        for (Lin* L : m->bc) {
-            if (L->mu_rows <= 0) continue;
-            if (!((models >> (m->id - 1)) & 1)) { L->mu_rows = 0; continue; }
+        for (BiasCalib& c : m->bc) {
+            Lin* L = c.layer;
+            if (c.mu_rows <= 0) continue;
+            if (!((models >> (m->id - 1)) & 1)) { c.mu_rows = 0; continue; }
             mu.resize(L->K);
-            HIPCHK(h, hipMemcpy(mu.data(), L->mu, sizeof(float) * L->K, hipMemcpyDeviceToHost));
+            HIPCHK(h, hipMemcpy(mu.data(), c.mu, sizeof(float) * L->K, hipMemcpyDeviceToHost));
             std::vector<float> nb(L->N);
-            const double inv = 1.0 / (double)L->mu_rows;
+            const double inv = 1.0 / (double)c.mu_rows;
             for (int n = 0; n < L->N; ++n) {
-                double c = 0.0;
-                const float* wr = &L->w32[(size_t)n * L->K];
-                for (int k = 0; k < L->K; ++k) c += (double)(wr[k] - (float)(f16)wr[k]) * ((double)mu[k] * inv);
-                nb[n] = L->b32[n] + (float)c;
+                double acc = 0.0;
+                const float* wr = &c.w32[(size_t)n * L->K];
+                for (int k = 0; k < L->K; ++k) acc += (double)(wr[k] - (float)(f16)wr[k]) * ((double)mu[k] * inv);
+                nb[n] = c.b32[n] + (float)acc;
             }
             HIPCHK(h, hipMemcpy(L->bias, nb.data(), sizeof(float) * L->N, hipMemcpyHostToDevice));
-            L->mu_rows = 0;
-            if (L->bc_pending) { L->wl = nullptr; L->bc_pending = false; }      // calibrated: single fp16 + corrected bias from here on
+            c.mu_rows = 0;
+            L->uncalibrated = false;          // calibrated: single fp16 + corrected bias from here on
         }
     h->gs.qpe_valid = false;          // the projected positional rows carry layer 0's qkv bias
     return JG_OK;
@@ -375,9 +360,9 @@ static int calibration_pass(jg_handle* h, int record, int apply, F&& pass) {
     int rc = JG_OK;
     for (Model* m : {&h->gs.m, &h->jg.m, &h->xl.m}) {
         if (!((record >> (m->id - 1)) & 1)) continue;
-        for (Lin* L : m->bc) {
-            if (hipMemsetAsync(L->mu, 0, sizeof(float) * L->K, h->stream) != hipSuccess) rc = JG_ERR_HIP;
-            L->mu_rows = 0;
+        for (BiasCalib& c : m->bc) {
+            if (hipMemsetAsync(c.mu, 0, sizeof(float) * c.layer->K, h->stream) != hipSuccess) rc = JG_ERR_HIP;
+            c.mu_rows = 0;
         }
     }
     if (rc != JG_OK) h->err = "hipMemsetAsync(mu) failed";

@@ -68,6 +68,44 @@ def test_gemm_planner_matches_the_recorded_choices(golden_dir):
         gemm_plan(M=256, N=256, K=512, lda=512, ldw=512, ldc=256, out16=True, opts=dict(gemm_no_such_option=1))
 
 
+def test_weight_forms_match_the_recorded_rule(golden_dir):
+    """Which weights a layer's GEMM runs with (jegal_amd/csrc/weight_form.h, asked through jg_debug_weight_form / jg_debug_gemm_runs_lo: no
+    handle, no device) against what pack_matrix and gemm() decided BEFORE the rule moved there: all 7 precision modes x 4 layer kinds x
+    3 models x keep32 with the three booleans, whether the lo matrix was uploaded, whether the run-time pointer was set after finalize
+    and bc_pending; and all 32 rows of the run-time question.  Recorded by tools/weight_form_recorder.cpp from a stubbed copy of the old
+    expressions, never from the new functions."""
+    import json
+
+    import __graft_entry__ as G
+    G.build()
+    from jegal_amd._lib import WEIGHT_FORMS, gemm_runs_lo, weight_form
+    t = json.load(open(os.path.join(golden_dir, "weight_form_cases.json")))
+    assert len(t["pack"]) == 7 * 4 * 3 * 2 and len(t["run"]) == 4 * 2 * 2 * 2
+    assert len({(c["precision"], c["kind"], c["model"], c["keep32"]) for c in t["pack"]}) == 168
+    assert len({(c["form"], c["uncalibrated"], c["calibrating"], c["clip_bias"]) for c in t["run"]}) == 32
+    wrong = []
+    for c in t["pack"]:
+        assert c["split"] + c["bc"] + c["rc"] <= 1, c           # the forms exclude each other: one enum can carry them
+        want = WEIGHT_FORMS[1 * c["split"] + 2 * c["bc"] + 3 * c["rc"]]
+        form, lo_kept, uncal = weight_form(c["precision"], c["kind"], c["model"], c["keep32"])
+        # (a GEMM never asks for a lo matrix that was not kept)
+        assert lo_kept or not any(gemm_runs_lo(form, uncal, cal, cb) for cal in (0, 1) for cb in (0, 1)), c
+        # the old run-time pointer was what gemm() started from and what the fused-plan question read: the operand of a call that takes
+        # the per-clip bias wherever the layer has one (a run-time corrected layer kept its lo matrix behind the other pointer)
+        after_finalize = lo_kept and gemm_runs_lo(form, uncalibrated=uncal, clip_bias=True)
+        if (form, lo_kept, uncal, after_finalize) != (want, bool(c["lo_uploaded"]), bool(c["bc_pending"]), bool(c["wl_after_finalize"])):
+            wrong.append((c, form, lo_kept, uncal, after_finalize))
+    for c in t["run"]:
+        got = gemm_runs_lo(c["form"], c["uncalibrated"], c["calibrating"], c["clip_bias"])
+        if got != bool(c["lo"]):
+            wrong.append((c, got))
+    assert not wrong, wrong[:5]
+    from jegal_amd._lib import JegalError
+    for bad in ((7, 0, 1), (0, 4, 1), (0, 0, 0), (0, 0, 4)):     # an unknown mode / kind / model is an error, not a default
+        with pytest.raises(JegalError):
+            weight_form(*bad)
+
+
 def test_hot_kernels_do_not_spill():
     """the LN-fused GEMM carried 6 VGPR spills (28 B scratch), the 512x128 conv instance 8.  Read
     .vgpr_spill_count of every kernel from the gfx950 code objects inside libjegal_hip.so so that cannot come back."""
