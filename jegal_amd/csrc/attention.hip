@@ -643,6 +643,7 @@ static hipError_t launch_attn_mfma(const f16* qkv, const float* keymask, long np
     return hipGetLastError();
 }
 
+#ifndef JG_BF16      // fp16 only (declared in common.h's fp16-only block): a bf16 handle never has the tiled token stream this path needs
 // Layer-0 attention of the GestSync transformer from per-position projections (see attn_mfma_s32_kernel<true>):
 // B = windows (nclip * g.Twin), S <= 32 tokens, dk = 64.
 hipError_t launch_attention_gather(const f16* qkv_pos, const AttnGather& g, int B, int S, int H, f16* out, hipStream_t s, char* kname) {
@@ -655,6 +656,7 @@ hipError_t launch_attention_gather(const f16* qkv_pos, const AttnGather& g, int 
     else hipLaunchKernelGGL((attn_mfma_s32_kernel<true, 32>), dim3((blocks + 7) / 8 * 8), dim3(256), 0, s, qkv_pos, (int)npairs, S, H, out, g);
     return hipGetLastError();
 }
+#endif
 
 hipError_t launch_attention(const f16* qkv, const float* keymask, int B, int S, int H, int dk, f16* out, const EngineOpts& o, hipStream_t s) {
     if (B <= 0 || S <= 0) return hipSuccess;

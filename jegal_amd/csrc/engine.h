@@ -2,7 +2,7 @@
 // gestsync.hip, jegal.hip, xlmr.hip, checks.hip).  Host code only; the kernel units do not include it.
 #pragma once
 #include "common.h"
-#define JG_BF16                  // the bf16 build's declarations (namespace bf): same launchers, f16 = __bf16
+#define JG_BF16                  // the bf16 build's declarations (namespace bf): the dispatched launchers, f16 = __bf16
 #include "common.h"
 #undef JG_BF16
 #include "gemm_plan.h"
@@ -23,12 +23,12 @@ namespace engine {
 
 // ---- dispatch between the two kernel builds.  LAUNCH(h, launch_x, args...) calls launch_x of the fp16 build or bf::launch_x of
 // the bf16 build (precision mode JG_PREC_BF16): same argument lists, the 16-bit pointers and the structs that carry them are
-// layout-identical in both builds and simply re-typed.
+// layout-identical in both builds and simply re-typed.  Only launchers that depend on the 16-bit type AND run on a bf16 handle
+// exist in both builds and go through LAUNCH (the rule: common.h); every other launcher exists once and is called plainly.
 [[maybe_unused]] inline const bf::f16* to_bf(const f16* p) { return reinterpret_cast<const bf::f16*>(p); }
 inline bf::f16* to_bf(f16* p) { return reinterpret_cast<bf::f16*>(p); }
 inline const bf::GemmArgs& to_bf(const GemmArgs& a) { return reinterpret_cast<const bf::GemmArgs&>(a); }
-inline const bf::EngineOpts& to_bf(const EngineOpts& o) { return reinterpret_cast<const bf::EngineOpts&>(o); }
-static_assert(sizeof(bf::GemmArgs) == sizeof(GemmArgs) && sizeof(bf::EngineOpts) == sizeof(EngineOpts), "the two builds share their argument structs");
+static_assert(sizeof(bf::GemmArgs) == sizeof(GemmArgs), "the two builds share their argument struct");
 template <class T> inline T to_bf(T v) { return v; }
 template <class F, class G, class... A>
 inline hipError_t dispatch_build(bool bf16, F f, G g, A... a) { return bf16 ? g(to_bf(a)...) : f(a...); }
@@ -159,7 +159,7 @@ struct jg_handle {
     const int* last_conv_totals = nullptr;   // device [4]: rows conv2 .. conv5 of the last conv stack computed (jg_debug_conv_rows)
     long last_conv_full[4] = {0, 0, 0, 0};   // ... of these many
     std::map<std::string, engine::HostTensor> host;
-    EngineOpts opts;               // per-handle tuning switches + per-device resources (common.h)
+    EngineOpts opts;               // per-handle tuning switches + per-device resources (shared.h)
     char kname[KNAME_LEN] = {0};   // instance the last kernel check point launched (jg_debug_last_kernel)
     engine::Arena ws;
     bool prof = false;

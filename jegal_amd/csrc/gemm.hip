@@ -1040,30 +1040,10 @@ src = xsrc[i] + ((!XE && a.a_tiled) ? (long)sk0 * 128 : (long)sk0);        // ti
 #endif
 }
 
-// ---- host side: engine_opts_init / release, the launch thunks and launch_gemm.  Every tuning switch and per-device resource lives
-// in the caller's EngineOpts (one per jg_handle): nothing here is process-global except the "dynamic LDS attribute set" flags, which
-// are per (kernel instance, device).  The choice of the instance is the planner's (gemm_plan.hip).
+// ---- host side: the launch thunks and launch_gemm.  Every tuning switch and per-device resource lives in the caller's EngineOpts
+// (one per jg_handle): nothing here is process-global except the "dynamic LDS attribute set" flags, which are per (kernel instance,
+// device).  The choice of the instance is the planner's (gemm_plan.hip).
 constexpr int MAX_DEV = 64;
-
-hipError_t engine_opts_init(EngineOpts& o, int device) {
-    o.device = device;
-    hipDeviceProp_t prop;
-    hipError_t e = hipGetDeviceProperties(&prop, device);
-    if (e != hipSuccess) return e;
-    o.num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    f16* z = nullptr;
-    e = hipMalloc(&z, 256);                  // zero page on THIS device: LDS-DMA cannot predicate, but it can read zeros
-    if (e != hipSuccess) return e;
-    e = hipMemset(z, 0, 256);
-    if (e != hipSuccess) return e;
-    o.zeros = z;
-    return hipSuccess;
-}
-
-void engine_opts_release(EngineOpts& o) {
-    if (o.zeros) (void)hipFree(const_cast<f16*>(o.zeros));
-    o.zeros = nullptr;
-}
 
 // One launch thunk per entry of the instance table (gemm_plan.h): it owns the instance's "dynamic LDS attribute set" flags and
 // launches with the plan's figures.  Nothing is chosen here.
@@ -1081,8 +1061,8 @@ static hipError_t run_glds(const GemmArgs& a, const GemmPlan& p, const EngineOpt
     }
     if (!o.zeros) return hipErrorInvalidValue;
     record_kernel(o.kname, "%s", p.name);
-    hipLaunchKernelGGL((gemm_glds_kernel<W2, CONV, MI, WM, WN, LNF, SPR, XE, C32>), dim3(p.grid), dim3(512), p.lds, s, a, p.n_tiles, p.total_tiles, o.zeros,
-                       o.gemm_counted | (p.stagger << 8));
+    hipLaunchKernelGGL((gemm_glds_kernel<W2, CONV, MI, WM, WN, LNF, SPR, XE, C32>), dim3(p.grid), dim3(512), p.lds, s, a, p.n_tiles, p.total_tiles,
+                       static_cast<const f16*>(o.zeros), o.gemm_counted | (p.stagger << 8));
     return hipGetLastError();
 }
 
@@ -1106,8 +1086,7 @@ static_assert(sizeof(GEMM_THUNKS) / sizeof(GEMM_THUNKS[0]) == GEMM_NUM_INSTANCES
 // shape of the arguments -> plan (gemm_plan.hip: every rule lives there) -> the table
 hipError_t launch_gemm(const GemmArgs& a, bool conv, const EngineOpts& o, hipStream_t s) {
     if (a.M <= 0) return hipSuccess;
-    // (the planner reads the options through the fp16 build's EngineOpts; the two builds' structs are layout-identical, engine.h)
-    const GemmPlan p = plan_gemm(gemm_shape(a, conv), reinterpret_cast<const ::EngineOpts&>(o));
+    const GemmPlan p = plan_gemm(gemm_shape(a, conv), o);
     if (!p.ok()) return hipErrorInvalidValue;
     return GEMM_THUNKS[p.instance](a, p, o, s);
 }

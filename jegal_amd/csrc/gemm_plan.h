@@ -6,9 +6,7 @@
 // (checks.hip) shows the answer on a machine without a GPU.  The choice does not depend on the 16-bit operand type, so this header
 // is included once and is not part of the fp16 / bf16 double include of common.h: there is one planner in the library.
 #pragma once
-#include <cstddef>
-
-struct EngineOpts;      // common.h, the fp16 build's (the bf16 build's struct is layout-identical: engine.h)
+#include "shared.h"      // EngineOpts
 
 // ---- the instance table: every gemm_glds_kernel / gemm_kernel instantiation the library holds per build, each exactly once.
 // gemm_glds_kernel<W2, CONV, MI, WM, WN, LNF, SPR, XE, C32> (LDS-DMA; block tile 16 MI WM x 64 WN) ...

@@ -1,6 +1,5 @@
-// libjegal_hip: the GEMM planner (gemm_plan.h) -- every admission rule and every tile choice of launch_gemm.  Host code only, one
-// copy for both kernel builds.
-#include "common.h"
+// libjegal_hip: the GEMM planner (gemm_plan.h) -- every admission rule and every tile choice of launch_gemm -- and the EngineOpts
+// it reads (engine_opts_set / init / release).  Host code only, one copy for both kernel builds.
 #include "gemm_plan.h"
 
 #include <algorithm>
@@ -170,4 +169,24 @@ bool engine_opts_set(EngineOpts& o, const char* name, int value) {
     else if (!std::strcmp(name, "gemm_stagger")) o.gemm_stagger = value;
     else return false;
     return true;
+}
+
+hipError_t engine_opts_init(EngineOpts& o, int device) {
+    o.device = device;
+    hipDeviceProp_t prop;
+    hipError_t e = hipGetDeviceProperties(&prop, device);
+    if (e != hipSuccess) return e;
+    o.num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    void* z = nullptr;
+    e = hipMalloc(&z, 256);                  // zero page on THIS device: LDS-DMA cannot predicate, but it can read zeros
+    if (e != hipSuccess) return e;
+    e = hipMemset(z, 0, 256);
+    if (e != hipSuccess) return e;
+    o.zeros = z;
+    return hipSuccess;
+}
+
+void engine_opts_release(EngineOpts& o) {
+    if (o.zeros) (void)hipFree(const_cast<void*>(o.zeros));
+    o.zeros = nullptr;
 }

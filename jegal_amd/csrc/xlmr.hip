@@ -160,7 +160,7 @@ static int xlmr_encode_folded(jg_handle* h, const int32_t* ids, const int32_t* a
         RET(timed(h, JG_ST_MISC, [&] { return launch_mask_i32_f32(amask, mk, M, h->stream); }));
     }
     RET(timed(h, JG_ST_MISC, [&] { return LAUNCH(h, launch_xlmr_embed_planes, ids, B, L, D, 1, xl.vocab, xl.maxpos, xl.word, xl.pos, xl.type, xh, xlo, part, h->stream); }));
-    auto ln_stats = [&]() { return timed(h, JG_ST_NORM, [&] { return LAUNCH(h, launch_ln_stats, part, Mp, P, stats, h->stream); }); };
+    auto ln_stats = [&]() { return timed(h, JG_ST_NORM, [&] { return launch_ln_stats(part, Mp, P, stats, h->stream); }); };
     RET(ln_stats());
     const LNp* prev = &xl.emb_ln;
     for (int l = 0; l < (int)xl.layers.size(); ++l) {

@@ -143,6 +143,27 @@ def test_no_packed_fp32_instructions_in_the_library():
     assert not packed, packed
 
 
+def test_bf16_build_holds_exactly_the_dispatched_launchers():
+    """The rule of the two kernel builds (jegal_amd/csrc/common.h): a launcher exists in namespace bf if and only if some call site
+    dispatches it with LAUNCH(h, launch_x, ...).  The library's symbol table against a scan of the sources; EngineOpts and its
+    engine_opts_* functions do not depend on the 16-bit type and exist once."""
+    import glob
+    import __graft_entry__ as G
+    G.build()
+    dispatched = set()
+    for path in glob.glob(os.path.join(ROOT, "jegal_amd", "csrc", "*.hip")):
+        dispatched |= set(re.findall(r"\bLAUNCH\(\s*h\s*,\s*(launch_\w+)", open(path).read()))
+    assert len(dispatched) >= 10
+    nm = subprocess.run(["nm", "--defined-only", os.path.join(ROOT, "jegal_amd", "libjegal_hip.so")],
+                        capture_output=True, text=True, check=True).stdout
+    # mangled names: this toolchain's demangler leaves some names with __bf16 parameters as they are
+    in_bf = {m.group(2)[:int(m.group(1))] for m in re.finditer(r"\b_ZN2bf(\d+)(\w+)", nm)}
+    assert {n for n in in_bf if n.startswith("launch_")} == dispatched
+    assert not {n for n in in_bf if n.startswith("engine_opts_")}
+    plain = {m.group(2)[:int(m.group(1))] for m in re.finditer(r"\b_Z(\d+)(launch_\w+)", nm)}
+    assert dispatched <= plain                   # and the fp16 build defines every one of them too
+
+
 def test_engine_fails_loudly_without_gpu():
     if torch.cuda.is_available():
         pytest.skip("GPU present")
