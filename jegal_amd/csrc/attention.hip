@@ -250,11 +250,6 @@ __global__ __launch_bounds__(256, 5) void attn_mfma_s32_kernel(const f16* __rest
             vv[r] += *reinterpret_cast<const f16x8*>(p + 2 * D);
         }
     }
-    auto wave_sync = [] {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    };
     f16x8 kA[4], qB[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -263,16 +258,16 @@ __global__ __launch_bounds__(256, 5) void attn_mfma_s32_kernel(const f16* __rest
 #pragma unroll
         for (int e = 0; e < 8; ++e) *reinterpret_cast<f16*>(sVt + (part * 8 + e) * VT_PITCH + row * 2) = vv[r][e];
     }
-    wave_sync();
+    wave_lds_sync();
 #pragma unroll
     for (int s = 0; s < 4; ++s) kA[s] = *reinterpret_cast<const f16x8*>(sO + r31o * O_PITCH + (8 * hh + 16 * s) * 2);
-    wave_sync();
+    wave_lds_sync();
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int c = lane + 64 * r, row = c >> 3, part = c & 7;
         if (OR == 32 || row < OR) *reinterpret_cast<f16x8*>(sO + row * O_PITCH + part * 16) = qq[r];
     }
-    wave_sync();
+    wave_lds_sync();
 #pragma unroll
     for (int s = 0; s < 4; ++s) qB[s] = *reinterpret_cast<const f16x8*>(sO + r31o * O_PITCH + (8 * hh + 16 * s) * 2);
 
@@ -313,9 +308,7 @@ __global__ __launch_bounds__(256, 5) void attn_mfma_s32_kernel(const f16* __rest
         }
 
     // ---- O^T = V^T P^T
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     f32x16 o[2];
 #pragma unroll
     for (int blk = 0; blk < 2; ++blk) {
@@ -338,9 +331,7 @@ __global__ __launch_bounds__(256, 5) void attn_mfma_s32_kernel(const f16* __rest
             const f16x4 hv = {(f16)o[blk][4 * g], (f16)o[blk][4 * g + 1], (f16)o[blk][4 * g + 2], (f16)o[blk][4 * g + 3]};
             if (OR == 32 || r31 < OR) *reinterpret_cast<f16x4*>(sO + r31 * O_PITCH + (32 * blk + 8 * g + 4 * hh) * 2) = hv;
         }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     f16* obase = out + (long)b * S * D + head * DK;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -473,9 +464,7 @@ __global__ __launch_bounds__(64 * NB) void attn_mfma_kernel(const f16* __restric
             const f16x4 hv = {(f16)o[blk][4 * g], (f16)o[blk][4 * g + 1], (f16)o[blk][4 * g + 2], (f16)o[blk][4 * g + 3]};
             *reinterpret_cast<f16x4*>(sO + r31 * O_PITCH + (32 * blk + 8 * g + 4 * hh) * 2) = hv;
         }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     f16* obase = out + ((long)b * S + q0) * D + head * DK;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -616,17 +605,13 @@ __global__ __launch_bounds__(512) void attn_mfma_flash_kernel(const f16* __restr
             const f16x4 hv = {(f16)(o[blk][4 * g] * inv), (f16)(o[blk][4 * g + 1] * inv), (f16)(o[blk][4 * g + 2] * inv), (f16)(o[blk][4 * g + 3] * inv)};
             *reinterpret_cast<f16x4*>(sO + r31 * O_PITCH + (8 * g + 4 * hh) * 2) = hv;
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
 #pragma unroll
         for (int r = 0; r < 2; ++r) {
             const int c = lane + 64 * r, row = c >> 2, part = c & 3;
             if (q0 + row < S) *reinterpret_cast<f16x8*>(obase + (long)row * D + 32 * blk + part * 8) = *reinterpret_cast<const f16x8*>(sO + row * O_PITCH + part * 16);
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
     }
 }
 

@@ -82,6 +82,13 @@ __device__ __forceinline__ float wave_sum(float v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+// One wave hands data to its own lanes through LDS (a per-wave scratch area): what its lanes wrote before this point is visible to what
+// they read after it, and the compiler moves no access across it.  No workgroup barrier: the other waves are not involved.
+__device__ __forceinline__ void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
 #endif
 
 // out[m][n] = epi( sum_k A[m][k] * (Wh[n][k] + Wl[n][k]) )

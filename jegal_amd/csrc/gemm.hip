@@ -16,6 +16,10 @@
 //   rounding, not activation rounding, dominates the end-to-end error (precision).
 // * CONV: the activation "row" m is an output pixel (img,oh,ow) of an NHWC tensor and
 //   k = (kh,kw,c); out-of-image taps are zero-filled at staging time.
+// * The parts, in file order: act4; gemm_kernel (register-staged); for the LDS-DMA kernel the tile context (TileCtx; the tile's sizes
+//   and LDS layout are GldsTile in gemm_plan.h), load_scale_bias, the epilogue functions epi_ln_producer and epi_rows16 (plain instances), then
+//   gemm_glds_kernel itself: persistent tile walk, per-lane loader state (setup / stage_begin / stage_piece), k loop, LayerNorm-fused
+//   epilogue and the ladder that picks one of the other epilogues (what is still written out in the kernel body, and why: see there).
 // * Host side (end of the file): launch_gemm asks the planner (gemm_plan.h / gemm_plan.hip) which instance a launch gets and
 //   launches that entry of one table of thunks; no admission rule and no tile choice lives in this file.
 #include "common.h"
@@ -229,6 +233,216 @@ typedef const __attribute__((address_space(1))) void* glb_ptr_t;
 
 template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
+// What an epilogue knows about the tile at hand (gemm_glds_kernel fills it in per tile, behind the k loop); GldsTile (gemm_plan.h) is the
+// compile-time half: the sizes and the offsets of the scratch in LDS stage 1.
+struct TileCtx {
+    const GemmArgs& a;
+    char* smem;               // the two LDS stages
+    int wave, lane;
+    int frow, fq;             // the lane's place in a 16x16 MFMA tile: it holds D[n = 4*fq + r][m = frow]
+    int wm, wn;               // the wave's place in the block tile
+    int cm0, cn0;             // first row / column of the tile
+    int nb, mb;               // first column / row of the lane (+ i*16 / + j*16 per MFMA tile)
+    int Mrows;                // rows of the launch
+    bool m_full;              // the tile has all its rows: no store needs a mask
+};
+
+// scale / bias of the lane's 4 x 4 columns nb + i*16 .. +3 (1 / 0 where the vector is absent)
+__device__ __forceinline__ void load_scale_bias(const float* scale, const float* bias, int nb, f32x4 (&sc)[4], f32x4 (&bi)[4]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        sc[i] = f32x4{1.f, 1.f, 1.f, 1.f};
+        bi[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    if (scale) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) sc[i] = *reinterpret_cast<const f32x4*>(scale + nb + i * 16);
+    }
+    if (bias) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) bi[i] = *reinterpret_cast<const f32x4*>(bias + nb + i * 16);
+    }
+}
+
+// ---- epi_ln_producer (XE 2): implicit-LayerNorm producer: v = acc + bias + gamma * rstd[m] * (x_prev - mean[m]); v leaves as two fp16
+// planes (hi = fp16(v), the next GEMM's A operand; lo = fp16(v - hi)) through the row-transposing scratch, one plane after
+// the other, plus the (sum, sum of squares) of this wave's 64 columns per row.  The residual planes are read in
+// fragment order (4 x 8 B per plane and 16-row block: one 128-B line per row over the four i), one block ahead.
+// registers (the 256x256 instance holds 128 accumulators): the bias goes into the accumulators up front, the row
+// statistics ride with the residual prefetch, and where LDS stage 1 has room for two scratch areas per wave the lo plane
+// is written to its own area next to the hi plane instead of waiting in registers
+template <bool W2, int MI, int WM, int WN>
+__device__ __forceinline__ void epi_ln_producer(const TileCtx& c, f32x4 (&acc)[4][MI]) {
+    constexpr GldsTile T = glds_tile(W2, MI, WM, WN);
+    constexpr bool LO_LDS = T.LO_LDS;
+    constexpr int TP16 = T.TP16;
+    static_assert(T.PROD_END <= T.STAGE, "LDS stage 1 holds the producer epilogue's scratch and gamma");
+    const GemmArgs& a = c.a;
+    const int wave = c.wave, lane = c.lane, frow = c.frow, fq = c.fq, wn = c.wn, cn0 = c.cn0, nb = c.nb, mb = c.mb, Mrows = c.Mrows;
+    const bool m_full = c.m_full;
+    const int orow_m = c.cm0 + c.wm * (16 * MI) + (lane >> 3);
+    char* tsc = c.smem + T.STAGE + wave * T.PROD_WAVE;
+    char* tsl = LO_LDS ? tsc + T.PROD_WAVE / 2 : tsc;
+    // gamma of this wave's 64 columns waits in LDS (256 B behind the transposing scratch; one ds_read_b128 per use)
+    float* gsc = reinterpret_cast<float*>(c.smem + T.STAGE + T.PROD_GSC) + wave * 64;
+    gsc[lane] = a.scale[cn0 + wn * 64 + lane];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const f32x4 bi = *reinterpret_cast<const f32x4*>(a.bias + nb + i * 16);
+#pragma unroll
+        for (int j = 0; j < MI; ++j) acc[i][j] += bi;
+    }
+    wave_lds_sync();
+    f16x4 rh[2][4], rl[2][4];
+    f32x2_t rst[2];
+    auto ldres = [&](int j) __attribute__((always_inline)) {
+        const int m = mb + j * 16 < Mrows ? mb + j * 16 : Mrows - 1;
+        const long o = (long)m * a.ldc + nb;
+        rst[j & 1] = *reinterpret_cast<const f32x2_t*>(a.ln_stats + 2 * (long)m);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            rh[j & 1][i] = *reinterpret_cast<const f16x4*>(a.xres_hi + o + i * 16);
+            rl[j & 1][i] = *reinterpret_cast<const f16x4*>(a.xres_lo + o + i * 16);
+        }
+    };
+    ldres(0);
+    const long ocol = cn0 + wn * 64 + (lane & 7) * 8;
+    const int sblk = (cn0 >> 6) + wn, nblk = a.N >> 6;
+#pragma unroll
+    for (int j = 0; j < MI; ++j) {
+        if (j + 1 < MI) ldres(j + 1);
+        float s1 = 0.f, s2 = 0.f;
+        f16x4 lo4[LO_LDS ? 1 : 4];
+        const float mu = rst[j & 1].x, rs = rst[j & 1].y;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const f16x4 xh = rh[j & 1][i], xl = rl[j & 1][i];
+            const f32x4 x = {(float)xh.x + (float)xl.x, (float)xh.y + (float)xl.y, (float)xh.z + (float)xl.z, (float)xh.w + (float)xl.w};
+            const f32x4 v = acc[i][j] + *reinterpret_cast<const f32x4*>(gsc + i * 16 + fq * 4) * ((x - mu) * rs);
+            s1 += (v.x + v.y) + (v.z + v.w);
+            s2 += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
+            const f16x4 hv = {(f16)v.x, (f16)v.y, (f16)v.z, (f16)v.w};
+            const f16x4 lv = {(f16)(v.x - (float)hv.x), (f16)(v.y - (float)hv.y), (f16)(v.z - (float)hv.z), (f16)(v.w - (float)hv.w)};
+            *reinterpret_cast<f16x4*>(tsc + frow * TP16 + i * 32 + fq * 8) = hv;
+            if (LO_LDS) *reinterpret_cast<f16x4*>(tsl + frow * TP16 + i * 32 + fq * 8) = lv;
+            else lo4[i] = lv;
+        }
+#pragma unroll
+        for (int pl = 0; pl < 2; ++pl) {
+            if (pl == 1 && LO_LDS) break;
+            if (pl == 1) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) *reinterpret_cast<f16x4*>(tsc + frow * TP16 + i * 32 + fq * 8) = lo4[LO_LDS ? 0 : i];
+            }
+            wave_lds_sync();
+            // (its own row store, not a helper shared with epi_rows16: the shared form cost the 128x128 single-weight instance 2 VGPRs)
+#pragma unroll
+            for (int q2 = 0; q2 < (LO_LDS ? 2 : 1); ++q2) {
+                f16* const plane = (LO_LDS ? q2 : pl) ? a.out_lo : a.out16;
+                const char* src = (LO_LDS && q2) ? tsl : tsc;
+#pragma unroll
+                for (int h2 = 0; h2 < 2; ++h2) {
+                    const f16x8 o = *reinterpret_cast<const f16x8*>(src + (h2 * 8 + (lane >> 3)) * TP16 + (lane & 7) * 16);
+                    const long orow = orow_m + j * 16 + h2 * 8;
+                    if (m_full || orow < Mrows) *reinterpret_cast<f16x8*>(plane + orow * a.ldc + ocol) = o;
+                }
+            }
+            wave_lds_sync();
+        }
+        s1 += __shfl_xor(s1, 16, 64);
+        s2 += __shfl_xor(s2, 16, 64);
+        s1 += __shfl_xor(s1, 32, 64);
+        s2 += __shfl_xor(s2, 32, 64);
+        if (fq == 0 && (m_full || mb + j * 16 < Mrows))
+            *reinterpret_cast<f32x2_t*>(a.stat_out + 2 * ((long)(mb + j * 16) * nblk + sblk)) = f32x2_t{s1, s2};
+    }
+}
+
+// ---- epi_rows16: fp16-only outputs (qkv, linear1, the conv layers) are transposed through LDS so that every store
+// instruction writes 8 rows x 128 contiguous bytes.  In the MFMA fragment layout a store instruction covers
+// 16 rows x 32 B, and the CU's write path retires those at ~17 GB/s: 8-9 us per 256x256 tile, as long as the
+// whole k loop at K = 512 (tools/store_pattern.hip, profiles/r5_gemm_timeline.txt).  The scratch is this wave's
+// slice of LDS stage 1, idle until the next tile's k-tile 1 is staged (after the barrier at the loop top);
+// a wave's LDS instructions execute in order, so consecutive 16-row blocks reuse the same 2.3 KB.
+// XE 1: the implicit-LayerNorm consumer form, with per-row (rstd, mean) factors.  Leaves 2 MI stores per lane in flight.
+// Plain instances only: the conv instances keep their form of it in the kernel body (see the ladder there).
+template <bool W2, int MI, int WM, int WN, int XE>
+__device__ __forceinline__ void epi_rows16(const TileCtx& c, f32x4 (&acc)[4][MI]) {
+    constexpr GldsTile T = glds_tile(W2, MI, WM, WN);
+    constexpr int TP16 = T.TP16;
+    static_assert(T.ROWS_END <= T.STAGE, "LDS stage 1 holds the row epilogue's scratch and its per-wave table");
+    const GemmArgs& a = c.a;
+    const int wave = c.wave, lane = c.lane, frow = c.frow, fq = c.fq, wn = c.wn, cm0 = c.cm0, cn0 = c.cn0, nb = c.nb, mb = c.mb, Mrows = c.Mrows;
+    const int orow_m = cm0 + c.wm * (16 * MI) + (lane >> 3);
+    char* tsc = c.smem + T.STAGE + wave * T.ROWS_WAVE;
+    // per-clip bias (GemmArgs::bias_clip; plain instances): a tile inside one clip just takes that clip's vector; a tile that
+    // meets a clip boundary (one in twelve at 3150 rows per clip) picks the vector per 16-row block and lane
+    const float* bias_t = a.bias;
+    bool straddle = false;
+    if constexpr (XE == 0) {
+        if (a.bias_clip) {
+            const int c0 = cm0 / a.rpc;
+            straddle = (cm0 + T.BM - 1) / a.rpc != c0;
+            bias_t = a.bias_clip + (long)(c0 < a.nclips ? c0 : a.nclips - 1) * a.N;
+        }
+    }
+    f32x4 sc[4], bi[4];
+    load_scale_bias(XE == 1 ? nullptr : a.scale, bias_t, nb, sc, bi);
+    f16* ocol = a.out16 + cn0 + wn * 64 + (lane & 7) * 8;
+    // ln_mode 1: out = rstd[m] * (acc - mean[m] * c1[n]) + bias[n], c1 (column sums of the folded weights) in GemmArgs::scale
+    float xrs[XE ? MI : 1], xrm[XE ? MI : 1];
+    // (registers: c1 of this wave's 64 columns waits in LDS behind the transposing scratch instead of in `sc`)
+    float* gsc = reinterpret_cast<float*>(c.smem + T.STAGE + T.ROWS_TAB) + wave * 64;
+    if constexpr (XE == 1) {
+        gsc[lane] = a.scale[cn0 + wn * 64 + lane];
+        wave_lds_sync();
+#pragma unroll
+        for (int j = 0; j < MI; ++j) {
+            const int m = mb + j * 16 < Mrows ? mb + j * 16 : Mrows - 1;
+            const f32x2_t st = *reinterpret_cast<const f32x2_t*>(a.ln_stats + 2 * (long)m);
+            xrs[j] = st.y;
+            xrm[j] = st.x * st.y;
+        }
+    }
+    auto store_rows = [&](auto masked_tag, auto straddle_tag) __attribute__((always_inline)) {
+        constexpr bool MASKED = decltype(masked_tag)::value;
+        constexpr bool STRADDLE = decltype(straddle_tag)::value;
+#pragma unroll
+        for (int j = 0; j < MI; ++j) {
+            const float* bj = nullptr;
+            if constexpr (STRADDLE) {
+                const int cj = (mb + j * 16) / a.rpc;
+                bj = a.bias_clip + (long)(cj < a.nclips ? cj : a.nclips - 1) * a.N + nb;
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                f32x4 v;
+                if constexpr (XE == 1) v = acc[i][j] * xrs[XE ? j : 0] + (bi[i] - *reinterpret_cast<const f32x4*>(gsc + i * 16 + fq * 4) * xrm[XE ? j : 0]);
+                else if constexpr (STRADDLE) v = acc[i][j] * sc[i] + *reinterpret_cast<const f32x4*>(bj + i * 16);
+                else v = acc[i][j] * sc[i] + bi[i];
+                v = act4(v, a.relu);
+                f16x4 hv = {(f16)v.x, (f16)v.y, (f16)v.z, (f16)v.w};
+                *reinterpret_cast<f16x4*>(tsc + frow * TP16 + i * 32 + fq * 8) = hv;
+            }
+            wave_lds_sync();
+#pragma unroll
+            for (int h2 = 0; h2 < 2; ++h2) {
+                const f16x8 o = *reinterpret_cast<const f16x8*>(tsc + (h2 * 8 + (lane >> 3)) * TP16 + (lane & 7) * 16);
+                const long orow = orow_m + j * 16 + h2 * 8;
+                if (!MASKED || orow_m + j * 16 + h2 * 8 < Mrows) __builtin_nontemporal_store(o, reinterpret_cast<f16x8*>(ocol + orow * a.ldc));
+            }
+            wave_lds_sync();
+        }
+    };
+    if constexpr (XE == 0) {
+        if (straddle) {
+            if (c.m_full) store_rows(std::false_type{}, std::true_type{}); else store_rows(std::true_type{}, std::true_type{});
+        } else if (c.m_full) store_rows(std::false_type{}, std::false_type{}); else store_rows(std::true_type{}, std::false_type{});
+    } else {
+        if (c.m_full) store_rows(std::false_type{}, std::false_type{}); else store_rows(std::true_type{}, std::false_type{});
+    }
+}
+
 // MI = 16-row MFMA tiles per wave along m (4: 64x64 wave tile, 8: 128x64); WM x WN waves.
 //   <4,4,2>: 256x128 block tile (hi+lo weights fit two LDS stages);  <8,2,4>: 256x256 block tile for single-fp16
 //   weights -- 1.5x fewer L2->LDS bytes per FLOP, which is what bounds the 256x128 kernel once the lo MFMAs are gone.
@@ -249,10 +463,8 @@ __global__ __launch_bounds__(512) void gemm_glds_kernel(GemmArgs a, int n_tiles,
     static_assert(!C32 || (CONV && !SPR && !W2), "C32: plain conv instance, single fp16 weights");
     static_assert(!LNF || (WM == 1 && !W2), "fused LayerNorm needs a row-wide tile: all 8 waves side by side along n");
     static_assert(!XE || (!CONV && !LNF), "implicit-LayerNorm epilogues: plain GEMM instances only");
-    constexpr int BM = 16 * MI * WM, BN = 64 * WN;
-    constexpr int XI = BM / 64, WI = BN / 64;            // LDS-DMA instructions (8 rows each) per wave per k-tile
-    constexpr int XB = BM * 128, WB = BN * 128;
-    constexpr int STAGE = XB + WB * (W2 ? 2 : 1);
+    constexpr GldsTile T = glds_tile(W2, MI, WM, WN);
+    constexpr int BM = T.BM, BN = T.BN, XI = T.XI, WI = T.WI, XB = T.XB, WB = T.WB, STAGE = T.STAGE, NPIECE = T.NPIECE;
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
     const int t = threadIdx.x, lane = t & 63;
@@ -357,8 +569,8 @@ __global__ __launch_bounds__(512) void gemm_glds_kernel(GemmArgs a, int n_tiles,
                 if constexpr (ROWCONST) xalt[i] = a.g.const_in + ((long)ih * a.g.W + iw) * a.g.C + c * 8;
             } else {
                 xpix[i] = 0;
-xsrc[i] = (!XE && a.a_tiled) ? a.A + (long)(m >> 7) * 65536 + ((m & 127) >> 4) * 1024 + (m & 15) * 16 + (c >> 1) * 256 + (c & 1) * 8
-                                            : a.A + (long)m * a.lda + c * 8;
+                xsrc[i] = (!XE && a.a_tiled) ? a.A + (long)(m >> 7) * 65536 + ((m & 127) >> 4) * 1024 + (m & 15) * 16 + (c >> 1) * 256 + (c & 1) * 8
+                                             : a.A + (long)m * a.lda + c * 8;
             }
         }
         // N % BN == 0 (launch_gemm sends anything else to gemm_kernel): no row clamp, piece i = base[i & 1] + (i >> 1) * 16 rows
@@ -377,7 +589,6 @@ xsrc[i] = (!XE && a.a_tiled) ? a.A + (long)(m >> 7) * 65536 + ((m & 127) >> 4) *
     // inside the k loop the pieces are spread over the MFMA schedule (an LDS-DMA issue costs ~60 cycles between
     // MFMAs but 100-185 in a burst of eight in front of them -- MI355X_MICROARCH.md -- and during that burst the
     // matrix pipe of every SIMD idles, because all waves leave the barrier together).
-    constexpr int NPIECE = XI + WI * (W2 ? 2 : 1);
     int sk0 = 0;
     long stapoff = 0;
     int stkh = 0, stkw = 0;
@@ -422,7 +633,7 @@ xsrc[i] = (!XE && a.a_tiled) ? a.A + (long)(m >> 7) * 65536 + ((m & 127) >> 4) *
                 src = ok ? xsrc[i] + stapoff : zeros;
                 if (ROWCONST && ok && ih < (xpix[i] & 0xff)) src = xalt[i] + stapoff;
             } else {
-src = xsrc[i] + ((!XE && a.a_tiled) ? (long)sk0 * 128 : (long)sk0);        // tiled plane: a k-tile is 8192 elements on
+                src = xsrc[i] + ((!XE && a.a_tiled) ? (long)sk0 * 128 : (long)sk0);        // tiled plane: a k-tile is 8192 elements on
             }
             // LNF, long K (linear2: 413 MB of hidden activations read once by one tile each): nontemporal (aux = 2) so
             // the stream does not push the weights out of L2.  Measured: linear2+LN 282 -> 266 us; for out_proj (K = 512,
@@ -631,24 +842,21 @@ src = xsrc[i] + ((!XE && a.a_tiled) ? (long)sk0 * 128 : (long)sk0);        // ti
             __syncthreads();     // drains the LDS-DMA of tile kt+1 (vmcnt(0)) and fences the reads of tile kt
         }
 
-        // fp16-only outputs (qkv, linear1, the conv layers) leave through the row-transposing epilogue below
-        constexpr int TP16 = 144;                        // row pitch: 16-B aligned, 36 banks -> conflict-free b64 writes
-        constexpr bool ROWS_OK = STAGE / 8 >= 16 * TP16;
-        const bool rows16 = ROWS_OK && interior && a.out16 && !a.out32 && !ares && (a.ldc & 7) == 0;
-        // implicit LayerNorm (XE instances; launch_gemm checks the shapes): 1 = consumer, through the rows16 path with per-row
-        // (rstd, mean) factors; 2 = producer, the two-plane path below
-        const int orow_m = cm0 + wm * (16 * MI) + (lane >> 3);
-        // ConvGeom::rowmap: the full output rows of this wave's 16*MI tile rows (both store paths below stay inside them) go
+        // fp16-only outputs (qkv, linear1, the conv layers) leave through the row-transposing epilogue (epi_rows16).  Every tile has room for
+        // its scratch in LDS stage 1: the epilogue asserts it, so an instance with a smaller tile fails to build instead of falling back
+        // to the fragment store.
+        const bool rows16 = interior && a.out16 && !a.out32 && !ares && (a.ldc & 7) == 0;
+        // ConvGeom::rowmap: the full output rows of this wave's 16*MI tile rows (epi_rows16 and the fragment store stay inside them) go
         // through a per-wave table in LDS -- 1-2 loads per lane, in front of the next tile's setup and OLDER than its first DMA,
         // so nothing in the epilogue waits for that DMA.  (Sixteen row indices per lane in registers spilled the 512x128 and
         // the ROWCONST instances, and so did two values kept live across setup().)  The table sits behind
-        // the transposing epilogue's scratch in LDS stage 1, which is idle until the next tile's k-tile 1 is staged.
+        // the transposing epilogue's scratch in LDS stage 1 (GldsTile::ROWS_TAB), which is idle until the next tile's k-tile 1 is staged.
         constexpr int WROWS = 16 * MI;
         // (per-lane table addresses are recomputed from a laundered lane id per tile: hoisted out of the persistent loop as
         // invariants they cost the 512x128 instance four spilled registers)
         int lane_t = lane;
         if constexpr (CONV) asm volatile("" : "+v"(lane_t));
-        int* rtab = reinterpret_cast<int*>(smem + STAGE + 8 * (16 * TP16)) + wave * 128;
+        int* rtab = reinterpret_cast<int*>(smem + STAGE + T.ROWS_TAB) + wave * 128;
         const bool use_rtab = CONV && rmap && interior;
         if constexpr (CONV) {
             if (use_rtab) {
@@ -657,9 +865,7 @@ src = xsrc[i] + ((!XE && a.a_tiled) ? (long)sk0 * 128 : (long)sk0);        // ti
                 const int i0 = wrow0 + lane_t < Mrows ? wrow0 + lane_t : Mrows - 1, i1 = wrow0 + 64 + lane_t < Mrows ? wrow0 + 64 + lane_t : Mrows - 1;
                 if (WROWS >= 64 || lane_t < WROWS) rtab[lane_t] = rmap[i0] & 0xffffff;
                 if (WROWS > 64) rtab[64 + lane_t] = rmap[i1] & 0xffffff;
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                wave_lds_sync();
             }
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -682,8 +888,9 @@ src = xsrc[i] + ((!XE && a.a_tiled) ? (long)sk0 * 128 : (long)sk0);        // ti
             // is retired with a counted wait.  Whole 128-row tiles are written: the planes hold ceil(M/128)*128 rows.
             // bias / gamma / beta come from LDS (3 x 512 floats, re-staged per tile: the k loop owns the LDS).
             constexpr int JD = JG_LNF_JD;                                 // row block in front of which the next tile's DMA goes (default 2)
-            float* red = reinterpret_cast<float*>(smem + STAGE);          // [2][8 waves][BM rows]
-            float* lnp = red + 2 * 8 * BM;                                // [4][BN]: bias, gamma, beta, bias of the tile's second clip
+            static_assert(T.LN_END <= STAGE, "LDS stage 1 holds the LayerNorm epilogue's statistics and parameters");
+            float* red = reinterpret_cast<float*>(smem + STAGE + T.LN_RED);        // [2][8 waves][BM rows]
+            float* lnp = reinterpret_cast<float*>(smem + STAGE + T.LN_PAR);        // [4][BN]: bias, gamma, beta, bias of the tile's second clip
             static_assert(BN == 512, "one parked element per thread");
             lnp[t] = pf_b0;
             lnp[BN + t] = pf_g;
@@ -761,202 +968,54 @@ src = xsrc[i] + ((!XE && a.a_tiled) ? (long)sk0 * 128 : (long)sk0);        // ti
             pending = counted_ok ? (MI - JD) * 8 : 0;
             continue;
         }
-        // ---- epilogue: lane holds D[n = 4*fq + r][m = frow] of each 16x16 tile.
-        // Interior tiles take a branch-free path: ALL residual / scale / bias loads are issued first, then
+        // ---- the other epilogues, one flat ladder: lane holds D[n = 4*fq + r][m = frow] of each 16x16 tile.  The XE instances are
+        // compiled with their one epilogue (launch_gemm checks the shapes).  epi_ln_producer and epi_rows16 are functions above the
+        // kernel.  Written out here, each because as a __forceinline__ function it cost instances registers (the figures per instance:
+        // profiles/gemm_glds_split_isa.md): the fragment store and the generic path (VGPRs, one spill), the LayerNorm epilogue above
+        // (16 VGPRs), the k loop (1 VGPR nearly everywhere, a peeled last iteration), and `pending` as one expression at the bottom.
+        // Fragment store: ALL residual / scale / bias loads are issued first, then
         // the math, then all stores.  (Per-element `if (m < M) load` made hipcc branch around every load
         // and wait vmcnt(0) after each one: 16 serial HBM round trips per tile, 1/3 of the Linear time.)
-        // fp16-only outputs (qkv, linear1, the conv layers): transpose the tile through LDS so that every store
-        // instruction writes 8 rows x 128 contiguous bytes.  In the MFMA fragment layout a store instruction covers
-        // 16 rows x 32 B, and the CU's write path retires those at ~17 GB/s: 8-9 us per 256x256 tile, as long as the
-        // whole k loop at K = 512 (tools/store_pattern.hip, profiles/r5_gemm_timeline.txt).  The scratch is this wave's
-        // slice of LDS stage 1, idle until the next tile's k-tile 1 is staged (after the barrier at the loop top);
-        // a wave's LDS instructions execute in order, so consecutive 16-row blocks reuse the same 2.3 KB.
-        constexpr bool xdone = XE == 2;
+        const TileCtx c = {a, smem, wave, lane, frow, fq, wm, wn, cm0, cn0, nb, mb, Mrows, m_full};
         if constexpr (XE == 2) {
-            {
-                // ---- implicit-LayerNorm producer: v = acc + bias + gamma * rstd[m] * (x_prev - mean[m]); v leaves as two fp16 planes
-                // (hi = fp16(v), the next GEMM's A operand; lo = fp16(v - hi)) through the row-transposing scratch, one plane after
-                // the other, plus the (sum, sum of squares) of this wave's 64 columns per row.  The residual planes are read in
-                // fragment order (4 x 8 B per plane and 16-row block: one 128-B line per row over the four i), one block ahead.
-                // registers (the 256x256 instance holds 128 accumulators): the bias goes into the accumulators up front, the row
-                // statistics ride with the residual prefetch, and where LDS stage 1 has room for two scratch areas per wave the lo plane
-                // is written to its own area next to the hi plane instead of waiting in registers
-                constexpr bool LO_LDS = STAGE / 8 >= 32 * TP16;
-                char* tsc = smem + STAGE + wave * ((LO_LDS ? 32 : 16) * TP16);
-                char* tsl = LO_LDS ? tsc + 16 * TP16 : tsc;
-                // gamma of this wave's 64 columns waits in LDS (256 B behind the transposing scratch; one ds_read_b128 per use)
-                float* gsc = reinterpret_cast<float*>(smem + STAGE + 8 * ((LO_LDS ? 32 : 16) * TP16)) + wave * 64;
-                static_assert(STAGE >= 8 * ((LO_LDS ? 32 : 16) * TP16) + 8 * 256, "LDS stage 1 holds the epilogue scratch");
-                gsc[lane] = a.scale[cn0 + wn * 64 + lane];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const f32x4 bi = *reinterpret_cast<const f32x4*>(a.bias + nb + i * 16);
-#pragma unroll
-                    for (int j = 0; j < MI; ++j) acc[i][j] += bi;
-                }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                f16x4 rh[2][4], rl[2][4];
-                f32x2_t rst[2];
-                auto ldres = [&](int j) __attribute__((always_inline)) {
-                    const int m = mb + j * 16 < Mrows ? mb + j * 16 : Mrows - 1;
-                    const long o = (long)m * a.ldc + nb;
-                    rst[j & 1] = *reinterpret_cast<const f32x2_t*>(a.ln_stats + 2 * (long)m);
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        rh[j & 1][i] = *reinterpret_cast<const f16x4*>(a.xres_hi + o + i * 16);
-                        rl[j & 1][i] = *reinterpret_cast<const f16x4*>(a.xres_lo + o + i * 16);
-                    }
-                };
-                ldres(0);
-                const long ocol = cn0 + wn * 64 + (lane & 7) * 8;
-                const int sblk = (cn0 >> 6) + wn, nblk = a.N >> 6;
-#pragma unroll
-                for (int j = 0; j < MI; ++j) {
-                    if (j + 1 < MI) ldres(j + 1);
-                    float s1 = 0.f, s2 = 0.f;
-                    f16x4 lo4[LO_LDS ? 1 : 4];
-                    const float mu = rst[j & 1].x, rs = rst[j & 1].y;
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        const f16x4 xh = rh[j & 1][i], xl = rl[j & 1][i];
-                        const f32x4 x = {(float)xh.x + (float)xl.x, (float)xh.y + (float)xl.y, (float)xh.z + (float)xl.z, (float)xh.w + (float)xl.w};
-                        const f32x4 v = acc[i][j] + *reinterpret_cast<const f32x4*>(gsc + i * 16 + fq * 4) * ((x - mu) * rs);
-                        s1 += (v.x + v.y) + (v.z + v.w);
-                        s2 += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
-                        const f16x4 hv = {(f16)v.x, (f16)v.y, (f16)v.z, (f16)v.w};
-                        const f16x4 lv = {(f16)(v.x - (float)hv.x), (f16)(v.y - (float)hv.y), (f16)(v.z - (float)hv.z), (f16)(v.w - (float)hv.w)};
-                        *reinterpret_cast<f16x4*>(tsc + frow * TP16 + i * 32 + fq * 8) = hv;
-                        if (LO_LDS) *reinterpret_cast<f16x4*>(tsl + frow * TP16 + i * 32 + fq * 8) = lv;
-                        else lo4[i] = lv;
-                    }
-#pragma unroll
-                    for (int pl = 0; pl < 2; ++pl) {
-                        if (pl == 1 && LO_LDS) break;
-                        if (pl == 1) {
-#pragma unroll
-                            for (int i = 0; i < 4; ++i) *reinterpret_cast<f16x4*>(tsc + frow * TP16 + i * 32 + fq * 8) = lo4[LO_LDS ? 0 : i];
-                        }
-                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                        __builtin_amdgcn_wave_barrier();
-                        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#pragma unroll
-                        for (int q2 = 0; q2 < (LO_LDS ? 2 : 1); ++q2) {
-                            f16* const plane = (LO_LDS ? q2 : pl) ? a.out_lo : a.out16;
-                            const char* src = (LO_LDS && q2) ? tsl : tsc;
-#pragma unroll
-                            for (int h2 = 0; h2 < 2; ++h2) {
-                                const f16x8 o = *reinterpret_cast<const f16x8*>(src + (h2 * 8 + (lane >> 3)) * TP16 + (lane & 7) * 16);
-                                const long orow = orow_m + j * 16 + h2 * 8;
-                                if (m_full || orow < Mrows) *reinterpret_cast<f16x8*>(plane + orow * a.ldc + ocol) = o;
-                            }
-                        }
-                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                        __builtin_amdgcn_wave_barrier();
-                        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                    }
-                    s1 += __shfl_xor(s1, 16, 64);
-                    s2 += __shfl_xor(s2, 16, 64);
-                    s1 += __shfl_xor(s1, 32, 64);
-                    s2 += __shfl_xor(s2, 32, 64);
-                    if (fq == 0 && (m_full || mb + j * 16 < Mrows))
-                        *reinterpret_cast<f32x2_t*>(a.stat_out + 2 * ((long)(mb + j * 16) * nblk + sblk)) = f32x2_t{s1, s2};
-                }
-            }
-        }
-        if constexpr (xdone) {
-        } else if (rows16 || XE == 1) {
-            char* tsc = smem + STAGE + wave * (16 * TP16);
-            f32x4 sc[4], bi[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                sc[i] = f32x4{1.f, 1.f, 1.f, 1.f};
-                bi[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-            }
-            if (XE != 1 && a.scale) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) sc[i] = *reinterpret_cast<const f32x4*>(a.scale + nb + i * 16);
-            }
-            // per-clip bias (GemmArgs::bias_clip; plain instances): a tile inside one clip just takes that clip's vector; a tile that
-            // meets a clip boundary (one in twelve at 3150 rows per clip) picks the vector per 16-row block and lane
-            const float* bias_t = a.bias;
-            bool straddle = false;
-            if constexpr (!CONV && XE == 0) {
-                if (a.bias_clip) {
-                    const int c0 = cm0 / a.rpc;
-                    straddle = (cm0 + BM - 1) / a.rpc != c0;
-                    bias_t = a.bias_clip + (long)(c0 < a.nclips ? c0 : a.nclips - 1) * a.N;
-                }
-            }
-            if (bias_t) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) bi[i] = *reinterpret_cast<const f32x4*>(bias_t + nb + i * 16);
-            }
-            f16* ocol = a.out16 + cn0 + wn * 64 + (lane & 7) * 8;
-            // ln_mode 1: out = rstd[m] * (acc - mean[m] * c1[n]) + bias[n], c1 (column sums of the folded weights) in `sc`
-            float xrs[XE ? MI : 1], xrm[XE ? MI : 1];
-            // (registers: c1 of this wave's 64 columns waits in LDS behind the transposing scratch instead of in `sc`)
-            float* gsc = reinterpret_cast<float*>(smem + STAGE + 8 * (16 * TP16)) + wave * 64;
-            if constexpr (XE == 1) {
-                static_assert(!XE || STAGE >= 8 * (16 * TP16) + 8 * 256, "LDS stage 1 holds the epilogue scratch");
-                gsc[lane] = a.scale[cn0 + wn * 64 + lane];
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                {
+            epi_ln_producer<W2, MI, WM, WN>(c, acc);
+        } else if (XE == 1 || rows16) {
+            if constexpr (!CONV) {
+                epi_rows16<W2, MI, WM, WN, XE>(c, acc);
+            } else {
+                // the conv form of epi_rows16 (ReLU only, output rows through rtab), written out: as a call it cost three conv instances 1-2 SGPR spills
+                static_assert(T.ROWS_END <= STAGE, "LDS stage 1 holds the row epilogue's scratch and its per-wave table");
+                constexpr int TP16 = T.TP16;
+                char* tsc = smem + STAGE + wave * T.ROWS_WAVE;
+                const int orow_m = cm0 + wm * (16 * MI) + (lane >> 3);
+                f32x4 sc[4], bi[4];
+                load_scale_bias(a.scale, a.bias, nb, sc, bi);
+                f16* ocol = a.out16 + cn0 + wn * 64 + (lane & 7) * 8;
+                auto store_rows = [&](auto masked_tag) __attribute__((always_inline)) {
+                    constexpr bool MASKED = decltype(masked_tag)::value;
 #pragma unroll
                     for (int j = 0; j < MI; ++j) {
-                        const int m = mb + j * 16 < Mrows ? mb + j * 16 : Mrows - 1;
-                        const f32x2_t st = *reinterpret_cast<const f32x2_t*>(a.ln_stats + 2 * (long)m);
-                        xrs[j] = st.y;
-                        xrm[j] = st.x * st.y;
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) {
+                            f32x4 v = acc[i][j] * sc[i] + bi[i];
+                            v = act4(v, a.relu != 0);
+                            f16x4 hv = {(f16)v.x, (f16)v.y, (f16)v.z, (f16)v.w};
+                            *reinterpret_cast<f16x4*>(tsc + frow * TP16 + i * 32 + fq * 8) = hv;
+                        }
+                        wave_lds_sync();
+#pragma unroll
+                        for (int h2 = 0; h2 < 2; ++h2) {
+                            const f16x8 o = *reinterpret_cast<const f16x8*>(tsc + (h2 * 8 + (lane >> 3)) * TP16 + (lane & 7) * 16);
+                            const long orow = use_rtab ? rtab[j * 16 + h2 * 8 + (lane_t >> 3)] : orow_m + j * 16 + h2 * 8;
+                            if (!MASKED || orow_m + j * 16 + h2 * 8 < Mrows) __builtin_nontemporal_store(o, reinterpret_cast<f16x8*>(ocol + orow * a.ldc));
+                        }
+                        wave_lds_sync();
                     }
-                }
+                };
+                if (m_full) store_rows(std::false_type{}); else store_rows(std::true_type{});
             }
-            auto store_rows = [&](auto masked_tag, auto straddle_tag) __attribute__((always_inline)) {
-                constexpr bool MASKED = decltype(masked_tag)::value;
-                constexpr bool STRADDLE = decltype(straddle_tag)::value;
-#pragma unroll
-                for (int j = 0; j < MI; ++j) {
-                    const float* bj = nullptr;
-                    if constexpr (STRADDLE) {
-                        const int cj = (mb + j * 16) / a.rpc;
-                        bj = a.bias_clip + (long)(cj < a.nclips ? cj : a.nclips - 1) * a.N + nb;
-                    }
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        f32x4 v;
-                        if constexpr (XE == 1) v = acc[i][j] * xrs[XE ? j : 0] + (bi[i] - *reinterpret_cast<const f32x4*>(gsc + i * 16 + fq * 4) * xrm[XE ? j : 0]);
-                        else if constexpr (STRADDLE) v = acc[i][j] * sc[i] + *reinterpret_cast<const f32x4*>(bj + i * 16);
-                        else v = acc[i][j] * sc[i] + bi[i];
-                        v = act4(v, CONV ? (a.relu != 0) : a.relu);
-                        f16x4 hv = {(f16)v.x, (f16)v.y, (f16)v.z, (f16)v.w};
-                        *reinterpret_cast<f16x4*>(tsc + frow * TP16 + i * 32 + fq * 8) = hv;
-                    }
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#pragma unroll
-                    for (int h2 = 0; h2 < 2; ++h2) {
-                        const f16x8 o = *reinterpret_cast<const f16x8*>(tsc + (h2 * 8 + (lane >> 3)) * TP16 + (lane & 7) * 16);
-                        const long orow = use_rtab ? rtab[j * 16 + h2 * 8 + (lane_t >> 3)] : orow_m + j * 16 + h2 * 8;
-                        if (!MASKED || orow_m + j * 16 + h2 * 8 < Mrows) __builtin_nontemporal_store(o, reinterpret_cast<f16x8*>(ocol + orow * a.ldc));
-                    }
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                }
-            };
-            if constexpr (!CONV && XE == 0) {
-                if (straddle) {
-                    if (m_full) store_rows(std::false_type{}, std::true_type{}); else store_rows(std::true_type{}, std::true_type{});
-                } else if (m_full) store_rows(std::false_type{}, std::false_type{}); else store_rows(std::true_type{}, std::false_type{});
-            } else {
-                if (m_full) store_rows(std::false_type{}, std::false_type{}); else store_rows(std::true_type{}, std::false_type{});
-            }
-        } else if constexpr (XE != 0) {
         } else if (interior) {
+            // (its own scale / bias block: with load_scale_bias hipcc laid the plain instances' store paths out with one more global store)
             f32x4 sc[4], bi[4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
@@ -1030,7 +1089,7 @@ src = xsrc[i] + ((!XE && a.a_tiled) ? (long)sk0 * 128 : (long)sk0);        // ti
             }
         }
         if (nbid < 0) break;
-        pending = !(interior && m_full && counted_ok) || xdone ? 0 : rows16 ? 2 * MI : (a.out32 ? 4 * MI : 0) + (a.out16 ? 4 * MI : 0);
+        pending = !(interior && m_full && counted_ok) || XE == 2 ? 0 : rows16 ? 2 * MI : (a.out32 ? 4 * MI : 0) + (a.out16 ? 4 * MI : 0);
     }
 #if defined(JG_CLOCK_STAMPS) && !defined(JG_BF16)
     if (wave == 0 && lane == 0 && blockIdx.x < 1024) {

@@ -46,6 +46,48 @@ constexpr GemmInstance GEMM_INSTANCES[] = {
 };
 constexpr int GEMM_NUM_INSTANCES = sizeof(GEMM_INSTANCES) / sizeof(GEMM_INSTANCES[0]);
 
+// ---- the LDS-DMA tile of gemm_glds_kernel<W2, CONV, MI, WM, WN, ...>: its sizes and the layout of the scratch that the epilogues keep
+// in LDS stage 1 (idle from the end of a tile's k loop until the next tile's k-tile 1 is staged).  One definition for the kernel, its
+// epilogues (gemm.hip: each one that keeps scratch there asserts that its areas fit in STAGE) and the planner (GemmPlan::lds).  A new
+// epilogue that needs scratch adds its offsets and its *_END here.
+struct GldsTile {
+    int BM, BN;             // block tile: 16 MI WM rows (m) x 64 WN columns (n); k-step 64 = one 128-B row per tile row
+    int XI, WI;             // LDS-DMA instructions (8 rows each) per wave and k-tile: activations, weights (hi; as many again for lo)
+    int XB, WB;             // bytes of a stage's activation tile / of one weight tile
+    int STAGE;              // bytes of one of the two stages: activations, hi weights (, lo weights)
+    int NPIECE;             // LDS-DMA instructions per wave and k-tile in all
+    int TP16;               // row pitch of the row-transposing scratch: 16-B aligned, 36 banks -> conflict-free b64 writes
+    // byte offsets from the start of stage 1
+    int ROWS_WAVE;          // epi_rows16: 16 rows x TP16 of transposing scratch per wave, from offset 0 ...
+    int ROWS_TAB;           // ... and behind the 8 waves' scratch the per-wave tables: 128 output rows (ConvGeom::rowmap; the fragment store reads
+    int ROWS_END;           //     them too) or 64 column factors (XE 1)
+    bool LO_LDS;            // epi_ln_producer: room for a second scratch area per wave (the lo plane, PROD_WAVE / 2 behind the hi plane)?
+    int PROD_WAVE;          // its transposing scratch per wave, from offset 0 ...
+    int PROD_GSC, PROD_END; // ... and gamma of each wave's 64 columns behind it
+    int LN_RED, LN_PAR, LN_END;      // LayerNorm-fused epilogue: row statistics [2][8 waves][BM], then [4][BN] bias / gamma / beta / second clip's bias
+    constexpr size_t lds() const { return 2 * (size_t)STAGE; }      // double-buffered; 128x512 LN-fused = 160 KiB, the whole LDS
+};
+constexpr GldsTile glds_tile(bool w2, int mi, int wm, int wn) {
+    GldsTile t = {};
+    t.BM = 16 * mi * wm; t.BN = 64 * wn;
+    t.XI = t.BM / 64; t.WI = t.BN / 64;
+    t.XB = t.BM * 128; t.WB = t.BN * 128;
+    t.STAGE = t.XB + t.WB * (w2 ? 2 : 1);
+    t.NPIECE = t.XI + t.WI * (w2 ? 2 : 1);
+    t.TP16 = 144;
+    t.ROWS_WAVE = 16 * t.TP16;
+    t.ROWS_TAB = 8 * t.ROWS_WAVE;
+    t.ROWS_END = t.ROWS_TAB + 8 * 128 * 4;
+    t.LO_LDS = t.STAGE / 8 >= 32 * t.TP16;
+    t.PROD_WAVE = (t.LO_LDS ? 32 : 16) * t.TP16;
+    t.PROD_GSC = 8 * t.PROD_WAVE;
+    t.PROD_END = t.PROD_GSC + 8 * 64 * 4;
+    t.LN_RED = 0;
+    t.LN_PAR = 2 * 8 * t.BM * 4;
+    t.LN_END = t.LN_PAR + 4 * t.BN * 4;
+    return t;
+}
+
 // ---- minimum row counts of the routes (the planner's own rules use them; the host pads or asks, it does not restate them)
 constexpr int GEMM_GLDS_MIN_ROWS = 128;         // a Linear launch reaches the LDS-DMA kernel from this many rows (shorter batches: pad with zero rows)
 constexpr int GEMM_GLDS_CONV_MIN_ROWS = 256;    // ... and a conv launch from this many output pixels

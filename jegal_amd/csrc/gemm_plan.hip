@@ -20,7 +20,7 @@ GemmPlan instance(const GemmShape& a, const EngineOpts& o, bool glds, bool w2, T
     const int bm = (glds ? 16 * t.mi : 64) * t.wm, bn = 64 * t.wn;
     const long tiles = ((a.M + bm - 1) / bm) * ((a.N + bn - 1) / bn);
     p.n_tiles = (a.N + bn - 1) / bn; p.total_tiles = (int)tiles;
-    p.lds = (size_t)(bm + bn * (w2 ? 2 : 1)) * 128 * (glds ? 2 : 1);      // LDS-DMA: double-buffered; 128x512 LN-fused = 160 KiB, the whole LDS
+    p.lds = glds ? glds_tile(w2, t.mi, t.wm, t.wn).lds() : (size_t)(bm + bn * (w2 ? 2 : 1)) * 128;      // register-staged: one stage
     p.grid = (unsigned)tiles;                                             // register-staged: one workgroup per tile
     if (!glds) return p;
     if ((lnf || o.gemm_persistent) && tiles > o.num_cu) p.grid = (unsigned)o.num_cu;

@@ -159,9 +159,7 @@ __global__ __launch_bounds__(256) void spot_kernel(const float* __restrict__ g, 
             dot = wsum(dot) / temp;
             if (lane == 0) L[w] = dot;
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
         float mx = -INFINITY;
         for (int w = lane; w < W; w += 64) mx = fmaxf(mx, L[w]);
         mx = wmax(mx);

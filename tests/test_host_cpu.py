@@ -122,6 +122,45 @@ def test_hot_kernels_do_not_spill():
     assert not spilled, spilled
 
 
+def test_kernel_isa_diff_sees_every_kernel_and_reports_what_differs():
+    """tools/kernel_isa_diff.py is what an edit to a kernel is checked with.  It has to see every kernel of the
+    library -- the set tools/kernel_resources.py reads the registers of -- with an instruction stream, the GEMM kernels' with every
+    instruction class it counts; to report no difference between a library and itself; and, given a copy in which one kernel lost an
+    instruction, another a register and a third is missing, to name exactly those with their old -> new figures."""
+    import copy
+    import re
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import kernel_isa_diff as D
+    from kernel_resources import kernel_resources
+    lib = os.path.join(ROOT, "jegal_amd", "libjegal_hip.so")
+    meta = kernel_resources(lib)
+    st = D.streams(lib, meta)
+    assert len(st) >= 150 and set(st) == set(meta)
+    assert all(len(v) > 10 for v in st.values())
+    glds = sorted(k for k in st if "gemm_glds_kernel" in k)
+    assert len(glds) >= 2 and all(sum(1 for x in st[k] if re.match(p, x)) > 0 for k in glds for _, p in D.COUNTED)
+    lines = []
+    assert D.compare(st, st, meta, meta, lines.append) == ([], True)
+    assert lines == [f"{len(st)} kernels in OLD, {len(st)} in NEW: {len(st)} identical, 0 differ"]
+    # a synthetic NEW: kernel a without its last MFMA, kernel b with one VGPR more, kernel c gone
+    a, b, c = glds[0], glds[1], sorted(k for k in st if k not in glds)[0]
+    st2, meta2 = dict(st), copy.deepcopy(meta)
+    last = max(i for i, x in enumerate(st[a]) if x.startswith("v_mfma"))
+    st2[a] = st[a][:last] + st[a][last + 1:]
+    meta2[b]["vgpr"] += 1
+    del st2[c], meta2[c]
+    lines = []
+    differ, same_names = D.compare(st, st2, meta, meta2, lines.append)
+    assert differ == sorted([a, b]) and not same_names
+    assert lines[0] == "only in OLD: " + c
+    n_ins, n_mfma = len(st[a]), sum(1 for x in st[a] if x.startswith("v_mfma"))
+    row_a = lines[lines.index("DIFFERS  " + a) + 1]
+    assert f"instructions {n_ins} -> {n_ins - 1}" in row_a and f"mfma {n_mfma} -> {n_mfma - 1}" in row_a and f"vgpr {meta[a]['vgpr']}  " in row_a
+    row_b = lines[lines.index("DIFFERS  " + b + "   (same instruction stream, other metadata)") + 1]
+    assert f"vgpr {meta[b]['vgpr']} -> {meta[b]['vgpr'] + 1}" in row_b and f"instructions {len(st[b])}  " in row_b
+    assert lines[-1] == f"{len(st)} kernels in OLD, {len(st) - 1} in NEW: {len(st) - 3} identical, 2 differ"
+
+
 def test_no_packed_fp32_instructions_in_the_library():
     """Round 6: on MI355X a v_pk_{fma,mul,add}_f32 whose low half selects the HIGH register of its second operand (op_sel:[0,1,..], what hipcc
     emits for `f32x4 * pair.y`) can read that operand as 0 in lanes 48-63 while waves of ANOTHER kernel issue MFMAs on the same SIMD

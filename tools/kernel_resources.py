@@ -36,7 +36,7 @@ def kernel_resources(lib=None):
                 get = lambda k: int(re.search(r"\." + k + r":\s+(\d+)", blk).group(1))
                 dem = subprocess.run(["c++filt", name.group(1)], capture_output=True, text=True).stdout.strip()
                 res[dem] = {"vgpr": get("vgpr_count"), "sgpr": get("sgpr_count"), "spill": get("vgpr_spill_count"),
-                            "scratch": get("private_segment_fixed_size"), "lds": get("group_segment_fixed_size")}
+                            "sgpr_spill": get("sgpr_spill_count"), "scratch": get("private_segment_fixed_size"), "lds": get("group_segment_fixed_size")}
     return res
 
 
