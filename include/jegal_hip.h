@@ -89,7 +89,7 @@ int jg_set_chunk(jg_handle* h, int clips_per_chunk);
  *   "dual_stream"     1: jg_extract_gesture and jg_gestsync_clip split a batch of >= 8 clips (and >= 256 frames in the smaller part) into two halves (option "dual_split": eighths of the batch on the first lane, default 4 since round 6; rounds 3-5: 3) and run the two parts concurrently on two internal
  *                     streams (own workspaces; the caller's stream is joined at entry and exit): one part's next kernel fills
  *                     the partly empty last round of the other's persistent kernels.  Bit-identical results.
- *   "num_cu"          workgroups a persistent kernel launches (default: the device's CU count; experiment)
+ *   "num_cu"          workgroups a persistent kernel launches, 1..1024 (default: the device's CU count; experiment)
  *   "lane_priority"   3 (default): the two lane streams are created with the device's highest stream priority; 0: normal priority (rounds 3-5);
  *                     1 / 2: only the second / first lane (a change drains and re-creates the lane streams).  HIP deals streams onto four hardware
  *                     queues PER PRIORITY LEVEL in creation order: normal-priority lanes can end up on one queue when the application owns
@@ -212,6 +212,36 @@ int jg_debug_weight_form(int precision, int kind, int model, int keep32, int* fo
 /* ... and whether a GEMM on a layer of that form takes the lo operand: uncalibrated as above, calibrating: a calibration pass is in
  * progress, clip_bias: the call takes the per-clip bias (a run-time corrected layer runs hi+lo in every call that cannot). */
 int jg_debug_gemm_runs_lo(int form, int uncalibrated, int calibrating, int clip_bias, int* lo);
+/* Implicit-GEMM convolution (launch_gemm with conv = true; tests/test_gpu_conv_fp64.py): ONE conv launch on caller operands, the geometry
+ * built by the function production uses (engine::geom), M = nimg * OH * OW output pixels.
+ *   out[(img, oh, ow)][n] = relu?( sum_{t, c} in[img][oh SH - PH + kh_t][ow SW - PW + kw_t][c] (Wh + Wl)[n][t C + c] * scale[n] + bias[n] )
+ * with the taps t in ConvGeom's order (reorder: by parity class when KH KW <= 32, jegal_amd/csrc/common.h), zero outside the image.
+ * K must be KH KW C, C a power of two >= 8, relu 0 or 1 (the conv epilogues know ReLU only).
+ * s2_host (host [nimg], optional; LDS-DMA instances only): the launch runs behind a row skip as conv layer `op` (0..3) of the GestSync
+ * stack does -- image img leaves out its first conv_skip_decode(s2[img], op) output rows (they stay untouched) and runs over the
+ * compacted row map that the production launch_conv_rowmaps builds in the handle's workspace in front of the GEMM; with const_in
+ * ([H][W][C] 16-bit) its input rows below conv_skip_decode(s2[img], op - 1) are read from const_in instead of `in`.  Every s2 must lie in
+ * 0..255 and leave its image at least one output row. */
+typedef struct jg_conv_check {
+    const void* in;                               /* NHWC 16-bit, [nimg][H][W][C] */
+    int nimg, H, W, C, KH, KW, SH, SW, PH, PW, reorder;
+    const void* Wh; const void* Wl; int64_t ldw;  /* [N][ldw] 16-bit, k = t C + c; Wl NULL: single weights */
+    int N, K;
+    const float* scale; const float* bias;        /* per n, or NULL */
+    int relu;
+    float* out32; void* out16; int64_t ldc;       /* [M][ldc], either or both */
+    const int32_t* s2_host; int op; const void* const_in;
+} jg_conv_check;
+int jg_debug_conv_check(jg_handle* h, const jg_conv_check* c);
+/* 3x3 / stride 2 max-pool, NHWC 16-bit (launch_maxpool3x3s2): in [nimg][H][W][C] -> out [nimg][(H-3)/2+1][(W-3)/2+1][C], C % 8 == 0, H, W >= 3.
+ * s2_host (host [nimg]) with const_in ([H][W][C]): input rows of image img below conv_skip_decode(s2[img], in_op) (<= H) come from const_in. */
+int jg_debug_maxpool(jg_handle* h, const void* in, int nimg, int H, int W, int C, const int32_t* s2_host, int in_op, const void* const_in, void* out);
+/* The compaction maps of conv layers op = 0 .. nlayers-1 behind a row-skipping conv1 (launch_conv_rowmaps) from the per-image counts
+ * s2_host (host [NF], each 0..255 with conv_skip_decode(s2, op) <= OH[op]).  Synchronises and copies to HOST buffers: map_host[l]
+ * NF*OH[l]*OW[l] ints (the device buffer is filled with the caller's content of map_host[l] first: only the first total entries are
+ * written), base_host[l] NF+1 ints, total_host[l] one int.  NF*OH*OW >= 2^24 or nlayers outside 1..4: JG_ERR_ARG. */
+int jg_debug_conv_rowmaps(jg_handle* h, const int32_t* s2_host, int NF, const int* OH, const int* OW, int nlayers, int32_t* const* map_host,
+                          int32_t* const* base_host, int32_t* total_host);
 /* fp32 GEMM of the audit mode (launch_gemm32): out = act(A W^T * scale + bias + res[m % res_mod]), act 0 / 1 ReLU / 2 exact GELU. */
 int jg_debug_gemm32(jg_handle* h, const float* A, int64_t lda, const float* W, int64_t ldw, int M, int N, int K, const float* scale,
                     const float* bias, const float* res, int64_t ldr, int res_mod, int act, float* out, int64_t ldc);

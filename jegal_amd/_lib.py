@@ -31,6 +31,11 @@ class GemmCheck(ctypes.Structure):
                 ("res", _P), ("ldr", _L), ("res_mod", _I), ("relu", _I), ("out32", _P), ("out16", _P), ("ldc", _L),
                 ("ln_w", _P), ("ln_b", _P), ("res16", _P),
                 ("ln_mode", _I), ("ln_stats", _P), ("xres_hi", _P), ("xres_lo", _P), ("out_lo", _P), ("stat_out", _P)]
+class ConvCheck(ctypes.Structure):
+    """struct jg_conv_check (include/jegal_hip.h): operands of one jg_debug_conv_check launch."""
+    _fields_ = [("in_", _P)] + [(k, _I) for k in ("nimg", "H", "W", "C", "KH", "KW", "SH", "SW", "PH", "PW", "reorder")] + [
+        ("Wh", _P), ("Wl", _P), ("ldw", _L), ("N", _I), ("K", _I), ("scale", _P), ("bias", _P), ("relu", _I),
+        ("out32", _P), ("out16", _P), ("ldc", _L), ("s2_host", ctypes.POINTER(ctypes.c_int32)), ("op", _I), ("const_in", _P)]
 class ConvShape(ctypes.Structure):
     """struct jg_conv_shape (include/jegal_hip.h): the part of a conv geometry the GEMM planner reads."""
     _fields_ = [(k, _I) for k in ("H", "W", "C", "KH", "KW", "PH", "PW", "tap_table", "rowmap", "const_in")]
@@ -56,6 +61,10 @@ _SIGS = {
     "jg_debug_gemm_ex": [_P, _P, _P, _I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_double)],
     "jg_debug_conv2_rowskip": [_P, ctypes.POINTER(ctypes.c_int)],
     "jg_debug_gemm_check": [_P, _P],
+    "jg_debug_conv_check": [_P, _P],
+    "jg_debug_maxpool": [_P, _P, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_int32), _I, _P, _P],
+    "jg_debug_conv_rowmaps": [_P, ctypes.POINTER(ctypes.c_int32), _I, ctypes.POINTER(_I), ctypes.POINTER(_I), _I, ctypes.POINTER(_P), ctypes.POINTER(_P),
+                              ctypes.POINTER(ctypes.c_int32)],
     "jg_debug_gemm_plan": [_P, _P, _I, _I, _I, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(_I), _I, ctypes.c_char_p, _I,
                            ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I)],
     "jg_debug_weight_form": [_I, _I, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I)],
@@ -353,6 +362,56 @@ class Engine:
                 v = v.data_ptr()
             setattr(c, k, v)
         self._ck(self.lib.jg_debug_gemm_check(self.h, ctypes.byref(c)))
+
+    def debug_conv_check(self, **kw):
+        """Implicit-GEMM convolution (launch_gemm, conv): keyword arguments are the fields of jg_conv_check (`in_` for its `in`); tensors are
+        passed by pointer, s2_host is a sequence of nimg ints (or None)."""
+        self._bind_stream()
+        c = ConvCheck()
+        s2 = kw.pop("s2_host", None)
+        for k, v in kw.items():
+            if isinstance(v, torch.Tensor):
+                if v.device != self.device:
+                    raise ValueError(f"debug_conv_check: {k} must be on {self.device}")
+                v = v.data_ptr()
+            setattr(c, "in_" if k == "in" else k, v)
+        if s2 is not None:
+            s2 = [int(x) for x in s2]
+            if len(s2) != c.nimg:
+                raise ValueError("debug_conv_check: s2_host needs one entry per image")
+            keep = (ctypes.c_int32 * len(s2))(*s2)
+            c.s2_host = ctypes.cast(keep, ctypes.POINTER(ctypes.c_int32))
+        self._ck(self.lib.jg_debug_conv_check(self.h, ctypes.byref(c)))
+
+    def debug_maxpool(self, x, out, s2_host=None, in_op=0, const_in=None):
+        """3x3 / stride 2 max-pool (launch_maxpool3x3s2): x (nimg,H,W,C) 16-bit NHWC -> out (nimg,(H-3)//2+1,(W-3)//2+1,C), written in place.
+        s2_host (nimg ints) / in_op / const_in (H,W,C): input rows below conv_skip_decode(s2, in_op) come from const_in."""
+        self._bind_stream()
+        nimg, H, W, C = x.shape
+        s2 = None
+        if s2_host is not None:
+            s2 = [int(v) for v in s2_host]
+            if len(s2) != nimg:
+                raise ValueError("debug_maxpool: s2_host needs one entry per image")
+            s2 = (ctypes.c_int32 * nimg)(*s2)
+        self._ck(self.lib.jg_debug_maxpool(self.h, _ptr(x), nimg, H, W, C, s2, int(in_op), _ptr(const_in), _ptr(out)))
+
+    def debug_conv_rowmaps(self, s2_host, layers, fill=-1):
+        """Compaction maps of conv layers op = 0 .. len(layers)-1 (launch_conv_rowmaps) for the per-image counts s2_host; layers: (OH, OW) per layer.
+        -> per layer (map int32 [NF*OH*OW], prefilled with `fill`: only the first `total` entries are written; base int32 [NF+1]; total)."""
+        self._bind_stream()
+        s2 = np.ascontiguousarray(np.asarray(s2_host, np.int32))
+        NF, nl = int(s2.size), len(layers)
+        maps = [np.full(NF * oh * ow, fill, np.int32) for oh, ow in layers]
+        bases = [np.full(NF + 1, fill, np.int32) for _ in layers]
+        totals = np.full(max(nl, 1), fill, np.int32)
+        i32p = ctypes.POINTER(ctypes.c_int32)
+        OH = (_I * max(nl, 1))(*[oh for oh, _ in layers])
+        OW = (_I * max(nl, 1))(*[ow for _, ow in layers])
+        mp = (_P * max(nl, 1))(*[m.ctypes.data for m in maps])
+        bp = (_P * max(nl, 1))(*[b.ctypes.data for b in bases])
+        self._ck(self.lib.jg_debug_conv_rowmaps(self.h, s2.ctypes.data_as(i32p), NF, OH, OW, nl, mp, bp, totals.ctypes.data_as(i32p)))
+        return [(maps[l], bases[l], int(totals[l])) for l in range(nl)]
 
     def debug_gemm32(self, A, lda, W, ldw, M, N, K, out, ldc, scale=None, bias=None, res=None, ldr=0, res_mod=0, act=0):
         self._bind_stream()

@@ -149,6 +149,118 @@ int jg_debug_gemm_check(jg_handle* h, const jg_gemm_check* c) {
     return check_result(h, LAUNCH(h, launch_gemm, a, false, o, h->stream), "launch_gemm");
 }
 
+// One conv launch of launch_gemm.  With s2_host the launch runs as layer `op` of the row-skipping chain does in gs_conv_stack: the production
+// launch_conv_rowmaps builds the layer's compacted map in the workspace in front of the GEMM.  The planner is asked before anything is
+// enqueued, so a rejected argument set launches nothing at all.
+int jg_debug_conv_check(jg_handle* h, const jg_conv_check* c) {
+    ENTER(h);
+    h->kname[0] = 0;
+    if (!c || !c->in || !c->Wh || c->nimg <= 0 || c->H <= 0 || c->W <= 0 || c->C < 8 || (c->C & (c->C - 1)) || c->KH <= 0 || c->KW <= 0 || c->KH > 15 ||
+        c->KW > 15 || c->SH <= 0 || c->SW <= 0 || c->PH < 0 || c->PW < 0 || c->H + 2 * c->PH < c->KH || c->W + 2 * c->PW < c->KW || c->N <= 0 ||
+        (long)c->KH * c->KW * c->C != c->K || c->ldw < c->K || (!c->out32 && !c->out16) || c->ldc < c->N || c->relu < 0 || c->relu > 1 || c->op < 0 ||
+        c->op > 3 || (c->const_in && (!c->s2_host || c->op == 0)))
+        JG_FAIL(h, JG_ERR_ARG, "jg_debug_conv_check: bad arguments (K = KH KW C, C a power of two >= 8, relu 0 / 1, op 0..3, const_in needs s2_host and op >= 1)");
+    ConvGeom g = geom(c->H, c->W, c->C, c->KH, c->KW, c->SH, c->SW, c->PH, c->PW, c->reorder != 0);
+    const long M = (long)c->nimg * g.OH * g.OW;
+    if (M >= (1L << 31)) JG_FAIL(h, JG_ERR_ARG, "jg_debug_conv_check: too many output pixels");
+    if (c->s2_host) {
+        for (int i = 0; i < c->nimg; ++i)
+            if (c->s2_host[i] < 0 || c->s2_host[i] > 255 || conv_skip_decode(c->s2_host[i], c->op) >= g.OH)
+                JG_FAIL(h, JG_ERR_ARG, "jg_debug_conv_check: s2[%d] = %d outside 0..255 or leaves image %d no output row", i, c->s2_host[i], i);
+    }
+    GemmArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.A = static_cast<const f16*>(c->in);
+    a.Wh = static_cast<const f16*>(c->Wh); a.Wl = static_cast<const f16*>(c->Wl); a.ldw = c->ldw;
+    a.M = (int)M; a.N = c->N; a.K = c->K;
+    a.scale = c->scale; a.bias = c->bias; a.relu = c->relu;
+    a.out32 = c->out32; a.out16 = static_cast<f16*>(c->out16); a.ldc = c->ldc;
+    EngineOpts o = h->opts;
+    o.kname = h->kname;          // the name slot the launchers write
+    if (c->s2_host) {
+        GemmShape q = gemm_shape(a, false);
+        q.set_geom(g);
+        q.rowmap = true; q.const_in = c->const_in != nullptr;
+        if (!plan_gemm(q, o).ok()) JG_FAIL(h, JG_ERR_ARG, "launch_gemm: the launcher rejects this shape / argument set");
+        h->ws.reset();
+        int32_t* s2;
+        int* totals;
+        ConvRowMap rm;
+        rm.OH = g.OH; rm.OW = g.OW; rm.op = c->op;
+        RET(wsalloc(h, (size_t)c->nimg, &s2));
+        RET(wsalloc(h, (size_t)M, &rm.map));
+        RET(wsalloc(h, (size_t)c->nimg + 1, &rm.base));
+        RET(wsalloc(h, (size_t)64, &totals));
+        rm.total = totals;
+        RET(upload_i32_async(h, c->s2_host, (size_t)c->nimg, s2));
+        const int rc = check_result(h, launch_conv_rowmaps(s2, c->nimg, &rm, 1, h->stream), "launch_conv_rowmaps");
+        if (rc != JG_OK) return rc;
+        g.rowmap = rm.map; g.rows_total = rm.total;
+        g.in_op = c->op - 1; g.const_in = static_cast<const f16*>(c->const_in);
+    }
+    a.g = g;
+    return check_result(h, LAUNCH(h, launch_gemm, a, true, o, h->stream), "launch_gemm");
+}
+
+int jg_debug_maxpool(jg_handle* h, const void* in, int nimg, int H, int W, int C, const int32_t* s2_host, int in_op, const void* const_in, void* out) {
+    ENTER(h);
+    h->kname[0] = 0;
+    if (!in || !out || nimg <= 0 || H < 3 || W < 3 || C <= 0 || C % 8 || (s2_host != nullptr) != (const_in != nullptr) || in_op < 0 || in_op > 3)
+        JG_FAIL(h, JG_ERR_ARG, "jg_debug_maxpool: bad arguments (C %% 8 == 0, H, W >= 3, s2_host and const_in together, in_op 0..3)");
+    int32_t* s2 = nullptr;
+    if (s2_host) {
+        for (int i = 0; i < nimg; ++i)
+            if (s2_host[i] < 0 || s2_host[i] > 255 || conv_skip_decode(s2_host[i], in_op) > H)
+                JG_FAIL(h, JG_ERR_ARG, "jg_debug_maxpool: s2[%d] = %d outside 0..255 or past the image's %d rows", i, s2_host[i], H);
+        h->ws.reset();
+        RET(wsalloc(h, (size_t)nimg, &s2));
+        RET(upload_i32_async(h, s2_host, (size_t)nimg, s2));
+    }
+    const int rc = check_result(h, LAUNCH(h, launch_maxpool3x3s2, static_cast<const f16*>(in), static_cast<f16*>(out), nimg, H, W, C, h->stream,
+                                          static_cast<const int*>(s2), in_op, static_cast<const f16*>(const_in)), "launch_maxpool3x3s2");
+    if (rc == JG_OK) record_kernel(h->kname, "%s", "maxpool_kernel");
+    return rc;
+}
+
+int jg_debug_conv_rowmaps(jg_handle* h, const int32_t* s2_host, int NF, const int* OH, const int* OW, int nlayers, int32_t* const* map_host,
+                          int32_t* const* base_host, int32_t* total_host) {
+    ENTER(h);
+    h->kname[0] = 0;
+    if (!s2_host || !OH || !OW || !map_host || !base_host || !total_host || NF <= 0) JG_FAIL(h, JG_ERR_ARG, "jg_debug_conv_rowmaps: bad arguments");
+    if (nlayers < 1 || nlayers > 4) JG_FAIL(h, JG_ERR_ARG, "launch_conv_rowmaps: the launcher rejects this shape / argument set");
+    for (int l = 0; l < nlayers; ++l) {
+        if (OH[l] <= 0 || OW[l] <= 0 || !map_host[l] || !base_host[l]) JG_FAIL(h, JG_ERR_ARG, "jg_debug_conv_rowmaps: bad layer %d", l);
+        for (int i = 0; i < NF; ++i)
+            if (s2_host[i] < 0 || s2_host[i] > 255 || conv_skip_decode(s2_host[i], l) > OH[l])
+                JG_FAIL(h, JG_ERR_ARG, "jg_debug_conv_rowmaps: s2[%d] = %d outside 0..255 or past layer %d's %d rows", i, s2_host[i], l, OH[l]);
+    }
+    h->ws.reset();
+    int32_t* s2;
+    int* totals;
+    ConvRowMap rm[4];
+    RET(wsalloc(h, (size_t)NF, &s2));
+    RET(wsalloc(h, (size_t)64, &totals));
+    RET(upload_i32_async(h, s2_host, (size_t)NF, s2));
+    for (int l = 0; l < nlayers; ++l) {
+        const size_t n = (size_t)NF * OH[l] * OW[l];
+        rm[l].OH = OH[l]; rm[l].OW = OW[l]; rm[l].op = l;
+        RET(wsalloc(h, n, &rm[l].map));
+        RET(wsalloc(h, (size_t)NF + 1, &rm[l].base));
+        rm[l].total = totals + l;
+        HIPCHK(h, hipMemcpy(rm[l].map, map_host[l], n * sizeof(int), hipMemcpyHostToDevice));      // the caller's fill: the launch writes the first *total entries only
+    }
+    const int rc = check_result(h, launch_conv_rowmaps(s2, NF, rm, nlayers, h->stream), "launch_conv_rowmaps");
+    if (rc != JG_OK) return rc;
+    record_kernel(h->kname, "%s", "conv_rowmap_scan_kernel+conv_rowmap_fill_kernel");
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (int l = 0; l < nlayers; ++l) {
+        HIPCHK(h, hipMemcpy(map_host[l], rm[l].map, (size_t)NF * OH[l] * OW[l] * sizeof(int), hipMemcpyDeviceToHost));
+        HIPCHK(h, hipMemcpy(base_host[l], rm[l].base, ((size_t)NF + 1) * sizeof(int), hipMemcpyDeviceToHost));
+        HIPCHK(h, hipMemcpy(total_host + l, rm[l].total, sizeof(int), hipMemcpyDeviceToHost));
+    }
+    return JG_OK;
+}
+
 int jg_debug_gemm_plan(const jg_gemm_check* c, const jg_conv_shape* conv, int a_tiled, int num_cu, int lanes_active, const char* const* opt_names,
                        const int* opt_values, int n_opts, char* name, int name_len, int* grid, int* lds, int* stagger) {
     if (!c || c->M <= 0 || c->N <= 0 || c->K <= 0 || num_cu <= 0 || n_opts < 0 || (n_opts && (!opt_names || !opt_values)) || !name || name_len <= 0 ||

@@ -136,12 +136,14 @@ GemmPlan plan_gemm(const GemmShape& a, const EngineOpts& o) {
     if (a.a_tiled && (a.conv || narrow || !o.gemm_glds || a.K != 512 || a.M < GEMM_GLDS_MIN_ROWS || a.N % 128)) return rejected;
     if (a.conv) {
         if (a.res) return rejected;          // the conv instances are compiled without the residual path
+        // as for the plain GEMMs below: 4 columns per lane in every store, 16-byte pieces of the weight rows in every loader
+        if (a.N % 4 || a.ldc % 4 || a.ldw % 8) return rejected;
         const bool coords_ok = a.H + a.PH < 2048 && a.W + a.PW < 2048 && a.M < (1 << 24);      // packed pixel coordinates / rowmap entries
         // C = 32 -> N = 64 (the second audio conv): its own LDS-DMA instance, 256x64 tiles (round 5; before: the register-staged kernel)
         if (o.gemm_glds && !a.w2 && a.N == 64 && a.C == 32 && a.K % 32 == 0 && a.K == a.KH * a.KW * 32 && !a.tap_table && !a.rowmap &&
             a.M >= GEMM_GLDS_CONV_MIN_ROWS && coords_ok && a.out16 && !a.out32 && (a.ldc & 7) == 0 && (a.ldw & 7) == 0)
             return glds(a, o, false, {2, 8, 1}, false, 0, true);
-        if (narrow) return staged(a, o, 4, 1);
+        if (narrow) return a.rowmap ? rejected : staged(a, o, 4, 1);      // (a row map: as below)
         if (o.gemm_glds && a.M >= GEMM_GLDS_CONV_MIN_ROWS && a.C % 64 == 0 && a.N % 128 == 0 && coords_ok) return plan_glds(a, o);
         if (a.rowmap) return rejected;          // only the LDS-DMA kernel knows the compaction
         return staged(a, o, 2, 2);

@@ -68,6 +68,30 @@ def test_gemm_planner_matches_the_recorded_choices(golden_dir):
         gemm_plan(M=256, N=256, K=512, lda=512, ldw=512, ldc=256, out16=True, opts=dict(gemm_no_such_option=1))
 
 
+def test_every_gemm_instance_has_a_kernel_level_case():
+    """The instance table of jegal_amd/csrc/gemm_plan.h, expanded from the text of its two macros, is exactly what the two float64 kernel
+    tests launch one by one (each ends with SEEN == its list): an instance added to the table cannot go without a kernel-level case."""
+    from test_gpu_conv_fp64 import CONV_INSTANCES
+    from test_gpu_kernels_fp64 import LINEAR_INSTANCES
+    text = open(os.path.join(ROOT, "jegal_amd", "csrc", "gemm_plan.h")).read()
+
+    def expand(macro, kernel, arity):
+        m = re.search(r"#define " + macro + r"\(X\)((?:.*\\\n)*.*\n)", text)
+        assert m, macro
+        body = re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S)
+        args = [[a.strip() for a in x.split(",")] for x in re.findall(r"\bX\(([^()]*)\)", body)]
+        assert args and all(len(a) == arity for a in args), (macro, args)
+        assert re.sub(r"\bX\([^()]*\)|[\s\\]", "", body) == "", f"{macro}: something besides X(...) entries"
+        return [f"{kernel}<{','.join(a)}>" for a in args]
+    table = expand("JG_GEMM_GLDS_INSTANCES", "gemm_glds_kernel", 9) + expand("JG_GEMM_STAGED_INSTANCES", "gemm_kernel", 4)
+    assert len(table) == len(set(table)) == 37
+    assert len(CONV_INSTANCES) == 16 and not (CONV_INSTANCES & LINEAR_INSTANCES)
+    assert LINEAR_INSTANCES | CONV_INSTANCES == set(table), (sorted(set(table) - LINEAR_INSTANCES - CONV_INSTANCES),
+                                                             sorted((LINEAR_INSTANCES | CONV_INSTANCES) - set(table)))
+    # CONV is the second template argument of the LDS-DMA kernel and the third of the register-staged one
+    assert all(n.split("<")[1].split(",")[1 if n.startswith("gemm_glds") else 2] == "1" for n in CONV_INSTANCES)
+
+
 def test_weight_forms_match_the_recorded_rule(golden_dir):
     """Which weights a layer's GEMM runs with (jegal_amd/csrc/weight_form.h, asked through jg_debug_weight_form / jg_debug_gemm_runs_lo: no
     handle, no device) against what pack_matrix and gemm() decided BEFORE the rule moved there: all 7 precision modes x 4 layer kinds x
