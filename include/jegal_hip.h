@@ -90,6 +90,9 @@ int jg_set_chunk(jg_handle* h, int clips_per_chunk);
  *                     streams (own workspaces; the caller's stream is joined at entry and exit): one part's next kernel fills
  *                     the partly empty last round of the other's persistent kernels.  Bit-identical results.
  *   "num_cu"          workgroups a persistent kernel launches, 1..1024 (default: the device's CU count; experiment)
+ *                     conv1_direct_kernel needs num_cu >= 8 or no more column strips (5 per position) than num_cu: it deals the strips out
+ *                     per XCD (workgroup index & 7), and with fewer than 8 workgroups some XCD ranges would have nobody; such a
+ *                     launch is rejected (JG_ERR_HIP, invalid value) instead of leaving pooled rows unwritten.
  *   "lane_priority"   3 (default): the two lane streams are created with the device's highest stream priority; 0: normal priority (rounds 3-5);
  *                     1 / 2: only the second / first lane (a change drains and re-creates the lane streams).  HIP deals streams onto four hardware
  *                     queues PER PRIORITY LEVEL in creation order: normal-priority lanes can end up on one queue when the application owns

@@ -110,98 +110,306 @@ __device__ __forceinline__ int conv1_s2_of_mask(unsigned sk) {
     return rs < C2_OH ? rs : C2_OH - 1;
 }
 
-// M16: the MFMA waves run v_mfma_f32_16x16x32_f16 (two pixel slots per k-step) instead of 32x32x16 (one slot): the same FLOPs per
-// cycle, but the chip holds a higher clock on the 16x16x32 shape (MI355X_MICROARCH.md "DVFS give-back" item 7; tools/mfma_rate.hip
-// on this part, random data, registers only: 19.7 ns per 32x32x16 = 1.70 PFLOP/s against 8.2-9.2 ns per 16x16x32 = 1.8-2.05),
-// and the MFMA waves are this kernel's critical role.  See the M16 block below for the k-step pairing and the LDS addressing.
+// ---- the strip walk ------------------------------------------------------------------------------------------------------------
+// Strip assignment, XCD-aware: workgroups b, b+8, b+16, ... share an XCD (and its 4 MB L2), so each
+// XCD gets ONE contiguous range of strips (= whole clips) and its workgroups walk it together --
+// the 5 frames of a position are then fetched into that L2 once instead of into all eight.
+// local tile t of this workgroup -> strip s_lo + (t/22)*GX, row tile t%22
+// All of this index math is 32-bit and incremental: the first version decoded every tile id with 64-bit
+// divisions (t/22, strip/5, nf/P) in both issue() and pool() -- ~1.2 us of VALU per tile on the loader waves,
+// which made THEM the critical path.
+struct Strips {
+    int s_lo, r_hi, GX;         // this workgroup's strips: s_lo, s_lo + GX, ... below r_hi (the end of its XCD's range)
+    // The skip masks of this workgroup's strips sit in LDS (filled by the kernel before the roles split): a global load inside the
+    // walks would put an s_waitcnt vmcnt(0) -- hipcc cannot count across the walks' loops -- behind every batch of frame loads.
+    const unsigned* tab;        // smem + OFF_SKIP: the positions' zero-band masks z of strip s_lo + k * GX
+    bool use_skip;              // the table is filled (Conv1Args::zmask)
+    __device__ __forceinline__ bool any() const { return s_lo < r_hi && GX > 0; }
+    __device__ __forceinline__ unsigned zero_bands(int k) const {
+        return use_skip ? (unsigned)__builtin_amdgcn_readfirstlane((int)tab[k]) : 0u;
+    }
+};
+__device__ __forceinline__ Strips conv1_strips(const Conv1Args& a, const char* smem) {
+    const int G32 = (int)gridDim.x;
+    const int xcd = blockIdx.x & 7, xidx = blockIdx.x >> 3;
+    const int GX = (G32 + 7 - xcd) >> 3;                                 // workgroups on this XCD
+    const int per = (a.nstrips + 7) >> 3;
+    const int r_lo = xcd * per, r_hi = (r_lo + per < a.nstrips) ? r_lo + per : a.nstrips;
+    return Strips{r_lo + xidx, r_hi, GX, reinterpret_cast<const unsigned*>(smem + OFF_SKIP), a.zmask != nullptr};
+}
+// strip -> (position nf, column tile j)
+__device__ __forceinline__ void strip_split(int strip, int& nf, int& j) {
+    nf = (int)((unsigned)strip / 5u);
+    j = strip - nf * 5;
+}
+// Tiles that are skipped OUTRIGHT (zmask, produced by conv1_zero_scan_kernel from the frames): a tile whose 16 input rows are
+// zero in all 5 frames computes relu(bias) everywhere; if the tile above is such a tile too (or does not exist), both of
+// its pooled rows and its carry are that constant whatever is below, so the tile needs no loads, no barrier slot and no
+// MFMA -- its pooled rows are filled with the constant when the pool waves enter the strip, and the tile below takes the
+// constant as its carry (pool(), carry_const).  A zero tile BELOW a non-zero tile still runs (2 bias slots, see
+// cvt_write): its upper pooled row mixes with real data.
+// z: bit rt = band rt is zero -> bit rt = tile rt is skipped: its band and the band above are zero
+__device__ __forceinline__ unsigned skip_of(unsigned z) { return z & ((z << 1) | 1u); }
+// The walk visits the remaining tiles of this workgroup's strips in order; all of it is wave-uniform.
+struct Walk {
+    int strip, rt;
+    int k;              // strip = s_lo + k * GX: index into the workgroup's skip table in LDS
+    unsigned skip;      // bit rt: tile rt of `strip` is skipped
+    unsigned z;         // bit rt: input band rt is zero in all five frames of the strip's position (the pre-scan's knowledge)
+    bool done;
+};
+// on_strip(strip, skip) is called once for every strip the walk enters (the pool walk fills the skipped tiles there)
+template <class F>
+__device__ __forceinline__ void walk_next(const Strips& S, Walk& q, F&& on_strip) {
+    if (q.done) return;
+    while (true) {
+        if (++q.rt == ROW_TILES) {
+            q.rt = 0;
+            q.strip += S.GX;
+            ++q.k;
+            if (q.strip >= S.r_hi) { q.done = true; return; }
+            q.z = S.zero_bands(q.k);
+            q.skip = skip_of(q.z);
+            on_strip(q.strip, q.skip);
+        }
+        if (!((q.skip >> q.rt) & 1u)) return;
+    }
+}
+template <class F>
+__device__ __forceinline__ Walk walk_first(const Strips& S, F&& on_strip) {
+    Walk q = {S.s_lo, -1, 0, 0u, 0u, !S.any()};
+    if (q.done) return q;
+    q.z = S.zero_bands(0);
+    q.skip = skip_of(q.z);
+    on_strip(q.strip, q.skip);
+    walk_next(S, q, on_strip);
+    return q;
+}
+
+// ---- tile state shared by the two roles ----------------------------------------------------------------------------------------
+// live[t & 1]: written by the loaders before the barrier of iteration t; 0 = the workgroup's tiles are done (this was the final barrier)
+__device__ __forceinline__ bool tile_live(const char* smem, int t) {
+    return __builtin_amdgcn_readfirstlane(*reinterpret_cast<const int*>(smem + OFF_LIVE + (t & 1) * 4)) != 0;
+}
+// no loader wave saw a non-zero byte in tile buffer t & 1 (flags, see cvt_write): final once the barrier of iteration t is passed
+__device__ __forceinline__ bool tile_is_zero(const char* smem, int t) {
+    const int4 fl = *reinterpret_cast<const int4*>(smem + OFF_INIT + (t & 1) * 16);
+    return __builtin_amdgcn_readfirstlane(fl.x | fl.y | fl.z | fl.w) == 0;
+}
+
+// ---- MFMA role (waves 0-3): two forms of one tile loop -------------------------------------------------------------------------
+// A wave computes, per tile, two blocks q (conv rows mb0 + 2q) of 32 columns x 32 channels (chalf).  A form supplies NSTEP k-steps per
+// block, NCB column blocks per step, DEPTH patch fragments in flight, its weight panel (constructor), the tile's base addresses
+// (set_tile), fragment gi = ((q * NSTEP + st) * NCB + cb) of the tile's stream (frag), the accumulate step and the epilogue (store).
+//
+// The 32x32x16 form: one k-step = one (kh, kw) pixel slot.
+struct Mfma32 {
+    static constexpr int NSTEP = 49, NCB = 1;
+    static constexpr int DEPTH = 6;                      // patch fragments in flight per wave
+    typedef f32x16 Acc;
+    const int chalf, r, h;
+    f16x8 wreg[49];
+    const char* base;
+    __device__ __forceinline__ Mfma32(const f16* Wd, int lane, int chalf_) : chalf(chalf_), r(lane & 31), h(lane >> 5) {
+#pragma unroll
+        for (int s = 0; s < 49; ++s)
+            wreg[s] = *reinterpret_cast<const f16x8*>(Wd + ((long)(s * 64 + chalf * 32 + r) * 16 + 8 * h));
+    }
+    // patch-fragment address of lane (r,h) for slot (kh,kw): pixel x = 3r+kw ->
+    //   (3*mb+kh)*ROW_PITCH + 32*x + 16*(x/3) + 16*h = [112*r + 16*h] + [kh*ROW_PITCH + 32*kw + 16*(kw/3)]
+    __device__ __forceinline__ void set_tile(const char* cur) { base = cur + 112 * r + 16 * h; }
+    __device__ __forceinline__ f16x8 frag(int gi) const {
+        const int q = gi / 49, s = gi - q * 49;
+        const int kh = s / 7, kw = s - kh * 7;
+        return *reinterpret_cast<const f16x8*>(base + (6 * q + kh) * ROW_PITCH + 32 * kw + 16 * (kw / 3));
+    }
+    __device__ __forceinline__ static void zero(Acc& acc) {
+#pragma unroll
+        for (int x = 0; x < 16; ++x) acc[x] = 0.f;
+    }
+    __device__ __forceinline__ void step(Acc& acc, int s, int, f16x8 f) const {
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wreg[s], f, acc, 0, 0, 0);
+    }
+    // D[i][jj]: jj = lane&31 -> conv column r, i = (x&3) + 8*(x>>2) + 4*h -> channel 32*chalf + 8g + 4h + (x&3).
+    // conv buffer [row mb][channel group chalf*4+g][col r][16 B], this lane's 4 channels = 8 B at +8h
+    // (scale is multiplied per element: as `vector * scale` the optimiser widens the kernel-argument load of `scale` over the
+    // neighbouring `out` pointer, which then loses its global address space -- the pooled-row stores become flat stores)
+    __device__ __forceinline__ void store(const Acc& acc, char* cbuf, int mb, float scale) const {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const f16x4 hv = {(f16)fmaxf(acc[4 * g] * scale, 0.f), (f16)fmaxf(acc[4 * g + 1] * scale, 0.f),
+                              (f16)fmaxf(acc[4 * g + 2] * scale, 0.f), (f16)fmaxf(acc[4 * g + 3] * scale, 0.f)};
+            *reinterpret_cast<f16x4*>(cbuf + ((mb * 8 + chalf * 4 + g) * 32 + r) * 16 + 8 * h) = hv;
+        }
+    }
+};
+// The 16x16x32 form (two pixel slots per k-step): the same FLOPs per cycle, but the chip holds a higher clock on the 16x16x32 shape
+// (MI355X_MICROARCH.md "DVFS give-back" item 7; tools/mfma_rate.hip on this part, random data, registers only: 19.7 ns per 32x32x16 =
+// 1.70 PFLOP/s against 8.2-9.2 ns per 16x16x32 = 1.8-2.05), and the MFMA waves are this kernel's critical role.
+// ---- v_mfma_f32_16x16x32_f16: a wave's block (conv row mb, 32 columns, 32 channels) = 2 channel blocks (ob) x 2 column
+// blocks (cb) of 16x16, K = 25 steps of 32 = two pixel slots each.  Lane (n = lane & 15, kq = lane >> 4) holds the k-slice
+//   slot = kq & 1 ? sB(t) : sA(t),   halves 8 * (kq >> 1) .. + 7
+// of step t, for the weights (A operand, registers) and for the patch (B operand, one ds_read_b128 from the tile image).
+// Pairing: (kh, kw) with (kh + 1, kw) for kh = 0, 2, 4 (21 steps, the B slot is one image row below: + ROW_PITCH), then in the
+// last kernel row kw (1,2), (4,5) (+ 32 B), (0,6) (+ 224 B) and kw = 3 alone (the B slot's weights are zero).  One base
+// register per distance and compile-time immediates for all the rest, as in the 32x32x16 form.
+// Bank conflicts: a ds_read_b128 group is {kq = 0 lanes n = 0-3, 12-15} + {kq = 1 lanes n = 4-11} (and its three images), so
+// the two slots of a step sit side by side in one group: the slot distance moves the 16-B bank quad by an EVEN amount in
+// all pairs (3744 / 16 = 234, 32 / 16 = 2, 224 / 16 = 14), and lane n's conv column is permuted so that n = 4..11 take the
+// even columns of the 16-column block and the others the odd ones (quad = 7 * column mod 16): conflict-free.
+struct Mfma16 {
+    static constexpr int NSTEP = 25, NCB = 2;
+    static constexpr int DEPTH = 4;                      // patch fragments in flight per wave (2 steps x 2 column blocks; 6 spill)
+    struct Acc { f32x4 v[2][2]; };                       // [channel block ob][column block cb]
+    const int chalf, n16, kq, sel, half, colp;
+    f16x8 wreg[25][2];
+    int lb_row, lb_32, lb_224;
+    int st_off;                                          // lane part of the epilogue's store address (with the full expression in store() the
+                                                         // zero-tile epilogue takes one address register per store: 253 -> 256 VGPRs)
+    const char *p_row, *p_32, *p_224;
+    __device__ __forceinline__ static void step_slots(int t, int& kha, int& kwa, int& khb, int& kwb) {
+        if (t < 21) { kha = 2 * (t / 7); kwa = t % 7; khb = kha + 1; kwb = kwa; }
+        else if (t == 21) { kha = khb = 6; kwa = 1; kwb = 2; }
+        else if (t == 22) { kha = khb = 6; kwa = 4; kwb = 5; }
+        else if (t == 23) { kha = khb = 6; kwa = 0; kwb = 6; }
+        else { kha = khb = 6; kwa = 3; kwb = 4; }          // t = 24: slot B is padding: zero weights, and its lanes read slot (6,4) -- a
+                                                           // real slot (finite values; the 16-B pads between slots are never written)
+    }
+    __device__ __forceinline__ Mfma16(const f16* Wd, int lane, int chalf_)
+        : chalf(chalf_), n16(lane & 15), kq(lane >> 4), sel(kq & 1), half(kq >> 1),
+          colp((n16 >= 4 && n16 < 12) ? 2 * (n16 - 4) : (n16 < 4 ? 2 * n16 + 1 : 2 * (n16 - 8) + 1)) {
+#pragma unroll
+        for (int t = 0; t < 25; ++t) {
+            int kha, kwa, khb, kwb;
+            step_slots(t, kha, kwa, khb, kwb);
+            const int sl = sel ? khb * 7 + kwb : kha * 7 + kwa;
+#pragma unroll
+            for (int ob = 0; ob < 2; ++ob) {
+                wreg[t][ob] = *reinterpret_cast<const f16x8*>(Wd + ((long)(sl * 64 + chalf * 32 + ob * 16 + n16) * 16 + 8 * half));
+                if (t == 24 && sel) wreg[t][ob] = f16x8{0, 0, 0, 0, 0, 0, 0, 0};
+            }
+        }
+        // lane part of the patch address: column block cb adds 16 columns = 1792 B, the step its slot-A offset; slot B = + sel * distance
+        const int lb = 112 * colp + 16 * half;
+        lb_row = lb + sel * ROW_PITCH; lb_32 = lb + sel * 32; lb_224 = lb + sel * 224;
+        st_off = ((chalf * 4 + (kq >> 1)) * 32 + colp) * 16 + 8 * (kq & 1);
+    }
+    __device__ __forceinline__ void set_tile(const char* cur) {
+        p_row = cur + lb_row;
+        p_32 = cur + lb_32;
+        p_224 = cur + lb_224;
+    }
+    // fragment gi of the tile's stream: (block q, step st, column block cb)
+    __device__ __forceinline__ f16x8 frag(int gi) const {
+        const int q = gi / 50, st = (gi - q * 50) >> 1, cb = gi & 1;
+        int kha, kwa, khb, kwb;
+        step_slots(st, kha, kwa, khb, kwb);
+        const int off = (6 * q + kha) * ROW_PITCH + 32 * kwa + 16 * (kwa / 3) + 1792 * cb;
+        const char* pb = st < 21 ? p_row : (st == 23 ? p_224 : p_32);
+        return *reinterpret_cast<const f16x8*>(pb + off);
+    }
+    __device__ __forceinline__ static void zero(Acc& acc) {
+#pragma unroll
+        for (int ob = 0; ob < 2; ++ob)
+#pragma unroll
+            for (int cb = 0; cb < 2; ++cb) acc.v[ob][cb] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    __device__ __forceinline__ void step(Acc& acc, int st, int cb, f16x8 f) const {
+        acc.v[0][cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wreg[st][0], f, acc.v[0][cb], 0, 0, 0);
+        acc.v[1][cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wreg[st][1], f, acc.v[1][cb], 0, 0, 0);
+    }
+    // D of a 16x16 block: lane (n, kq) holds channels 4 kq .. 4 kq + 3 of the channel block for column n.
+    // conv buffer [row mb][channel group][col][16 B]: group = chalf*4 + ob*2 + (kq >> 1), the lane's 4 channels = 8 B at + 8 (kq & 1)
+    // = st_off (the lane's part, column colp of the column block) + the wave-uniform (mb, ob, cb) part
+    __device__ __forceinline__ void store(const Acc& acc, char* cbuf, int mb, float scale) const {
+#pragma unroll
+        for (int ob = 0; ob < 2; ++ob)
+#pragma unroll
+            for (int cb = 0; cb < 2; ++cb) {
+                const f32x4 v = acc.v[ob][cb];
+                const f16x4 hv = {(f16)fmaxf(v.x * scale, 0.f), (f16)fmaxf(v.y * scale, 0.f), (f16)fmaxf(v.z * scale, 0.f), (f16)fmaxf(v.w * scale, 0.f)};
+                *reinterpret_cast<f16x4*>(cbuf + st_off + ((mb * 8 + ob * 2) * 32 + cb * 16) * 16) = hv;
+            }
+    }
+};
+
+// The tile loop of an MFMA wave.  The BN-folded bias rides in the GEMM: element 15 of every pixel slot is "1.0" (2^-24, the
+// same scale as the pixel values, see cvt_write) and the weight panel
+// holds shift/scale (hi+lo fp16 pair) at [slot 0][c][15] and [slot 1][c][15] -- no accumulator
+// init read, no global load in the epilogue:  out = relu(acc * scale).
+template <class Form>
+__device__ __forceinline__ void conv1_mfma_role(const f16* Wd, float scale, char* smem, int lane, int wave) {
+    constexpr int NSTEP = Form::NSTEP, NCB = Form::NCB, DEPTH = Form::DEPTH, NFRAG = 2 * NSTEP * NCB;
+    const int mb0 = (wave >> 1) & 1;
+    Form F(Wd, lane, wave & 1);
+#ifdef JG_CLOCK_STAMPS
+    const unsigned long long ck0 = __builtin_amdgcn_s_memtime(), rt0 = __builtin_amdgcn_s_memrealtime();
+#endif
+    for (int t = 0;; ++t) {
+        __syncthreads();
+        if (!tile_live(smem, t)) break;
+        F.set_tile(smem + (t & 1) * TILE_BYTES + 3 * mb0 * ROW_PITCH);
+        char* cbuf = smem + OFF_CONV + (t & 1) * CONV_BYTES;
+        if (tile_is_zero(smem, t)) {
+            // all-zero tile (see cvt_write): only slots (0,0) and (0,1) carry anything -- the bias pair on the pad lane: steps 0 and 1
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                typename Form::Acc acc;
+                Form::zero(acc);
+#pragma unroll
+                for (int st = 0; st < 2; ++st)
+#pragma unroll
+                    for (int cb = 0; cb < NCB; ++cb) F.step(acc, st, cb, F.frag((q * NSTEP + st) * NCB + cb));
+                F.store(acc, cbuf, mb0 + 2 * q, scale);
+            }
+            continue;
+        }
+        // The two blocks of a tile form ONE stream of NFRAG (block, step, column block) fragments with DEPTH of them in
+        // flight, so block 1's first fragments are already loading while block 0's epilogue runs.
+        f16x8 fr[DEPTH];
+#pragma unroll
+        for (int gi = 0; gi < DEPTH; ++gi) fr[gi] = F.frag(gi);
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            typename Form::Acc acc;
+            Form::zero(acc);
+#pragma unroll
+            for (int st = 0; st < NSTEP; ++st)
+#pragma unroll
+                for (int cb = 0; cb < NCB; ++cb) {
+                    const int gi = (q * NSTEP + st) * NCB + cb;
+                    F.step(acc, st, cb, fr[gi % DEPTH]);
+                    if (gi + DEPTH < NFRAG) fr[gi % DEPTH] = F.frag(gi + DEPTH);
+                    // pin the order: without this hipcc sinks every ds_read next to its MFMA (one fragment
+                    // register, lgkmcnt(0) per MFMA) and the LDS latency is exposed once per step
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            F.store(acc, cbuf, mb0 + 2 * q, scale);
+        }
+    }
+#ifdef JG_CLOCK_STAMPS
+    if (wave == 0 && lane == 0 && blockIdx.x < 1024) {
+        jg_clock_stamps_conv1[2 * blockIdx.x] = __builtin_amdgcn_s_memtime() - ck0;
+        jg_clock_stamps_conv1[2 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime() - rt0;
+    }
+#endif
+}
+
+// M16: the MFMA waves run the 16x16x32 form (Mfma16) instead of the 32x32x16 one (Mfma32).
 template <bool M16>
 __global__ __launch_bounds__(512, 2) void conv1_direct_kernel(Conv1Args a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const long G = gridDim.x;
-    // The BN-folded bias rides in the GEMM: element 15 of every pixel slot is "1.0" (2^-24, the
-    // same scale as the pixel values, see cvt_write) and the weight panel
-    // holds shift/scale (hi+lo fp16 pair) at [slot 0][c][15] and [slot 1][c][15] -- no accumulator
-    // init read, no global load in the epilogue:  out = relu(acc * scale).
-
-    // Strip assignment, XCD-aware: workgroups b, b+8, b+16, ... share an XCD (and its 4 MB L2), so each
-    // XCD gets ONE contiguous range of strips (= whole clips) and its workgroups walk it together --
-    // the 5 frames of a position are then fetched into that L2 once instead of into all eight.
-    // local tile t of this workgroup -> strip s_lo + (t/22)*GX, row tile t%22
-    // All of this index math is 32-bit and incremental: the first version decoded every tile id with 64-bit
-    // divisions (t/22, strip/5, nf/P) in both issue() and pool() -- ~1.2 us of VALU per tile on the loader waves,
-    // which made THEM the critical path.
-    const int G32 = (int)G;
-    const int xcd = blockIdx.x & 7, xidx = blockIdx.x >> 3;
-    const int GX = (G32 + 7 - xcd) >> 3;                                 // workgroups on this XCD
-    const int per = (a.nstrips + 7) >> 3;
-    const int r_lo = xcd * per, r_hi = (r_lo + per < a.nstrips) ? r_lo + per : a.nstrips;
-    const int s_lo = r_lo + xidx;
-    // Tiles that are skipped OUTRIGHT (zmask, produced by conv1_zero_scan_kernel from the frames): a tile whose 16 input rows are
-    // zero in all 5 frames computes relu(bias) everywhere; if the tile above is such a tile too (or does not exist), both of
-    // its pooled rows and its carry are that constant whatever is below, so the tile needs no loads, no barrier slot and no
-    // MFMA -- its pooled rows are filled with the constant when the pool waves enter the strip, and the tile below takes the
-    // constant as its carry (pool(), carry_const).  A zero tile BELOW a non-zero tile still runs (2 bias slots, see
-    // cvt_write): its upper pooled row mixes with real data.
-    // The walk below visits the remaining tiles of this workgroup's strips in order; all of it is wave-uniform.
-    struct Walk {
-        int strip, rt;
-        int k;              // strip = s_lo + k * GX: index into the workgroup's skip table in LDS
-        unsigned skip;      // bit rt: tile rt of `strip` is skipped
-        unsigned z;         // bit rt: input band rt is zero in all five frames of the strip's position (the pre-scan's knowledge)
-        bool done;
-    };
-    // strip -> (position nf, column tile j, clip b, padded-clip position p)
-    auto decode = [&](int strip, int& nf, int& j, int& b, int& pp) {
-        nf = (int)((unsigned)strip / 5u);
-        j = strip - nf * 5;
-        b = (int)((float)nf * a.invP);               // nf < 2^24 (checked by the launcher): off by at most one
-        pp = nf - b * a.P;
-        if (pp < 0) { --b; pp += a.P; }
-        else if (pp >= a.P) { ++b; pp -= a.P; }
-    };
-    // The skip masks of this workgroup's strips sit in LDS (filled below, before the roles split): a global load inside the
-    // walks would put an s_waitcnt vmcnt(0) -- hipcc cannot count across the walks' loops -- behind every batch of frame loads.
-    const unsigned* skip_tab = reinterpret_cast<const unsigned*>(smem + OFF_SKIP);
-    const bool use_skip = a.zmask != nullptr;
-    // the table holds the positions' zero-band masks z; a tile is skipped when its band and the band above are zero
-    auto strip_zero = [&](int k) -> unsigned {
-        return use_skip ? (unsigned)__builtin_amdgcn_readfirstlane((int)skip_tab[k]) : 0u;
-    };
-    auto skip_of = [](unsigned z) -> unsigned { return z & ((z << 1) | 1u); };
-    // on_strip(strip, skip) is called once for every strip the walk enters (the pool walk fills the skipped tiles there)
-    auto walk_next = [&](Walk& q, auto&& on_strip) {
-        if (q.done) return;
-        while (true) {
-            if (++q.rt == ROW_TILES) {
-                q.rt = 0;
-                q.strip += GX;
-                ++q.k;
-                if (q.strip >= r_hi) { q.done = true; return; }
-                q.z = strip_zero(q.k);
-                q.skip = skip_of(q.z);
-                on_strip(q.strip, q.skip);
-            }
-            if (!((q.skip >> q.rt) & 1u)) return;
-        }
-    };
-    auto walk_first = [&](auto&& on_strip) -> Walk {
-        Walk q = {s_lo, -1, 0, 0u, 0u, !(s_lo < r_hi && GX > 0)};
-        if (q.done) return q;
-        q.z = strip_zero(0);
-        q.skip = skip_of(q.z);
-        on_strip(q.strip, q.skip);
-        walk_next(q, on_strip);
-        return q;
-    };
-
-    if (!(s_lo < r_hi && GX > 0)) return;      // a workgroup without a strip (launches of fewer strips than CUs): nothing to do, for either role
-    if (use_skip) {
+    const Strips S = conv1_strips(a, smem);
+    if (!S.any()) return;      // a workgroup without a strip (launches of fewer strips than CUs): nothing to do, for either role
+    if (S.use_skip) {
         unsigned* tab = reinterpret_cast<unsigned*>(smem + OFF_SKIP);
         for (int k = tid; k < MAX_WG_STRIPS; k += 512) {
-            const int strip = s_lo + k * GX;
-            tab[k] = strip < r_hi ? a.zmask[(unsigned)strip / 5u] : 0u;
+            const int strip = S.s_lo + k * S.GX;
+            int nf, j;
+            strip_split(strip, nf, j);
+            tab[k] = strip < S.r_hi ? a.zmask[nf] : 0u;
         }
         __syncthreads();
     }
@@ -223,6 +431,14 @@ __global__ __launch_bounds__(512, 2) void conv1_direct_kernel(Conv1Args a) {
         uint32_t fb0_lo = (uint32_t)(uintptr_t)a.src, fb0_hi = (uint32_t)((uintptr_t)a.src >> 32);   // frame clamp(p - pad) of the issue walk's strip
         uint32_t fdelta[5] = {0, 0, 0, 0, 0};       // byte distance of frame dt from it
         uint32_t ioff[2] = {0, 0};                  // per lane: ((row_u) * IW + px_u) * 3 for the strip's column tile
+        // strip -> (position nf, column tile j, clip b, padded-clip position p)
+        auto decode = [&](int strip, int& nf, int& j, int& b, int& pp) {
+            strip_split(strip, nf, j);
+            b = (int)((float)nf * a.invP);               // nf < 2^24 (checked by the launcher): off by at most one
+            pp = nf - b * a.P;
+            if (pp < 0) { --b; pp += a.P; }
+            else if (pp >= a.P) { ++b; pp -= a.P; }
+        };
         auto strip_setup = [&](int strip) {
             int nf, j, b, p;
             decode(strip, nf, j, b, p);
@@ -297,7 +513,7 @@ __global__ __launch_bounds__(512, 2) void conv1_direct_kernel(Conv1Args a) {
         // instructions + a ballot per tile on the role that sets the tile time.
         auto cvt_write = [&](const C1Regs& R, char* buf, int slot, bool known_zero) {
             bool any;
-            if (use_skip) {
+            if (S.use_skip) {
                 any = !known_zero;
             } else {
                 uint32_t nz = 0;
@@ -345,7 +561,7 @@ __global__ __launch_bounds__(512, 2) void conv1_direct_kernel(Conv1Args a) {
         f16* const dump = a.dump + ((long)blockIdx.x * 256 + ltid) * 8;
         // relu(bias) of this thread's 8 channels: what every conv1 output over an all-zero patch is (loaded once: no global
         // load may sit inside the tile loop, see wait_frames)
-        const f16x8 cz = use_skip ? *reinterpret_cast<const f16x8*>(a.zconst + pcg * 8) : f16x8{0, 0, 0, 0, 0, 0, 0, 0};
+        const f16x8 cz = S.use_skip ? *reinterpret_cast<const f16x8*>(a.zconst + pcg * 8) : f16x8{0, 0, 0, 0, 0, 0, 0, 0};
         const int prow = __builtin_amdgcn_readfirstlane(ltid >> 7);               // wave-uniform: waves 4,5 / 6,7
         const int ccol = ltid & 31, ccg = ltid >> 5;                              // part C: 8 x 32 threads
         // fastz: tile t AND the carry above it come from all-zero input tiles, so every conv value involved is the same
@@ -354,8 +570,8 @@ __global__ __launch_bounds__(512, 2) void conv1_direct_kernel(Conv1Args a) {
         const int pthr = (prow * PW + ppw) * 64 + pcg * 8;
         // carry_const: the tile above was skipped outright -- nobody wrote its carry, which is the constant cz in every column
         auto pool = [&](int strip, int rt, int t, bool fastz, bool carry_const) {
-            const int nf = (int)((unsigned)strip / 5u);
-            const int j = strip - nf * 5;
+            int nf, j;
+            strip_split(strip, nf, j);
             const char* cbuf = smem + OFF_CONV + (t & 1) * CONV_BYTES;
             const char* cin = smem + OFF_CARRY + ((rt & 1) ^ 1) * CARRY_BYTES;
             char* cout = smem + OFF_CARRY + (rt & 1) * CARRY_BYTES;
@@ -410,8 +626,8 @@ __global__ __launch_bounds__(512, 2) void conv1_direct_kernel(Conv1Args a) {
             if (!skip) return;
             // first pooled row the fill must write: conv2 of THIS position reads pooled rows >= 2 s2 only (conv1_s2_of_mask)
             const int fill_lo = a.fill_partial ? 2 * conv1_s2_of_mask(skip) : 0;
-            const int nf = (int)((unsigned)strip / 5u);
-            const int j = strip - nf * 5;
+            int nf, j;
+            strip_split(strip, nf, j);
             const int pw = 16 * j + ppw;
             for (unsigned m = skip; m; m &= m - 1) {
                 const int rt = __builtin_ctz(m);
@@ -436,7 +652,7 @@ __global__ __launch_bounds__(512, 2) void conv1_direct_kernel(Conv1Args a) {
             strip_setup(strip);
             fill_skipped(strip, skip);
         };
-        Walk qi = walk_first(on_strip);
+        Walk qi = walk_first(S, on_strip);
         auto hist = [](const Walk& q) { return Hist{q.strip, q.rt, q.skip, q.rt >= 0 && ((q.z >> q.rt) & 1u) != 0, q.done}; };
         const Hist none = {0, 0, 0u, false, true};
         Hist hA = none, hB = none, hC = none, hD = none;
@@ -451,7 +667,7 @@ __global__ __launch_bounds__(512, 2) void conv1_direct_kernel(Conv1Args a) {
             issue(last_rt, R);
             // the strip state (fb0, fdelta, ioff) must stay that of the LAST tile once the walk is done: walk_next() only calls
             // on_strip() for a strip that exists
-            walk_next(qi, on_strip);
+            walk_next(S, qi, on_strip);
         };
         if (ltid == 0) { live[0] = qi.done ? 0 : 1; live[1] = 0; }
         const bool any_tile = !qi.done;
@@ -467,12 +683,10 @@ __global__ __launch_bounds__(512, 2) void conv1_direct_kernel(Conv1Args a) {
         //   (2) reload the same registers with tile t+3,
         //   (3) pool tile t-1 (its stores go last).
         // Two register sets, so the loop is unrolled by two (a runtime-selected set would be a phi again).
+        // The body is written out once per set on purpose: as ONE function of C1Regs& called for RB and then RA (a lambda here, or
+        // a member of a loader struct) both instances go from 4 to 16-18 SGPR spill slots (profiles/conv1_split_isa.md).
         // zero status (flags, see cvt_write) of the tiles t-1 and t-2: final once the barrier of their iteration is passed
         bool z1 = false, z2 = false;
-        auto tile_is_zero = [&](int tt) -> bool {
-            const int4 fl = *reinterpret_cast<const int4*>(smem + OFF_INIT + (tt & 1) * 16);
-            return __builtin_amdgcn_readfirstlane(fl.x | fl.y | fl.z | fl.w) == 0;
-        };
         // fastz for the tile hD: it is a zero tile and so is the tile above it (the previous tile of the walk, or a skipped
         // one, or there is none) -- every conv value in its pooling windows is then the per-channel constant
         auto pool_step = [&](int tprev) {
@@ -483,7 +697,7 @@ __global__ __launch_bounds__(512, 2) void conv1_direct_kernel(Conv1Args a) {
         int t = 0;
         while (!hC.done) {                      // hC = tile t
             __syncthreads();
-            const bool zc0 = tile_is_zero(t);          // before cvt_write reuses the other slot; this slot is rewritten at t+1
+            const bool zc0 = tile_is_zero(smem, t);          // before cvt_write reuses the other slot; this slot is rewritten at t+1
             if (ltid == 0) live[(t + 1) & 1] = hB.done ? 0 : 1;
             wait_frames(RB, t >= 2 ? 2 : 1);
             if (!hB.done) cvt_write(RB, smem + ((t + 1) & 1) * TILE_BYTES, (t + 1) & 1, hB.zero);
@@ -493,7 +707,7 @@ __global__ __launch_bounds__(512, 2) void conv1_direct_kernel(Conv1Args a) {
             ++t;
             if (hC.done) break;
             __syncthreads();
-            const bool zc1 = tile_is_zero(t);
+            const bool zc1 = tile_is_zero(smem, t);
             if (ltid == 0) live[(t + 1) & 1] = hB.done ? 0 : 1;
             wait_frames(RA, t >= 2 ? 2 : 1);
             if (!hB.done) cvt_write(RA, smem + ((t + 1) & 1) * TILE_BYTES, (t + 1) & 1, hB.zero);
@@ -511,203 +725,8 @@ __global__ __launch_bounds__(512, 2) void conv1_direct_kernel(Conv1Args a) {
         return;
     }
 
-    // =========================== MFMA waves ===========================
-    const int chalf = wave & 1, mb0 = (wave >> 1) & 1;
-    if constexpr (M16) {
-        // ---- v_mfma_f32_16x16x32_f16: a wave's block (conv row mb, 32 columns, 32 channels) = 2 channel blocks (ob) x 2 column
-        // blocks (cb) of 16x16, K = 25 steps of 32 = two pixel slots each.  Lane (n = lane & 15, kq = lane >> 4) holds the k-slice
-        //   slot = kq & 1 ? sB(t) : sA(t),   halves 8 * (kq >> 1) .. + 7
-        // of step t, for the weights (A operand, registers) and for the patch (B operand, one ds_read_b128 from the tile image).
-        // Pairing: (kh, kw) with (kh + 1, kw) for kh = 0, 2, 4 (21 steps, the B slot is one image row below: + ROW_PITCH), then in the
-        // last kernel row kw (1,2), (4,5) (+ 32 B), (0,6) (+ 224 B) and kw = 3 alone (the B slot's weights are zero).  One base
-        // register per distance and compile-time immediates for all the rest, as in the 32x32x16 path.
-        // Bank conflicts: a ds_read_b128 group is {kq = 0 lanes n = 0-3, 12-15} + {kq = 1 lanes n = 4-11} (and its three images), so
-        // the two slots of a step sit side by side in one group: the slot distance moves the 16-B bank quad by an EVEN amount in
-        // all pairs (3744 / 16 = 234, 32 / 16 = 2, 224 / 16 = 14), and lane n's conv column is permuted so that n = 4..11 take the
-        // even columns of the 16-column block and the others the odd ones (quad = 7 * column mod 16): conflict-free.
-        const int n16 = lane & 15, kq = lane >> 4;
-        const int sel = kq & 1, half = kq >> 1;
-        const int colp = (n16 >= 4 && n16 < 12) ? 2 * (n16 - 4) : (n16 < 4 ? 2 * n16 + 1 : 2 * (n16 - 8) + 1);
-        auto step_slots = [](int t, int& kha, int& kwa, int& khb, int& kwb) {
-            if (t < 21) { kha = 2 * (t / 7); kwa = t % 7; khb = kha + 1; kwb = kwa; }
-            else if (t == 21) { kha = khb = 6; kwa = 1; kwb = 2; }
-            else if (t == 22) { kha = khb = 6; kwa = 4; kwb = 5; }
-            else if (t == 23) { kha = khb = 6; kwa = 0; kwb = 6; }
-            else { kha = khb = 6; kwa = 3; kwb = 4; }          // t = 24: slot B is padding: zero weights, and its lanes read slot (6,4) -- a
-                                                               // real slot (finite values; the 16-B pads between slots are never written)
-        };
-        f16x8 wreg[25][2];
-#pragma unroll
-        for (int t = 0; t < 25; ++t) {
-            int kha, kwa, khb, kwb;
-            step_slots(t, kha, kwa, khb, kwb);
-            const int sl = sel ? khb * 7 + kwb : kha * 7 + kwa;
-#pragma unroll
-            for (int ob = 0; ob < 2; ++ob) {
-                wreg[t][ob] = *reinterpret_cast<const f16x8*>(a.Wd + ((long)(sl * 64 + chalf * 32 + ob * 16 + n16) * 16 + 8 * half));
-                if (t == 24 && sel) wreg[t][ob] = f16x8{0, 0, 0, 0, 0, 0, 0, 0};
-            }
-        }
-        // lane part of the patch address: column block cb adds 16 columns = 1792 B, the step its slot-A offset; slot B = + sel * distance
-        const int lb = 112 * colp + 16 * half;
-        const int lb_row = lb + sel * ROW_PITCH, lb_32 = lb + sel * 32, lb_224 = lb + sel * 224;
-        constexpr int DEPTH = 4;                             // patch fragments in flight per wave (2 steps x 2 column blocks; 6 spill)
-#ifdef JG_CLOCK_STAMPS
-        const unsigned long long ck0 = __builtin_amdgcn_s_memtime(), rt0 = __builtin_amdgcn_s_memrealtime();
-#endif
-        for (int t = 0;; ++t) {
-            __syncthreads();
-            if (__builtin_amdgcn_readfirstlane(*reinterpret_cast<const int*>(smem + OFF_LIVE + (t & 1) * 4)) == 0) break;
-            const char* cur = smem + (t & 1) * TILE_BYTES + 3 * mb0 * ROW_PITCH;
-            char* cbuf = smem + OFF_CONV + (t & 1) * CONV_BYTES;
-            const char* p_row = cur + lb_row;
-            const char* p_32 = cur + lb_32;
-            const char* p_224 = cur + lb_224;
-            // fragment gi of the tile's stream: (block q, step st, column block cb)
-            auto frag = [&](int gi) -> f16x8 {
-                const int q = gi / 50, st = (gi - q * 50) >> 1, cb = gi & 1;
-                int kha, kwa, khb, kwb;
-                step_slots(st, kha, kwa, khb, kwb);
-                const int off = (6 * q + kha) * ROW_PITCH + 32 * kwa + 16 * (kwa / 3) + 1792 * cb;
-                const char* pb = st < 21 ? p_row : (st == 23 ? p_224 : p_32);
-                return *reinterpret_cast<const f16x8*>(pb + off);
-            };
-            // D of a 16x16 block: lane (n, kq) holds channels 4 kq .. 4 kq + 3 of the channel block for column n.
-            // conv buffer [row mb][channel group][col][16 B]: group = chalf*4 + ob*2 + (kq >> 1), the lane's 4 channels = 8 B at + 8 (kq & 1)
-            auto epilogue = [&](const f32x4 (&acc)[2][2], int mb) {
-#pragma unroll
-                for (int ob = 0; ob < 2; ++ob)
-#pragma unroll
-                    for (int cb = 0; cb < 2; ++cb) {
-                        const f32x4 v = acc[ob][cb] * a.scale;
-                        const f16x4 hv = {(f16)fmaxf(v.x, 0.f), (f16)fmaxf(v.y, 0.f), (f16)fmaxf(v.z, 0.f), (f16)fmaxf(v.w, 0.f)};
-                        *reinterpret_cast<f16x4*>(cbuf + ((mb * 8 + chalf * 4 + ob * 2 + (kq >> 1)) * 32 + cb * 16 + colp) * 16 + 8 * (kq & 1)) = hv;
-                    }
-            };
-            const int4 fl = *reinterpret_cast<const int4*>(smem + OFF_INIT + (t & 1) * 16);
-            const bool zero_tile = __builtin_amdgcn_readfirstlane(fl.x | fl.y | fl.z | fl.w) == 0;
-            if (zero_tile) {
-                // all-zero tile (see cvt_write): only slots (0,0) and (0,1) carry anything -- the bias pair on the pad lane: steps 0 and 1
-#pragma unroll
-                for (int q = 0; q < 2; ++q) {
-                    f32x4 acc[2][2];
-#pragma unroll
-                    for (int ob = 0; ob < 2; ++ob)
-#pragma unroll
-                        for (int cb = 0; cb < 2; ++cb) acc[ob][cb] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                    for (int st = 0; st < 2; ++st)
-#pragma unroll
-                        for (int cb = 0; cb < 2; ++cb) {
-                            const f16x8 f = frag(q * 50 + st * 2 + cb);
-#pragma unroll
-                            for (int ob = 0; ob < 2; ++ob) acc[ob][cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wreg[st][ob], f, acc[ob][cb], 0, 0, 0);
-                        }
-                    epilogue(acc, mb0 + 2 * q);
-                }
-                continue;
-            }
-            f16x8 fr[DEPTH];
-#pragma unroll
-            for (int gi = 0; gi < DEPTH; ++gi) fr[gi] = frag(gi);
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                f32x4 acc[2][2];
-#pragma unroll
-                for (int ob = 0; ob < 2; ++ob)
-#pragma unroll
-                    for (int cb = 0; cb < 2; ++cb) acc[ob][cb] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int st = 0; st < 25; ++st)
-#pragma unroll
-                    for (int cb = 0; cb < 2; ++cb) {
-                        const int gi = q * 50 + st * 2 + cb;
-                        acc[0][cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wreg[st][0], fr[gi % DEPTH], acc[0][cb], 0, 0, 0);
-                        acc[1][cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wreg[st][1], fr[gi % DEPTH], acc[1][cb], 0, 0, 0);
-                        if (gi + DEPTH < 100) fr[gi % DEPTH] = frag(gi + DEPTH);
-                        __builtin_amdgcn_sched_barrier(0);       // pin the order (see the 32x32x16 path)
-                    }
-                epilogue(acc, mb0 + 2 * q);
-            }
-        }
-#ifdef JG_CLOCK_STAMPS
-        if (wave == 0 && lane == 0 && blockIdx.x < 1024) {
-            jg_clock_stamps_conv1[2 * blockIdx.x] = __builtin_amdgcn_s_memtime() - ck0;
-            jg_clock_stamps_conv1[2 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime() - rt0;
-        }
-#endif
-        return;
-    }
-    const int r = lane & 31, h = lane >> 5;
-    f16x8 wreg[49];
-#pragma unroll
-    for (int s = 0; s < 49; ++s)
-        wreg[s] = *reinterpret_cast<const f16x8*>(a.Wd + ((long)(s * 64 + chalf * 32 + r) * 16 + 8 * h));
-    // patch-fragment address of lane (r,h) for slot (kh,kw): pixel x = 3r+kw ->
-    //   (3*mb+kh)*ROW_PITCH + 32*x + 16*(x/3) + 16*h = [112*r + 16*h] + [kh*ROW_PITCH + 32*kw + 16*(kw/3)]
-    const int lbase = 112 * r + 16 * h;
-    constexpr int DEPTH = 6;                             // patch fragments in flight per wave
-    for (int t = 0;; ++t) {
-        __syncthreads();
-        // live[t & 1]: written by the loaders before this barrier; 0 = the workgroup's tiles are done (this was the final barrier)
-        if (__builtin_amdgcn_readfirstlane(*reinterpret_cast<const int*>(smem + OFF_LIVE + (t & 1) * 4)) == 0) break;
-        const char* cur = smem + (t & 1) * TILE_BYTES;
-        char* cbuf = smem + OFF_CONV + (t & 1) * CONV_BYTES;
-        // The two blocks of a tile form ONE stream of 98 (block, slot) steps with DEPTH fragments in
-        // flight, so block 1's first fragments are already loading while block 0's epilogue runs.
-        const char* base = cur + 3 * mb0 * ROW_PITCH + lbase;
-        auto frag = [&](int gi) -> f16x8 {
-            const int q = gi / 49, s = gi - q * 49;
-            const int kh = s / 7, kw = s - kh * 7;
-            return *reinterpret_cast<const f16x8*>(base + (6 * q + kh) * ROW_PITCH + 32 * kw + 16 * (kw / 3));
-        };
-        // D[i][jj]: jj = lane&31 -> conv column r, i = (x&3) + 8*(x>>2) + 4*h -> channel 32*chalf + 8g + 4h + (x&3).
-        // conv buffer [row mb][channel group chalf*4+g][col r][16 B], this lane's 4 channels = 8 B at +8h
-        auto epilogue = [&](const f32x16& acc, int mb) {
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                f32x4 v = {acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]};
-                v *= a.scale;
-                f16x4 hv = {(f16)fmaxf(v.x, 0.f), (f16)fmaxf(v.y, 0.f), (f16)fmaxf(v.z, 0.f), (f16)fmaxf(v.w, 0.f)};
-                *reinterpret_cast<f16x4*>(cbuf + ((mb * 8 + chalf * 4 + g) * 32 + r) * 16 + 8 * h) = hv;
-            }
-        };
-        const int4 fl = *reinterpret_cast<const int4*>(smem + OFF_INIT + (t & 1) * 16);
-        if (__builtin_amdgcn_readfirstlane(fl.x | fl.y | fl.z | fl.w) == 0) {
-            // all-zero tile (see cvt_write): only slots 0 and 1 carry anything -- the bias pair on the pad lane
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                f32x16 acc;
-#pragma unroll
-                for (int x = 0; x < 16; ++x) acc[x] = 0.f;
-                const f16x8 f0 = frag(q * 49), f1 = frag(q * 49 + 1);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wreg[0], f0, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wreg[1], f1, acc, 0, 0, 0);
-                epilogue(acc, mb0 + 2 * q);
-            }
-            continue;
-        }
-        f16x8 fr[DEPTH];
-#pragma unroll
-        for (int gi = 0; gi < DEPTH; ++gi) fr[gi] = frag(gi);
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            const int mb = mb0 + 2 * q;
-            f32x16 acc;
-#pragma unroll
-            for (int x = 0; x < 16; ++x) acc[x] = 0.f;
-#pragma unroll
-            for (int s = 0; s < 49; ++s) {
-                const int gi = q * 49 + s;
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wreg[s], fr[gi % DEPTH], acc, 0, 0, 0);
-                if (gi + DEPTH < 98) fr[gi % DEPTH] = frag(gi + DEPTH);
-                // pin the order: without this hipcc sinks every ds_read next to its MFMA (one fragment
-                // register, lgkmcnt(0) per MFMA) and the LDS latency is exposed 49 times per block
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            epilogue(acc, mb);
-        }
-    }
+    if constexpr (M16) conv1_mfma_role<Mfma16>(a.Wd, a.scale, smem, lane, wave);
+    else conv1_mfma_role<Mfma32>(a.Wd, a.scale, smem, lane, wave);
 }
 
 // out[nf][ph][16j+15][:] = max(out[...], edge[nf][ph][j][:])  for j = 0..3 (pooled columns 15,31,47,63)
@@ -799,7 +818,7 @@ __global__ void conv1_skip_mask_kernel(const unsigned* __restrict__ fz, int ncli
             f = f < 0 ? 0 : (f > T - 1 ? T - 1 : f);
             z &= fz[b * T + f];
         }
-        const unsigned sk = z & ((z << 1) | 1u);
+        const unsigned sk = skip_of(z);
         skip[nf] = z;                                    // the kernel derives sk itself and uses z for the tiles that still run
         rs = conv1_s2_of_mask(sk);
         s2[nf] = rs;
@@ -812,88 +831,12 @@ __global__ void conv1_skip_mask_kernel(const unsigned* __restrict__ fz, int ncli
     if ((threadIdx.x & 63) == 0 && rs != 0x7fffffff) atomicMin(rowskip_min, rs);
 }
 
-// ---- compaction maps of the conv layers behind conv1 (common.h: ConvGeom::rowmap, ConvRowMap) ----------------------------------
-// Image (position) img computes rows >= s = conv_skip_decode(s2[img], op) of a layer's OH x OW output.  Step 1, one workgroup:
-// exclusive prefix of the images' computed pixels per layer (base[img], *total).  Step 2, one workgroup per image: its computed
-// pixels (one contiguous run of full indices per layer) go to their compacted place, | s2 << 24.
-struct RowMapArgs {
-    const int* s2;
-    int NF, nl;
-    ConvRowMap L[4];
-};
-__global__ __launch_bounds__(1024) void conv_rowmap_scan_kernel(RowMapArgs a) {
-    __shared__ int part[4][1024];
-    const int tid = threadIdx.x;
-    const int per = (a.NF + 1023) / 1024;                  // consecutive images per thread
-    const int i0 = tid * per, i1 = i0 + per < a.NF ? i0 + per : a.NF;
-    int sum[4] = {0, 0, 0, 0};
-    for (int i = i0; i < i1; ++i) {
-        const int w = a.s2[i];
-#pragma unroll
-        for (int l = 0; l < 4; ++l) sum[l] += (a.L[l].OH - conv_skip_decode(w, a.L[l].op)) * a.L[l].OW;
-    }
-#pragma unroll
-    for (int l = 0; l < 4; ++l) part[l][tid] = sum[l];
-    __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {                   // Hillis-Steele inclusive scan, the four layers side by side
-        int v[4];
-#pragma unroll
-        for (int l = 0; l < 4; ++l) v[l] = tid >= d ? part[l][tid - d] : 0;
-        __syncthreads();
-#pragma unroll
-        for (int l = 0; l < 4; ++l) part[l][tid] += v[l];
-        __syncthreads();
-    }
-    int run[4];
-#pragma unroll
-    for (int l = 0; l < 4; ++l) run[l] = part[l][tid] - sum[l];
-    for (int i = i0; i < i1; ++i) {
-        const int w = a.s2[i];
-#pragma unroll
-        for (int l = 0; l < 4; ++l) {
-            if (l < a.nl) a.L[l].base[i] = run[l];
-            run[l] += (a.L[l].OH - conv_skip_decode(w, a.L[l].op)) * a.L[l].OW;
-        }
-    }
-    if (tid == 1023) {
-#pragma unroll
-        for (int l = 0; l < 4; ++l)
-            if (l < a.nl) { a.L[l].base[a.NF] = part[l][1023]; *a.L[l].total = part[l][1023]; }
-    }
-}
-// one workgroup per image: its computed pixels of every layer, in order
-__global__ __launch_bounds__(256) void conv_rowmap_fill_kernel(RowMapArgs a) {
-    const int img = blockIdx.x;
-    const int w = a.s2[img];
-    for (int l = 0; l < a.nl; ++l) {
-        const ConvRowMap& R = a.L[l];
-        const int s = conv_skip_decode(w, R.op);
-        const int n = (R.OH - s) * R.OW;                   // computed pixels of this image: full rows s*OW .. OH*OW - 1
-        const int first = img * R.OH * R.OW + s * R.OW;
-        int* dst = R.map + R.base[img];
-        for (int i = threadIdx.x; i < n; i += 256) dst[i] = (first + i) | (w << 24);
-    }
-}
-
 // workspace words: header of CONV1_ZHDR_WORDS (zconst: 64 halves = 32 words; word CONV1_ROWSKIP_WORD: constant leading rows of
 // conv2's output) + nclip*T (frame masks) + nclip*(T+2*pad-4) (position skip masks)
 // + nclip*(T+2*pad-4) (per-position counts s2); sized for pad <= 12
 size_t conv1_zmask_elems(int nclip, int T) { return (size_t)CONV1_ZHDR_WORDS + (size_t)nclip * T + 2 * (size_t)nclip * (T + 20); }
 const int* conv1_s2_counts(const unsigned* zscratch, int nclip, int T, int pad) {
     return reinterpret_cast<const int*>(zscratch + CONV1_ZHDR_WORDS + (size_t)nclip * T + (size_t)nclip * (T + 2 * pad - 4));
-}
-
-hipError_t launch_conv_rowmaps(const int* s2, int NF, const ConvRowMap* layers, int nlayers, hipStream_t s) {
-    if (NF <= 0 || nlayers <= 0 || nlayers > 4) return hipErrorInvalidValue;
-    RowMapArgs a;
-    a.s2 = s2; a.NF = NF; a.nl = nlayers;
-    for (int l = 0; l < 4; ++l) {
-        a.L[l] = layers[l < nlayers ? l : nlayers - 1];
-        if ((long)NF * a.L[l].OH * a.L[l].OW >= (1L << 24)) return hipErrorInvalidValue;      // 24-bit row index in the map entries
-    }
-    hipLaunchKernelGGL(conv_rowmap_scan_kernel, dim3(1), dim3(1024), 0, s, a);
-    hipLaunchKernelGGL(conv_rowmap_fill_kernel, dim3((unsigned)NF), dim3(256), 0, s, a);
-    return hipGetLastError();
 }
 
 // Zero-band scan + per-position skip masks + the zero-patch constant into `zscratch` (conv1_zmask_elems words).
@@ -947,6 +890,8 @@ hipError_t launch_conv1_direct(const uint8_t* src, int nclip, int T, int pad, co
         if (!fill_all) a.fill_partial = 1;
     }
     if (a.nstrips <= 0) return hipSuccess;
+    // XCD range rule (conv1_strips): XCD x = blockIdx.x & 7 owns strips [x * per, (x + 1) * per) -- under 8 workgroups some ranges have none
+    if (num_cu < 8 && a.nstrips > num_cu) return hipErrorInvalidValue;
     const unsigned grid = (unsigned)(a.nstrips < num_cu ? a.nstrips : num_cu);
     if (o.conv1_mfma16) hipLaunchKernelGGL((conv1_direct_kernel<true>), dim3(grid), dim3(512), LDS_BYTES, s, a);
     else hipLaunchKernelGGL((conv1_direct_kernel<false>), dim3(grid), dim3(512), LDS_BYTES, s, a);

@@ -399,3 +399,79 @@ hipError_t launch_unpack_masked(const uint8_t* packed, const int* row0, const lo
     hipLaunchKernelGGL(unpack_masked_kernel, dim3((unsigned)n_frames, 9), dim3(256), 0, s, packed, row0, offs, dst, packed_bytes);
     return hipGetLastError();
 }
+
+// ---- compaction maps of the conv layers behind conv1 (common.h: ConvGeom::rowmap, ConvRowMap) ----------------------------------
+// Image (position) img computes rows >= s = conv_skip_decode(s2[img], op) of a layer's OH x OW output.  Step 1, one workgroup:
+// exclusive prefix of the images' computed pixels per layer (base[img], *total).  Step 2, one workgroup per image: its computed
+// pixels (one contiguous run of full indices per layer) go to their compacted place, | s2 << 24.
+struct RowMapArgs {
+    const int* s2;
+    int NF, nl;
+    ConvRowMap L[4];
+};
+__global__ __launch_bounds__(1024) void conv_rowmap_scan_kernel(RowMapArgs a) {
+    __shared__ int part[4][1024];
+    const int tid = threadIdx.x;
+    const int per = (a.NF + 1023) / 1024;                  // consecutive images per thread
+    const int i0 = tid * per, i1 = i0 + per < a.NF ? i0 + per : a.NF;
+    int sum[4] = {0, 0, 0, 0};
+    for (int i = i0; i < i1; ++i) {
+        const int w = a.s2[i];
+#pragma unroll
+        for (int l = 0; l < 4; ++l) sum[l] += (a.L[l].OH - conv_skip_decode(w, a.L[l].op)) * a.L[l].OW;
+    }
+#pragma unroll
+    for (int l = 0; l < 4; ++l) part[l][tid] = sum[l];
+    __syncthreads();
+    for (int d = 1; d < 1024; d <<= 1) {                   // Hillis-Steele inclusive scan, the four layers side by side
+        int v[4];
+#pragma unroll
+        for (int l = 0; l < 4; ++l) v[l] = tid >= d ? part[l][tid - d] : 0;
+        __syncthreads();
+#pragma unroll
+        for (int l = 0; l < 4; ++l) part[l][tid] += v[l];
+        __syncthreads();
+    }
+    int run[4];
+#pragma unroll
+    for (int l = 0; l < 4; ++l) run[l] = part[l][tid] - sum[l];
+    for (int i = i0; i < i1; ++i) {
+        const int w = a.s2[i];
+#pragma unroll
+        for (int l = 0; l < 4; ++l) {
+            if (l < a.nl) a.L[l].base[i] = run[l];
+            run[l] += (a.L[l].OH - conv_skip_decode(w, a.L[l].op)) * a.L[l].OW;
+        }
+    }
+    if (tid == 1023) {
+#pragma unroll
+        for (int l = 0; l < 4; ++l)
+            if (l < a.nl) { a.L[l].base[a.NF] = part[l][1023]; *a.L[l].total = part[l][1023]; }
+    }
+}
+// one workgroup per image: its computed pixels of every layer, in order
+__global__ __launch_bounds__(256) void conv_rowmap_fill_kernel(RowMapArgs a) {
+    const int img = blockIdx.x;
+    const int w = a.s2[img];
+    for (int l = 0; l < a.nl; ++l) {
+        const ConvRowMap& R = a.L[l];
+        const int s = conv_skip_decode(w, R.op);
+        const int n = (R.OH - s) * R.OW;                   // computed pixels of this image: full rows s*OW .. OH*OW - 1
+        const int first = img * R.OH * R.OW + s * R.OW;
+        int* dst = R.map + R.base[img];
+        for (int i = threadIdx.x; i < n; i += 256) dst[i] = (first + i) | (w << 24);
+    }
+}
+
+hipError_t launch_conv_rowmaps(const int* s2, int NF, const ConvRowMap* layers, int nlayers, hipStream_t s) {
+    if (NF <= 0 || nlayers <= 0 || nlayers > 4) return hipErrorInvalidValue;
+    RowMapArgs a;
+    a.s2 = s2; a.NF = NF; a.nl = nlayers;
+    for (int l = 0; l < 4; ++l) {
+        a.L[l] = layers[l < nlayers ? l : nlayers - 1];
+        if ((long)NF * a.L[l].OH * a.L[l].OW >= (1L << 24)) return hipErrorInvalidValue;      // 24-bit row index in the map entries
+    }
+    hipLaunchKernelGGL(conv_rowmap_scan_kernel, dim3(1), dim3(1024), 0, s, a);
+    hipLaunchKernelGGL(conv_rowmap_fill_kernel, dim3((unsigned)NF), dim3(256), 0, s, a);
+    return hipGetLastError();
+}

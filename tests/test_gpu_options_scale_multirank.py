@@ -150,11 +150,11 @@ def test_precision_w2_all(option_case):
     assert err < TOL
 
 
-def test_conv1_zero_band_skip_is_bit_identical(engine, models):
-    """conv1 skips input tiles that conv1_zero_scan_kernel finds all-zero (bands of 16 rows, all 5 frames of a position).
-    Skipping must never change a bit.  Patterns: the reference's face mask (zero prefix), no zero row at all, zero bands in
-    the middle and at the bottom, whole black frames (fully skipped strips), black clips next to normal ones, and a single
-    non-zero byte hidden in an otherwise black band (defeats the 16-byte probe, caught by the full row check)."""
+@pytest.fixture(scope="module")
+def zero_band_frames():
+    """Six clips, T = 9: the reference's face mask (zero prefix), no zero row at all, zero bands in the middle and at the bottom, whole
+    black frames (fully skipped strips), black clips next to normal ones, and a single non-zero byte hidden in an otherwise black band
+    (defeats the 16-byte probe, caught by the full row check)."""
     rng = np.random.default_rng(77)
     T = 9
     clips = rng.integers(0, 256, (6, T, 270, 480, 3), dtype=np.uint8)
@@ -167,22 +167,85 @@ def test_conv1_zero_band_skip_is_bit_identical(engine, models):
     clips[4, 2:5] = 0                                       # black frames inside a masked clip
     clips[5, :, :110] = 0
     clips[5, 6, 50, 479, 2] = 255                           # last byte of a row inside the mask
-    frames = torch.from_numpy(clips).cuda()
-    engine.set_option("conv1_zero_skip", 0)
+    return torch.from_numpy(clips).cuda()
+
+
+@pytest.fixture(scope="module")
+def zero_band_implicit_gemm(engine, models, zero_band_frames):
+    """conv1 + pool of zero_band_frames by the stack + implicit-GEMM formulation (conv1_direct = 0: independent kernels)"""
+    engine.set_option("conv1_direct", 0)
     try:
-        ref = engine.debug_conv1_pool(frames, 4).clone()
+        return engine.debug_conv1_pool(zero_band_frames, 4).clone()
     finally:
-        engine.set_option("conv1_zero_skip", 1)
-    out = engine.debug_conv1_pool(frames, 4)
+        engine.set_option("conv1_direct", 1)
+
+
+@pytest.mark.parametrize("mfma16", [1, 0])
+def test_conv1_zero_band_skip_is_bit_identical(engine, models, zero_band_frames, zero_band_implicit_gemm, mfma16):
+    """conv1 skips input tiles that conv1_zero_scan_kernel finds all-zero (bands of 16 rows, all 5 frames of a position).
+    Skipping must never change a bit, in either form of the MFMA waves (conv1_mfma16 = 1: 16x16x32, 0: 32x32x16); patterns:
+    zero_band_frames."""
+    frames = zero_band_frames
+    engine.set_option("conv1_mfma16", mfma16)
+    try:
+        engine.set_option("conv1_zero_skip", 0)
+        try:
+            ref = engine.debug_conv1_pool(frames, 4).clone()
+        finally:
+            engine.set_option("conv1_zero_skip", 1)
+        out = engine.debug_conv1_pool(frames, 4).clone()
+    finally:
+        engine.set_option("conv1_mfma16", 1)
     assert torch.isfinite(out.float()).all()
     assert torch.equal(out, ref)
     # and against the stack + implicit-GEMM formulation (independent kernels): same fp16 operands, fp32 sums in another order
-    engine.set_option("conv1_direct", 0)
+    assert rel(out.float(), zero_band_implicit_gemm.float()) < 3e-4
+
+
+def test_conv1_zero_detection_without_the_skip_table(engine, models):
+    """The per-workgroup table of skip masks holds 640 strips.  A launch whose workgroups get more (here 41 clips, T = 5, pad 12:
+    1025 positions, 5125 strips on num_cu = 8 workgroups, 641 + 8 > 640; 40 clips still fit) runs with zero-skip on but without the
+    table: no tile is skipped outright, and the loader waves find the zero tiles by OR-ing the bytes they loaded.  That must not
+    change a bit against the same launch with conv1_zero_skip = 0.  Clips: face-mask prefixes, one black clip, one black band
+    with a single non-zero byte."""
+    rng = np.random.default_rng(4100)
+    clips = rng.integers(0, 256, (41, 5, 270, 480, 3), dtype=np.uint8)
+    clips[::3, :, :110] = 0                                 # face mask in every third clip
+    clips[7] = 0                                            # black clip
+    clips[11, :, 96:160] = 0                                # bands 8..12 black (band rt = rows 12 rt .. 12 rt + 15) ...
+    clips[11, 2, 115, 301, 0] = 1                           # ... but for one byte of one frame
+    frames = torch.from_numpy(clips).cuda()
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    engine.set_option("num_cu", 8)
     try:
-        alt = engine.debug_conv1_pool(frames, 4)
+        engine.set_option("conv1_zero_skip", 0)
+        try:
+            ref = engine.debug_conv1_pool(frames, 12).clone()
+        finally:
+            engine.set_option("conv1_zero_skip", 1)
+        out = engine.debug_conv1_pool(frames, 12)
+        torch.cuda.synchronize()
     finally:
-        engine.set_option("conv1_direct", 1)
-    assert rel(out.float(), alt.float()) < 3e-4
+        engine.set_option("num_cu", cus)
+    assert torch.isfinite(out).all()
+    assert torch.equal(out, ref)
+
+
+def test_conv1_rejects_a_grid_that_leaves_strips_out(engine, models):
+    """conv1_direct_kernel gives XCD x = blockIdx.x & 7 the x-th eighth of the strips: with fewer than 8 workgroups and more strips
+    than workgroups some eighths would have nobody.  Such a launch (num_cu = 4; 2 clips, T = 5, pad 0: 2 positions, 10 strips) is
+    an error, not a silent partial result."""
+    from jegal_amd._lib import JegalError
+    frames = torch.from_numpy(np.random.default_rng(5).integers(0, 256, (2, 5, 270, 480, 3), dtype=np.uint8)).cuda()
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    engine.set_option("num_cu", 4)
+    try:
+        with pytest.raises(JegalError):
+            engine.debug_conv1_pool(frames, 0)
+    finally:
+        engine.set_option("num_cu", cus)
+    out = engine.debug_conv1_pool(frames, 0)
+    assert out.shape == (2, 43, 78, 64) and torch.isfinite(out).all()
 
 
 def _expected_conv_rows(zero_rows, pad=4):

@@ -16,7 +16,8 @@ import tempfile
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from kernel_resources import LLVM, MAGIC, kernel_resources  # noqa: E402
 
-COUNTED = (("mfma", r"v_mfma"), ("lds_dma", r"global_load_lds"), ("barrier", r"s_barrier\b"), ("gstore", r"global_store"))
+COUNTED = (("mfma", r"v_mfma"), ("lds_dma", r"global_load_lds"), ("barrier", r"s_barrier\b"), ("gstore", r"global_store"),
+           ("global_load", r"global_load_(?!lds)"))
 META = ("vgpr", "sgpr", "spill", "sgpr_spill", "scratch", "lds")
 
 
@@ -49,7 +50,10 @@ def streams(lib, kernels):
             dem = subprocess.run(["c++filt"], input="\n".join(raw), capture_output=True, text=True).stdout.split("\n")
             for name, d in zip(raw, dem):
                 if d.strip() in kernels:
-                    out[d.strip()] = raw[name]
+                    ins = raw[name]
+                    while ins and ins[-1] in ("s_nop 0", "s_code_end"):     # the padding behind the LAST kernel of a code object is not part of it
+                        ins.pop()
+                    out[d.strip()] = ins
     return out
 
 
