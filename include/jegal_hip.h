@@ -260,6 +260,56 @@ int jg_debug_attention(jg_handle* h, const void* qkv, const float* keymask, int 
 int jg_debug_attention_gather(jg_handle* h, const void* qkv_pos, const void* pe_qkv, int Twin, int P, int shift, int B, int S, int H, void* out);
 /* fp32 attention of the audit mode (launch_attention32): as jg_debug_attention with fp32 qkv / out. */
 int jg_debug_attention32(jg_handle* h, const float* qkv, const float* keymask, int B, int S, int H, int dk, float* out);
+/* Check points of the element-wise and reduction launchers (jegal_amd/csrc/elementwise*.hip; tests/test_gpu_elementwise_fp64.py): ONE
+ * production launch each on device buffers the caller owns, scratch included; "16-bit" is fp16 or, on a JG_PREC_BF16 handle, bf16.  Every
+ * entry refuses with JG_ERR_ARG, before anything is enqueued, null pointers, sizes <= 0, a leading dimension below the row, pointers or
+ * strides that break the kernel's 16-byte accesses and `valid` arrays that are not one entry per clip, as well as what the launcher
+ * itself rejects.  valid_host arrays live on the HOST (n_valid entries; NULL with n_valid = 0 where optional) and are staged in the
+ * handle's workspace.  pe_project, broadcast_channels, col_sum and rc_bias are fp16-build kernels: JG_ERR_STATE on a bf16 handle.
+ *   stack_frames: dst [B][T+2pad-4][H][W][16] 16-bit = channels c < 3 of frames clamp(p + dt - pad, 0, T-1), dt < 5, channel 15 = 0;
+ *     src u8 or fp32 with element strides sb / st / sh / sw / sc (>= 0), src_elems = elements the caller's source buffer holds.
+ *   window_gather: x[(b,i,j)] = conv[b][clamp(i + j - shift, 0, P-1)] + pe[j], conv (B,P,D) fp32; row-major x32 (+ x16 unless NULL;
+ *     D % 4 == 0), or tiled != 0: x16 alone as the tiled token plane of whole 128-row tiles (D = 512).
+ *   layernorm: flavour 0 nn.LayerNorm (biased variance, eps 1e-5 inside the root), 1 the annotated form (unbiased std + 1e-6); D 512 or
+ *     768; out32 and / or out16; out32 == in allowed.  layernorm_planes: out32 = nn.LayerNorm(hi + lo), D = 768.
+ *   group_mean: out[g] = mean of rows g L .. g L + L - 1 of in [groups L][D] 16-bit (D % 8 == 0).  cast: n fp32 -> 16-bit, n % 4 == 0.
+ *   audio_conv0: mel (B,Tm,F <= 80) fp32, wh / wl (or NULL) [32][32] 16-bit with k = 5 kh + kw < 25, bias [32] -> out (B,Tm,F,32) 16-bit =
+ *     ReLU(5x5 conv, pad 2, of the mel rounded to 16 bits and read as zero from row valid[b] on) with rows t >= valid[b] zero.
+ *   zero_tail: rows h >= len_b of x [B][H][row_elems] 16-bit zeroed, len_b = max(valid[b], 0) halved (len - 1) / 2 + 1 `halvings` times.
+ *   xlmr_embed: out (B,L,D) = (word[id] + type) + pos[pid]; pid = pad_id + non-pad tokens up to and including t (pads: pad_id), clamped
+ *     below maxpos; id clamped to 0 .. vocab-1; D % 4 == 0.  xlmr_embed_planes: the same values as hi = 16-bit(v), lo = 16-bit(v - hi) and
+ *     part [B L][D / 64][2] = (sum, sum of squares) per 64 columns; D % 256 == 0.
+ *   ln_stats: stats [rows][2] = (mean, 1 / sqrt(var + 1e-5)) from part [rows][P][2] (sums over 64 columns each).
+ *   mask_i32_f32: out = in != 0.  transpose_tokens: (N,L,D) -> (N,D,L) fp32.
+ *   pe_project: out [S][N] fp16 = sum_k (Wh + Wl)[n][k] pe[j][k] + bias[n], Wl / bias optional.  broadcast_channels: out[i] = v[i % C].
+ *   col_sum: out[k] += sum_m A[m][k], or of (A[m][k] - stats[m][0]) stats[m][1]; A [M][lda] fp16, K % 8 == 0; scratch >= 64 K floats.
+ *   rc_bias: out [nclips][N] = bias[n] + sum_k lo[n][k] mean_c[k], mean_c = fp16 mean of a fixed sample of the first clamp(valid[c], 1, rpc)
+ *     rows of clip c (every row below 1024 rows, otherwise rows with (r >> 4) % 8 == 0); A row-major [nclips rpc][lda] or the tiled plane
+ *     (K = 512), a_elems = elements the caller's A holds; K 512 or 2048, N % 32 == 0; scratch >= nclips K floats, and the fp16 means
+ *     [nclips][K] are left at its start. */
+int jg_debug_stack_frames(jg_handle* h, const void* src, int src_is_u8, int64_t sb, int64_t st, int64_t sh, int64_t sw, int64_t sc, int64_t src_elems,
+                          int B, int T, int pad, int H, int W, void* dst);
+int jg_debug_window_gather(jg_handle* h, const float* conv, const float* pe, int B, int P, int Twin, int L, int D, int shift, int tiled, float* x32,
+                           void* x16);
+int jg_debug_layernorm(jg_handle* h, const float* in, const float* w, const float* b, int rows, int D, int flavour, int relu, float* out32, void* out16);
+int jg_debug_layernorm_planes(jg_handle* h, const void* hi, const void* lo, const float* w, const float* b, int rows, int D, float* out32);
+int jg_debug_group_mean(jg_handle* h, const void* in, int groups, int L, int D, void* out);
+int jg_debug_cast(jg_handle* h, const float* in, void* out, int64_t n);
+int jg_debug_audio_conv0(jg_handle* h, const float* mel, int B, int Tm, int F, const void* wh, const void* wl, const float* bias, void* out,
+                         const int32_t* valid_host, int n_valid);
+int jg_debug_zero_tail(jg_handle* h, void* x, const int32_t* valid_host, int n_valid, int halvings, int B, int H, int64_t row_elems);
+int jg_debug_xlmr_embed(jg_handle* h, const int32_t* ids, int B, int L, int D, int pad_id, int vocab, int maxpos, const float* word, const float* pos,
+                        const float* type, float* out);
+int jg_debug_xlmr_embed_planes(jg_handle* h, const int32_t* ids, int B, int L, int D, int pad_id, int vocab, int maxpos, const float* word,
+                               const float* pos, const float* type, void* hi, void* lo, float* part);
+int jg_debug_ln_stats(jg_handle* h, const float* part, int rows, int P, float* stats);
+int jg_debug_mask_i32_f32(jg_handle* h, const int32_t* in, float* out, int64_t n);
+int jg_debug_transpose_tokens(jg_handle* h, const float* in, int N, int L, int D, float* out);
+int jg_debug_pe_project(jg_handle* h, const float* pe, int S, const void* Wh, const void* Wl, const float* bias, int N, int K, void* out);
+int jg_debug_broadcast_channels(jg_handle* h, const void* v, int C, void* out, int64_t pixels);
+int jg_debug_col_sum(jg_handle* h, const void* A, int64_t lda, int M, int K, float* scratch, int64_t scratch_elems, float* out, const float* stats);
+int jg_debug_rc_bias(jg_handle* h, const void* A, int64_t lda, int64_t a_elems, int tiled, int nclips, int rpc, const int32_t* valid_host, int n_valid,
+                     const void* lo, const float* bias, int N, int K, float* scratch, int64_t scratch_elems, float* out);
 /* Name of the kernel instance the last check point launched, with its template arguments (e.g. "gemm_glds_kernel<1,0,4,4,2,0,0,0,0>";
  * empty if it launched nothing).  Host only, no synchronisation. */
 int jg_debug_last_kernel(jg_handle* h, char* buf, int len);

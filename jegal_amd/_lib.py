@@ -74,6 +74,23 @@ _SIGS = {
     "jg_debug_attention": [_P, _P, _P, _I, _I, _I, _I, _P],
     "jg_debug_attention_gather": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "jg_debug_attention32": [_P, _P, _P, _I, _I, _I, _I, _P],
+    "jg_debug_stack_frames": [_P, _P, _I, _L, _L, _L, _L, _L, _L, _I, _I, _I, _I, _I, _P],
+    "jg_debug_window_gather": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P],
+    "jg_debug_layernorm": [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P],
+    "jg_debug_layernorm_planes": [_P, _P, _P, _P, _P, _I, _I, _P],
+    "jg_debug_group_mean": [_P, _P, _I, _I, _I, _P],
+    "jg_debug_cast": [_P, _P, _P, _L],
+    "jg_debug_audio_conv0": [_P, _P, _I, _I, _I, _P, _P, _P, _P, ctypes.POINTER(ctypes.c_int32), _I],
+    "jg_debug_zero_tail": [_P, _P, ctypes.POINTER(ctypes.c_int32), _I, _I, _I, _I, _L],
+    "jg_debug_xlmr_embed": [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P],
+    "jg_debug_xlmr_embed_planes": [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P],
+    "jg_debug_ln_stats": [_P, _P, _I, _I, _P],
+    "jg_debug_mask_i32_f32": [_P, _P, _P, _L],
+    "jg_debug_transpose_tokens": [_P, _P, _I, _I, _I, _P],
+    "jg_debug_pe_project": [_P, _P, _I, _P, _P, _P, _I, _I, _P],
+    "jg_debug_broadcast_channels": [_P, _P, _I, _P, _L],
+    "jg_debug_col_sum": [_P, _P, _L, _I, _I, _P, _L, _P, _P],
+    "jg_debug_rc_bias": [_P, _P, _L, _L, _I, _I, _I, ctypes.POINTER(ctypes.c_int32), _I, _P, _P, _I, _I, _P, _L, _P],
     "jg_debug_last_kernel": [_P, ctypes.c_char_p, _I],
     "jg_debug_conv_rows": [_P, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)],
     "jg_jegal_gestures": [_P, _P, _P, _I, _I, _I, _P],
@@ -434,6 +451,91 @@ class Engine:
     def debug_attention32(self, qkv, keymask, B, S, H, dk, out):
         self._bind_stream()
         self._ck(self.lib.jg_debug_attention32(self.h, _ptr(qkv), _ptr(keymask), B, S, H, dk, _ptr(out)))
+
+    # ---- check points of the element-wise and reduction launchers (include/jegal_hip.h): device tensors by pointer, sizes as given -- the
+    # library validates them and raises JegalError(.code == JG_ERR_ARG) before anything is enqueued; `valid`: a sequence of host ints or None
+    @staticmethod
+    def _valid_arg(valid):
+        if valid is None:
+            return None, 0
+        v = [int(x) for x in valid]
+        return (ctypes.c_int32 * max(len(v), 1))(*v), len(v)
+
+    def debug_stack_frames(self, src, strides, B, T, pad, H, W, dst):
+        """strides = (sb, st, sh, sw, sc) in elements of src (uint8 or float32)."""
+        self._bind_stream()
+        sb, st, sh, sw, sc = (int(x) for x in strides)
+        self._ck(self.lib.jg_debug_stack_frames(self.h, _ptr(src), int(src.dtype == torch.uint8), sb, st, sh, sw, sc, src.numel(), B, T, pad, H, W, _ptr(dst)))
+
+    def debug_window_gather(self, conv, pe, B, P, Twin, L, D, shift, tiled, x32, x16):
+        self._bind_stream()
+        self._ck(self.lib.jg_debug_window_gather(self.h, _ptr(conv), _ptr(pe), B, P, Twin, L, D, shift, int(bool(tiled)), _ptr(x32), _ptr(x16)))
+
+    def debug_layernorm(self, x, w, b, rows, D, flavour, relu, out32=None, out16=None):
+        self._bind_stream()
+        self._ck(self.lib.jg_debug_layernorm(self.h, _ptr(x), _ptr(w), _ptr(b), rows, D, flavour, relu, _ptr(out32), _ptr(out16)))
+
+    def debug_layernorm_planes(self, hi, lo, w, b, rows, D, out32):
+        self._bind_stream()
+        self._ck(self.lib.jg_debug_layernorm_planes(self.h, _ptr(hi), _ptr(lo), _ptr(w), _ptr(b), rows, D, _ptr(out32)))
+
+    def debug_group_mean(self, x, groups, L, D, out):
+        self._bind_stream()
+        self._ck(self.lib.jg_debug_group_mean(self.h, _ptr(x), groups, L, D, _ptr(out)))
+
+    def debug_cast(self, x, out, n):
+        self._bind_stream()
+        self._ck(self.lib.jg_debug_cast(self.h, _ptr(x), _ptr(out), n))
+
+    def debug_audio_conv0(self, mel, B, Tm, F, wh, wl, bias, out, valid=None):
+        self._bind_stream()
+        v, n = self._valid_arg(valid)
+        self._ck(self.lib.jg_debug_audio_conv0(self.h, _ptr(mel), B, Tm, F, _ptr(wh), _ptr(wl), _ptr(bias), _ptr(out), v, n))
+
+    def debug_zero_tail(self, x, valid, halvings, B, H, row_elems):
+        self._bind_stream()
+        v, n = self._valid_arg(valid)
+        self._ck(self.lib.jg_debug_zero_tail(self.h, _ptr(x), v, n, halvings, B, H, row_elems))
+
+    def debug_xlmr_embed(self, ids, B, L, D, pad_id, vocab, maxpos, word, pos, type_, out):
+        self._bind_stream()
+        self._ck(self.lib.jg_debug_xlmr_embed(self.h, _ptr(ids), B, L, D, pad_id, vocab, maxpos, _ptr(word), _ptr(pos), _ptr(type_), _ptr(out)))
+
+    def debug_xlmr_embed_planes(self, ids, B, L, D, pad_id, vocab, maxpos, word, pos, type_, hi, lo, part):
+        self._bind_stream()
+        self._ck(self.lib.jg_debug_xlmr_embed_planes(self.h, _ptr(ids), B, L, D, pad_id, vocab, maxpos, _ptr(word), _ptr(pos), _ptr(type_), _ptr(hi),
+                                                     _ptr(lo), _ptr(part)))
+
+    def debug_ln_stats(self, part, rows, P, stats):
+        self._bind_stream()
+        self._ck(self.lib.jg_debug_ln_stats(self.h, _ptr(part), rows, P, _ptr(stats)))
+
+    def debug_mask_i32_f32(self, x, out, n):
+        self._bind_stream()
+        self._ck(self.lib.jg_debug_mask_i32_f32(self.h, _ptr(x), _ptr(out), n))
+
+    def debug_transpose_tokens(self, x, N, L, D, out):
+        self._bind_stream()
+        self._ck(self.lib.jg_debug_transpose_tokens(self.h, _ptr(x), N, L, D, _ptr(out)))
+
+    def debug_pe_project(self, pe, S, Wh, Wl, bias, N, K, out):
+        self._bind_stream()
+        self._ck(self.lib.jg_debug_pe_project(self.h, _ptr(pe), S, _ptr(Wh), _ptr(Wl), _ptr(bias), N, K, _ptr(out)))
+
+    def debug_broadcast_channels(self, v, C, out, pixels):
+        self._bind_stream()
+        self._ck(self.lib.jg_debug_broadcast_channels(self.h, _ptr(v), C, _ptr(out), pixels))
+
+    def debug_col_sum(self, A, lda, M, K, scratch, out, stats=None):
+        self._bind_stream()
+        self._ck(self.lib.jg_debug_col_sum(self.h, _ptr(A), lda, M, K, _ptr(scratch), scratch.numel(), _ptr(out), _ptr(stats)))
+
+    def debug_rc_bias(self, A, lda, tiled, nclips, rpc, lo, bias, N, K, scratch, out, valid=None):
+        """scratch: float32, at least nclips * K elements; its first nclips * K fp16 values are the clip means afterwards."""
+        self._bind_stream()
+        v, n = self._valid_arg(valid)
+        self._ck(self.lib.jg_debug_rc_bias(self.h, _ptr(A), lda, A.numel(), int(bool(tiled)), nclips, rpc, v, n, _ptr(lo), _ptr(bias), N, K, _ptr(scratch),
+                                           scratch.numel(), _ptr(out)))
 
     def debug_last_kernel(self):
         buf = ctypes.create_string_buffer(128)

@@ -32,6 +32,15 @@ GemmArgs gemm_check_args(const jg_gemm_check* c) {
     a.out_lo = static_cast<f16*>(c->out_lo); a.stat_out = c->stat_out;
     return a;
 }
+bool al(const void* p, unsigned bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
+// a host [n] int32 array as the device array the launchers take, in the handle's workspace (as jg_debug_maxpool does for s2)
+int upload_valid(jg_handle* h, const int32_t* host, int n, int32_t** dev) {
+    h->ws.reset();
+    RET(wsalloc(h, (size_t)n, dev));
+    return upload_i32_async(h, host, (size_t)n, *dev);
+}
+#define FP16_ONLY(h, name) \
+    if ((h)->bf16) JG_FAIL(h, JG_ERR_STATE, name ": an fp16-build kernel (no bf16 handle reaches its launcher)")
 }  // namespace
 
 extern "C" {
@@ -352,6 +361,211 @@ int jg_debug_attention32(jg_handle* h, const float* qkv, const float* keymask, i
     h->kname[0] = 0;
     if (!qkv || !out || B <= 0 || S <= 0 || H <= 0) JG_FAIL(h, JG_ERR_ARG, "jg_debug_attention32: bad arguments");
     return check_result(h, launch_attention32(qkv, keymask, B, S, H, dk, out, h->stream, h->kname), "launch_attention32");
+}
+
+// ---- the element-wise and reduction launchers (elementwise.hip, elementwise_f32.hip, elementwise_fp16.hip; tests/test_gpu_elementwise_fp64.py).
+// Each check point refuses up front whatever could make its kernel touch memory outside the caller's buffers (null pointers, sizes <= 0,
+// a leading dimension below the row, a pointer or stride that breaks the kernel's 16-byte accesses, a `valid` array of the wrong
+// length); the shape rules the launcher itself carries come back through check_result.  Nothing is enqueued in either case.
+int jg_debug_stack_frames(jg_handle* h, const void* src, int src_is_u8, int64_t sb, int64_t st, int64_t sh, int64_t sw, int64_t sc, int64_t src_elems,
+                          int B, int T, int pad, int H, int W, void* dst) {
+    ENTER(h);
+    h->kname[0] = 0;
+    if (!src || !dst || B <= 0 || T <= 0 || H <= 0 || W <= 0 || pad < 0 || T + 2 * pad < 5 || sb < 0 || st < 0 || sh < 0 || sw < 0 || sc < 0 ||
+        (src_is_u8 != 0 && src_is_u8 != 1) || !al(dst, 16) || (!src_is_u8 && !al(src, 4)) ||
+        (B - 1) * sb + (T - 1) * st + (H - 1) * sh + (W - 1) * sw + 2 * sc >= src_elems)
+        JG_FAIL(h, JG_ERR_ARG, "jg_debug_stack_frames: bad arguments (T + 2 pad >= 5, strides >= 0 and inside src_elems, dst 16-byte aligned)");
+    const int rc = check_result(h, LAUNCH(h, launch_stack_frames, src, src_is_u8, (long)sb, (long)st, (long)sh, (long)sw, (long)sc, B, T, pad, H, W,
+                                          static_cast<f16*>(dst), h->stream), "launch_stack_frames");
+    if (rc == JG_OK) record_kernel(h->kname, "stack_frames_kernel<%s>", src_is_u8 ? "uint8_t" : "float");
+    return rc;
+}
+
+int jg_debug_window_gather(jg_handle* h, const float* conv, const float* pe, int B, int P, int Twin, int L, int D, int shift, int tiled, float* x32,
+                           void* x16) {
+    ENTER(h);
+    h->kname[0] = 0;
+    if (!conv || !pe || B <= 0 || D <= 0 || shift < 0 || (tiled ? !x16 : !x32) || !al(conv, 16) || !al(pe, 16) || !al(x32, 16) || !al(x16, 8))
+        JG_FAIL(h, JG_ERR_ARG, "jg_debug_window_gather: bad arguments (tiled: x16, row-major: x32; 16-byte aligned fp32 rows)");
+    const int rc = check_result(h, LAUNCH(h, launch_window_gather, conv, pe, B, P, Twin, L, D, shift, tiled != 0, x32, static_cast<f16*>(x16), h->stream),
+                                "launch_window_gather");
+    if (rc == JG_OK) record_kernel(h->kname, "%s", tiled ? "window_gather_tiled_kernel" : "window_gather_kernel");
+    return rc;
+}
+
+int jg_debug_layernorm(jg_handle* h, const float* in, const float* w, const float* b, int rows, int D, int flavour, int relu, float* out32, void* out16) {
+    ENTER(h);
+    h->kname[0] = 0;
+    if (!in || !w || !b || rows <= 0 || D <= 0 || (!out32 && !out16) || (flavour != LN_STD && flavour != LN_ANNOTATED) || relu < 0 || relu > 1 ||
+        !al(in, 16) || !al(w, 16) || !al(b, 16) || !al(out32, 16) || !al(out16, 8))
+        JG_FAIL(h, JG_ERR_ARG, "jg_debug_layernorm: bad arguments (flavour 0 / 1, relu 0 / 1, out32 and / or out16, 16-byte aligned rows)");
+    const int rc = check_result(h, LAUNCH(h, launch_layernorm, in, w, b, rows, D, flavour, relu, out32, static_cast<f16*>(out16), h->stream), "launch_layernorm");
+    if (rc == JG_OK) record_kernel(h->kname, "layernorm_kernel<%d>", D / 256);
+    return rc;
+}
+
+int jg_debug_layernorm_planes(jg_handle* h, const void* hi, const void* lo, const float* w, const float* b, int rows, int D, float* out32) {
+    ENTER(h);
+    h->kname[0] = 0;
+    if (!hi || !lo || !w || !b || !out32 || rows <= 0 || D <= 0 || !al(hi, 8) || !al(lo, 8) || !al(w, 16) || !al(b, 16) || !al(out32, 16))
+        JG_FAIL(h, JG_ERR_ARG, "jg_debug_layernorm_planes: bad arguments");
+    const int rc = check_result(h, LAUNCH(h, launch_layernorm_planes, static_cast<const f16*>(hi), static_cast<const f16*>(lo), w, b, rows, D, out32, h->stream),
+                                "launch_layernorm_planes");
+    if (rc == JG_OK) record_kernel(h->kname, "layernorm_planes_kernel<%d>", D / 256);
+    return rc;
+}
+
+int jg_debug_group_mean(jg_handle* h, const void* in, int groups, int L, int D, void* out) {
+    ENTER(h);
+    h->kname[0] = 0;
+    if (!in || !out || groups <= 0 || D <= 0 || !al(in, 16) || !al(out, 16)) JG_FAIL(h, JG_ERR_ARG, "jg_debug_group_mean: bad arguments");
+    const int rc = check_result(h, LAUNCH(h, launch_group_mean, static_cast<const f16*>(in), groups, L, D, static_cast<f16*>(out), h->stream), "launch_group_mean");
+    if (rc == JG_OK) record_kernel(h->kname, "%s", "group_mean_kernel");
+    return rc;
+}
+
+int jg_debug_cast(jg_handle* h, const float* in, void* out, int64_t n) {
+    ENTER(h);
+    h->kname[0] = 0;
+    if (!in || !out || n <= 0 || !al(in, 16) || !al(out, 8)) JG_FAIL(h, JG_ERR_ARG, "jg_debug_cast: bad arguments");
+    const int rc = check_result(h, LAUNCH(h, launch_cast_f32_f16, in, static_cast<f16*>(out), (long)n, h->stream), "launch_cast_f32_f16");
+    if (rc == JG_OK) record_kernel(h->kname, "%s", "cast_kernel");
+    return rc;
+}
+
+int jg_debug_audio_conv0(jg_handle* h, const float* mel, int B, int Tm, int F, const void* wh, const void* wl, const float* bias, void* out,
+                         const int32_t* valid_host, int n_valid) {
+    ENTER(h);
+    h->kname[0] = 0;
+    if (!mel || !wh || !bias || !out || B <= 0 || Tm <= 0 || F <= 0 || !al(out, 16) || (valid_host ? n_valid != B : n_valid != 0))
+        JG_FAIL(h, JG_ERR_ARG, "jg_debug_audio_conv0: bad arguments (valid_host: one entry per clip)");
+    if (F > 80) JG_FAIL(h, JG_ERR_ARG, "launch_audio_conv0: the launcher rejects this shape / argument set");      // before the upload: nothing enqueued
+    int32_t* valid = nullptr;
+    if (valid_host) RET(upload_valid(h, valid_host, B, &valid));
+    const int rc = check_result(h, LAUNCH(h, launch_audio_conv0, mel, B, Tm, F, static_cast<const f16*>(wh), static_cast<const f16*>(wl), bias,
+                                          static_cast<f16*>(out), static_cast<const int*>(valid), h->stream), "launch_audio_conv0");
+    if (rc == JG_OK) record_kernel(h->kname, "%s", "audio_conv0_kernel");
+    return rc;
+}
+
+int jg_debug_zero_tail(jg_handle* h, void* x, const int32_t* valid_host, int n_valid, int halvings, int B, int H, int64_t row_elems) {
+    ENTER(h);
+    h->kname[0] = 0;
+    if (!x || !valid_host || B <= 0 || H <= 0 || n_valid != B || halvings < 0 || halvings > 30 || row_elems <= 0 || !al(x, 16))
+        JG_FAIL(h, JG_ERR_ARG, "jg_debug_zero_tail: bad arguments (valid_host: one entry per clip)");
+    if (row_elems % 8) JG_FAIL(h, JG_ERR_ARG, "launch_zero_tail: the launcher rejects this shape / argument set");     // before the upload: nothing enqueued
+    int32_t* valid;
+    RET(upload_valid(h, valid_host, B, &valid));
+    const int rc = check_result(h, LAUNCH(h, launch_zero_tail, static_cast<f16*>(x), static_cast<const int*>(valid), halvings, B, H, (long)row_elems, h->stream),
+                                "launch_zero_tail");
+    if (rc == JG_OK) record_kernel(h->kname, "%s", "zero_tail_kernel");
+    return rc;
+}
+
+int jg_debug_xlmr_embed(jg_handle* h, const int32_t* ids, int B, int L, int D, int pad_id, int vocab, int maxpos, const float* word, const float* pos,
+                        const float* type, float* out) {
+    ENTER(h);
+    h->kname[0] = 0;
+    if (!ids || !word || !pos || !type || !out || B <= 0 || L <= 0 || D <= 0 || vocab <= 0 || maxpos <= 0 || pad_id < 0 || pad_id >= maxpos ||
+        !al(word, 16) || !al(pos, 16) || !al(type, 16) || !al(out, 16))
+        JG_FAIL(h, JG_ERR_ARG, "jg_debug_xlmr_embed: bad arguments (0 <= pad_id < maxpos)");
+    const int rc = check_result(h, launch_xlmr_embed(ids, B, L, D, pad_id, vocab, maxpos, word, pos, type, out, h->stream), "launch_xlmr_embed");
+    if (rc == JG_OK) record_kernel(h->kname, "%s", "xlmr_embed_kernel");
+    return rc;
+}
+
+int jg_debug_xlmr_embed_planes(jg_handle* h, const int32_t* ids, int B, int L, int D, int pad_id, int vocab, int maxpos, const float* word,
+                               const float* pos, const float* type, void* hi, void* lo, float* part) {
+    ENTER(h);
+    h->kname[0] = 0;
+    if (!ids || !word || !pos || !type || !hi || !lo || !part || B <= 0 || L <= 0 || D <= 0 || vocab <= 0 || maxpos <= 0 || pad_id < 0 || pad_id >= maxpos ||
+        !al(word, 16) || !al(pos, 16) || !al(type, 16) || !al(hi, 8) || !al(lo, 8) || !al(part, 8))
+        JG_FAIL(h, JG_ERR_ARG, "jg_debug_xlmr_embed_planes: bad arguments (0 <= pad_id < maxpos)");
+    const int rc = check_result(h, LAUNCH(h, launch_xlmr_embed_planes, ids, B, L, D, pad_id, vocab, maxpos, word, pos, type, static_cast<f16*>(hi),
+                                          static_cast<f16*>(lo), part, h->stream), "launch_xlmr_embed_planes");
+    if (rc == JG_OK) record_kernel(h->kname, "%s", "xlmr_embed_planes_kernel");
+    return rc;
+}
+
+int jg_debug_ln_stats(jg_handle* h, const float* part, int rows, int P, float* stats) {
+    ENTER(h);
+    h->kname[0] = 0;
+    if (!part || !stats || rows <= 0 || P <= 0 || !al(part, 8) || !al(stats, 8)) JG_FAIL(h, JG_ERR_ARG, "jg_debug_ln_stats: bad arguments");
+    const int rc = check_result(h, launch_ln_stats(part, rows, P, stats, h->stream), "launch_ln_stats");
+    if (rc == JG_OK) record_kernel(h->kname, "%s", "ln_stats_kernel");
+    return rc;
+}
+
+int jg_debug_mask_i32_f32(jg_handle* h, const int32_t* in, float* out, int64_t n) {
+    ENTER(h);
+    h->kname[0] = 0;
+    if (!in || !out || n <= 0) JG_FAIL(h, JG_ERR_ARG, "jg_debug_mask_i32_f32: bad arguments");
+    const int rc = check_result(h, launch_mask_i32_f32(in, out, (long)n, h->stream), "launch_mask_i32_f32");
+    if (rc == JG_OK) record_kernel(h->kname, "%s", "mask_i32_f32_kernel");
+    return rc;
+}
+
+int jg_debug_transpose_tokens(jg_handle* h, const float* in, int N, int L, int D, float* out) {
+    ENTER(h);
+    h->kname[0] = 0;
+    if (!in || !out || N <= 0 || L <= 0 || D <= 0 || N > 65535 || (L + 31) / 32 > 65535)
+        JG_FAIL(h, JG_ERR_ARG, "jg_debug_transpose_tokens: bad arguments (N and L / 32 are grid dimensions: <= 65535)");
+    const int rc = check_result(h, launch_transpose_tokens(in, N, L, D, out, h->stream), "launch_transpose_tokens");
+    if (rc == JG_OK) record_kernel(h->kname, "%s", "transpose_tokens_kernel");
+    return rc;
+}
+
+int jg_debug_pe_project(jg_handle* h, const float* pe, int S, const void* Wh, const void* Wl, const float* bias, int N, int K, void* out) {
+    ENTER(h);
+    h->kname[0] = 0;
+    if (!pe || !Wh || !out || S <= 0 || N <= 0 || K <= 0 || (long)S * N >= (1L << 31)) JG_FAIL(h, JG_ERR_ARG, "jg_debug_pe_project: bad arguments");
+    FP16_ONLY(h, "jg_debug_pe_project");
+    const int rc = check_result(h, launch_pe_project(pe, S, static_cast<const f16*>(Wh), static_cast<const f16*>(Wl), bias, N, K, static_cast<f16*>(out), h->stream),
+                                "launch_pe_project");
+    if (rc == JG_OK) record_kernel(h->kname, "%s", "pe_project_kernel");
+    return rc;
+}
+
+int jg_debug_broadcast_channels(jg_handle* h, const void* v, int C, void* out, int64_t pixels) {
+    ENTER(h);
+    h->kname[0] = 0;
+    if (!v || !out || C <= 0 || pixels <= 0) JG_FAIL(h, JG_ERR_ARG, "jg_debug_broadcast_channels: bad arguments");
+    FP16_ONLY(h, "jg_debug_broadcast_channels");
+    const int rc = check_result(h, launch_broadcast_channels(static_cast<const f16*>(v), C, static_cast<f16*>(out), (long)pixels, h->stream),
+                                "launch_broadcast_channels");
+    if (rc == JG_OK) record_kernel(h->kname, "%s", "broadcast_channels_kernel");
+    return rc;
+}
+
+int jg_debug_col_sum(jg_handle* h, const void* A, int64_t lda, int M, int K, float* scratch, int64_t scratch_elems, float* out, const float* stats) {
+    ENTER(h);
+    h->kname[0] = 0;
+    if (!A || !scratch || !out || M <= 0 || K <= 0 || lda < K || lda % 8 || !al(A, 16) || scratch_elems < (int64_t)col_sum_scratch_elems(K))
+        JG_FAIL(h, JG_ERR_ARG, "jg_debug_col_sum: bad arguments (lda >= K, lda %% 8 == 0, A 16-byte aligned, scratch of 64 K floats)");
+    FP16_ONLY(h, "jg_debug_col_sum");
+    const int rc = check_result(h, launch_col_sum(static_cast<const f16*>(A), (long)lda, M, K, scratch, out, h->stream, stats), "launch_col_sum");
+    if (rc == JG_OK) record_kernel(h->kname, "%s", "col_sum_kernel+col_sum_finish_kernel");
+    return rc;
+}
+
+int jg_debug_rc_bias(jg_handle* h, const void* A, int64_t lda, int64_t a_elems, int tiled, int nclips, int rpc, const int32_t* valid_host, int n_valid,
+                     const void* lo, const float* bias, int N, int K, float* scratch, int64_t scratch_elems, float* out) {
+    ENTER(h);
+    h->kname[0] = 0;
+    if (!A || !lo || !scratch || !out || nclips <= 0 || rpc <= 0 || N <= 0 || K <= 0 || !al(A, 16) || !al(lo, 16) || !al(scratch, 16) ||
+        (valid_host ? n_valid != nclips : n_valid != 0) || (long)nclips * rpc >= (1L << 31) || scratch_elems < (int64_t)rc_scratch_elems(nclips, K))
+        JG_FAIL(h, JG_ERR_ARG, "jg_debug_rc_bias: bad arguments (valid_host: one entry per clip; scratch of nclips K floats)");
+    const long rows = (long)nclips * rpc;
+    if (tiled ? (long)pad128(rows) * K > a_elems : (lda < K || lda % 8 || (rows - 1) * lda + K > a_elems))
+        JG_FAIL(h, JG_ERR_ARG, "jg_debug_rc_bias: A too small for nclips rpc rows (tiled: whole 128-row tiles), or lda < K / lda %% 8 != 0");
+    FP16_ONLY(h, "jg_debug_rc_bias");
+    if (!rc_bias_ok(N, K, tiled)) JG_FAIL(h, JG_ERR_ARG, "launch_rc_bias: the launcher rejects this shape / argument set");      // before the upload: nothing enqueued
+    int32_t* valid = nullptr;
+    if (valid_host) RET(upload_valid(h, valid_host, nclips, &valid));
+    const int rc = check_result(h, launch_rc_bias(static_cast<const f16*>(A), (long)lda, tiled, nclips, rpc, static_cast<const int*>(valid),
+                                                  static_cast<const f16*>(lo), bias, N, K, scratch, out, h->stream), "launch_rc_bias");
+    if (rc == JG_OK) record_kernel(h->kname, "%s", "rc_col_mean_kernel+rc_gemv_kernel");
+    return rc;
 }
 
 int jg_debug_last_kernel(jg_handle* h, char* buf, int len) {

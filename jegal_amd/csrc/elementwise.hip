@@ -156,6 +156,8 @@ __global__ __launch_bounds__(256) void window_gather_tiled_kernel(const float* _
 hipError_t launch_window_gather(const float* conv, const float* pe, int B, int P, int Twin, int L, int D, int shift, bool tiled,
                                 float* x32, f16* x16, hipStream_t s) {
     if (tiled && D != 512) return hipErrorInvalidValue;
+    if (P <= 0 || L <= 0 || Twin <= 0) return hipErrorInvalidValue;      // an empty clamp range; both kernels divide by L and Twin
+    if (!tiled && D % 4) return hipErrorInvalidValue;                    // four columns per thread
     if (tiled) {
         if ((long)B * Twin * L >= (1L << 31)) return hipErrorInvalidValue;
         const long nblk = (((long)B * Twin * L + 15) >> 4) * 8;
@@ -248,6 +250,7 @@ __global__ void group_mean_kernel(const f16* __restrict__ in, int groups, int L,
 }
 
 hipError_t launch_group_mean(const f16* in, int groups, int L, int D, f16* out, hipStream_t s) {
+    if (D % 8 || L <= 0) return hipErrorInvalidValue;      // eight columns per thread; the mean of no rows
     const long total = (long)groups * (D / 8);
     if (total <= 0) return hipSuccess;
     hipLaunchKernelGGL(group_mean_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, in, groups, L, D, out);
@@ -264,7 +267,8 @@ __global__ void cast_kernel(const float* __restrict__ in, f16* __restrict__ out,
 
 hipError_t launch_cast_f32_f16(const float* in, f16* out, long n, hipStream_t s) {
     if (n <= 0) return hipSuccess;
-    const long n4 = n / 4;   // all call sites have n % 4 == 0
+    if (n % 4) return hipErrorInvalidValue;      // four elements per thread
+    const long n4 = n / 4;
     const int grid = (int)((n4 + 255) / 256 < 65536 * 4 ? (n4 + 255) / 256 : 65536 * 4);
     hipLaunchKernelGGL(cast_kernel, dim3(grid), dim3(256), 0, s, in, out, n4);
     return hipGetLastError();

@@ -67,6 +67,7 @@ size_t col_sum_scratch_elems(int K) { return (size_t)64 * K; }
 
 hipError_t launch_col_sum(const f16* A, long lda, int M, int K, float* scratch, float* out, hipStream_t s, const float* stats) {
     if (M <= 0 || K <= 0) return hipSuccess;
+    if (K % 8) return hipErrorInvalidValue;      // eight columns per thread
     const int cols = K / 8;
     const int gy = M < 64 ? M : 64;
     hipLaunchKernelGGL(col_sum_kernel, dim3((cols + 63) / 64, gy), dim3(64), 0, s, A, lda, M, K, scratch, stats);
