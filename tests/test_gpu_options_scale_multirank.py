@@ -47,11 +47,11 @@ def oracle_sd():
     return O.tensors(synth.gestsync_state_dict(include_unused=False)), O.tensors(synth.jegal_state_dict())
 
 
-# ------------------------------------------------------------------ (a) long sequences: VALU attention + MFMA NB = 5
+# ------------------------------------------------------------------ (a) long sequences: flash MFMA attention + MFMA NB = 5
 @pytest.mark.parametrize("T", [150, 161, 220, 500])
 def test_jegal_gesture_long_clips(models, oracle_sd, T):
     """JEGAL clips are 25-220 frames (dataset/avs_*.csv), the PE table allows 500 (modules.py:136): T = 161, 220 and 500
-    run attn_kernel<64> (VALU), T = 150 the 5-block MFMA kernel; ragged batch with a key mask (modules.py:61-75)."""
+    run attn_mfma_flash_kernel<64>, T = 150 the 5-block MFMA kernel; ragged batch with a key mask (modules.py:61-75)."""
     _, jg = models
     _, jsd = oracle_sd
     rng = np.random.default_rng(700 + T)
@@ -74,7 +74,7 @@ def test_jegal_gesture_long_clips(models, oracle_sd, T):
 
 @pytest.mark.parametrize("L", [33, 70, 200])
 def test_jegal_text_long_sequences(models, oracle_sd, L):
-    """Text encoder (d = 768, dk = 96: attn_kernel<96>) beyond one 32-key block, with a padded clip."""
+    """Text encoder (d = 768, dk = 96: attn_mfma_flash_kernel<96>) beyond one 32-key block, with a padded clip."""
     _, jg = models
     _, jsd = oracle_sd
     rng = np.random.default_rng(800 + L)

@@ -43,7 +43,7 @@ def test_xlmr_matches_transformers_golden(xlmr, golden_dir):
 
 @pytest.mark.parametrize("B,L", [(1, 3), (2, 33), (5, 70), (2, 200), (1, 512), (103, 160)])      # (103, 160): two lanes of 8 160 / 8 320 rows -- 256x256 tiles, the last one partial along M
 def test_xlmr_lengths_vs_oracle(xlmr, B, L):
-    """Short, odd and long sequences (MFMA attention up to 160 tokens, the VALU kernel beyond; 512 = the position table's limit),
+    """Short, odd and long sequences (attn_mfma_kernel up to 160 tokens, attn_mfma_flash_kernel<64> beyond; 512 = the position table's limit),
     ragged padding, against the fp32 restatement."""
     ids, mask = synth.xlmr_inputs(100 + L, B, L)
     sd = synth.xlmr_state_dict()
