@@ -395,6 +395,23 @@ int jg_sim_rank(jg_handle* h, const float* e1, const float* e2, int n_local, int
  * validate them): a clip outside the limits gets pred = -1 and score = NaN instead of a result. */
 int jg_spot(jg_handle* h, const float* gesture, const float* content, const int32_t* g_offsets, const int32_t* c_offsets,
             const int32_t* target, int n_clips, int D, float temp, int32_t* pred, float* score);
+/* evaluate_spotting.py:39-57 (normalize = 1) / utils/plot_heatmap.py:34-59 (normalize = 0) for a ragged batch, and the arg-max of
+ * evaluate_spotting.py:72-73 for EVERY word: per clip A_i = softmax((G_i C_i^T) / temp, dim=1)^T, fp32 row-major (W_i, T_i), written at
+ * A + a_offsets[i] (device int64 ELEMENT offsets, caller-chosen, non-overlapping, gaps allowed; nothing outside the W_i * T_i elements
+ * is written), and per word (in c_offsets order) best_frame = its first arg-max frame, best_score = A_i[w][best_frame] bit for bit.
+ * normalize != 0: both operands' rows are F.normalize'd first (x / max(||x||, 1e-12)); 0: the rows as stored.  The logits run on
+ * exact-fp32 MFMAs: an entry depends on its two rows alone, duplicate frames give bit-equal columns and ties go to the first frame.
+ * Limits per clip as for jg_spot: 1..8192 frames, 1..1024 words; D % 64 == 0; max_frames (1..8192) >= the longest clip sizes the grid.
+ * The offsets are device arrays: a clip outside the limits or longer than max_frames gets best_frame = -1 and best_score = NaN for
+ * its words and nothing of its A is written; the other clips are computed normally.  Bad arguments (null operands, gesture / content
+ * not 16-byte aligned, A without a_offsets, no output at all, max_frames, D, temp <= 0) return JG_ERR_ARG before anything is enqueued.
+ * Workspace: with best_frame or best_score the call takes n_clips * 1024 64-bit arg-max keys (8 KB per clip whatever its word count:
+ * the host cannot see the word counts; 32 MB for 4000 clips) from the handle's workspace; only the keys of existing words are touched.
+ * Asynchronous. */
+int jg_attn_matrix(jg_handle* h, const float* gesture, const float* content, const int32_t* g_offsets, const int32_t* c_offsets,
+                   int n_clips, int D, int max_frames, float temp, int normalize,
+                   float* A, const int64_t* a_offsets,          /* A may be NULL: no matrix is written (one pass over G, the spot-every-word mode) */
+                   int32_t* best_frame, float* best_score);     /* [sum W], in c_offsets order; both may be NULL when A is not */
 /* evaluate_asd.py:43-51,94-100: pred (n,3) = argmax over the first 2/4/6 candidates */
 int jg_asd(jg_handle* h, const float* query, const float* cand, const int32_t* c_offsets, int n, int D, float temp, int32_t* pred);
 

@@ -111,6 +111,7 @@ _SIGS = {
     "jg_pool_mean": [_P, _P, _P, _I, _I, _P],
     "jg_sim_rank": [_P, _P, _P, _I, _I, _I, _I, _P, _P],
     "jg_spot": [_P, _P, _P, _P, _P, _P, _I, _I, ctypes.c_float, _P, _P],
+    "jg_attn_matrix": [_P, _P, _P, _P, _P, _I, _I, _I, ctypes.c_float, _I, _P, _P, _P, _P],
     "jg_asd": [_P, _P, _P, _P, _I, _I, ctypes.c_float, _P],
     "jg_comm_get_unique_id": [ctypes.c_char_p],
     "jg_comm_init": [_P, ctypes.c_char_p, _I, _I],
@@ -765,6 +766,41 @@ class Engine:
         score = torch.empty(n, dtype=torch.float32, device=self.device)
         self._ck(self.lib.jg_spot(self.h, _ptr(g), _ptr(c), _ptr(go), _ptr(co), _ptr(tg), n, g.shape[-1], temp, _ptr(pred), _ptr(score)))
         return pred, score
+
+    def attn_matrix(self, gesture, content, g_offsets, c_offsets, temp=0.07, normalize=True, want_matrix=True):
+        """jg_attn_matrix: per clip A_i = softmax((G_i C_i^T) / temp, dim=1)^T (W_i, T_i) and, for every word, its first arg-max frame and
+        that probability.  gesture (sum T, D) / content (sum W, D); g_offsets / c_offsets: HOST arrays of n + 1 entries.
+        Returns (A_flat | None, a_offsets, best_frame, best_score): clip i's matrix is A_flat[a_offsets[i] : a_offsets[i + 1]].reshape(W_i, T_i)
+        (a_offsets: host int64, n + 1 entries), best_* are device tensors indexed like content's rows (c_offsets[-1] entries: clip i's words
+        are best_*[c_offsets[i] : c_offsets[i + 1]]; entries no clip covers are -1 / NaN).  want_matrix=False: no matrix is written."""
+        goh, coh = (np.asarray(a, np.int64).reshape(-1) for a in (g_offsets, c_offsets))
+        n = goh.size - 1
+        if n < 0 or coh.size != n + 1:
+            raise ValueError("g_offsets / c_offsets need the same number of entries (clips + 1)")
+        T, W = np.diff(goh), np.diff(coh)
+        if n and (T.min() <= 0 or T.max() > 8192 or W.min() <= 0 or W.max() > 1024):
+            raise ValueError("jg_attn_matrix limits: 1..8192 frames and 1..1024 words per clip")
+        if not temp > 0:
+            raise ValueError("temp must be positive")
+        gs, cs = tuple(gesture.shape), tuple(content.shape)
+        if len(gs) != 2 or len(cs) != 2 or gs[1] != cs[1] or gs[1] % 64:
+            raise ValueError("gesture / content must be (rows, D) with the same D, a multiple of 64")
+        if goh[0] < 0 or coh[0] < 0 or gs[0] < goh[-1] or cs[0] < coh[-1]:
+            raise ValueError("offsets must lie inside gesture / content")
+        a_off = np.zeros(n + 1, np.int64)
+        a_off[1:] = np.cumsum(T * W)
+        self._bind_stream()
+        g, c = self._f32(gesture), self._f32(content)
+        A = torch.empty(int(a_off[-1]), dtype=torch.float32, device=self.device) if want_matrix else None
+        best_frame = torch.full((int(coh[-1]),), -1, dtype=torch.int32, device=self.device)
+        best_score = torch.full((int(coh[-1]),), float("nan"), dtype=torch.float32, device=self.device)
+        if n == 0:
+            return A, a_off, best_frame, best_score
+        go, co = self._i32(goh), self._i32(coh)
+        ao = torch.as_tensor(a_off[:-1].copy(), device=self.device) if want_matrix else None
+        self._ck(self.lib.jg_attn_matrix(self.h, _ptr(g), _ptr(c), _ptr(go), _ptr(co), n, gs[1], int(T.max()), float(temp),
+                                         int(bool(normalize)), _ptr(A), _ptr(ao), _ptr(best_frame), _ptr(best_score)))
+        return A, a_off, best_frame, best_score
 
     def asd(self, query, cand, c_offsets, temp=0.07):
         self._bind_stream()

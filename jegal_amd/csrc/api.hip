@@ -508,6 +508,29 @@ int jg_spot(jg_handle* h, const float* g, const float* c, const int32_t* goff, c
     return timed(h, JG_ST_MISC, [&] { return launch_spot(g, c, goff, coff, target, n, D, temp, pred, score, h->stream); });
 }
 
+int jg_attn_matrix(jg_handle* h, const float* g, const float* c, const int32_t* goff, const int32_t* coff, int n, int D, int max_frames,
+                   float temp, int normalize, float* A, const int64_t* aoff, int32_t* best_frame, float* best_score) {
+    ENTER(h);
+    if (!g || !c || !goff || !coff) JG_FAIL(h, JG_ERR_ARG, "null buffer");
+    if (A && !aoff) JG_FAIL(h, JG_ERR_ARG, "A needs a_offsets");
+    if (!A && !best_frame && !best_score) JG_FAIL(h, JG_ERR_ARG, "no output: A, best_frame and best_score are all NULL");
+    if (n < 0 || max_frames < 1 || max_frames > 8192) JG_FAIL(h, JG_ERR_ARG, "max_frames must be 1..8192 (and n_clips >= 0)");
+    if (D <= 0 || D % 64) JG_FAIL(h, JG_ERR_ARG, "D must be a positive multiple of 64");
+    if (!(temp > 0.f)) JG_FAIL(h, JG_ERR_ARG, "temp must be positive");
+    if ((reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(c)) & 15) JG_FAIL(h, JG_ERR_ARG, "gesture / content must be 16-byte aligned");
+    if (n == 0) return JG_OK;
+    unsigned long long* keys = nullptr;          // per-word arg-max keys, combined across the frame blocks of a clip
+    if (best_frame || best_score) {
+        h->ws.reset();
+        RET(wsalloc(h, attn_matrix_key_elems(n), &keys));
+        if (h->ws_poison)                       // test aid: whatever a kernel reads without having written it is NaN
+            for (auto& ch : h->ws.chunks) HIPCHK(h, launch_poison(ch.p, ch.cap, h->stream));
+    }
+    return timed(h, JG_ST_MISC, [&] {
+        return launch_attn_matrix(g, c, goff, coff, n, D, max_frames, temp, normalize, A, aoff, keys, best_frame, best_score, h->stream);
+    });
+}
+
 int jg_asd(jg_handle* h, const float* q, const float* cand, const int32_t* coff, int n, int D, float temp, int32_t* pred) {
     ENTER(h);
     if (!q || !cand || !coff || !pred) JG_FAIL(h, JG_ERR_ARG, "null buffer");

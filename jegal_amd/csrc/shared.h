@@ -84,5 +84,11 @@ hipError_t launch_sim_rank(const float* e1, const float* e2, int n_local, int n_
                            int32_t* rank, int32_t* ties, hipStream_t s);
 hipError_t launch_spot(const float* g, const float* c, const int32_t* goff, const int32_t* coff, const int32_t* target,
                        int n, int D, float temp, int32_t* pred, float* score, hipStream_t s);
+// A (optional; with aoff, int64 element offsets per clip) and / or best_frame / best_score (optional; they need keys: attn_matrix_key_elems(n)
+// words of scratch).  A clip outside the limits (1..8192 frames, <= max_frames, 1..1024 words) is left out: its words read -1 / NaN
+size_t attn_matrix_key_elems(int n_clips);
+hipError_t launch_attn_matrix(const float* g, const float* c, const int32_t* goff, const int32_t* coff, int n, int D, int max_frames,
+                              float temp, int normalize, float* A, const int64_t* aoff, unsigned long long* keys,
+                              int32_t* best_frame, float* best_score, hipStream_t s);
 hipError_t launch_asd(const float* q, const float* cand, const int32_t* coff, int n, int D, float temp,
                       int32_t* pred2, hipStream_t s);

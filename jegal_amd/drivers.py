@@ -6,6 +6,7 @@
     python -m jegal_amd.drivers evaluate_spotting  --path D  # evaluation/evaluate_spotting.py
     python -m jegal_amd.drivers evaluate_asd --path D --file avs_asd.csv   # evaluation/evaluate_asd.py
     python -m jegal_amd.drivers inference_embs ...            # inference_embs.py (single clip -> <fname>.pkl)
+    python -m jegal_amd.drivers attn_matrix --path F|D        # utils/plot_heatmap.py without the rendering (-> <name>.attn.npz)
 
 Same flags, file naming and on-disk formats as the reference.  What is upstream of the hot path is
 NOT rebuilt: video decoding / mediapipe masking (the drivers read already masked 270x480 crops as
@@ -450,7 +451,51 @@ def cmd_evaluate_asd(argv):
     return a2, a4, a6
 
 
+def cmd_attn_matrix(argv, engine=None):
+    """utils/plot_heatmap.py without the matplotlib rendering: the gesture-word attention matrix of one feature .pkl, or of every .pkl of
+    a directory (one jg_attn_matrix call for all of them).  Per clip ``<res_dir>/<name>.attn.npz`` = {attn (W,T) float32, words,
+    best_frame (W,) int32, best_score (W,) float32}; <name> is --fname for a single file (plot_heatmap's flag), the .pkl's own name
+    otherwise.  --normalize 0 (default) is what plot_heatmap.py computes on the stored, already normalised embeddings; 1 re-normalises the
+    rows first (evaluate_spotting.py:39-57).  engine: the Engine to run on (default: this process's)."""
+    from . import metrics as M
+    p = argparse.ArgumentParser(prog="attn_matrix")
+    p.add_argument("--path", required=True, help="a JEGAL feature .pkl, or a directory of them")
+    p.add_argument("--fname", default=None, help="name of the output for a single .pkl (default: the .pkl's name)")
+    p.add_argument("--res_dir", default=".")
+    p.add_argument("--normalize", type=int, default=0, choices=[0, 1])
+    p.add_argument("--temp", type=float, default=0.07)
+    args = p.parse_args(argv)
+    if os.path.isdir(args.path):
+        files, feats = _load_pkls(args.path)
+        names = [os.path.basename(f)[:-len(".pkl")] for f in files]
+    else:
+        with open(args.path, "rb") as f:
+            feats = [pickle.load(f)]
+        names = [args.fname or os.path.basename(args.path).rsplit(".", 1)[0]]
+    if not feats:
+        raise SystemExit("no .pkl under {}".format(args.path))
+    words = []
+    for ft in feats:
+        wb = ft["info"]["word_boundaries"]          # info: the csv row (a pandas Series) or inference_embs' {fname, word_boundaries, text}
+        if isinstance(wb, str):
+            wb = ast.literal_eval(wb)
+        words.append([str(b[0]) for b in wb])
+    eng = engine if engine is not None else _models(args)[0]
+    mats, best = M._attn_call([np.asarray(ft["gesture_emb"], np.float32) for ft in feats],
+                              [np.asarray(ft["content_emb"], np.float32) for ft in feats],
+                              args.temp, bool(args.normalize), eng, None, True)          # matrices and best_* from ONE call
+    os.makedirs(args.res_dir, exist_ok=True)
+    for name, a, w, (bf, bs) in zip(names, mats, words, best):
+        if len(w) != a.shape[0]:
+            raise ValueError("{}: {} word boundaries for {} content rows".format(name, len(w), a.shape[0]))
+        out = os.path.join(args.res_dir, name + ".attn.npz")
+        np.savez(out, attn=a, words=np.asarray(w), best_frame=bf, best_score=bs)
+        print("Attn mtx: ", a.shape, " -> ", out)
+    return 0
+
+
 COMMANDS = {
+    "attn_matrix": cmd_attn_matrix,
     "extract_gestsync_feats": cmd_extract_gestsync_feats,
     "extract_jegal_embs": cmd_extract_jegal_embs,
     "evaluate_retrieval": cmd_evaluate_retrieval,

@@ -111,6 +111,54 @@ def spotting_accuracy(gestures, contents, word_boundaries, targets, thresh=0.5, 
     return 100.0 * correct / max(1, total)
 
 
+def _ragged_inputs(gestures, contents, offsets):
+    """lists of per-clip arrays, or concatenated tensors with offsets=(g_offsets, c_offsets) -> (g, c, host g_offsets, host c_offsets)"""
+    if offsets is not None:
+        goff, coff = (o.cpu().numpy() if isinstance(o, torch.Tensor) else np.asarray(o) for o in offsets)
+        return gestures, contents, goff.astype(np.int64), coff.astype(np.int64)
+    if not len(gestures):
+        return None, None, np.zeros(1, np.int64), np.zeros(1, np.int64)
+    g = torch.as_tensor(np.concatenate([np.asarray(x, np.float32) for x in gestures], 0))
+    c = torch.as_tensor(np.concatenate([np.asarray(x, np.float32) for x in contents], 0))
+    return g, c, _offsets(gestures).astype(np.int64), _offsets(contents).astype(np.int64)
+
+
+def _host(x):
+    return x.cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+
+
+def _attn_call(gestures, contents, temp, normalize, engine, offsets, want_matrix):
+    """One Engine.attn_matrix call for the batch -> (matrices | None, [(frames, scores)]) per clip, on the host"""
+    g, c, goff, coff = _ragged_inputs(gestures, contents, offsets)
+    n = len(goff) - 1
+    if n == 0:
+        return [], []
+    eng = engine or Engine.get()
+    A, aoff, bf, bs = eng.attn_matrix(g, c, goff, coff, temp=temp, normalize=normalize, want_matrix=want_matrix)
+    T, W = np.diff(goff), np.diff(coff)
+    mats = None
+    if want_matrix:
+        A = _host(A)
+        mats = [A[aoff[i]:aoff[i + 1]].reshape(W[i], T[i]) for i in range(n)]
+    bf, bs = _host(bf), _host(bs)
+    return mats, [(bf[coff[i]:coff[i + 1]], bs[coff[i]:coff[i + 1]]) for i in range(n)]
+
+
+def attention_matrices(gestures, contents, temp=0.07, normalize=True, engine=None, offsets=None):
+    """The gesture-word heat maps of a batch of clips: per clip softmax((G C^T) / temp, dim=1)^T, float32 (W_i, T_i) -- get_attn_matrix of
+    evaluate_spotting.py:39-57 (normalize=True: rows L2-normalised first) or of utils/plot_heatmap.py:34-59 (normalize=False: rows as stored).
+    Inputs as for spotting_accuracy: lists of per-clip (T_i,512) / (W_i,512) arrays, or the concatenated tensors with
+    ``offsets=(g_offsets, c_offsets)``.  One jg_attn_matrix call for the whole batch."""
+    return _attn_call(gestures, contents, temp, normalize, engine, offsets, True)[0]
+
+
+def spot_words(gestures, contents, temp=0.07, normalize=True, engine=None, offsets=None):
+    """Every word of every clip localised (evaluate_spotting.py:72-73 applied to each row of the attention matrix): per clip
+    (frames int32 (W_i,), scores float32 (W_i,)) = first arg-max frame of the word's row and its probability.  The matrix itself is
+    not written (jg_attn_matrix with A = NULL)."""
+    return _attn_call(gestures, contents, temp, normalize, engine, offsets, False)[1]
+
+
 def asd_counts(pred):
     """[correct for 2, 4, 6 speakers, queries] from jg_asd's (n,3) argmax indices: the positive is candidate 0 (evaluate_asd.py:101-113)."""
     pred = np.asarray(pred).reshape(-1, 3)
