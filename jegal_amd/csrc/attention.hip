@@ -6,7 +6,7 @@
 //     attn_kernel<DK>        option attn_mfma = 0 only (A/B, tests): VALU kernel, one lane per
 //                            query row, K/V rows in LDS read as wave-wide broadcasts, v_dot2_f32_f16, online softmax
 //                            over blocks of 8 keys, fp32 state.  For S <= 32 one wave carries floor(64/S) (sequence, head) pairs.
-//     the parts of the MFMA kernels, each written once: the accumulator layout (acc_key), the loads and the LDS images
+//     the parts of the MFMA kernels, each written once: the accumulator layout (mfma32_row), the loads and the LDS images
 //                            (load16, stage_row, stage_vt, stage_kv, stage_mask, operand_frag, load_q_operand), the score
 //                            tile and its masking (score_tile, mask_scale_tile, exp_sum_tile), P.V from the score
 //                            accumulators (split_hi_lo + pv_mfma = pv_step) and the output path (store_rows).
@@ -181,9 +181,8 @@ __global__ __launch_bounds__(256) void attn_kernel(const f16* __restrict__ qkv, 
 // tile, hh the half of a k-step's 16 values it holds.  Rows beyond S are clamped on load (finite values), masked to -inf as
 // keys and never stored as queries.
 
-// THE accumulator layout of the 32x32x16 tile: register i of a lane in half hh holds row acc_key(i, hh) of the lane's column --
-// a key of a score tile, a d of an output block.  Registers 4g .. 4g+3 are the four consecutive rows from acc_key(4g, hh).
-__device__ __forceinline__ constexpr int acc_key(int i, int hh) { return (i & 3) + 8 * (i >> 2) + 4 * hh; }
+// THE accumulator layout of the 32x32x16 tile: register i of a lane in half hh holds row mfma32_row(i, hh) of the lane's column --
+// a key of a score tile, a d of an output block.  Registers 4g .. 4g+3 are the four consecutive rows from mfma32_row(4g, hh).
 
 template <int N>
 __device__ __forceinline__ void zero_tiles(f32x16 (&t)[N]) {
@@ -250,7 +249,7 @@ __device__ __forceinline__ f32x16 score_tile(const char* sK, int kb, const f16x8
 __device__ __forceinline__ void mask_scale_tile(f32x16& sc, const float* sMt, int hh, float scale, float& mx) {
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
-        const f32x4 mk = *reinterpret_cast<const f32x4*>(&sMt[acc_key(4 * g, hh)]);
+        const f32x4 mk = *reinterpret_cast<const f32x4*>(&sMt[mfma32_row(4 * g, hh)]);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             float v = sc[4 * g + e] * scale;
@@ -270,7 +269,7 @@ __device__ __forceinline__ void exp_sum_tile(f32x16& sc, float mx, float& sum) {
 }
 
 // O^T += V^T P^T, one k-step (s = 0, 1: 16 keys) of a tile of probabilities at a time.  The operand trick: registers 8s .. 8s+7
-// of a lane ARE the B fragment of k-step s (lane = query), in the permuted key order acc_key(8s + j, hh).
+// of a lane ARE the B fragment of k-step s (lane = query), in the permuted key order mfma32_row(8s + j, hh).
 // split_hi_lo: that fragment as 16-bit hi + lo (two MFMAs per block of 32 d): the probabilities keep fp32 accuracy, as in the
 // VALU kernel, and the matrix pipe has nothing else to do.  NORM: times inv = 1 / sum first (kernels that know the sum by now).
 template <bool NORM>
@@ -284,10 +283,10 @@ __device__ __forceinline__ void split_hi_lo(const f32x16& sc, int s, f16x8& pH, 
     }
 }
 // pv_mfma: the two MFMAs of one block of 32 d (row = this lane's d).  V^T is read in the fragment's key order: four keys from
-// key0 + acc_key(8s, hh) and the four 8 further on (acc_key(8s + 4, hh)); key0 = the tile's first key in the V^T image.
+// key0 + mfma32_row(8s, hh) and the four 8 further on (mfma32_row(8s + 4, hh)); key0 = the tile's first key in the V^T image.
 template <int PITCH>
 __device__ __forceinline__ void pv_mfma(f16x8 pH, f16x8 pL, int s, const char* sVt, int key0, int row, int hh, f32x16& o) {
-    const char* vp = sVt + row * PITCH + (key0 + acc_key(8 * s, hh)) * 2;
+    const char* vp = sVt + row * PITCH + (key0 + mfma32_row(8 * s, hh)) * 2;
     const f16x4 v0 = *reinterpret_cast<const f16x4*>(vp), v1 = *reinterpret_cast<const f16x4*>(vp + 16);
     const f16x8 vA = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
     o = JG_MFMA_32x32x16(vA, pH, o);
@@ -302,7 +301,7 @@ __device__ __forceinline__ void pv_step(const f32x16& sc, int s, const char* sVt
     for (int blk = 0; blk < NBLK; ++blk) pv_mfma<PITCH>(pH, pL, s, sVt, key0, r31 + 32 * blk, hh, o[blk]);
 }
 
-// Output path: the accumulator blocks o (register i of block blk <-> d = 32 blk + acc_key(i, hh), lane <-> query) -> [query][d]
+// Output path: the accumulator blocks o (register i of block blk <-> d = 32 blk + mfma32_row(i, hh), lane <-> query) -> [query][d]
 // 16-bit rows in the wave's LDS slice sO -> whole-row stores to obase[row][..] for the rows with q0 + row < S.  PASS blocks
 // (32 PASS columns) go through the slice at a time; NORM folds inv = 1 / sum into the conversion; rows >= OR do not exist in
 // the slice (OR = 32: all do).  The wave's LDS operations execute in order; the wave_lds_sync()s keep the compiler to it.
@@ -318,7 +317,7 @@ __device__ __forceinline__ void store_rows(const f32x16 (&o)[NBLK], char* sO, f1
                 f16x4 hv;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) hv[e] = (f16)(NORM ? o[b0 + blk][4 * g + e] * inv : o[b0 + blk][4 * g + e]);
-                if (OR == 32 || r31 < OR) *reinterpret_cast<f16x4*>(sO + r31 * PITCH + (32 * blk + acc_key(4 * g, hh)) * 2) = hv;
+                if (OR == 32 || r31 < OR) *reinterpret_cast<f16x4*>(sO + r31 * PITCH + (32 * blk + mfma32_row(4 * g, hh)) * 2) = hv;
             }
         wave_lds_sync();
 #pragma unroll
@@ -433,7 +432,7 @@ __global__ __launch_bounds__(256, 5) void attn_mfma_s32_kernel(const f16* __rest
     float mx = -INFINITY;
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
-        sc[i] = acc_key(i, hh) < S ? sc[i] * scale : -INFINITY;
+        sc[i] = mfma32_row(i, hh) < S ? sc[i] * scale : -INFINITY;
         mx = fmaxf(mx, sc[i]);
     }
     mx = fmaxf(mx, __shfl_xor(mx, 32, 64));

@@ -141,7 +141,7 @@ __global__ __launch_bounds__(256) void gemm32_kernel(Gemm32Args a) {
                 for (int j = 0; j < NB; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[i], x[j], acc[i][j], 0, 0, 0);
         }
     }
-    // D layout: B index (m) = lane & 31, A index (n) = (x & 3) + 8 (x >> 2) + 4 (lane >> 5)
+    // D layout: B index (m) = lane & 31, A index (n) = mfma32_row(x, lane >> 5): registers 4q .. 4q + 3 are four consecutive n
     const bool n4ok = (a.N & 3) == 0 && (a.ldc & 3) == 0 && (!a.res || (a.ldr & 3) == 0);
 #pragma unroll
     for (int j = 0; j < NB; ++j) {
@@ -152,7 +152,7 @@ __global__ __launch_bounds__(256) void gemm32_kernel(Gemm32Args a) {
         for (int i = 0; i < NB; ++i)
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const int n = n0 + wn * (BT / 2) + i * 32 + 8 * q + 4 * (lane >> 5);
+                const int n = n0 + wn * (BT / 2) + i * 32 + mfma32_row(4 * q, lane >> 5);
                 if (n >= a.N) continue;
                 float v[4];
 #pragma unroll
@@ -423,7 +423,6 @@ __global__ void poison_kernel(uint4* __restrict__ p, size_t n16) {
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n16; i += (size_t)gridDim.x * blockDim.x) p[i] = make_uint4(~0u, ~0u, ~0u, ~0u);
 }
 
-inline int grid_for(long total) { return (int)((total + 255) / 256 < 65536 * 4 ? (total + 255) / 256 : 65536 * 4); }
 
 }  // namespace
 

@@ -174,7 +174,7 @@ int jg_debug_conv_check(jg_handle* h, const jg_conv_check* c) {
     if (M >= (1L << 31)) JG_FAIL(h, JG_ERR_ARG, "jg_debug_conv_check: too many output pixels");
     if (c->s2_host) {
         for (int i = 0; i < c->nimg; ++i)
-            if (c->s2_host[i] < 0 || c->s2_host[i] > 255 || conv_skip_decode(c->s2_host[i], c->op) >= g.OH)
+            if (c->s2_host[i] < 0 || c->s2_host[i] > ROWMAP_MAX_S2 || conv_skip_decode(c->s2_host[i], c->op) >= g.OH)
                 JG_FAIL(h, JG_ERR_ARG, "jg_debug_conv_check: s2[%d] = %d outside 0..255 or leaves image %d no output row", i, c->s2_host[i], i);
     }
     GemmArgs a;
@@ -193,19 +193,13 @@ int jg_debug_conv_check(jg_handle* h, const jg_conv_check* c) {
         if (!plan_gemm(q, o).ok()) JG_FAIL(h, JG_ERR_ARG, "launch_gemm: the launcher rejects this shape / argument set");
         h->ws.reset();
         int32_t* s2;
-        int* totals;
         ConvRowMap rm;
-        rm.OH = g.OH; rm.OW = g.OW; rm.op = c->op;
+        const f16* const cin = static_cast<const f16*>(c->const_in);
         RET(wsalloc(h, (size_t)c->nimg, &s2));
-        RET(wsalloc(h, (size_t)M, &rm.map));
-        RET(wsalloc(h, (size_t)c->nimg + 1, &rm.base));
-        RET(wsalloc(h, (size_t)64, &totals));
-        rm.total = totals;
+        RET(rowmap_chain(h, c->nimg, 1, &g.OH, &g.OW, c->op, &rm, &g, &cin));
         RET(upload_i32_async(h, c->s2_host, (size_t)c->nimg, s2));
         const int rc = check_result(h, launch_conv_rowmaps(s2, c->nimg, &rm, 1, h->stream), "launch_conv_rowmaps");
         if (rc != JG_OK) return rc;
-        g.rowmap = rm.map; g.rows_total = rm.total;
-        g.in_op = c->op - 1; g.const_in = static_cast<const f16*>(c->const_in);
     }
     a.g = g;
     return check_result(h, LAUNCH(h, launch_gemm, a, true, o, h->stream), "launch_gemm");
@@ -219,7 +213,7 @@ int jg_debug_maxpool(jg_handle* h, const void* in, int nimg, int H, int W, int C
     int32_t* s2 = nullptr;
     if (s2_host) {
         for (int i = 0; i < nimg; ++i)
-            if (s2_host[i] < 0 || s2_host[i] > 255 || conv_skip_decode(s2_host[i], in_op) > H)
+            if (s2_host[i] < 0 || s2_host[i] > ROWMAP_MAX_S2 || conv_skip_decode(s2_host[i], in_op) > H)
                 JG_FAIL(h, JG_ERR_ARG, "jg_debug_maxpool: s2[%d] = %d outside 0..255 or past the image's %d rows", i, s2_host[i], H);
         h->ws.reset();
         RET(wsalloc(h, (size_t)nimg, &s2));
@@ -240,24 +234,17 @@ int jg_debug_conv_rowmaps(jg_handle* h, const int32_t* s2_host, int NF, const in
     for (int l = 0; l < nlayers; ++l) {
         if (OH[l] <= 0 || OW[l] <= 0 || !map_host[l] || !base_host[l]) JG_FAIL(h, JG_ERR_ARG, "jg_debug_conv_rowmaps: bad layer %d", l);
         for (int i = 0; i < NF; ++i)
-            if (s2_host[i] < 0 || s2_host[i] > 255 || conv_skip_decode(s2_host[i], l) > OH[l])
+            if (s2_host[i] < 0 || s2_host[i] > ROWMAP_MAX_S2 || conv_skip_decode(s2_host[i], l) > OH[l])
                 JG_FAIL(h, JG_ERR_ARG, "jg_debug_conv_rowmaps: s2[%d] = %d outside 0..255 or past layer %d's %d rows", i, s2_host[i], l, OH[l]);
     }
     h->ws.reset();
     int32_t* s2;
-    int* totals;
     ConvRowMap rm[4];
     RET(wsalloc(h, (size_t)NF, &s2));
-    RET(wsalloc(h, (size_t)64, &totals));
+    RET(rowmap_chain(h, NF, nlayers, OH, OW, 0, rm));
     RET(upload_i32_async(h, s2_host, (size_t)NF, s2));
-    for (int l = 0; l < nlayers; ++l) {
-        const size_t n = (size_t)NF * OH[l] * OW[l];
-        rm[l].OH = OH[l]; rm[l].OW = OW[l]; rm[l].op = l;
-        RET(wsalloc(h, n, &rm[l].map));
-        RET(wsalloc(h, (size_t)NF + 1, &rm[l].base));
-        rm[l].total = totals + l;
-        HIPCHK(h, hipMemcpy(rm[l].map, map_host[l], n * sizeof(int), hipMemcpyHostToDevice));      // the caller's fill: the launch writes the first *total entries only
-    }
+    for (int l = 0; l < nlayers; ++l)      // the caller's fill: the launch writes the first *total entries only
+        HIPCHK(h, hipMemcpy(rm[l].map, map_host[l], (size_t)NF * OH[l] * OW[l] * sizeof(int), hipMemcpyHostToDevice));
     const int rc = check_result(h, launch_conv_rowmaps(s2, NF, rm, nlayers, h->stream), "launch_conv_rowmaps");
     if (rc != JG_OK) return rc;
     record_kernel(h->kname, "%s", "conv_rowmap_scan_kernel+conv_rowmap_fill_kernel");

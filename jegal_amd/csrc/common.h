@@ -56,7 +56,7 @@ struct ConvGeom {
     // ("const chain", gestsync.hip).  PER POSITION (image) p, conv2 leaves its first s2[p] output rows out and every deeper layer the
     // count conv_skip_decode(s2[p], op) derived from it; a consumer reads the input rows its producer left out from the const
     // image of its input instead.  The computed rows of a launch are COMPACTED: the kernel runs over m' = 0 .. *rows_total - 1 and
-    //   rowmap[m'] = (full output row = (img*OH + oh)*OW + ow) | s2[img] << 24
+    //   rowmap[m'] = rowmap_entry(full output row = (img*OH + oh)*OW + ow, s2[img])      (shared.h)
     // gives it the pixel to compute, the row to store to and the image's count (launch_conv_rowmaps builds the maps on the
     // device from conv1_skip_mask_kernel's per-position counts; the host never sees a value, nothing synchronises).
     const int* rowmap;        // nullptr: every row is computed, m' = m
@@ -140,14 +140,7 @@ struct GemmArgs {
     int rpc, nclips;
 };
 
-// ---- tiled token stream (N = 512 columns, row tiles of 128) -----------------------------------------------------
-// The residual stream of the fused transformer is one fp16 plane: in a post-norm transformer the LayerNorm output is
-// rounded to fp16 as the next GEMM's operand anyway, and carrying the residual at that precision costs 1-5 % of the
-// feature error (oracle/precision_families.py) for no extra bytes and no codec arithmetic.
-// The plane is stored in the MFMA fragment order of the 128x512 LN kernel:
-//   x16t element (m, n): R*65536 + (n>>6)*8192 + ((m&127)>>4)*1024 + ((n&63)>>4)*256 + (m&15)*16 + (n&15),  R = m>>7
-//        (a wave's 8-byte accesses of one (j, i) block are one contiguous 512 B; a 64-wide k-tile of a 128-row
-//         panel is one contiguous 16 KB -> the consumer GEMMs' LDS-DMA reads it with a_tiled addressing)
+// (the tiled token stream x16t of the fused transformer -- GemmArgs::res16 / a_tiled -- has its layout in shared.h: x16t_index)
 #ifdef __HIPCC__
 typedef float f32x2_t __attribute__((ext_vector_type(2)));
 #endif

@@ -213,7 +213,7 @@ struct Mfma32 {
     __device__ __forceinline__ Mfma32(const f16* Wd, int lane, int chalf_) : chalf(chalf_), r(lane & 31), h(lane >> 5) {
 #pragma unroll
         for (int s = 0; s < 49; ++s)
-            wreg[s] = *reinterpret_cast<const f16x8*>(Wd + ((long)(s * 64 + chalf * 32 + r) * 16 + 8 * h));
+            wreg[s] = *reinterpret_cast<const f16x8*>(Wd + conv1_wd_index(s, chalf * 32 + r, 8 * h));
     }
     // patch-fragment address of lane (r,h) for slot (kh,kw): pixel x = 3r+kw ->
     //   (3*mb+kh)*ROW_PITCH + 32*x + 16*(x/3) + 16*h = [112*r + 16*h] + [kh*ROW_PITCH + 32*kw + 16*(kw/3)]
@@ -285,7 +285,7 @@ struct Mfma16 {
             const int sl = sel ? khb * 7 + kwb : kha * 7 + kwa;
 #pragma unroll
             for (int ob = 0; ob < 2; ++ob) {
-                wreg[t][ob] = *reinterpret_cast<const f16x8*>(Wd + ((long)(sl * 64 + chalf * 32 + ob * 16 + n16) * 16 + 8 * half));
+                wreg[t][ob] = *reinterpret_cast<const f16x8*>(Wd + conv1_wd_index(sl, chalf * 32 + ob * 16 + n16, 8 * half));
                 if (t == 24 && sel) wreg[t][ob] = f16x8{0, 0, 0, 0, 0, 0, 0, 0};
             }
         }
@@ -752,7 +752,7 @@ __global__ void conv1_edge_fix_kernel(f16* __restrict__ out, const f16* __restri
 // relu(bias) of channel c as the MFMA path rounds it: the bias is the hi+lo pair on the pad lane of slots 0 and 1, times the pad
 // lane's "1.0" = 2^-24; both products and their sum are exact in fp32
 __device__ __forceinline__ f16 conv1_zero_patch_value(const f16* __restrict__ Wd, float scale, int c) {
-    const float hi = (float)Wd[(0 * 64 + c) * 16 + 15], lo = (float)Wd[(1 * 64 + c) * 16 + 15];
+    const float hi = (float)Wd[conv1_wd_index(0, c, CONV1_BIAS_LANE)], lo = (float)Wd[conv1_wd_index(1, c, CONV1_BIAS_LANE)];
     const float acc = hi * 5.9604644775390625e-8f + lo * 5.9604644775390625e-8f;
     return (f16)fmaxf(acc * scale, 0.f);
 }
@@ -760,8 +760,7 @@ __global__ void conv1_zconst_kernel(const f16* __restrict__ Wd, float scale, f16
     if (threadIdx.x < 64) zconst[threadIdx.x] = conv1_zero_patch_value(Wd, scale, threadIdx.x);
 }
 
-__device__ __forceinline__ int* zmask_hdr(f16* zconst) { return reinterpret_cast<int*>(zconst); }   // zconst = word 0 of the header
-
+// zconst: the start of the scan scratch (Conv1Scan, shared.h), whose header also holds the launch-wide minimum reset below
 __global__ __launch_bounds__(256) void conv1_zero_scan_kernel(const uint8_t* __restrict__ src, unsigned* __restrict__ zmask,
                                                               const f16* __restrict__ Wd, float scale, f16* __restrict__ zconst) {
     __shared__ int rowz[IH + 2];
@@ -796,7 +795,7 @@ __global__ __launch_bounds__(256) void conv1_zero_scan_kernel(const uint8_t* __r
     }
     if (blockIdx.x == 0 && tid < 64) zconst[tid] = conv1_zero_patch_value(Wd, scale, tid);
     // reset the launch-wide minimum that conv1_skip_mask_kernel (next on the stream) reduces into
-    if (blockIdx.x == 0 && tid == 64) zmask_hdr(zconst)[CONV1_ROWSKIP_WORD] = 0x7fffffff;
+    if (blockIdx.x == 0 && tid == 64) reinterpret_cast<int*>(zconst)[CONV1_ROWSKIP_WORD] = 0x7fffffff;
 }
 
 // position nf = (clip b, padded-clip position p) reads frames clamp(p + dt - pad), dt = 0..4: a tile is all-zero for the position
@@ -831,24 +830,21 @@ __global__ void conv1_skip_mask_kernel(const unsigned* __restrict__ fz, int ncli
     if ((threadIdx.x & 63) == 0 && rs != 0x7fffffff) atomicMin(rowskip_min, rs);
 }
 
-// workspace words: header of CONV1_ZHDR_WORDS (zconst: 64 halves = 32 words; word CONV1_ROWSKIP_WORD: constant leading rows of
-// conv2's output) + nclip*T (frame masks) + nclip*(T+2*pad-4) (position skip masks)
-// + nclip*(T+2*pad-4) (per-position counts s2); sized for pad <= 12
-size_t conv1_zmask_elems(int nclip, int T) { return (size_t)CONV1_ZHDR_WORDS + (size_t)nclip * T + 2 * (size_t)nclip * (T + 20); }
+// workspace words of the scan scratch (layout: Conv1Scan, shared.h), sized for pad <= CONV1_SCAN_MAX_PAD
+size_t conv1_zmask_elems(int nclip, int T) { return conv1_scan_view(nullptr, nclip, T, CONV1_SCAN_MAX_PAD).words; }
 const int* conv1_s2_counts(const unsigned* zscratch, int nclip, int T, int pad) {
-    return reinterpret_cast<const int*>(zscratch + CONV1_ZHDR_WORDS + (size_t)nclip * T + (size_t)nclip * (T + 2 * pad - 4));
+    return conv1_scan_view(const_cast<unsigned*>(zscratch), nclip, T, pad).s2();
 }
 
 // Zero-band scan + per-position skip masks + the zero-patch constant into `zscratch` (conv1_zmask_elems words).
 hipError_t launch_conv1_scan(const uint8_t* src, int nclip, int T, int pad, const f16* Wd, float scale, unsigned* zscratch, hipStream_t s) {
     if (nclip * T <= 0) return hipSuccess;
     const int P = T + 2 * pad - 4;
-    unsigned* fz = zscratch + CONV1_ZHDR_WORDS;
-    unsigned* sk = fz + (size_t)nclip * T;
-    f16* zc = reinterpret_cast<f16*>(zscratch);
-    hipLaunchKernelGGL(conv1_zero_scan_kernel, dim3((unsigned)(nclip * T)), dim3(256), 0, s, src, fz, Wd, scale * 16777216.0f, zc);
-    hipLaunchKernelGGL(conv1_skip_mask_kernel, dim3((unsigned)((nclip * P + 255) / 256)), dim3(256), 0, s, fz, nclip, T, pad, P, sk,
-                       reinterpret_cast<int*>(sk + (size_t)nclip * P), reinterpret_cast<int*>(zscratch) + CONV1_ROWSKIP_WORD);
+    const Conv1Scan z = conv1_scan_view(zscratch, nclip, T, pad);
+    hipLaunchKernelGGL(conv1_zero_scan_kernel, dim3((unsigned)(nclip * T)), dim3(256), 0, s, src, z.frame_mask(), Wd, scale * 16777216.0f,
+                       static_cast<f16*>(z.zconst()));
+    hipLaunchKernelGGL(conv1_skip_mask_kernel, dim3((unsigned)((nclip * P + 255) / 256)), dim3(256), 0, s, z.frame_mask(), nclip, T, pad, P,
+                       z.pos_mask(), z.s2(), z.rowskip_min());
     return hipGetLastError();
 }
 
@@ -885,8 +881,9 @@ hipError_t launch_conv1_direct(const uint8_t* src, int nclip, int T, int pad, co
     a.fill_partial = 0;
     if (num_cu > MAX_WGS) return hipErrorInvalidValue;
     if (a.zskip && zscratch && nclip * T > 0 && (a.nstrips + num_cu - 1) / num_cu + 8 <= MAX_WG_STRIPS) {
-        a.zmask = zscratch + CONV1_ZHDR_WORDS + (size_t)nclip * T;
-        a.zconst = reinterpret_cast<const f16*>(zscratch);
+        const Conv1Scan z = conv1_scan_view(const_cast<unsigned*>(zscratch), nclip, T, pad);
+        a.zmask = z.pos_mask();
+        a.zconst = static_cast<const f16*>(z.zconst());
         if (!fill_all) a.fill_partial = 1;
     }
     if (a.nstrips <= 0) return hipSuccess;

@@ -41,7 +41,7 @@ __global__ void stack_frames_kernel(const SRC* __restrict__ src, long sb, long s
 hipError_t launch_stack_frames(const void* src, int src_is_u8, long sb, long st, long sh, long sw, long sc,
                                int B, int T, int pad, int H, int W, f16* dst, hipStream_t s) {
     const long total = (long)B * (T + 2 * pad - 4) * H * W;
-    const int grid = (int)((total + 255) / 256 < 65536 * 4 ? (total + 255) / 256 : 65536 * 4);
+    const int grid = grid_for(total);
     if (src_is_u8)
         hipLaunchKernelGGL(stack_frames_kernel<uint8_t>, dim3(grid), dim3(256), 0, s, (const uint8_t*)src, sb, st, sh, sw, sc, B, T, pad, H, W, dst);
     else
@@ -85,7 +85,7 @@ hipError_t launch_maxpool3x3s2(const f16* in, f16* out, int N, int H, int W, int
                                const f16* const_in) {
     const int OH = (H - 3) / 2 + 1, OW = (W - 3) / 2 + 1;
     const long total = (long)N * OH * OW * (C / 8);
-    const int grid = (int)((total + 255) / 256 < 65536 * 4 ? (total + 255) / 256 : 65536 * 4);
+    const int grid = grid_for(total);
     hipLaunchKernelGGL(maxpool_kernel, dim3(grid), dim3(256), 0, s, in, out, N, H, W, C, OH, OW, s2, in_op, const_in);
     return hipGetLastError();
 }
@@ -143,13 +143,13 @@ __global__ __launch_bounds__(256) void window_gather_tiled_kernel(const float* _
     pp = pp < 0 ? 0 : (pp > P - 1 ? P - 1 : pp);
     const float* src = conv + ((long)b * P + pp) * 512 + cb * 64 + 4 * ng;
     const float* pes = pe + (long)j * 512 + cb * 64 + 4 * ng;
-    const long base = (rb >> 3) * 65536 + (long)cb * 8192 + (rb & 7) * 1024;
+    f16* const dst = x16 + x16t_row_off(rb * 16 + m15) + x16t_col_off(cb * 64 + 4 * ng);      // + q * X16T_QUAD: the row's four column quads
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         f32x4 v = *reinterpret_cast<const f32x4*>(src + 16 * q);
         v += *reinterpret_cast<const f32x4*>(pes + 16 * q);
         const f16x4 h = {(f16)v.x, (f16)v.y, (f16)v.z, (f16)v.w};
-        if (live) __builtin_nontemporal_store(h, reinterpret_cast<f16x4*>(x16 + base + q * 256 + m15 * 16 + 4 * ng));
+        if (live) __builtin_nontemporal_store(h, reinterpret_cast<f16x4*>(dst + q * X16T_QUAD));
     }
 }
 
@@ -165,7 +165,7 @@ hipError_t launch_window_gather(const float* conv, const float* pe, int B, int P
         return hipGetLastError();
     }
     const long total = (long)B * Twin * L * (D / 4);
-    const int grid = (int)((total + 255) / 256 < 65536 * 4 ? (total + 255) / 256 : 65536 * 4);
+    const int grid = grid_for(total);
     hipLaunchKernelGGL(window_gather_kernel, dim3(grid), dim3(256), 0, s, conv, pe, B, P, Twin, L, D, shift, x32, x16);
     return hipGetLastError();
 }
@@ -269,7 +269,7 @@ hipError_t launch_cast_f32_f16(const float* in, f16* out, long n, hipStream_t s)
     if (n <= 0) return hipSuccess;
     if (n % 4) return hipErrorInvalidValue;      // four elements per thread
     const long n4 = n / 4;
-    const int grid = (int)((n4 + 255) / 256 < 65536 * 4 ? (n4 + 255) / 256 : 65536 * 4);
+    const int grid = grid_for(n4);
     hipLaunchKernelGGL(cast_kernel, dim3(grid), dim3(256), 0, s, in, out, n4);
     return hipGetLastError();
 }
@@ -424,7 +424,7 @@ __global__ __launch_bounds__(256) void xlmr_embed_planes_kernel(const int32_t* _
             s1 += __shfl_xor(s1, d, 64);
             s2 += __shfl_xor(s2, d, 64);
         }
-        if ((lane & 15) == 0) *reinterpret_cast<f32x2_t*>(part + 2 * (row * (D >> 6) + (c >> 6))) = f32x2_t{s1, s2};
+        if ((lane & 15) == 0) *reinterpret_cast<f32x2_t*>(part + ln_part_index(row, D >> 6, c >> 6)) = f32x2_t{s1, s2};
     }
 }
 hipError_t launch_xlmr_embed_planes(const int32_t* ids, int B, int L, int D, int pad_id, int vocab, int maxpos, const float* word, const float* pos,

@@ -87,7 +87,7 @@ __global__ void ln_stats_kernel(const float* __restrict__ part, int rows, int P,
     if (r >= rows) return;
     double s1 = 0.0, s2 = 0.0;
     for (int p = 0; p < P; ++p) {
-        const f32x2_t v = *reinterpret_cast<const f32x2_t*>(part + 2 * ((long)r * P + p));
+        const f32x2_t v = *reinterpret_cast<const f32x2_t*>(part + ln_part_index(r, P, p));
         s1 += (double)v.x;
         s2 += (double)v.y;
     }
@@ -195,6 +195,48 @@ hipError_t launch_logmel(const float* wav, int B, int n_samples, const float* me
 // Packed source (offs != nullptr): the producer ships only the source rows BELOW each frame's mask -- frame f's rows
 // row0 = max(mask_y[f] + 1, 0) .. H-1 start at src + offs[f]; the blanked rows are never read here, so they need not exist.
 // A frame whose kept rows would end beyond `src_bytes` (bad metadata) is written as zeros instead of being read.
+// The arithmetic, written once for the two kernels below (they differ in how they stage the source, and must stay bit-identical):
+__device__ inline int mr_sat_short(float v) {
+    int r = __float2int_rn(v);
+    return r < -32768 ? -32768 : (r > 32767 ? 32767 : r);
+}
+// output column dx -> source columns sx, min(sx + 1, W - 1) with weights a0, a1 (scale_x = W / 480 in double; all three fit a short
+// when W <= 32767: the banded kernel keeps them in LDS as such)
+__device__ __forceinline__ void mr_col_coef(int dx, double scale_x, int W, int& sx, int& a0, int& a1) {
+    float fx = (float)((dx + 0.5) * scale_x - 0.5);
+    sx = (int)floorf(fx);
+    fx -= sx;
+    if (sx < 0) { fx = 0.f; sx = 0; }
+    if (sx + 1 >= W) { fx = 0.f; sx = W - 1; }
+    a0 = mr_sat_short((1.f - fx) * 2048.f);
+    a1 = mr_sat_short(fx * 2048.f);
+}
+// output row dy -> source rows y0, y1 (clamped to the frame) with weights b0, b1 (scale_y = H / 270 in double)
+__device__ inline void mr_row_coef(int dy, double scale_y, int H, int& y0, int& y1, int& b0, int& b1) {
+    float fy = (float)((dy + 0.5) * scale_y - 0.5);
+    const int sy = (int)floorf(fy);
+    fy -= sy;
+    b0 = mr_sat_short((1.f - fy) * 2048.f);
+    b1 = mr_sat_short(fy * 2048.f);
+    y0 = sy < 0 ? 0 : (sy < H ? sy : H - 1);
+    y1 = sy + 1 < 0 ? 0 : (sy + 1 < H ? sy + 1 : H - 1);
+}
+// the 8-bit blend of the four neighbours (rows y0 / y1 x columns sx / x1)
+__device__ __forceinline__ uint8_t mr_blend(int p00, int p01, int p10, int p11, int a0, int a1, int b0, int b1) {
+    const int S0 = p00 * a0 + p01 * a1, S1 = p10 * a0 + p11 * a1;
+    const int v = (((b0 * (S0 >> 4)) >> 16) + ((b1 * (S1 >> 4)) >> 16) + 2) >> 2;
+    return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
+}
+// the first source row a frame keeps: the one below its mask (face found), or row 0 (face None: the blank rows are cut AFTER the resize)
+// (a macro: as a function it is simplified on its own before it is inlined, and the banded kernel's scalar code comes out in another order)
+#define MR_FIRST_ROW(my, H) ((my) >= 0 ? ((my) + 1 < (H) ? (my) + 1 : (H)) : 0)
+// Packed source: the frame's kept rows row0 .. H-1 start at src + o.  Where its row 0 would be (the rows above row0 do not exist and are
+// never read), and whether the metadata is bad (the kept rows would start in front of src or end beyond src_bytes)
+__device__ __forceinline__ const uint8_t* mr_packed_base(const uint8_t* __restrict__ src, long long o, int H, int W, int row0, long long src_bytes, bool& bad) {
+    bad = o < 0 || o + (long long)(H - row0) * W * 3 > src_bytes;
+    return src + o - (long long)row0 * W * 3;
+}
+
 __global__ void mask_resize_kernel(const uint8_t* __restrict__ src, int T, int H, int W, const int* __restrict__ mask_y,
                                    uint8_t* __restrict__ dst, const long long* __restrict__ offs, long long src_bytes) {
     constexpr int OH = 270, OW = 480;
@@ -209,44 +251,23 @@ __global__ void mask_resize_kernel(const uint8_t* __restrict__ src, int T, int H
         o[0] = o[1] = o[2] = 0;
         return;
     }
-    const double scale_x = (double)W / OW, scale_y = (double)H / OH;
-    float fx = (float)((dx + 0.5) * scale_x - 0.5);
-    int sx = (int)floorf(fx);
-    fx -= sx;
-    if (sx < 0) { fx = 0.f; sx = 0; }
-    if (sx + 1 >= W) { fx = 0.f; sx = W - 1; }
-    float fy = (float)((dy + 0.5) * scale_y - 0.5);
-    const int sy = (int)floorf(fy);
-    fy -= sy;
-    auto sat_short = [](float v) -> int {
-        int r = __float2int_rn(v);
-        return r < -32768 ? -32768 : (r > 32767 ? 32767 : r);
-    };
-    const int a0 = sat_short((1.f - fx) * 2048.f), a1 = sat_short(fx * 2048.f);
-    const int b0 = sat_short((1.f - fy) * 2048.f), b1 = sat_short(fy * 2048.f);
-    const int y0 = sy < 0 ? 0 : (sy < H ? sy : H - 1);
-    const int y1 = sy + 1 < 0 ? 0 : (sy + 1 < H ? sy + 1 : H - 1);
+    int sx, a0, a1, y0, y1, b0, b1;
+    mr_col_coef(dx, (double)W / OW, W, sx, a0, a1);
+    mr_row_coef(dy, (double)H / OH, H, y0, y1, b0, b1);
     const int x1 = sx + 1 < W ? sx + 1 : W - 1;
     const uint8_t* fr = src + (long)f * H * W * 3;
     bool bad = false;
-    if (offs) {
-        const int row0 = my >= 0 ? (my + 1 < H ? my + 1 : H) : 0;
-        const long long o = offs[f];
-        bad = o < 0 || o + (long long)(H - row0) * W * 3 > src_bytes;
-        fr = src + o - (long long)row0 * W * 3;
-    }
+    if (offs) fr = mr_packed_base(src, offs[f], H, W, MR_FIRST_ROW(my, H), src_bytes, bad);
     const bool z0 = bad || (my >= 0 && y0 <= my), z1 = bad || (my >= 0 && y1 <= my);       // blanked source rows
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         const int p00 = z0 ? 0 : fr[((long)y0 * W + sx) * 3 + c], p01 = z0 ? 0 : fr[((long)y0 * W + x1) * 3 + c];
         const int p10 = z1 ? 0 : fr[((long)y1 * W + sx) * 3 + c], p11 = z1 ? 0 : fr[((long)y1 * W + x1) * 3 + c];
-        const int S0 = p00 * a0 + p01 * a1, S1 = p10 * a0 + p11 * a1;
-        const int v = (((b0 * (S0 >> 4)) >> 16) + ((b1 * (S1 >> 4)) >> 16) + 2) >> 2;
-        o[c] = (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
+        o[c] = mr_blend(p00, p01, p10, p11, a0, a1, b0, b1);
     }
 }
 
-// The same arithmetic, banded (round 4: the streamed source-resolution upload runs this kernel on the upload stream next to the
+// The same arithmetic (the mr_* functions above), banded (round 4: the streamed source-resolution upload runs this kernel on the upload stream next to the
 // compute, so its cost is CU time taken from the extraction): one workgroup = RB output rows of one frame.  The source rows the
 // band touches are one contiguous byte span of the frame: staged into LDS with dword loads (the span's start is aligned down, a
 // tail of < 4 bytes is loaded bytewise, nothing outside [src, src + src_bytes) is touched), the per-column (sx, a1) and per-row
@@ -270,34 +291,17 @@ __global__ __launch_bounds__(256) void mask_resize_band_kernel(const uint8_t* __
     const int my = mask_y[f];
     uint4* out16 = reinterpret_cast<uint4*>(dst + ((long)f * OH + dy0) * (OW * 3));
     constexpr int OUT_V = RB * OW * 3 / 16;    // 540 16-byte pieces
-    auto sat_short = [](float v) -> int {
-        int r = __float2int_rn(v);
-        return r < -32768 ? -32768 : (r > 32767 ? 32767 : r);
-    };
     const double scale_x = (double)W / OW, scale_y = (double)H / OH;
     // per-row coefficients (every thread computes the band's first / last source row itself: wave-uniform, no barrier needed for them)
-    auto row_coef = [&](int dy, int& y0, int& y1, int& b0, int& b1) {
-        float fy = (float)((dy + 0.5) * scale_y - 0.5);
-        const int sy = (int)floorf(fy);
-        fy -= sy;
-        b0 = sat_short((1.f - fy) * 2048.f);
-        b1 = sat_short(fy * 2048.f);
-        y0 = sy < 0 ? 0 : (sy < H ? sy : H - 1);
-        y1 = sy + 1 < 0 ? 0 : (sy + 1 < H ? sy + 1 : H - 1);
-    };
     int ylo, yhi, t0, t1, t2;
-    row_coef(dy0, ylo, t0, t1, t2);
-    row_coef(dy0 + RB - 1, t0, yhi, t1, t2);
-    // rows the band READS: those below the mask (face found) or all of them (face None: the blank rows are cut AFTER the resize)
-    const int row0 = my >= 0 ? (my + 1 < H ? my + 1 : H) : 0;
+    mr_row_coef(dy0, scale_y, H, ylo, t0, t1, t2);
+    mr_row_coef(dy0 + RB - 1, scale_y, H, t0, yhi, t1, t2);
+    // rows the band READS: those the frame keeps
+    const int row0 = MR_FIRST_ROW(my, H);
     const int rlo = ylo > row0 ? ylo : row0;
     const uint8_t* fr = src + (long)f * H * W * 3;
     bool bad = false;
-    if (offs) {
-        const long long o = offs[f];
-        bad = o < 0 || o + (long long)(H - row0) * W * 3 > src_bytes;
-        fr = src + o - (long long)row0 * W * 3;
-    }
+    if (offs) fr = mr_packed_base(src, offs[f], H, W, row0, src_bytes, bad);
     const bool none = bad || rlo > yhi || (my < 0 && dy0 + RB - 1 <= 110);      // nothing of the source reaches this band
     if (none) {
         for (int i = tid; i < OUT_V; i += 256) out16[i] = make_uint4(0u, 0u, 0u, 0u);
@@ -312,16 +316,13 @@ __global__ __launch_bounds__(256) void mask_resize_band_kernel(const uint8_t* __
     for (long i = tid; i < nfull; i += 256) reinterpret_cast<uint32_t*>(span)[i] = reinterpret_cast<const uint32_t*>(p_al)[i];
     for (long i = nfull * 4 + tid; i < shift + nbytes; i += 256) span[i] = p_al[i];
     for (int dx = tid; dx < OW; dx += 256) {
-        float fx = (float)((dx + 0.5) * scale_x - 0.5);
-        int sx = (int)floorf(fx);
-        fx -= sx;
-        if (sx < 0) { fx = 0.f; sx = 0; }
-        if (sx + 1 >= W) { fx = 0.f; sx = W - 1; }
+        int sx, a0, a1;
+        mr_col_coef(dx, scale_x, W, sx, a0, a1);
         cx_s[dx] = (short)sx;
-        cx_a0[dx] = (short)sat_short((1.f - fx) * 2048.f);
-        cx_a[dx] = (short)sat_short(fx * 2048.f);
+        cx_a0[dx] = (short)a0;
+        cx_a[dx] = (short)a1;
     }
-    if (tid < RB) row_coef(dy0 + tid, ry0[tid], ry1[tid], rb0[tid], rb1[tid]);
+    if (tid < RB) mr_row_coef(dy0 + tid, scale_y, H, ry0[tid], ry1[tid], rb0[tid], rb1[tid]);
     __syncthreads();
     const int rowb = W * 3;
     for (int i = tid; i < RB * OW; i += 256) {
@@ -341,9 +342,7 @@ __global__ __launch_bounds__(256) void mask_resize_band_kernel(const uint8_t* __
         for (int c = 0; c < 3; ++c) {
             const int p00 = z0 ? 0 : q0[sx * 3 + c], p01 = z0 ? 0 : q0[x1 * 3 + c];
             const int p10 = z1 ? 0 : q1[sx * 3 + c], p11 = z1 ? 0 : q1[x1 * 3 + c];
-            const int S0 = p00 * a0 + p01 * a1, S1 = p10 * a0 + p11 * a1;
-            const int v = (((b0 * (S0 >> 4)) >> 16) + ((b1 * (S1 >> 4)) >> 16) + 2) >> 2;
-            o[c] = (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
+            o[c] = mr_blend(p00, p01, p10, p11, a0, a1, b0, b1);
         }
     }
     __syncthreads();
@@ -403,7 +402,7 @@ hipError_t launch_unpack_masked(const uint8_t* packed, const int* row0, const lo
 // ---- compaction maps of the conv layers behind conv1 (common.h: ConvGeom::rowmap, ConvRowMap) ----------------------------------
 // Image (position) img computes rows >= s = conv_skip_decode(s2[img], op) of a layer's OH x OW output.  Step 1, one workgroup:
 // exclusive prefix of the images' computed pixels per layer (base[img], *total).  Step 2, one workgroup per image: its computed
-// pixels (one contiguous run of full indices per layer) go to their compacted place, | s2 << 24.
+// pixels (one contiguous run of full indices per layer) go to their compacted place as rowmap_entry(full index, s2).
 struct RowMapArgs {
     const int* s2;
     int NF, nl;
@@ -459,7 +458,7 @@ __global__ __launch_bounds__(256) void conv_rowmap_fill_kernel(RowMapArgs a) {
         const int n = (R.OH - s) * R.OW;                   // computed pixels of this image: full rows s*OW .. OH*OW - 1
         const int first = img * R.OH * R.OW + s * R.OW;
         int* dst = R.map + R.base[img];
-        for (int i = threadIdx.x; i < n; i += 256) dst[i] = (first + i) | (w << 24);
+        for (int i = threadIdx.x; i < n; i += 256) dst[i] = rowmap_entry(first + i, w);
     }
 }
 
@@ -469,7 +468,7 @@ hipError_t launch_conv_rowmaps(const int* s2, int NF, const ConvRowMap* layers, 
     a.s2 = s2; a.NF = NF; a.nl = nlayers;
     for (int l = 0; l < 4; ++l) {
         a.L[l] = layers[l < nlayers ? l : nlayers - 1];
-        if ((long)NF * a.L[l].OH * a.L[l].OW >= (1L << 24)) return hipErrorInvalidValue;      // 24-bit row index in the map entries
+        if ((long)NF * a.L[l].OH * a.L[l].OW >= ROWMAP_MAX_ROWS) return hipErrorInvalidValue;      // the row index of a map entry
     }
     hipLaunchKernelGGL(conv_rowmap_scan_kernel, dim3(1), dim3(1024), 0, s, a);
     hipLaunchKernelGGL(conv_rowmap_fill_kernel, dim3((unsigned)NF), dim3(256), 0, s, a);

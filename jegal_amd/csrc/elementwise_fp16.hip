@@ -105,8 +105,7 @@ __global__ __launch_bounds__(256) void rc_col_mean_kernel(const f16* __restrict_
     float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     auto row_ptr = [&](int r) -> const f16* {
         const long m = (long)clip * rpc_all + r;
-        return tiled ? A + (m >> 7) * 65536 + (long)(n >> 6) * 8192 + ((m & 127) >> 4) * 1024 + ((n & 63) >> 4) * 256 + (m & 15) * 16 + (n & 15)
-                     : A + m * lda + n;
+        return tiled ? A + x16t_index(m, n) : A + m * lda + n;
     };
     // row lane rl takes row (rl & 15) of every second sampled run (runs of its parity rl >> 4); EIGHT loads in flight per thread (the
     // rows were just written with nontemporal stores: every load is an HBM round trip, and a 150-frame clip gives a thread 13 rows),
@@ -179,10 +178,10 @@ __global__ __launch_bounds__(256) void rc_gemv_kernel(const f16* __restrict__ me
     }
     __syncthreads();
     if (wave == 0 && c0 + r31 < nclips) {
-        // register i <-> column n0 + (i & 3) + 8 (i >> 2) + 4 hh, lane <-> clip
+        // register i <-> column n0 + mfma32_row(i, hh), lane <-> clip
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-            const int n = n0 + (i & 3) + 8 * (i >> 2) + 4 * hh;
+            const int n = n0 + mfma32_row(i, hh);
             out[(long)(c0 + r31) * N + n] = (bias ? bias[n] : 0.f) + (((acc[i] + red[0][i][lane]) + red[1][i][lane]) + red[2][i][lane]);
         }
     }

@@ -308,6 +308,27 @@ int wsalloc(jg_handle* h, size_t n, T** out) {
     return JG_OK;
 }
 
+// Row-map chain set-up (ConvGeom::rowmap, launch_conv_rowmaps): rm[l], l < n, becomes the compaction map of a conv layer with OH[l] x OW[l]
+// outputs per image and conv_skip_decode op op0 + l over NF images -- map, base and the layer's word of one block of totals (rm[0].total)
+// come from the workspace.  g (optional, [n]): the layers' geometries, patched to run compacted and to read the rows their producer
+// left out from const_in[l].
+inline int rowmap_chain(jg_handle* h, long NF, int n, const int* OH, const int* OW, int op0, ConvRowMap* rm, ConvGeom* g = nullptr,
+                        const f16* const* const_in = nullptr) {
+    int* totals;
+    RET(wsalloc(h, (size_t)64, &totals));
+    for (int l = 0; l < n; ++l) {
+        rm[l].OH = OH[l]; rm[l].OW = OW[l]; rm[l].op = op0 + l;
+        RET(wsalloc(h, (size_t)NF * OH[l] * OW[l], &rm[l].map));
+        RET(wsalloc(h, (size_t)NF + 1, &rm[l].base));
+        rm[l].total = totals + l;
+        if (g) {
+            g[l].rowmap = rm[l].map; g[l].rows_total = rm[l].total;
+            g[l].in_op = rm[l].op - 1; g[l].const_in = const_in ? const_in[l] : nullptr;
+        }
+    }
+    return JG_OK;
+}
+
 constexpr int FH = 270, FW = 480;
 inline size_t pad128(size_t rows) { return (rows + 127) / 128 * 128; }
 

@@ -354,7 +354,7 @@ __device__ __forceinline__ void epi_ln_producer(const TileCtx& c, f32x4 (&acc)[4
         s1 += __shfl_xor(s1, 32, 64);
         s2 += __shfl_xor(s2, 32, 64);
         if (fq == 0 && (m_full || mb + j * 16 < Mrows))
-            *reinterpret_cast<f32x2_t*>(a.stat_out + 2 * ((long)(mb + j * 16) * nblk + sblk)) = f32x2_t{s1, s2};
+            *reinterpret_cast<f32x2_t*>(a.stat_out + ln_part_index(mb + j * 16, nblk, sblk)) = f32x2_t{s1, s2};
     }
 }
 
@@ -498,7 +498,7 @@ __global__ __launch_bounds__(512) void gemm_glds_kernel(GemmArgs a, int n_tiles,
     const bool rowconst = ROWCONST && rmap && a.g.const_in;
     auto row_full = [&](int m) -> long {
         if (!CONV || !rmap) return m;
-        return rmap[m] & 0xffffff;
+        return rowmap_row(rmap[m]);
     };
 
     // Persistent: one workgroup per CU walks rounds of G tiles.  Within a round the workgroups of one
@@ -547,8 +547,8 @@ __global__ __launch_bounds__(512) void gemm_glds_kernel(GemmArgs a, int n_tiles,
                 int s2 = 0;
                 if (rmap) {
                     const int e = rmap[m];
-                    m = e & 0xffffff;
-                    s2 = (int)((unsigned)e >> 24);
+                    m = rowmap_row(e);
+                    s2 = rowmap_s2(e);
                 }
                 // m < 2^24 (launch_gemm): quotients from float reciprocals with a +-1 fix-up instead of two integer divisions
                 // (8 pieces x 2 divisions per tile and lane, and their temporaries on top of 128 live accumulators)
@@ -569,7 +569,8 @@ __global__ __launch_bounds__(512) void gemm_glds_kernel(GemmArgs a, int n_tiles,
                 if constexpr (ROWCONST) xalt[i] = a.g.const_in + ((long)ih * a.g.W + iw) * a.g.C + c * 8;
             } else {
                 xpix[i] = 0;
-                xsrc[i] = (!XE && a.a_tiled) ? a.A + (long)(m >> 7) * 65536 + ((m & 127) >> 4) * 1024 + (m & 15) * 16 + (c >> 1) * 256 + (c & 1) * 8
+                // (the chunk's column offset x16t_col_off(8 c), term by term: as one sum it changes the register allocation of every plain instance)
+                xsrc[i] = (!XE && a.a_tiled) ? a.A + x16t_row_off(m) + (c >> 1) * X16T_QUAD + (c & 1) * 8
                                              : a.A + (long)m * a.lda + c * 8;
             }
         }
@@ -633,7 +634,7 @@ __global__ __launch_bounds__(512) void gemm_glds_kernel(GemmArgs a, int n_tiles,
                 src = ok ? xsrc[i] + stapoff : zeros;
                 if (ROWCONST && ok && ih < (xpix[i] & 0xff)) src = xalt[i] + stapoff;
             } else {
-                src = xsrc[i] + ((!XE && a.a_tiled) ? (long)sk0 * 128 : (long)sk0);        // tiled plane: a k-tile is 8192 elements on
+                src = xsrc[i] + ((!XE && a.a_tiled) ? (long)sk0 * (X16T_COLBLK / 64) : (long)sk0);        // tiled plane: a 64-wide k-tile is X16T_COLBLK elements on
             }
             // LNF, long K (linear2: 413 MB of hidden activations read once by one tile each): nontemporal (aux = 2) so
             // the stream does not push the weights out of L2.  Measured: linear2+LN 282 -> 266 us; for out_proj (K = 512,
@@ -687,14 +688,14 @@ __global__ __launch_bounds__(512) void gemm_glds_kernel(GemmArgs a, int n_tiles,
     //   acc[0][j] = {x16 i=0 (2 regs), x16 i=3 (2 regs)},  acc[1][j].xy = x16 i=1,  acc[2][j].xy = x16 i=2.
     // (As separate arrays hipcc spilled every loaded value to scratch right behind its load.)
     f32x4 acc[4][MI];
-    auto x16t_off = [&](int tm0) -> long { return (long)(tm0 / BM) * 65536 + (long)wn * 8192 + frow * 16 + fq * 4; };     // + j*1024 + i*256
+    auto x16t_off = [&](int tm0) -> long { return (long)(tm0 / BM) * X16T_TILE + (long)wn * X16T_COLBLK + frow * 16 + fq * 4; };     // + j * X16T_ROWBLK + i * X16T_QUAD
     auto asf = [](unsigned v) -> float { return __builtin_bit_cast(float, v); };
     auto load_stream = [&](int tm0, int j) __attribute__((always_inline)) {
-        const f16* xp = a.res16 + x16t_off(tm0) + j * 1024;
+        const f16* xp = a.res16 + x16t_off(tm0) + j * X16T_ROWBLK;
         typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
         // read-once stream: nontemporal, so it does not push the weights out of L2
-        const u32x2 r0 = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(xp)), r1 = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(xp + 256));
-        const u32x2 r2 = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(xp + 512)), r3 = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(xp + 768));
+        const u32x2 r0 = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(xp)), r1 = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(xp + X16T_QUAD));
+        const u32x2 r2 = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(xp + 2 * X16T_QUAD)), r3 = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(xp + 3 * X16T_QUAD));
         acc[0][j] = f32x4{asf(r0.x), asf(r0.y), asf(r3.x), asf(r3.y)};
         acc[1][j] = f32x4{asf(r1.x), asf(r1.y), 0.f, 0.f};
         acc[2][j] = f32x4{asf(r2.x), asf(r2.y), 0.f, 0.f};
@@ -863,8 +864,8 @@ __global__ __launch_bounds__(512) void gemm_glds_kernel(GemmArgs a, int n_tiles,
                 const int wrow0 = cm0 + wm * WROWS;
                 // (rows past Mrows of an M-partial tile: clamped -- their stores are masked, but the read must stay inside the map)
                 const int i0 = wrow0 + lane_t < Mrows ? wrow0 + lane_t : Mrows - 1, i1 = wrow0 + 64 + lane_t < Mrows ? wrow0 + 64 + lane_t : Mrows - 1;
-                if (WROWS >= 64 || lane_t < WROWS) rtab[lane_t] = rmap[i0] & 0xffffff;
-                if (WROWS > 64) rtab[64 + lane_t] = rmap[i1] & 0xffffff;
+                if (WROWS >= 64 || lane_t < WROWS) rtab[lane_t] = rowmap_row(rmap[i0]);
+                if (WROWS > 64) rtab[64 + lane_t] = rowmap_row(rmap[i1]);
                 wave_lds_sync();
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -959,7 +960,7 @@ __global__ __launch_bounds__(512) void gemm_glds_kernel(GemmArgs a, int n_tiles,
                     const f32x4 y = acc[i][j] * inv * *reinterpret_cast<const f32x4*>(lnp + BN + ncol + i * 16) +
                                     *reinterpret_cast<const f32x4*>(lnp + 2 * BN + ncol + i * 16);
                     const f16x4 hv = {(f16)y.x, (f16)y.y, (f16)y.z, (f16)y.w};
-                    *reinterpret_cast<f16x4*>(o16 + j * 1024 + i * 256) = hv;
+                    *reinterpret_cast<f16x4*>(o16 + j * X16T_ROWBLK + i * X16T_QUAD) = hv;
                 }
                 if (nbid >= 0) load_stream(m0, j);                        // m0 is already the next tile's
             }

@@ -138,7 +138,7 @@ GemmPlan plan_gemm(const GemmShape& a, const EngineOpts& o) {
         if (a.res) return rejected;          // the conv instances are compiled without the residual path
         // as for the plain GEMMs below: 4 columns per lane in every store, 16-byte pieces of the weight rows in every loader
         if (a.N % 4 || a.ldc % 4 || a.ldw % 8) return rejected;
-        const bool coords_ok = a.H + a.PH < 2048 && a.W + a.PW < 2048 && a.M < (1 << 24);      // packed pixel coordinates / rowmap entries
+        const bool coords_ok = a.H + a.PH < 2048 && a.W + a.PW < 2048 && a.M < ROWMAP_MAX_ROWS;      // packed pixel coordinates / rowmap entries
         // C = 32 -> N = 64 (the second audio conv): its own LDS-DMA instance, 256x64 tiles (round 5; before: the register-staged kernel)
         if (o.gemm_glds && !a.w2 && a.N == 64 && a.C == 32 && a.K % 32 == 0 && a.K == a.KH * a.KW * 32 && !a.tap_table && !a.rowmap &&
             a.M >= GEMM_GLDS_CONV_MIN_ROWS && coords_ok && a.out16 && !a.out32 && (a.ldc & 7) == 0 && (a.ldw & 7) == 0)

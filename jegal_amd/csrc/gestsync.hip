@@ -62,15 +62,15 @@ int finalize_gestsync(jg_handle* h) {
         HIPCHK(h, hipMemcpy(hostw.data(), gs.c1.wh, hostw.size() * sizeof(f16), hipMemcpyDeviceToHost));
         for (int s = 0; s < 49; ++s)
             for (int o = 0; o < 64; ++o)
-                for (int e = 0; e < 16; ++e) wd[((size_t)s * 64 + o) * 16 + e] = hostw[(size_t)o * 784 + s * 16 + e];
-        // bias lane: the kernel sets element 15 of every pixel slot to 1.0; shift*255 as hi+lo fp16 pair
+                for (int e = 0; e < 16; ++e) wd[conv1_wd_index(s, o, e)] = hostw[(size_t)o * 784 + s * 16 + e];
+        // bias lane: the kernel sets element CONV1_BIAS_LANE of every pixel slot to 1.0; shift*255 as hi+lo fp16 pair
         std::vector<float> shift(64);
         HIPCHK(h, hipMemcpy(shift.data(), gs.c1.bias, 64 * sizeof(float), hipMemcpyDeviceToHost));
         for (int o = 0; o < 64; ++o) {
             const float v = shift[o] * 255.0f;
             const f16 hi = (f16)v;
-            wd[((size_t)0 * 64 + o) * 16 + 15] = hi;
-            wd[((size_t)1 * 64 + o) * 16 + 15] = (f16)(v - (float)hi);
+            wd[conv1_wd_index(0, o, CONV1_BIAS_LANE)] = hi;
+            wd[conv1_wd_index(1, o, CONV1_BIAS_LANE)] = (f16)(v - (float)hi);
         }
         RET(upload(h, m, wd, &gs.c1_direct));
     }
@@ -179,21 +179,15 @@ static int gs_conv_stack(jg_handle* h, const void* src, int src_u8, long sb, lon
         s2pos = conv1_s2_counts(zscr, nclip, T, pad);
         const f16* cin[4] = {nullptr, gs.c2C, gs.c3C, gs.c4C};
         ConvRowMap rm[4];
-        int* totals;
-        RET(wsalloc(h, (size_t)64, &totals));
+        int OH[4], OW[4];
         for (int l = 0; l < 4; ++l) {
-            ConvGeom& gl = g[l + 1];
-            rm[l].OH = gl.OH; rm[l].OW = gl.OW; rm[l].op = l;
-            RET(wsalloc(h, (size_t)NF * gl.OH * gl.OW, &rm[l].map));
-            RET(wsalloc(h, (size_t)NF + 1, &rm[l].base));
-            rm[l].total = totals + l;
-            gl.rowmap = rm[l].map; gl.rows_total = rm[l].total;
-            gl.in_op = l - 1; gl.const_in = cin[l];
-            h->last_conv_full[l] = NF * gl.OH * gl.OW;
+            OH[l] = g[l + 1].OH; OW[l] = g[l + 1].OW;
+            h->last_conv_full[l] = NF * OH[l] * OW[l];
         }
+        RET(rowmap_chain(h, NF, 4, OH, OW, 0, rm, g + 1, cin));
         RET(timed(h, JG_ST_CONV1_AUX, [&] { return launch_conv_rowmaps(s2pos, (int)NF, rm, 4, h->stream); }));
-        h->last_conv_totals = totals;
-        h->last_rowskip = reinterpret_cast<const int*>(zscr) + CONV1_ROWSKIP_WORD;
+        h->last_conv_totals = rm[0].total;
+        h->last_rowskip = conv1_scan_view(zscr, nclip, T, pad).rowskip_min();
     }
     Epi e;
     e.relu = 1;

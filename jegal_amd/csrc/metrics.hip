@@ -56,11 +56,11 @@ __global__ __launch_bounds__(256) void sim_rank_kernel(const float* __restrict__
                 acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0);
             }
         }
-        // D layout: col = lane&31 (gallery), row = (x&3) + 8*(x>>2) + 4*(lane>>5) (query)
+        // D layout: col = lane & 31 (gallery), row = mfma32_row(x, lane >> 5) (query)
         if (tile < 0) {
 #pragma unroll
             for (int x = 0; x < 16; ++x) {
-                const int row = wr * 32 + (x & 3) + 8 * (x >> 2) + 4 * (lane >> 5);
+                const int row = wr * 32 + mfma32_row(x, lane >> 5);
                 const int col = wc * 32 + (lane & 31);
                 if (row == col) sDiag[row] = acc[x];
             }
@@ -70,7 +70,7 @@ __global__ __launch_bounds__(256) void sim_rank_kernel(const float* __restrict__
             const bool jok = j < n_total;
 #pragma unroll
             for (int x = 0; x < 16; ++x) {
-                const int row = wr * 32 + (x & 3) + 8 * (x >> 2) + 4 * (lane >> 5);
+                const int row = wr * 32 + mfma32_row(x, lane >> 5);
                 const float d = sDiag[row];
                 cnt_gt[x] += (jok && acc[x] > d) ? 1 : 0;
                 cnt_eq[x] += (jok && acc[x] == d) ? 1 : 0;
@@ -84,7 +84,7 @@ __global__ __launch_bounds__(256) void sim_rank_kernel(const float* __restrict__
 #pragma unroll
         for (int o = 16; o > 0; o >>= 1) { g += __shfl_xor(g, o, 64); e += __shfl_xor(e, o, 64); }
         if ((lane & 31) == 0) {
-            const int row = wr * 32 + (x & 3) + 8 * (x >> 2) + 4 * (lane >> 5);
+            const int row = wr * 32 + mfma32_row(x, lane >> 5);
             atomicAdd(&sRank[row], g);
             atomicAdd(&sTies[row], e);
         }
@@ -108,11 +108,6 @@ hipError_t launch_sim_rank(const float* e1, const float* e2, int n_local, int n_
 // Word spotting (evaluate_spotting.py:39-82): per clip A = softmax((G C^T)/temp, dim=1) over words
 // with re-normalised rows; pred = first argmax_t A[t][w*], score = A[pred][w*].
 // One block per clip, one wave per frame row; the W logits of a row go through a per-wave LDS line.
-__device__ __forceinline__ float wsum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 __device__ __forceinline__ float wmax(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
@@ -142,7 +137,7 @@ __global__ __launch_bounds__(256) void spot_kernel(const float* __restrict__ g, 
     for (int w = wave; w < W; w += 4) {
         float sq = 0.f;
         for (int d = lane; d < D; d += 64) { const float v = c[(long)(w0 + w) * D + d]; sq += v * v; }
-        sq = wsum(sq);
+        sq = wave_sum(sq);
         if (lane == 0) sCn[w] = 1.f / fmaxf(sqrtf(sq), 1e-12f);
     }
     __syncthreads();
@@ -151,12 +146,12 @@ __global__ __launch_bounds__(256) void spot_kernel(const float* __restrict__ g, 
         const float* gr = g + (long)(t0 + t) * D;
         float sq = 0.f;
         for (int d = lane; d < D; d += 64) { const float v = gr[d]; sq += v * v; }
-        const float gn = 1.f / fmaxf(sqrtf(wsum(sq)), 1e-12f);
+        const float gn = 1.f / fmaxf(sqrtf(wave_sum(sq)), 1e-12f);
         for (int w = 0; w < W; ++w) {
             const float* cr = c + (long)(w0 + w) * D;
             float dot = 0.f;
             for (int d = lane; d < D; d += 64) dot += (gr[d] * gn) * (cr[d] * sCn[w]);
-            dot = wsum(dot) / temp;
+            dot = wave_sum(dot) / temp;
             if (lane == 0) L[w] = dot;
         }
         wave_lds_sync();
@@ -165,7 +160,7 @@ __global__ __launch_bounds__(256) void spot_kernel(const float* __restrict__ g, 
         mx = wmax(mx);
         float e = 0.f;
         for (int w = lane; w < W; w += 64) e += expf(L[w] - mx);
-        const float den = wsum(e);
+        const float den = wave_sum(e);
         const float a = expf(L[wt] - mx) / den;
         if (lane == 0) sA[t] = a;
         __builtin_amdgcn_wave_barrier();         // L is rewritten for the next frame
@@ -218,6 +213,12 @@ constexpr int AM_REG_W = 128;                // widest clip of the in-register f
 constexpr int AM_KEY_PITCH = SPOT_MAX_W;     // keys[clip][word]: the host cannot know sum W (the offsets are device arrays)
 
 size_t attn_matrix_key_elems(int n_clips) { return (size_t)n_clips * AM_KEY_PITCH; }
+// The arg-max key of a word: (fp32 bits of the probability << 32) | ~frame, so that a 64-bit max prefers the larger probability and then
+// the smaller frame; 0 = no frame yet.  (The pack is a macro: as a function, inlined or not, it changes the register allocation of both
+// attn_matrix_kernel instances.)
+#define ARGMAX_KEY(prob, frame) (((unsigned long long)__float_as_uint(prob) << 32) | (0xffffffffu - (frame)))
+__device__ __forceinline__ int32_t argmax_key_frame(unsigned long long key) { return (int32_t)(0xffffffffu - (unsigned)key); }
+__device__ __forceinline__ float argmax_key_prob(unsigned long long key) { return __uint_as_float((unsigned)(key >> 32)); }
 
 __device__ __forceinline__ bool attn_clip_ok(int T, int W, int max_frames) {
     return T > 0 && T <= SPOT_MAX_T && T <= max_frames && W > 0 && W <= SPOT_MAX_W;
@@ -230,7 +231,7 @@ __device__ __forceinline__ float row_rnorm(const float* __restrict__ row, int D,
         const f32x4 v = *reinterpret_cast<const f32x4*>(row + d);
         sq += v.x * v.x; sq += v.y * v.y; sq += v.z * v.z; sq += v.w * v.w;
     }
-    return 1.f / fmaxf(sqrtf(wsum(sq)), 1e-12f);
+    return 1.f / fmaxf(sqrtf(wave_sum(sq)), 1e-12f);
 }
 
 // rows r0, r0 + rstep, .. < npad of `rows`, columns k0 .. k0 + KC - 1, scaled by rinv[r], into dst[k][r] (pitch floats per k);
@@ -281,7 +282,7 @@ __device__ __forceinline__ void am_fold(f32x16 (&acc)[NT], f32x16 (&tot)[NT]) {
 }
 
 // Softmax over the clip's words for the wave's 32 frames (frame0 ..), as torch evaluates it: exp(x - max) / sum exp(x - max); then the
-// stores and the arg-max keys.  Accumulator layout: frame = lane & 31, word = 32 tile + (x & 3) + 8 (x >> 2) + 4 (lane >> 5).
+// stores and the arg-max keys.  Accumulator layout: frame = lane & 31, word = 32 tile + mfma32_row(x, lane >> 5).
 // TSTEP > 1: the four waves hold different words of the SAME frames and every wave of the workgroup makes this call.
 template <int NT, int TSTEP>
 __device__ __forceinline__ void am_finish(f32x16 (&acc)[NT], int tbase, int W, int T, int frame0, float temp, float* __restrict__ Aclip,
@@ -299,7 +300,7 @@ __device__ __forceinline__ void am_finish(f32x16 (&acc)[NT], int tbase, int W, i
 #pragma unroll
         for (int x = 0; x < 16; ++x) {
             acc[i][x] = acc[i][x] / temp;
-            if ((x & 3) + 8 * (x >> 2) < wl - i * TSTEP * 32) mx = fmaxf(mx, acc[i][x]);
+            if (mfma32_row(x, 0) < wl - i * TSTEP * 32) mx = fmaxf(mx, acc[i][x]);
         }
     mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
     if constexpr (TSTEP > 1) {
@@ -312,7 +313,7 @@ __device__ __forceinline__ void am_finish(f32x16 (&acc)[NT], int tbase, int W, i
     for (int i = 0; i < NT; ++i)
 #pragma unroll
         for (int x = 0; x < 16; ++x) {
-            const float e = (x & 3) + 8 * (x >> 2) < wl - i * TSTEP * 32 ? expf(acc[i][x] - mx) : 0.f;
+            const float e = mfma32_row(x, 0) < wl - i * TSTEP * 32 ? expf(acc[i][x] - mx) : 0.f;
             acc[i][x] = e;
             sum += e;
         }
@@ -330,7 +331,7 @@ __device__ __forceinline__ void am_finish(f32x16 (&acc)[NT], int tbase, int W, i
             float* Arow = Aclip ? Aclip + ((long)word0 * T + frame) : nullptr;
 #pragma unroll
             for (int x = 0; x < 16; ++x) {
-                const int roff = (x & 3) + 8 * (x >> 2);
+                const int roff = mfma32_row(x, 0);
                 const bool wok = roff < wl - i * TSTEP * 32;
                 const float p = acc[i][x] / sum;
                 if (Aclip && fok && wok) Arow[roff * T] = p;          // W T <= 2^23 elements per clip
@@ -343,7 +344,7 @@ __device__ __forceinline__ void am_finish(f32x16 (&acc)[NT], int tbase, int W, i
                     const unsigned mine = (unsigned)(bal >> (32 * h));
                     if (l31 == 0 && wok && mine) {
                         const unsigned first = frame0 + __ffs(mine) - 1;
-                        atomicMax(&kclip[word0 + roff], ((unsigned long long)__float_as_uint(m) << 32) | (0xffffffffu - first));
+                        atomicMax(&kclip[word0 + roff], ARGMAX_KEY(m, first));
                     }
                 }
             }
@@ -436,8 +437,8 @@ __global__ void attn_best_kernel(const int32_t* __restrict__ goff, const int32_t
     const bool ok = attn_clip_ok(T, W, max_frames);
     for (int w = threadIdx.x; w < W; w += blockDim.x) {
         const unsigned long long key = ok ? keys[(size_t)clip * AM_KEY_PITCH + w] : 0ull;
-        if (best_frame) best_frame[w0 + w] = key ? (int32_t)(0xffffffffu - (unsigned)key) : -1;
-        if (best_score) best_score[w0 + w] = key ? __uint_as_float((unsigned)(key >> 32)) : __builtin_nanf("");
+        if (best_frame) best_frame[w0 + w] = key ? argmax_key_frame(key) : -1;
+        if (best_score) best_score[w0 + w] = key ? argmax_key_prob(key) : __builtin_nanf("");
     }
 }
 
@@ -468,7 +469,7 @@ __global__ void asd_kernel(const float* __restrict__ q, const float* __restrict_
     const float* qr = q + (long)qi * D;
     float qs = 0.f;
     for (int d = lane; d < D; d += 64) qs += qr[d] * qr[d];
-    const float qn = sqrtf(wsum(qs));
+    const float qn = sqrtf(wave_sum(qs));
     const int c0 = coff[qi];
     int P = coff[qi + 1] - c0;
     P = P < 6 ? P : 6;
@@ -480,8 +481,8 @@ __global__ void asd_kernel(const float* __restrict__ q, const float* __restrict_
             const float* cr = cand + (long)(c0 + p) * D;
             float dot = 0.f, cs = 0.f;
             for (int d = lane; d < D; d += 64) { dot += qr[d] * cr[d]; cs += cr[d] * cr[d]; }
-            dot = wsum(dot);
-            const float cn = sqrtf(wsum(cs));
+            dot = wave_sum(dot);
+            const float cn = sqrtf(wave_sum(cs));
             sim[p] = dot / fmaxf(qn * cn, 1e-8f) / temp;
         }
     }

@@ -20,8 +20,86 @@ struct ConvRowMap {
     int* base;                // [NF + 1] scratch: exclusive prefix of the images' computed rows
     int* total;               // device word
 };
-constexpr int CONV1_ZHDR_WORDS = 64;        // header of conv1's zero-scan scratch: 32 words of zconst, then ...
-constexpr int CONV1_ROWSKIP_WORD = 32;      // ... the min over the launch's positions of conv2's position-independent leading rows (debug only)
+
+// ---- layouts that a writer and a reader share -------------------------------------------------------------------
+// Each is defined here once; the kernel (or host loop) that writes it and the ones that read it call the same function, and a
+// static_assert pins it to points worked out by hand from the formula in its comment.  (In the register-tight kernels a function is
+// written with the integer widths and the association of the address expression it stands for: see the overloads of x16t_row_off.)
+//
+// Tiled token plane x16t (N = 512 columns, row tiles of 128).  The residual stream of the fused transformer is one fp16 plane: in a
+// post-norm transformer the LayerNorm output is rounded to fp16 as the next GEMM's operand anyway, and carrying the residual at that
+// precision costs 1-5 % of the feature error (oracle/precision_families.py) for no extra bytes and no codec arithmetic.
+// The plane is stored in the MFMA fragment order of the 128x512 LN kernel:
+//   x16t element (m, n): R*65536 + (n>>6)*8192 + ((m&127)>>4)*1024 + ((n&63)>>4)*256 + (m&15)*16 + (n&15),  R = m>>7
+//        (a wave's 8-byte accesses of one (j, i) block are one contiguous 512 B; a 64-wide k-tile of a 128-row
+//         panel is one contiguous 16 KB -> the consumer GEMMs' LDS-DMA reads it with a_tiled addressing)
+constexpr int X16T_TILE = 65536;            // 128 rows x 512 columns
+constexpr int X16T_COLBLK = 8192;           // ... of which 128 rows x 64 columns (one k-tile of the consumer GEMMs)
+constexpr int X16T_ROWBLK = 1024;           // ... of which 16 rows x 64 columns
+constexpr int X16T_QUAD = 256;              // ... of which 16 rows x 16 columns, row-major (16 elements per row)
+__host__ __device__ __forceinline__ constexpr long x16t_row_off(long m) { return (m >> 7) * X16T_TILE + ((m & 127) >> 4) * X16T_ROWBLK + (m & 15) * 16; }
+__host__ __device__ __forceinline__ constexpr long x16t_row_off(int m) { return (long)(m >> 7) * X16T_TILE + ((m & 127) >> 4) * X16T_ROWBLK + (m & 15) * 16; }
+__host__ __device__ __forceinline__ constexpr long x16t_col_off(int n) { return (long)(n >> 6) * X16T_COLBLK + ((n & 63) >> 4) * X16T_QUAD + (n & 15); }
+__host__ __device__ __forceinline__ constexpr long x16t_index(long m, int n) { return x16t_row_off(m) + x16t_col_off(n); }
+static_assert(x16t_index(0, 0) == 0 && x16t_index(1, 1) == 17 && x16t_index(16, 16) == 1024 + 256, "x16t: rows of 16 inside a quad, quads, row blocks");
+static_assert(x16t_index(128, 64) == 65536 + 8192 && x16t_index(300, 500) == 2 * 65536 + 7 * 8192 + 2 * 1024 + 3 * 256 + 12 * 16 + 4, "x16t: tiles and column blocks");
+static_assert(x16t_row_off(300) == x16t_row_off(300L), "x16t: the two widths agree");
+
+// Entry of a compacted conv row map (ConvGeom::rowmap): the full output row (img*OH + oh)*OW + ow in the low 24 bits, the image's
+// count s2 (conv2's position-independent leading rows) above them.
+constexpr int ROWMAP_ROW_BITS = 24;
+constexpr int ROWMAP_MAX_ROWS = 1 << ROWMAP_ROW_BITS;       // full output rows of a launch: row < ROWMAP_MAX_ROWS
+constexpr int ROWMAP_MAX_S2 = 255;
+__host__ __device__ __forceinline__ constexpr int rowmap_entry(int row, int s2) { return row | (s2 << ROWMAP_ROW_BITS); }
+__host__ __device__ __forceinline__ constexpr int rowmap_row(int e) { return e & (ROWMAP_MAX_ROWS - 1); }
+__host__ __device__ __forceinline__ constexpr int rowmap_s2(int e) { return (int)((unsigned)e >> ROWMAP_ROW_BITS); }
+static_assert(rowmap_entry(5, 3) == 0x03000005 && rowmap_row(0x03000005) == 5 && rowmap_s2(0x03000005) == 3, "row map entry");
+static_assert(rowmap_row(rowmap_entry(ROWMAP_MAX_ROWS - 1, ROWMAP_MAX_S2)) == 0xffffff && rowmap_s2(rowmap_entry(ROWMAP_MAX_ROWS - 1, ROWMAP_MAX_S2)) == 255,
+              "row map entry: both limits survive the sign bit");
+
+// Accumulator of a 32x32 MFMA: register i of the lane half `half` (lane >> 5) holds row (i&3) + 8*(i>>2) + 4*half of column lane & 31.
+__host__ __device__ __forceinline__ constexpr int mfma32_row(int i, int half) { return (i & 3) + 8 * (i >> 2) + 4 * half; }
+static_assert(mfma32_row(0, 0) == 0 && mfma32_row(5, 1) == 13 && mfma32_row(15, 1) == 31, "32x32 accumulator rows");
+
+// LayerNorm partial sums part[row][nblk][2]: (sum, sum of squares) of the row's 64-column block blk, nblk = D / 64.
+__host__ __device__ __forceinline__ constexpr long ln_part_index(long row, int nblk, int blk) { return 2 * (row * nblk + blk); }
+static_assert(ln_part_index(0, 12, 1) == 2 && ln_part_index(3, 12, 5) == 82, "LayerNorm partial sums");
+
+// conv1's weight panel Wd[slot][ch][16] (49 pixel slots (kh, kw), 64 output channels, 16 halves: 5 frames x 3 colours and the pad
+// lane CONV1_BIAS_LANE, which the kernel feeds 1.0): the BN-folded weights, and on the pad lane of slots 0 / 1 the hi / lo halves
+// of the channel's bias.
+constexpr int CONV1_BIAS_LANE = 15;
+__host__ __device__ __forceinline__ constexpr long conv1_wd_index(int slot, int ch, int e) { return (long)(slot * 64 + ch) * 16 + e; }
+static_assert(conv1_wd_index(0, 0, CONV1_BIAS_LANE) == 15 && conv1_wd_index(1, 2, 3) == 1059 && conv1_wd_index(48, 63, 15) == 49 * 64 * 16 - 1, "conv1 weight panel");
+
+// conv1's zero-scan scratch (launch_conv1_scan writes it; launch_conv1_direct and the conv stack behind it read it), in 32-bit words:
+//   header of CONV1_ZHDR_WORDS: words 0..31 zconst (64 values of the 16-bit type: what conv1 gives over an all-zero patch), word
+//   CONV1_ROWSKIP_WORD the min over the launch's positions of s2 (debug only); then the frame masks [nclip*T], the position masks
+//   [nclip*P] and the per-position counts s2 [nclip*P] (conv2's position-independent leading rows), P = T + 2*pad - 4.
+constexpr int CONV1_ZHDR_WORDS = 64;
+constexpr int CONV1_ROWSKIP_WORD = 32;
+constexpr int CONV1_SCAN_MAX_PAD = 12;      // the scratch is sized for this pad (conv1_zmask_elems)
+struct Conv1Scan {
+    unsigned* z;                            // the scratch (may be null when only the sizes are asked for)
+    size_t frame_off, pos_off, s2_off, words;
+    void* zconst() const { return z; }
+    int* rowskip_min() const { return reinterpret_cast<int*>(z) + CONV1_ROWSKIP_WORD; }
+    unsigned* frame_mask() const { return z + frame_off; }
+    unsigned* pos_mask() const { return z + pos_off; }
+    int* s2() const { return reinterpret_cast<int*>(z + s2_off); }
+};
+inline Conv1Scan conv1_scan_view(unsigned* zscratch, int nclip, int T, int pad) {
+    Conv1Scan v;
+    v.z = zscratch;
+    v.frame_off = CONV1_ZHDR_WORDS;
+    v.pos_off = v.frame_off + (size_t)nclip * T;
+    v.s2_off = v.pos_off + (size_t)nclip * (T + 2 * pad - 4);
+    v.words = v.s2_off + (size_t)nclip * (T + 2 * pad - 4);
+    return v;
+}
+
+// blocks of 256 threads for a grid-stride loop over `total` items
+inline int grid_for(long total) { return (int)((total + 255) / 256 < 65536 * 4 ? (total + 255) / 256 : 65536 * 4); }
 
 enum { LN_STD = 0, LN_ANNOTATED = 1 };
 

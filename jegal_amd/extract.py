@@ -100,34 +100,42 @@ FRAME_ROW_BYTES = 480 * 3
 FRAME_BYTES = 270 * FRAME_ROW_BYTES
 
 
-class _MaskedPacker:
-    """Host side of the masked upload: the kept rows (>= row0) of every frame of a batch, back to back in a pinned buffer."""
+class _RowPacker:
+    """Host side of a packed-rows upload: of every (H, W, 3) frame of a batch only the rows from its first kept row on, back to back in a
+    pinned buffer (buf), with per frame the byte offset of its rows (offs) and the number the device kernel derives its first kept row
+    from (rows; what it means is the front end's business: _MaskedPacker, _SourcePacker)."""
 
-    def __init__(self, batch, T, pinned=True):
-        self.batch, self.T = batch, T
+    def __init__(self, batch, T, H, W, pinned=True):
+        self.batch, self.T, self.H, self.W = batch, T, int(H), int(W)
+        self.row_bytes = self.W * 3
         pin = (lambda t: t.pin_memory()) if pinned else (lambda t: t)        # pinned=False: host-logic tests without a GPU
-        self.buf = pin(torch.empty((batch * T * FRAME_BYTES,), dtype=torch.uint8))
-        self.row0 = pin(torch.zeros((batch * T,), dtype=torch.int32))
+        self.buf = pin(torch.empty((batch * T * self.H * self.row_bytes,), dtype=torch.uint8))
+        self.rows = pin(torch.zeros((batch * T,), dtype=torch.int32))
         self.offs = pin(torch.zeros((batch * T,), dtype=torch.int64))
         self.reset()
 
     def reset(self):
         self.n, self.used = 0, 0
 
-    def add(self, clip, row0):
-        """clip (T,270,480,3) uint8 whose rows < row0 are blank (not checked: they are simply not shipped); row0: int or (T,) ints."""
+    def _first_rows(self, rows):
+        """(T,) int64 per-frame numbers as the caller gave them -> the frames' first kept rows (0..H); ValueError if out of range"""
+        if rows.min() < 0 or rows.max() > self.H:
+            raise ValueError(f"row0 must be in 0..{self.H}")
+        return rows
+
+    def add(self, clip, first_row):
+        """clip (T,H,W,3) uint8; first_row: int or (T,) ints (rows above it are simply not shipped)."""
         clip = np.asarray(clip)
-        if clip.shape != (self.T, 270, 480, 3) or clip.dtype != np.uint8:
-            raise ValueError(f"clip must be uint8 ({self.T},270,480,3), got {clip.dtype} {clip.shape}")
+        if clip.shape != (self.T, self.H, self.W, 3) or clip.dtype != np.uint8:
+            raise ValueError(f"clip must be uint8 ({self.T},{self.H},{self.W},3), got {clip.dtype} {clip.shape}")
         if self.n >= self.batch:
             raise ValueError("batch is full")
-        r0 = np.broadcast_to(np.asarray(row0, np.int64), (self.T,))
-        if r0.min() < 0 or r0.max() > 270:
-            raise ValueError("row0 must be in 0..270")
+        rows = np.broadcast_to(np.asarray(first_row, np.int64), (self.T,))
+        r0 = self._first_rows(rows)
         f0 = self.n * self.T
-        kept = (270 - r0) * FRAME_ROW_BYTES
+        kept = (self.H - r0) * self.row_bytes
         offs = self.used + np.concatenate(([0], np.cumsum(kept)[:-1]))
-        self.row0.numpy()[f0:f0 + self.T] = r0
+        self.rows.numpy()[f0:f0 + self.T] = rows
         self.offs.numpy()[f0:f0 + self.T] = offs
         dst = self.buf.numpy()
         if (r0 == r0[0]).all():                                   # one strided copy for a clip with one mask height
@@ -140,48 +148,117 @@ class _MaskedPacker:
         self.n += 1
 
 
-class _SourcePacker:
+class _MaskedPacker(_RowPacker):
+    """Host side of the masked upload: the kept rows (>= row0) of every 270x480 crop of a batch -- what jg_unpack_masked consumes.
+    add(clip, row0): the rows < row0 of the clip are blank (not checked: they are simply not shipped)."""
+
+    def __init__(self, batch, T, pinned=True):
+        super().__init__(batch, T, 270, 480, pinned)
+        self.row0 = self.rows
+
+
+class _SourcePacker(_RowPacker):
     """Host side of the source-resolution upload: decoder-resolution frames (T,H,W,3) with their mask rows (mask_y = y2+15 per frame,
-    -1 = no face; inference_embs.py:255-270), only the rows BELOW each frame's mask packed back to back in a pinned buffer --
-    what jg_mask_resize_packed consumes."""
+    -1 = no face; inference_embs.py:255-270), only the rows BELOW each frame's mask -- what jg_mask_resize_packed consumes.
+    add(clip, mask_y): the clip is NOT masked, its rows 0..mask_y are simply not shipped."""
 
     def __init__(self, batch, T, H, W, pinned=True):
-        self.batch, self.T, self.H, self.W = batch, T, int(H), int(W)
-        self.row_bytes = self.W * 3
-        pin = (lambda t: t.pin_memory()) if pinned else (lambda t: t)
-        self.buf = pin(torch.empty((batch * T * self.H * self.row_bytes,), dtype=torch.uint8))
-        self.mask_y = pin(torch.zeros((batch * T,), dtype=torch.int32))
-        self.offs = pin(torch.zeros((batch * T,), dtype=torch.int64))
-        self.reset()
+        super().__init__(batch, T, H, W, pinned)
+        self.mask_y = self.rows
 
-    def reset(self):
-        self.n, self.used = 0, 0
-
-    def add(self, clip, mask_y):
-        """clip (T,H,W,3) uint8 source frames (NOT masked: the rows 0..mask_y are simply not shipped); mask_y int or (T,) ints."""
-        clip = np.asarray(clip)
-        if clip.shape != (self.T, self.H, self.W, 3) or clip.dtype != np.uint8:
-            raise ValueError(f"clip must be uint8 ({self.T},{self.H},{self.W},3), got {clip.dtype} {clip.shape}")
-        if self.n >= self.batch:
-            raise ValueError("batch is full")
-        my = np.broadcast_to(np.asarray(mask_y, np.int64), (self.T,))
-        if my.min() < -1:
+    def _first_rows(self, mask_y):
+        if mask_y.min() < -1:
             raise ValueError("mask_y must be >= -1 (-1: no face found)")
-        r0 = np.clip(my + 1, 0, self.H)
-        f0 = self.n * self.T
-        kept = (self.H - r0) * self.row_bytes
-        offs = self.used + np.concatenate(([0], np.cumsum(kept)[:-1]))
-        self.mask_y.numpy()[f0:f0 + self.T] = my
-        self.offs.numpy()[f0:f0 + self.T] = offs
-        dst = self.buf.numpy()
-        if (r0 == r0[0]).all():
-            n = int(kept[0])
-            dst[self.used:self.used + self.T * n].reshape(self.T, n)[:] = clip[:, int(r0[0]):].reshape(self.T, n)
+        return np.clip(mask_y + 1, 0, self.H)
+
+
+class _DenseUpload:
+    """Streamer transport: whole (T,270,480,3) crops through a pinned staging buffer; nothing to rebuild on the device."""
+
+    def __init__(self, st):
+        self.st = st
+        st.h_in = [torch.empty(st.d_in[0].shape, dtype=torch.uint8).pin_memory() for _ in range(2)]
+
+    def buffer(self, slot):
+        return self.st.h_in[slot].numpy()
+
+    def pack(self, it, slot, rows_it):
+        st, dst, n = self.st, self.buffer(slot), 0
+        for clip in it:
+            clip = np.asarray(clip)
+            if clip.shape != (st.T, 270, 480, 3) or clip.dtype != np.uint8:
+                raise ValueError(f"clip must be uint8 ({st.T},270,480,3), got {clip.dtype} {clip.shape}")
+            dst[n] = clip
+            n += 1
+            if n == st.batch:
+                break
+        return n
+
+    def upload(self, slot, n):
+        self.st.d_in[slot][:n].copy_(self.st.h_in[slot][:n], non_blocking=True)
+
+    def unpack(self, slot, n):
+        pass
+
+
+class _PackedUpload:
+    """Streamer transport: the kept rows of every frame through a _RowPacker; `rebuild` makes the dense batch from them on the device."""
+    no_mask = 0                               # what a clip without mask_rows gets: the whole frame is shipped
+
+    def __init__(self, st, packers):
+        self.st = st
+        st.packer = packers
+        dev, frames = st.eng.device, st.batch * st.T
+        self.d_packed = [torch.empty((pk.buf.numel(),), dtype=torch.uint8, device=dev) for pk in packers]
+        self.d_rows = [torch.empty((frames,), dtype=torch.int32, device=dev) for _ in range(2)]      # the packer's `rows`
+        self.d_offs = [torch.empty((frames,), dtype=torch.int64, device=dev) for _ in range(2)]
+        self.used = [0, 0]                    # packed bytes of the batch in each slot
+
+    def buffer(self, slot):
+        return self.st.packer[slot]
+
+    def pack(self, it, slot, rows_it):
+        pk = self.st.packer[slot]
+        pk.reset()
+        for clip in it:
+            pk.add(clip, self.no_mask if rows_it is None else next(rows_it))
+            if pk.n == self.st.batch:
+                break
+        return pk.n
+
+    def upload(self, slot, n):
+        pk, F = self.st.packer[slot], n * self.st.T
+        self.d_packed[slot][:pk.used].copy_(pk.buf[:pk.used], non_blocking=True)
+        self.d_rows[slot][:F].copy_(pk.rows[:F], non_blocking=True)
+        self.d_offs[slot][:F].copy_(pk.offs[:F], non_blocking=True)
+        self.used[slot] = pk.used
+
+    def unpack(self, slot, n):
+        F, used, dst = n * self.st.T, self.used[slot], self.st.d_in[slot][:n]
+        if used == 0:                         # every frame masked completely: nothing crossed the link
+            dst.zero_()
         else:
-            for t in range(self.T):
-                dst[offs[t]:offs[t] + kept[t]] = clip[t, int(r0[t]):].reshape(-1)
-        self.used += int(kept.sum())
-        self.n += 1
+            self.rebuild(self.d_packed[slot][:used], self.d_rows[slot][:F], self.d_offs[slot][:F], dst)
+
+
+class _MaskedUpload(_PackedUpload):
+    def __init__(self, st):
+        super().__init__(st, [_MaskedPacker(st.batch, st.T) for _ in range(2)])
+
+    def rebuild(self, packed, row0, offs, dst):
+        self.st.eng.unpack_masked(packed, row0, offs, dst)
+
+
+class _SourceUpload(_PackedUpload):
+    no_mask = -1
+
+    def __init__(self, st):
+        H, W = st.source_hw
+        super().__init__(st, [_SourcePacker(st.batch, st.T, H, W) for _ in range(2)])
+
+    def rebuild(self, packed, mask_y, offs, dst):
+        H, W = self.st.source_hw
+        self.st.eng.mask_resize_packed(packed, offs, mask_y, H, W, dst)
 
 
 class GestureStreamer:
@@ -220,52 +297,17 @@ class GestureStreamer:
         self.source_hw = None if source_hw is None else (int(source_hw[0]), int(source_hw[1]))
         dev = engine.device
         shape = (self.batch, self.T, 270, 480, 3)
-        if self.source_hw is not None:
-            H, W = self.source_hw
-            self.packer = [_SourcePacker(self.batch, self.T, H, W) for _ in range(2)]
-            self.d_packed = [torch.empty((self.batch * self.T * H * W * 3,), dtype=torch.uint8, device=dev) for _ in range(2)]
-            self.d_row0 = [torch.empty((self.batch * self.T,), dtype=torch.int32, device=dev) for _ in range(2)]      # mask_y here
-            self.d_offs = [torch.empty((self.batch * self.T,), dtype=torch.int64, device=dev) for _ in range(2)]
-        elif self.masked:
-            self.packer = [_MaskedPacker(self.batch, self.T) for _ in range(2)]
-            self.d_packed = [torch.empty((self.batch * self.T * FRAME_BYTES,), dtype=torch.uint8, device=dev) for _ in range(2)]
-            self.d_row0 = [torch.empty((self.batch * self.T,), dtype=torch.int32, device=dev) for _ in range(2)]
-            self.d_offs = [torch.empty((self.batch * self.T,), dtype=torch.int64, device=dev) for _ in range(2)]
-        else:
-            self.h_in = [torch.empty(shape, dtype=torch.uint8).pin_memory() for _ in range(2)]
         self.d_in = [torch.empty(shape, dtype=torch.uint8, device=dev) for _ in range(2)]
+        # how a batch crosses the host link: .packer (packed modes) or .h_in (dense) are the transport's
+        self.mode = _SourceUpload(self) if self.source_hw is not None else _MaskedUpload(self) if self.masked else _DenseUpload(self)
         self.d_out = [torch.empty((self.batch, self.T, 512), dtype=torch.float32, device=dev) for _ in range(2)]
         self.h_out = [torch.empty((self.batch, self.T, 512), dtype=torch.float32).pin_memory() for _ in range(2)]
         self.copy = torch.cuda.Stream(dev)          # H2D
         self.down = torch.cuda.Stream(dev)          # D2H: on its own stream, or upload k+1 would queue behind `wait computed k`
         self.compute = torch.cuda.Stream(dev)
-        self._used = [0, 0]                         # packed bytes of the batch in each slot
         self.uploaded = [torch.cuda.Event() for _ in range(2)]
         self.computed = [torch.cuda.Event() for _ in range(2)]
         self.downloaded = [torch.cuda.Event() for _ in range(2)]
-
-    def _pack(self, it, slot, rows_it=None):
-        """Fill pinned buffer `slot` from the iterator; returns the number of clips packed."""
-        n = 0
-        if self.masked:
-            pk = self.packer[slot]
-            pk.reset()
-            none = -1 if self.source_hw is not None else 0          # no mask given: the whole frame is shipped
-            for clip in it:
-                pk.add(clip, none if rows_it is None else next(rows_it))
-                if pk.n == self.batch:
-                    break
-            return pk.n
-        dst = self.h_in[slot].numpy()
-        for clip in it:
-            clip = np.asarray(clip)
-            if clip.shape != (self.T, 270, 480, 3) or clip.dtype != np.uint8:
-                raise ValueError(f"clip must be uint8 ({self.T},270,480,3), got {clip.dtype} {clip.shape}")
-            dst[n] = clip
-            n += 1
-            if n == self.batch:
-                break
-        return n
 
     def run(self, clips, mask_rows=None):
         """clips: iterable of (T,270,480,3) uint8 arrays (copied into the pinned staging buffers here).  masked streamer:
@@ -275,37 +317,16 @@ class GestureStreamer:
         rows_it = None if mask_rows is None else iter(mask_rows)
         if rows_it is not None and not self.masked:
             raise ValueError("mask_rows needs GestureStreamer(..., masked=True)")
-        return self.run_filled(lambda buf, k: self._pack(it, k & 1, rows_it))
+        return self.run_filled(lambda buf, k: self.mode.pack(it, k & 1, rows_it))
 
     def _upload(self, slot, n):
-        """H2D of batch `slot` on the copy stream.  The kernel that rebuilds the dense batch from the packed rows (_unpack) is NOT
+        """H2D of batch `slot` on the copy stream.  The kernel that rebuilds the dense batch from the packed rows (the mode's unpack) is NOT
         issued here: beside the persistent compute kernels of the previous batch it cost that batch 1.5-2.7 ms (its workgroups
         take CUs the one-workgroup-per-CU kernels were launched for), in front of its own batch on the compute stream it costs its
         stand-alone 1.0 ms (tools/stream_timeline.py: 15.3 -> 13.6 ms per streamed batch)."""
         with torch.cuda.stream(self.copy):
-            if self.masked:
-                pk = self.packer[slot]
-                F = n * self.T
-                self.d_packed[slot][:pk.used].copy_(pk.buf[:pk.used], non_blocking=True)
-                self.d_row0[slot][:F].copy_((pk.mask_y if self.source_hw is not None else pk.row0)[:F], non_blocking=True)
-                self.d_offs[slot][:F].copy_(pk.offs[:F], non_blocking=True)
-                self._used[slot] = pk.used
-            else:
-                self.d_in[slot][:n].copy_(self.h_in[slot][:n], non_blocking=True)
+            self.mode.upload(slot, n)
             self.uploaded[slot].record(self.copy)
-
-    def _unpack(self, slot, n):
-        """Packed rows -> dense (n,T,270,480,3) batch on the CURRENT (compute) stream: jg_mask_resize_packed / jg_unpack_masked."""
-        if not self.masked:
-            return
-        F, used = n * self.T, self._used[slot]
-        if used == 0:                            # every frame masked completely: nothing crossed the link
-            self.d_in[slot][:n].zero_()
-        elif self.source_hw is not None:
-            self.eng.mask_resize_packed(self.d_packed[slot][:used], self.d_offs[slot][:F], self.d_row0[slot][:F], self.source_hw[0],
-                                        self.source_hw[1], self.d_in[slot][:n])
-        else:
-            self.eng.unpack_masked(self.d_packed[slot][:used], self.d_row0[slot][:F], self.d_offs[slot][:F], self.d_in[slot][:n])
 
     def run_filled(self, fill):
         """fill(buffer, batch_index) -> number of clips written (0 = end), for producers (decoders) that can write their crops
@@ -313,7 +334,7 @@ class GestureStreamer:
         _MaskedPacker -- call reset() and add(clip, row0) per clip, or leave it as it is to re-send its content."""
         pending = []                      # (slot, first index, n) of batches whose embeddings are not yet returned
         first, k = 0, 0
-        buf = (lambda s_: self.packer[s_]) if self.masked else (lambda s_: self.h_in[s_].numpy())
+        buf = self.mode.buffer
         n = fill(buf(0), 0)
         while n > 0 or pending:
             slot = k & 1
@@ -321,7 +342,7 @@ class GestureStreamer:
                 self._upload(slot, n)
                 with torch.cuda.stream(self.compute):
                     self.compute.wait_event(self.uploaded[slot])
-                    self._unpack(slot, n)
+                    self.mode.unpack(slot, n)               # packed rows -> dense (n,T,270,480,3) batch, on the compute stream (see _upload)
                     self.eng.extract_gesture(self.d_in[slot][:n], self.d_out[slot][:n])
                     self.computed[slot].record(self.compute)
                 with torch.cuda.stream(self.down):
