@@ -102,8 +102,9 @@ int jg_set_chunk(jg_handle* h, int clips_per_chunk);
  *                     tools/experiments/stream_queue_sweep.sh)
  *   "xlmr_lanes"      2 (default), 1 .. 4: jg_xlmr_encode runs a batch as that many equal parts on as many streams (the first two are the
  *                     lane streams of "dual_stream" / "lane_priority")
- *   "ws_poison"       1 (test aid, default 0): the workspace is filled with 0xff bytes (fp16/fp32 NaN) before every clip chunk, so a
- *                     kernel that reads a row nobody wrote (the row / band skips leave rows unwritten on purpose) shows up as NaN
+ *   "ws_poison"       1 (test aid, default 0): the workspace is filled with 0xff bytes (fp16/fp32 NaN) before every pass -- every entry
+ *                     point that uses the workspace, every clip chunk of a long batch -- so a kernel that reads a row nobody wrote
+ *                     (the row / band skips leave rows unwritten on purpose) shows up as NaN
  *   "jegal_fp32_ends" 1 (default): the two ends of the JEGAL gesture branch (proj_ip_rgb; final norm + proj_op_rgb + proj_op_align_gesture) and
  *                     of the content path (proj_op_text, fusion / align MLPs) keep fp32 activations and run on the split-operand GEMM
  *                     (three fp16 MFMAs per tile: fp32-grade products); 0: the round-5 arithmetic (fp16 activations, hi+lo weights).  DESIGN.md section 3.
@@ -315,10 +316,13 @@ int jg_debug_rc_bias(jg_handle* h, const void* A, int64_t lda, int64_t a_elems, 
 int jg_debug_last_kernel(jg_handle* h, char* buf, int len);
 /* Check point for "conv2_row_skip": the MINIMUM over the positions of the last conv stack of the leading conv2 output rows that
  * were read from the const chain instead of computed (every position skips its own count: jg_debug_conv_rows);
- * 0: none, or the option is off.  Synchronises the stream. */
+ * 0: none, or the option is off.  The report describes the last conv stack of the LAST call on this handle: it reads 0 once another
+ * workspace pass has begun (any later call that uses the workspace) or the stream was switched (jg_set_stream).  Synchronises the stream. */
 int jg_debug_conv2_rowskip(jg_handle* h, int* rows);
 /* Check point for the per-position form of it: computed[l] / full[l] = output pixels (rows of the implicit GEMM) that conv2 .. conv5
- * (l = 0..3) of the LAST conv stack computed / would compute without the skip (0 / 0: option off or path not taken).  Synchronises. */
+ * (l = 0..3) of the LAST conv stack computed / would compute without the skip (0 / 0: option off or path not taken).  The same
+ * lifetime as jg_debug_conv2_rowskip: the last conv stack of the last call on this handle, 0 / 0 once another workspace pass has begun
+ * or the stream was switched.  Synchronises. */
 int jg_debug_conv_rows(jg_handle* h, int64_t* computed, int64_t* full);
 /* Tuning aid: ms per launch of the production GEMM for a shape (mode bit0 hi+lo weights, bit1 fp32 residual in/out, bit2 ReLU). */
 int jg_debug_gemm(jg_handle* h, int M, int N, int K, int mode, int iters, double* ms);

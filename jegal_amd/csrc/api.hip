@@ -179,7 +179,7 @@ int jg_destroy(jg_handle* h) {
 }
 const char* jg_last_error(jg_handle* h) { return h ? h->err.c_str() : "null handle"; }
 
-// The workspace arena is stream-ordered (every entry point resets and re-uses it), so it belongs to ONE stream: a handle that is
+// The workspace arena is stream-ordered (every entry point begins a pass at its start: begin_pass), so it belongs to ONE stream: a handle that is
 // driven from several streams -- e.g. JEGAL.forward_inference runs the content path on a side stream beside the gesture encoder --
 // keeps one arena per stream and switches with the stream.  (Before round 4 two calls on two un-synchronised streams shared one arena.)
 int jg_set_stream(jg_handle* h, void* s) {
@@ -193,7 +193,7 @@ int jg_set_stream(jg_handle* h, void* s) {
         h->ws_parked.erase(ns);
         // A caller cycling through many streams (a fresh torch.cuda.Stream per batch): at most 6 parked arenas (>= 1 GiB each, INTEGRATION.md
         // section 6) -- the LEAST RECENTLY used one goes, alone.  Its stream may no longer exist, so the device is synchronised rather
-        // than the stream (hipFree would wait for the device anyway); the debug pointers into a released arena are dropped with it.
+        // than the stream (hipFree would wait for the device anyway).
         while (h->ws_parked.size() > 6) {
             auto lru = h->ws_parked.begin();
             for (auto it = h->ws_parked.begin(); it != h->ws_parked.end(); ++it)
@@ -202,10 +202,9 @@ int jg_set_stream(jg_handle* h, void* s) {
             (void)hipDeviceSynchronize();
             lru->second.release();
             h->ws_parked.erase(lru);
-            h->last_rowskip = nullptr;                   // (they may point into the arena that was just released)
-            h->last_conv_totals = nullptr;
         }
         h->stream = ns;
+        h->conv_report.clear();                          // it described a pass of the arena that was just parked (or released)
     }
     return JG_OK;
 }
@@ -372,7 +371,7 @@ int jg_gestsync_windows(jg_handle* h, const float* x, int N, float* out, float* 
 int jg_jegal_gestures(jg_handle* h, const float* feats, const float* mask, int B, int T, int align, float* out) {
     ENTER(h);
     if (!feats || !out) JG_FAIL(h, JG_ERR_ARG, "null buffer");
-    h->ws.reset();
+    RET(begin_pass(h));
     return jegal_gestures_impl(h, feats, mask, B, T, align, out);
 }
 
@@ -386,7 +385,7 @@ int jg_jegal_audio(jg_handle* h, const float* mel, int B, int Tm, float* out) { 
 int jg_jegal_audio_ragged(jg_handle* h, const float* mel, int B, int Tm, const int32_t* valid_tm_host, float* out) {
     ENTER(h);
     if (!mel || !out) JG_FAIL(h, JG_ERR_ARG, "null buffer");
-    h->ws.reset();
+    RET(begin_pass(h));
     return jegal_audio_impl(h, mel, B, Tm, valid_tm_host, out);
 }
 
@@ -421,7 +420,7 @@ int jg_logmel(jg_handle* h, const float* wav, int B, int n_samples, const float*
 int jg_jegal_text(jg_handle* h, const float* states, const float* mask, int B, int L, float* out) {
     ENTER(h);
     if (!states || !out) JG_FAIL(h, JG_ERR_ARG, "null buffer");
-    h->ws.reset();
+    RET(begin_pass(h));
     return jegal_text_impl(h, states, mask, B, L, out);
 }
 
@@ -432,9 +431,7 @@ int jg_xlmr_encode(jg_handle* h, const int32_t* input_ids, const int32_t* attent
     // GEMMs are single rounds of 192 tiles on 256 CUs and qkv is 2.25 rounds -- two half batches on two streams let one lane's
     // kernels start on the CUs the other's last round leaves idle.
     auto run_part = [&](int b0, int nb) -> int {
-        h->ws.reset();
-        if (h->ws_poison)                       // test aid: whatever a kernel reads without having written it is NaN
-            for (auto& c : h->ws.chunks) HIPCHK(h, launch_poison(c.p, c.cap, h->stream));
+        RET(begin_pass(h));
         return xlmr_encode_impl(h, input_ids + (size_t)b0 * L, attention_mask ? attention_mask + (size_t)b0 * L : nullptr, nb, L,
                                 out + (size_t)b0 * L * 768);
     };
@@ -450,7 +447,7 @@ int jg_word_pool(jg_handle* h, const float* seq, int D, const int32_t* seg, int 
 int jg_fuse_content(jg_handle* h, const float* fused, int rows, float* out) {
     ENTER(h);
     if (!fused || !out) JG_FAIL(h, JG_ERR_ARG, "null buffer");
-    h->ws.reset();
+    RET(begin_pass(h));
     return fuse_content_impl(h, fused, rows, out);
 }
 
@@ -479,8 +476,8 @@ int jg_extract_gesture(jg_handle* h, const void* frames, int dtype, int B, int T
         const char* fr = reinterpret_cast<const char*>(frames) + (size_t)b0 * T * FH * FW * 3 * esz;
         float* feats = h->feats + (size_t)b0 * T * 1024;
         float* emb = out_emb + (size_t)b0 * T * 512;
+        // one pass for both stages: gestsync_clip_impl begins it, the JEGAL stage goes on allocating behind the last chunk's buffers
         RET(gestsync_clip_impl(h, fr, dtype, nb, T, feats));
-        h->ws.reset();
         RET(jegal_gestures_impl(h, feats, nullptr, nb, T, 1, emb));
         return timed(h, JG_ST_MISC, [&] { return launch_l2norm(emb, emb, nb * T, 512, h->stream); });
     };
@@ -520,12 +517,8 @@ int jg_attn_matrix(jg_handle* h, const float* g, const float* c, const int32_t* 
     if ((reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(c)) & 15) JG_FAIL(h, JG_ERR_ARG, "gesture / content must be 16-byte aligned");
     if (n == 0) return JG_OK;
     unsigned long long* keys = nullptr;          // per-word arg-max keys, combined across the frame blocks of a clip
-    if (best_frame || best_score) {
-        h->ws.reset();
-        RET(wsalloc(h, attn_matrix_key_elems(n), &keys));
-        if (h->ws_poison)                       // test aid: whatever a kernel reads without having written it is NaN
-            for (auto& ch : h->ws.chunks) HIPCHK(h, launch_poison(ch.p, ch.cap, h->stream));
-    }
+    RET(begin_pass(h));
+    if (best_frame || best_score) RET(wsalloc(h, attn_matrix_key_elems(n), &keys));
     return timed(h, JG_ST_MISC, [&] {
         return launch_attn_matrix(g, c, goff, coff, n, D, max_frames, temp, normalize, A, aoff, keys, best_frame, best_score, h->stream);
     });

@@ -35,7 +35,7 @@ GemmArgs gemm_check_args(const jg_gemm_check* c) {
 bool al(const void* p, unsigned bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
 // a host [n] int32 array as the device array the launchers take, in the handle's workspace (as jg_debug_maxpool does for s2)
 int upload_valid(jg_handle* h, const int32_t* host, int n, int32_t** dev) {
-    h->ws.reset();
+    RET(begin_pass(h));
     RET(wsalloc(h, (size_t)n, dev));
     return upload_i32_async(h, host, (size_t)n, *dev);
 }
@@ -49,9 +49,9 @@ int jg_debug_conv2_rowskip(jg_handle* h, int* rows) {
     ENTER(h);
     if (!rows) JG_FAIL(h, JG_ERR_ARG, "rows is NULL");
     *rows = 0;
-    if (!h->last_rowskip) return JG_OK;
+    if (!h->conv_report.rowskip) return JG_OK;
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipMemcpy(rows, h->last_rowskip, sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(rows, h->conv_report.rowskip, sizeof(int), hipMemcpyDeviceToHost));
     return JG_OK;
 }
 
@@ -59,11 +59,11 @@ int jg_debug_conv_rows(jg_handle* h, int64_t* computed, int64_t* full) {
     ENTER(h);
     if (!computed || !full) JG_FAIL(h, JG_ERR_ARG, "null buffer");
     for (int l = 0; l < 4; ++l) computed[l] = full[l] = 0;
-    if (!h->last_conv_totals) return JG_OK;
+    if (!h->conv_report.totals) return JG_OK;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     int t[4];
-    HIPCHK(h, hipMemcpy(t, h->last_conv_totals, sizeof(t), hipMemcpyDeviceToHost));
-    for (int l = 0; l < 4; ++l) { computed[l] = t[l]; full[l] = h->last_conv_full[l]; }
+    HIPCHK(h, hipMemcpy(t, h->conv_report.totals, sizeof(t), hipMemcpyDeviceToHost));
+    for (int l = 0; l < 4; ++l) { computed[l] = t[l]; full[l] = h->conv_report.full[l]; }
     return JG_OK;
 }
 
@@ -72,7 +72,7 @@ int jg_debug_conv1_pool(jg_handle* h, const void* frames_u8, int B, int T, int p
     if (!h->gs.m.ready) JG_FAIL(h, JG_ERR_STATE, "GestSync weights not finalized");
     if (!frames_u8 || !out_f16 || B <= 0 || pad < 0 || pad > 12 || T + 2 * pad < 5)      // conv1's skip-mask area is sized for pad <= 12
         JG_FAIL(h, JG_ERR_ARG, "bad arguments (need 0 <= pad <= 12 and T + 2*pad >= 5)");
-    h->ws.reset();
+    RET(begin_pass(h));
     const long sw = 3, sh = (long)FW * 3, st = (long)FH * FW * 3, sb = (long)T * st;
     unsigned* zscr;
     return gs_conv1_stage(h, frames_u8, 1, sb, st, sh, sw, 1, B, T, pad, static_cast<f16*>(out_f16), true, &zscr);
@@ -89,7 +89,7 @@ int jg_debug_gemm(jg_handle* h, int M, int N, int K, int mode, int iters, double
 int jg_debug_gemm_ex(jg_handle* h, const void* a16, const void* w16, int M, int N, int K, int mode, int iters, double* ms) {
     if (!h || !ms || M <= 0 || N <= 0 || K <= 0 || iters <= 0) return JG_ERR_ARG;
     ENTER(h);
-    h->ws.reset();
+    RET(begin_pass(h));
     f16 *A, *Wh, *Wl, *o16;
     float *bias, *x32;
     RET(wsalloc(h, (size_t)M * K, &A));
@@ -191,7 +191,7 @@ int jg_debug_conv_check(jg_handle* h, const jg_conv_check* c) {
         q.set_geom(g);
         q.rowmap = true; q.const_in = c->const_in != nullptr;
         if (!plan_gemm(q, o).ok()) JG_FAIL(h, JG_ERR_ARG, "launch_gemm: the launcher rejects this shape / argument set");
-        h->ws.reset();
+        RET(begin_pass(h));
         int32_t* s2;
         ConvRowMap rm;
         const f16* const cin = static_cast<const f16*>(c->const_in);
@@ -215,7 +215,7 @@ int jg_debug_maxpool(jg_handle* h, const void* in, int nimg, int H, int W, int C
         for (int i = 0; i < nimg; ++i)
             if (s2_host[i] < 0 || s2_host[i] > ROWMAP_MAX_S2 || conv_skip_decode(s2_host[i], in_op) > H)
                 JG_FAIL(h, JG_ERR_ARG, "jg_debug_maxpool: s2[%d] = %d outside 0..255 or past the image's %d rows", i, s2_host[i], H);
-        h->ws.reset();
+        RET(begin_pass(h));
         RET(wsalloc(h, (size_t)nimg, &s2));
         RET(upload_i32_async(h, s2_host, (size_t)nimg, s2));
     }
@@ -237,14 +237,14 @@ int jg_debug_conv_rowmaps(jg_handle* h, const int32_t* s2_host, int NF, const in
             if (s2_host[i] < 0 || s2_host[i] > ROWMAP_MAX_S2 || conv_skip_decode(s2_host[i], l) > OH[l])
                 JG_FAIL(h, JG_ERR_ARG, "jg_debug_conv_rowmaps: s2[%d] = %d outside 0..255 or past layer %d's %d rows", i, s2_host[i], l, OH[l]);
     }
-    h->ws.reset();
+    RET(begin_pass(h));
     int32_t* s2;
     ConvRowMap rm[4];
     RET(wsalloc(h, (size_t)NF, &s2));
     RET(rowmap_chain(h, NF, nlayers, OH, OW, 0, rm));
     RET(upload_i32_async(h, s2_host, (size_t)NF, s2));
-    for (int l = 0; l < nlayers; ++l)      // the caller's fill: the launch writes the first *total entries only
-        HIPCHK(h, hipMemcpy(rm[l].map, map_host[l], (size_t)NF * OH[l] * OW[l] * sizeof(int), hipMemcpyHostToDevice));
+    for (int l = 0; l < nlayers; ++l)      // the caller's fill: the launch writes the first *total entries only (on the stream: behind the pass's poison)
+        HIPCHK(h, hipMemcpyAsync(rm[l].map, map_host[l], (size_t)NF * OH[l] * OW[l] * sizeof(int), hipMemcpyHostToDevice, h->stream));
     const int rc = check_result(h, launch_conv_rowmaps(s2, NF, rm, nlayers, h->stream), "launch_conv_rowmaps");
     if (rc != JG_OK) return rc;
     record_kernel(h->kname, "%s", "conv_rowmap_scan_kernel+conv_rowmap_fill_kernel");

@@ -49,6 +49,19 @@ hipError_t launch_l2norm(const float* in, float* out, int rows, int D, hipStream
     return hipGetLastError();
 }
 
+// Test aid (option ws_poison, begin_pass): 0xff bytes -- fp16 / fp32 NaN -- over a workspace chunk
+namespace {
+__global__ void poison_kernel(uint4* __restrict__ p, size_t n16) {
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n16; i += (size_t)gridDim.x * blockDim.x) p[i] = make_uint4(~0u, ~0u, ~0u, ~0u);
+}
+}  // namespace
+
+hipError_t launch_poison(void* p, size_t bytes, hipStream_t s) {
+    if (!p || bytes < 16) return hipSuccess;
+    hipLaunchKernelGGL(poison_kernel, dim3(4096), dim3(256), 0, s, reinterpret_cast<uint4*>(p), bytes / 16);
+    return hipGetLastError();
+}
+
 // ---------------------------------------------------------------------------------------------
 // XLM-RoBERTa front end (third-party transformers.XLMRobertaModel, call site jegal.py:116-129).
 // Embeddings: word[id] + position[pid] + token_type[0], pid = padding_idx + (number of non-pad tokens up to and including

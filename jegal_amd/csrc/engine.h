@@ -75,7 +75,7 @@ struct Arena {          // stream-ordered bump allocator over persistent chunks
     struct Chunk { char* p; size_t cap; };
     std::vector<Chunk> chunks;
     size_t cur = 0, off = 0;
-    void reset() { cur = 0; off = 0; }
+    void reset() { cur = 0; off = 0; }     // begin_pass, and nobody else: what else a pass's beginning means is decided there
     unsigned long tick = 0;         // jg_set_stream: when this arena was last parked (least recently used goes first)
     size_t total() const { size_t t = 0; for (auto& c : chunks) t += c.cap; return t; }
     void* alloc(size_t bytes, hipError_t* err) {
@@ -92,7 +92,17 @@ struct Arena {          // stream-ordered bump allocator over persistent chunks
         cur = chunks.size() - 1; off = bytes;
         return p;
     }
-    void release() { for (auto& c : chunks) (void)hipFree(c.p); chunks.clear(); reset(); }
+    void release() { for (auto& c : chunks) (void)hipFree(c.p); chunks.clear(); cur = off = 0; }
+};
+
+// What the last conv stack on this handle did (jg_debug_conv2_rowskip, jg_debug_conv_rows).  The two device words lie in the workspace of
+// the pass that ran the stack, so the report lives exactly as long as that pass: gs_conv_stack fills it, begin_pass and a switch of
+// streams (jg_set_stream) clear it.
+struct ConvReport {
+    const int* rowskip = nullptr;       // device word: min over the stack's positions of conv2's row skip
+    const int* totals = nullptr;        // device [4]: rows conv2 .. conv5 computed
+    long full[4] = {0, 0, 0, 0};        // ... of these many
+    void clear() { *this = ConvReport(); }
 };
 
 struct ProfRec { int stage; hipEvent_t e0, e1; };
@@ -153,11 +163,9 @@ struct jg_handle {
     bool edge_dedup = true;        // skip the 16 duplicated edge positions of a padded clip
     bool conv1_direct = true;      // fused u8 conv1 kernel (false: stack_frames + implicit GEMM)
     bool qkv0_linear = true;       // layer-0 qkv projection over the distinct conv positions + gather in the attention kernel
-    bool ws_poison = false;        // option "ws_poison": fill the workspace with 0xff before every clip chunk (tests)
+    bool ws_poison = false;        // option "ws_poison": fill the workspace with 0xff before every pass (begin_pass; tests)
     bool conv2_row_skip = true;    // conv2 leaves out the leading output rows that the zero-band scan proves to be copies of one row
-    const int* last_rowskip = nullptr;   // device word: min over the last conv stack's positions of conv2's row skip (jg_debug_conv2_rowskip)
-    const int* last_conv_totals = nullptr;   // device [4]: rows conv2 .. conv5 of the last conv stack computed (jg_debug_conv_rows)
-    long last_conv_full[4] = {0, 0, 0, 0};   // ... of these many
+    engine::ConvReport conv_report;
     std::map<std::string, engine::HostTensor> host;
     EngineOpts opts;               // per-handle tuning switches + per-device resources (shared.h)
     char kname[KNAME_LEN] = {0};   // instance the last kernel check point launched (jg_debug_last_kernel)
@@ -305,6 +313,18 @@ int wsalloc(jg_handle* h, size_t n, T** out) {
     void* p = h->ws.alloc(n * sizeof(T), &e);
     if (!p) JG_FAIL(h, JG_ERR_HIP, "workspace allocation of %zu bytes failed: %s", n * sizeof(T), hipGetErrorString(e));
     *out = reinterpret_cast<T*>(p);
+    return JG_OK;
+}
+
+// Where a workspace pass begins, and the only place: the arena is handed out from its start again, so what pointed into it is void (the
+// conv report), and with option ws_poison every chunk is filled with 0xff (fp16 / fp32 NaN) on the handle's stream, in front of the pass's
+// kernels -- whatever one of them reads without having written it is NaN, not the previous identical run's value.  The stages of
+// one call share one pass (jg_extract_gesture: the JEGAL stage allocates behind the last GestSync chunk's buffers).
+inline int begin_pass(jg_handle* h) {
+    h->ws.reset();
+    h->conv_report.clear();
+    if (h->ws_poison)
+        for (auto& c : h->ws.chunks) HIPCHK(h, launch_poison(c.p, c.cap, h->stream));
     return JG_OK;
 }
 

@@ -149,8 +149,6 @@ static int gs_conv_stack(jg_handle* h, const void* src, int src_u8, long sb, lon
     const long NF = (long)nclip * P;
     f16 *p1, *o2, *o3, *o4, *o5, *p5;
     const int* s2pos = nullptr;          // per-position row-skip counts (direct path with conv2_row_skip)
-    h->last_rowskip = nullptr;
-    h->last_conv_totals = nullptr;
     ConvGeom g[5];
     gs_conv_geoms(g);
     RET(wsalloc(h, (size_t)NF * 43 * 78 * 64, &p1));
@@ -182,12 +180,12 @@ static int gs_conv_stack(jg_handle* h, const void* src, int src_u8, long sb, lon
         int OH[4], OW[4];
         for (int l = 0; l < 4; ++l) {
             OH[l] = g[l + 1].OH; OW[l] = g[l + 1].OW;
-            h->last_conv_full[l] = NF * OH[l] * OW[l];
+            h->conv_report.full[l] = NF * OH[l] * OW[l];
         }
         RET(rowmap_chain(h, NF, 4, OH, OW, 0, rm, g + 1, cin));
         RET(timed(h, JG_ST_CONV1_AUX, [&] { return launch_conv_rowmaps(s2pos, (int)NF, rm, 4, h->stream); }));
-        h->last_conv_totals = rm[0].total;
-        h->last_rowskip = conv1_scan_view(zscr, nclip, T, pad).rowskip_min();
+        h->conv_report.totals = rm[0].total;
+        h->conv_report.rowskip = conv1_scan_view(zscr, nclip, T, pad).rowskip_min();
     }
     Epi e;
     e.relu = 1;
@@ -377,9 +375,7 @@ int gestsync_clip_impl(jg_handle* h, const void* frames, int dtype, int B, int T
     const int chunk = (am & AUD_CONV) ? std::min(h->chunk, 2) : h->chunk;
     for (int b0 = 0; b0 < B; b0 += chunk) {
         const int nb = std::min(chunk, B - b0);
-        h->ws.reset();
-        if (h->ws_poison)                       // test aid: whatever a kernel reads without having written it is NaN
-            for (auto& c : h->ws.chunks) HIPCHK(h, launch_poison(c.p, c.cap, h->stream));
+        RET(begin_pass(h));
         float* conv;
         RET(wsalloc(h, (size_t)nb * P * 512, &conv));
         const char* src = reinterpret_cast<const char*>(frames) + (size_t)b0 * sb * esz;
@@ -434,7 +430,7 @@ int gestsync_windows_impl(jg_handle* h, const float* x, int N, float* out, float
     const int wchunk = (am & AUD_CONV) ? 16 : std::max(1, h->chunk * 8);      // (fp32 conv stack: 0.26 GB per window)
     for (int n0 = 0; n0 < N; n0 += wchunk) {
         const int nb = std::min(wchunk, N - n0);
-        h->ws.reset();
+        RET(begin_pass(h));
         float* conv;
         RET(wsalloc(h, (size_t)nb * S * 512, &conv));
         if (am & AUD_CONV) RET(gs_conv_stack32(h, x + (size_t)n0 * sb, 0, sb, st, sh, sw, sc, nb, 25, 0, conv));

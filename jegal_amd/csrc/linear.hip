@@ -414,7 +414,7 @@ int calibrate_gesture(jg_handle* h, const void* frames, int dtype, int B, int T,
             if (hipMemcpy(feats, hf.data(), hf.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return JG_ERR_HIP;
         }
         if (!h->jg.m.ready) return JG_OK;
-        h->ws.reset();
+        RET(begin_pass(h));
         return jegal_gestures_impl(h, feats, nullptr, B, T, 1, emb);
     });
 }
@@ -446,7 +446,7 @@ int calibrate_xlmr(jg_handle* h, const int32_t* ids_dev, const int32_t* mask_dev
         float* out = nullptr;
         if (hipMalloc(&out, (size_t)B * L * 768 * sizeof(float)) != hipSuccess) JG_FAIL(h, JG_ERR_HIP, "hipMalloc failed");
         bufs.push_back(out);
-        h->ws.reset();
+        RET(begin_pass(h));
         return xlmr_encode_impl(h, ids_dev, mask_dev, B, L, out);
     });
 }

@@ -147,6 +147,10 @@ hipError_t launch_conv_rowmaps(const int* s2, int NF, const ConvRowMap* layers, 
 size_t conv1_edge_elems(long positions);
 hipError_t launch_transpose_tokens(const float* in, int N, int L, int D, float* out, hipStream_t s);
 hipError_t launch_l2norm(const float* in, float* out, int rows, int D, hipStream_t s);
+// Test aid (option ws_poison): fill with 0xff bytes (fp16 / fp32 NaN) by a kernel of our own on the stream -- NOT hipMemsetAsync: two 1-GiB
+// hipMemsetAsync fills running concurrently on two streams were observed to overlap the kernels enqueued BEHIND them on their own stream
+// (tools/experiments/xlmr_race/xl_poison_probe.py, round 6)
+hipError_t launch_poison(void* p, size_t bytes, hipStream_t s);
 hipError_t launch_xlmr_embed(const int32_t* ids, int B, int L, int D, int pad_id, int vocab, int maxpos, const float* word, const float* pos,
                              const float* type, float* out, hipStream_t s);
 // part [rows][P][2] (sum, sum of squares per 64-column block, P = D / 64) -> stats [rows][2] = (mean, 1 / sqrt(var_biased + 1e-5))

@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import jegal_oracle as O
+import test_gpu_workspace_pass as WP
 from jegal_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -138,6 +139,13 @@ def test_audit_ragged_audio_and_long_sequences(fp32, oracle_sd):
     with torch.no_grad():
         rt = O.jegal_forward_text(jsd, st, tm.unsqueeze(1))
     assert rel(ft, rt) < AUD_TOL, rel(ft, rt)
+
+
+@pytest.mark.parametrize("name", WP.JEGAL_SMALL)
+def test_audit_jegal_entries_are_reproducible_under_a_poisoned_workspace(fp32, name):
+    """The fp32 forms of the JEGAL entry points read nothing their pass has not written (tests/test_gpu_workspace_pass.py has the cases)."""
+    e, _, _ = fp32
+    WP.assert_reproducible_under_poison(e, WP.CASES[name]())
 
 
 def test_audit_xlmr_against_transformers_golden(golden_dir):
