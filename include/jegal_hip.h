@@ -394,6 +394,24 @@ int jg_pool_mean(jg_handle* h, const float* x, const int32_t* offsets, int n, in
 /* evaluate_retrieval.py:38-65 on already-normalised rows: rank/ties of the diagonal per local row */
 int jg_sim_rank(jg_handle* h, const float* e1, const float* e2, int n_local, int n_total, int row_offset, int D,
                 int32_t* rank, int32_t* ties);
+/* Retrieval itself, without the similarity matrix.  For each query row i, the k gallery rows with the largest s_ij = <queries[i], gallery[j]>
+ * (rows as stored: the caller normalises, as for jg_sim_rank), best first.  idx / score: [n_queries][k], device.
+ * s_ij is computed exactly as jg_sim_rank computes it (exact-fp32 MFMA, one k-ascending chain per element), so a score depends on its two
+ * rows alone and is bit-identical to the value jg_sim_rank compares; -0.0 is treated (and returned) as +0.0.  The order is total: larger
+ * score first, on equal scores the smaller gallery index first (np.argsort(-s, kind="stable")).  idx holds gallery_offset + j, score[i][r]
+ * is s_ij bit for bit.  A NaN score is never selected; when fewer than k candidates exist (n_gallery < k, NaN scores) the remaining slots
+ * are idx = -1, score = -inf.
+ * merge == 0: idx and score are outputs only, their previous contents are never read.  merge != 0: idx and score hold the result of earlier
+ * jg_sim_topk calls with the same queries and k for OTHER gallery rows (slots with idx < 0 are empty) and the call leaves the best k of the
+ * union in the same total order -- a gallery cut into pieces, in any order, gives the bits of one call over the whole gallery (galleries
+ * larger than device memory, gallery-sharded ranks).  If the index ranges gallery_offset .. gallery_offset + n_gallery - 1 of merged calls
+ * overlap, or idx / score hold anything but such a result, the result is unspecified.
+ * Limits: 1 <= k <= 128; D > 0, D % 64 == 0; n_queries >= 0, n_gallery >= 0; gallery_offset >= 0, gallery_offset + n_gallery <= INT32_MAX;
+ * queries and gallery 16-byte aligned.  A violated limit or a null buffer returns JG_ERR_ARG before anything is enqueued.  n_queries == 0
+ * returns JG_OK and launches nothing; n_gallery == 0 without merge fills -1 / -inf.  Nothing outside the n_queries * k entries of idx and
+ * score is written; no workspace is used.  Asynchronous. */
+int jg_sim_topk(jg_handle* h, const float* queries, const float* gallery, int n_queries, int n_gallery, int D, int k,
+                int gallery_offset, int merge, int32_t* idx, float* score);
 /* evaluate_spotting.py:39-82: per clip first-argmax frame and its softmax score for word `target`.
  * Limits per clip: <= 1024 words, <= 8192 frames, 0 <= target < words.  The offsets are device arrays (no host sync to
  * validate them): a clip outside the limits gets pred = -1 and score = NaN instead of a result. */

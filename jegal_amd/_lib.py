@@ -110,6 +110,7 @@ _SIGS = {
     "jg_extract_gesture": [_P, _P, _I, _I, _I, _P],
     "jg_pool_mean": [_P, _P, _P, _I, _I, _P],
     "jg_sim_rank": [_P, _P, _P, _I, _I, _I, _I, _P, _P],
+    "jg_sim_topk": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P],
     "jg_spot": [_P, _P, _P, _P, _P, _P, _I, _I, ctypes.c_float, _P, _P],
     "jg_attn_matrix": [_P, _P, _P, _P, _P, _I, _I, _I, ctypes.c_float, _I, _P, _P, _P, _P],
     "jg_asd": [_P, _P, _P, _P, _I, _I, ctypes.c_float, _P],
@@ -750,6 +751,39 @@ class Engine:
         ties = torch.empty(n_local, dtype=torch.int32, device=self.device)
         self._ck(self.lib.jg_sim_rank(self.h, _ptr(e1), _ptr(e2), n_local, e2.shape[0], row_offset, D, _ptr(rank), _ptr(ties)))
         return rank, ties
+
+    def sim_topk(self, queries, gallery, k, gallery_offset=0, merge_into=None):
+        """jg_sim_topk: per query row the k gallery rows with the largest <q_i, g_j> (rows as stored: normalise first, as for sim_rank), best
+        first; on equal scores the smaller gallery row first.  queries (n, D) / gallery (m, D), D % 64 == 0, 1 <= k <= 128.
+        Returns (idx (n, k) int32 = gallery_offset + j, score (n, k) float32) as device tensors; slots beyond the candidates are -1 / -inf.
+        merge_into = (idx, score) of an earlier call with the same queries and k on OTHER gallery rows: the two are updated in place to the
+        best k of the union and returned (a gallery too large for the device goes through in pieces, each with its gallery_offset)."""
+        qs, gs = tuple(queries.shape), tuple(gallery.shape)
+        if len(qs) != 2 or len(gs) != 2 or qs[1] != gs[1] or qs[1] <= 0 or qs[1] % 64:
+            raise ValueError("queries / gallery must be (rows, D) with the same D, a positive multiple of 64")
+        k, gallery_offset = int(k), int(gallery_offset)
+        if not 1 <= k <= 128:
+            raise ValueError("jg_sim_topk limit: 1 <= k <= 128")
+        if gallery_offset < 0 or gallery_offset + gs[0] > 2 ** 31 - 1:
+            raise ValueError("gallery_offset must be >= 0 and gallery_offset + gallery rows <= INT32_MAX")
+        if merge_into is not None:
+            if not isinstance(merge_into, (tuple, list)) or len(merge_into) != 2 or not all(isinstance(t, torch.Tensor) for t in merge_into):
+                raise ValueError("merge_into must be the (idx, score) pair of an earlier sim_topk call")
+            idx, score = merge_into
+            if (tuple(idx.shape) != (qs[0], k) or tuple(score.shape) != (qs[0], k) or idx.dtype != torch.int32 or score.dtype != torch.float32
+                    or not idx.is_contiguous() or not score.is_contiguous()):
+                raise ValueError(f"merge_into must be contiguous (idx int32, score float32) tensors of shape ({qs[0]}, {k})")
+            if idx.device != self.device or score.device != self.device:
+                raise ValueError(f"merge_into must be on {self.device}")
+        self._bind_stream()
+        q, g = self._f32(queries), self._f32(gallery)
+        if merge_into is None:
+            idx = torch.full((qs[0], k), -1, dtype=torch.int32, device=self.device)
+            score = torch.full((qs[0], k), float("-inf"), dtype=torch.float32, device=self.device)
+        if qs[0] and gs[0]:                            # (no gallery row: nothing to merge, or the empty result above)
+            self._ck(self.lib.jg_sim_topk(self.h, _ptr(q), _ptr(g), qs[0], gs[0], qs[1], k, gallery_offset, int(merge_into is not None),
+                                          _ptr(idx), _ptr(score)))
+        return idx, score
 
     def spot(self, gesture, content, g_offsets, c_offsets, targets, temp=0.07):
         self._bind_stream()

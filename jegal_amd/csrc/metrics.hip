@@ -105,6 +105,168 @@ hipError_t launch_sim_rank(const float* e1, const float* e2, int n_local, int n_
 }
 
 // ---------------------------------------------------------------------------------------------
+// Top-k retrieval: for each query row the k gallery rows with the largest <q_i, g_j>, best first, without the similarity matrix.
+// The tile loop is sim_rank_kernel's, statement for statement (same staging order, one k-ascending MFMA chain per element), so a score
+// is bit-identical to the value jg_sim_rank compares.  A candidate is the 64-bit key (order-preserving bits of the score << 32) | ~index:
+// keys of distinct gallery rows are distinct and totally ordered (larger score first, then the smaller index), so "the k largest keys of
+// a set" does not depend on the order of arrival, nor on how the gallery is cut into calls.  Key 0 = empty slot (no number has it).
+//
+// Per query row in LDS: LCAP >= k keys sorted descending (sL), the k-th of them as the threshold (sThr), and a queue of this tile's
+// survivors (sQ, 64 slots = the tile's 64 columns, so it cannot overflow; it lies over the staging buffers, which are dead between the
+// last MFMA of a tile and the staging of the next).  After every tile a wave takes 16 rows and inserts the queued keys of each one by one:
+// the list lives in the wave's registers (position = lane, lane + 64), an insertion is one compare and a shift by one lane.
+using u64 = unsigned long long;
+__device__ __forceinline__ unsigned topk_ord(float s) {          // fp32 -> unsigned, order-preserving; -0.0 counts as +0.0
+    const unsigned b = __float_as_uint(s);
+    return b == 0x80000000u ? 0x80000000u : (b & 0x80000000u) ? ~b : b | 0x80000000u;
+}
+__device__ __forceinline__ float topk_score(u64 key) {
+    const unsigned o = (unsigned)(key >> 32);
+    return key ? __uint_as_float((o & 0x80000000u) ? o ^ 0x80000000u : ~o) : -INFINITY;
+}
+__device__ __forceinline__ int32_t topk_index(u64 key) { return key ? (int32_t)(0xffffffffu - (unsigned)key) : -1; }
+__device__ __forceinline__ u64 topk_key(float s, unsigned index) { return ((u64)topk_ord(s) << 32) | (0xffffffffu - index); }
+__device__ __forceinline__ u64 topk_readlane(u64 v, int src) {   // src: wave-uniform
+    const unsigned lo = __builtin_amdgcn_readlane((int)(unsigned)v, src), hi = __builtin_amdgcn_readlane((int)(unsigned)(v >> 32), src);
+    return ((u64)hi << 32) | lo;
+}
+
+// the wave's 16 rows: queued keys into the sorted lists, new thresholds, queues emptied
+template <int LCAP>
+__device__ __forceinline__ void topk_flush(u64 (*sL)[LCAP], const u64 (*sQ)[64], int* sCnt, u64* sThr, int k, int wave, int lane) {
+    for (int rr = 0; rr < 16; ++rr) {
+        const int row = wave * 16 + rr;
+        const int n = __builtin_amdgcn_readfirstlane(sCnt[row]);
+        if (n == 0) continue;
+        const u64 cand = lane < n ? sQ[row][lane] : 0ull;
+        u64 e0 = sL[row][lane], e1 = 0ull;
+        if constexpr (LCAP == 128) e1 = sL[row][64 + lane];
+        u64 kth = sThr[row];
+        for (int i = 0; i < n; ++i) {
+            const u64 c = topk_readlane(cand, i);
+            if (c < kth) continue;                               // an earlier insertion of this tile has raised the threshold past it
+            // position p keeps its key if that beats c; else it takes c if the key before it beats c, else the key before it
+            u64 p0 = __shfl_up(e0, 1, 64);
+            if (lane == 0) p0 = ~0ull;
+            if constexpr (LCAP == 128) {
+                u64 p1 = __shfl_up(e1, 1, 64);
+                const u64 last0 = topk_readlane(e0, 63);
+                if (lane == 0) p1 = last0;
+                e1 = e1 > c ? e1 : (p1 > c ? c : p1);
+            }
+            e0 = e0 > c ? e0 : (p0 > c ? c : p0);
+            kth = topk_readlane(LCAP == 128 && k > 64 ? e1 : e0, (k - 1) & 63);
+        }
+        sL[row][lane] = e0;
+        if constexpr (LCAP == 128) sL[row][64 + lane] = e1;
+        if (lane == 0) { sThr[row] = kth; sCnt[row] = 0; }
+    }
+}
+
+template <int LCAP>
+__global__ __launch_bounds__(256) void sim_topk_kernel(const float* __restrict__ e1, const float* __restrict__ e2, int n_queries,
+                                                       int n_gallery, int D, int k, int gallery_offset, int merge,
+                                                       int32_t* __restrict__ idx, float* __restrict__ score) {
+    __shared__ __attribute__((aligned(16))) u64 sStage[64 * 64];       // staging (sA, sB) during a tile's k loop, the queues after it
+    __shared__ u64 sL[64][LCAP];
+    __shared__ u64 sThr[64];
+    __shared__ int sCnt[64];
+    float (*sA)[64] = reinterpret_cast<float (*)[64]>(sStage);         // [k][query row]
+    float (*sB)[64] = sA + 64;                                         // [k][gallery row]
+    u64 (*sQ)[64] = reinterpret_cast<u64 (*)[64]>(sStage);             // [query row][slot]
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wr = wave & 1, wc = wave >> 1;
+    const int i0 = blockIdx.x * 64;
+    const int r = tid & 63, kq = tid >> 6;
+
+    // the lists start empty, or (merge) from the caller's earlier result: sorted, empty slots (idx < 0) last
+    for (int rr = 0; rr < 16; ++rr) {
+        const int row = wave * 16 + rr;
+        const long base = (long)(i0 + row) * k;
+        u64 kth = 0ull;
+#pragma unroll
+        for (int p = lane; p < LCAP; p += 64) {
+            u64 key = 0ull;
+            if (merge && p < k && i0 + row < n_queries) {
+                const int32_t j = idx[base + p];
+                const float s = score[base + p];
+                if (j >= 0 && s == s) key = topk_key(s, (unsigned)j);
+            }
+            sL[row][p] = key;
+            if (p == k - 1) kth = key;
+        }
+        if (lane == ((k - 1) & 63)) sThr[row] = kth;
+        if (lane == 0) sCnt[row] = 0;
+    }
+
+    const int ntiles = (n_gallery + 63) / 64;
+    for (int tile = 0; tile < ntiles; ++tile) {
+        const int j0 = tile * 64;
+        f32x16 acc;
+#pragma unroll
+        for (int x = 0; x < 16; ++x) acc[x] = 0.f;
+        for (int k0 = 0; k0 < D; k0 += 64) {
+            __syncthreads();
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int kk = kq * 16 + q * 4;
+                f32x4 va = {0.f, 0.f, 0.f, 0.f}, vb = va;
+                if (i0 + r < n_queries) va = *reinterpret_cast<const f32x4*>(e1 + (long)(i0 + r) * D + k0 + kk);
+                if (j0 + r < n_gallery) vb = *reinterpret_cast<const f32x4*>(e2 + (long)(j0 + r) * D + k0 + kk);
+                sA[kk][r] = va.x; sA[kk + 1][r] = va.y; sA[kk + 2][r] = va.z; sA[kk + 3][r] = va.w;
+                sB[kk][r] = vb.x; sB[kk + 1][r] = vb.y; sB[kk + 2][r] = vb.z; sB[kk + 3][r] = vb.w;
+            }
+            __syncthreads();
+#pragma unroll 8
+            for (int kk = 0; kk < 64; kk += 2) {
+                const float a = sA[kk + (lane >> 5)][wr * 32 + (lane & 31)];
+                const float b = sB[kk + (lane >> 5)][wc * 32 + (lane & 31)];
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0);
+            }
+        }
+        __syncthreads();                                         // the staging buffers become the queues
+        // D layout: col = lane & 31 (gallery), row = mfma32_row(x, lane >> 5) (query)
+        const int j = j0 + wc * 32 + (lane & 31);
+        const bool jok = j < n_gallery;
+        const unsigned gj = (unsigned)gallery_offset + (unsigned)j;
+#pragma unroll
+        for (int x = 0; x < 16; ++x) {
+            const int row = wr * 32 + mfma32_row(x, lane >> 5);
+            const u64 key = topk_key(acc[x], gj);
+            if (jok && acc[x] == acc[x] && i0 + row < n_queries && key > sThr[row])      // a NaN is never a candidate
+                sQ[row][atomicAdd(&sCnt[row], 1)] = key;
+        }
+        __syncthreads();
+        topk_flush<LCAP>(sL, sQ, sCnt, sThr, k, wave, lane);
+    }
+    // a wave stores the lists of the rows it seeded and flushed itself, each row as one contiguous run
+    for (int rr = 0; rr < 16; ++rr) {
+        const int row = wave * 16 + rr;
+        if (i0 + row >= n_queries) break;
+        const long base = (long)(i0 + row) * k;
+        for (int p = lane; p < k; p += 64) {
+            const u64 key = sL[row][p];
+            idx[base + p] = topk_index(key);
+            score[base + p] = topk_score(key);
+        }
+    }
+}
+
+hipError_t launch_sim_topk(const float* queries, const float* gallery, int n_queries, int n_gallery, int D, int k, int gallery_offset,
+                           int merge, int32_t* idx, float* score, hipStream_t s) {
+    if (n_queries <= 0) return hipSuccess;
+    if (D <= 0 || D % 64 || k < 1 || k > SIM_TOPK_MAX_K || n_gallery < 0 || gallery_offset < 0 || gallery_offset > INT32_MAX - n_gallery)
+        return hipErrorInvalidValue;
+    const dim3 grid((n_queries + 63) / 64);
+    if (k <= 64)
+        hipLaunchKernelGGL(sim_topk_kernel<64>, grid, dim3(256), 0, s, queries, gallery, n_queries, n_gallery, D, k, gallery_offset, merge, idx, score);
+    else
+        hipLaunchKernelGGL(sim_topk_kernel<128>, grid, dim3(256), 0, s, queries, gallery, n_queries, n_gallery, D, k, gallery_offset, merge, idx, score);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
 // Word spotting (evaluate_spotting.py:39-82): per clip A = softmax((G C^T)/temp, dim=1) over words
 // with re-normalised rows; pred = first argmax_t A[t][w*], score = A[pred][w*].
 // One block per clip, one wave per frame row; the W logits of a row go through a per-wave LDS line.

@@ -164,6 +164,11 @@ inline bool rc_bias_ok(int N, int K, int tiled) { return (K == 512 || K == 2048)
 hipError_t launch_ragged_mean(const float* x, const int32_t* offsets, int n, int D, float* out, hipStream_t s);
 hipError_t launch_sim_rank(const float* e1, const float* e2, int n_local, int n_total, int row_offset, int D,
                            int32_t* rank, int32_t* ties, hipStream_t s);
+// per query row the k <= SIM_TOPK_MAX_K best gallery rows (idx = gallery_offset + j, best first; -1 / -inf where there are fewer); merge:
+// idx / score hold an earlier result for other gallery rows and the best k of the union are left.  No scratch.
+constexpr int SIM_TOPK_MAX_K = 128;
+hipError_t launch_sim_topk(const float* queries, const float* gallery, int n_queries, int n_gallery, int D, int k, int gallery_offset,
+                           int merge, int32_t* idx, float* score, hipStream_t s);
 hipError_t launch_spot(const float* g, const float* c, const int32_t* goff, const int32_t* coff, const int32_t* target,
                        int n, int D, float temp, int32_t* pred, float* score, hipStream_t s);
 // A (optional; with aoff, int64 element offsets per clip) and / or best_frame / best_score (optional; they need keys: attn_matrix_key_elems(n)

@@ -7,6 +7,7 @@
     python -m jegal_amd.drivers evaluate_asd --path D --file avs_asd.csv   # evaluation/evaluate_asd.py
     python -m jegal_amd.drivers inference_embs ...            # inference_embs.py (single clip -> <fname>.pkl)
     python -m jegal_amd.drivers attn_matrix --path F|D        # utils/plot_heatmap.py without the rendering (-> <name>.attn.npz)
+    python -m jegal_amd.drivers retrieve --path D [--topk 10] # the retrieval evaluate_retrieval.py grades (-> retrieve_<direction>.npz)
 
 Same flags, file naming and on-disk formats as the reference.  What is upstream of the hot path is
 NOT rebuilt: video decoding / mediapipe masking (the drivers read already masked 270x480 crops as
@@ -494,8 +495,49 @@ def cmd_attn_matrix(argv, engine=None):
     return 0
 
 
+RETRIEVE_DIRECTIONS = {"c2g": ("Content to Gesture", "content_emb", "gesture_emb"), "g2c": ("Gesture to Content", "gesture_emb", "content_emb")}
+
+
+def cmd_retrieve(argv, engine=None):
+    """The retrieval that evaluate_retrieval only grades: for every clip of a directory of feature .pkl files (loaded, pooled and sharded as
+    evaluate_retrieval does) the --topk best clips of the other modality.  Rank 0 writes ``<res_dir>/retrieve_<direction>.npz`` = {names (N,):
+    the .pkl base names = the gallery order, idx (N,K) int32 gallery rows best first (-1 where N < K), score (N,K) float32, rank (N,)
+    int32: jg_sim_rank's rank of the clip's own partner from the same normalised rows}.  engine: the Engine to run on (default: this
+    process's)."""
+    from . import metrics as M
+    p = argparse.ArgumentParser(prog="retrieve")
+    p.add_argument("--path", required=True, help="a directory of JEGAL feature .pkl files")
+    p.add_argument("--topk", type=int, default=10, help="gallery clips kept per query (1..128)")
+    p.add_argument("--direction", default="both", choices=["c2g", "g2c", "both"])
+    p.add_argument("--res_dir", default=".")
+    args = p.parse_args(argv)
+    if not 1 <= args.topk <= 128:
+        raise SystemExit("--topk must be 1..128")
+    eng = engine if engine is not None else _models(args)[0]
+    files, feats = _load_pkls(args.path)
+    if not feats:
+        raise SystemExit("no .pkl under {}".format(args.path))
+    names = np.asarray([os.path.basename(f)[:-len(".pkl")] for f in files])
+    lo, hi = jdist.shard_range(len(feats))
+    pooled = {key: M.video_level(eng, [f[key] for f in feats[lo:hi]]) for key in ("gesture_emb", "content_emb")}
+    res = {}
+    for d in (["c2g", "g2c"] if args.direction == "both" else [args.direction]):
+        title, qk, gk = RETRIEVE_DIRECTIONS[d]
+        idx, score = M.retrieve(pooled[qk], pooled[gk], k=args.topk, engine=eng)
+        rank = M.partner_ranks(pooled[qk], pooled[gk], engine=eng)
+        res[d] = dict(names=names, idx=idx, score=score, rank=rank)
+        if jdist.rank() == 0:
+            os.makedirs(args.res_dir, exist_ok=True)
+            out = os.path.join(args.res_dir, "retrieve_{}.npz".format(d))
+            np.savez(out, **res[d])
+            print("{} retrieval: top-{} of {} clips, own partner ranked under {} for {} -> {}".format(
+                title, args.topk, len(names), args.topk, int(np.sum(rank < args.topk)), out))
+    return 0
+
+
 COMMANDS = {
     "attn_matrix": cmd_attn_matrix,
+    "retrieve": cmd_retrieve,
     "extract_gestsync_feats": cmd_extract_gestsync_feats,
     "extract_jegal_embs": cmd_extract_jegal_embs,
     "evaluate_retrieval": cmd_evaluate_retrieval,

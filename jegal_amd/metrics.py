@@ -61,6 +61,34 @@ def retrieval_metrics(emb1, emb2, engine=None):
     return metrics_from_ranks(rank.flatten().cpu().numpy(), ties.flatten().cpu().numpy())
 
 
+def retrieve(emb_q, emb_g, k=10, engine=None):
+    """The retrieval itself: for each row of the query set emb_q the k rows of the gallery emb_g with the largest cosine similarity, best
+    first, ties to the smaller gallery row (both (N,512), un-normalised video-level means, as for retrieval_metrics).  The scores are the
+    ones retrieval_metrics ranks by, bit for bit (jg_sim_topk next to jg_sim_rank); the N x N matrix is never written.  Sharded like
+    retrieval_metrics when torch.distributed is initialised: every rank passes ITS contiguous block of both sets, the gallery is
+    all-gathered, each rank runs its queries and the results are gathered in rank order.
+    Returns host arrays (idx (N,k) int32: global gallery rows, -1 where the gallery has fewer than k; score (N,k) float32)."""
+    eng = engine or Engine.get()
+    q = eng.l2norm(_tensor(emb_q))
+    g = eng.l2norm(_tensor(emb_g))
+    g, _ = jdist.all_gather_rows(g)                  # (a single process: the rows themselves)
+    idx, score = eng.sim_topk(q, g, k)
+    idx, _ = jdist.all_gather_rows(idx)
+    score, _ = jdist.all_gather_rows(score)
+    return _host(idx), _host(score)
+
+
+def partner_ranks(emb1, emb2, engine=None):
+    """jg_sim_rank's rank of every query's own partner (row i of emb1 belongs to row i of emb2), the number retrieval_metrics turns into
+    R@K: host int32 (N,), over all ranks' rows in rank order when sharded."""
+    eng = engine or Engine.get()
+    e1 = eng.l2norm(_tensor(emb1))
+    gallery, row_offset = jdist.all_gather_rows(eng.l2norm(_tensor(emb2)))
+    rank, _ = eng.sim_rank(e1, gallery, row_offset)
+    rank, _ = jdist.all_gather_rows(rank.to(torch.int32).reshape(-1, 1))
+    return _host(rank).reshape(-1).astype(np.int32)
+
+
 def reduce_counts(counts, device=None):
     """Sum a short list of integer counters over the ranks (spotting / ASD need only this): every rank evaluates ITS
     contiguous block of clips (jdist.shard_range) and the totals are all-reduced -- RCCL on device tensors under nccl, host
