@@ -437,6 +437,37 @@ int jg_attn_matrix(jg_handle* h, const float* gesture, const float* content, con
 /* evaluate_asd.py:43-51,94-100: pred (n,3) = argmax over the first 2/4/6 candidates */
 int jg_asd(jg_handle* h, const float* query, const float* cand, const int32_t* c_offsets, int n, int D, float temp, int32_t* pred);
 
+/* ASD itself, per time window (the arithmetic of evaluate_asd.py:26-51, load_feats + get_similarity_cos, applied to the rows of a window):
+ * which of a scene's candidate tracks gestures to the utterance, with what probability, and when.  All pointers are device pointers.
+ *   gesture (sum T, D) fp32: frame-level rows of n_tracks tracks, g_offsets [n_tracks + 1] their row offsets;
+ *   content (sum W, D) fp32: word-level rows of n_scenes utterances, c_offsets [n_scenes + 1]; word_start / word_end [sum W]: inclusive
+ *     frame bounds of every word on the scene's frame axis (info["word_boundaries"]); both may be NULL when win == 0;
+ *   trk [sum P], s_offsets [n_scenes + 1]: scene i's candidates are the tracks trk[s_offsets[i] : s_offsets[i + 1]] (indices into
+ *     g_offsets); a track may be a candidate of many scenes and more than once in one.  Frame t of a scene is row t of each of its tracks;
+ *   win, hop: window j covers frames lo = j hop .. hi = lo + win - 1; win == 0: one window over every frame and every word (clip-level ASD;
+ *     hop ignored);  w_offsets [n_scenes + 1]: scene i owns pred rows w_offsets[i] .. w_offsets[i + 1] - 1 (n_win_i windows, the caller's
+ *     choice);  p_offsets [n_scenes] int64: ELEMENT offset of the scene's (n_win_i, P_i) block in prob / cosv (caller-chosen, gaps allowed);
+ *     max_windows >= every n_win_i sizes the grid.
+ * Per window: q = mean of the content rows of the words with word_end >= lo and word_start <= hi; candidate p is PRESENT if its track has
+ * a frame in [lo, hi], g_p = mean of those frames; cos_p = <q, g_p> / max(|q| |g_p|, 1e-8); prob = softmax(cos / temp) over the present
+ * candidates, evaluated as exp(x - max) / sum; pred = first arg-max, an index into the scene's candidate list.  An absent candidate gets
+ * prob 0 and cosv NaN.  A window without a word or without a present candidate is UNDECIDED: pred -1, its prob and cosv rows NaN.
+ * Outputs: prob fp32 (n_win_i, P_i) row-major at p_offsets[i]; cosv the same layout, optional (NULL); pred int32 [w_offsets[n_scenes]].
+ * Determinism: a window's cosv, prob and pred are a function of its own rows, added in ascending row order, and of nothing else -- not of
+ * hop, of the window's place in its workgroup, of the scene's place in the batch or of the other scenes.  The same [lo, hi] reached through
+ * different (hop, j) gives the same bits; win == 0 gives the bits of one window with win >= the longest track; a track listed twice gives
+ * bit-equal columns and the tie goes to the first.
+ * Limits per scene: 1..64 candidates, 1..1024 words, tracks of 1..8192 frames, 1..max_windows windows, trk entries inside 0..n_tracks-1.
+ * The offsets are device arrays: a scene outside the limits is undecided in ALL of its windows, none of its rows is read, and the other
+ * scenes are computed normally.  Bad arguments return JG_ERR_ARG before anything is enqueued: null operands, D <= 0, D % 64, D > 1024,
+ * win < 0, win > 8192, hop < 1 with win > 0, temp <= 0, max_windows outside 1..8192, win > 0 without word bounds, gesture / content not
+ * 16-byte aligned.  n_scenes == 0 returns JG_OK and launches nothing.  Nothing outside the described elements is written; no workspace
+ * is used.  Asynchronous. */
+int jg_asd_windows(jg_handle* h, const float* gesture, const int32_t* g_offsets, int n_tracks, const float* content, const int32_t* c_offsets,
+                   const int32_t* word_start, const int32_t* word_end, const int32_t* trk, const int32_t* s_offsets, int n_scenes, int D,
+                   int win, int hop, const int32_t* w_offsets, const int64_t* p_offsets, int max_windows, float temp,
+                   float* prob, float* cosv /* may be NULL */, int32_t* pred);
+
 /* ---- multi-GPU exchange.  The reference is single-process (its only parallelism is the --rank / --nshard file-list split of
  *      preprocess/extract_gestsync_feats.py:366-370); clips shard with no data-path collective, and the ONE exchange of the path is the
  *      gallery all-gather in front of the retrieval similarity matrix (+ a counter all-reduce for R@K / spotting / ASD).  These entries give a

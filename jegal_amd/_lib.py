@@ -114,6 +114,7 @@ _SIGS = {
     "jg_spot": [_P, _P, _P, _P, _P, _P, _I, _I, ctypes.c_float, _P, _P],
     "jg_attn_matrix": [_P, _P, _P, _P, _P, _I, _I, _I, ctypes.c_float, _I, _P, _P, _P, _P],
     "jg_asd": [_P, _P, _P, _P, _I, _I, ctypes.c_float, _P],
+    "jg_asd_windows": [_P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _I, ctypes.c_float, _P, _P, _P],
     "jg_comm_get_unique_id": [ctypes.c_char_p],
     "jg_comm_init": [_P, ctypes.c_char_p, _I, _I],
     "jg_comm_destroy": [_P],
@@ -844,6 +845,71 @@ class Engine:
         pred = torch.empty((n, 3), dtype=torch.int32, device=self.device)
         self._ck(self.lib.jg_asd(self.h, _ptr(q), _ptr(c), _ptr(co), n, q.shape[-1], temp, _ptr(pred)))
         return pred
+
+    def asd_windows(self, gesture, g_offsets, content, c_offsets, trk, s_offsets, win=0, hop=1, n_windows=None, word_start=None,
+                    word_end=None, temp=0.07, want_cos=False):
+        """jg_asd_windows: per scene and time window the probability that each candidate track gestures to the utterance, and the winner.
+        gesture (sum T, D): frame rows of the tracks, g_offsets their n_tracks + 1 row offsets; content (sum W, D): word rows of the scenes'
+        utterances, c_offsets (n + 1); trk / s_offsets (n + 1): scene i's candidates are the tracks trk[s_offsets[i] : s_offsets[i + 1]]; all
+        offsets are HOST arrays.  win == 0: one window per scene over every frame and word (clip-level ASD).  win > 0: window j covers frames
+        j hop .. j hop + win - 1, word_start / word_end (sum W) are the words' inclusive frame bounds, and scene i gets n_windows[i]
+        windows (default: ceil(its longest candidate track / hop)).
+        Returns (prob, p_offsets, pred, w_offsets, cosv | None): scene i's probabilities are prob[p_offsets[i] : p_offsets[i + 1]].reshape(
+        n_win_i, P_i) (cosv likewise, with want_cos), its winners pred[w_offsets[i] : w_offsets[i + 1]]; prob / cosv / pred are device tensors,
+        the offsets host int64.  A window without a word or without a frame of any candidate reads pred -1 and NaN; a candidate without
+        a frame in a decided window prob 0 and cosv NaN."""
+        goh, coh, soh = (np.asarray(a, np.int64).reshape(-1) for a in (g_offsets, c_offsets, s_offsets))
+        tk = np.asarray(trk, np.int64).reshape(-1)
+        n, n_tracks = soh.size - 1, goh.size - 1
+        if n < 0 or n_tracks < 0 or coh.size != n + 1:
+            raise ValueError("c_offsets / s_offsets need the same number of entries (scenes + 1), g_offsets tracks + 1")
+        win, hop = int(win), int(hop)
+        if not 0 <= win <= 8192 or (win and hop < 1):
+            raise ValueError("jg_asd_windows limits: win 0 (clip level) or 1..8192 frames, hop >= 1")
+        if not temp > 0:
+            raise ValueError("temp must be positive")
+        gs, cs = tuple(gesture.shape), tuple(content.shape)
+        if len(gs) != 2 or len(cs) != 2 or gs[1] != cs[1] or gs[1] <= 0 or gs[1] % 64 or gs[1] > 1024:
+            raise ValueError("gesture / content must be (rows, D) with the same D, a positive multiple of 64, at most 1024")
+        T, W, P = np.diff(goh), np.diff(coh), np.diff(soh)
+        if goh[0] < 0 or coh[0] < 0 or soh[0] < 0 or gs[0] < goh[-1] or cs[0] < coh[-1] or tk.size < soh[-1]:
+            raise ValueError("offsets must lie inside gesture / content / trk")
+        if n and (P.min() < 1 or P.max() > 64 or W.min() < 1 or W.max() > 1024):
+            raise ValueError("jg_asd_windows limits: 1..64 candidates and 1..1024 words per scene")
+        used = tk[soh[0]:soh[-1]]
+        if used.size and (used.min() < 0 or used.max() >= n_tracks or T[used].min() < 1 or T[used].max() > 8192):
+            raise ValueError("jg_asd_windows limits: candidates must be existing tracks of 1..8192 frames")
+        if win:
+            if word_start is None or word_end is None:
+                raise ValueError("windows need word_start / word_end")
+            wsh, weh = (np.asarray(a, np.int64).reshape(-1) for a in (word_start, word_end))
+            if wsh.size < coh[-1] or weh.size != wsh.size or (n and max(np.abs(wsh).max(), np.abs(weh).max()) >= 2 ** 31):
+                raise ValueError("word_start / word_end need one int32 entry per content row")
+            if n_windows is None:
+                n_windows = [-(-int(T[tk[soh[i]:soh[i + 1]]].max()) // hop) for i in range(n)]
+        elif n_windows is None:
+            n_windows = np.ones(n, np.int64)
+        nw = np.asarray(n_windows, np.int64).reshape(-1)
+        if nw.size != n or (n and (nw.min() < 1 or nw.max() > 8192)):
+            raise ValueError("jg_asd_windows limits: 1..8192 windows per scene, one count per scene")
+        w_off, p_off = np.zeros(n + 1, np.int64), np.zeros(n + 1, np.int64)
+        w_off[1:], p_off[1:] = np.cumsum(nw), np.cumsum(nw * P)
+        if w_off[-1] >= 2 ** 31:
+            raise ValueError("more than 2^31 windows in one call")
+        self._bind_stream()
+        prob = torch.full((int(p_off[-1]),), float("nan"), dtype=torch.float32, device=self.device)
+        cosv = torch.full((int(p_off[-1]),), float("nan"), dtype=torch.float32, device=self.device) if want_cos else None
+        pred = torch.full((int(w_off[-1]),), -1, dtype=torch.int32, device=self.device)
+        if n == 0:
+            return prob, p_off, pred, w_off, cosv
+        g, c = self._f32(gesture), self._f32(content)
+        go, co, so, tr, wo = (self._i32(a) for a in (goh, coh, soh, tk, w_off))
+        ws = self._i32(wsh) if win else None
+        we = self._i32(weh) if win else None
+        po = torch.as_tensor(p_off[:-1].copy(), device=self.device)
+        self._ck(self.lib.jg_asd_windows(self.h, _ptr(g), _ptr(go), n_tracks, _ptr(c), _ptr(co), _ptr(ws), _ptr(we), _ptr(tr), _ptr(so), n,
+                                         gs[1], win, hop, _ptr(wo), _ptr(po), int(nw.max()), float(temp), _ptr(prob), _ptr(cosv), _ptr(pred)))
+        return prob, p_off, pred, w_off, cosv
 
     # ---- profiling
     # ---- multi-GPU exchange on RCCL through the C ABI (jegal_amd/dist.py uses torch.distributed for the same exchange)

@@ -545,6 +545,28 @@ int jg_asd(jg_handle* h, const float* q, const float* cand, const int32_t* coff,
     return timed(h, JG_ST_MISC, [&] { return launch_asd(q, cand, coff, n, D, temp, pred, h->stream); });
 }
 
+int jg_asd_windows(jg_handle* h, const float* gesture, const int32_t* g_offsets, int n_tracks, const float* content, const int32_t* c_offsets,
+                   const int32_t* word_start, const int32_t* word_end, const int32_t* trk, const int32_t* s_offsets, int n_scenes, int D,
+                   int win, int hop, const int32_t* w_offsets, const int64_t* p_offsets, int max_windows, float temp, float* prob,
+                   float* cosv, int32_t* pred) {
+    ENTER(h);
+    if (!gesture || !g_offsets || !content || !c_offsets || !trk || !s_offsets || !w_offsets || !p_offsets || !prob || !pred)
+        JG_FAIL(h, JG_ERR_ARG, "null buffer");
+    if (n_scenes < 0 || n_tracks < 0) JG_FAIL(h, JG_ERR_ARG, "n_scenes and n_tracks must be >= 0");
+    if (D <= 0 || D % 64 || D > ASDW_MAX_D) JG_FAIL(h, JG_ERR_ARG, "D must be a positive multiple of 64, at most %d", ASDW_MAX_D);
+    if (win < 0 || win > 8192) JG_FAIL(h, JG_ERR_ARG, "win must be 0 (one window over everything) or 1..8192 frames");
+    if (win > 0 && hop < 1) JG_FAIL(h, JG_ERR_ARG, "hop must be >= 1");
+    if (win > 0 && (!word_start || !word_end)) JG_FAIL(h, JG_ERR_ARG, "windows need word_start and word_end");
+    if (!(temp > 0.f)) JG_FAIL(h, JG_ERR_ARG, "temp must be positive");
+    if (max_windows < 1 || max_windows > 8192) JG_FAIL(h, JG_ERR_ARG, "max_windows must be 1..8192");
+    if ((reinterpret_cast<uintptr_t>(gesture) | reinterpret_cast<uintptr_t>(content)) & 15) JG_FAIL(h, JG_ERR_ARG, "gesture / content must be 16-byte aligned");
+    if (n_scenes == 0) return JG_OK;
+    return timed(h, JG_ST_MISC, [&] {
+        return launch_asd_windows(gesture, g_offsets, n_tracks, content, c_offsets, word_start, word_end, trk, s_offsets, n_scenes, D, win, hop,
+                                  w_offsets, p_offsets, max_windows, temp, prob, cosv, pred, h->stream);
+    });
+}
+
 // ---- multi-GPU exchange on RCCL: one communicator per handle = per rank = per GPU
 int jg_comm_get_unique_id(char* id128_host) {
     if (!id128_host) return JG_ERR_ARG;

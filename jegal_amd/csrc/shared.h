@@ -179,3 +179,11 @@ hipError_t launch_attn_matrix(const float* g, const float* c, const int32_t* gof
                               int32_t* best_frame, float* best_score, hipStream_t s);
 hipError_t launch_asd(const float* q, const float* cand, const int32_t* coff, int n, int D, float temp,
                       int32_t* pred2, hipStream_t s);
+// ASD per time window (metrics.hip: asd_windows_kernel): prob / cosv (optional) (n_win_i, P_i) at poff[i], pred [woff[n_scenes]].  A scene
+// outside the limits (1..64 candidates, 1..1024 words, 1..max_windows windows, tracks of 1..8192 frames inside 0..n_tracks-1) gets
+// pred = -1 and NaN rows in all of its windows.  No scratch.
+constexpr int ASDW_MAX_D = 1024;
+hipError_t launch_asd_windows(const float* g, const int32_t* goff, int n_tracks, const float* c, const int32_t* coff, const int32_t* wstart,
+                              const int32_t* wend, const int32_t* trk, const int32_t* soff, int n_scenes, int D, int win, int hop,
+                              const int32_t* woff, const int64_t* poff, int max_windows, float temp, float* prob, float* cosv,
+                              int32_t* pred, hipStream_t s);

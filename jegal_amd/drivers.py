@@ -8,6 +8,7 @@
     python -m jegal_amd.drivers inference_embs ...            # inference_embs.py (single clip -> <fname>.pkl)
     python -m jegal_amd.drivers attn_matrix --path F|D        # utils/plot_heatmap.py without the rendering (-> <name>.attn.npz)
     python -m jegal_amd.drivers retrieve --path D [--topk 10] # the retrieval evaluate_retrieval.py grades (-> retrieve_<direction>.npz)
+    python -m jegal_amd.drivers asd --path D --file avs_asd.csv [--win N --hop M]   # the detection evaluate_asd.py grades (-> asd.npz)
 
 Same flags, file naming and on-disk formats as the reference.  What is upstream of the hot path is
 NOT rebuilt: video decoding / mediapipe masking (the drivers read already masked 270x480 crops as
@@ -535,9 +536,90 @@ def cmd_retrieve(argv, engine=None):
     return 0
 
 
+def cmd_asd(argv, engine=None):
+    """The detection that evaluate_asd only grades: for every row of the csv whose feature .pkl exists, the probability that each of its
+    candidates -- the query clip first, then its neg_files that exist, as evaluate_asd builds the list -- gestures to the query's speech.
+    Writes ``<res_dir>/asd.npz`` = {names (N,): the queries' .pkl base names, cand_names (sum P,), cand_offsets (N + 1,), prob (sum P,)
+    float32: query i's probabilities are prob[cand_offsets[i] : cand_offsets[i + 1]], pred (N,) int32: the winner's place in the list (0 =
+    the query's own clip)}.  With --win also the timeline of every query, ``<res_dir>/<name>.asd.npz`` = {candidates (P,), start (n_win,)
+    int32, prob (n_win, P) float32, pred (n_win,) int32}: windows of --win frames, --hop apart, on the query's word boundaries.  A clip
+    that is a candidate of many queries is on the device once.  engine: the Engine to run on (default: this process's)."""
+    import pandas as pd
+    from . import metrics as M
+    p = argparse.ArgumentParser(prog="asd", description="Single process: sharding over ranks is not built for this command.")
+    p.add_argument("--path", required=True, help="a directory of JEGAL feature .pkl files")
+    p.add_argument("--file", required=True, help="the csv of evaluate_asd: filename, neg_files")
+    p.add_argument("--win", type=int, default=None, help="frames per window: also write every query's timeline (1..8192)")
+    p.add_argument("--hop", type=int, default=5, help="frames between window starts")
+    p.add_argument("--temp", type=float, default=0.07)
+    p.add_argument("--res_dir", default=".")
+    args = p.parse_args(argv)
+    if args.win is not None and (not 1 <= args.win <= 8192 or args.hop < 1):
+        raise SystemExit("--win must be 1..8192 and --hop >= 1")
+    df = pd.read_csv(args.file)
+    print("Total files: {}".format(len(df)))
+    stem = lambda fname: fname.split("/")[0] + "__" + fname.split("/")[1]
+    feats, track_of, tracks = {}, {}, []
+
+    def load(fname):
+        if fname not in feats:
+            fn = os.path.join(args.path, stem(fname) + ".pkl")
+            feats[fname] = None
+            if os.path.exists(fn):
+                with open(fn, "rb") as f:
+                    feats[fname] = pickle.load(f)
+                track_of[fname] = len(tracks)
+                tracks.append(np.asarray(feats[fname]["gesture_emb"], np.float32))
+        return feats[fname]
+
+    names, cand_names, contents, bounds, trk, s_off = [], [], [], [], [], [0]
+    for i in range(len(df)):
+        row = df.iloc[i]
+        q = load(row.filename)
+        if q is None:
+            continue
+        cands = [row.filename] + [neg for neg in ast.literal_eval(row.neg_files) if load(neg) is not None]
+        if len(cands) > 64:
+            raise SystemExit("{}: {} candidates; jg_asd_windows takes at most 64 per query".format(row.filename, len(cands)))
+        names.append(stem(row.filename))
+        cand_names.append([stem(c) for c in cands])
+        contents.append(np.asarray(q["content_emb"], np.float32))
+        bounds.append(q["info"]["word_boundaries"])
+        trk += [track_of[c] for c in cands]
+        s_off.append(len(trk))
+    if not names:
+        raise SystemExit("no query of {} has a .pkl under {}".format(args.file, args.path))
+    eng = engine if engine is not None else _models(args)[0]
+    g, c = M._cat(tracks), M._cat(contents)
+    goff, coff = M._offsets(tracks), M._offsets(contents)
+    prob, _, pred, _, _ = eng.asd_windows(g, goff, c, coff, trk, s_off, win=0, temp=args.temp)
+    os.makedirs(args.res_dir, exist_ok=True)
+    out = os.path.join(args.res_dir, "asd.npz")
+    pred = M._host(pred).astype(np.int32)
+    np.savez(out, names=np.asarray(names), cand_names=np.asarray([c for cs in cand_names for c in cs]), cand_offsets=np.asarray(s_off, np.int64),
+             prob=M._host(prob), pred=pred)
+    print("ASD: {} queries, own clip chosen for {} -> {}".format(len(names), int(np.sum(pred == 0)), out))
+    if args.win is not None:
+        se = [M._bounds(wb) for wb in bounds]
+        for name, (s, _), ct in zip(names, se, contents):
+            if len(s) != len(ct):
+                raise ValueError("{}: {} word boundaries for {} content rows".format(name, len(s), len(ct)))
+        prob, p_off, pred, w_off, _ = eng.asd_windows(g, goff, c, coff, trk, s_off, win=args.win, hop=args.hop, temp=args.temp,
+                                                      word_start=np.concatenate([s for s, _ in se]), word_end=np.concatenate([e for _, e in se]))
+        prob, pred = M._host(prob), M._host(pred)
+        for i, name in enumerate(names):
+            n_win = int(w_off[i + 1] - w_off[i])
+            np.savez(os.path.join(args.res_dir, name + ".asd.npz"), candidates=np.asarray(cand_names[i]),
+                     start=(np.arange(n_win) * args.hop).astype(np.int32), prob=prob[p_off[i]:p_off[i + 1]].reshape(n_win, len(cand_names[i])),
+                     pred=pred[w_off[i]:w_off[i + 1]].astype(np.int32))
+        print("ASD timelines: win {} hop {} -> {}/<name>.asd.npz".format(args.win, args.hop, args.res_dir))
+    return 0
+
+
 COMMANDS = {
     "attn_matrix": cmd_attn_matrix,
     "retrieve": cmd_retrieve,
+    "asd": cmd_asd,
     "extract_gestsync_feats": cmd_extract_gestsync_feats,
     "extract_jegal_embs": cmd_extract_jegal_embs,
     "evaluate_retrieval": cmd_evaluate_retrieval,

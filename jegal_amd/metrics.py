@@ -205,3 +205,66 @@ def asd_accuracy(query_content, candidate_gestures, engine=None):
     c2, c4, c6, n = reduce_counts(counts, eng.device)
     n = max(1, n)
     return c2 / n, c4 / n, c6 / n
+
+
+def _cat(mats):
+    return torch.as_tensor(np.concatenate([np.asarray(m, np.float32) for m in mats], 0))
+
+
+def asd_scores(contents, candidates, temp=0.07, engine=None):
+    """Active-speaker detection itself (evaluate_asd.py:26-51 without the grading): per query the word-level content (W_i, D) and a list
+    of 1..64 frame-level candidate arrays (T, D) -> per query (prob (P_i,) float32 = softmax(cosine(mean content, mean gesture) / temp)
+    over its candidates, pred = the first arg-max).  One jg_asd_windows call (clip-level mode) for the batch."""
+    if not len(contents):
+        return []
+    if len(candidates) != len(contents):
+        raise ValueError("one candidate list per query")
+    eng = engine or Engine.get()
+    tracks = [t for cands in candidates for t in cands]
+    s_off = np.zeros(len(candidates) + 1, np.int64)
+    s_off[1:] = np.cumsum([len(cands) for cands in candidates])
+    prob, p_off, pred, _, _ = eng.asd_windows(_cat(tracks), _offsets(tracks), _cat(contents), _offsets(contents), np.arange(len(tracks)),
+                                              s_off, win=0, temp=temp)
+    prob, pred = _host(prob), _host(pred)
+    return [(prob[p_off[i]:p_off[i + 1]], int(pred[i])) for i in range(len(contents))]
+
+
+def _bounds(wb):
+    """word boundaries of one scene -> (start, end) int arrays: [word, start, end] triplets (or their repr, as the csv rows hold them)
+    or (start, end) pairs"""
+    wb = ast.literal_eval(wb) if isinstance(wb, str) else wb
+    se = [(b[-2], b[-1]) for b in wb]
+    return np.asarray([b[0] for b in se], np.int64), np.asarray([b[1] for b in se], np.int64)
+
+
+def asd_timeline(contents, word_boundaries, tracks, win=25, hop=5, temp=0.07, engine=None):
+    """Who gestures to the speech, and when: for a scene with the word-level content (W, D) of one utterance, its word boundaries (frames
+    of the scene, inclusive) and a list of 1..64 co-temporal frame-level tracks (T_p, D), the speaker probabilities of every window of
+    `win` frames, `hop` frames apart -> dict(start (n_win,) int32: first frame of each window, prob (n_win, P) float32, pred (n_win,)
+    int32), n_win = ceil(longest track / hop).  A window without a word or beyond every track is undecided (pred -1, prob NaN); a track
+    that has ended gets prob 0.  One scene (contents a (W, D) array) or a list of scenes (-> a list of dicts); one jg_asd_windows call."""
+    single = not isinstance(contents, (list, tuple))
+    if single:
+        contents, word_boundaries, tracks = [contents], [word_boundaries], [tracks]
+    if not len(contents):
+        return []
+    if win < 1 or hop < 1:
+        raise ValueError("win and hop must be >= 1")
+    eng = engine or Engine.get()
+    flat = [t for scene in tracks for t in scene]
+    s_off = np.zeros(len(tracks) + 1, np.int64)
+    s_off[1:] = np.cumsum([len(scene) for scene in tracks])
+    se = [_bounds(wb) for wb in word_boundaries]
+    for (s, _), c in zip(se, contents):
+        if len(s) != len(c):
+            raise ValueError("{} word boundaries for {} content rows".format(len(s), len(c)))
+    prob, p_off, pred, w_off, _ = eng.asd_windows(_cat(flat), _offsets(flat), _cat(contents), _offsets(contents), np.arange(len(flat)), s_off,
+                                                  win=win, hop=hop, word_start=np.concatenate([s for s, _ in se]),
+                                                  word_end=np.concatenate([e for _, e in se]), temp=temp)
+    prob, pred = _host(prob), _host(pred)
+    out = []
+    for i, scene in enumerate(tracks):
+        n_win = int(w_off[i + 1] - w_off[i])
+        out.append(dict(start=(np.arange(n_win) * hop).astype(np.int32), prob=prob[p_off[i]:p_off[i + 1]].reshape(n_win, len(scene)),
+                        pred=pred[w_off[i]:w_off[i + 1]]))
+    return out[0] if single else out

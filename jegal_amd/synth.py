@@ -455,3 +455,24 @@ def planted_asd(seed, n_queries, d=512, n_frames=12, n_words=5, noise=1.6):
         positives.append(pos.astype(np.float32))
         negatives.append(negs)
     return contents, positives, negatives
+
+
+def planted_scene(seed, P, T, W, d=512, span=5, noise=1.0, turns=3):
+    """A scene for ASD over time: W unit-norm content rows, word j on frames span j .. span j + span - 2 (a silent gap frame follows every
+    word), P co-temporal tracks of N(0, 1/d) rows -- track 0 is 7 frames shorter than T, the others have T frames.  The speaker of word j
+    is track (j // turns) % P: its frames inside the word's span are content_j + noise x their original values.
+    Returns (content (W,d), bounds [[w_j, start, end]], tracks [(T_p,d)], speakers [W])."""
+    rng = np.random.default_rng(seed)
+    content = rng.standard_normal((W, d)).astype(np.float32)
+    content /= np.linalg.norm(content, axis=1, keepdims=True)
+    tracks = [(rng.standard_normal((T if p else T - 7, d)) / math.sqrt(d)).astype(np.float32) for p in range(P)]
+    bounds, speakers = [], []
+    for j in range(W):
+        s, e = span * j, span * j + span - 2
+        p = (j // turns) % P
+        bounds.append([f"w{j}", s, e])
+        speakers.append(p)
+        e = min(e + 1, tracks[p].shape[0])
+        if s < e:
+            tracks[p][s:e] = content[j][None] + np.float32(noise) * tracks[p][s:e]
+    return content, bounds, tracks, speakers
