@@ -333,9 +333,9 @@ struct Mfma16 {
     }
 };
 
-// The tile loop of an MFMA wave.  The BN-folded bias rides in the GEMM: element 15 of every pixel slot is "1.0" (2^-24, the
-// same scale as the pixel values, see cvt_write) and the weight panel
-// holds shift/scale (hi+lo fp16 pair) at [slot 0][c][15] and [slot 1][c][15] -- no accumulator
+// The tile loop of an MFMA wave.  The BN-folded bias rides in the GEMM: element 15 of every pixel slot is "1.0" (CONV1_BIAS_ONE = 2^-14,
+// a NORMAL fp16: shared.h has why; see cvt_write) and the weight panel
+// holds shift/scale * 2^-10 (hi+lo fp16 pair: the product has the pixel values' scale 2^-24) at [slot 0][c][15] and [slot 1][c][15] -- no accumulator
 // init read, no global load in the epilogue:  out = relu(acc * scale).
 template <class Form>
 __device__ __forceinline__ void conv1_mfma_role(const f16* Wd, float scale, char* smem, int lane, int wave) {
@@ -485,7 +485,7 @@ __global__ __launch_bounds__(512, 2) void conv1_direct_kernel(Conv1Args a) {
         // bit-identical results).  One v_perm_b32 places two bytes -> 8 VALU ops per 16-element pixel slot instead
         // of ~40 (cvt_f32_ubyte + cvt_f16_f32 + pack); the loader waves share their SIMDs with the MFMA waves and
         // their VALU time is what the tile time was waiting for.
-        // slot element k = 3*dt + c (dt = frame 0..4, c = channel), k = 15: the bias lane, 2^-24 (= 1.0 * 2^-24).
+        // slot element k = 3*dt + c (dt = frame 0..4, c = channel), k = 15: the bias lane, CONV1_BIAS_ONE (2^-14; the pair it meets carries the other 2^-10).
         // Zero tiles: the reference blanks the face region of every frame (inference_embs.py:264,270: rows 0..y2+15,
         // ~40 % of the crop).  A tile whose 16 x 100 x 5 source pixels are all zero contributes nothing but the bias
         // slots: the MFMA waves then run 2 of the 49 slots (bit-identical: the other 47 add exact zeros), and a tile
@@ -538,15 +538,15 @@ __global__ __launch_bounds__(512, 2) void conv1_direct_kernel(Conv1Args a) {
                         const int k0 = 2 * m, k1 = 2 * m + 1;
                         const int b0 = 3 * q + k0 % 3;                               // byte of the 12-byte chunk of frame k0/3
                         const uint32_t lo = R.w[u][k0 / 3][b0 >> 2];
-                        uint32_t hi = 1u;                                            // k = 15: the constant 0x0001
-                        int hb = 0;
+                        // v_perm_b32: selector bytes 0-3 pick from the second operand, 4-7 from the first, 0x0c = 0x00
                         if (k1 < 15) {
                             const int b1 = 3 * q + k1 % 3;
-                            hi = R.w[u][k1 / 3][b1 >> 2];
-                            hb = b1 & 3;
+                            const uint32_t hi = R.w[u][k1 / 3][b1 >> 2];
+                            d[m] = __builtin_amdgcn_perm(hi, lo, 0x0c000c00u | ((4u + (uint32_t)(b1 & 3)) << 16) | (uint32_t)(b0 & 3));
+                        } else {
+                            // k = 15: the constant CONV1_BIAS_ONE_BITS (0x0400) in the upper half -- its high byte from byte 0 of the first operand
+                            d[m] = __builtin_amdgcn_perm(CONV1_BIAS_ONE_BITS >> 8, lo, 0x040c0c00u | (uint32_t)(b0 & 3));
                         }
-                        // v_perm_b32: selector bytes 0-3 pick from the second operand, 4-7 from the first, 0x0c = 0x00
-                        d[m] = __builtin_amdgcn_perm(hi, lo, 0x0c000c00u | ((4u + hb) << 16) | (uint32_t)(b0 & 3));
                     }
                     const int x = 4 * g + q;
                     char* dst = buf + row * ROW_PITCH + slot_off(x);
@@ -748,12 +748,12 @@ __global__ void conv1_edge_fix_kernel(f16* __restrict__ out, const f16* __restri
 //   2. full check of the candidate rows, one wave per row, coalesced 16-B loads,
 //   3. band flags -> 22-bit mask.
 // Block 0 also computes the constant every all-zero patch produces: relu(bias) as the MFMA path rounds it (conv1 bias = the
-// hi+lo pair on the pad lane of slots 0 and 1, times 2^-24; both products and their sum are exact in fp32).
+// hi+lo pair on the pad lane of slots 0 and 1, times the pad lane's "1.0"; both products and their sum are exact in fp32).
 // relu(bias) of channel c as the MFMA path rounds it: the bias is the hi+lo pair on the pad lane of slots 0 and 1, times the pad
-// lane's "1.0" = 2^-24; both products and their sum are exact in fp32
+// lane's "1.0" = CONV1_BIAS_ONE; both products and their sum are exact in fp32
 __device__ __forceinline__ f16 conv1_zero_patch_value(const f16* __restrict__ Wd, float scale, int c) {
     const float hi = (float)Wd[conv1_wd_index(0, c, CONV1_BIAS_LANE)], lo = (float)Wd[conv1_wd_index(1, c, CONV1_BIAS_LANE)];
-    const float acc = hi * 5.9604644775390625e-8f + lo * 5.9604644775390625e-8f;
+    const float acc = hi * CONV1_BIAS_ONE + lo * CONV1_BIAS_ONE;
     return (f16)fmaxf(acc * scale, 0.f);
 }
 __global__ void conv1_zconst_kernel(const f16* __restrict__ Wd, float scale, f16* __restrict__ zconst) {

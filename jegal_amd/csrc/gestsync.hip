@@ -63,11 +63,12 @@ int finalize_gestsync(jg_handle* h) {
         for (int s = 0; s < 49; ++s)
             for (int o = 0; o < 64; ++o)
                 for (int e = 0; e < 16; ++e) wd[conv1_wd_index(s, o, e)] = hostw[(size_t)o * 784 + s * 16 + e];
-        // bias lane: the kernel sets element CONV1_BIAS_LANE of every pixel slot to 1.0; shift*255 as hi+lo fp16 pair
+        // bias lane: the kernel sets element CONV1_BIAS_LANE of every pixel slot to "1.0" = CONV1_BIAS_ONE; shift*255 (times the power
+        // of two CONV1_BIAS_PAIR_SCALE that makes the product shift*255 * 2^-24, shared.h) as hi+lo fp16 pair
         std::vector<float> shift(64);
         HIPCHK(h, hipMemcpy(shift.data(), gs.c1.bias, 64 * sizeof(float), hipMemcpyDeviceToHost));
         for (int o = 0; o < 64; ++o) {
-            const float v = shift[o] * 255.0f;
+            const float v = shift[o] * 255.0f * CONV1_BIAS_PAIR_SCALE;
             const f16 hi = (f16)v;
             wd[conv1_wd_index(0, o, CONV1_BIAS_LANE)] = hi;
             wd[conv1_wd_index(1, o, CONV1_BIAS_LANE)] = (f16)(v - (float)hi);

@@ -65,7 +65,8 @@ def test_strict_load_rejects_missing_key(engine):
 
 def test_conv1_pool_kernel(models, golden_dir, oracle_sd):
     """conv1+BN+ReLU+maxpool: fused u8 kernel and the stack+implicit-GEMM formulation, against the
-    reference golden slice and the full oracle tensor."""
+    reference golden slice and the full oracle tensor.
+    (The kernel-level check, element by element against float64 and bit for bit: tests/test_gpu_conv1_fp64.py.)"""
     gs, _ = models
     gsd, _ = oracle_sd
     g = np.load(os.path.join(golden_dir, "gestsync_clip.npz"))
