@@ -412,6 +412,39 @@ int jg_sim_rank(jg_handle* h, const float* e1, const float* e2, int n_local, int
  * score is written; no workspace is used.  Asynchronous. */
 int jg_sim_topk(jg_handle* h, const float* queries, const float* gallery, int n_queries, int n_gallery, int D, int k,
                 int gallery_offset, int merge, int32_t* idx, float* score);
+/* Grouped top-k: for this word or phrase, which clips gesture it, and at which frame.  The gallery rows (frame-level) are partitioned into
+ * contiguous groups (a clip, or a fixed-length segment of a long track); a group scores as its best row; per query row the k best groups
+ * are returned, each as the row that earned the score.  The n_queries x n_gallery matrix is never written.
+ * Scores: s_ij = <queries[i], gallery[j]> exactly as jg_sim_topk and jg_sim_rank compute it (exact-fp32 MFMA, one k-ascending chain per
+ * element, the same staging order): a score depends on its two rows alone and is bit-identical to theirs; -0.0 is treated (and returned)
+ * as +0.0; a NaN score is never a candidate.
+ * Groups: g_offsets [n_groups + 1], a DEVICE array; group g owns the local gallery rows g_offsets[g] .. g_offsets[g + 1] - 1 (0 ..
+ * n_gallery), a contiguous non-decreasing partition, empty groups allowed.  Rows below g_offsets[0] or from g_offsets[n_groups] on belong
+ * to no group and are never returned.  A group's champion is its row with the largest score, on equal scores the smallest row (the first
+ * arg-max, np.argmax); a group without a non-NaN row has none.
+ * Result: per query the k best champions in the total order "larger score first, then the smaller row" (= the smaller group); idx[i][r] =
+ * gallery_offset + row, score[i][r] its score bit for bit; when fewer than k groups have a champion the remaining slots are idx = -1,
+ * score = -inf.  No two returned rows of one call lie in the same group.  idx / score: [n_queries][k], device.
+ * merge as for jg_sim_topk: with merge != 0, idx and score hold the result of earlier calls with the same queries and k for OTHER gallery
+ * rows and the call leaves the best k of the union -- a gallery cut into pieces AT GROUP BOUNDARIES, in any order, gives the bits of one
+ * call over the whole gallery.  A group split across calls, or overlapping row ranges, give an unspecified result.
+ * Safety: the host cannot validate g_offsets, so the kernel never addresses the gallery through it: it walks the rows 0 .. n_gallery - 1 and
+ * uses the offsets only to classify a row.  Offsets that are not a non-decreasing partition give an unspecified result, never a read
+ * outside the two operands and g_offsets[0 .. n_groups], nor a write outside the n_queries * k entries of idx and score.
+ * Limits as for jg_sim_topk: 1 <= k <= 128; D > 0, D % 64 == 0; n_queries, n_gallery, n_groups >= 0; gallery_offset >= 0, gallery_offset +
+ * n_gallery <= INT32_MAX; queries and gallery 16-byte aligned.  A violated limit or a null buffer (g_offsets when n_groups > 0) returns
+ * JG_ERR_ARG before anything is enqueued.  n_queries == 0 returns JG_OK and launches nothing; n_gallery == 0 or n_groups == 0 fills -1 /
+ * -inf without merge and keeps the list with it.  No workspace is used.  Asynchronous. */
+int jg_sim_topk_grouped(jg_handle* h, const float* queries, const float* gallery, int n_queries, int n_gallery, int D, int k,
+                        const int32_t* g_offsets /* device, [n_groups + 1] */, int n_groups,
+                        int gallery_offset, int merge, int32_t* idx, float* score);
+/* The rows jg_sim_topk_grouped returns, back to (group, position inside the group), on the device: grp[e] = the group whose range holds
+ * idx[e] - gallery_offset, pos[e] = the row's offset inside it; both -1 for idx[e] < 0 or a row in no group.  An element-wise binary
+ * search over g_offsets (device, [n_groups + 1]); a caller of merged calls passes its global offsets with gallery_offset = 0.  n, n_groups,
+ * gallery_offset >= 0; a null buffer (g_offsets when n_groups > 0) or a negative count returns JG_ERR_ARG; n == 0 launches nothing.
+ * Only the n entries of grp and pos are written.  Asynchronous. */
+int jg_group_of_rows(jg_handle* h, const int32_t* idx, int64_t n, const int32_t* g_offsets, int n_groups, int gallery_offset,
+                     int32_t* grp, int32_t* pos);
 /* evaluate_spotting.py:39-82: per clip first-argmax frame and its softmax score for word `target`.
  * Limits per clip: <= 1024 words, <= 8192 frames, 0 <= target < words.  The offsets are device arrays (no host sync to
  * validate them): a clip outside the limits gets pred = -1 and score = NaN instead of a result. */

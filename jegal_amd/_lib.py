@@ -111,6 +111,8 @@ _SIGS = {
     "jg_pool_mean": [_P, _P, _P, _I, _I, _P],
     "jg_sim_rank": [_P, _P, _P, _I, _I, _I, _I, _P, _P],
     "jg_sim_topk": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P],
+    "jg_sim_topk_grouped": [_P, _P, _P, _I, _I, _I, _I, _P, _I, _I, _I, _P, _P],
+    "jg_group_of_rows": [_P, _P, _L, _P, _I, _I, _P, _P],
     "jg_spot": [_P, _P, _P, _P, _P, _P, _I, _I, ctypes.c_float, _P, _P],
     "jg_attn_matrix": [_P, _P, _P, _P, _P, _I, _I, _I, ctypes.c_float, _I, _P, _P, _P, _P],
     "jg_asd": [_P, _P, _P, _P, _I, _I, ctypes.c_float, _P],
@@ -785,6 +787,73 @@ class Engine:
             self._ck(self.lib.jg_sim_topk(self.h, _ptr(q), _ptr(g), qs[0], gs[0], qs[1], k, gallery_offset, int(merge_into is not None),
                                           _ptr(idx), _ptr(score)))
         return idx, score
+
+    @staticmethod
+    def _check_group_offsets(g_offsets, rows):
+        """g_offsets of the grouped entries -> number of groups.  A host array is checked (a non-decreasing partition inside 0 .. rows); a
+        tensor is taken as it is, as the C entry takes it: only its shape and type are looked at."""
+        if isinstance(g_offsets, torch.Tensor):
+            if g_offsets.ndim != 1 or g_offsets.numel() < 1 or g_offsets.dtype not in (torch.int32, torch.int64):
+                raise ValueError("g_offsets must be a 1-d integer tensor of groups + 1 entries")
+            return g_offsets.numel() - 1
+        off = np.asarray(g_offsets)
+        if off.ndim != 1 or off.size < 1 or not np.issubdtype(off.dtype, np.integer):
+            raise ValueError("g_offsets must be a 1-d integer array of groups + 1 entries")
+        if off[0] < 0 or (rows is not None and off[-1] > rows) or off[-1] > 2 ** 31 - 1 or np.any(np.diff(off.astype(np.int64)) < 0):
+            raise ValueError("g_offsets must be non-decreasing and lie inside 0 .. gallery rows")
+        return off.size - 1
+
+    def sim_topk_grouped(self, queries, gallery, g_offsets, k, gallery_offset=0, merge_into=None):
+        """jg_sim_topk_grouped: the gallery rows are cut into contiguous groups (group i = rows g_offsets[i] .. g_offsets[i + 1] - 1 of
+        `gallery`; a host array or a tensor of groups + 1 entries), a group scores as its best row, and per query row the k best groups come
+        back, each as the row that earned the score: (idx (n, k) int32 = gallery_offset + row, score (n, k) float32), device tensors, best
+        first, on equal scores the smaller row; never two rows of one group; -1 / -inf where fewer than k groups have a row.  Scores are
+        those of sim_topk / sim_rank bit for bit.  merge_into = (idx, score) of an earlier call with the same queries and k on OTHER
+        gallery rows, cut at group boundaries: updated in place to the best k of the union and returned."""
+        qs, gs = tuple(queries.shape), tuple(gallery.shape)
+        if len(qs) != 2 or len(gs) != 2 or qs[1] != gs[1] or qs[1] <= 0 or qs[1] % 64:
+            raise ValueError("queries / gallery must be (rows, D) with the same D, a positive multiple of 64")
+        k, gallery_offset = int(k), int(gallery_offset)
+        if not 1 <= k <= 128:
+            raise ValueError("jg_sim_topk_grouped limit: 1 <= k <= 128")
+        if gallery_offset < 0 or gallery_offset + gs[0] > 2 ** 31 - 1:
+            raise ValueError("gallery_offset must be >= 0 and gallery_offset + gallery rows <= INT32_MAX")
+        n_groups = self._check_group_offsets(g_offsets, gs[0])
+        if merge_into is not None:
+            if not isinstance(merge_into, (tuple, list)) or len(merge_into) != 2 or not all(isinstance(t, torch.Tensor) for t in merge_into):
+                raise ValueError("merge_into must be the (idx, score) pair of an earlier sim_topk_grouped call")
+            idx, score = merge_into
+            if (tuple(idx.shape) != (qs[0], k) or tuple(score.shape) != (qs[0], k) or idx.dtype != torch.int32 or score.dtype != torch.float32
+                    or not idx.is_contiguous() or not score.is_contiguous()):
+                raise ValueError(f"merge_into must be contiguous (idx int32, score float32) tensors of shape ({qs[0]}, {k})")
+            if idx.device != self.device or score.device != self.device:
+                raise ValueError(f"merge_into must be on {self.device}")
+        self._bind_stream()
+        q, g, off = self._f32(queries), self._f32(gallery), self._i32(g_offsets)
+        if merge_into is None:
+            idx = torch.full((qs[0], k), -1, dtype=torch.int32, device=self.device)
+            score = torch.full((qs[0], k), float("-inf"), dtype=torch.float32, device=self.device)
+        if qs[0] and gs[0] and n_groups:               # (no gallery row, no group: nothing to merge, or the empty result above)
+            self._ck(self.lib.jg_sim_topk_grouped(self.h, _ptr(q), _ptr(g), qs[0], gs[0], qs[1], k, _ptr(off), n_groups, gallery_offset,
+                                                  int(merge_into is not None), _ptr(idx), _ptr(score)))
+        return idx, score
+
+    def group_of_rows(self, idx, g_offsets, gallery_offset=0):
+        """jg_group_of_rows: the rows sim_topk_grouped returned (an int32 tensor of any shape) -> (grp, pos) int32 device tensors of that
+        shape: the group whose range holds idx - gallery_offset and the row's place inside it; -1 / -1 for idx < 0 or a row in no group.
+        After merged calls: the offsets of the whole gallery with gallery_offset = 0."""
+        if not isinstance(idx, torch.Tensor) or idx.dtype != torch.int32:
+            raise ValueError("idx must be an int32 tensor (the idx of sim_topk_grouped)")
+        gallery_offset = int(gallery_offset)
+        if not 0 <= gallery_offset <= 2 ** 31 - 1:
+            raise ValueError("gallery_offset must be 0 .. INT32_MAX")
+        n_groups = self._check_group_offsets(g_offsets, None)
+        self._bind_stream()
+        rows, off = self._i32(idx), self._i32(g_offsets)
+        grp, pos = torch.full_like(rows, -1), torch.full_like(rows, -1)
+        if rows.numel():
+            self._ck(self.lib.jg_group_of_rows(self.h, _ptr(rows), rows.numel(), _ptr(off), n_groups, gallery_offset, _ptr(grp), _ptr(pos)))
+        return grp, pos
 
     def spot(self, gesture, content, g_offsets, c_offsets, targets, temp=0.07):
         self._bind_stream()

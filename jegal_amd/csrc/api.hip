@@ -513,6 +513,31 @@ int jg_sim_topk(jg_handle* h, const float* queries, const float* gallery, int n_
     });
 }
 
+int jg_sim_topk_grouped(jg_handle* h, const float* queries, const float* gallery, int n_queries, int n_gallery, int D, int k,
+                        const int32_t* g_offsets, int n_groups, int gallery_offset, int merge, int32_t* idx, float* score) {
+    ENTER(h);
+    if (!queries || !gallery || !idx || !score || (n_groups > 0 && !g_offsets)) JG_FAIL(h, JG_ERR_ARG, "null buffer");
+    if (k < 1 || k > SIM_TOPK_MAX_K) JG_FAIL(h, JG_ERR_ARG, "k must be 1..%d", SIM_TOPK_MAX_K);
+    if (D <= 0 || D % 64) JG_FAIL(h, JG_ERR_ARG, "D must be a positive multiple of 64");
+    if (n_queries < 0 || n_gallery < 0 || n_groups < 0 || gallery_offset < 0 || gallery_offset > INT32_MAX - n_gallery)
+        JG_FAIL(h, JG_ERR_ARG, "bad sim_topk_grouped geometry (counts and gallery_offset >= 0, gallery_offset + n_gallery <= INT32_MAX)");
+    if ((reinterpret_cast<uintptr_t>(queries) | reinterpret_cast<uintptr_t>(gallery)) & 15) JG_FAIL(h, JG_ERR_ARG, "queries / gallery must be 16-byte aligned");
+    if (n_queries == 0) return JG_OK;
+    return timed(h, JG_ST_MISC, [&] {
+        return launch_sim_topk_grouped(queries, gallery, n_queries, n_gallery, D, k, g_offsets, n_groups, gallery_offset, merge, idx, score,
+                                       h->stream);
+    });
+}
+
+int jg_group_of_rows(jg_handle* h, const int32_t* idx, int64_t n, const int32_t* g_offsets, int n_groups, int gallery_offset,
+                     int32_t* grp, int32_t* pos) {
+    ENTER(h);
+    if (!idx || !grp || !pos || (n_groups > 0 && !g_offsets)) JG_FAIL(h, JG_ERR_ARG, "null buffer");
+    if (n < 0 || n_groups < 0 || gallery_offset < 0) JG_FAIL(h, JG_ERR_ARG, "n, n_groups and gallery_offset must be >= 0");
+    if (n == 0) return JG_OK;
+    return timed(h, JG_ST_MISC, [&] { return launch_group_of_rows(idx, (long)n, g_offsets, n_groups, gallery_offset, grp, pos, h->stream); });
+}
+
 int jg_spot(jg_handle* h, const float* g, const float* c, const int32_t* goff, const int32_t* coff, const int32_t* target,
             int n, int D, float temp, int32_t* pred, float* score) {
     ENTER(h);

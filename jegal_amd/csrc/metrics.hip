@@ -268,6 +268,224 @@ hipError_t launch_sim_topk(const float* queries, const float* gallery, int n_que
 }
 
 // ---------------------------------------------------------------------------------------------
+// Grouped top-k: the gallery rows are partitioned into contiguous groups (goff[g] .. goff[g + 1] - 1, local rows), a group scores as its
+// best row (its champion: the largest key of its rows, so on equal scores the first row), and per query the k best champions are kept,
+// each with its row.  The tile loop is sim_topk_kernel's, statement for statement, and so are the keys, the per-row sorted list, the
+// threshold and the per-tile queue.  What is new is the invariant AT MOST ONE LIST ENTRY PER GROUP: an insertion first looks for the
+// entry of the candidate's group; if that entry beats the candidate the candidate is dropped, else the entry is removed and the candidate
+// inserted -- one pass, since the candidate lands at or before the entry it replaces: the positions behind that entry keep their keys.
+// Entries only ever move towards the end of the list, and replacing an entry by a larger one can only raise the k-th key, so the
+// threshold stays monotone: what is below a threshold that ever held is below the final k-th champion.
+//
+// Groups are contiguous, so "same group" is a range test on the row half of a key against the candidate's [goff[g], goff[g + 1]); the
+// list needs no second array.  The range comes from a wave-uniform binary search over goff when the candidate is broadcast, and is kept
+// for the candidates behind it: the queue of a tile holds 64 consecutive rows, mostly of one or two groups.  Entries seeded by merge lie
+// outside this call's rows and never match.  goff is a device array that nobody has checked: it is only ever read at 0 .. n_groups
+// (the search is bounded by n_groups, not by what it reads) and its values are only compared with row numbers, never used as addresses.
+
+// [lo, hi) of the group that holds local row j, given goff[0] <= j < goff[n_groups] (else: some range); all arguments wave-uniform
+__device__ __forceinline__ void group_range(const int32_t* __restrict__ goff, int n_groups, int j, int& lo, int& hi) {
+    int a = 0, b = n_groups;
+    lo = goff[0];
+    hi = goff[n_groups];
+    while (b - a > 1) {                                          // goff[a] <= j < goff[b]
+        const int mid = (a + b) >> 1, v = goff[mid];
+        if (v <= j) { a = mid; lo = v; } else { b = mid; hi = v; }
+    }
+}
+
+// topk_flush with the invariant: the wave's 16 rows, queued keys into the sorted lists, one entry per group
+template <int LCAP>
+__device__ __forceinline__ void topk_flush_grouped(u64 (*sL)[LCAP], const u64 (*sQ)[64], int* sCnt, u64* sThr, int k, int wave, int lane,
+                                                   const int32_t* __restrict__ goff, int n_groups, unsigned gallery_offset) {
+    unsigned first = 0u, len = 0u;                               // global rows first .. first + len - 1: the group searched last
+    for (int rr = 0; rr < 16; ++rr) {
+        const int row = wave * 16 + rr;
+        const int n = __builtin_amdgcn_readfirstlane(sCnt[row]);
+        if (n == 0) continue;
+        const u64 cand = lane < n ? sQ[row][lane] : 0ull;
+        u64 e0 = sL[row][lane], e1 = 0ull;
+        if constexpr (LCAP == 128) e1 = sL[row][64 + lane];
+        u64 kth = sThr[row];
+        for (int i = 0; i < n; ++i) {
+            const u64 c = topk_readlane(cand, i);
+            if (c < kth) continue;                               // below the k-th champion: its group's entry, if any, beats it as well
+            const unsigned gi = 0xffffffffu - (unsigned)c;
+            if (gi - first >= len) {
+                int lo, hi;
+                group_range(goff, n_groups, (int)(gi - gallery_offset), lo, hi);
+                first = gallery_offset + (unsigned)lo;
+                len = (unsigned)hi - (unsigned)lo;
+            }
+            // m: the position of the group's entry (the first one, should hostile offsets give several), LCAP when it has none
+            const unsigned long long hit0 = __ballot(e0 != 0ull && 0xffffffffu - (unsigned)e0 - first < len);
+            int m = hit0 ? __builtin_ctzll(hit0) : LCAP;
+            if constexpr (LCAP == 128) {
+                const unsigned long long hit1 = __ballot(e1 != 0ull && 0xffffffffu - (unsigned)e1 - first < len);
+                if (!hit0 && hit1) m = 64 + __builtin_ctzll(hit1);
+            }
+            if (m < LCAP && topk_readlane(m < 64 ? e0 : e1, m & 63) > c) continue;       // the group's champion stays
+            // positions behind m keep their keys; up to m: position p keeps its key if that beats c, else it takes c if the key before it
+            // beats c, else the key before it (the entry at m is below c, so it is the one that leaves)
+            u64 p0 = __shfl_up(e0, 1, 64);
+            if (lane == 0) p0 = ~0ull;
+            if constexpr (LCAP == 128) {
+                u64 p1 = __shfl_up(e1, 1, 64);
+                const u64 last0 = topk_readlane(e0, 63);
+                if (lane == 0) p1 = last0;
+                e1 = (64 + lane > m || e1 > c) ? e1 : (p1 > c ? c : p1);
+            }
+            e0 = (lane > m || e0 > c) ? e0 : (p0 > c ? c : p0);
+            kth = topk_readlane(LCAP == 128 && k > 64 ? e1 : e0, (k - 1) & 63);
+        }
+        sL[row][lane] = e0;
+        if constexpr (LCAP == 128) sL[row][64 + lane] = e1;
+        if (lane == 0) { sThr[row] = kth; sCnt[row] = 0; }
+    }
+}
+
+template <int LCAP>
+__global__ __launch_bounds__(256) void sim_topk_grouped_kernel(const float* __restrict__ e1, const float* __restrict__ e2, int n_queries,
+                                                               int n_gallery, int D, int k, const int32_t* __restrict__ goff, int n_groups,
+                                                               int gallery_offset, int merge, int32_t* __restrict__ idx,
+                                                               float* __restrict__ score) {
+    __shared__ __attribute__((aligned(16))) u64 sStage[64 * 64];       // staging (sA, sB) during a tile's k loop, the queues after it
+    __shared__ u64 sL[64][LCAP];
+    __shared__ u64 sThr[64];
+    __shared__ int sCnt[64];
+    float (*sA)[64] = reinterpret_cast<float (*)[64]>(sStage);         // [k][query row]
+    float (*sB)[64] = sA + 64;                                         // [k][gallery row]
+    u64 (*sQ)[64] = reinterpret_cast<u64 (*)[64]>(sStage);             // [query row][slot]
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wr = wave & 1, wc = wave >> 1;
+    const int i0 = blockIdx.x * 64;
+    const int r = tid & 63, kq = tid >> 6;
+
+    // the lists start empty, or (merge) from the caller's earlier result: sorted, empty slots (idx < 0) last
+    for (int rr = 0; rr < 16; ++rr) {
+        const int row = wave * 16 + rr;
+        const long base = (long)(i0 + row) * k;
+        u64 kth = 0ull;
+#pragma unroll
+        for (int p = lane; p < LCAP; p += 64) {
+            u64 key = 0ull;
+            if (merge && p < k && i0 + row < n_queries) {
+                const int32_t j = idx[base + p];
+                const float s = score[base + p];
+                if (j >= 0 && s == s) key = topk_key(s, (unsigned)j);
+            }
+            sL[row][p] = key;
+            if (p == k - 1) kth = key;
+        }
+        if (lane == ((k - 1) & 63)) sThr[row] = kth;
+        if (lane == 0) sCnt[row] = 0;
+    }
+
+    // rows below goff[0] or from goff[n_groups] on belong to no group; without a group there is no candidate and no tile to walk
+    const int grp_lo = n_groups > 0 ? goff[0] : 0, grp_hi = n_groups > 0 ? goff[n_groups] : 0;
+    const int ntiles = n_groups > 0 ? (n_gallery + 63) / 64 : 0;
+    for (int tile = 0; tile < ntiles; ++tile) {
+        const int j0 = tile * 64;
+        f32x16 acc;
+#pragma unroll
+        for (int x = 0; x < 16; ++x) acc[x] = 0.f;
+        for (int k0 = 0; k0 < D; k0 += 64) {
+            __syncthreads();
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int kk = kq * 16 + q * 4;
+                f32x4 va = {0.f, 0.f, 0.f, 0.f}, vb = va;
+                if (i0 + r < n_queries) va = *reinterpret_cast<const f32x4*>(e1 + (long)(i0 + r) * D + k0 + kk);
+                if (j0 + r < n_gallery) vb = *reinterpret_cast<const f32x4*>(e2 + (long)(j0 + r) * D + k0 + kk);
+                sA[kk][r] = va.x; sA[kk + 1][r] = va.y; sA[kk + 2][r] = va.z; sA[kk + 3][r] = va.w;
+                sB[kk][r] = vb.x; sB[kk + 1][r] = vb.y; sB[kk + 2][r] = vb.z; sB[kk + 3][r] = vb.w;
+            }
+            __syncthreads();
+#pragma unroll 8
+            for (int kk = 0; kk < 64; kk += 2) {
+                const float a = sA[kk + (lane >> 5)][wr * 32 + (lane & 31)];
+                const float b = sB[kk + (lane >> 5)][wc * 32 + (lane & 31)];
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0);
+            }
+        }
+        __syncthreads();                                         // the staging buffers become the queues
+        // D layout: col = lane & 31 (gallery), row = mfma32_row(x, lane >> 5) (query)
+        const int j = j0 + wc * 32 + (lane & 31);
+        const bool jok = j < n_gallery && j >= grp_lo && j < grp_hi;
+        const unsigned gj = (unsigned)gallery_offset + (unsigned)j;
+#pragma unroll
+        for (int x = 0; x < 16; ++x) {
+            const int row = wr * 32 + mfma32_row(x, lane >> 5);
+            const u64 key = topk_key(acc[x], gj);
+            if (jok && acc[x] == acc[x] && i0 + row < n_queries && key > sThr[row])      // a NaN is never a candidate
+                sQ[row][atomicAdd(&sCnt[row], 1)] = key;
+        }
+        __syncthreads();
+        topk_flush_grouped<LCAP>(sL, sQ, sCnt, sThr, k, wave, lane, goff, n_groups, (unsigned)gallery_offset);
+    }
+    // a wave stores the lists of the rows it seeded and flushed itself, each row as one contiguous run
+    for (int rr = 0; rr < 16; ++rr) {
+        const int row = wave * 16 + rr;
+        if (i0 + row >= n_queries) break;
+        const long base = (long)(i0 + row) * k;
+        for (int p = lane; p < k; p += 64) {
+            const u64 key = sL[row][p];
+            idx[base + p] = topk_index(key);
+            score[base + p] = topk_score(key);
+        }
+    }
+}
+
+hipError_t launch_sim_topk_grouped(const float* queries, const float* gallery, int n_queries, int n_gallery, int D, int k,
+                                   const int32_t* g_offsets, int n_groups, int gallery_offset, int merge, int32_t* idx, float* score,
+                                   hipStream_t s) {
+    if (n_queries <= 0) return hipSuccess;
+    if (D <= 0 || D % 64 || k < 1 || k > SIM_TOPK_MAX_K || n_gallery < 0 || n_groups < 0 || (n_groups > 0 && !g_offsets) ||
+        gallery_offset < 0 || gallery_offset > INT32_MAX - n_gallery)
+        return hipErrorInvalidValue;
+    const dim3 grid((n_queries + 63) / 64);
+    if (k <= 64)
+        hipLaunchKernelGGL(sim_topk_grouped_kernel<64>, grid, dim3(256), 0, s, queries, gallery, n_queries, n_gallery, D, k, g_offsets, n_groups,
+                           gallery_offset, merge, idx, score);
+    else
+        hipLaunchKernelGGL(sim_topk_grouped_kernel<128>, grid, dim3(256), 0, s, queries, gallery, n_queries, n_gallery, D, k, g_offsets, n_groups,
+                           gallery_offset, merge, idx, score);
+    return hipGetLastError();
+}
+
+// rows (as jg_sim_topk_grouped returns them) -> group and position inside it: an element-wise binary search; -1 / -1 for idx < 0 or a row
+// in no group.  Hostile offsets give some group and position, nothing else.
+__global__ void group_of_rows_kernel(const int32_t* __restrict__ idx, long n, const int32_t* __restrict__ goff, int n_groups,
+                                     int gallery_offset, int32_t* __restrict__ grp, int32_t* __restrict__ pos) {
+    for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long)gridDim.x * blockDim.x) {
+        const long j = (long)idx[e] - gallery_offset;
+        int g = -1, p = -1;
+        if (idx[e] >= 0 && n_groups > 0 && j >= goff[0] && j < goff[n_groups]) {
+            int a = 0, b = n_groups;
+            while (b - a > 1) {                                  // goff[a] <= j < goff[b]
+                const int mid = (a + b) >> 1;
+                if (goff[mid] <= j) a = mid; else b = mid;
+            }
+            g = a;
+            p = (int)(j - goff[a]);
+        }
+        grp[e] = g;
+        pos[e] = p;
+    }
+}
+
+hipError_t launch_group_of_rows(const int32_t* idx, long n, const int32_t* g_offsets, int n_groups, int gallery_offset, int32_t* grp,
+                                int32_t* pos, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    if (n_groups < 0 || (n_groups > 0 && !g_offsets)) return hipErrorInvalidValue;
+    const long blocks = (n + 255) / 256;
+    hipLaunchKernelGGL(group_of_rows_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, s, idx, n, g_offsets, n_groups,
+                       gallery_offset, grp, pos);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
 // Word spotting (evaluate_spotting.py:39-82): per clip A = softmax((G C^T)/temp, dim=1) over words
 // with re-normalised rows; pred = first argmax_t A[t][w*], score = A[pred][w*].
 // One block per clip, one wave per frame row; the W logits of a row go through a per-wave LDS line.

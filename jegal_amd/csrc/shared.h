@@ -178,6 +178,15 @@ hipError_t launch_sim_rank(const float* e1, const float* e2, int n_local, int n_
 constexpr int SIM_TOPK_MAX_K = 128;
 hipError_t launch_sim_topk(const float* queries, const float* gallery, int n_queries, int n_gallery, int D, int k, int gallery_offset,
                            int merge, int32_t* idx, float* score, hipStream_t s);
+// the same over groups of gallery rows (group g = local rows g_offsets[g] .. g_offsets[g + 1] - 1, device array of n_groups + 1 entries): per
+// query row the k best groups, each as its best row (one row per group at most; rows in no group are never returned).  The offsets are
+// only ever compared with row numbers: whatever they hold, nothing outside the operands is read.  No scratch.
+hipError_t launch_sim_topk_grouped(const float* queries, const float* gallery, int n_queries, int n_gallery, int D, int k,
+                                   const int32_t* g_offsets, int n_groups, int gallery_offset, int merge, int32_t* idx, float* score,
+                                   hipStream_t s);
+// grp / pos [n]: the group that holds row idx[e] - gallery_offset and the row's place inside it; -1 / -1 for idx[e] < 0 or a row in no group
+hipError_t launch_group_of_rows(const int32_t* idx, long n, const int32_t* g_offsets, int n_groups, int gallery_offset, int32_t* grp,
+                                int32_t* pos, hipStream_t s);
 hipError_t launch_spot(const float* g, const float* c, const int32_t* goff, const int32_t* coff, const int32_t* target,
                        int n, int D, float temp, int32_t* pred, float* score, hipStream_t s);
 // A (optional; with aoff, int64 element offsets per clip) and / or best_frame / best_score (optional; they need keys: attn_matrix_key_elems(n)

@@ -8,6 +8,7 @@
     python -m jegal_amd.drivers inference_embs ...            # inference_embs.py (single clip -> <fname>.pkl)
     python -m jegal_amd.drivers attn_matrix --path F|D        # utils/plot_heatmap.py without the rendering (-> <name>.attn.npz)
     python -m jegal_amd.drivers retrieve --path D [--topk 10] # the retrieval evaluate_retrieval.py grades (-> retrieve_<direction>.npz)
+    python -m jegal_amd.drivers search --path D --query F.pkl [--level word|phrase]   # which clips gesture a word, and at which frame (-> search_<F>.npz)
     python -m jegal_amd.drivers asd --path D --file avs_asd.csv [--win N --hop M]   # the detection evaluate_asd.py grades (-> asd.npz)
 
 Same flags, file naming and on-disk formats as the reference.  What is upstream of the hot path is
@@ -536,6 +537,61 @@ def cmd_retrieve(argv, engine=None):
     return 0
 
 
+def cmd_search(argv, engine=None):
+    """For this word, or this phrase, which clips of a corpus gesture it, and at which frame: the query rows are the --query .pkl's
+    content_emb rows (--level word: one query per word) or their mean (--level phrase: one query), the gallery is every gesture_emb row of
+    the .pkl files under --path, a clip scores as its best frame (metrics.search, jg_sim_topk_grouped).  --segment N: runs of N frames
+    score on their own, so a long clip can come back with several moments.  Writes ``<res_dir>/search_<query name>.npz`` = {words (Q,): the
+    query's words (phrase: the words joined), names (N,): the .pkl base names = the clip numbering, clip (Q,K) int32, frame (Q,K) int32:
+    the frame inside the clip, score (Q,K) float32; -1 / -1 / -inf where fewer than K groups exist} and prints one line per query row.
+    engine: the Engine to run on (default: this process's)."""
+    from . import metrics as M
+    p = argparse.ArgumentParser(prog="search", description="Single process: sharding over ranks is not built for this command.")
+    p.add_argument("--path", required=True, help="a directory of JEGAL feature .pkl files: the corpus")
+    p.add_argument("--query", required=True, help="a JEGAL feature .pkl whose content_emb rows are the query")
+    p.add_argument("--level", default="word", choices=["word", "phrase"])
+    p.add_argument("--topk", type=int, default=10, help="clips (or segments) kept per query row (1..128)")
+    p.add_argument("--segment", type=int, default=0, help="frames per group; 0: a clip is one group")
+    p.add_argument("--normalize", type=int, default=1, choices=[0, 1], help="1: cosine similarity (rows re-normalised); 0: the rows as stored")
+    p.add_argument("--max_rows", type=int, default=None, help="gallery rows on the device at a time (default: all)")
+    p.add_argument("--res_dir", default=".")
+    args = p.parse_args(argv)
+    if not 1 <= args.topk <= 128:
+        raise SystemExit("--topk must be 1..128")
+    if args.segment < 0:
+        raise SystemExit("--segment must be >= 0")
+    with open(args.query, "rb") as f:
+        qf = pickle.load(f)
+    if qf.get("content_emb") is None:
+        raise SystemExit("{} holds no content_emb".format(args.query))
+    queries = np.asarray(qf["content_emb"], np.float32)
+    wb = qf["info"]["word_boundaries"] if qf.get("info") is not None and "word_boundaries" in qf["info"] else None
+    if isinstance(wb, str):
+        wb = ast.literal_eval(wb)
+    words = [str(b[0]) for b in wb] if wb is not None else ["word{}".format(i) for i in range(len(queries))]
+    if len(words) != len(queries):
+        raise ValueError("{}: {} word boundaries for {} content rows".format(args.query, len(words), len(queries)))
+    if args.level == "phrase":
+        queries, words = queries.mean(axis=0, keepdims=True), [" ".join(words)]
+    files, feats = _load_pkls(args.path)
+    feats = [(fn, ft) for fn, ft in zip(files, feats) if ft.get("gesture_emb") is not None]
+    if not feats:
+        raise SystemExit("no .pkl with gesture_emb under {}".format(args.path))
+    names = np.asarray([os.path.basename(fn)[:-len(".pkl")] for fn, _ in feats])
+    eng = engine if engine is not None else _models(args)[0]
+    clip, frame, score = M.search(queries, [np.asarray(ft["gesture_emb"], np.float32) for _, ft in feats], k=args.topk, segment=args.segment,
+                                  normalize=bool(args.normalize), engine=eng, max_rows=args.max_rows)
+    os.makedirs(args.res_dir, exist_ok=True)
+    qname = os.path.basename(args.query).rsplit(".", 1)[0]
+    out = os.path.join(args.res_dir, "search_{}.npz".format(qname))
+    np.savez(out, words=np.asarray(words), names=names, clip=clip, frame=frame, score=score)
+    for i, w in enumerate(words):
+        hits = ["{}@{} ({:.3f})".format(names[c], f, s) for c, f, s in zip(clip[i][:3], frame[i][:3], score[i][:3]) if c >= 0]
+        print("search: \"{}\" -> {} of {} clips: {}".format(w, int(np.sum(clip[i] >= 0)), len(names), ", ".join(hits) or "nothing"))
+    print("search: {} query rows x top-{} -> {}".format(len(words), args.topk, out))
+    return 0
+
+
 def cmd_asd(argv, engine=None):
     """The detection that evaluate_asd only grades: for every row of the csv whose feature .pkl exists, the probability that each of its
     candidates -- the query clip first, then its neg_files that exist, as evaluate_asd builds the list -- gestures to the query's speech.
@@ -619,6 +675,7 @@ def cmd_asd(argv, engine=None):
 COMMANDS = {
     "attn_matrix": cmd_attn_matrix,
     "retrieve": cmd_retrieve,
+    "search": cmd_search,
     "asd": cmd_asd,
     "extract_gestsync_feats": cmd_extract_gestsync_feats,
     "extract_jegal_embs": cmd_extract_jegal_embs,

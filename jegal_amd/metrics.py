@@ -78,6 +78,89 @@ def retrieve(emb_q, emb_g, k=10, engine=None):
     return _host(idx), _host(score)
 
 
+def search_groups(lengths, segment=0):
+    """The groups search() cuts a list of clips into: (g_offsets (G + 1,) int64 over the concatenated frame rows, clip (G,) int32, start (G,)
+    int32 = the group's first frame inside its clip).  segment == 0: one group per clip; segment > 0: runs of `segment` frames, the last run
+    of a clip shorter, every clip ending a group."""
+    sizes, clip, start = [], [], []
+    for i, t in enumerate(int(t) for t in lengths):
+        step = segment if segment > 0 else max(t, 1)
+        for s in range(0, max(t, 1), step):            # (an empty clip is one empty group)
+            sizes.append(min(step, t - s))
+            clip.append(i)
+            start.append(s)
+    off = np.zeros(len(sizes) + 1, np.int64)
+    off[1:] = np.cumsum(sizes)
+    return off, np.asarray(clip, np.int32), np.asarray(start, np.int32)
+
+
+def search(queries, clips, k=10, segment=0, normalize=True, engine=None, max_rows=None):
+    """For each query row (a word, a phrase: (Q, D), the space of the content embeddings), the k clips of a corpus that gesture it and the
+    frame at which they do: clips is a list of (T_i, D) frame-level gesture arrays; a clip scores as its best frame (jg_sim_topk_grouped:
+    no pooling, no Q x sum T matrix, scores as jg_sim_topk computes them).  segment > 0: the groups are runs of `segment` frames of a clip
+    instead of whole clips, so a long track can come back with several moments.  normalize: rows are L2-normalised first (cosine
+    similarity); False: the rows as stored.  max_rows: the gallery goes to the device in pieces of at most that many rows, cut at group
+    boundaries and merged -- the same result, for corpora larger than device memory.
+    Returns host arrays (clip (Q, k) int32, frame (Q, k) int32: the frame inside the clip, score (Q, k) float32), best first, ties to the
+    earlier clip and frame; -1 / -1 / -inf where fewer than k groups exist."""
+    k, segment = int(k), int(segment)
+    if not 1 <= k <= 128:
+        raise ValueError("k must be 1..128")
+    if segment < 0:
+        raise ValueError("segment must be >= 0 (0: one group per clip)")
+    q = _tensor(queries)
+    if q.ndim != 2:
+        raise ValueError("queries must be (Q, D)")
+    Q, D = int(q.shape[0]), int(q.shape[1])
+    clips = [c if isinstance(c, torch.Tensor) else np.asarray(c, np.float32) for c in clips]
+    if any(c.ndim != 2 or c.shape[1] != D for c in clips):
+        raise ValueError("every clip must be (T_i, {}) like the queries".format(D))
+    goff, gclip, gstart = search_groups([c.shape[0] for c in clips], segment)
+    n_groups = len(gclip)
+    if goff[-1] > 2 ** 31 - 1:
+        raise ValueError("more than INT32_MAX gallery rows")
+    sizes = np.diff(goff)
+    if max_rows is not None and (int(max_rows) < 1 or (n_groups and sizes.max() > int(max_rows))):
+        raise ValueError("max_rows must hold the largest group ({} rows): groups are never split; use segment".format(int(sizes.max()) if n_groups else 0))
+    empty = (np.full((Q, k), -1, np.int32), np.full((Q, k), -1, np.int32), np.full((Q, k), -np.inf, np.float32))
+    if Q == 0 or goff[-1] == 0:
+        return empty
+    eng = engine or Engine.get()
+    if normalize:
+        q = eng.l2norm(q)
+    # pieces = runs of whole groups of at most max_rows rows
+    cuts, g0 = [], 0
+    while g0 < n_groups:
+        g1 = g0 + 1
+        if max_rows is None:
+            g1 = n_groups
+        else:
+            while g1 < n_groups and goff[g1 + 1] - goff[g0] <= int(max_rows):
+                g1 += 1
+        cuts.append((g0, g1))
+        g0 = g1
+    first_clip = np.concatenate([[0], np.cumsum([c.shape[0] for c in clips])])
+    res = None
+    for g0, g1 in cuts:
+        r0, r1 = int(goff[g0]), int(goff[g1])
+        if r1 == r0:
+            continue
+        c0, c1 = int(gclip[g0]), int(gclip[g1 - 1]) + 1                      # the clips the piece's rows come from
+        rows = [torch.as_tensor(c) for c in clips[c0:c1]]
+        rows = torch.cat(rows, 0)[r0 - int(first_clip[c0]):r1 - int(first_clip[c0])].to(torch.float32)
+        if normalize:
+            rows = eng.l2norm(rows)
+        res = eng.sim_topk_grouped(q, rows, goff[g0:g1 + 1] - r0, k, gallery_offset=r0, merge_into=res)
+    if res is None:
+        return empty
+    grp, pos = eng.group_of_rows(res[0], goff, 0)
+    grp, pos, score = _host(grp).astype(np.int64), _host(pos).astype(np.int32), _host(res[1]).astype(np.float32)
+    found = grp >= 0
+    clip = np.where(found, gclip[np.maximum(grp, 0)], -1).astype(np.int32)
+    frame = np.where(found, gstart[np.maximum(grp, 0)] + pos, -1).astype(np.int32)
+    return clip, frame, score
+
+
 def partner_ranks(emb1, emb2, engine=None):
     """jg_sim_rank's rank of every query's own partner (row i of emb1 belongs to row i of emb2), the number retrieval_metrics turns into
     R@K: host int32 (N,), over all ranks' rows in rank order when sharded."""
