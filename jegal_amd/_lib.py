@@ -755,23 +755,22 @@ class Engine:
         self._ck(self.lib.jg_sim_rank(self.h, _ptr(e1), _ptr(e2), n_local, e2.shape[0], row_offset, D, _ptr(rank), _ptr(ties)))
         return rank, ties
 
-    def sim_topk(self, queries, gallery, k, gallery_offset=0, merge_into=None):
-        """jg_sim_topk: per query row the k gallery rows with the largest <q_i, g_j> (rows as stored: normalise first, as for sim_rank), best
-        first; on equal scores the smaller gallery row first.  queries (n, D) / gallery (m, D), D % 64 == 0, 1 <= k <= 128.
-        Returns (idx (n, k) int32 = gallery_offset + j, score (n, k) float32) as device tensors; slots beyond the candidates are -1 / -inf.
-        merge_into = (idx, score) of an earlier call with the same queries and k on OTHER gallery rows: the two are updated in place to the
-        best k of the union and returned (a gallery too large for the device goes through in pieces, each with its gallery_offset)."""
+    def _sim_topk_args(self, entry, queries, gallery, k, gallery_offset, merge_into, g_offsets=None):
+        """What sim_topk and sim_topk_grouped (`entry`; the latter passes g_offsets) share: the checks of the shapes, k, gallery_offset,
+        the group offsets and merge_into, then the stream, and the result to fill: merge_into's pair, or an empty one (-1 / -inf).
+        Returns (rows of queries, rows of gallery, D, k, gallery_offset, groups or None, idx, score)."""
         qs, gs = tuple(queries.shape), tuple(gallery.shape)
         if len(qs) != 2 or len(gs) != 2 or qs[1] != gs[1] or qs[1] <= 0 or qs[1] % 64:
             raise ValueError("queries / gallery must be (rows, D) with the same D, a positive multiple of 64")
         k, gallery_offset = int(k), int(gallery_offset)
         if not 1 <= k <= 128:
-            raise ValueError("jg_sim_topk limit: 1 <= k <= 128")
+            raise ValueError(f"jg_{entry} limit: 1 <= k <= 128")
         if gallery_offset < 0 or gallery_offset + gs[0] > 2 ** 31 - 1:
             raise ValueError("gallery_offset must be >= 0 and gallery_offset + gallery rows <= INT32_MAX")
+        n_groups = None if g_offsets is None else self._check_group_offsets(g_offsets, gs[0])
         if merge_into is not None:
             if not isinstance(merge_into, (tuple, list)) or len(merge_into) != 2 or not all(isinstance(t, torch.Tensor) for t in merge_into):
-                raise ValueError("merge_into must be the (idx, score) pair of an earlier sim_topk call")
+                raise ValueError(f"merge_into must be the (idx, score) pair of an earlier {entry} call")
             idx, score = merge_into
             if (tuple(idx.shape) != (qs[0], k) or tuple(score.shape) != (qs[0], k) or idx.dtype != torch.int32 or score.dtype != torch.float32
                     or not idx.is_contiguous() or not score.is_contiguous()):
@@ -779,13 +778,21 @@ class Engine:
             if idx.device != self.device or score.device != self.device:
                 raise ValueError(f"merge_into must be on {self.device}")
         self._bind_stream()
-        q, g = self._f32(queries), self._f32(gallery)
         if merge_into is None:
             idx = torch.full((qs[0], k), -1, dtype=torch.int32, device=self.device)
             score = torch.full((qs[0], k), float("-inf"), dtype=torch.float32, device=self.device)
-        if qs[0] and gs[0]:                            # (no gallery row: nothing to merge, or the empty result above)
-            self._ck(self.lib.jg_sim_topk(self.h, _ptr(q), _ptr(g), qs[0], gs[0], qs[1], k, gallery_offset, int(merge_into is not None),
-                                          _ptr(idx), _ptr(score)))
+        return qs[0], gs[0], qs[1], k, gallery_offset, n_groups, idx, score
+
+    def sim_topk(self, queries, gallery, k, gallery_offset=0, merge_into=None):
+        """jg_sim_topk: per query row the k gallery rows with the largest <q_i, g_j> (rows as stored: normalise first, as for sim_rank), best
+        first; on equal scores the smaller gallery row first.  queries (n, D) / gallery (m, D), D % 64 == 0, 1 <= k <= 128.
+        Returns (idx (n, k) int32 = gallery_offset + j, score (n, k) float32) as device tensors; slots beyond the candidates are -1 / -inf.
+        merge_into = (idx, score) of an earlier call with the same queries and k on OTHER gallery rows: the two are updated in place to the
+        best k of the union and returned (a gallery too large for the device goes through in pieces, each with its gallery_offset)."""
+        n, m, D, k, gallery_offset, _, idx, score = self._sim_topk_args("sim_topk", queries, gallery, k, gallery_offset, merge_into)
+        q, g = self._f32(queries), self._f32(gallery)
+        if n and m:                                    # (no gallery row: nothing to merge, or the empty result)
+            self._ck(self.lib.jg_sim_topk(self.h, _ptr(q), _ptr(g), n, m, D, k, gallery_offset, int(merge_into is not None), _ptr(idx), _ptr(score)))
         return idx, score
 
     @staticmethod
@@ -810,31 +817,11 @@ class Engine:
         first, on equal scores the smaller row; never two rows of one group; -1 / -inf where fewer than k groups have a row.  Scores are
         those of sim_topk / sim_rank bit for bit.  merge_into = (idx, score) of an earlier call with the same queries and k on OTHER
         gallery rows, cut at group boundaries: updated in place to the best k of the union and returned."""
-        qs, gs = tuple(queries.shape), tuple(gallery.shape)
-        if len(qs) != 2 or len(gs) != 2 or qs[1] != gs[1] or qs[1] <= 0 or qs[1] % 64:
-            raise ValueError("queries / gallery must be (rows, D) with the same D, a positive multiple of 64")
-        k, gallery_offset = int(k), int(gallery_offset)
-        if not 1 <= k <= 128:
-            raise ValueError("jg_sim_topk_grouped limit: 1 <= k <= 128")
-        if gallery_offset < 0 or gallery_offset + gs[0] > 2 ** 31 - 1:
-            raise ValueError("gallery_offset must be >= 0 and gallery_offset + gallery rows <= INT32_MAX")
-        n_groups = self._check_group_offsets(g_offsets, gs[0])
-        if merge_into is not None:
-            if not isinstance(merge_into, (tuple, list)) or len(merge_into) != 2 or not all(isinstance(t, torch.Tensor) for t in merge_into):
-                raise ValueError("merge_into must be the (idx, score) pair of an earlier sim_topk_grouped call")
-            idx, score = merge_into
-            if (tuple(idx.shape) != (qs[0], k) or tuple(score.shape) != (qs[0], k) or idx.dtype != torch.int32 or score.dtype != torch.float32
-                    or not idx.is_contiguous() or not score.is_contiguous()):
-                raise ValueError(f"merge_into must be contiguous (idx int32, score float32) tensors of shape ({qs[0]}, {k})")
-            if idx.device != self.device or score.device != self.device:
-                raise ValueError(f"merge_into must be on {self.device}")
-        self._bind_stream()
+        n, m, D, k, gallery_offset, n_groups, idx, score = self._sim_topk_args("sim_topk_grouped", queries, gallery, k, gallery_offset,
+                                                                               merge_into, g_offsets)
         q, g, off = self._f32(queries), self._f32(gallery), self._i32(g_offsets)
-        if merge_into is None:
-            idx = torch.full((qs[0], k), -1, dtype=torch.int32, device=self.device)
-            score = torch.full((qs[0], k), float("-inf"), dtype=torch.float32, device=self.device)
-        if qs[0] and gs[0] and n_groups:               # (no gallery row, no group: nothing to merge, or the empty result above)
-            self._ck(self.lib.jg_sim_topk_grouped(self.h, _ptr(q), _ptr(g), qs[0], gs[0], qs[1], k, _ptr(off), n_groups, gallery_offset,
+        if n and m and n_groups:                       # (no gallery row, no group: nothing to merge, or the empty result)
+            self._ck(self.lib.jg_sim_topk_grouped(self.h, _ptr(q), _ptr(g), n, m, D, k, _ptr(off), n_groups, gallery_offset,
                                                   int(merge_into is not None), _ptr(idx), _ptr(score)))
         return idx, score
 

@@ -498,15 +498,22 @@ int jg_sim_rank(jg_handle* h, const float* e1, const float* e2, int n_local, int
     return timed(h, JG_ST_MISC, [&] { return launch_sim_rank(e1, e2, n_local, n_total, row_offset, D, rank, ties, h->stream); });
 }
 
+// the arguments jg_sim_topk and jg_sim_topk_grouped share (`entry` names the caller in the geometry message; n_groups: 0 for the former)
+static int sim_topk_check(jg_handle* h, const char* entry, const float* queries, const float* gallery, int n_queries, int n_gallery, int D,
+                          int k, int n_groups, int gallery_offset) {
+    if (k < 1 || k > SIM_TOPK_MAX_K) JG_FAIL(h, JG_ERR_ARG, "k must be 1..%d", SIM_TOPK_MAX_K);
+    if (D <= 0 || D % 64) JG_FAIL(h, JG_ERR_ARG, "D must be a positive multiple of 64");
+    if (n_queries < 0 || n_gallery < 0 || n_groups < 0 || gallery_offset < 0 || gallery_offset > INT32_MAX - n_gallery)
+        JG_FAIL(h, JG_ERR_ARG, "bad %s geometry (counts and gallery_offset >= 0, gallery_offset + n_gallery <= INT32_MAX)", entry);
+    if ((reinterpret_cast<uintptr_t>(queries) | reinterpret_cast<uintptr_t>(gallery)) & 15) JG_FAIL(h, JG_ERR_ARG, "queries / gallery must be 16-byte aligned");
+    return JG_OK;
+}
+
 int jg_sim_topk(jg_handle* h, const float* queries, const float* gallery, int n_queries, int n_gallery, int D, int k,
                 int gallery_offset, int merge, int32_t* idx, float* score) {
     ENTER(h);
     if (!queries || !gallery || !idx || !score) JG_FAIL(h, JG_ERR_ARG, "null buffer");
-    if (k < 1 || k > SIM_TOPK_MAX_K) JG_FAIL(h, JG_ERR_ARG, "k must be 1..%d", SIM_TOPK_MAX_K);
-    if (D <= 0 || D % 64) JG_FAIL(h, JG_ERR_ARG, "D must be a positive multiple of 64");
-    if (n_queries < 0 || n_gallery < 0 || gallery_offset < 0 || gallery_offset > INT32_MAX - n_gallery)
-        JG_FAIL(h, JG_ERR_ARG, "bad sim_topk geometry (counts and gallery_offset >= 0, gallery_offset + n_gallery <= INT32_MAX)");
-    if ((reinterpret_cast<uintptr_t>(queries) | reinterpret_cast<uintptr_t>(gallery)) & 15) JG_FAIL(h, JG_ERR_ARG, "queries / gallery must be 16-byte aligned");
+    RET(sim_topk_check(h, "sim_topk", queries, gallery, n_queries, n_gallery, D, k, 0, gallery_offset));
     if (n_queries == 0) return JG_OK;
     return timed(h, JG_ST_MISC, [&] {
         return launch_sim_topk(queries, gallery, n_queries, n_gallery, D, k, gallery_offset, merge, idx, score, h->stream);
@@ -517,11 +524,7 @@ int jg_sim_topk_grouped(jg_handle* h, const float* queries, const float* gallery
                         const int32_t* g_offsets, int n_groups, int gallery_offset, int merge, int32_t* idx, float* score) {
     ENTER(h);
     if (!queries || !gallery || !idx || !score || (n_groups > 0 && !g_offsets)) JG_FAIL(h, JG_ERR_ARG, "null buffer");
-    if (k < 1 || k > SIM_TOPK_MAX_K) JG_FAIL(h, JG_ERR_ARG, "k must be 1..%d", SIM_TOPK_MAX_K);
-    if (D <= 0 || D % 64) JG_FAIL(h, JG_ERR_ARG, "D must be a positive multiple of 64");
-    if (n_queries < 0 || n_gallery < 0 || n_groups < 0 || gallery_offset < 0 || gallery_offset > INT32_MAX - n_gallery)
-        JG_FAIL(h, JG_ERR_ARG, "bad sim_topk_grouped geometry (counts and gallery_offset >= 0, gallery_offset + n_gallery <= INT32_MAX)");
-    if ((reinterpret_cast<uintptr_t>(queries) | reinterpret_cast<uintptr_t>(gallery)) & 15) JG_FAIL(h, JG_ERR_ARG, "queries / gallery must be 16-byte aligned");
+    RET(sim_topk_check(h, "sim_topk_grouped", queries, gallery, n_queries, n_gallery, D, k, n_groups, gallery_offset));
     if (n_queries == 0) return JG_OK;
     return timed(h, JG_ST_MISC, [&] {
         return launch_sim_topk_grouped(queries, gallery, n_queries, n_gallery, D, k, g_offsets, n_groups, gallery_offset, merge, idx, score,

@@ -226,6 +226,31 @@ def test_consistent_with_sim_rank(eng, planted, planted_single, k):
         assert np.array_equal(bits(np.concatenate([p[1] for p in parts])), bits(score))
 
 
+@pytest.mark.parametrize("D", [64, 192])
+def test_rank_and_ties_follow_from_the_topk_bits(eng, D):
+    """One tile loop serves both kernels: k = 128 returns every one of 100 scores per query, and jg_sim_rank's rank / ties are the counts
+    of those very bits above / equal to the query's own (row_offset + i).  Two gallery tiles (the second partial), two query blocks (the
+    second of one row), one (D = 64) and three (D = 192) k chunks; gallery rows 3 and 70 are equal, and each is some query's own row."""
+    rng = np.random.default_rng(4350 + D)
+    g = rng.standard_normal((100, D)).astype(np.float32)
+    q = rng.standard_normal((65, D)).astype(np.float32)
+    g[70] = g[3]
+    qd, gd = dev(q), dev(g)
+    idx, score = call(eng, qd, gd, 128)
+    assert np.all(idx[:, 100:] == -1) and np.all(np.isneginf(score[:, 100:]))
+    assert np.array_equal(np.sort(idx[:, :100], axis=1), np.tile(np.arange(100, dtype=np.int32), (65, 1)))
+    s = np.empty((65, 100), np.float32)
+    np.put_along_axis(s, idx[:, :100].astype(np.int64), score[:, :100], axis=1)
+    assert np.array_equal(bits(s[:, 3]), bits(s[:, 70]))
+    for row_offset in (0, 35):
+        rank, ties = (t.cpu().numpy() for t in eng.sim_rank(qd, gd, row_offset=row_offset))
+        own = s[np.arange(65), row_offset + np.arange(65)][:, None]
+        want_rank, want_ties = np.sum(s > own, axis=1), np.sum(s == own, axis=1)
+        assert want_ties[(3, 70)[row_offset > 0] - row_offset] >= 2           # (query 3 owns row 3, query 35 row 70: the equal pair)
+        assert np.array_equal(rank, want_rank), (D, row_offset)
+        assert np.array_equal(ties, want_ties), (D, row_offset)
+
+
 # ------------------------------------------------------------------------------------------------ 4. float64
 @pytest.mark.parametrize("k", [10, 128])
 def test_against_float64_planted(planted, planted_single, k):

@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
 """Kernel-by-kernel comparison of the gfx950 code of two builds of libjegal_hip.so: what a refactor of a kernel has to show.
 
-    python tools/kernel_isa_diff.py OLD.so NEW.so [--strict]
+    python tools/kernel_isa_diff.py OLD.so NEW.so [--strict] [--rename OLDNAME=NEWNAME ...]
 
 For every kernel it says whether the instruction stream is identical (addresses, comments, labels and directives stripped); for the
 ones that differ it prints old -> new: instruction count, vgpr / sgpr count, VGPR / SGPR spills, scratch and LDS bytes
 (tools/kernel_resources.py) and the number of MFMA, LDS-DMA, s_barrier and global-store instructions.  Exit status 1 if the kernel
-name sets differ; with --strict also if any kernel differs."""
+name sets differ; with --strict also if any kernel differs.  --rename: a kernel that the refactor renamed (names without the parameter
+list, as in 'sim_topk_grouped_kernel<64>=sim_topk_kernel<64, true>'); OLD's kernel is compared with, and reported as, NEW's."""
 import os
 import re
 import subprocess
@@ -71,11 +72,22 @@ def compare(so, sn, mo, mn, out=print):
     return differ, set(so) == set(sn)
 
 
+def bare(name):
+    """a demangled kernel name without its return type and parameter list"""
+    return name.split("(")[0].replace("void ", "").strip()
+
+
 def main(argv):
     strict = "--strict" in argv
-    old_lib, new_lib = [a for a in argv if a != "--strict"]
+    renames = dict(argv[i + 1].split("=", 1) for i, a in enumerate(argv) if a == "--rename")
+    old_lib, new_lib = [a for i, a in enumerate(argv) if a not in ("--strict", "--rename") and (i == 0 or argv[i - 1] != "--rename")]
     mo, mn = kernel_resources(old_lib), kernel_resources(new_lib)
-    differ, same_names = compare(streams(old_lib, mo), streams(new_lib, mn), mo, mn)
+    so, sn = streams(old_lib, mo), streams(new_lib, mn)
+    for old, new in renames.items():
+        (ko,), (kn,) = [k for k in so if bare(k) == old], [k for k in sn if bare(k) == new]
+        print(f"renamed: {old} -> {new}")
+        so[kn], mo[kn] = so.pop(ko), mo.pop(ko)
+    differ, same_names = compare(so, sn, mo, mn)
     return 1 if not same_names or (strict and differ) else 0
 
 

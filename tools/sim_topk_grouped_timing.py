@@ -6,11 +6,16 @@ events:
   grouped_per_clip            jg_sim_topk_grouped, one group per clip: what metrics.search runs
   grouped_per_row             groups of one row: jg_sim_topk's result through the grouped epilogue and flush
   grouped_one_group           one group over everything: the list never fills, every score is queued and replaces the champion or is dropped
+--baseline-lib: another build of libjegal_hip.so (the parent commit's, when kernels are to be compared across builds): every variant then
+runs from both libraries, this build's call and the other's next to each other, and so does the other's jg_sim_rank on the same rows; the
+result carries the other's figures ("baseline"), the per-iteration ratios this build / other ("over_baseline") and the other's spread:
+max / min - 1 over the iterations of its variant / its own jg_sim_rank.
 FLOPs come from the shapes: 2 Q N D; roof 157 TFLOP/s (fp32 MFMA).
 The queue model is arithmetic on the first workgroup's 64 query rows (torch, on the device, from the matrix the kernels never write): per
 64-row tile, with the threshold of a row = its k-th best score (rows) or k-th best group champion (groups) over the tiles before, the keys
 that pass it (= keys queued = insertions attempted) and the rows with a non-empty queue (= row flushes).
-  python tools/sim_topk_grouped_timing.py [--iters 10] [--clips 4000] [--frames 150] [--queries 1000] [--out profiles/sim_topk_grouped_timing.json]"""
+  python tools/sim_topk_grouped_timing.py [--iters 10] [--clips 4000] [--frames 150] [--queries 1000] [--baseline-lib PATH]
+         [--out profiles/sim_topk_grouped_timing.json]"""
 import argparse
 import ctypes
 import json
@@ -72,6 +77,7 @@ def main():
     ap.add_argument("--frames", type=int, default=150)
     ap.add_argument("--queries", type=int, default=1000)
     ap.add_argument("--no-model", action="store_true")
+    ap.add_argument("--baseline-lib", default=None)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "sim_topk_grouped_timing.json"))
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -91,23 +97,39 @@ def main():
             "grouped_one_group": torch.tensor([0, N], dtype=torch.int32, device="cuda")}
     names = ["jg_sim_topk"] + list(offs)
     outs = {n: (torch.empty((Q, K), dtype=torch.int32, device="cuda"), torch.empty((Q, K), dtype=torch.float32, device="cuda")) for n in names}
+    libs = {"": (lib, h)}                                          # variant name prefix -> (library, handle)
+    if args.baseline_lib:
+        base_lib = ctypes.CDLL(os.path.abspath(args.baseline_lib))
+        base_h = ctypes.c_void_p()
+        assert base_lib.jg_create(0, ctypes.byref(base_h)) == 0
+        for fn in ("jg_sim_rank", "jg_sim_topk", "jg_sim_topk_grouped", "jg_set_stream"):
+            getattr(base_lib, fn).argtypes = getattr(lib, fn).argtypes
+        assert base_lib.jg_set_stream(base_h, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)) == 0
+        libs["baseline/"] = (base_lib, base_h)
+        rank = torch.empty(Q, dtype=torch.int32, device="cuda")
+        ties = torch.empty(Q, dtype=torch.int32, device="cuda")
 
     def run(name):
-        i, s = outs[name]
-        if name == "jg_sim_topk":
-            rc = lib.jg_sim_topk(h, P(q), P(g), Q, N, D, K, 0, 0, P(i), P(s))
+        l, lh = libs["baseline/" if name.startswith("baseline/") else ""]
+        name = name.replace("baseline/", "")
+        if name == "jg_sim_rank":
+            rc = l.jg_sim_rank(lh, P(q), P(g), Q, N, 0, D, P(rank), P(ties))
+        elif name == "jg_sim_topk":
+            rc = l.jg_sim_topk(lh, P(q), P(g), Q, N, D, K, 0, 0, P(outs[name][0]), P(outs[name][1]))
         else:
-            rc = lib.jg_sim_topk_grouped(h, P(q), P(g), Q, N, D, K, P(offs[name]), offs[name].numel() - 1, 0, 0, P(i), P(s))
-        assert rc == 0, lib.jg_last_error(h)
+            rc = l.jg_sim_topk_grouped(lh, P(q), P(g), Q, N, D, K, P(offs[name]), offs[name].numel() - 1, 0, 0, P(outs[name][0]), P(outs[name][1]))
+        assert rc == 0, name
 
+    # the other build's call first: what is left in `outs` and checked below is this build's
+    runs = [pre + n for n in names for pre in reversed(list(libs))] + (["baseline/jg_sim_rank"] if args.baseline_lib else [])
     for _ in range(args.warmup):
-        for n in names:
+        for n in runs:
             run(n)
     torch.cuda.synchronize()
-    times = {n: [] for n in names}
+    times = {n: [] for n in runs}
     for _ in range(args.iters):
         evs = []
-        for n in names:
+        for n in runs:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
             run(n)
@@ -120,8 +142,19 @@ def main():
     res = {"input": f"{C} clips x {T} frames, D = {D}, unit rows (random walk per clip), {Q} query rows = noisy corpus frames, k = {K}",
            "iters": args.iters, "flop": flop, "fp32_mfma_flop_per_s": MFMA32_FLOPS, "workgroups": -(-Q // 64), "tiles_per_workgroup": -(-N // 64)}
     yard = np.asarray(times["jg_sim_topk"])
+
+    def ratio(a, b):
+        r = np.asarray(times[a]) / np.asarray(times[b])
+        return {"median": float(np.median(r)), "min": float(r.min()), "max": float(r.max())}
+
     for n in names:
         res[n] = summarise(times[n], flop)
+        if args.baseline_lib:
+            base = summarise(times["baseline/" + n], flop)
+            base["over_jg_sim_rank"] = ratio("baseline/" + n, "baseline/jg_sim_rank")
+            base["spread"] = base["over_jg_sim_rank"]["max"] / base["over_jg_sim_rank"]["min"] - 1.0
+            res[n]["baseline"] = base
+            res[n]["over_baseline"] = ratio(n, "baseline/" + n)
         if n != "jg_sim_topk":
             r = np.asarray(times[n]) / yard
             res[n]["over_jg_sim_topk"] = {"median": float(np.median(r)), "min": float(r.min()), "max": float(r.max())}
@@ -148,6 +181,9 @@ def main():
         json.dump(res, f, indent=1)
         f.write("\n")
     print(json.dumps(res))
+    if args.baseline_lib:
+        base_lib.jg_destroy.argtypes = [ctypes.c_void_p]
+        base_lib.jg_destroy(base_h)
     eng.close()
     return 0
 

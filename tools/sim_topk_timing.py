@@ -1,8 +1,10 @@
 """Time jg_sim_topk next to jg_sim_rank and next to the route without it (torch.mm + torch.topk, which writes the N x N matrix) on
 synth.planted_retrieval(1237, N), rows normalised on the engine, device-resident.  GPU only, no fallback.
 Each iteration runs every variant back to back, each call between its own pair of device events, so the variants alternate in one
-process and every iteration is one comparison.  --baseline-lib: another build of libjegal_hip.so whose jg_sim_rank is the yardstick
-(the parent commit's, when the tile loop of the two kernels is to be compared across builds); default: this build's.
+process and every iteration is one comparison.  --baseline-lib: another build of libjegal_hip.so (the parent commit's, when kernels are
+to be compared across builds): every jg_ variant then runs from both libraries, this build's call and the other's next to each other, the
+other's jg_sim_rank is the yardstick, and the result carries the other's figures ("baseline"), the per-iteration ratios this build /
+other ("over_baseline") and the other's spread: max / min - 1 over the iterations of its variant / its own jg_sim_rank.
 FLOPs come from the shapes: 2 N^2 D; roof 157 TFLOP/s (fp32 MFMA).
 The flush model is host arithmetic on the first --model-blocks workgroups (64 query rows each): with the threshold of a row = its k-th
 best score over the tiles before, per 64-column tile the number of scores that pass it (= keys queued; the flush inserts those that still beat the running threshold) and the rows with a
@@ -76,27 +78,31 @@ def main():
     ties = torch.empty(N, dtype=torch.int32, device="cuda")
     outs = {k: (torch.empty((N, k), dtype=torch.int32, device="cuda"), torch.empty((N, k), dtype=torch.float32, device="cuda")) for k in KS}
 
-    base_lib, base_h = lib, h
+    libs = {"": (lib, h)}                                  # variant name prefix -> (library, handle)
     if args.baseline_lib:
         base_lib = ctypes.CDLL(os.path.abspath(args.baseline_lib))
         base_h = ctypes.c_void_p()
         assert base_lib.jg_create(0, ctypes.byref(base_h)) == 0
-        base_lib.jg_sim_rank.argtypes = lib.jg_sim_rank.argtypes
-        base_lib.jg_set_stream.argtypes = lib.jg_set_stream.argtypes
+        for fn in ("jg_sim_rank", "jg_sim_topk", "jg_set_stream"):
+            getattr(base_lib, fn).argtypes = getattr(lib, fn).argtypes
         assert base_lib.jg_set_stream(base_h, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)) == 0
+        libs["baseline/"] = (base_lib, base_h)
 
-    def sim_rank():
-        assert base_lib.jg_sim_rank(base_h, P(q), P(g), N, N, 0, D, P(rank), P(ties)) == 0
+    def sim_rank(l, lh):
+        assert l.jg_sim_rank(lh, P(q), P(g), N, N, 0, D, P(rank), P(ties)) == 0
 
-    def topk(k):
-        assert lib.jg_sim_topk(h, P(q), P(g), N, N, D, k, 0, 0, P(outs[k][0]), P(outs[k][1])) == 0, lib.jg_last_error(h)
+    def topk(l, lh, k):
+        assert l.jg_sim_topk(lh, P(q), P(g), N, N, D, k, 0, 0, P(outs[k][0]), P(outs[k][1])) == 0
 
     torch_out = {}
 
     def torch_route():
         torch_out["r"] = torch.topk(torch.mm(q, g.t()), 10, dim=1)
 
-    variants = [("jg_sim_rank", sim_rank)] + [(f"jg_sim_topk_k{k}", (lambda k=k: topk(k))) for k in KS] + [("torch_mm_topk_k10", torch_route)]
+    jg = [("jg_sim_rank", sim_rank)] + [(f"jg_sim_topk_k{k}", (lambda l, lh, k=k: topk(l, lh, k))) for k in KS]
+    # the other build's call first: what is left in `outs` and compared with torch below is this build's
+    variants = [(pre + name, (lambda fn=fn, pre=pre: fn(*libs[pre]))) for name, fn in jg for pre in reversed(list(libs))]
+    variants.append(("torch_mm_topk_k10", torch_route))
     for _ in range(args.warmup):
         for _, fn in variants:
             fn()
@@ -115,13 +121,25 @@ def main():
             times[name].append(e0.elapsed_time(e1))
     flop = 2.0 * N * N * D
     res = {"input": f"synth.planted_retrieval(1237, {N}), D = {D}, rows normalised by jg_l2norm", "iters": args.iters, "flop": flop,
-           "fp32_mfma_flop_per_s": MFMA32_FLOPS, "jg_sim_rank_from": args.baseline_lib or "this build"}
+           "fp32_mfma_flop_per_s": MFMA32_FLOPS, "jg_sim_rank_from": os.path.basename(args.baseline_lib) if args.baseline_lib else "this build"}
+
+    def ratio(a, b):
+        r = np.asarray(times[a]) / np.asarray(times[b])
+        return {"median": float(np.median(r)), "min": float(r.min()), "max": float(r.max())}
+
+    yard = "baseline/jg_sim_rank" if args.baseline_lib else "jg_sim_rank"
     for name, _ in variants:
+        if name.startswith("baseline/"):
+            continue
         res[name] = summarise(times[name], flop)
-    yard = np.asarray(times["jg_sim_rank"])
-    for name, _ in variants[1:]:
-        r = np.asarray(times[name]) / yard
-        res[name]["over_jg_sim_rank"] = {"median": float(np.median(r)), "min": float(r.min()), "max": float(r.max())}
+        if name != "jg_sim_rank":
+            res[name]["over_jg_sim_rank"] = ratio(name, yard)
+        if "baseline/" + name in times:
+            base = summarise(times["baseline/" + name], flop)
+            base["over_jg_sim_rank"] = ratio("baseline/" + name, yard)
+            base["spread"] = base["over_jg_sim_rank"]["max"] / base["over_jg_sim_rank"]["min"] - 1.0
+            res[name]["baseline"] = base
+            res[name]["over_baseline"] = ratio(name, "baseline/" + name)
     # what the device route and the torch route agree on: the share of equal neighbours at k = 10 (their summation orders differ)
     res["k10_indices_equal_to_torch_share"] = float((outs[10][0].cpu() == torch_out["r"].indices.cpu().to(torch.int32)).float().mean())
     qh, gh = q.cpu().numpy(), g.cpu().numpy()
