@@ -9,6 +9,7 @@
 #include "weight_form.h"
 #include "../../include/jegal_hip.h"
 #include "audit32.h"
+#include "gemm_x3.h"
 
 #include <cmath>
 #include <cstdio>
@@ -404,8 +405,54 @@ int gemm(jg_handle* h, int stage, const f16* A, long lda, int M, const Lin& L, c
 int gemm32(jg_handle* h, int stage, const float* A, long lda, int M, const Lin& L, float* out, const Epi32& e = Epi32(), const ConvGeom* g = nullptr);
 int gemm_x3(jg_handle* h, int stage, const float* A, long lda, int M, const Lin& L, float* out, const Epi32& e = Epi32());
 ConvGeom geom(int H, int W, int C, int KH, int KW, int SH, int SW, int PH, int PW, bool reorder = false);
-int post_norm_layer32(jg_handle* h, const EncLayer& L, float* x32, float* t32, float* qkv, float* att, float* hid, const float* mask, int B, int S,
-                      int H, int D, int Dff, int act, float* out);
+
+// ------------------------------------------------------------------------------------ the arithmetic of a model graph (linear.hip)
+// A model graph is written once, templated on the element type T of its activations, and takes its arithmetic as a value: Arith<f16> is
+// the handle's 16-bit build (gemm() and LAUNCH: fp16, or bf16 on a bf16 handle), Arith<float> the fp32 kernels -- the fp32 MFMA of the
+// audit path (gemm32) or, x3, the split operands on the fp16 matrix cores (gemm_x3: the ends of the JEGAL branches in the fp16 contract
+// modes).  The residual stream between sub-layers is fp32 in every arithmetic.  One overload per primitive and arithmetic; stage tags:
+// a linear layer is JG_ST_CONV with a geometry and JG_ST_GEMM without, the others are what their names say.
+template <class T> struct Arith {};
+template <> struct Arith<float> { bool x3 = false; };
+using A16 = Arith<f16>;
+using A32 = Arith<float>;
+// out = act(A W^T + b), T activations (act: 0 none, 1 ReLU, 2 exact GELU)
+int linear(jg_handle* h, A16 ar, const f16* A, long lda, int M, const Lin& L, f16* out, int act = 0, const ConvGeom* g = nullptr);
+int linear(jg_handle* h, A32 ar, const float* A, long lda, int M, const Lin& L, float* out, int act = 0, const ConvGeom* g = nullptr);
+// out32 = A W^T + b + res[m % res_mod]: into the fp32 stream (res and out32 may be the same rows) or a stage's fp32 output
+int linear_to32(jg_handle* h, A16 ar, const f16* A, long lda, int M, const Lin& L, float* out32, const float* res = nullptr, long ldr = 0, int res_mod = 0);
+int linear_to32(jg_handle* h, A32 ar, const float* A, long lda, int M, const Lin& L, float* out32, const float* res = nullptr, long ldr = 0, int res_mod = 0);
+// LayerNorm of fp32 rows in ONE launch: the next GEMM's operand `copy` and, optionally, fp32 rows `out32`.  T = float: the operand IS
+// the fp32 rows -- the launch writes out32 when given, else copy
+int layernorm(jg_handle* h, A16 ar, const float* x, const LNp& ln, int M, int D, int flavour, int relu, f16* copy, float* out32 = nullptr);
+int layernorm(jg_handle* h, A32 ar, const float* x, const LNp& ln, int M, int D, int flavour, int relu, float* copy, float* out32 = nullptr);
+int attention(jg_handle* h, A16 ar, const f16* qkv, const float* mask, int B, int S, int H, int dk, f16* out);
+int attention(jg_handle* h, A32 ar, const float* qkv, const float* mask, int B, int S, int H, int dk, float* out);
+// rows beyond each clip's own extent of an NHWC tensor [B][H][row_elems] set to zero (launch_zero_tail); valid == nullptr: nothing to do
+int zero_tail(jg_handle* h, A16 ar, f16* x, const int* valid, int halvings, int B, int H, long row_elems);
+int zero_tail(jg_handle* h, A32 ar, float* x, const int* valid, int halvings, int B, int H, long row_elems);
+// cnn.0 + BatchNorm + ReLU of the audio CNN from fp32 mel frames (B, Tm, F), rows beyond valid[b] zero on both sides of the layer
+int audio_conv0(jg_handle* h, A16 ar, const float* mel, int B, int Tm, int F, const Lin& L, const ConvGeom& g, const int* valid, f16* out);
+int audio_conv0(jg_handle* h, A32 ar, const float* mel, int B, int Tm, int F, const Lin& L, const ConvGeom& g, const int* valid, float* out);
+// a stage's fp32 input of n elements as the arithmetic's operand: a 16-bit copy in the workspace, or the rows themselves
+int operand(jg_handle* h, A16 ar, const float* x, long n, const f16** out);
+int operand(jg_handle* h, A32 ar, const float* x, long n, const float** out);
+
+// One post-norm layer, x = LN(x + f(x)) (GestSync's unfused plan, XLM-RoBERTa unfolded; torch.nn.TransformerEncoderLayer / the BERT
+// layer): x32 the fp32 stream, x its operand copy (T = float: x32 itself), t32 the projections' fp32 output (may be x32: in place);
+// the last LayerNorm's fp32 rows go to `out`.  act: the feed-forward activation (1 ReLU, 2 exact GELU).
+template <class T>
+int post_norm_layer(jg_handle* h, Arith<T> ar, const EncLayer& L, float* x32, T* x, float* t32, T* qkv, T* att, T* hid, const float* mask, int B,
+                    int S, int H, int D, int Dff, int act, float* out) {
+    const int M = B * S;
+    RET(linear(h, ar, x, D, M, L.qkv, qkv));
+    RET(attention(h, ar, qkv, mask, B, S, H, D / H, att));
+    RET(linear_to32(h, ar, att, D, M, L.out, t32, x32, D));
+    RET(layernorm(h, ar, t32, L.n1, M, D, LN_STD, 0, x, x32));
+    RET(linear(h, ar, x, D, M, L.ff1, hid, act));
+    RET(linear_to32(h, ar, hid, Dff, M, L.ff2, t32, x32, D));
+    return layernorm(h, ar, t32, L.n2, M, D, LN_STD, 0, x, out);
+}
 
 // ------------------------------------------------------------------------------------ weight packing (linear.hip)
 // (layer kinds LK_* and the form each gets under the handle's mode: weight_form.h)

@@ -1,4 +1,4 @@
-// libjegal_hip: GestSync -- finalize, const chain, conv stack, transformer, clip and window paths, fp16 and fp32 (audit) forms.  Host code only.
+// libjegal_hip: GestSync -- finalize, const chain, conv stacks, transformer (fused plan; unfused plan per arithmetic), clip and window paths.  Host code only.
 #include "engine.h"
 
 namespace engine {
@@ -238,17 +238,37 @@ struct Qkv0 {
     int nclip, P, Twin, shift;
 };
 
-// rc_clips > 0: the rows are rc_clips clips of M / rc_clips rows each (the clip path; JG_PREC_FP16_RC's per-clip corrections)
+// The unfused plan: six post-norm layers (post_norm_layer, engine.h) on the stream x32 with its operand copy x (T = float: x32 itself).
+// t32: the projections' fp32 output -- the 16-bit plan runs in place (t32 = x32), the audit path through a buffer of its own
+template <class T>
+static int gs_layers(jg_handle* h, Arith<T> ar, float* x32, T* x, float* t32, int nseq, int S) {
+    const int M = nseq * S;
+    T *qkv, *att, *hid;
+    RET(wsalloc(h, (size_t)M * 1536, &qkv));
+    RET(wsalloc(h, (size_t)M * 512, &att));
+    RET(wsalloc(h, (size_t)M * 2048, &hid));
+    for (int l = 0; l < 6; ++l) RET(post_norm_layer(h, ar, h->gs.layers[l], x32, x, t32, qkv, att, hid, nullptr, nseq, S, 8, 512, 2048, 1, x32));
+    return JG_OK;
+}
+
+// The fused plan (gs_fused_plan) stays a graph of its own: its token stream is the tiled fp16 plane x16 alone, out_proj / linear2 carry the
+// residual add and the post-norm LayerNorm in their epilogues (row-wide 128x512 tiles), and layer 0 may take its qkv by linearity (Qkv0) --
+// none of which exists in fp32 or bf16.  rc_clips > 0: the rows are rc_clips clips of M / rc_clips rows each (the clip path;
+// JG_PREC_FP16_RC's per-clip corrections)
 static int gs_transformer(jg_handle* h, float* x32, f16* x16, int nseq, int S, bool tiled, const Qkv0* q0 = nullptr, int rc_clips = 0,
                           const int* rc_valid = nullptr) {
+    if (!tiled) return gs_layers(h, A16(), x32, x16, x32, nseq, S);
     GestSyncModel& gs = h->gs;
     const int M = nseq * S;
-    const int rc_rpc = rc_clips > 0 && tiled ? M / rc_clips : 0;
-    if (!rc_rpc) rc_clips = 0;
+    const int rc_rpc = rc_clips > 0 ? M / rc_clips : 0;
     f16 *qkv, *att, *hid;
     RET(wsalloc(h, (size_t)M * 1536, &qkv));
     RET(wsalloc(h, (size_t)M * 512, &att));
     RET(wsalloc(h, (size_t)M * 2048, &hid));
+    Epi e, r, f;
+    e.out16 = qkv; e.a_tiled = 1; e.rc_rpc = rc_rpc; e.rc_clips = rc_clips; e.rc_valid = rc_valid;
+    r.res16 = x16; r.out16 = x16; r.ln_flavour = LN_STD; r.rc_rpc = rc_rpc; r.rc_clips = rc_clips; r.rc_valid = rc_valid;
+    f = e; f.relu = 1; f.out16 = hid;
     for (int l = 0; l < 6; ++l) {
         const EncLayer& L = gs.layers[l];
         if (l == 0 && q0) {
@@ -256,9 +276,9 @@ static int gs_transformer(jg_handle* h, float* x32, f16* x16, int nseq, int S, b
             RET(wsalloc(h, (size_t)q0->nclip * q0->P * 1536, &qpos));
             if (!gs.qpe) RET(walloc(h, gs.m, (size_t)32 * 1536, &gs.qpe));
             f16* qpe = gs.qpe;
-            Epi e;
-            e.out16 = qpos; e.no_bias = 1;
-            RET(gemm(h, JG_ST_GEMM, q0->conv16, 512, q0->nclip * q0->P, L.qkv, e));
+            Epi p;
+            p.out16 = qpos; p.no_bias = 1;
+            RET(gemm(h, JG_ST_GEMM, q0->conv16, 512, q0->nclip * q0->P, L.qkv, p));
             if (!gs.qpe_valid) {
                 RET(timed(h, JG_ST_GEMM, [&] { return launch_pe_project(gs.pe, S, L.qkv.wh, run_lo(h, L.qkv, false), L.qkv.bias, 1536, 512, qpe, h->stream); }));
                 HIPCHK(h, hipStreamSynchronize(h->stream));      // once per weight load: later calls may come on another stream
@@ -267,29 +287,12 @@ static int gs_transformer(jg_handle* h, float* x32, f16* x16, int nseq, int S, b
             const AttnGather ag = {qpe, q0->Twin, q0->P, q0->shift};
             RET(timed(h, JG_ST_ATTN, [&] { return launch_attention_gather(qpos, ag, nseq, S, 8, att, h->stream); }));
         } else {
-            Epi e;
-            e.out16 = qkv; e.a_tiled = tiled; e.rc_rpc = rc_rpc; e.rc_clips = rc_clips; e.rc_valid = rc_valid;
             RET(gemm(h, JG_ST_GEMM, x16, 512, M, L.qkv, e));
-            RET(timed(h, JG_ST_ATTN, [&] { return LAUNCH(h, launch_attention, qkv, nullptr, nseq, S, 8, 64, att, h->opts, h->stream); }));
+            RET(attention(h, A16(), qkv, nullptr, nseq, S, 8, 64, att));
         }
-        // out_proj / linear2 with the residual add and the post-norm LayerNorm fused into the epilogue (row-wide
-        // 128x512 tiles, tiled fp16 token stream) when gs_fused_plan() says so; otherwise GEMM + LayerNorm kernel.
-        auto proj_ln = [&](const f16* A, long lda, const Lin& W, const LNp& ln) -> int {
-            Epi r;
-            if (tiled) {
-                r.res16 = x16; r.out16 = x16; r.ln = &ln; r.ln_flavour = LN_STD;
-                r.rc_rpc = rc_rpc; r.rc_clips = rc_clips; r.rc_valid = rc_valid;
-                return gemm(h, JG_ST_GEMM, A, lda, M, W, r);
-            }
-            r.res = x32; r.ldr = 512; r.out32 = x32;
-            RET(gemm(h, JG_ST_GEMM, A, lda, M, W, r));
-            return timed(h, JG_ST_NORM, [&] { return LAUNCH(h, launch_layernorm, x32, ln.w, ln.b, M, 512, LN_STD, 0, x32, x16, h->stream); });
-        };
-        RET(proj_ln(att, 512, L.out, L.n1));
-        Epi f;
-        f.relu = 1; f.out16 = hid; f.a_tiled = tiled; f.rc_rpc = rc_rpc; f.rc_clips = rc_clips; f.rc_valid = rc_valid;
+        r.ln = &L.n1; RET(gemm(h, JG_ST_GEMM, att, 512, M, L.out, r));
         RET(gemm(h, JG_ST_GEMM, x16, 512, M, L.ff1, f));
-        RET(proj_ln(hid, 2048, L.ff2, L.n2));
+        r.ln = &L.n2; RET(gemm(h, JG_ST_GEMM, hid, 2048, M, L.ff2, r));
     }
     return JG_OK;
 }
@@ -302,6 +305,8 @@ static int gs_transformer(jg_handle* h, float* x32, f16* x16, int nseq, int S, b
 // residual / activation, the mean(-1) AFTER ff_vid.2 as in inference_embs.py:511); ~40-60 clips/s.
 
 // conv stack over `nclip` temporal volumes -> conv_out (nclip*P, 512) fp32 (gestsync.py:34-87,308-325: conv + BatchNorm(eval, folded) + ReLU, two max-pools)
+// A graph of its own next to gs_conv_stack: that one is the direct u8 conv1 with its zero-band scan and the row-skip chain behind it, this
+// one the plain chain of seven layers -- they share the geometry (gs_conv_geoms) and nothing else.
 static int gs_conv_stack32(jg_handle* h, const void* src, int src_u8, long sb, long st, long sh, long sw, long sc, int nclip, int T, int pad, float* conv_out) {
     const GestSyncModel& gs = h->gs;
     const int P = T + 2 * pad - 4;
@@ -331,25 +336,16 @@ static int gs_conv_stack32(jg_handle* h, const void* src, int src_u8, long sb, l
     return gemm32(h, JG_ST_CONV, p5, 4096, (int)NF, gs.fc6, conv_out, e);
 }
 
-// post-norm transformer (gestsync.py:19-21) in place on x32, M = nseq * S tokens
-static int gs_transformer32(jg_handle* h, float* x32, int nseq, int S) {
-    const int M = nseq * S;
-    float *qkv, *att, *hid, *t;
-    RET(wsalloc(h, (size_t)M * 1536, &qkv));
-    RET(wsalloc(h, (size_t)M * 512, &att));
-    RET(wsalloc(h, (size_t)M * 2048, &hid));
-    RET(wsalloc(h, (size_t)M * 512, &t));
-    for (int l = 0; l < 6; ++l) RET(post_norm_layer32(h, h->gs.layers[l], x32, t, qkv, att, hid, nullptr, nseq, S, 8, 512, 2048, 1, x32));
-    return JG_OK;
-}
-
 // windows + PE + transformer + ff_vid on the fp32 kernels: conv (nb*P, 512) fp32 -> *full (nb*T*21, 1024), T windows per volume
+// The tail is not shared with the 16-bit clip path on purpose: that one takes the window mean BEFORE ff_vid.2 (by linearity, 21 x fewer
+// rows), the audit path after it, as the reference does.
 static int gs_tail32(jg_handle* h, const float* conv, int nb, int P, int T, int shift, float** full) {
     const int S = 21, nseq = nb * T, M = nseq * S;
-    float *x32, *hid;
+    float *x32, *t32, *hid;
     RET(wsalloc(h, (size_t)M * 512, &x32));
+    RET(wsalloc(h, (size_t)M * 512, &t32));
     RET(timed(h, JG_ST_MISC, [&] { return launch_window_gather(conv, h->gs.pe, nb, P, T, S, 512, shift, 0, x32, nullptr, h->stream); }));
-    RET(gs_transformer32(h, x32, nseq, S));
+    RET(gs_layers(h, A32(), x32, x32, t32, nseq, S));
     RET(wsalloc(h, (size_t)M * 512, &hid));
     RET(wsalloc(h, (size_t)M * 1024, full));
     Epi32 f; f.act = 1;

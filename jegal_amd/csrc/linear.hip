@@ -290,22 +290,7 @@ int gemm32(jg_handle* h, int stage, const float* A, long lda, int M, const Lin& 
     return timed(h, stage, [&] { return launch_gemm32(a, h->stream); });
 }
 
-// one post-norm layer, x = LN(x + f(x)), on the fp32 kernels in place on x32 (its last LayerNorm writes `out`); t32, qkv, att, hid: scratch
-int post_norm_layer32(jg_handle* h, const EncLayer& L, float* x32, float* t32, float* qkv, float* att, float* hid, const float* mask, int B, int S,
-                      int H, int D, int Dff, int act, float* out) {
-    const int M = B * S;
-    Epi32 r; r.res = x32; r.ldr = D;
-    Epi32 f; f.act = act;
-    RET(gemm32(h, JG_ST_GEMM, x32, D, M, L.qkv, qkv));
-    RET(timed(h, JG_ST_ATTN, [&] { return launch_attention32(qkv, mask, B, S, H, D / H, att, h->stream); }));
-    RET(gemm32(h, JG_ST_GEMM, att, D, M, L.out, t32, r));
-    RET(timed(h, JG_ST_NORM, [&] { return launch_layernorm(t32, L.n1.w, L.n1.b, M, D, LN_STD, 0, x32, nullptr, h->stream); }));
-    RET(gemm32(h, JG_ST_GEMM, x32, D, M, L.ff1, hid, f));
-    RET(gemm32(h, JG_ST_GEMM, hid, Dff, M, L.ff2, t32, r));
-    return timed(h, JG_ST_NORM, [&] { return launch_layernorm(t32, L.n2.w, L.n2.b, M, D, LN_STD, 0, out, nullptr, h->stream); });
-}
-
-// The same product on the fp16 matrix cores with split operands (audit32.h, GemmX3Args): A fp32, W = hi + lo, three MFMAs per fragment pair
+// The same product on the fp16 matrix cores with split operands (gemm_x3.h, GemmX3Args): A fp32, W = hi + lo, three MFMAs per fragment pair
 int gemm_x3(jg_handle* h, int stage, const float* A, long lda, int M, const Lin& L, float* out, const Epi32& e) {
     if (!L.wh || !L.lo) JG_FAIL(h, JG_ERR_STATE, "split-operand GEMM on a layer that was packed without its lo half");
     GemmX3Args a;
@@ -319,6 +304,72 @@ int gemm_x3(jg_handle* h, int stage, const float* A, long lda, int M, const Lin&
     if (e.act > 1) JG_FAIL(h, JG_ERR_ARG, "gemm_x3: ReLU only");
     return timed(h, stage, [&] { return launch_gemm_x3(a, h->stream); });
 }
+
+// ------------------------------------------------------------------------------------ the primitives of the two arithmetics (engine.h)
+static int gemm_a32(jg_handle* h, A32 ar, const float* A, long lda, int M, const Lin& L, float* out, const Epi32& e, const ConvGeom* g = nullptr) {
+    if (!ar.x3) return gemm32(h, g ? JG_ST_CONV : JG_ST_GEMM, A, lda, M, L, out, e, g);
+    if (g) JG_FAIL(h, JG_ERR_ARG, "gemm_x3: no convolutions");
+    return gemm_x3(h, JG_ST_GEMM, A, lda, M, L, out, e);
+}
+int linear(jg_handle* h, A16, const f16* A, long lda, int M, const Lin& L, f16* out, int act, const ConvGeom* g) {
+    Epi e; e.out16 = out; e.relu = act;
+    return gemm(h, g ? JG_ST_CONV : JG_ST_GEMM, A, lda, M, L, e, g);
+}
+int linear(jg_handle* h, A32 ar, const float* A, long lda, int M, const Lin& L, float* out, int act, const ConvGeom* g) {
+    Epi32 e; e.act = act;
+    return gemm_a32(h, ar, A, lda, M, L, out, e, g);
+}
+int linear_to32(jg_handle* h, A16, const f16* A, long lda, int M, const Lin& L, float* out32, const float* res, long ldr, int res_mod) {
+    Epi e; e.out32 = out32; e.res = res; e.ldr = ldr; e.res_mod = res_mod;
+    return gemm(h, JG_ST_GEMM, A, lda, M, L, e);
+}
+int linear_to32(jg_handle* h, A32 ar, const float* A, long lda, int M, const Lin& L, float* out32, const float* res, long ldr, int res_mod) {
+    Epi32 e; e.res = res; e.ldr = ldr; e.res_mod = res_mod;
+    return gemm_a32(h, ar, A, lda, M, L, out32, e);
+}
+int layernorm(jg_handle* h, A16, const float* x, const LNp& ln, int M, int D, int flavour, int relu, f16* copy, float* out32) {
+    return timed(h, JG_ST_NORM, [&] { return LAUNCH(h, launch_layernorm, x, ln.w, ln.b, M, D, flavour, relu, out32, copy, h->stream); });
+}
+int layernorm(jg_handle* h, A32, const float* x, const LNp& ln, int M, int D, int flavour, int relu, float* copy, float* out32) {
+    return timed(h, JG_ST_NORM, [&] { return launch_layernorm(x, ln.w, ln.b, M, D, flavour, relu, out32 ? out32 : copy, nullptr, h->stream); });
+}
+int attention(jg_handle* h, A16, const f16* qkv, const float* mask, int B, int S, int H, int dk, f16* out) {
+    return timed(h, JG_ST_ATTN, [&] { return LAUNCH(h, launch_attention, qkv, mask, B, S, H, dk, out, h->opts, h->stream); });
+}
+int attention(jg_handle* h, A32, const float* qkv, const float* mask, int B, int S, int H, int dk, float* out) {
+    return timed(h, JG_ST_ATTN, [&] { return launch_attention32(qkv, mask, B, S, H, dk, out, h->stream); });
+}
+int zero_tail(jg_handle* h, A16, f16* x, const int* valid, int halvings, int B, int H, long row_elems) {
+    if (!valid) return JG_OK;
+    return timed(h, JG_ST_MISC, [&] { return LAUNCH(h, launch_zero_tail, x, valid, halvings, B, H, row_elems, h->stream); });
+}
+int zero_tail(jg_handle* h, A32, float* x, const int* valid, int halvings, int B, int H, long row_elems) {
+    if (!valid) return JG_OK;
+    return timed(h, JG_ST_MISC, [&] { return launch_zero_tail32(x, valid, halvings, B, H, row_elems, h->stream); });
+}
+// 16-bit: one fused kernel straight from the mel frames, which zeroes the ragged tails itself (round 2: im2col + a K = 32 GEMM)
+int audio_conv0(jg_handle* h, A16, const float* mel, int B, int Tm, int F, const Lin& L, const ConvGeom&, const int* valid, f16* out) {
+    return timed(h, JG_ST_CONV, [&] { return LAUNCH(h, launch_audio_conv0, mel, B, Tm, F, L.wh, run_lo(h, L, false), L.bias, out, valid, h->stream); });
+}
+// fp32: the implicit-GEMM convolution, between a zero-tailed copy of a ragged batch's frames and the zero tail of its output
+int audio_conv0(jg_handle* h, A32 ar, const float* mel, int B, int Tm, int F, const Lin& L, const ConvGeom& g, const int* valid, float* out) {
+    if (valid) {
+        float* m0;
+        RET(wsalloc(h, (size_t)B * Tm * F, &m0));
+        HIPCHK(h, hipMemcpyAsync(m0, mel, (size_t)B * Tm * F * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+        RET(zero_tail(h, ar, m0, valid, 0, B, Tm, F));
+        mel = m0;
+    }
+    RET(linear(h, ar, mel, 0, B * Tm * F, L, out, 1, &g));
+    return zero_tail(h, ar, out, valid, 0, B, Tm, (long)F * L.N);
+}
+int operand(jg_handle* h, A16, const float* x, long n, const f16** out) {
+    f16* x16;
+    RET(wsalloc(h, (size_t)n, &x16));
+    *out = x16;
+    return timed(h, JG_ST_MISC, [&] { return LAUNCH(h, launch_cast_f32_f16, x, x16, n, h->stream); });
+}
+int operand(jg_handle*, A32, const float* x, long, const float** out) { *out = x; return JG_OK; }
 
 // ------------------------------------------------------------------------------------ bias-corrected precision
 // Weight rounding (w -> fp16) leaves an error (w - fp16(w)) . x per output that is the SAME for every token,

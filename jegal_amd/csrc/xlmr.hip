@@ -1,5 +1,6 @@
-// libjegal_hip: XLM-RoBERTa, the text front end -- finalize and the folded, unfolded and fp32 (audit) passes.  Host code only.
+// libjegal_hip: XLM-RoBERTa, the text front end -- finalize, the folded pass, the unfolded pass per arithmetic.  Host code only.
 #include "engine.h"
+#include <type_traits>
 
 namespace engine {
 
@@ -105,13 +106,16 @@ int finalize_xlmr(jg_handle* h) {
     return JG_OK;
 }
 
-// XLMRobertaModel.forward (explicit LayerNorms, un-folded matrices: finalize_xlmr packs them that way when audit weights are kept)
-static int xlmr_encode_impl32(jg_handle* h, const int32_t* ids, const int32_t* amask, int B, int L, float* out) {
+// XLMRobertaModel.forward with explicit LayerNorms on un-folded matrices (option xlmr_fold = 0; finalize_xlmr also packs them that way
+// when audit weights are kept): embeddings + LayerNorm, then post-norm BERT layers (post_norm_layer, engine.h) with exact GELU
+template <class T>
+static int xlmr_encode_unfolded(jg_handle* h, Arith<T> ar, const int32_t* ids, const int32_t* amask, int B, int L, float* out) {
     const XlmrModel& xl = h->xl;
-    if (xl.folded) JG_FAIL(h, JG_ERR_STATE, "the XLM-RoBERTa weights were packed for the implicit-LayerNorm pass: finalize them with audit weights for the fp32 path");
     const int M = B * L;
-    float *x32, *t32, *qkv, *att, *hid, *mk = nullptr;
+    float *x32, *t32, *mk = nullptr;
+    T *x, *qkv, *att, *hid;
     RET(wsalloc(h, (size_t)M * D, &x32));
+    if constexpr (std::is_same<T, float>::value) x = x32; else RET(wsalloc(h, (size_t)M * D, &x));
     RET(wsalloc(h, (size_t)M * D, &t32));
     RET(wsalloc(h, (size_t)M * 3 * D, &qkv));
     RET(wsalloc(h, (size_t)M * D, &att));
@@ -121,9 +125,9 @@ static int xlmr_encode_impl32(jg_handle* h, const int32_t* ids, const int32_t* a
         RET(timed(h, JG_ST_MISC, [&] { return launch_mask_i32_f32(amask, mk, M, h->stream); }));
     }
     RET(timed(h, JG_ST_MISC, [&] { return launch_xlmr_embed(ids, B, L, D, 1, xl.vocab, xl.maxpos, xl.word, xl.pos, xl.type, t32, h->stream); }));
-    RET(timed(h, JG_ST_NORM, [&] { return launch_layernorm(t32, xl.emb_ln.w, xl.emb_ln.b, M, D, LN_STD, 0, x32, nullptr, h->stream); }));
+    RET(layernorm(h, ar, t32, xl.emb_ln, M, D, LN_STD, 0, x, x32));
     const int n = (int)xl.layers.size();
-    for (int l = 0; l < n; ++l) RET(post_norm_layer32(h, xl.layers[l], x32, t32, qkv, att, hid, mk, B, L, H, D, DFF, 2, l + 1 == n ? out : x32));
+    for (int l = 0; l < n; ++l) RET(post_norm_layer(h, ar, xl.layers[l], x32, x, t32, qkv, att, hid, mk, B, L, H, D, DFF, 2, l + 1 == n ? out : x32));
     return JG_OK;
 }
 
@@ -135,6 +139,7 @@ static int xlmr_encode_impl32(jg_handle* h, const int32_t* ids, const int32_t* a
 // added to LN(x) recomputes gamma (x - mean) rstd + beta from the planes there, writes the new planes in place and the per-64-column
 // (sum, sum of squares) of the new rows; launch_ln_stats (one thread per row) makes the next (mean, rstd).  Per pass: 25 LayerNorm
 // launches over fp32 rows (10 % of the time, 18 B per element and sub-layer through HBM) become 24 x 3 us and 8 B per element.
+// A graph of its own: no LayerNorm launch, no fp32 stream and no operand copy exist here, and only the 16-bit LDS-DMA GEMM has its epilogues.
 static int xlmr_encode_folded(jg_handle* h, const int32_t* ids, const int32_t* amask, int B, int L, float* out) {
     const XlmrModel& xl = h->xl;
     constexpr int P = D / 64;
@@ -185,41 +190,15 @@ int xlmr_encode_impl(jg_handle* h, const int32_t* ids, const int32_t* amask, int
     const XlmrModel& xl = h->xl;
     if (!xl.m.ready) JG_FAIL(h, JG_ERR_STATE, "XLM-RoBERTa weights not finalized (jg_finalize_weights(h, 4))");
     if (B <= 0 || L <= 0 || L > xl.maxpos - 2) JG_FAIL(h, JG_ERR_ARG, "need B > 0 and 0 < L <= %d", xl.maxpos - 2);
-    if (audit_mask(h) & AUD_XLMR) return xlmr_encode_impl32(h, ids, amask, B, L, out);
+    if (audit_mask(h) & AUD_XLMR) {
+        if (xl.folded) JG_FAIL(h, JG_ERR_STATE, "the XLM-RoBERTa weights were packed for the implicit-LayerNorm pass: finalize them with audit weights for the fp32 path");
+        return xlmr_encode_unfolded(h, A32(), ids, amask, B, L, out);
+    }
     if (xl.folded && !h->opts.gemm_glds)      // (plan_gemm would reject every implicit-LayerNorm launch: say why up front)
         JG_FAIL(h, JG_ERR_STATE, "the XLM-RoBERTa weights were packed for the implicit-LayerNorm pass, which needs the LDS-DMA GEMM: set option "
                                  "gemm_glds=0 (or xlmr_fold=0) BEFORE jg_finalize_weights(h, 4)");
     if (xl.folded) return xlmr_encode_folded(h, ids, amask, B, L, out);
-    const int M = B * L;
-    float *x32, *t32, *mk = nullptr;
-    f16 *x16, *qkv, *att, *hid;
-    RET(wsalloc(h, (size_t)M * D, &x32));
-    RET(wsalloc(h, (size_t)M * D, &x16));
-    RET(wsalloc(h, (size_t)M * D, &t32));
-    RET(wsalloc(h, (size_t)M * 3 * D, &qkv));
-    RET(wsalloc(h, (size_t)M * D, &att));
-    RET(wsalloc(h, (size_t)M * DFF, &hid));
-    if (amask) {
-        RET(wsalloc(h, (size_t)M, &mk));
-        RET(timed(h, JG_ST_MISC, [&] { return launch_mask_i32_f32(amask, mk, M, h->stream); }));
-    }
-    RET(timed(h, JG_ST_MISC, [&] { return launch_xlmr_embed(ids, B, L, D, 1, xl.vocab, xl.maxpos, xl.word, xl.pos, xl.type, t32, h->stream); }));
-    RET(timed(h, JG_ST_NORM, [&] { return LAUNCH(h, launch_layernorm, t32, xl.emb_ln.w, xl.emb_ln.b, M, D, LN_STD, 0, x32, x16, h->stream); }));
-    for (int l = 0; l < (int)xl.layers.size(); ++l) {
-        const EncLayer& Ly = xl.layers[l];
-        const bool last = l + 1 == (int)xl.layers.size();
-        Epi e; e.out16 = qkv;
-        RET(gemm(h, JG_ST_GEMM, x16, D, M, Ly.qkv, e));
-        RET(timed(h, JG_ST_ATTN, [&] { return LAUNCH(h, launch_attention, qkv, mk, B, L, H, 64, att, h->opts, h->stream); }));
-        Epi r; r.res = x32; r.ldr = D; r.out32 = t32;
-        RET(gemm(h, JG_ST_GEMM, att, D, M, Ly.out, r));
-        RET(timed(h, JG_ST_NORM, [&] { return LAUNCH(h, launch_layernorm, t32, Ly.n1.w, Ly.n1.b, M, D, LN_STD, 0, x32, x16, h->stream); }));
-        Epi f; f.relu = 2; f.out16 = hid;             // exact GELU in the GEMM epilogue (round 2: fp32 M x 3072 out + a separate kernel)
-        RET(gemm(h, JG_ST_GEMM, x16, D, M, Ly.ff1, f));
-        RET(gemm(h, JG_ST_GEMM, hid, DFF, M, Ly.ff2, r));
-        RET(timed(h, JG_ST_NORM, [&] { return LAUNCH(h, launch_layernorm, t32, Ly.n2.w, Ly.n2.b, M, D, LN_STD, 0, last ? out : x32, x16, h->stream); }));
-    }
-    return JG_OK;
+    return xlmr_encode_unfolded(h, A16(), ids, amask, B, L, out);
 }
 
 }  // namespace engine

@@ -500,7 +500,7 @@ def test_gemm_x3_vs_fp64():
     assert worst <= 1, worst
 
 
-# Operand scale of the split A = fp16(a) + fp16(a - fp16(a)) (audit32.hip): once |a| < ~2^-3 the lo half is subnormal in fp16 and carries
+# Operand scale of the split A = fp16(a) + fp16(a - fp16(a)) (gemm_x3.hip): once |a| < ~2^-3 the lo half is subnormal in fp16 and carries
 # an ABSOLUTE quantum of 2^-24 (error <= 2^-25 per element), so the norm-wise error of a row is ~2^-25 / rms(a): within the 2 sqrt(K) u
 # bound while the rows' rms is >= ~2^-7 at K = 512; |a| >= 65520 overflows the hi half.
 # The activations at the engine's gemm_x3 call sites (proj_ip_rgb on the GestSync features, the LayerNorm / ReLU outputs in front of

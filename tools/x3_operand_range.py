@@ -27,7 +27,7 @@ import jegal_oracle as O  # noqa: E402
 from jegal_amd import synth  # noqa: E402
 
 FAMILIES = [("gauss", 0), ("gauss", 1), ("gauss", 2), ("heavy", 0), ("sharp2", 0), ("sharp", 0)]
-# Linears on gemm_x3 in the fp16 modes (jegal.hip: jegal_input32 / jegal_tail32 / jegal_text_impl / fuse_content_impl); the encoder
+# Linears on gemm_x3 in the fp16 modes (jegal.hip: jegal_input / jegal_tail / jegal_text / fuse_content in the split-operand arithmetic, Arith<float>{x3}); the encoder
 # feed-forward ones are not, and are measured as a wider envelope (rows marked ffn_x3_only, summary "with_ffn")
 X3_SITES = ["proj_ip_rgb.0", "proj_ip_rgb.3", "proj_op_rgb", "proj_op_align_gesture.0", "proj_op_align_gesture.2", "proj_op_text",
             "proj_op_fusion_content.0", "proj_op_fusion_content.2", "proj_op_align_content.0", "proj_op_align_content.2"]
