@@ -93,6 +93,13 @@ int jg_set_chunk(jg_handle* h, int clips_per_chunk);
  *                     conv1_direct_kernel needs num_cu >= 8 or no more column strips (5 per position) than num_cu: it deals the strips out
  *                     per XCD (workgroup index & 7), and with fewer than 8 workgroups some XCD ranges would have nobody; such a
  *                     launch is rejected (JG_ERR_HIP, invalid value) instead of leaving pooled rows unwritten.
+ *   "lane_walk_gemm", "lane_walk_conv", "lane_walk_lnf", "lane_walk_conv1" ("lane_walk": all four), 1..4: inside a two-lane batch a persistent
+ *                     kernel of the family (plain GEMMs / conv GEMMs / the LayerNorm-fused GEMM / conv1_direct_kernel) launches
+ *                     min(tiles, factor x num_cu) workgroups, so that each walks 1 / factor of the tiles and a CU can pass to the other
+ *                     lane's next kernel whenever a workgroup exits.  Tile choice, cost estimates and admission keep using num_cu;
+ *                     bit-identical results for every factor.  Handle defaults: plain GEMMs 4, the others 1 (measured:
+ *                     tools/experiments/README.md); the planner's built-in default (jg_debug_gemm_plan) is 1.  One-stream batches: no effect.
+ *   "debug_lanes"     1: jg_debug_gemm_check, jg_debug_conv_check and jg_debug_conv1_pool launch as inside a two-lane batch (tests)
  *   "lane_priority"   3 (default): the two lane streams are created with the device's highest stream priority; 0: normal priority (rounds 3-5);
  *                     1 / 2: only the second / first lane (a change drains and re-creates the lane streams).  HIP deals streams onto four hardware
  *                     queues PER PRIORITY LEVEL in creation order: normal-priority lanes can end up on one queue when the application owns
@@ -202,7 +209,7 @@ int jg_debug_gemm_check(jg_handle* h, const jg_gemm_check* c);
  * (jegal_amd/csrc/gemm_plan.h).  Of `c` only the sizes and the null-ness of the pointers are read.  conv (optional): the launch is an
  * implicit-GEMM convolution of this geometry (rowmap / const_in: whether ConvGeom's pointers are set).  a_tiled: the A operand is the
  * tiled token plane.  num_cu: compute units of the device; lanes_active: the launch is part of a two-lane batch.  opt_names / opt_values:
- * n_opts options as for jg_set_option ("gemm_*"; the defaults otherwise).  name receives the instance as jg_debug_last_kernel reports it,
+ * n_opts options as for jg_set_option ("gemm_*", "lane_walk*"; the built-in defaults otherwise, every walk factor 1).  name receives the instance as jg_debug_last_kernel reports it,
  * or "rejected" (launch_gemm would return an error and launch nothing; grid = lds = stagger = 0 then); grid = workgroups, lds = dynamic
  * LDS bytes, stagger = de-phasing delay in 10-ns ticks.  Returns JG_ERR_ARG for bad arguments or an unknown option. */
 typedef struct jg_conv_shape { int H, W, C, KH, KW, PH, PW, tap_table, rowmap, const_in; } jg_conv_shape;

@@ -158,7 +158,8 @@ def load_library():
 def gemm_plan(num_cu=256, lanes_active=False, opts=None, conv=None, a_tiled=False, **fields):
     """The GEMM planner's answer (jg_debug_gemm_plan) -> (instance name or "rejected", grid, lds bytes, stagger).  Needs no Engine and no
     GPU.  fields: those of jg_gemm_check, as for Engine.debug_gemm_check; of a pointer field only its presence counts, so a tensor or
-    True stands for "set" (None / False / 0: NULL).  opts: engine options (gemm_*; "num_cu" overrides num_cu); conv: dict of the jg_conv_shape fields."""
+    True stands for "set" (None / False / 0: NULL).  opts: engine options (gemm_*, lane_walk*; "num_cu" overrides num_cu, "debug_lanes" overrides
+    lanes_active, as the handle options of those names do for the check points); conv: dict of the jg_conv_shape fields."""
     lib = load_library()
     c = GemmCheck()
     ptr_fields = {k for k, t in GemmCheck._fields_ if t is _P}
@@ -168,6 +169,7 @@ def gemm_plan(num_cu=256, lanes_active=False, opts=None, conv=None, a_tiled=Fals
         setattr(c, k, v)
     opts = dict(opts or {})
     num_cu = opts.pop("num_cu", num_cu)
+    lanes_active = opts.pop("debug_lanes", lanes_active)
     names = (ctypes.c_char_p * max(len(opts), 1))(*[k.encode() for k in opts])
     values = (_I * max(len(opts), 1))(*[int(v) for v in opts.values()])
     cs = ConvShape(**{k: int(v) for k, v in conv.items()}) if conv is not None else None

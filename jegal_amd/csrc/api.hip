@@ -228,7 +228,8 @@ int jg_set_chunk(jg_handle* h, int c) {
 int jg_set_option(jg_handle* h, const char* name, int value) {
     if (!h || !name) return JG_ERR_ARG;
     EngineOpts& o = h->opts;
-    if (engine_opts_set(o, name, value)) return JG_OK;      // the launchers' own switches (gemm_*, attn_mfma, conv1_mfma16, conv1_zero_skip)
+    if (!std::strncmp(name, "lane_walk", 9) && (value < 1 || value > LANE_WALK_MAX)) JG_FAIL(h, JG_ERR_ARG, "%s must be 1..%d", name, LANE_WALK_MAX);
+    if (engine_opts_set(o, name, value)) return JG_OK;      // the launchers' own switches (gemm_*, lane_walk*, attn_mfma, conv1_mfma16, conv1_zero_skip)
     if (!std::strcmp(name, "conv1_direct")) { h->conv1_direct = value != 0; return JG_OK; }
     if (!std::strcmp(name, "fuse_ln")) { h->fuse_ln = value != 0; return JG_OK; }
     if (!std::strcmp(name, "edge_dedup")) { h->edge_dedup = value != 0; return JG_OK; }
@@ -258,6 +259,7 @@ int jg_set_option(jg_handle* h, const char* name, int value) {
         return JG_OK;
     }
     if (!std::strcmp(name, "dual_stream")) { h->dual_stream = value != 0; return JG_OK; }
+    if (!std::strcmp(name, "debug_lanes")) { h->debug_lanes = value != 0; return JG_OK; }
     if (!std::strcmp(name, "num_cu")) {          // experiments: persistent kernels of this handle launch this many workgroups (<= the device's CUs)
         if (value < 1 || value > 1024) JG_FAIL(h, JG_ERR_ARG, "num_cu out of range");      // (1, 2: many rounds per workgroup on a handful of tiles, tests/test_gpu_conv_fp64.py)
         o.num_cu = value;

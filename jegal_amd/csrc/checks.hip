@@ -75,7 +75,10 @@ int jg_debug_conv1_pool(jg_handle* h, const void* frames_u8, int B, int T, int p
     RET(begin_pass(h));
     const long sw = 3, sh = (long)FW * 3, st = (long)FH * FW * 3, sb = (long)T * st;
     unsigned* zscr;
-    return gs_conv1_stage(h, frames_u8, 1, sb, st, sh, sw, 1, B, T, pad, static_cast<f16*>(out_f16), true, &zscr);
+    h->opts.lanes_active = h->debug_lanes;
+    const int rc = gs_conv1_stage(h, frames_u8, 1, sb, st, sh, sw, 1, B, T, pad, static_cast<f16*>(out_f16), true, &zscr);
+    h->opts.lanes_active = false;
+    return rc;
 }
 
 // Tuning aid: time `iters` launches of the production GEMM on garbage operands of a given shape.
@@ -155,6 +158,7 @@ int jg_debug_gemm_check(jg_handle* h, const jg_gemm_check* c) {
     const GemmArgs a = gemm_check_args(c);
     EngineOpts o = h->opts;
     o.kname = h->kname;          // the name slot the launchers write
+    o.lanes_active = h->debug_lanes;
     return check_result(h, LAUNCH(h, launch_gemm, a, false, o, h->stream), "launch_gemm");
 }
 
@@ -186,6 +190,7 @@ int jg_debug_conv_check(jg_handle* h, const jg_conv_check* c) {
     a.out32 = c->out32; a.out16 = static_cast<f16*>(c->out16); a.ldc = c->ldc;
     EngineOpts o = h->opts;
     o.kname = h->kname;          // the name slot the launchers write
+    o.lanes_active = h->debug_lanes;
     if (c->s2_host) {
         GemmShape q = gemm_shape(a, false);
         q.set_geom(g);

@@ -43,6 +43,7 @@ extern "C" int jg_clock_read_conv1(unsigned long long* out, int n) {
     return hipMemcpyFromSymbol(out, HIP_SYMBOL(jg_clock_stamps_conv1), sizeof(unsigned long long) * (n < 2048 ? n : 2048)) == hipSuccess ? 0 : 1;
 }
 #endif
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -62,6 +63,7 @@ struct Conv1Args {
                               // (conv1_zero_scan_kernel + conv1_skip_mask_kernel); tile rt is skipped outright when bits rt and
                               // rt-1 are set; nullptr: no pre-scan, zero tiles are detected from the loaded bytes
     const f16* zconst;        // [64] relu(bias) per channel as fp16: the value of every conv1 output whose patch is all zero
+    int walk;                 // > 1: about `walk` workgroups per CU (EngineOpts::lane_walk); how the strips are dealt then: conv1_deal
     int fill_partial;         // 1: conv2 honours the per-position row skip (common.h, ConvGeom::rowmap): it reads pooled rows >= 2 s2 of a
                               // position only (s2 from the position's own skip mask), and the constant fill leaves the rows above unwritten
 };
@@ -129,13 +131,29 @@ struct Strips {
         return use_skip ? (unsigned)__builtin_amdgcn_readfirstlane((int)tab[k]) : 0u;
     }
 };
+// Workgroup b of G deals with strips s_lo, s_lo + GX, ... below r_hi.  walk = 1: all GX workgroups of the XCD walk its range together.
+// walk > 1 (more workgroups than CUs, Conv1Args::walk): only about GX / walk of them are resident at a time, in the order of their
+// ids, so the XCD's range is cut into that many consecutive sub-ranges and each group of ceil(GX / walk) consecutive workgroups walks
+// ONE of them together -- the resident workgroups stay on neighbouring strips (the frames of a position in L2 once), and every strip
+// still belongs to exactly one workgroup.  Host and device: launch_conv1_direct sizes the skip table with the same function.
+struct StripDeal { int s_lo, r_hi, GX; };
+__host__ __device__ inline StripDeal conv1_deal(int nstrips, int G, int walk, int b) {
+    const int xcd = b & 7, xidx = b >> 3;
+    const int GX = (G + 7 - xcd) >> 3;                                   // workgroups on this XCD
+    const int per = (nstrips + 7) >> 3;
+    const int r_lo = xcd * per, r_hi = (r_lo + per < nstrips) ? r_lo + per : nstrips;
+    if (walk <= 1 || GX <= 1 || r_hi <= r_lo) return StripDeal{r_lo + xidx, r_hi, GX};
+    const int W = (GX + walk - 1) / walk;                                // workgroups per group
+    const int groups = (GX + W - 1) / W;                                 // <= walk, each with at least one workgroup
+    const int g = xidx / W, l = xidx - g * W;
+    const int Wg = GX - g * W < W ? GX - g * W : W;
+    const int sub = (r_hi - r_lo + groups - 1) / groups;
+    const int lo = r_lo + g * sub, hi = lo + sub < r_hi ? lo + sub : r_hi;
+    return StripDeal{lo + l, hi, Wg};
+}
 __device__ __forceinline__ Strips conv1_strips(const Conv1Args& a, const char* smem) {
-    const int G32 = (int)gridDim.x;
-    const int xcd = blockIdx.x & 7, xidx = blockIdx.x >> 3;
-    const int GX = (G32 + 7 - xcd) >> 3;                                 // workgroups on this XCD
-    const int per = (a.nstrips + 7) >> 3;
-    const int r_lo = xcd * per, r_hi = (r_lo + per < a.nstrips) ? r_lo + per : a.nstrips;
-    return Strips{r_lo + xidx, r_hi, GX, reinterpret_cast<const unsigned*>(smem + OFF_SKIP), a.zmask != nullptr};
+    const StripDeal d = conv1_deal(a.nstrips, (int)gridDim.x, a.walk, (int)blockIdx.x);
+    return Strips{d.s_lo, d.r_hi, d.GX, reinterpret_cast<const unsigned*>(smem + OFF_SKIP), a.zmask != nullptr};
 }
 // strip -> (position nf, column tile j)
 __device__ __forceinline__ void strip_split(int strip, int& nf, int& j) {
@@ -859,7 +877,10 @@ hipError_t launch_conv1_direct(const uint8_t* src, int nclip, int T, int pad, co
                                f16* out_pooled, f16* edge, const unsigned* zscratch, bool fill_all, const EngineOpts& o, hipStream_t s) {
     static bool attr_set[64] = {};
     if (o.device < 0 || o.device >= 64) return hipErrorInvalidDevice;
-    const int num_cu = o.num_cu;
+    // workgroups of a launch with more strips than that: one per CU, or lane_walk per CU inside a two-lane batch (shared.h) -- each
+    // XCD's strip range is then dealt over more workgroups (conv1_strips), each walks fewer strips (a shorter skip table) and loads
+    // the weight panel (49 x 16 B per lane) once as before.  The dump area (conv1_edge_elems) has MAX_WGS slots.
+    const int wgs = std::min(o.num_cu * (o.lanes_active ? o.lane_walk[EngineOpts::LW_CONV1] : 1), std::max(o.num_cu, MAX_WGS));
     if (!attr_set[o.device]) {
         const void* ks[2] = {reinterpret_cast<const void*>(conv1_direct_kernel<false>), reinterpret_cast<const void*>(conv1_direct_kernel<true>)};
         for (const void* kf : ks) {
@@ -879,8 +900,16 @@ hipError_t launch_conv1_direct(const uint8_t* src, int nclip, int T, int pad, co
     a.zmask = nullptr;
     a.zconst = nullptr;
     a.fill_partial = 0;
-    if (num_cu > MAX_WGS) return hipErrorInvalidValue;
-    if (a.zskip && zscratch && nclip * T > 0 && (a.nstrips + num_cu - 1) / num_cu + 8 <= MAX_WG_STRIPS) {
+    if (wgs > MAX_WGS) return hipErrorInvalidValue;
+    const int grid_wgs = a.nstrips < wgs ? a.nstrips : wgs;
+    a.walk = grid_wgs > o.num_cu ? (grid_wgs + o.num_cu - 1) / o.num_cu : 1;
+    // the longest walk of the launch, in strips: the skip table in LDS has MAX_WG_STRIPS entries (8 spare, as ever)
+    int max_walk = 0;
+    for (int b = 0; b < grid_wgs; ++b) {
+        const StripDeal d = conv1_deal(a.nstrips, grid_wgs, a.walk, b);
+        if (d.s_lo < d.r_hi) max_walk = std::max(max_walk, (d.r_hi - d.s_lo + d.GX - 1) / d.GX);
+    }
+    if (a.zskip && zscratch && nclip * T > 0 && max_walk + 8 <= MAX_WG_STRIPS) {
         const Conv1Scan z = conv1_scan_view(const_cast<unsigned*>(zscratch), nclip, T, pad);
         a.zmask = z.pos_mask();
         a.zconst = static_cast<const f16*>(z.zconst());
@@ -888,8 +917,8 @@ hipError_t launch_conv1_direct(const uint8_t* src, int nclip, int T, int pad, co
     }
     if (a.nstrips <= 0) return hipSuccess;
     // XCD range rule (conv1_strips): XCD x = blockIdx.x & 7 owns strips [x * per, (x + 1) * per) -- under 8 workgroups some ranges have none
-    if (num_cu < 8 && a.nstrips > num_cu) return hipErrorInvalidValue;
-    const unsigned grid = (unsigned)(a.nstrips < num_cu ? a.nstrips : num_cu);
+    if (wgs < 8 && a.nstrips > wgs) return hipErrorInvalidValue;
+    const unsigned grid = (unsigned)grid_wgs;
     if (o.conv1_mfma16) hipLaunchKernelGGL((conv1_direct_kernel<true>), dim3(grid), dim3(512), LDS_BYTES, s, a);
     else hipLaunchKernelGGL((conv1_direct_kernel<false>), dim3(grid), dim3(512), LDS_BYTES, s, a);
     return hipGetLastError();

@@ -195,6 +195,7 @@ struct jg_handle {
     // internal streams with their own workspaces, so that one part's next kernel fills the partly empty last round of the
     // other's (persistent kernels run in rounds of one tile per CU: 788 LayerNorm tiles on 256 CUs are 3.08 rounds)
     bool dual_stream = true;
+    bool debug_lanes = false;      // option "debug_lanes": the one-launch check points (checks.hip) launch as inside a two-lane batch (EngineOpts::lanes_active)
     int dual_split = 4;            // the first lane gets dual_split/8 of the batch.  Round 6: equal halves (rounds 3-5: 3/8; with the run-time correction's
                                    // small launches and the split-operand GEMMs in the mix the sweep reads 12.77 ms at 12:20, 12.57 at 14:18, 12.53-12.61 at 16:16,
                                    // 12.57-12.66 at 17:15 / 18:14, 12.66-12.73 at 20:12 -- tools/experiments/README.md)

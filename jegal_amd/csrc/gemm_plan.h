@@ -145,8 +145,9 @@ struct GemmPlan {
     bool glds() const { return instance >= 0 && GEMM_INSTANCES[instance].key[0]; }
 };
 
-// Pure: no HIP call, dereferences nothing, keeps no state.  Reads the gemm_* options, num_cu and lanes_active of `o`.
+// Pure: no HIP call, dereferences nothing, keeps no state.  Reads the gemm_* options, num_cu, lanes_active and lane_walk of `o`.
 GemmPlan plan_gemm(const GemmShape& s, const EngineOpts& o);
 
-// The EngineOpts half of jg_set_option ("gemm_*", "attn_mfma", "conv1_mfma16", "conv1_zero_skip"): true if `name` is one of them
+// The EngineOpts half of jg_set_option ("gemm_*", "lane_walk*", "attn_mfma", "conv1_mfma16", "conv1_zero_skip"): true if `name` is one of them
+// (and, for a walk factor, the value is in 1..LANE_WALK_MAX)
 bool engine_opts_set(EngineOpts& o, const char* name, int value);

@@ -23,7 +23,10 @@ GemmPlan instance(const GemmShape& a, const EngineOpts& o, bool glds, bool w2, T
     p.lds = glds ? glds_tile(w2, t.mi, t.wm, t.wn).lds() : (size_t)(bm + bn * (w2 ? 2 : 1)) * 128;      // register-staged: one stage
     p.grid = (unsigned)tiles;                                             // register-staged: one workgroup per tile
     if (!glds) return p;
-    if ((lnf || o.gemm_persistent) && tiles > o.num_cu) p.grid = (unsigned)o.num_cu;
+    // Persistent: num_cu workgroups walk the tiles in rounds; inside a two-lane batch lane_walk x num_cu of them (shared.h), each with
+    // 1/lane_walk of the rounds.  tile_of (gemm.hip) deals the tiles over any grid; no workgroup waits for another.
+    const int walk = !o.lanes_active ? 1 : o.lane_walk[lnf ? EngineOpts::LW_LNF : a.conv ? EngineOpts::LW_CONV : EngineOpts::LW_GEMM];
+    if ((lnf || o.gemm_persistent) && tiles > o.num_cu) p.grid = (unsigned)std::min(tiles, (long)walk * o.num_cu);
     // De-phasing the workgroups (4 phases, 2 us apart; the last phase falls on the workgroups that run one tile fewer):
     // once the outputs were nontemporal the epilogues became HBM-write-burst bound (every CU stores its 128 KB at the
     // same moment) and spreading them pays: qkv 157 -> 146 us.  Only for long plain GEMMs (>= 4 rounds); the LN-fused
@@ -37,7 +40,10 @@ GemmPlan instance(const GemmShape& a, const EngineOpts& o, bool glds, bool w2, T
     // last round is less than half full, because the highest block ids - the ones delayed longest - run one tile fewer: out_proj
     // 108 -> 94 us, linear2 265 -> 256 us at M = 100 800 (3.08 rounds), 52 -> 48 us at 1.15 rounds; with a nearly full last round it
     // costs what it delays (1.92 rounds: 58 -> 61 us), so it is off there -- and it stays on inside the two-lane batches.
-    const bool pays = tiles > o.num_cu && 2 * (tiles % o.num_cu) < o.num_cu;
+    // With more workgroups than CUs (lane_walk) there is no de-phasing: the kernel's phase is blockIdx.x * 4 / grid, which takes all
+    // workgroups to start together, and "the last phase runs one tile fewer" is an argument about resident workgroups.  The later
+    // workgroups start whenever a CU frees, which spreads the bursts by itself.
+    const bool pays = tiles > o.num_cu && 2 * (tiles % o.num_cu) < o.num_cu && p.grid <= (unsigned)o.num_cu;
     const int auto_stagger = !pays ? 0 : lnf ? (a.K <= 1024 ? 500 : 1400) : (!a.conv && !o.lanes_active ? 300 : 0);
     p.stagger = o.gemm_stagger < 0 ? 0 : o.gemm_stagger > 0 ? o.gemm_stagger : auto_stagger;
     return p;
@@ -169,6 +175,14 @@ bool engine_opts_set(EngineOpts& o, const char* name, int value) {
     else if (!std::strcmp(name, "gemm_counted")) o.gemm_counted = value != 0;
     else if (!std::strcmp(name, "gemm_persistent")) o.gemm_persistent = value != 0;
     else if (!std::strcmp(name, "gemm_stagger")) o.gemm_stagger = value;
+    else if (!std::strncmp(name, "lane_walk", 9)) {
+        static const char* const family[4] = {"_gemm", "_conv", "_lnf", "_conv1"};
+        if (value < 1 || value > LANE_WALK_MAX) return false;
+        bool known = !name[9];                                            // "lane_walk": every family
+        for (int f = 0; f < 4; ++f)
+            if (!name[9] || !std::strcmp(name + 9, family[f])) { o.lane_walk[f] = value; known = true; }
+        return known;
+    }
     else return false;
     return true;
 }
@@ -179,6 +193,9 @@ hipError_t engine_opts_init(EngineOpts& o, int device) {
     hipError_t e = hipGetDeviceProperties(&prop, device);
     if (e != hipSuccess) return e;
     o.num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    // production walk factors (shared.h; measurements: tools/experiments/README.md, "Lane walk"): the plain GEMMs of a two-lane batch
+    // launch four workgroups per CU; the conv GEMMs, the LayerNorm-fused kernel and conv1 measured neutral or slower and stay at one
+    o.lane_walk[EngineOpts::LW_GEMM] = 4;
     void* z = nullptr;
     e = hipMalloc(&z, 256);                  // zero page on THIS device: LDS-DMA cannot predicate, but it can read zeros
     if (e != hipSuccess) return e;

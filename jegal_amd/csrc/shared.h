@@ -127,12 +127,20 @@ struct EngineOpts {
     int gemm_stagger = 0;                // 10-ns ticks per phase (0: default policy, -1: off)
     bool lanes_active = false;           // the launch is part of a two-lane batch (api.hip, run_in_lanes): the other lane's kernels already
                                          // spread the store bursts, the default de-phasing only costs time there (12.22 -> 12.16 ms per step)
+    // Walk factors (options lane_walk_gemm / _conv / _lnf / _conv1, "lane_walk" = all four; 1..LANE_WALK_MAX): inside a two-lane batch a
+    // persistent kernel of the family launches min(tiles, factor x num_cu) workgroups instead of num_cu, so that each walks 1/factor of
+    // the tiles and a CU changes hands -- possibly to the other lane's next kernel -- whenever one exits.  Tile choice, cost estimates
+    // and admission keep using num_cu; the work per tile does not depend on which workgroup runs it.  Built-in default 1 (the planner
+    // as jg_debug_gemm_plan shows it); engine_opts_init sets the production values of a handle.
+    enum { LW_GEMM = 0, LW_CONV = 1, LW_LNF = 2, LW_CONV1 = 3 };
+    int lane_walk[4] = {1, 1, 1, 1};
     bool attn_mfma = true;
     bool conv1_zero_skip = true;
     bool conv1_mfma16 = true;            // conv1_direct_kernel's MFMA waves on 16x16x32 MFMAs (false: 32x32x16, the round-1/2 form)
     char* kname = nullptr;               // kernel check points (jg_debug_last_kernel): the launchers write the name of the instance they
                                          // launch here, with its template arguments (KNAME_LEN bytes; nullptr: not recorded)
 };
+constexpr int LANE_WALK_MAX = 4;
 constexpr int KNAME_LEN = 96;
 // printf-style into kname (if any): host side of a launcher
 template <class... T>
