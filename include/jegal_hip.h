@@ -132,10 +132,14 @@ int jg_sync(jg_handle* h);
 
 /* ---- weights: replaces model.load_state_dict(sd) (inference_embs.py:92-119,
  *      evaluation/extract_jegal_embs.py:32-53).  `name` is the reference state_dict key with any
- *      "module." prefix already stripped; unknown keys (net_aud.*, lstm.*, ...) are accepted and
- *      ignored, missing hot-path keys make jg_finalize_weights fail (strict). ------------------- */
+ *      "module." prefix already stripped; keys that no finalize consumes (lstm.*, logits_scale.*, fc.* of
+ *      a GestSync checkpoint: no forward uses them) are accepted and ignored, missing keys of a model that
+ *      is finalized make jg_finalize_weights fail (strict). ------------------------------------- */
 int jg_load_tensor(jg_handle* h, const char* name, const void* data_host, const int64_t* shape_host, int ndim, int dtype);
-/* which: bit 0 = GestSync, bit 1 = JEGAL, bit 2 = XLM-RoBERTa (keys of transformers.XLMRobertaModel under the prefix "xlmr.").
+/* which: bit 0 = GestSync (the video stream: net_vid, transformer, ff_vid), bit 1 = JEGAL, bit 2 = XLM-RoBERTa (keys of
+ * transformers.XLMRobertaModel under the prefix "xlmr."), bit 3 (value 8) = GestSync's audio stream (net_aud.conv1..fc6 with bn1..6,
+ * ff_aud.fc7 / bn7 / fc8; strict like the others and independent of bit 0: a checkpoint without audio keys still finalizes with 1 and
+ * fails with 8).
  * Folds BatchNorm, packs k=(kh,kw,c), splits hi/lo.
  * Staged tensors: the ones this call consumed are dropped; tensors staged for a model that is finalized by a LATER call stay
  * (load everything, then finalize(1), finalize(2) works); keys no finalize consumes stay until jg_clear_staged_tensors.
@@ -143,7 +147,8 @@ int jg_load_tensor(jg_handle* h, const char* name, const void* data_host, const 
  * bias corrections of the other model - e.g. from jg_calibrate_gesture on real clips - are kept.  Re-finalizing a model
  * discards ITS corrections: call jg_calibrate_gesture again after re-loading it. */
 int jg_finalize_weights(jg_handle* h, int which);
-/* Drop every staged host tensor (the unused net_aud / lstm tensors of a GestSync checkpoint, tensors of a model never finalized). */
+/* Drop every staged host tensor (the lstm tensors of a GestSync checkpoint, tensors of a model never finalized -- e.g. net_aud.* when
+ * bit 3 is not wanted). */
 int jg_clear_staged_tensors(jg_handle* h);
 
 /* Re-run the JG_PREC_FP16_BC calibration on caller-supplied clips (same layout as jg_gestsync_clip; device
@@ -179,6 +184,27 @@ int jg_gestsync_clip(jg_handle* h, const void* frames, int frames_dtype, int B, 
  * unfused hi+lo plan, in a padded batch the fused one: each within the 1e-3 contract of the reference, 5e-4 apart in the test -- not bit for bit.)  The
  * other modes ignore the lengths.  Rows t >= valid_frames[b] of the output are padding for the caller to strip. */
 int jg_gestsync_clip_ragged(jg_handle* h, const void* frames, int frames_dtype, int B, int T, const int32_t* valid_frames_host, float* out_feats);
+/* GestSync's audio stream (needs jg_finalize_weights bit 3; fp16 modes and JG_PREC_FP32 -- a JG_PREC_BF16 handle is refused with
+ * JG_ERR_STATE).  All data pointers are device pointers.  Bad arguments (null buffers, non-positive sizes, valid_tm outside 1..Tm) return
+ * JG_ERR_ARG before anything is enqueued; weights that were never finalized return JG_ERR_STATE.  Both use the workspace and run on the
+ * handle's stream, asynchronously.
+ * Drop-in for GestSync.forward_aud (gestsync.py:164-168): x (N,1,80,100) fp32 (mel band x 100 mel steps = 25 frames) -> out (N,1024) fp32. */
+int jg_gestsync_audio_windows(jg_handle* h, const float* x, int N, float* out);
+/* Per-clip form: mel (B,Tm,80) fp32, time-major as jg_logmel writes it -> out (B,T,1024): window t of clip b = mel rows
+ * clamp(4(t-12) + w, 0, valid_tm[b] - 1), w = 0..99 -- the audio twin of the video path's +-12 frame edge pad; the windows are never
+ * materialised.  valid_tm_host (host [B], 1..Tm; NULL: every clip fills its Tm rows): rows of clip b that are its own, so that a clip's
+ * rows do not depend on a longer neighbour.
+ * A window's embedding is a function of its own 8000 values: the two entries give bit-identical rows when called with the same number of
+ * windows (N = B T) in the same order.  Across different N the GEMM planner may pick other kernel instances: only the parity contract
+ * (1e-3 rel-L2 of the reference in the default mode) holds there. */
+int jg_gestsync_audio_clip(jg_handle* h, const float* mel, int B, int Tm, int T, const int32_t* valid_tm_host, float* out);
+/* Kernel check points of the audio stream: one production launch on caller buffers (jg_debug_last_kernel names it).
+ * conv1 + BatchNorm + ReLU + 3x3/s2 max-pool: src as x above (clip_form 0; then T = 1, B = N, valid_host NULL) or as mel above
+ * (clip_form 1), w [64][9] fp32 with the BatchNorm scale folded, shift [64] -> out [B T][19][24][64] fp16, or fp32 with out_f32.
+ * max-pool window (2,3) stride (2,2): in (nimg,H,W,C) NHWC fp16 (f32: fp32) -> out (nimg,(H-2)/2+1,(W-3)/2+1,C); C % 8 == 0. */
+int jg_debug_gsa_conv1_pool(jg_handle* h, const float* src, int clip_form, int B, int Tm, int T, const int32_t* valid_host, const float* w,
+                            const float* shift, void* out, int out_f32);
+int jg_debug_maxpool_2x3(jg_handle* h, const void* in, int nimg, int H, int W, int C, void* out, int f32);
 /* Kernel-level check point: conv1+BN+ReLU+maxpool (gestsync.py:36-46) only.  frames (B,T,270,480,3) u8,
  * pad = temporal edge padding (12 for clips, 0 for a raw 25-frame window) -> out (B*(T+2*pad-4),43,78,64) fp16 NHWC. */
 int jg_debug_conv1_pool(jg_handle* h, const void* frames_u8, int B, int T, int pad, void* out_f16);
@@ -507,6 +533,31 @@ int jg_asd_windows(jg_handle* h, const float* gesture, const int32_t* g_offsets,
                    const int32_t* word_start, const int32_t* word_end, const int32_t* trk, const int32_t* s_offsets, int n_scenes, int D,
                    int win, int hop, const int32_t* w_offsets, const int64_t* p_offsets, int max_windows, float temp,
                    float* prob, float* cosv /* may be NULL */, int32_t* pred);
+
+/* Audio-visual offset and confidence per clip from the two streams of GestSync window embeddings (jg_gestsync_clip,
+ * jg_gestsync_audio_clip); no counterpart in the reference tree, the SyncNet convention.  All pointers are device pointers.
+ *   vid (sum Tv, D), aud (sum Ta, D) fp32 rows, used as stored; v_offsets / a_offsets [n_clips + 1]: clip i owns video rows
+ *   v_offsets[i] .. v_offsets[i + 1] - 1 (Tv) and audio rows likewise (Ta; the two may differ).
+ * For a shift d in -R .. R (R = max_shift) the pairs are (t, t + d) with 0 <= t < Tv and 0 <= t + d < Ta, n_d of them, and
+ *   curve[d + R] = (1 / n_d) sum_t <v_t, a_{t+d}> / max(|v_t| |a_{t+d}|, 1e-8), summed in ascending t;  NaN when n_d < min_overlap;
+ *   offset = the d of the first maximum in ascending d over the non-NaN entries (np.nanargmax);
+ *   conf   = that maximum minus the median of the non-NaN entries (np.nanmedian).
+ * Sign: offset d > 0 means that the audio row matching video row t is row t + d.
+ * Outputs: curve fp32 [n_clips][2R + 1] (may be NULL), offset int32 [n_clips], conf fp32 [n_clips].
+ * A clip's result is a function of its own rows: not of its place in the batch nor of n_clips.  The offsets are device arrays: a clip
+ * with Tv or Ta outside 1..8192, or without a non-NaN shift, gets offset 0, conf NaN and a NaN curve row; nothing of it is read (in the
+ * first case) and the other clips are computed normally.
+ * Bad arguments return JG_ERR_ARG before anything is enqueued: null operands, D <= 0, D % 64, D > 1024, max_shift outside 0..64,
+ * min_overlap < 1, vid / aud not 16-byte aligned, n_clips < 0.  n_clips == 0 returns JG_OK and launches nothing.  Nothing outside the
+ * described elements is written; no workspace is used.  Asynchronous.
+ * Cost: ONE workgroup (one CU) walks a clip's video rows in blocks of 32, in order -- that is what keeps the per-shift sums in
+ * ascending t without scratch -- so the parallelism comes from n_clips.  A batch of many short clips is the intended use (4000 clips of
+ * 150 rows, D = 1024, R = 15: 3.7 ms on MI355X); a single clip of 8192 rows is 256 blocks on one CU -- 16.6 ms at D = 1024, R = 15 and
+ * 31 ms at R = 64, measured, while the rest of the device idles: cut a long recording into clips (with max_shift rows of overlap) if
+ * its offset is wanted quickly. */
+int jg_sync_offset(jg_handle* h, const float* vid, const int32_t* v_offsets, const float* aud, const int32_t* a_offsets,
+                   int n_clips, int D, int max_shift, int min_overlap,
+                   float* curve /* may be NULL */, int32_t* offset, float* conf);
 
 /* ---- multi-GPU exchange.  The reference is single-process (its only parallelism is the --rank / --nshard file-list split of
  *      preprocess/extract_gestsync_feats.py:366-370); clips shard with no data-path collective, and the ONE exchange of the path is the

@@ -56,6 +56,11 @@ _SIGS = {
     "jg_gestsync_clip": [_P, _P, _I, _I, _I, _P],
     "jg_gestsync_clip_ragged": [_P, _P, _I, _I, _I, ctypes.POINTER(ctypes.c_int32), _P],
     "jg_gestsync_windows": [_P, _P, _I, _P, _P],
+    "jg_gestsync_audio_windows": [_P, _P, _I, _P],
+    "jg_gestsync_audio_clip": [_P, _P, _I, _I, _I, ctypes.POINTER(ctypes.c_int32), _P],
+    "jg_debug_gsa_conv1_pool": [_P, _P, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_int32), _P, _P, _P, _I],
+    "jg_debug_maxpool_2x3": [_P, _P, _I, _I, _I, _I, _P, _I],
+    "jg_sync_offset": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P],
     "jg_debug_conv1_pool": [_P, _P, _I, _I, _I, _P],
     "jg_debug_gemm": [_P, _I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_double)],
     "jg_debug_gemm_ex": [_P, _P, _P, _I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_double)],
@@ -289,7 +294,8 @@ class Engine:
 
     def finalize(self, which, clear_staged=True):
         """jg_finalize_weights; the Python facades load one model's state_dict and finalize it at once, so whatever that
-        finalize did not consume (net_aud.*, lstm.* of a GestSync checkpoint) is dropped afterwards."""
+        finalize did not consume (lstm.* of a GestSync checkpoint; net_aud.* / ff_aud.* unless bit 3, value 8, is in `which`) is dropped
+        afterwards.  which: 1 GestSync video stream, 2 JEGAL, 4 XLM-RoBERTa, 8 GestSync audio stream."""
         with torch.cuda.device(self.device):
             self._ck(self.lib.jg_finalize_weights(self.h, which))
         if clear_staged:
@@ -580,6 +586,52 @@ class Engine:
         oc = torch.empty((N, 512, 21), dtype=torch.float32, device=self.device) if return_feats else None
         self._ck(self.lib.jg_gestsync_windows(self.h, _ptr(x), N, _ptr(out), _ptr(oc)))
         return (out, oc) if return_feats else out
+
+    def gestsync_audio_windows(self, x):
+        """jg_gestsync_audio_windows, GestSync.forward_aud's arithmetic: x (N,1,80,100) (mel band x mel step) -> (N,1024) fp32.  Needs
+        finalize bit 3 (value 8)."""
+        self._bind_stream()
+        x = self._f32(x)
+        if x.dim() != 4 or tuple(x.shape[1:]) != (1, 80, 100) or x.shape[0] < 1:
+            raise ValueError(f"x must be (N,1,80,100) with N >= 1, got {tuple(x.shape)}")
+        N = x.shape[0]
+        out = torch.empty((N, 1024), dtype=torch.float32, device=self.device)
+        self._ck(self.lib.jg_gestsync_audio_windows(self.h, _ptr(x), N, _ptr(out)))
+        return out
+
+    def gestsync_audio_clip(self, mel, T, lengths=None):
+        """jg_gestsync_audio_clip: mel (B,Tm,80) time-major (Engine.logmel's layout) -> (B,T,1024): window t = mel rows 4(t-12) .. 4(t-12)+99,
+        clamped to the clip's own rows.  lengths (B ints, optional): mel rows of each clip that are its own in a padded batch."""
+        self._bind_stream()
+        mel = self._f32(mel)
+        if mel.dim() != 3 or mel.shape[2] != 80 or mel.shape[0] < 1 or mel.shape[1] < 1 or int(T) < 1:
+            raise ValueError(f"mel must be (B,Tm,80) with B, Tm, T >= 1, got {tuple(mel.shape)}, T = {T}")
+        B, Tm = mel.shape[0], mel.shape[1]
+        v = None
+        if lengths is not None:
+            v = [int(x) for x in lengths]
+            if len(v) != B:
+                raise ValueError("lengths needs one entry per clip")
+            v = (ctypes.c_int32 * B)(*v)
+        out = torch.empty((B, int(T), 1024), dtype=torch.float32, device=self.device)
+        self._ck(self.lib.jg_gestsync_audio_clip(self.h, _ptr(mel), B, Tm, int(T), v, _ptr(out)))
+        return out
+
+    def debug_gsa_conv1_pool(self, src, w, shift, out, T=None, lengths=None):
+        """One launch of gsa_conv1_pool_kernel: src (N,1,80,100) (T None) or mel (B,Tm,80) with T windows per clip; w (64,9) / shift (64,) fp32
+        device tensors; out (windows,19,24,64) fp16 or fp32, written in place."""
+        self._bind_stream()
+        clip = T is not None
+        B, Tm = (src.shape[0], src.shape[1]) if clip else (src.shape[0], 0)
+        v = None if lengths is None else (ctypes.c_int32 * B)(*[int(x) for x in lengths])
+        self._ck(self.lib.jg_debug_gsa_conv1_pool(self.h, _ptr(src), int(clip), B, Tm, int(T) if clip else 1, v, _ptr(w), _ptr(shift), _ptr(out),
+                                                  int(out.dtype == torch.float32)))
+
+    def debug_maxpool_2x3(self, x, out):
+        """One launch of maxpool_2x3_s2_kernel: x (nimg,H,W,C) fp16 or fp32 NHWC -> out (nimg,(H-2)//2+1,(W-3)//2+1,C), written in place."""
+        self._bind_stream()
+        nimg, H, W, C = x.shape
+        self._ck(self.lib.jg_debug_maxpool_2x3(self.h, _ptr(x), nimg, H, W, C, _ptr(out), int(x.dtype == torch.float32)))
 
     def extract_gesture(self, frames, out=None):
         """frames -> unit-norm gesture embedding (B,T,512), one library call."""
@@ -894,6 +946,37 @@ class Engine:
         self._ck(self.lib.jg_attn_matrix(self.h, _ptr(g), _ptr(c), _ptr(go), _ptr(co), n, gs[1], int(T.max()), float(temp),
                                          int(bool(normalize)), _ptr(A), _ptr(ao), _ptr(best_frame), _ptr(best_score)))
         return A, a_off, best_frame, best_score
+
+    def sync_offset(self, vid, aud, v_offsets, a_offsets, max_shift=15, min_overlap=1, want_curve=True):
+        """jg_sync_offset: per clip the audio-visual offset (frames; d > 0: audio row t + d matches video row t), its confidence
+        (max - median of the curve) and the curve of mean cosines over the shifts -max_shift .. max_shift.  vid (sum Tv, D) / aud (sum Ta, D)
+        rows as stored; v_offsets / a_offsets: n + 1 row offsets each (host arrays or device int32 tensors).
+        Returns device tensors (offset (n,) int32, conf (n,) fp32, curve (n, 2 max_shift + 1) fp32 or None).  A clip with no rows, more than
+        8192 rows, or no shift with min_overlap pairs: offset 0, conf NaN, NaN curve."""
+        R, mo = int(max_shift), int(min_overlap)
+        if not 0 <= R <= 64 or mo < 1:
+            raise ValueError("jg_sync_offset limits: max_shift 0..64, min_overlap >= 1")
+        vs, as_ = tuple(vid.shape), tuple(aud.shape)
+        if len(vs) != 2 or len(as_) != 2 or vs[1] != as_[1] or vs[1] % 64 or not 0 < vs[1] <= 1024:
+            raise ValueError("vid / aud must be (rows, D) with the same D, a multiple of 64, at most 1024")
+        n = int(v_offsets.shape[0] if hasattr(v_offsets, "shape") else len(v_offsets)) - 1
+        n_a = int(a_offsets.shape[0] if hasattr(a_offsets, "shape") else len(a_offsets)) - 1
+        if n < 0 or n_a != n:
+            raise ValueError("v_offsets / a_offsets need the same number of entries (clips + 1)")
+        if not isinstance(v_offsets, torch.Tensor):
+            voh, aoh = np.asarray(v_offsets, np.int64), np.asarray(a_offsets, np.int64)
+            if voh[0] < 0 or aoh[0] < 0 or np.any(np.diff(voh) < 0) or np.any(np.diff(aoh) < 0) or voh[-1] > vs[0] or aoh[-1] > as_[0]:
+                raise ValueError("offsets must ascend and lie inside vid / aud")
+        self._bind_stream()
+        v, a = self._f32(vid), self._f32(aud)
+        vo, ao = self._i32(v_offsets), self._i32(a_offsets)
+        offset = torch.zeros((n,), dtype=torch.int32, device=self.device)
+        conf = torch.full((n,), float("nan"), dtype=torch.float32, device=self.device)
+        curve = torch.full((n, 2 * R + 1), float("nan"), dtype=torch.float32, device=self.device) if want_curve else None
+        if n == 0 or vs[0] == 0 or as_[0] == 0:          # (no rows at all: every clip is outside the limits)
+            return offset, conf, curve
+        self._ck(self.lib.jg_sync_offset(self.h, _ptr(v), _ptr(vo), _ptr(a), _ptr(ao), n, vs[1], R, mo, _ptr(curve), _ptr(offset), _ptr(conf)))
+        return offset, conf, curve
 
     def asd(self, query, cand, c_offsets, temp=0.07):
         self._bind_stream()

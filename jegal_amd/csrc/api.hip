@@ -162,7 +162,7 @@ int jg_destroy(jg_handle* h) {
         DeviceGuard dg(h->device);
         (void)hipDeviceSynchronize();
         for (auto& r : h->recs) { (void)hipEventDestroy(r.e0); (void)hipEventDestroy(r.e1); }
-        for (Model* m : {&h->gs.m, &h->jg.m, &h->xl.m})
+        for (Model* m : {&h->gs.m, &h->gsa.m, &h->jg.m, &h->xl.m})
             for (void* p : m->allocs) (void)hipFree(p);
         if (h->feats) (void)hipFree(h->feats);
         h->ws.release();
@@ -212,7 +212,7 @@ int jg_set_stream(jg_handle* h, void* s) {
 int jg_set_precision(jg_handle* h, int mode) {
     if (!h) return JG_ERR_ARG;
     if (mode < JG_PREC_FP16 || mode > JG_PREC_FP32) JG_FAIL(h, JG_ERR_ARG, "unknown precision mode %d", mode);
-    if ((h->gs.m.ready || h->jg.m.ready || h->xl.m.ready) && mode != h->precision) JG_FAIL(h, JG_ERR_STATE, "set the precision before jg_finalize_weights");
+    if ((h->gs.m.ready || h->gsa.m.ready || h->jg.m.ready || h->xl.m.ready) && mode != h->precision) JG_FAIL(h, JG_ERR_STATE, "set the precision before jg_finalize_weights");
     h->precision = mode;
     h->bf16 = mode == JG_PREC_BF16;
     return JG_OK;
@@ -237,12 +237,12 @@ int jg_set_option(jg_handle* h, const char* name, int value) {
     if (!std::strcmp(name, "ws_poison")) { h->ws_poison = value != 0; return JG_OK; }
     if (!std::strcmp(name, "jegal_fp32_ends")) { h->jegal_fp32_ends = value != 0; return JG_OK; }
     if (!std::strcmp(name, "conv_round_diffuse")) {
-        if (h->gs.m.ready || h->jg.m.ready) JG_FAIL(h, JG_ERR_STATE, "set conv_round_diffuse before jg_finalize_weights");
+        if (h->gs.m.ready || h->gsa.m.ready || h->jg.m.ready) JG_FAIL(h, JG_ERR_STATE, "set conv_round_diffuse before jg_finalize_weights");
         h->conv_round_diffuse = value != 0;
         return JG_OK;
     }
     if (!std::strcmp(name, "audit_weights")) {
-        if (h->gs.m.ready || h->jg.m.ready || h->xl.m.ready) JG_FAIL(h, JG_ERR_STATE, "set audit_weights before jg_finalize_weights");
+        if (h->gs.m.ready || h->gsa.m.ready || h->jg.m.ready || h->xl.m.ready) JG_FAIL(h, JG_ERR_STATE, "set audit_weights before jg_finalize_weights");
         h->audit_weights = value != 0;
         return JG_OK;
     }
@@ -326,9 +326,10 @@ int jg_finalize_weights(jg_handle* h, int which) {
     if (which & 1) RET(finalize_gestsync(h));
     if (which & 2) RET(finalize_jegal(h));
     if (which & 4) RET(finalize_xlmr(h));
+    if (which & 8) RET(finalize_gestsync_audio(h));
     // The fp32 host copies this finalize consumed are no longer needed (packed device weights + the w32 / b32 of the
     // bias-corrected layers' calibration records carry everything).  Tensors staged for a model that is finalized LATER stay staged; what no
-    // finalize consumes (the unused audio/LSTM tensors of gestsync.py:23-32) stays until jg_clear_staged_tensors / jg_destroy.
+    // finalize consumes (the LSTM / logits_scale / fc tensors of gestsync.py:23-32, which no forward uses) stays until jg_clear_staged_tensors / jg_destroy.
     for (auto it = h->host.begin(); it != h->host.end();) it = it->second.used ? h->host.erase(it) : std::next(it);
     // Built-in calibration only for the gesture models finalized by THIS call (XLM-R has no bias-corrected layers): the bias
     // corrections of the other model -- possibly from jg_calibrate_gesture on real clips -- are left as they are.
@@ -368,6 +369,18 @@ int jg_gestsync_windows(jg_handle* h, const float* x, int N, float* out, float* 
     ENTER(h);
     if (!x || !out) JG_FAIL(h, JG_ERR_ARG, "null buffer");
     return gestsync_windows_impl(h, x, N, out, out_conv);
+}
+
+int jg_gestsync_audio_windows(jg_handle* h, const float* x, int N, float* out) {
+    ENTER(h);
+    if (!x || !out) JG_FAIL(h, JG_ERR_ARG, "null buffer");
+    return gestsync_audio_impl(h, x, 0, N, 0, 1, nullptr, out);
+}
+
+int jg_gestsync_audio_clip(jg_handle* h, const float* mel, int B, int Tm, int T, const int32_t* valid_tm_host, float* out) {
+    ENTER(h);
+    if (!mel || !out) JG_FAIL(h, JG_ERR_ARG, "null buffer");
+    return gestsync_audio_impl(h, mel, 1, B, Tm, T, valid_tm_host, out);
 }
 
 int jg_jegal_gestures(jg_handle* h, const float* feats, const float* mask, int B, int T, int align, float* out) {
@@ -566,6 +579,21 @@ int jg_attn_matrix(jg_handle* h, const float* g, const float* c, const int32_t* 
     if (best_frame || best_score) RET(wsalloc(h, attn_matrix_key_elems(n), &keys));
     return timed(h, JG_ST_MISC, [&] {
         return launch_attn_matrix(g, c, goff, coff, n, D, max_frames, temp, normalize, A, aoff, keys, best_frame, best_score, h->stream);
+    });
+}
+
+int jg_sync_offset(jg_handle* h, const float* vid, const int32_t* v_offsets, const float* aud, const int32_t* a_offsets, int n_clips, int D,
+                   int max_shift, int min_overlap, float* curve, int32_t* offset, float* conf) {
+    ENTER(h);
+    if (!vid || !v_offsets || !aud || !a_offsets || !offset || !conf) JG_FAIL(h, JG_ERR_ARG, "null buffer");
+    if (n_clips < 0) JG_FAIL(h, JG_ERR_ARG, "n_clips must be >= 0");
+    if (D <= 0 || D % 64 || D > SYNC_MAX_D) JG_FAIL(h, JG_ERR_ARG, "D must be a positive multiple of 64, at most %d", SYNC_MAX_D);
+    if (max_shift < 0 || max_shift > SYNC_MAX_R) JG_FAIL(h, JG_ERR_ARG, "max_shift must be 0..%d", SYNC_MAX_R);
+    if (min_overlap < 1) JG_FAIL(h, JG_ERR_ARG, "min_overlap must be >= 1");
+    if ((reinterpret_cast<uintptr_t>(vid) | reinterpret_cast<uintptr_t>(aud)) & 15) JG_FAIL(h, JG_ERR_ARG, "vid / aud must be 16-byte aligned");
+    if (n_clips == 0) return JG_OK;
+    return timed(h, JG_ST_MISC, [&] {
+        return launch_sync_offset(vid, v_offsets, aud, a_offsets, n_clips, D, max_shift, min_overlap, curve, offset, conf, h->stream);
     });
 }
 

@@ -230,6 +230,26 @@ int jg_debug_maxpool(jg_handle* h, const void* in, int nimg, int H, int W, int C
     return rc;
 }
 
+int jg_debug_gsa_conv1_pool(jg_handle* h, const float* src, int clip_form, int B, int Tm, int T, const int32_t* valid_host, const float* w,
+                            const float* shift, void* out, int out_f32) {
+    ENTER(h);
+    h->kname[0] = 0;
+    if (!src || !w || !shift || !out || B <= 0 || T <= 0 || (clip_form && Tm <= 0) || (!clip_form && (T != 1 || valid_host)) || !al(out, 16))
+        JG_FAIL(h, JG_ERR_ARG, "jg_debug_gsa_conv1_pool: bad arguments (window form: T = 1 and no valid_host)");
+    for (int b = 0; valid_host && b < B; ++b)
+        if (valid_host[b] < 1 || valid_host[b] > Tm) JG_FAIL(h, JG_ERR_ARG, "jg_debug_gsa_conv1_pool: valid[%d] = %d outside 1..Tm = %d", b, valid_host[b], Tm);
+    int32_t* valid = nullptr;
+    if (valid_host) RET(upload_valid(h, valid_host, B, &valid));
+    return check_result(h, launch_gsa_conv1_pool(src, clip_form, 0, B * T, T, Tm, valid, w, shift, out, out_f32, h->stream, h->kname), "launch_gsa_conv1_pool");
+}
+
+int jg_debug_maxpool_2x3(jg_handle* h, const void* in, int nimg, int H, int W, int C, void* out, int f32) {
+    ENTER(h);
+    h->kname[0] = 0;
+    if (!in || !out || nimg <= 0) JG_FAIL(h, JG_ERR_ARG, "jg_debug_maxpool_2x3: bad arguments");
+    return check_result(h, launch_maxpool_2x3_s2(in, out, nimg, H, W, C, f32, h->stream, h->kname), "launch_maxpool_2x3_s2");
+}
+
 int jg_debug_conv_rowmaps(jg_handle* h, const int32_t* s2_host, int NF, const int* OH, const int* OW, int nlayers, int32_t* const* map_host,
                           int32_t* const* base_host, int32_t* total_host) {
     ENTER(h);

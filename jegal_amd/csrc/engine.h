@@ -1,5 +1,5 @@
 // libjegal_hip host side: the handle, the packed model state and the helpers the host units share (api.hip, linear.hip,
-// gestsync.hip, jegal.hip, xlmr.hip, checks.hip).  Host code only; the kernel units do not include it.
+// gestsync.hip, gestsync_audio.hip, jegal.hip, xlmr.hip, checks.hip).  Host code only; the kernel units do not include it.
 #pragma once
 #include "common.h"
 #define JG_BF16                  // the bf16 build's declarations (namespace bf): the dispatched launchers, f16 = __bf16
@@ -130,6 +130,15 @@ struct GestSyncModel {
     bool qpe_valid = false;
 };
 
+// GestSync's audio stream (net_aud + ff_aud, gestsync.py:89-146,346-361; gestsync_audio.hip): `which` bit 3, a model of its own beside
+// the video stream -- either can be finalized without the other.  Weight forms as a GestSync model (id 1)
+struct GestSyncAudioModel {
+    Model m{1};
+    float* c1w = nullptr;          // conv1 [64][9] fp32, BatchNorm scale folded (gsa_conv1_pool_kernel)
+    float* c1shift = nullptr;      // [64]
+    Lin c2, c3, c4, c5, fc6, fc7, fc8;      // channels padded to powers of two: 192 -> 256 (c2 out, c3 in), 384 -> 512 (c3 out, c4 in)
+};
+
 struct JegalModel {
     Model m{2};
     Lin ip0, ip3, op_rgb, al_g0, al_g2, fu0, fu2, al_c0, al_c2, op_text, op_audio;
@@ -178,6 +187,7 @@ struct jg_handle {
     int64_t prof_n[JG_ST_COUNT] = {0};
 
     engine::GestSyncModel gs;
+    engine::GestSyncAudioModel gsa;
     engine::JegalModel jg;
     engine::XlmrModel xl;
     // implicit LayerNorm (option "xlmr_fold", read when the XLM-R weights are finalized): the 25 LayerNorms of a pass are never
@@ -463,18 +473,22 @@ int pack_matrix(jg_handle* h, Model& m, const std::vector<float>& w, const std::
                 bool ln_consumer = false, bool keep32 = false, int diffuse_group = 0);
 int make_linear(jg_handle* h, Model& m, const std::string& wname, const std::string& bname, int N, int K, Lin* L, int kind = LK_GESTURE, bool keep32 = false);
 int make_ln(jg_handle* h, Model& m, const std::string& wname, const std::string& bname, int D, LNp* p);
+// Opad > O: output channels O .. Opad - 1 are added with zero weights and zero shift (relu(0) = 0 for whoever reads them)
 int make_conv(jg_handle* h, Model& m, const std::string& conv, const std::string& bn, int O, int I, int KT, int KH, int KW,
-              int slot, int kpad, Lin* L, int SH = 1, int SW = 1, bool reorder = false);
+              int slot, int kpad, Lin* L, int SH = 1, int SW = 1, bool reorder = false, int Opad = 0, int kind = LK_CONV);
 int make_annotated_layer(jg_handle* h, Model& m, const std::string& p, int D, int Dff, EncLayer* L, int kind);
 int calibrate_gesture(jg_handle* h, const void* frames, int dtype, int B, int T, int models);
 int calibrate_xlmr(jg_handle* h, const int32_t* ids_dev, const int32_t* mask_dev, int B, int L);
 
-// ------------------------------------------------------------------------------------ models (gestsync.hip, jegal.hip, xlmr.hip)
+// ------------------------------------------------------------------------------------ models (gestsync.hip, gestsync_audio.hip, jegal.hip, xlmr.hip)
 int finalize_gestsync(jg_handle* h);
 int gs_conv1_stage(jg_handle* h, const void* src, int src_u8, long sb, long st, long sh, long sw, long sc, int nclip, int T, int pad,
                    f16* pooled, bool fill_all, unsigned** zscr);
 int gestsync_clip_impl(jg_handle* h, const void* frames, int dtype, int B, int T, float* out_feats, const int32_t* valid_host = nullptr);
 int gestsync_windows_impl(jg_handle* h, const float* x, int N, float* out, float* out_conv);
+int finalize_gestsync_audio(jg_handle* h);
+// src: x (N, 1, 80, 100) (clip_form 0: B = N, T = 1) or mel (B, Tm, 80) (clip_form 1) -> out (B * T, 1024)
+int gestsync_audio_impl(jg_handle* h, const float* src, int clip_form, int B, int Tm, int T, const int32_t* valid_host, float* out);
 int finalize_jegal(jg_handle* h);
 int jegal_gestures_impl(jg_handle* h, const float* feats, const float* mask, int B, int T, int align, float* out);
 int jegal_audio_impl(jg_handle* h, const float* mel, int B, int Tm, const int32_t* valid_host, float* out);

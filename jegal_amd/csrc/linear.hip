@@ -148,7 +148,7 @@ static std::vector<std::pair<int, int>> tap_order(int KH, int KW, int SH, int SW
 }
 
 int make_conv(jg_handle* h, Model& m, const std::string& conv, const std::string& bn, int O, int I, int KT, int KH, int KW,
-              int slot, int kpad, Lin* L, int SH, int SW, bool reorder) {
+              int slot, int kpad, Lin* L, int SH, int SW, bool reorder, int Opad, int kind) {
     const HostTensor *w, *b;
     RET(need(h, conv + ".weight", (int64_t)O * I * KT * KH * KW, &w));
     RET(need(h, conv + ".bias", O, &b));
@@ -165,7 +165,9 @@ int make_conv(jg_handle* h, Model& m, const std::string& conv, const std::string
         }
     }
     const int K = kpad > 0 ? kpad : KH * KW * slot;
-    std::vector<float> p((size_t)O * K, 0.f);
+    const int N = Opad > O ? Opad : O;
+    shift.resize(N, 0.f);
+    std::vector<float> p((size_t)N * K, 0.f);
     const auto order = tap_order(KH, KW, SH, SW, reorder);
     for (int o = 0; o < O; ++o)
         for (int c = 0; c < I; ++c)
@@ -175,7 +177,7 @@ int make_conv(jg_handle* h, Model& m, const std::string& conv, const std::string
                     const float v = w->v[((((size_t)o * I + c) * KT + kt) * KH + kh) * KW + kw] * s[o];
                     p[(size_t)o * K + t * slot + kt * I + c] = v;
                 }
-    return pack_matrix(h, m, p, shift, O, K, LK_CONV, L, false, false, h->conv_round_diffuse ? slot : 0);
+    return pack_matrix(h, m, p, shift, N, K, kind, L, false, false, h->conv_round_diffuse ? slot : 0);
 }
 
 int make_annotated_layer(jg_handle* h, Model& m, const std::string& p, int D, int Dff, EncLayer* L, int kind) {

@@ -989,3 +989,193 @@ hipError_t launch_asd_windows(const float* g, const int32_t* goff, int n_tracks,
 #undef ASDW_LAUNCH
     return hipGetLastError();
 }
+
+// ---------------------------------------------------------------------------------------------
+// Audio-visual offset of a clip from its two streams of window embeddings (GestSync's use; the SyncNet convention).  Clip i owns video
+// rows voff[i] .. voff[i + 1] - 1 (Tv) and audio rows aoff[i] .. (Ta).  For a shift d in -R .. R the pairs are (t, t + d) with
+// 0 <= t < Tv, 0 <= t + d < Ta (n_d of them) and
+//     curve[d + R] = (1 / n_d) sum_t <v_t, a_{t+d}> / max(||v_t|| ||a_{t+d}||, 1e-8)      (NaN when n_d < min_overlap)
+// offset = the d of the first maximum over the non-NaN entries (np.nanargmax), conf = that maximum - their median (np.nanmedian).
+//
+// The band of dot products runs on v_mfma_f32_32x32x2_f32 with [k][row] staging, as sim_tile and attn_matrix_kernel: a block of 32
+// video rows (B operand, column = lane & 31) against the 32 + 2R audio rows its band touches (A operand, NT tiles of 32).  The four
+// waves split every 32-wide k chunk (eight k each, so all four are busy whatever R is) and their partial sums meet in LDS in wave
+// order; a wave's chain is cut every SYNC_KSPLIT terms like attn_matrix_kernel's.  A dot product depends on its two rows alone.
+// ONE workgroup walks its clip's row blocks in ascending order and thread d + R adds the block's cosines of shift d to its running sum
+// in ascending t, with a compensation term (Kahan): the per-shift sum is the left-to-right sum over t whatever the clip's length -- at
+// 150 rows and a cosine of 0.9 the plain fp32 sum's rounding is 3-4 x the error of everything else in the curve, with the compensation
+// it disappears -- no partial sums of row blocks cross workgroups, and nothing but the outputs is written.  (A (clip, row block) grid needs scratch for those partial sums, which
+// the call does not have, or floating-point atomics in arrival order; a clip is 5 blocks at 150 rows and the batch supplies the
+// parallelism.)
+constexpr int SYNC_KC = 32;                  // k per staged chunk
+constexpr int SYNC_KSPLIT = 128;             // terms of one wave's fmaf chain before it is folded
+static_assert((4 * SYNC_KSPLIT) % SYNC_KC == 0 && SYNC_KC % 8 == 0, "a wave takes a quarter of every chunk, two k per MFMA, and its chain is cut at whole chunks");
+
+// ||row||; the same bits in every lane
+__device__ __forceinline__ float row_norm(const float* __restrict__ row, int D, int lane) {
+    float sq = 0.f;
+    for (int d = lane * 4; d < D; d += 256) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(row + d);
+        sq += v.x * v.x; sq += v.y * v.y; sq += v.z * v.z; sq += v.w * v.w;
+    }
+    return sqrtf(wave_sum(sq));
+}
+
+template <int NT>
+__global__ __launch_bounds__(256) void sync_offset_kernel(const float* __restrict__ vid, const int32_t* __restrict__ voff,
+                                                          const float* __restrict__ aud, const int32_t* __restrict__ aoff, int D, int R,
+                                                          int min_overlap, float* __restrict__ curve, int32_t* __restrict__ offset,
+                                                          float* __restrict__ conf) {
+    constexpr int NA = 32 * NT, BP = NA + 1;
+    __shared__ float sV[SYNC_KC * 32];       // [k][video row]
+    __shared__ float sA[SYNC_KC * NA];       // [k][audio row of the band]
+    __shared__ float sRed[4][16][64];        // one tile's accumulators, per wave
+    __shared__ float sBand[32 * BP];         // [video row][d + R]: the block's cosines
+    __shared__ float sVn[32], sAn[NA];
+    __shared__ float sCurve[2 * SYNC_MAX_R + 1];
+    __shared__ float sMed[2];
+    const int clip = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int v0 = voff[clip], Tv = voff[clip + 1] - v0;
+    const int a0 = aoff[clip], Ta = aoff[clip + 1] - a0;
+    const int W = 2 * R + 1;
+    const float nan = __builtin_nanf("");
+    if (Tv < 1 || Tv > SYNC_MAX_T || Ta < 1 || Ta > SYNC_MAX_T) {       // block-uniform: nothing of the clip is read
+        if (curve && tid < W) curve[(long)clip * W + tid] = nan;
+        if (tid == 0) { offset[clip] = 0; conf[clip] = nan; }
+        return;
+    }
+    const int nband = 32 + 2 * R;            // audio rows a block's band touches (<= NA)
+    float S = 0.f, Sc = 0.f;                 // thread d + R: running sum of shift d and its compensation
+    for (int t0 = 0; t0 < Tv; t0 += 32) {
+        const int nv = Tv - t0 < 32 ? Tv - t0 : 32;
+        const int ja0 = t0 - R;              // audio row of band column 0
+        for (int r = wave; r < 32 + NA; r += 4) {
+            float nr = 0.f;
+            if (r < 32) {
+                if (r < nv) nr = row_norm(vid + (long)(v0 + t0 + r) * D, D, lane);
+                if (lane == 0) sVn[r] = nr;
+            } else {
+                const int j = r - 32, a = ja0 + j;
+                if (j < nband && a >= 0 && a < Ta) nr = row_norm(aud + (long)(a0 + a) * D, D, lane);
+                if (lane == 0) sAn[j] = nr;
+            }
+        }
+        f32x16 acc[NT], tot[NT];
+#pragma unroll
+        for (int i = 0; i < NT; ++i)
+#pragma unroll
+            for (int x = 0; x < 16; ++x) { acc[i][x] = 0.f; tot[i][x] = 0.f; }
+        const int sr = tid & 31, sk = (tid >> 5) * 4;
+        for (int k0 = 0; k0 < D; k0 += SYNC_KC) {
+            __syncthreads();
+            {
+                f32x4 v = {0.f, 0.f, 0.f, 0.f};
+                if (sr < nv) v = *reinterpret_cast<const f32x4*>(vid + (long)(v0 + t0 + sr) * D + k0 + sk);
+                float* d = sV + sk * 32 + sr;
+                d[0] = v.x; d[32] = v.y; d[64] = v.z; d[96] = v.w;
+            }
+#pragma unroll
+            for (int u = 0; u < NT; ++u) {
+                const int j = u * 32 + sr, a = ja0 + j;
+                f32x4 v = {0.f, 0.f, 0.f, 0.f};
+                if (j < nband && a >= 0 && a < Ta) v = *reinterpret_cast<const f32x4*>(aud + (long)(a0 + a) * D + k0 + sk);
+                float* d = sA + sk * NA + j;
+                d[0] = v.x; d[NA] = v.y; d[2 * NA] = v.z; d[3 * NA] = v.w;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int kk = 0; kk < SYNC_KC / 4; kk += 2) {
+                const int kr = wave * (SYNC_KC / 4) + kk + (lane >> 5);
+                const float b = sV[kr * 32 + (lane & 31)];
+#pragma unroll
+                for (int i = 0; i < NT; ++i) {
+                    const float a = sA[kr * NA + i * 32 + (lane & 31)];
+                    acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc[i], 0, 0, 0);
+                }
+            }
+            if ((k0 + SYNC_KC) % (4 * SYNC_KSPLIT) == 0 || k0 + SYNC_KC == D) {
+#pragma unroll
+                for (int i = 0; i < NT; ++i)
+#pragma unroll
+                    for (int x = 0; x < 16; ++x) { tot[i][x] += acc[i][x]; acc[i][x] = 0.f; }
+            }
+        }
+        // the waves' partial sums of one tile at a time, in wave order; register x of lane l: audio band column 32 n + mfma32_row(x, l >> 5),
+        // video row l & 31
+#pragma unroll
+        for (int n = 0; n < NT; ++n) {
+            __syncthreads();
+#pragma unroll
+            for (int x = 0; x < 16; ++x) sRed[wave][x][lane] = tot[n][x];
+            __syncthreads();
+            for (int e = tid; e < 1024; e += 256) {
+                const int x = e >> 6, l = e & 63;
+                const float dot = ((sRed[0][x][l] + sRed[1][x][l]) + sRed[2][x][l]) + sRed[3][x][l];
+                const int i = l & 31, j = n * 32 + mfma32_row(x, l >> 5), dd = j - i;
+                if (dd >= 0 && dd < W) sBand[i * BP + dd] = dot / fmaxf(sVn[i] * sAn[j], 1e-8f);
+            }
+        }
+        __syncthreads();
+        if (tid < W) {
+            const int d = tid - R;
+            for (int i = 0; i < nv; ++i) {
+                const int a = t0 + i + d;
+                if (a >= 0 && a < Ta) {
+                    const float y = sBand[i * BP + tid] - Sc, t = S + y;
+                    Sc = (t - S) - y;
+                    S = t;
+                }
+            }
+        }
+    }
+    if (tid < W) {
+        const int d = tid - R;
+        const int lo = d < 0 ? -d : 0, hi = Tv < Ta - d ? Tv : Ta - d;
+        const int cnt = hi - lo;
+        const float v = cnt >= (min_overlap > 1 ? min_overlap : 1) ? S / (float)cnt : nan;
+        sCurve[tid] = v;
+        if (curve) curve[(long)clip * W + tid] = v;
+    }
+    __syncthreads();
+    if (tid < W) {               // the median by rank: entry e is the (rank)-th smallest of the m non-NaN entries (ties by position)
+        const float v = sCurve[tid];
+        int m = 0, rank = 0;
+        for (int k = 0; k < W; ++k) {
+            const float c = sCurve[k];
+            m += c == c;
+            rank += (c < v || (c == v && k < tid)) ? 1 : 0;
+        }
+        if (v == v) {
+            if (rank == (m - 1) / 2) sMed[0] = v;
+            if (rank == m / 2) sMed[1] = v;
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        int best = -1;
+        float mx = 0.f;
+        for (int k = 0; k < W; ++k) {
+            const float c = sCurve[k];
+            if (c == c && (best < 0 || c > mx)) { best = k; mx = c; }
+        }
+        offset[clip] = best < 0 ? 0 : best - R;
+        conf[clip] = best < 0 ? nan : mx - (sMed[0] + sMed[1]) * 0.5f;
+    }
+}
+
+hipError_t launch_sync_offset(const float* vid, const int32_t* voff, const float* aud, const int32_t* aoff, int n, int D, int R, int min_overlap,
+                              float* curve, int32_t* offset, float* conf, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    if (D <= 0 || D % 64 || D > SYNC_MAX_D || R < 0 || R > SYNC_MAX_R || min_overlap < 1) return hipErrorInvalidValue;
+    const int nt = (32 + 2 * R + 31) / 32;
+#define SYNC_LAUNCH(NT) hipLaunchKernelGGL(sync_offset_kernel<NT>, dim3(n), dim3(256), 0, s, vid, voff, aud, aoff, D, R, min_overlap, curve, offset, conf)
+    switch (nt) {
+        case 1: SYNC_LAUNCH(1); break;
+        case 2: SYNC_LAUNCH(2); break;
+        case 3: SYNC_LAUNCH(3); break;
+        case 4: SYNC_LAUNCH(4); break;
+        default: SYNC_LAUNCH(5); break;
+    }
+#undef SYNC_LAUNCH
+    return hipGetLastError();
+}

@@ -1,6 +1,7 @@
 // Build-independent declarations of libjegal_hip (gfx950 only): everything that does not depend on the 16-bit operand type.
 // Included once, global namespace, by both kernel builds (common.h includes it).  The rule of the two builds is in common.h:
-// a kernel with no 16-bit operand is compiled once (elementwise_f32.hip, metrics.hip) and its launcher is declared here.
+// a kernel with no 16-bit operand is compiled once (elementwise_f32.hip, metrics.hip) and its launcher is declared here; so are the
+// launchers of gsa_kernels.hip, whose output type (fp16 / fp32) is a run-time flag and which no bf16 handle reaches.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -205,6 +206,19 @@ hipError_t launch_attn_matrix(const float* g, const float* c, const int32_t* gof
                               int32_t* best_frame, float* best_score, hipStream_t s);
 hipError_t launch_asd(const float* q, const float* cand, const int32_t* coff, int n, int D, float temp,
                       int32_t* pred2, hipStream_t s);
+// Audio-visual offset per clip (metrics.hip: sync_offset_kernel): mean cosine of the row pairs (t, t + d) for d = -R .. R -> curve
+// (optional, [n][2R + 1]; NaN where fewer than min_overlap pairs exist), offset = first arg-max, conf = max - median.  A clip outside
+// the limits (1..SYNC_MAX_T video and audio rows, one shift with enough pairs) gets offset 0, conf NaN, a NaN curve row.  No scratch.
+constexpr int SYNC_MAX_R = 64, SYNC_MAX_T = 8192, SYNC_MAX_D = 1024;
+hipError_t launch_sync_offset(const float* vid, const int32_t* voff, const float* aud, const int32_t* aoff, int n, int D, int R, int min_overlap,
+                              float* curve, int32_t* offset, float* conf, hipStream_t s);
+// GestSync's audio stream (gsa_kernels.hip).  conv1 + BatchNorm + ReLU + max-pool of windows n0 .. n0 + nwin - 1 -> out [nwin][19][24][64]
+// (fp16, or fp32 with out32): clip_form 0: src = x (N, 1, 80, 100); 1: src = mel (B, Tm, 80), window n = b * T + t reads mel rows
+// clamp(4 (t - 12) + 0..99, 0, valid[b] - 1) (valid: device [B] or nullptr = Tm).  w [64][9] (BatchNorm scale folded), shift [64]: fp32
+hipError_t launch_gsa_conv1_pool(const float* src, int clip_form, int n0, int nwin, int T, int Tm, const int* valid, const float* w,
+                                 const float* shift, void* out, int out32, hipStream_t s, char* kname = nullptr);
+// NHWC max-pool, window (2, 3), stride (2, 2): (N, H, W, C) -> (N, (H - 2) / 2 + 1, (W - 3) / 2 + 1, C), fp16 or (f32) fp32 elements; C % 8 == 0
+hipError_t launch_maxpool_2x3_s2(const void* in, void* out, int N, int H, int W, int C, int f32, hipStream_t s, char* kname = nullptr);
 // ASD per time window (metrics.hip: asd_windows_kernel): prob / cosv (optional) (n_win_i, P_i) at poff[i], pred [woff[n_scenes]].  A scene
 // outside the limits (1..64 candidates, 1..1024 words, 1..max_windows windows, tracks of 1..8192 frames inside 0..n_tracks-1) gets
 // pred = -1 and NaN rows in all of its windows.  No scratch.

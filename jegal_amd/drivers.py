@@ -10,6 +10,7 @@
     python -m jegal_amd.drivers retrieve --path D [--topk 10] # the retrieval evaluate_retrieval.py grades (-> retrieve_<direction>.npz)
     python -m jegal_amd.drivers search --path D --query F.pkl [--level word|phrase]   # which clips gesture a word, and at which frame (-> search_<F>.npz)
     python -m jegal_amd.drivers asd --path D --file avs_asd.csv [--win N --hop M]   # the detection evaluate_asd.py grades (-> asd.npz)
+    python -m jegal_amd.drivers sync_offset --checkpoint_path_gestsync CKPT --frames F.npy --wav F.wav [--mel F.npy] [--max_shift 15]   # audio-visual offset of a clip (-> <name>.sync.npz)
 
 Same flags, file naming and on-disk formats as the reference.  What is upstream of the hot path is
 NOT rebuilt: video decoding / mediapipe masking (the drivers read already masked 270x480 crops as
@@ -672,7 +673,65 @@ def cmd_asd(argv, engine=None):
     return 0
 
 
+SYNC_OFFSET_NOTE = ("The released GestSync checkpoint was trained on its authors' own mel normalisation, which is not in the reference tree: "
+                    "--wav goes through this library's log-mel front end (JEGAL's), whose parity with GestSync's is unpinned -- pass the "
+                    "authors' mel with --mel for a real checkpoint.  Parity of the network itself is pinned (GestSync.forward_aud).")
+
+
+def cmd_sync_offset(argv, engine=None, gestsync=None):
+    """Audio-visual offset of one clip: the thin composition of GestSync.extract_clip_feats (frames -> (T,1024)), the log-mel front end
+    (--wav, Engine.logmel) or a caller's mel (--mel: (4T,80) fp32, time-major, 4 mel steps per frame), GestSync.extract_clip_audio_feats
+    (mel -> (T,1024)) and metrics.sync_offset.  Prints the offset in frames (d > 0: the audio matching frame t is found d frames later,
+    i.e. the audio track lags) and the confidence; writes ``<res_dir>/<name>.sync.npz`` = {offset, conf, curve (2 max_shift + 1,),
+    shifts}."""
+    from . import audio as jaudio
+    from . import metrics as M
+    p = argparse.ArgumentParser(prog="sync_offset", epilog=SYNC_OFFSET_NOTE)
+    p.add_argument("--checkpoint_path_gestsync", required=True,
+                   help="GestSync checkpoint with its audio stream; 'synthetic' = the seeded test weights, whose embeddings carry NO sync "
+                        "signal (the result then only shows that the path runs)")
+    p.add_argument("--frames", required=True, help=".npy of masked uint8 crops (T,270,480,3)")
+    p.add_argument("--wav", default=None, help="16 kHz mono .wav of the clip (log-mel on the GPU). " + SYNC_OFFSET_NOTE)
+    p.add_argument("--mel", default=None, help=".npy (Tm,80) fp32 time-major mel of the clip, 4 steps per frame: used instead of --wav")
+    p.add_argument("--max_shift", type=int, default=15)
+    p.add_argument("--min_overlap", type=int, default=1)
+    p.add_argument("--res_dir", default=".")
+    _add_precision_args(p)
+    args = p.parse_args(argv)
+    if (args.wav is None) == (args.mel is None):
+        raise SystemExit("sync_offset: give --wav or --mel (one of them)")
+    if args.checkpoint_path_gestsync == "synthetic":
+        print("WARNING: synthetic GestSync weights: their window embeddings are 0.93-0.996 correlated whatever the input, so the offset "
+              "and confidence below are MEANINGLESS as a sync measurement; pass a trained checkpoint.")
+    if gestsync is None:
+        engine, gestsync, _ = _models(args, need_gestsync=True)
+    eng = engine if engine is not None else gestsync.engine
+    frames = np.load(args.frames)
+    if frames.ndim != 4 or tuple(frames.shape[1:]) != (270, 480, 3) or frames.dtype != np.uint8:
+        raise ValueError("--frames must hold (T,270,480,3) uint8 masked crops")
+    T = frames.shape[0]
+    vid = gestsync.extract_clip_feats(torch.from_numpy(frames).to(eng.device))[0]
+    if args.mel is not None:
+        mel = torch.from_numpy(np.load(args.mel).astype(np.float32))
+        if mel.dim() != 2 or mel.shape[1] != 80 or mel.shape[0] < 1:
+            raise ValueError("--mel must hold (Tm,80) mel rows")
+        mel = mel[None].to(eng.device)
+    else:
+        wav = torch.from_numpy(np.asarray(jaudio.load_wav(args.wav)).astype(np.float32))
+        mel = jaudio.wav2filterbanks(wav[None].to(eng.device), engine=eng)[0]
+    Ta = max(1, min(T, -(-int(mel.shape[1]) // 4)))            # audio windows: one per frame the mel covers
+    aud = gestsync.extract_clip_audio_feats(mel, Ta)[0]
+    off, conf, curve = M.sync_offset([vid], [aud], args.max_shift, args.min_overlap, engine=eng)
+    name = os.path.basename(args.frames).rsplit(".", 1)[0]
+    os.makedirs(args.res_dir, exist_ok=True)
+    out = os.path.join(args.res_dir, name + ".sync.npz")
+    np.savez(out, offset=off[0], conf=conf[0], curve=curve[0], shifts=np.arange(-args.max_shift, args.max_shift + 1, dtype=np.int32))
+    print("AV offset: {} frames   confidence: {:.4f}   ({} video / {} audio windows) -> {}".format(int(off[0]), float(conf[0]), T, Ta, out))
+    return 0
+
+
 COMMANDS = {
+    "sync_offset": cmd_sync_offset,
     "attn_matrix": cmd_attn_matrix,
     "retrieve": cmd_retrieve,
     "search": cmd_search,

@@ -270,6 +270,26 @@ def spot_words(gestures, contents, temp=0.07, normalize=True, engine=None, offse
     return _attn_call(gestures, contents, temp, normalize, engine, offsets, False)[1]
 
 
+def sync_offset(vid_feats, aud_feats, max_shift=15, min_overlap=1, engine=None):
+    """Audio-visual offset of every clip of a ragged batch from its GestSync window embeddings: vid_feats / aud_feats are lists of per-clip
+    (Tv_i, D) / (Ta_i, D) arrays (GestSync.extract_clip_feats / extract_clip_audio_feats rows; Ta_i may differ from Tv_i).  For each shift
+    d in -max_shift .. max_shift the curve holds the mean cosine of the pairs (video row t, audio row t + d); a shift with fewer than
+    min_overlap pairs is NaN and cannot win.  One jg_sync_offset call.
+    Returns host arrays (offsets (n,) int32: d > 0 means the audio row matching video row t is row t + d, i.e. the audio track lags by d
+    frames; conf (n,) float32: the curve's maximum minus its median; curves (n, 2 max_shift + 1) float32).  A clip without rows, with more
+    than 8192, or without a shift of min_overlap pairs: offset 0, conf NaN."""
+    if len(vid_feats) != len(aud_feats):
+        raise ValueError("one audio array per video array")
+    n, W = len(vid_feats), 2 * int(max_shift) + 1
+    if n == 0:
+        return np.zeros(0, np.int32), np.zeros(0, np.float32), np.zeros((0, W), np.float32)
+    eng = engine or Engine.get()
+    def rows(mats):          # host arrays, or tensors already on the device (the extractors' outputs)
+        return torch.cat([m.to(torch.float32) for m in mats], 0) if isinstance(mats[0], torch.Tensor) else _cat(mats)
+    off, conf, curve = eng.sync_offset(rows(vid_feats), rows(aud_feats), _offsets(vid_feats), _offsets(aud_feats), max_shift, min_overlap)
+    return _host(off), _host(conf), _host(curve)
+
+
 def asd_counts(pred):
     """[correct for 2, 4, 6 speakers, queries] from jg_asd's (n,3) argmax indices: the positive is candidate 0 (evaluate_asd.py:101-113)."""
     pred = np.asarray(pred).reshape(-1, 3)
