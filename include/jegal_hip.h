@@ -421,6 +421,58 @@ int jg_l2norm(jg_handle* h, const float* in, float* out, int rows, int D);
  * inference_embs.py:526-646): jg_gestsync_clip + jg_jegal_gestures(align=1) + jg_l2norm. */
 int jg_extract_gesture(jg_handle* h, const void* frames, int frames_dtype, int B, int T, float* out_emb);
 
+/* ---- gesture tracks of any length --------------------------------------------------------------
+ * forward_gestures has a 500-row positional table (modules.py:136) and the reference fails beyond it; a longer track is encoded in
+ * windows.  The window rule, for two integers win >= 1 and ctx >= 0 with win + 2 ctx <= 500 and a track of T frames:
+ *   the track has ceil(T / win) windows; window j has the CORE [j win, min((j + 1) win, T)) and the SPAN
+ *   [max(0, j win - ctx), min(T, (j + 1) win + ctx)).  The span is encoded as a clip of its own (positional row 0 = the first span frame,
+ *   every span row a valid key, nothing else visible); the window emits the rows of its core alone.
+ * The cores partition the track, so every frame is emitted exactly once: output row t of a track is row t - span_start of forward_gestures
+ * (+ align MLP) on the span slice of the window whose core holds t.  A track with T <= win is one window whose span is the whole track:
+ * exactly what forward_gestures defines for that clip.  No averaging over overlapping windows.
+ *
+ * jg_track_windows is that rule as a table, on the host: no handle, no device.  t_offsets_host [n_tracks + 1]: track i owns rows
+ * t_offsets[i] .. t_offsets[i + 1] - 1 of the concatenated tracks (empty tracks allowed: no windows).  table_host [cap][4] receives per
+ * window (span first row, span length, core offset inside the span, core length), rows global, windows ordered by track, then by j;
+ * table_host == NULL only counts (cap ignored).  *n_windows = the number of windows, *span_max = the longest span (0 without windows).
+ * Returns JG_ERR_ARG and writes nothing for n_tracks < 0, a null t_offsets_host (with n_tracks > 0), n_windows or span_max, win < 1,
+ * ctx < 0, win + 2 ctx > 500, a negative or decreasing offset, more than INT32_MAX windows, or cap < the number of windows. */
+int jg_track_windows(const int32_t* t_offsets_host, int n_tracks, int win, int ctx, int32_t* table_host, int cap, int* n_windows, int* span_max);
+/* The gesture branch over tracks by that rule: feats (sum T, 1024) fp32 (device; GestSync features, the tracks back to back),
+ * t_offsets_host [n_tracks + 1] on the HOST (they size the graph) with t_offsets[0] = 0 -> out (sum T, 512) fp32 (device), row for row;
+ * align != 0 adds proj_op_align_gesture as for jg_jegal_gestures, normalize != 0 applies jg_l2norm to the rows of out in place.
+ * The row-wise ends run once per track row, not once per window row (a row lies in up to (win + 2 ctx) / win spans): proj_ip_rgb on the
+ * sum T rows, a gather into the padded (n_windows, span_max) batch with positional rows and key mask, the encoder, a compaction of the
+ * core rows back into track order, proj_op_rgb (+ align) on sum T rows.
+ * A track's rows are a function of that track, win and ctx alone: not of the other tracks or of the track's place among them.  In bits
+ * this holds between calls with the same n_windows and span_max (the same tracks in another order give the same rows bit for bit);
+ * between calls of other sizes the GEMM planner and the attention launcher may pick other kernel instances, and the rows agree within
+ * the precision mode's contract (1e-3 rel-L2 of the reference in the default mode, 2e-5 in JG_PREC_FP32).
+ * Every precision mode of jg_jegal_gestures, the fp32 audit stage included.  Uses the workspace (one pass), runs on the handle's stream,
+ * asynchronous.  Workspace: 13 316 bytes per WINDOW row (n_windows * span_max of them) in the 16-bit modes, 20 484 in JG_PREC_FP32, and
+ * 10 - 12 KB per track row; the defaults of the Python layer (win 120, ctx 50) make 1.83 window rows per track row.  Nothing is chunked inside the
+ * call: a caller bounds a call -- its workspace and JG_TRACKS_MAX_WINDOW_ROWS -- by splitting at track boundaries, which changes no
+ * row's definition.
+ * JG_ERR_ARG before anything is enqueued: what jg_track_windows refuses, t_offsets[0] != 0, a null feats or out (with sum T > 0), more
+ * than JG_TRACKS_MAX_WINDOW_ROWS window rows.  JG_ERR_STATE: JEGAL weights never finalized.  n_tracks == 0 or sum T == 0 returns JG_OK
+ * and launches nothing. */
+#define JG_TRACKS_MAX_WINDOW_ROWS 1048575      /* n_windows * span_max of one call: the widest activation is (window rows, 2048), and the
+                                                  launchers index elements with 31 bits */
+int jg_jegal_gesture_tracks(jg_handle* h, const float* feats, const int32_t* t_offsets_host, int n_tracks, int win, int ctx, int align,
+                            int normalize, float* out);
+/* Check points of its two row movers: ONE production launch each on device buffers the caller owns (jg_debug_last_kernel names it).
+ * table_dev: [n_windows][4] int32 as jg_track_windows writes it, on the DEVICE, 16-byte aligned; the host cannot read it, so the caller
+ * answers for first row + span length staying inside p32 / out and for spans of at most span_max rows.
+ *   span_gather : p32 (rows, D) fp32, pe (>= span_max, D) fp32 -> x32 (n_windows, span_max, D): x32[w][s] = p32[first_w + s] + pe[s] for
+ *                 s < len_w, zero beyond; mask (n_windows, span_max) fp32 = 1 / 0.  Every element of x32 and mask is written.
+ *   core_compact: in (n_windows, span_max, D) elements of elem_bytes (2 or 4) -> out row first_w + s = in[w][s] for the core rows
+ *                 coff_w <= s < coff_w + clen_w; nothing else of out is written.
+ * JG_ERR_ARG before anything is enqueued: null pointers, n_windows or span_max < 1, span_gather's span_max > 500, D <= 0, D % 4, rows of
+ * D elem_bytes that are no multiple of 16 bytes, n_windows * span_max >= 2^31, buffers not 16-byte aligned. */
+int jg_debug_span_gather(jg_handle* h, const float* p32, const float* pe, const int32_t* table_dev, int n_windows, int span_max, int D, float* x32,
+                         float* mask);
+int jg_debug_core_compact(jg_handle* h, const void* in, int elem_bytes, const int32_t* table_dev, int n_windows, int span_max, int D, void* out);
+
 /* ---- metrics (evaluation/evaluate_*.py) ----------------------------------------------------- */
 /* temporal mean of ragged blocks (evaluate_retrieval.py:30-31): out[i] = mean(x[off[i]:off[i+1]]) */
 int jg_pool_mean(jg_handle* h, const float* x, const int32_t* offsets, int n, int D, float* out);

@@ -99,6 +99,10 @@ _SIGS = {
     "jg_debug_last_kernel": [_P, ctypes.c_char_p, _I],
     "jg_debug_conv_rows": [_P, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)],
     "jg_jegal_gestures": [_P, _P, _P, _I, _I, _I, _P],
+    "jg_track_windows": [ctypes.POINTER(ctypes.c_int32), _I, _I, _I, ctypes.POINTER(ctypes.c_int32), _I, ctypes.POINTER(_I), ctypes.POINTER(_I)],
+    "jg_jegal_gesture_tracks": [_P, _P, ctypes.POINTER(ctypes.c_int32), _I, _I, _I, _I, _I, _P],
+    "jg_debug_span_gather": [_P, _P, _P, _P, _I, _I, _I, _P, _P],
+    "jg_debug_core_compact": [_P, _P, _I, _P, _I, _I, _I, _P],
     "jg_jegal_audio": [_P, _P, _I, _I, _P],
     "jg_jegal_audio_ragged": [_P, _P, _I, _I, ctypes.POINTER(ctypes.c_int32), _P],
     "jg_audio_len": [_I],
@@ -213,6 +217,32 @@ class JegalError(RuntimeError):
     def __init__(self, msg, code=None):
         super().__init__(msg)
         self.code = code
+
+
+def _track_offsets(lengths):
+    """Lengths of tracks -> the (n + 1) int32 row offsets jg_track_windows / jg_jegal_gesture_tracks take."""
+    lens = [int(x) for x in lengths]
+    if any(t < 0 for t in lens) or sum(lens) > 2**31 - 1:
+        raise ValueError("track lengths must be >= 0 and sum to less than 2^31 rows")
+    return (ctypes.c_int32 * (len(lens) + 1))(*np.concatenate([[0], np.cumsum(lens, dtype=np.int64)]).astype(np.int32))
+
+
+def track_windows(lengths, win, ctx):
+    """The window rule of long gesture tracks (jg_track_windows, include/jegal_hip.h) -> (table, span_max): table (n_windows, 4) int32 =
+    (span first row, span length, core offset inside the span, core length) per window, rows counted over the concatenated tracks.
+    Needs no Engine and no GPU."""
+    lib = load_library()
+    off = _track_offsets(lengths)
+    n, smax = _I(), _I()
+    rc = lib.jg_track_windows(off, len(off) - 1, int(win), int(ctx), None, 0, ctypes.byref(n), ctypes.byref(smax))
+    if rc != 0:
+        raise JegalError(f"jg_track_windows: bad arguments (need win >= 1, ctx >= 0, win + 2 ctx <= 500) ({rc})", rc)
+    table = np.zeros((n.value, 4), np.int32)
+    rc = lib.jg_track_windows(off, len(off) - 1, int(win), int(ctx), table.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), n.value,
+                              ctypes.byref(n), ctypes.byref(smax))
+    if rc != 0:
+        raise JegalError(f"jg_track_windows failed ({rc})", rc)
+    return table, smax.value
 
 
 def _ptr(t):
@@ -654,6 +684,49 @@ class Engine:
         out = torch.empty((B, T, 512), dtype=torch.float32, device=self.device)
         self._ck(self.lib.jg_jegal_gestures(self.h, _ptr(feats), _ptr(m), B, T, int(bool(align)), _ptr(out)))
         return out
+
+    @staticmethod
+    def track_windows(lengths, win, ctx):
+        """The window table of a set of tracks, (n, 4) int32, and span_max (the module's track_windows; no device involved)."""
+        return track_windows(lengths, win, ctx)
+
+    def jegal_gesture_tracks(self, feats, lengths, win=120, ctx=50, align=True, normalize=False):
+        """Gesture embeddings of tracks of ANY length (jg_jegal_gesture_tracks): feats (sum T, 1024), the tracks' GestSync features back to
+        back, lengths = frames per track -> (sum T, 512) on the device, row for row.  A track is encoded in windows: every `win` frames are
+        emitted from a span that reaches `ctx` frames further on both sides (win + 2 ctx <= 500, the positional table); a track of at
+        most `win` frames is one window, i.e. exactly jegal_gestures on that clip (include/jegal_hip.h has the rule).
+        The defaults give spans of at most 220 frames, the longest clip of the reference's dataset lists (dataset/avs_*.csv), i.e. what the
+        model was trained on.  That is a choice from the dataset's lengths, not a measured optimum: no trained checkpoint is available
+        to tune win / ctx on retrieval quality."""
+        self._bind_stream()
+        feats = self._f32(feats)
+        off = _track_offsets(lengths)
+        rows = int(off[len(off) - 1])
+        if feats.dim() != 2 or feats.shape[1] != 1024 or feats.shape[0] != rows:
+            raise ValueError(f"feats must be (sum of lengths = {rows}, 1024), got {tuple(feats.shape)}")
+        out = torch.empty((rows, 512), dtype=torch.float32, device=self.device)
+        self._ck(self.lib.jg_jegal_gesture_tracks(self.h, _ptr(feats), off, len(off) - 1, int(win), int(ctx), int(bool(align)), int(bool(normalize)),
+                                                  _ptr(out)))
+        return out
+
+    def extract_gesture_track(self, frames, win=120, ctx=50):
+        """One track of frames (T,270,480,3), T unbounded -> unit-norm gesture embeddings (T,512): gestsync_clip on the track as a batch of
+        one, then jegal_gesture_tracks(normalize=True).  (extract_gesture is the one-call form for clips of at most 500 frames.)"""
+        if not isinstance(frames, torch.Tensor):
+            frames = torch.as_tensor(frames)
+        if frames.dim() != 4:
+            raise ValueError(f"frames must be one track (T,270,480,3), got {tuple(frames.shape)}")
+        feats = self.gestsync_clip(frames[None])[0]
+        return self.jegal_gesture_tracks(feats, [feats.shape[0]], win=win, ctx=ctx, align=True, normalize=True)
+
+    def debug_span_gather(self, p32, pe, table, n_windows, span_max, D, x32, mask):
+        self._bind_stream()
+        self._ck(self.lib.jg_debug_span_gather(self.h, _ptr(p32), _ptr(pe), _ptr(table), n_windows, span_max, D, _ptr(x32), _ptr(mask)))
+
+    def debug_core_compact(self, x, table, n_windows, span_max, D, out):
+        """x (n_windows, span_max, D) of 2- or 4-byte elements; out rows of the same type, written in place."""
+        self._bind_stream()
+        self._ck(self.lib.jg_debug_core_compact(self.h, _ptr(x), x.element_size(), _ptr(table), n_windows, span_max, D, _ptr(out)))
 
     def audio_len(self, Tm):
         return int(self.lib.jg_audio_len(int(Tm)))

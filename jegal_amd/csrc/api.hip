@@ -390,6 +390,31 @@ int jg_jegal_gestures(jg_handle* h, const float* feats, const float* mask, int B
     return jegal_gestures_impl(h, feats, mask, B, T, align, out);
 }
 
+int jg_track_windows(const int32_t* t_offsets_host, int n_tracks, int win, int ctx, int32_t* table_host, int cap, int* n_windows, int* span_max) {
+    return plan_track_windows(t_offsets_host, n_tracks, win, ctx, table_host, cap, n_windows, span_max);
+}
+
+int jg_jegal_gesture_tracks(jg_handle* h, const float* feats, const int32_t* t_offsets_host, int n_tracks, int win, int ctx, int align, int normalize,
+                            float* out) {
+    ENTER(h);
+    int nw = 0, span_max = 0;
+    if (plan_track_windows(t_offsets_host, n_tracks, win, ctx, nullptr, 0, &nw, &span_max) != JG_OK)
+        JG_FAIL(h, JG_ERR_ARG, "bad tracks: need n_tracks >= 0, non-decreasing offsets >= 0, win >= 1, ctx >= 0, win + 2 ctx <= %d", TRACK_SPAN_MAX);
+    if (n_tracks > 0 && t_offsets_host[0] != 0) JG_FAIL(h, JG_ERR_ARG, "t_offsets[0] must be 0: feats and out hold the tracks' rows alone");
+    const int rows = n_tracks > 0 ? t_offsets_host[n_tracks] : 0;
+    if (rows == 0) return JG_OK;
+    if (!feats || !out) JG_FAIL(h, JG_ERR_ARG, "null buffer");
+    if ((long)nw * span_max > JG_TRACKS_MAX_WINDOW_ROWS)
+        JG_FAIL(h, JG_ERR_ARG, "%d windows of %d rows: more than %d window rows in one call (split at track boundaries)", nw, span_max, JG_TRACKS_MAX_WINDOW_ROWS);
+    if (!h->jg.m.ready) JG_FAIL(h, JG_ERR_STATE, "JEGAL weights not finalized");
+    std::vector<int32_t> table((size_t)nw * 4);
+    if (plan_track_windows(t_offsets_host, n_tracks, win, ctx, table.data(), nw, &nw, &span_max) != JG_OK) JG_FAIL(h, JG_ERR_ARG, "window table");
+    RET(begin_pass(h));
+    RET(jegal_gesture_tracks_impl(h, feats, table.data(), nw, span_max, rows, align, out));
+    if (!normalize) return JG_OK;
+    return timed(h, JG_ST_MISC, [&] { return launch_l2norm(out, out, rows, 512, h->stream); });
+}
+
 int jg_audio_len(int Tm) {
     const int h1 = (Tm + 2 - 3) / 2 + 1;
     return (h1 + 2 - 3) / 2 + 1;

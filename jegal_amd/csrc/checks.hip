@@ -580,6 +580,28 @@ int jg_debug_rc_bias(jg_handle* h, const void* A, int64_t lda, int64_t a_elems, 
     return rc;
 }
 
+int jg_debug_span_gather(jg_handle* h, const float* p32, const float* pe, const int32_t* table_dev, int n_windows, int span_max, int D, float* x32,
+                         float* mask) {
+    ENTER(h);
+    h->kname[0] = 0;
+    if (!p32 || !pe || !table_dev || !x32 || !mask || n_windows < 1 || span_max < 1 || span_max > TRACK_SPAN_MAX || D <= 0 || !al(p32, 16) ||
+        !al(pe, 16) || !al(table_dev, 16) || !al(x32, 16) || !al(mask, 4))
+        JG_FAIL(h, JG_ERR_ARG, "jg_debug_span_gather: bad arguments (span_max 1..%d, 16-byte aligned fp32 rows and table)", TRACK_SPAN_MAX);
+    const int rc = check_result(h, launch_span_gather(p32, pe, table_dev, n_windows, span_max, D, x32, mask, h->stream), "launch_span_gather");
+    if (rc == JG_OK) record_kernel(h->kname, "%s", "span_gather_kernel");
+    return rc;
+}
+
+int jg_debug_core_compact(jg_handle* h, const void* in, int elem_bytes, const int32_t* table_dev, int n_windows, int span_max, int D, void* out) {
+    ENTER(h);
+    h->kname[0] = 0;
+    if (!in || !table_dev || !out || n_windows < 1 || span_max < 1 || D <= 0 || D % 4 || !al(in, 16) || !al(table_dev, 16) || !al(out, 16))
+        JG_FAIL(h, JG_ERR_ARG, "jg_debug_core_compact: bad arguments (D %% 4 == 0, 16-byte aligned rows and table)");
+    const int rc = check_result(h, launch_core_compact(in, elem_bytes, table_dev, n_windows, span_max, D, out, h->stream), "launch_core_compact");
+    if (rc == JG_OK) record_kernel(h->kname, "%s", "core_compact_kernel");
+    return rc;
+}
+
 int jg_debug_last_kernel(jg_handle* h, char* buf, int len) {
     if (!h || !buf || len <= 0) return JG_ERR_ARG;
     snprintf(buf, (size_t)len, "%s", h->kname);

@@ -1,5 +1,6 @@
 // Helper kernels (gfx950) with no 16-bit operand: compiled once, launchers declared in shared.h.  Layout changes, L2-normalise,
-// ragged means, the XLM-RoBERTa embedding sum and LayerNorm statistics, the log-mel and mask + resize front ends.
+// the row movers of long gesture tracks, ragged means, the XLM-RoBERTa embedding sum and LayerNorm statistics, the log-mel and
+// mask + resize front ends.
 #include "common.h"
 
 // (N, L, D) -> (N, D, L): the .transpose(1,2) of gestsync.py:156 for the drop-in forward_vid output.
@@ -46,6 +47,67 @@ __global__ void l2norm_kernel(const float* in, float* out, int rows, int D) {
 hipError_t launch_l2norm(const float* in, float* out, int rows, int D, hipStream_t s) {
     if (rows <= 0) return hipSuccess;
     hipLaunchKernelGGL(l2norm_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, in, out, rows, D);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
+// Long gesture tracks (jegal.hip, jegal_gesture_tracks_impl; the window rule: include/jegal_hip.h, jg_track_windows).  A window w of the
+// table [n_windows][4] = (span first row, span length, core offset inside the span, core length) is encoded as a clip of span_max
+// rows.  Both kernels are row movers: one wave per (window, span row), the window's table entry in one 16-byte scalar load, 16 bytes
+// per lane and access (a 2 KB fp32 row of D = 512 is two accesses of the wave, each one contiguous KB), no LDS.
+//   span_gather : x32[w][s] = p32[first_w + s] + pe[s] and mask[w][s] = 1 for s < len_w; zeros and 0 for the padding rows s >= len_w,
+//                 which have to be WRITTEN: the encoder reads them as keys of weight exactly 0, and 0 * NaN is NaN (option ws_poison).
+//   core_compact: out[first_w + s] = in[w][s] for the core rows coff_w <= s < coff_w + clen_w -- the cores partition the tracks, so
+//                 every row of `out` is written exactly once, in track order.  Rows of row16 16-byte pieces, whatever the element type.
+typedef int i32x4_t __attribute__((ext_vector_type(4)));
+__global__ __launch_bounds__(256) void span_gather_kernel(const float* __restrict__ p32, const float* __restrict__ pe, const i32x4_t* __restrict__ table,
+                                                          unsigned rows, unsigned span_max, int D, float* __restrict__ x32, float* __restrict__ mask) {
+    const unsigned r = __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (threadIdx.x >> 6));      // wave-uniform: the table entry is a scalar load
+    if (r >= rows) return;
+    const int lane = threadIdx.x & 63;
+    const unsigned w = r / span_max, s = r - w * span_max;
+    const i32x4_t e = table[w];
+    const bool live = s < (unsigned)min(max(e.y, 0), (int)span_max);
+    const float* src = p32 + ((long)e.x + s) * D;
+    const float* pos = pe + (long)s * D;
+    float* dst = x32 + (long)r * D;
+    for (int c = lane * 4; c < D; c += 256) {
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};
+        if (live) v = *reinterpret_cast<const f32x4*>(src + c) + *reinterpret_cast<const f32x4*>(pos + c);
+        *reinterpret_cast<f32x4*>(dst + c) = v;
+    }
+    if (lane == 0) mask[r] = live ? 1.f : 0.f;
+}
+
+hipError_t launch_span_gather(const float* p32, const float* pe, const int32_t* table, int n_windows, int span_max, int D, float* x32, float* mask,
+                              hipStream_t s) {
+    if (n_windows <= 0) return hipSuccess;
+    if (span_max < 1 || D <= 0 || D % 4 || (long)n_windows * span_max >= (1L << 31)) return hipErrorInvalidValue;
+    const unsigned rows = (unsigned)n_windows * (unsigned)span_max;
+    hipLaunchKernelGGL(span_gather_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, p32, pe, reinterpret_cast<const i32x4_t*>(table), rows,
+                       (unsigned)span_max, D, x32, mask);
+    return hipGetLastError();
+}
+
+__global__ __launch_bounds__(256) void core_compact_kernel(const uint4* __restrict__ in, const i32x4_t* __restrict__ table, unsigned rows, unsigned span_max,
+                                                           int row16, uint4* __restrict__ out) {
+    const unsigned r = __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (threadIdx.x >> 6));
+    if (r >= rows) return;
+    const unsigned w = r / span_max, s = r - w * span_max;
+    const i32x4_t e = table[w];
+    if ((int)s < e.z || (int)s >= e.z + e.w) return;                  // not a core row: some other window emits this frame
+    const uint4* src = in + (long)r * row16;
+    uint4* dst = out + ((long)e.x + s) * row16;
+    for (int i = threadIdx.x & 63; i < row16; i += 64) dst[i] = src[i];
+}
+
+hipError_t launch_core_compact(const void* in, int elem_bytes, const int32_t* table, int n_windows, int span_max, int D, void* out, hipStream_t s) {
+    if (n_windows <= 0) return hipSuccess;
+    if (span_max < 1 || D <= 0 || (elem_bytes != 2 && elem_bytes != 4) || (long)D * elem_bytes % 16 || (long)n_windows * span_max >= (1L << 31))
+        return hipErrorInvalidValue;
+    const unsigned rows = (unsigned)n_windows * (unsigned)span_max;
+    hipLaunchKernelGGL(core_compact_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, static_cast<const uint4*>(in), reinterpret_cast<const i32x4_t*>(table),
+                       rows, (unsigned)span_max, (int)((long)D * elem_bytes / 16), static_cast<uint4*>(out));
     return hipGetLastError();
 }
 

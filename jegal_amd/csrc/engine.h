@@ -491,6 +491,8 @@ int finalize_gestsync_audio(jg_handle* h);
 int gestsync_audio_impl(jg_handle* h, const float* src, int clip_form, int B, int Tm, int T, const int32_t* valid_host, float* out);
 int finalize_jegal(jg_handle* h);
 int jegal_gestures_impl(jg_handle* h, const float* feats, const float* mask, int B, int T, int align, float* out);
+int plan_track_windows(const int32_t* off, int n_tracks, int win, int ctx, int32_t* table, int cap, int* n_windows, int* span_max);
+int jegal_gesture_tracks_impl(jg_handle* h, const float* feats, const int32_t* table_host, int n_windows, int span_max, int rows, int align, float* out);
 int jegal_audio_impl(jg_handle* h, const float* mel, int B, int Tm, const int32_t* valid_host, float* out);
 int jegal_text_impl(jg_handle* h, const float* states, const float* mask, int B, int L, float* out);
 int fuse_content_impl(jg_handle* h, const float* fused, int rows, float* out);

@@ -2,6 +2,8 @@
 // for the 16-bit and the fp32 arithmetics (engine.h, Arith<T>).  Host code only.
 #include "engine.h"
 
+#include <algorithm>
+
 namespace engine {
 
 int finalize_jegal(jg_handle* h) {
@@ -93,7 +95,8 @@ static int annotated_encoder(jg_handle* h, Arith<T> ar, const EncLayer* layers, 
     return layernorm(h, ar, x32, fin, M, D, LN_ANNOTATED, 0, n, n32);
 }
 
-// proj_ip_rgb + positional rows (jegal.py:25-28,84-85): feats (M, 1024) fp32 -> the stream x32 (M, 512); S tokens per clip
+// proj_ip_rgb + positional rows (jegal.py:25-28,84-85): feats (M, 1024) fp32 -> the stream x32 (M, 512); S tokens per clip.
+// S == 0: without the positional rows (long tracks: span_gather adds them per window)
 template <class T>
 static int jegal_input(jg_handle* h, Arith<T> ar, const float* feats, int M, int S, float* x32) {
     const JegalModel& jg = h->jg;
@@ -105,7 +108,7 @@ static int jegal_input(jg_handle* h, Arith<T> ar, const float* feats, int M, int
     RET(wsalloc(h, (size_t)M * 512, &t));
     RET(linear_to32(h, ar, in, 1024, M, jg.ip0, t32));
     RET(layernorm(h, ar, t32, jg.ip_ln, M, 512, LN_STD, 1, t));
-    return linear_to32(h, ar, t, 512, M, jg.ip3, x32, jg.rgb_pe, 512, S);
+    return linear_to32(h, ar, t, 512, M, jg.ip3, x32, S ? jg.rgb_pe : nullptr, 512, S);
 }
 
 // proj_op_rgb (+ proj_op_align_gesture) from the final norm's rows
@@ -205,6 +208,16 @@ static int jegal_audio(jg_handle* h, Arith<T> ar, const float* mel, int B, int T
 }
 
 // ------------------------------------------------------------------------------------ entries: choose the arithmetics and call
+// The gesture branch in the 16-bit modes: its two ends keep fp32 activations (option jegal_fp32_ends; not in the plain-fp16 / bf16 reported
+// modes, not while calibrating): in production with split operands on the fp16 matrix cores (`ends`), under diagnosis (audit_jegal_parts
+// bits 1 / 8) on the fp32 MFMA.  parts: audit_jegal_parts' bits as the graph runs them (1 input projection, 8 final norm + tail in `ends`)
+struct GestureEnds { int parts; A32 ends; };
+static GestureEnds gesture_ends(const jg_handle* h) {
+    const JegalModel& jg = h->jg;
+    const bool ends32 = split_ends(h, {&jg.ip0, &jg.ip3, &jg.op_rgb, &jg.al_g0, &jg.al_g2});
+    return {h->audit_jegal_parts | (ends32 ? 9 : 0), A32{ends32 && !(h->audit_jegal_parts & 9)}};
+}
+
 int jegal_gestures_impl(jg_handle* h, const float* feats, const float* mask, int B, int T, int align, float* out) {
     const JegalModel& jg = h->jg;
     if (!jg.m.ready) JG_FAIL(h, JG_ERR_STATE, "JEGAL weights not finalized");
@@ -218,17 +231,100 @@ int jegal_gestures_impl(jg_handle* h, const float* feats, const float* mask, int
         RET(annotated_encoder(h, A32(), jg.rgb_layers, 6, jg.rgb_norm, x32, n32, mask, B, T, 512, 2048));
         return jegal_tail(h, A32(), n32, M, align, out);
     }
-    // the branch's two ends keep fp32 activations (option jegal_fp32_ends; not in the plain-fp16 / bf16 reported modes, not while calibrating):
-    // in production with split operands on the fp16 matrix cores, under diagnosis (audit_jegal_parts bits 1 / 8) on the fp32 MFMA
-    const bool ends32 = split_ends(h, {&jg.ip0, &jg.ip3, &jg.op_rgb, &jg.al_g0, &jg.al_g2});
-    const int parts = h->audit_jegal_parts | (ends32 ? 9 : 0);
-    const A32 ends{ends32 && !(h->audit_jegal_parts & 9)};
+    const auto [parts, ends] = gesture_ends(h);
     f16* n16;
     RET(wsalloc(h, (size_t)M * 512, &n16));
     if (parts & 8) RET(wsalloc(h, (size_t)M * 512, &n32));
     RET(parts & 1 ? jegal_input(h, ends, feats, M, T, x32) : jegal_input(h, A16(), feats, M, T, x32));
     RET(annotated_encoder(h, A16(), jg.rgb_layers, 6, jg.rgb_norm, x32, n16, mask, B, T, 512, 2048, parts, n32));
     return parts & 8 ? jegal_tail(h, ends, n32, M, align, out) : jegal_tail(h, A16(), n16, M, align, out);
+}
+
+// The window rule of long gesture tracks (include/jegal_hip.h, jg_track_windows), and the only place it is written down: track i =
+// rows off[i] .. off[i + 1] - 1 is cut into ceil(T / win) windows; window j emits its core [j win, min((j + 1) win, T)) and is encoded
+// over its span [max(0, j win - ctx), min(T, (j + 1) win + ctx)).  table (optional) [cap][4] = (span first row, span length, core
+// offset inside the span, core length), rows global.  Pure host arithmetic; nothing is written unless every argument is good.
+int plan_track_windows(const int32_t* off, int n_tracks, int win, int ctx, int32_t* table, int cap, int* n_windows, int* span_max) {
+    if (n_tracks < 0 || (n_tracks > 0 && !off) || !n_windows || !span_max || win < 1 || ctx < 0 || (long)win + 2L * ctx > TRACK_SPAN_MAX)
+        return JG_ERR_ARG;
+    long n = 0;
+    int smax = 0;
+    for (int i = 0; i < n_tracks; ++i) {
+        if (off[i] < 0 || off[i + 1] < off[i]) return JG_ERR_ARG;
+        const int T = off[i + 1] - off[i];
+        n += ((long)T + win - 1) / win;
+        // the track's longest span: no span is longer than `bound`, and in a long track the first window clear of both ends reaches it
+        const int bound = std::min(T, win + 2 * ctx);
+        int st = 0;
+        for (long c0 = 0; c0 < T && st < bound; c0 += win)
+            st = std::max(st, (int)(std::min((long)T, c0 + win + ctx) - std::max(0L, c0 - ctx)));
+        smax = std::max(smax, st);
+    }
+    if (n > INT32_MAX || (table && (cap < 0 || n > cap))) return JG_ERR_ARG;
+    if (table) {
+        int32_t* e = table;
+        for (int i = 0; i < n_tracks; ++i) {
+            const long T = off[i + 1] - off[i];
+            for (long c0 = 0; c0 < T; c0 += win, e += 4) {
+                const long c1 = std::min(T, c0 + win), s0 = std::max(0L, c0 - ctx), s1 = std::min(T, c0 + win + ctx);
+                e[0] = (int32_t)(off[i] + s0); e[1] = (int32_t)(s1 - s0); e[2] = (int32_t)(c0 - s0); e[3] = (int32_t)(c1 - c0);
+            }
+        }
+    }
+    *n_windows = (int)n;
+    *span_max = smax;
+    return JG_OK;
+}
+
+// forward_gestures (+ align MLP) over the windows of long tracks.  The row-wise ends run once per TRACK row (a row lies in up to
+// (win + 2 ctx) / win spans): proj_ip_rgb on the `rows` track rows, span_gather into the (n_windows, span_max) padded batch with the
+// positional rows and the key mask, the encoder as jegal_gestures_impl runs it, core_compact of the final norm's rows -- the operand
+// the tail reads, 16-bit or fp32 -- back into track order, proj_op_rgb (+ align) on `rows` rows.  table_host: plan_track_windows
+int jegal_gesture_tracks_impl(jg_handle* h, const float* feats, const int32_t* table_host, int n_windows, int span_max, int rows, int align, float* out) {
+    const JegalModel& jg = h->jg;
+    if (!jg.m.ready) JG_FAIL(h, JG_ERR_STATE, "JEGAL weights not finalized");
+    if (n_windows <= 0 || rows <= 0 || span_max <= 0 || span_max > TRACK_SPAN_MAX) JG_FAIL(h, JG_ERR_ARG, "empty window table or span_max outside 1..500");
+    const int B = n_windows, S = span_max, M = B * S;
+    int32_t* table;
+    float *p32, *x32, *mask, *n32 = nullptr;
+    RET(wsalloc(h, (size_t)B * 4, &table));
+    RET(upload_i32_async(h, table_host, (size_t)B * 4, table));
+    RET(wsalloc(h, (size_t)rows * 512, &p32));
+    RET(wsalloc(h, (size_t)M * 512, &x32));
+    RET(wsalloc(h, (size_t)M, &mask));
+    auto gather = [&]() { return timed(h, JG_ST_MISC, [&] { return launch_span_gather(p32, jg.rgb_pe, table, B, S, 512, x32, mask, h->stream); }); };
+    auto compact = [&](const void* n, int elem_bytes, void* c) {
+        return timed(h, JG_ST_MISC, [&] { return launch_core_compact(n, elem_bytes, table, B, S, 512, c, h->stream); });
+    };
+    if (audit_mask(h) & AUD_JG) {
+        float* c32;
+        RET(wsalloc(h, (size_t)M * 512, &n32));
+        RET(wsalloc(h, (size_t)rows * 512, &c32));
+        RET(jegal_input(h, A32(), feats, rows, 0, p32));
+        RET(gather());
+        RET(annotated_encoder(h, A32(), jg.rgb_layers, 6, jg.rgb_norm, x32, n32, mask, B, S, 512, 2048));
+        RET(compact(n32, 4, c32));
+        return jegal_tail(h, A32(), c32, rows, align, out);
+    }
+    const auto [parts, ends] = gesture_ends(h);
+    f16 *n16, *c16 = nullptr;
+    float* c32 = nullptr;
+    RET(wsalloc(h, (size_t)M * 512, &n16));
+    if (parts & 8) {
+        RET(wsalloc(h, (size_t)M * 512, &n32));
+        RET(wsalloc(h, (size_t)rows * 512, &c32));
+    } else {
+        RET(wsalloc(h, (size_t)rows * 512, &c16));
+    }
+    RET(parts & 1 ? jegal_input(h, ends, feats, rows, 0, p32) : jegal_input(h, A16(), feats, rows, 0, p32));
+    RET(gather());
+    RET(annotated_encoder(h, A16(), jg.rgb_layers, 6, jg.rgb_norm, x32, n16, mask, B, S, 512, 2048, parts, n32));
+    if (parts & 8) {
+        RET(compact(n32, 4, c32));
+        return jegal_tail(h, ends, c32, rows, align, out);
+    }
+    RET(compact(n16, 2, c16));
+    return jegal_tail(h, A16(), c16, rows, align, out);
 }
 
 // valid_host (optional, host [B]): clip b holds valid_host[b] mel frames, the rest of its Tm rows is batch padding

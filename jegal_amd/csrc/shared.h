@@ -165,6 +165,14 @@ hipError_t launch_conv_rowmaps(const int* s2, int NF, const ConvRowMap* layers, 
 size_t conv1_edge_elems(long positions);
 hipError_t launch_transpose_tokens(const float* in, int N, int L, int D, float* out, hipStream_t s);
 hipError_t launch_l2norm(const float* in, float* out, int rows, int D, hipStream_t s);
+// Windows of long gesture tracks (elementwise_f32.hip; the rule: jg_track_windows).  table: device [n_windows][4] int32 = (span first row,
+// span length, core offset inside the span, core length), 16-byte aligned.  span_gather: x32 (n_windows, span_max, D) = p32 rows + pe rows,
+// zero beyond a span's length, mask (n_windows, span_max) = 1 / 0; pe needs span_max rows.  core_compact: the core rows of
+// in (n_windows, span_max, D) elements of elem_bytes (2 or 4; D elem_bytes % 16 == 0) -> out row (span first row + s).
+constexpr int TRACK_SPAN_MAX = 500;          // rows of JEGAL's positional table (modules.py:136): win + 2 ctx <= TRACK_SPAN_MAX
+hipError_t launch_span_gather(const float* p32, const float* pe, const int32_t* table, int n_windows, int span_max, int D, float* x32, float* mask,
+                              hipStream_t s);
+hipError_t launch_core_compact(const void* in, int elem_bytes, const int32_t* table, int n_windows, int span_max, int D, void* out, hipStream_t s);
 // Test aid (option ws_poison): fill with 0xff bytes (fp16 / fp32 NaN) by a kernel of our own on the stream -- NOT hipMemsetAsync: two 1-GiB
 // hipMemsetAsync fills running concurrently on two streams were observed to overlap the kernels enqueued BEHIND them on their own stream
 // (tools/experiments/xlmr_race/xl_poison_probe.py, round 6)

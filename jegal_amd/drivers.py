@@ -11,6 +11,7 @@
     python -m jegal_amd.drivers search --path D --query F.pkl [--level word|phrase]   # which clips gesture a word, and at which frame (-> search_<F>.npz)
     python -m jegal_amd.drivers asd --path D --file avs_asd.csv [--win N --hop M]   # the detection evaluate_asd.py grades (-> asd.npz)
     python -m jegal_amd.drivers sync_offset --checkpoint_path_gestsync CKPT --frames F.npy --wav F.wav [--mel F.npy] [--max_shift 15]   # audio-visual offset of a clip (-> <name>.sync.npz)
+    python -m jegal_amd.drivers embed_tracks --checkpoint_path_jegal CKPT --feature_dir D --result_dir R [--win 120 --ctx 50]   # gesture embeddings of tracks of any length (-> R/v/<vid>__<track>.pkl)
 
 Same flags, file naming and on-disk formats as the reference.  What is upstream of the hot path is
 NOT rebuilt: video decoding / mediapipe masking (the drivers read already masked 270x480 crops as
@@ -730,7 +731,97 @@ def cmd_sync_offset(argv, engine=None, gestsync=None):
     return 0
 
 
+def cmd_embed_tracks(argv, engine=None, jegal=None):
+    """Gesture embeddings of whole tracks, however long: reads the ``<feature_dir>/<vid>/<track>.npy`` (T,1024) GestSync features that
+    extract_gestsync_feats writes, runs JEGAL.forward_gesture_tracks on them (windows of --win emitted frames with --ctx frames of context
+    on both sides: include/jegal_hip.h, jg_jegal_gesture_tracks) and writes ``<result_dir>/v/<vid>__<track>.pkl`` = {"gesture_emb": (T,512)
+    unit rows, "content_emb": None, "info": {"fname", "win", "ctx"}} -- the file search, asd and attn_matrix read.  Tracks are packed into
+    engine calls of at most --rows_per_call frames (a longer track goes alone); a track's rows do not depend on what it is packed with.
+    engine / jegal: an Engine and a loaded JEGAL to run on (default: this process's, loaded from --checkpoint_path_jegal)."""
+    p = argparse.ArgumentParser(prog="embed_tracks")
+    p.add_argument("--checkpoint_path_jegal", required=True)
+    p.add_argument("--feature_dir", required=True, help="<vid>/<track>.npy GestSync features (T,1024)")
+    p.add_argument("--result_dir", required=True)
+    p.add_argument("--win", type=int, default=120, help="frames a window emits")
+    p.add_argument("--ctx", type=int, default=50, help="frames of context a window sees on each side (win + 2 ctx <= 500).  The defaults make spans of "
+                                                       "at most 220 frames, the longest clip of the training lists: a choice, not a measured optimum")
+    p.add_argument("--rows_per_call", type=int, default=16384, help="frames per engine call (bounds the workspace: ~25 KB per frame at the defaults)")
+    p.add_argument("--rank", type=int, default=None)
+    p.add_argument("--nshard", type=int, default=None)
+    _add_precision_args(p)
+    args = p.parse_args(argv)
+    if args.win < 1 or args.ctx < 0 or args.win + 2 * args.ctx > 500:
+        raise SystemExit("embed_tracks: need --win >= 1, --ctx >= 0 and win + 2 ctx <= 500")
+    if jegal is None:
+        ns = argparse.Namespace(checkpoint_path=args.checkpoint_path_jegal, precision=args.precision, calibrate_frames=args.calibrate_frames)
+        engine, _, jegal = _models(ns, need_jegal=True)
+    res_dir = os.path.join(args.result_dir, "v")
+    os.makedirs(res_dir, exist_ok=True)
+    files = sorted(glob.glob(os.path.join(args.feature_dir, "*", "*.npy")))
+    lo, hi = jdist.shard_range(len(files), args.rank, args.nshard)
+    print("Total tracks: {} | Start : End = {} : {}".format(len(files), lo, hi))
+    saved = err = 0
+    todo = []
+    for f in files[lo:hi]:
+        fname = f.split("/")[-2] + "/" + os.path.basename(f)[:-len(".npy")]
+        out = os.path.join(res_dir, fname.replace("/", "__") + ".pkl")
+        if os.path.exists(out):                      # resume: skip-if-exists, as extract_gestsync_feats
+            saved += 1
+            continue
+        try:
+            feats = np.load(f)
+            if feats.ndim != 2 or feats.shape[1] != 1024 or feats.shape[0] < 1:
+                raise ValueError("expected a (T,1024) feature .npy, got {}".format(feats.shape))
+            todo.append((np.ascontiguousarray(feats, np.float32), fname, out))
+        except Exception as e:
+            err += 1
+            print("Error: ", e, " | Feature file: ", f)
+
+    def run_group(group):
+        embs = jegal.forward_gesture_tracks([torch.from_numpy(ft) for ft, _, _ in group], win=args.win, ctx=args.ctx, normalize=True)
+        return [e.cpu().numpy() for e in embs]
+
+    cap = max(1, args.rows_per_call)
+    s0 = 0
+    while s0 < len(todo):
+        s1, rows = s0 + 1, todo[s0][0].shape[0]
+        while s1 < len(todo) and rows + todo[s1][0].shape[0] <= cap:
+            rows += todo[s1][0].shape[0]
+            s1 += 1
+        group = todo[s0:s1]
+        s0 = s1
+        try:
+            embs = run_group(group)
+        except Exception as e:                       # one bad track must not take its neighbours down: retry the group track by track
+            if len(group) == 1:
+                err += 1
+                print("Error: ", e, " | Track: ", group[0][1])
+                continue
+            embs = []
+            for item in group:
+                try:
+                    embs.append(run_group([item])[0])
+                except Exception as e1:
+                    embs.append(None)
+                    err += 1
+                    print("Error: ", e1, " | Track: ", item[1])
+        for emb, (_, fname, out) in zip(embs, group):
+            if emb is None:
+                continue
+            try:
+                with open(out, "wb") as f:
+                    pickle.dump({"gesture_emb": emb, "content_emb": None, "info": {"fname": fname, "win": args.win, "ctx": args.ctx}}, f)
+                saved += 1
+            except Exception as e:
+                err += 1
+                print("Error: ", e, " | Track: ", fname)
+    print("No of files saved = {} | Err = {}".format(saved, err))
+    print("Saved JEGAL gesture embeddings at: ", res_dir)
+    return 0
+
+
 COMMANDS = {
+    "embed_tracks": cmd_embed_tracks,
     "sync_offset": cmd_sync_offset,
     "attn_matrix": cmd_attn_matrix,
     "retrieve": cmd_retrieve,

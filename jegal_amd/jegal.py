@@ -107,6 +107,27 @@ class JEGAL:
         m = None if x_mask is None else x_mask.reshape(x.shape[0], x.shape[1])
         return self.engine.jegal_gestures(x, m, align=False)
 
+    def forward_gesture_tracks(self, tracks, win=120, ctx=50, normalize=False):
+        """Gesture embeddings of tracks of ANY length (not in the reference, which fails beyond the 500 rows of its positional table):
+        tracks = a list of (T_i, 1024) GestSync feature tensors -> a list of (T_i, 512) tensors, what forward_inference(visual_feats=...)
+        returns for a clip (forward_gestures + proj_op_align_gesture), unit rows with normalize=True.  A track is encoded in windows of
+        `win` emitted frames that see `ctx` frames of context on both sides (Engine.jegal_gesture_tracks, include/jegal_hip.h); a track of
+        at most `win` frames is one window and gets exactly its forward_inference rows.
+        The defaults make spans of at most 220 frames, the longest clip in the reference's dataset lists (dataset/avs_*.csv) and so the
+        longest sequence the model saw in training: a choice from the dataset's lengths, not a measured optimum -- no trained
+        checkpoint is available to measure one."""
+        self._check()
+        tracks = [torch.as_tensor(t) for t in tracks]
+        for t in tracks:
+            if t.dim() != 2 or t.shape[1] != 1024:
+                raise ValueError(f"every track must be (T, 1024), got {tuple(t.shape)}")
+        lengths = [int(t.shape[0]) for t in tracks]
+        if sum(lengths) == 0:
+            return [torch.empty((0, 512), dtype=torch.float32, device=self.engine.device) for _ in tracks]
+        feats = torch.cat([self.engine._f32(t) for t in tracks if t.shape[0]])
+        out = self.engine.jegal_gesture_tracks(feats, lengths, win=win, ctx=ctx, align=True, normalize=normalize)
+        return list(torch.split(out, lengths))
+
     def forward_text(self, x, x_mask=None):
         self._check()
         m = None if x_mask is None else x_mask.reshape(x.shape[0], x.shape[1])
