@@ -405,7 +405,9 @@ int jg_audio_len(int Tm);
  * NULL = jg_jegal_audio. */
 int jg_jegal_audio_ragged(jg_handle* h, const float* mel, int B, int Tm, const int32_t* valid_tm_host, float* out);
 /* wav2filterbanks (utils/audio_utils.py:28-66): wav (B,n_samples) fp32 (int16 scale, NOT normalised: audio_utils.py:20-25),
- * mel_basis (80,257) fp32 = librosa.filters.mel(sr=16000,n_fft=512,n_mels=80,fmin=0,fmax=8000) -> out (B, n_samples/160, 80) log-mel. */
+ * mel_basis (80,257) fp32 = librosa.filters.mel(sr=16000,n_fft=512,n_mels=80,fmin=0,fmax=8000) -> out (B, n_samples/160, 80) log-mel.
+ * n_samples >= 257: the STFT reflects 256 samples at either end, which is undefined for a shorter signal (torch.stft raises);
+ * fewer samples, or B <= 0, is JG_ERR_ARG and nothing is enqueued. */
 int jg_logmel(jg_handle* h, const float* wav, int B, int n_samples, const float* mel_basis, float* out);
 /* forward_text (jegal.py:95-103): states (B,L,768) fp32 (XLM-R last_hidden_state), mask (B,L) -> (B,L,256). */
 int jg_jegal_text(jg_handle* h, const float* states, const float* mask, int B, int L, float* out);

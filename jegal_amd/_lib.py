@@ -249,6 +249,11 @@ def _ptr(t):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
+def _shape(x):
+    """The shape of a tensor, an array or nested lists, without moving anything."""
+    return tuple(x.shape) if hasattr(x, "shape") else np.shape(x)
+
+
 class Engine:
     """One jg_handle on one GPU.  Not thread-safe; one per process/GPU."""
 
@@ -788,7 +793,12 @@ class Engine:
         return dst
 
     def logmel(self, wav, mel_basis):
-        """wav (B,n) fp32 (int16 scale) -> log-mel (B, n//160, 80)."""
+        """wav (B,n) fp32 (int16 scale), n >= 257 -> log-mel (B, n//160, 80)."""
+        ws, ms = _shape(wav), _shape(mel_basis)
+        if len(ws) != 2 or ws[0] < 1 or ms != (80, 257):
+            raise ValueError("wav must be (B, n) with B >= 1, mel_basis (80, 257)")
+        if ws[1] < 257:
+            raise ValueError("reflect padding needs more than 256 samples")
         self._bind_stream()
         wav = self._f32(wav)
         mb = self._f32(mel_basis)
@@ -864,7 +874,30 @@ class Engine:
         return out
 
     # ---- metrics
+    @staticmethod
+    def _check_row_offsets(offsets, rows, n=None):
+        """Row offsets of the ragged entries -> number of blocks.  What needs no sync is checked: the count (n + 1 entries when the caller
+        knows n), and for a host array that it is a non-decreasing partition inside 0 .. rows; a tensor's values stay on the device."""
+        if isinstance(offsets, torch.Tensor):
+            if offsets.ndim != 1 or offsets.numel() < 1 or offsets.dtype not in (torch.int32, torch.int64):
+                raise ValueError("offsets must be a 1-d integer tensor of blocks + 1 entries")
+            count = offsets.numel()
+        else:
+            off = np.asarray(offsets)
+            if off.ndim != 1 or off.size < 1 or not np.issubdtype(off.dtype, np.integer):
+                raise ValueError("offsets must be a 1-d integer array of blocks + 1 entries")
+            if off[0] < 0 or off[-1] > rows or np.any(np.diff(off.astype(np.int64)) < 0):
+                raise ValueError("offsets must be non-decreasing and lie inside 0 .. rows")
+            count = off.size
+        if n is not None and count != n + 1:
+            raise ValueError(f"offsets need {n + 1} entries (blocks + 1), not {count}")
+        return count - 1
+
     def pool_mean(self, x, offsets):
+        xs = _shape(x)
+        if len(xs) != 2 or xs[1] < 1:
+            raise ValueError("x must be (rows, D)")
+        self._check_row_offsets(offsets, xs[0])
         self._bind_stream()
         x = self._f32(x)
         off = self._i32(offsets)
@@ -874,6 +907,12 @@ class Engine:
         return out
 
     def sim_rank(self, e1, e2, row_offset=0):
+        s1, s2 = _shape(e1), _shape(e2)
+        if len(s1) != 2 or len(s2) != 2 or s1[1] != s2[1] or s1[1] <= 0 or s1[1] % 64:
+            raise ValueError("e1 / e2 must be (rows, D) with the same D, a positive multiple of 64")
+        row_offset = int(row_offset)
+        if row_offset < 0 or row_offset + s1[0] > s2[0]:
+            raise ValueError("row_offset must be >= 0 and row_offset + rows of e1 <= rows of e2")
         self._bind_stream()
         e1, e2 = self._f32(e1), self._f32(e2)
         n_local, D = e1.shape
@@ -1052,6 +1091,10 @@ class Engine:
         return offset, conf, curve
 
     def asd(self, query, cand, c_offsets, temp=0.07):
+        qs, cs = _shape(query), _shape(cand)
+        if len(qs) != 2 or len(cs) != 2 or qs[1] != cs[1] or qs[1] < 1:
+            raise ValueError("query / cand must be (rows, D) with the same D")
+        self._check_row_offsets(c_offsets, cs[0], qs[0])
         self._bind_stream()
         q, c = self._f32(query), self._f32(cand)
         co = self._i32(c_offsets)

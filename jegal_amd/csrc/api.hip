@@ -453,7 +453,8 @@ int jg_mask_resize_packed(jg_handle* h, const uint8_t* packed, int64_t packed_by
 
 int jg_logmel(jg_handle* h, const float* wav, int B, int n_samples, const float* mel_basis, float* out) {
     ENTER(h);
-    if (!wav || !mel_basis || !out || B <= 0 || n_samples < 160) JG_FAIL(h, JG_ERR_ARG, "bad logmel arguments");
+    if (!wav || !mel_basis || !out || B <= 0) JG_FAIL(h, JG_ERR_ARG, "bad logmel arguments");
+    if (n_samples < 257) JG_FAIL(h, JG_ERR_ARG, "reflect padding needs more than 256 samples");
     return timed(h, JG_ST_MISC, [&] { return launch_logmel(wav, B, n_samples, mel_basis, out, h->stream); });
 }
 

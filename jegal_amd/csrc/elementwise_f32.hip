@@ -209,7 +209,8 @@ hipError_t launch_ragged_mean(const float* x, const int32_t* offsets, int n, int
 // 512 window, center=True / reflect padding, onesided) -> drop the last frame -> |X| -> mel_basis (80x257) ->
 // log(. + 1e-20).  One block per frame: the windowed 512-sample segment and a 512-entry twiddle table live in
 // LDS, thread f computes bin f (and f+256) by direct DFT in fp32 (316 MFLOP per 150-frame clip: not worth an FFT),
-// then threads 0..79 do the mel dot products.
+// then threads 0..79 do the mel dot products.  n_samples >= 257 (jg_logmel refuses less): one reflection at either end then lands inside
+// the signal, as torch.stft demands; the clamp below is never reached.
 __global__ __launch_bounds__(256) void logmel_kernel(const float* __restrict__ wav, int n_samples, int n_frames,
                                                      const float* __restrict__ mel_basis, float* __restrict__ out) {
     __shared__ float seg[512];
