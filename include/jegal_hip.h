@@ -249,6 +249,26 @@ int jg_debug_weight_form(int precision, int kind, int model, int keep32, int* fo
 /* ... and whether a GEMM on a layer of that form takes the lo operand: uncalibrated as above, calibrating: a calibration pass is in
  * progress, clip_bias: the call takes the per-clip bias (a run-time corrected layer runs hi+lo in every call that cannot). */
 int jg_debug_gemm_runs_lo(int form, int uncalibrated, int calibrating, int clip_bias, int* lo);
+/* The weight packing on caller arrays (jegal_amd/csrc/weight_pack.h: the functions every finalize runs before it uploads), without a
+ * handle or a device.  16-bit values are uint16_t bit patterns.  JG_ERR_ARG for bad arguments, and then nothing is written.
+ * Conv layer: w [O][I][KT][KH][KW], bias [O] and an optional eval BatchNorm (all four of bn_* or none) -> matrix [N][K] fp32 with
+ *   k = t slot + kt I + c (t: the tap's place in the layer's order, by parity class with reorder when KH KW <= 32) and shift [N];
+ *   N = max(O, Opad) and K = kpad > 0 ? kpad : KH KW slot must be passed as such; KT I <= slot, KH KW slot <= K. */
+int jg_debug_pack_conv(const float* w, const float* bias, const float* bn_gamma, const float* bn_beta, const float* bn_mean, const float* bn_var, int O,
+                       int I, int KT, int KH, int KW, int slot, int kpad, int Opad, int SH, int SW, int reorder, int N, int K, float* matrix, float* shift);
+/* A layer's matrix w [N][K] and bias [N] packed under a rounding rule given as plain values: bf16 (single bf16 weights), form (as
+ *   jg_debug_weight_form), keep_lo, diffuse_group (>= 0; error diffusion along k = tap group + slot where it applies).  ln_gamma / ln_beta [K]
+ *   (both or neither): the layer is packed as the consumer of that LayerNorm, W diag(gamma) with b + W beta, and c1h / c1f [N] receive
+ *   the column sums of the packed weights; add_beta [N] (optional): the producer's b + beta.  hi [N][K], bias_out [N]; lo [N][K] if and
+ *   only if keep_lo; c1h / c1f if and only if ln_gamma; w32 [N][K] / b32 [N] (the fp32 matrix and bias as packed) if and only if device32
+ *   or form 2, which keep them. */
+int jg_debug_pack_round(const float* w, const float* bias, int N, int K, int bf16, int form, int keep_lo, int diffuse_group, const float* ln_gamma,
+                        const float* ln_beta, const float* add_beta, int device32, uint16_t* hi, uint16_t* lo, float* bias_out, float* c1h, float* c1f,
+                        float* w32, float* b32);
+/* conv1's slot-major panel for the direct kernel from the packed matrix hi [64][784] and shift [64] -> panel [49][64][16]. */
+int jg_debug_conv1_panel(const uint16_t* hi, const float* shift, uint16_t* panel);
+/* The bias of a bias-corrected layer after a calibration: w32 [N][K], b32 [N], mu [K] = column sums of the input over `rows` rows -> bias [N]. */
+int jg_debug_bias_correction(const float* w32, const float* b32, const float* mu, int64_t rows, int N, int K, float* bias);
 /* Implicit-GEMM convolution (launch_gemm with conv = true; tests/test_gpu_conv_fp64.py): ONE conv launch on caller operands, the geometry
  * built by the function production uses (engine::geom), M = nimg * OH * OW output pixels.
  *   out[(img, oh, ow)][n] = relu?( sum_{t, c} in[img][oh SH - PH + kh_t][ow SW - PW + kw_t][c] (Wh + Wl)[n][t C + c] * scale[n] + bias[n] )

@@ -74,6 +74,10 @@ _SIGS = {
                            ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I)],
     "jg_debug_weight_form": [_I, _I, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I)],
     "jg_debug_gemm_runs_lo": [_I, _I, _I, _I, ctypes.POINTER(_I)],
+    "jg_debug_pack_conv": [_P] * 6 + [_I] * 13 + [_P, _P],
+    "jg_debug_pack_round": [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I] + [_P] * 7,
+    "jg_debug_conv1_panel": [_P, _P, _P],
+    "jg_debug_bias_correction": [_P, _P, _P, _L, _I, _I, _P],
     "jg_debug_gemm32": [_P, _P, _L, _P, _L, _I, _I, _I, _P, _P, _P, _L, _I, _I, _P, _L],
     "jg_debug_gemm_x3": [_P, _P, _L, _P, _P, _L, _I, _I, _I, _P, _P, _L, _I, _I, _P, _L],
     "jg_debug_attention": [_P, _P, _P, _I, _I, _I, _I, _P],
@@ -211,6 +215,71 @@ def gemm_runs_lo(form, uncalibrated=False, calibrating=False, clip_bias=False):
     if rc != 0:
         raise JegalError(f"jg_debug_gemm_runs_lo: bad arguments ({rc})", rc)
     return bool(lo.value)
+
+
+def _host(a, dtype):
+    """a host array of `dtype`, C-contiguous, or None -> (array kept alive by the caller, pointer or None)"""
+    if a is None:
+        return None, None
+    a = np.ascontiguousarray(a, dtype=dtype)
+    return a, a.ctypes.data
+
+
+def pack_conv(w, bias, bn=None, *, slot, kpad=0, Opad=0, stride=(1, 1), reorder=False):
+    """A conv layer's folded matrix and shift (jg_debug_pack_conv): w (O, I, KT, KH, KW) fp32, bias (O,), bn = (gamma, beta, mean, var) or
+    None -> (matrix (N, K) fp32, shift (N,)).  Needs no Engine and no GPU."""
+    w = np.ascontiguousarray(w, np.float32)
+    O, I, KT, KH, KW = w.shape
+    N, K = max(O, Opad), kpad if kpad > 0 else KH * KW * slot
+    keep = [_host(x, np.float32) for x in (bias,) + (tuple(bn) if bn is not None else (None,) * 4)]
+    matrix, shift = np.empty((N, K), np.float32), np.empty(N, np.float32)
+    rc = load_library().jg_debug_pack_conv(w.ctypes.data, *[p for _, p in keep], O, I, KT, KH, KW, int(slot), int(kpad), int(Opad), int(stride[0]),
+                                           int(stride[1]), int(bool(reorder)), N, K, matrix.ctypes.data, shift.ctypes.data)
+    if rc != 0:
+        raise JegalError(f"jg_debug_pack_conv: bad arguments ({rc})", rc)
+    return matrix, shift
+
+
+def pack_round(w, bias, *, bf16=False, form="single", keep_lo=False, diffuse_group=0, ln=None, add_beta=None, device32=False):
+    """A layer packed under a rounding rule (jg_debug_pack_round): w (N, K) fp32, bias (N,); ln = (gamma, beta) packs it as that LayerNorm's
+    consumer, add_beta as a producer -> dict of hi / lo (uint16 bit patterns; lo None unless keep_lo), bias, c1h / c1f (None without ln),
+    w32 / b32 (None unless device32 or the form keeps them).  Needs no Engine and no GPU."""
+    w = np.ascontiguousarray(w, np.float32)
+    N, K = w.shape
+    keep = [_host(x, np.float32) for x in (bias,) + (tuple(ln) if ln is not None else (None, None)) + (add_beta,)]
+    keeps32 = bool(device32) or form == "bias_corrected"
+    out = dict(hi=np.empty((N, K), np.uint16), lo=np.empty((N, K), np.uint16) if keep_lo else None, bias=np.empty(N, np.float32),
+               c1h=np.empty(N, np.float32) if ln is not None else None, c1f=np.empty(N, np.float32) if ln is not None else None,
+               w32=np.empty((N, K), np.float32) if keeps32 else None, b32=np.empty(N, np.float32) if keeps32 else None)
+    rc = load_library().jg_debug_pack_round(w.ctypes.data, keep[0][1], N, K, int(bool(bf16)), WEIGHT_FORMS.index(form), int(bool(keep_lo)),
+                                            int(diffuse_group), keep[1][1], keep[2][1], keep[3][1], int(bool(device32)),
+                                            *[v.ctypes.data if v is not None else None for v in out.values()])
+    if rc != 0:
+        raise JegalError(f"jg_debug_pack_round: bad arguments ({rc})", rc)
+    return out
+
+
+def conv1_panel(hi, shift):
+    """conv1's slot-major panel for the direct kernel (jg_debug_conv1_panel): hi (64, 784) uint16 bit patterns, shift (64,) -> (49, 64, 16) uint16."""
+    hi, shift = np.ascontiguousarray(hi, np.uint16), np.ascontiguousarray(shift, np.float32)
+    if hi.shape != (64, 784) or shift.shape != (64,):
+        raise ValueError("conv1_panel: hi (64, 784), shift (64,)")
+    panel = np.empty((49, 64, 16), np.uint16)
+    rc = load_library().jg_debug_conv1_panel(hi.ctypes.data, shift.ctypes.data, panel.ctypes.data)
+    if rc != 0:
+        raise JegalError(f"jg_debug_conv1_panel: bad arguments ({rc})", rc)
+    return panel
+
+
+def bias_correction(w32, b32, mu, rows):
+    """The calibrated bias of a bias-corrected layer (jg_debug_bias_correction): w32 (N, K), b32 (N,), mu (K,) column sums over `rows` rows."""
+    w32, b32, mu = (np.ascontiguousarray(x, np.float32) for x in (w32, b32, mu))
+    N, K = w32.shape
+    bias = np.empty(N, np.float32)
+    rc = load_library().jg_debug_bias_correction(w32.ctypes.data, b32.ctypes.data, mu.ctypes.data, int(rows), N, K, bias.ctypes.data)
+    if rc != 0:
+        raise JegalError(f"jg_debug_bias_correction: bad arguments ({rc})", rc)
+    return bias
 
 
 class JegalError(RuntimeError):

@@ -320,6 +320,65 @@ int jg_debug_gemm_runs_lo(int form, int uncalibrated, int calibrating, int clip_
     return JG_OK;
 }
 
+// ---- the weight packing on caller arrays (weight_pack.h): no handle, no device; nothing is written unless every argument is good
+int jg_debug_pack_conv(const float* w, const float* bias, const float* bn_gamma, const float* bn_beta, const float* bn_mean, const float* bn_var, int O,
+                       int I, int KT, int KH, int KW, int slot, int kpad, int Opad, int SH, int SW, int reorder, int N, int K, float* matrix, float* shift) {
+    const bool bn = bn_gamma || bn_beta || bn_mean || bn_var;
+    if (!w || !bias || (bn && !(bn_gamma && bn_beta && bn_mean && bn_var)) || !matrix || !shift) return JG_ERR_ARG;
+    if (O <= 0 || I <= 0 || KT <= 0 || KH <= 0 || KW <= 0 || slot <= 0 || kpad < 0 || Opad < 0 || SH <= 0 || SW <= 0) return JG_ERR_ARG;
+    if ((long)KH * KW > 4096 || (long)KT * I > slot || (long)KH * KW * slot > (1L << 24)) return JG_ERR_ARG;
+    const ConvPack c = {O, I, KT, KH, KW, slot, kpad, Opad, SH, SW, reorder != 0};
+    if (N != conv_pack_N(c) || K != conv_pack_K(c) || KH * KW * slot > K) return JG_ERR_ARG;
+    std::vector<float> s(O, 1.f), sh(bias, bias + O);
+    if (bn) bn_fold(bias, bn_gamma, bn_beta, bn_mean, bn_var, O, s.data(), sh.data());
+    sh.resize(N, 0.f);
+    const std::vector<float> p = conv_matrix(w, s.data(), c);
+    std::memcpy(matrix, p.data(), p.size() * sizeof(float));
+    std::memcpy(shift, sh.data(), sh.size() * sizeof(float));
+    return JG_OK;
+}
+
+int jg_debug_pack_round(const float* w, const float* bias, int N, int K, int bf16, int form, int keep_lo, int diffuse_group, const float* ln_gamma,
+                        const float* ln_beta, const float* add_beta, int device32, uint16_t* hi, uint16_t* lo, float* bias_out, float* c1h, float* c1f,
+                        float* w32, float* b32) {
+    const bool consumer = ln_gamma || ln_beta;
+    if (!w || !bias || N <= 0 || K <= 0 || form < WF_SINGLE || form > WF_RUNTIME_CORRECTED || diffuse_group < 0 || !hi || !bias_out) return JG_ERR_ARG;
+    if ((keep_lo != 0) != (lo != nullptr) || (consumer && !(ln_gamma && ln_beta)) || consumer != (c1h != nullptr) || consumer != (c1f != nullptr))
+        return JG_ERR_ARG;
+    const bool keeps32 = device32 != 0 || form == WF_BIAS_CORRECTED;
+    if (keeps32 != (w32 != nullptr) || keeps32 != (b32 != nullptr)) return JG_ERR_ARG;
+    std::vector<float> wv(w, w + (size_t)N * K), bv(bias, bias + N);
+    if (consumer) fold_ln_consumer(wv.data(), bv.data(), N, K, ln_gamma, ln_beta);
+    if (add_beta) fold_ln_producer(bv.data(), N, add_beta);
+    const RoundRule rule = {bf16 != 0, (WeightForm)form, keep_lo != 0, diffuse_group};
+    const PackedLayer p = pack_layer(wv.data(), bv.data(), N, K, rule, false, consumer, device32 != 0);
+    std::memcpy(hi, p.hi.data(), p.hi.size() * 2);
+    if (lo) std::memcpy(lo, p.lo.data(), p.lo.size() * 2);
+    std::memcpy(bias_out, p.bias.data(), (size_t)N * sizeof(float));
+    if (consumer) {
+        std::memcpy(c1h, p.c1h.data(), (size_t)N * sizeof(float));
+        std::memcpy(c1f, p.c1f.data(), (size_t)N * sizeof(float));
+    }
+    if (keeps32) {
+        std::memcpy(w32, p.w32.data(), p.w32.size() * sizeof(float));
+        std::memcpy(b32, p.b32.data(), (size_t)N * sizeof(float));
+    }
+    return JG_OK;
+}
+
+int jg_debug_conv1_panel(const uint16_t* hi, const float* shift, uint16_t* panel) {
+    if (!hi || !shift || !panel) return JG_ERR_ARG;
+    const std::vector<uint16_t> wd = conv1_direct_panel(hi, shift);
+    std::memcpy(panel, wd.data(), wd.size() * 2);
+    return JG_OK;
+}
+
+int jg_debug_bias_correction(const float* w32, const float* b32, const float* mu, int64_t rows, int N, int K, float* bias) {
+    if (!w32 || !b32 || !mu || rows <= 0 || N <= 0 || K <= 0 || !bias) return JG_ERR_ARG;
+    bias_correction(w32, b32, mu, (long)rows, N, K, bias);
+    return JG_OK;
+}
+
 int jg_debug_gemm32(jg_handle* h, const float* A, int64_t lda, const float* W, int64_t ldw, int M, int N, int K, const float* scale,
                     const float* bias, const float* res, int64_t ldr, int res_mod, int act, float* out, int64_t ldc) {
     ENTER(h);

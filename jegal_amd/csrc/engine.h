@@ -6,7 +6,7 @@
 #include "common.h"
 #undef JG_BF16
 #include "gemm_plan.h"
-#include "weight_form.h"
+#include "weight_pack.h"      // (and weight_form.h)
 #include "../../include/jegal_hip.h"
 #include "audit32.h"
 #include "gemm_x3.h"
@@ -220,7 +220,7 @@ struct jg_handle {
     // round 6: the two ends of the JEGAL gesture branch -- proj_ip_rgb and final norm + proj_op_rgb + the align MLP, five
     // small GEMMs that carry two thirds of the branch's fp16 error -- run on the fp32 kernel in the fp16 contract modes
     bool jegal_fp32_ends = true;
-    bool conv_round_diffuse = true;      // conv weights rounded with per-channel error diffusion across the taps (pack_matrix)
+    bool conv_round_diffuse = true;      // conv weights rounded with per-channel error diffusion across the taps (round_matrix, weight_pack.h)
     bool audit_weights = false;
     int audit_stages = 0;
     // diagnosis inside the fp16 JEGAL gesture branch (option "audit_jegal_parts", needs audit_weights): 1 input projection, 2 attention
@@ -307,6 +307,13 @@ template <class T>
 int upload(jg_handle* h, Model& m, const std::vector<T>& v, T** out) {
     RET(walloc<T>(h, m, v.size(), out));
     HIPCHK(h, hipMemcpy(*out, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    return JG_OK;
+}
+
+// 16-bit values as the packing leaves them (weight_pack.h: bit containers) -> device operands of the handle's 16-bit type
+inline int upload(jg_handle* h, Model& m, const std::vector<uint16_t>& bits, f16** out) {
+    RET(walloc<f16>(h, m, bits.size(), out));
+    HIPCHK(h, hipMemcpy(*out, bits.data(), bits.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
     return JG_OK;
 }
 
@@ -469,13 +476,19 @@ int post_norm_layer(jg_handle* h, Arith<T> ar, const EncLayer& L, float* x32, T*
 // (layer kinds LK_* and the form each gets under the handle's mode: weight_form.h)
 const HostTensor* find(jg_handle* h, const std::string& name);
 int need(jg_handle* h, const std::string& name, int64_t numel, const HostTensor** out);
+// the one upload step of a packed layer (weight_pack.h): allocations, copies, the Lin, the calibration record
+int upload_layer(jg_handle* h, Model& m, PackedLayer&& p, Lin* L);
 int pack_matrix(jg_handle* h, Model& m, const std::vector<float>& w, const std::vector<float>& bias, int N, int K, int kind, Lin* L,
-                bool ln_consumer = false, bool keep32 = false, int diffuse_group = 0);
+                bool ln_consumer = false, bool keep32 = false);
 int make_linear(jg_handle* h, Model& m, const std::string& wname, const std::string& bname, int N, int K, Lin* L, int kind = LK_GESTURE, bool keep32 = false);
 int make_ln(jg_handle* h, Model& m, const std::string& wname, const std::string& bname, int D, LNp* p);
 // Opad > O: output channels O .. Opad - 1 are added with zero weights and zero shift (relu(0) = 0 for whoever reads them)
 int make_conv(jg_handle* h, Model& m, const std::string& conv, const std::string& bn, int O, int I, int KT, int KH, int KW,
               int slot, int kpad, Lin* L, int SH = 1, int SW = 1, bool reorder = false, int Opad = 0, int kind = LK_CONV);
+// the two halves of make_conv for whoever needs the host result: the folded fp32 matrix and shift alone (GestSync's audio conv1), and
+// the packed layer before its upload (GestSync's conv1: the direct kernel's panel is built from it)
+int fold_conv(jg_handle* h, const std::string& conv, const std::string& bn, const ConvPack& c, std::vector<float>* p, std::vector<float>* shift);
+int pack_conv(jg_handle* h, int model_id, const std::string& conv, const std::string& bn, const ConvPack& c, int kind, PackedLayer* out);
 int make_annotated_layer(jg_handle* h, Model& m, const std::string& p, int D, int Dff, EncLayer* L, int kind);
 int calibrate_gesture(jg_handle* h, const void* frames, int dtype, int B, int T, int models);
 int calibrate_xlmr(jg_handle* h, const int32_t* ids_dev, const int32_t* mask_dev, int B, int L);

@@ -49,7 +49,12 @@ int finalize_gestsync(jg_handle* h) {
     drop_model(h, h->gs);
     GestSyncModel& gs = h->gs;
     Model& m = gs.m;
-    RET(make_conv(h, m, "net_vid.conv1", "net_vid.bn1", 64, 3, 5, 7, 7, 16, 0, &gs.c1));
+    PackedLayer c1;
+    RET(pack_conv(h, m.id, "net_vid.conv1", "net_vid.bn1", {64, 3, 5, 7, 7, 16, 0, 0, 1, 1, false}, LK_CONV, &c1));
+    static_assert(CONV1_PANEL_O == 64 && CONV1_PANEL_K == 7 * 7 * 16, "the direct kernel's panel is conv1 as packed here");
+    std::vector<uint16_t> c1_direct;          // conv1_direct_kernel's slot-major panel (fp16 build only), from the host result
+    if (!h->bf16) c1_direct = conv1_direct_panel(c1.hi.data(), c1.bias.data());
+    RET(upload_layer(h, m, std::move(c1), &gs.c1));
     // conv2..conv5: taps grouped by stride parity class (ConvGeom::taps); gs_conv_geoms builds the same geometry
     RET(make_conv(h, m, "net_vid.conv2", "net_vid.bn2", 128, 64, 1, 5, 5, 64, 0, &gs.c2, 2, 2, true));
     RET(make_conv(h, m, "net_vid.conv3", "net_vid.bn3", 256, 128, 1, 3, 3, 128, 0, &gs.c3, 2, 2, true));
@@ -57,24 +62,7 @@ int finalize_gestsync(jg_handle* h) {
     RET(make_conv(h, m, "net_vid.conv5", "net_vid.bn5", 256, 256, 1, 3, 3, 256, 0, &gs.c5, 1, 1, true));
     RET(make_conv(h, m, "net_vid.fc6", "net_vid.bn6", 512, 256, 1, 4, 4, 256, 0, &gs.fc6));
     RET(upload(h, m, std::vector<float>(64, 1.0f / 255.0f), &gs.c1_scale255));
-    if (!h->bf16) {   // slot-major copy of the packed conv1 panel for conv1_direct_kernel: Wd[s][o][e] = W[o][s*16+e]
-        std::vector<f16> hostw((size_t)64 * 784), wd((size_t)49 * 64 * 16);
-        HIPCHK(h, hipMemcpy(hostw.data(), gs.c1.wh, hostw.size() * sizeof(f16), hipMemcpyDeviceToHost));
-        for (int s = 0; s < 49; ++s)
-            for (int o = 0; o < 64; ++o)
-                for (int e = 0; e < 16; ++e) wd[conv1_wd_index(s, o, e)] = hostw[(size_t)o * 784 + s * 16 + e];
-        // bias lane: the kernel sets element CONV1_BIAS_LANE of every pixel slot to "1.0" = CONV1_BIAS_ONE; shift*255 (times the power
-        // of two CONV1_BIAS_PAIR_SCALE that makes the product shift*255 * 2^-24, shared.h) as hi+lo fp16 pair
-        std::vector<float> shift(64);
-        HIPCHK(h, hipMemcpy(shift.data(), gs.c1.bias, 64 * sizeof(float), hipMemcpyDeviceToHost));
-        for (int o = 0; o < 64; ++o) {
-            const float v = shift[o] * 255.0f * CONV1_BIAS_PAIR_SCALE;
-            const f16 hi = (f16)v;
-            wd[conv1_wd_index(0, o, CONV1_BIAS_LANE)] = hi;
-            wd[conv1_wd_index(1, o, CONV1_BIAS_LANE)] = (f16)(v - (float)hi);
-        }
-        RET(upload(h, m, wd, &gs.c1_direct));
-    }
+    if (!h->bf16) RET(upload(h, m, c1_direct, &gs.c1_direct));
     RET(make_linear(h, m, "ff_vid.0.weight", "ff_vid.0.bias", 512, 512, &gs.ff0));
     RET(make_linear(h, m, "ff_vid.2.weight", "ff_vid.2.bias", 1024, 512, &gs.ff2));
     const HostTensor* pe;

@@ -14,19 +14,8 @@ int finalize_gestsync_audio(jg_handle* h) {
     GestSyncAudioModel& a = h->gsa;
     Model& m = a.m;
     {
-        const HostTensor *w, *b, *g, *be, *mu, *var;
-        RET(need(h, "net_aud.conv1.weight", 64 * 9, &w));
-        RET(need(h, "net_aud.conv1.bias", 64, &b));
-        RET(need(h, "net_aud.bn1.weight", 64, &g));
-        RET(need(h, "net_aud.bn1.bias", 64, &be));
-        RET(need(h, "net_aud.bn1.running_mean", 64, &mu));
-        RET(need(h, "net_aud.bn1.running_var", 64, &var));
-        std::vector<float> wf(64 * 9), shift(64);
-        for (int o = 0; o < 64; ++o) {
-            const float s = g->v[o] / std::sqrt(var->v[o] + 1e-5f);          // as make_conv folds
-            for (int k = 0; k < 9; ++k) wf[o * 9 + k] = w->v[o * 9 + k] * s;
-            shift[o] = (b->v[o] - mu->v[o]) * s + be->v[o];
-        }
+        std::vector<float> wf, shift;         // make_conv's fold and layout with I = 1, slot = 1: [64][9] in natural tap order
+        RET(fold_conv(h, "net_aud.conv1", "net_aud.bn1", {64, 1, 1, 3, 3, 1, 0, 0, 1, 1, false}, &wf, &shift));
         RET(upload(h, m, wf, &a.c1w));
         RET(upload(h, m, shift, &a.c1shift));
     }

@@ -3,14 +3,6 @@
 
 namespace engine {
 
-// fp32 -> bf16 bits, round to nearest even (host side of the weight packing)
-inline uint16_t bf16_bits(float v) {
-    uint32_t u;
-    std::memcpy(&u, &v, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);
-    return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
-
 const HostTensor* find(jg_handle* h, const std::string& name) {
     auto it = h->host.find(name);
     if (it == h->host.end()) return nullptr;
@@ -26,91 +18,49 @@ int need(jg_handle* h, const std::string& name, int64_t numel, const HostTensor*
     return JG_OK;
 }
 
-// [N][K] fp32 -> device fp16 hi (+lo), allocated into model `m`
-// keep32: the layer also runs on the fp32 kernel in the fp16 modes (the two ends of the JEGAL gesture branch, option jegal_fp32_ends)
-// diffuse_group > 0 (conv layers, option conv_round_diffuse): fp16 rounding with ERROR DIFFUSION along the taps of one (output channel,
-// input slot) pair -- k = tap * diffuse_group + slot -- instead of round-to-nearest per weight: the residuals w - fp16(w) of a
-// channel's taps then sum to less than half an ulp, so the part of the weight-rounding error that is the same for every output pixel,
-// sum_k (w - fp16(w))[k] E[x_k] = sum_slot E[x_slot] sum_taps (w - fp16(w)), vanishes wherever the input statistics do not depend on the
-// tap (everywhere but at the image border); the price is a per-weight residual of up to one ulp instead of half an ulp in the part
-// that averages out over pixels.  No calibration, no run-time cost (measured with tools/precision_floor.py).
-int pack_matrix(jg_handle* h, Model& m, const std::vector<float>& w, const std::vector<float>& bias, int N, int K, int kind, Lin* L, bool ln_consumer,
-                bool keep32, int diffuse_group) {
-    const WeightForm form = weight_form(h->precision, kind, m.id);
-    const bool want_lo = lo_kept(form, keep32);
-    std::vector<f16> hi((size_t)N * K), lo;
-    if (want_lo) lo.resize((size_t)N * K);
-    if (h->bf16) {                       // JG_PREC_BF16: single bf16 weights (the 16-bit container is re-typed by the bf16 build)
-        for (size_t i = 0; i < hi.size(); ++i) {
-            const uint16_t b = bf16_bits(w[i]);
-            std::memcpy(&hi[i], &b, 2);
-        }
-    } else if (diffuse_group > 0 && K % diffuse_group == 0 && form == WF_SINGLE) {
-        const int taps = K / diffuse_group;
-        for (int n = 0; n < N; ++n)
-            for (int sl = 0; sl < diffuse_group; ++sl) {
-                double carry = 0.0;
-                for (int t = 0; t < taps; ++t) {
-                    const size_t i = (size_t)n * K + (size_t)t * diffuse_group + sl;
-                    if (w[i] == 0.f) { hi[i] = (f16)0.f; continue; }        // padding slots stay exactly zero
-                    const double v = (double)w[i] + carry;
-                    const f16 a = (f16)(float)v;
-                    hi[i] = a;
-                    carry = v - (double)(float)a;
-                }
-            }
-    } else {
-        for (size_t i = 0; i < hi.size(); ++i) {
-            const f16 a = (f16)w[i];
-            hi[i] = a;
-            if (want_lo) lo[i] = (f16)(w[i] - (float)a);
-        }
-    }
-    L->N = N; L->K = K;
+// The one upload step: everything device-side of a packed layer -- its allocations and copies into model `m`, the Lin, and the
+// calibration record of a bias-corrected layer, which takes the fp32 copies
+int upload_layer(jg_handle* h, Model& m, PackedLayer&& p, Lin* L) {
+    L->N = p.N; L->K = p.K;
     L->c1h = L->c1f = nullptr;
-    if (ln_consumer) {            // column sums of the weights AS PACKED (Lin::c1h / c1f)
-        std::vector<float> c1h(N), c1f(N);
-        for (int n = 0; n < N; ++n) {
-            double sh = 0.0, sl = 0.0;
-            for (int k = 0; k < K; ++k) {
-                const size_t i = (size_t)n * K + k;
-                if (h->bf16) {
-                    uint16_t b;
-                    std::memcpy(&b, &hi[i], 2);
-                    const uint32_t u = (uint32_t)b << 16;
-                    float f;
-                    std::memcpy(&f, &u, 4);
-                    sh += (double)f;
-                } else {
-                    sh += (double)(float)hi[i];
-                    if (!lo.empty()) sl += (double)(float)lo[i];
-                }
-            }
-            c1h[n] = (float)sh;
-            c1f[n] = (float)(sh + sl);
-        }
-        RET(upload(h, m, c1h, &L->c1h));
-        RET(upload(h, m, c1f, &L->c1f));
+    if (!p.c1h.empty()) {
+        RET(upload(h, m, p.c1h, &L->c1h));
+        RET(upload(h, m, p.c1f, &L->c1f));
     }
-    RET(upload(h, m, hi, &L->wh));
-    RET(upload(h, m, bias, &L->bias));
+    RET(upload(h, m, p.hi, &L->wh));
+    RET(upload(h, m, p.bias, &L->bias));
     L->w32d = L->b32d = nullptr;
-    if (h->audit_weights || h->precision == JG_PREC_FP32 || keep32) {
-        RET(upload(h, m, w, &L->w32d));
-        RET(upload(h, m, bias, &L->b32d));
+    if (p.device32) {
+        RET(upload(h, m, p.w32, &L->w32d));
+        RET(upload(h, m, p.b32, &L->b32d));
     }
     L->lo = nullptr;
-    if (want_lo) RET(upload(h, m, lo, &L->lo));       // for the form's own GEMMs and / or the split-operand kernel (gemm_x3, keep32)
-    L->form = form;
-    L->uncalibrated = starts_uncalibrated(form, kind);
+    if (!p.lo.empty()) RET(upload(h, m, p.lo, &L->lo));       // for the form's own GEMMs and / or the split-operand kernel (gemm_x3, keep32)
+    L->form = p.form;
+    L->uncalibrated = p.uncalibrated;
     L->cal = nullptr;
-    if (form == WF_BIAS_CORRECTED) {
+    if (p.form == WF_BIAS_CORRECTED) {
         float* mu;
-        RET(walloc<float>(h, m, (size_t)K, &mu));
-        m.bc.push_back({L, mu, 0, w, bias});
+        RET(walloc<float>(h, m, (size_t)p.K, &mu));
+        m.bc.push_back({L, mu, 0, std::move(p.w32), std::move(p.b32)});
         L->cal = &m.bc.back();
     }
     return JG_OK;
+}
+
+// The handle's policy for one matrix as plain values (weight_form.h, the options), then the arithmetic (weight_pack.h).
+// keep32: the layer also runs on the fp32 kernel in the fp16 modes (the two ends of the JEGAL gesture branch, option jegal_fp32_ends)
+static PackedLayer pack_host(const jg_handle* h, int model_id, const float* w, const float* bias, int N, int K, int kind, bool ln_consumer, bool keep32,
+                             int diffuse_group) {
+    const WeightForm form = weight_form(h->precision, kind, model_id);
+    const RoundRule rule = {h->bf16, form, lo_kept(form, keep32), diffuse_group};
+    return pack_layer(w, bias, N, K, rule, starts_uncalibrated(form, kind), ln_consumer, h->audit_weights || h->precision == JG_PREC_FP32 || keep32);
+}
+
+// [N][K] fp32 -> device 16-bit hi (+lo), allocated into model `m`
+int pack_matrix(jg_handle* h, Model& m, const std::vector<float>& w, const std::vector<float>& bias, int N, int K, int kind, Lin* L, bool ln_consumer,
+                bool keep32) {
+    return upload_layer(h, m, pack_host(h, m.id, w.data(), bias.data(), N, K, kind, ln_consumer, keep32, 0), L);
 }
 
 int make_linear(jg_handle* h, Model& m, const std::string& wname, const std::string& bname, int N, int K, Lin* L, int kind, bool keep32) {
@@ -129,55 +79,39 @@ int make_ln(jg_handle* h, Model& m, const std::string& wname, const std::string&
     return JG_OK;
 }
 
-// conv weight [O][I][KT][KH][KW] (+ optional eval BatchNorm) -> [O][Kpad] with k = ((kh*KW+kw)*slot + (kt*I + c)),
-// slot = channels per (kh,kw) position after padding (16 for conv1's 5x3 temporal stack, I otherwise).
-// Tap order of a conv layer's K axis: natural (kh, kw) or, for strided layers run with `reorder`, grouped by
-// parity class (kh % SH, kw % SW) -- see ConvGeom::taps.  Used by BOTH the weight packing and the geometry.
-static std::vector<std::pair<int, int>> tap_order(int KH, int KW, int SH, int SW, bool reorder) {
-    std::vector<std::pair<int, int>> t;
-    if (!reorder || KH * KW > 32) {
-        for (int kh = 0; kh < KH; ++kh)
-            for (int kw = 0; kw < KW; ++kw) t.push_back({kh, kw});
-        return t;
+// conv weight [O][I][KT][KH][KW] (+ optional eval BatchNorm `bn`, "" for none) -> the folded matrix [N][K] and shift [N] (conv_matrix,
+// weight_pack.h)
+int fold_conv(jg_handle* h, const std::string& conv, const std::string& bn, const ConvPack& c, std::vector<float>* p, std::vector<float>* shift) {
+    const HostTensor *w, *b;
+    RET(need(h, conv + ".weight", (int64_t)c.O * c.I * c.KT * c.KH * c.KW, &w));
+    RET(need(h, conv + ".bias", c.O, &b));
+    std::vector<float> s(c.O, 1.f);
+    *shift = b->v;
+    if (!bn.empty()) {
+        const HostTensor *g, *be, *mu, *var;
+        RET(need(h, bn + ".weight", c.O, &g));
+        RET(need(h, bn + ".bias", c.O, &be));
+        RET(need(h, bn + ".running_mean", c.O, &mu));
+        RET(need(h, bn + ".running_var", c.O, &var));
+        bn_fold(b->v.data(), g->v.data(), be->v.data(), mu->v.data(), var->v.data(), c.O, s.data(), shift->data());
     }
-    for (int ph = 0; ph < SH; ++ph)
-        for (int pw = 0; pw < SW; ++pw)
-            for (int kh = ph; kh < KH; kh += SH)
-                for (int kw = pw; kw < KW; kw += SW) t.push_back({kh, kw});
-    return t;
+    shift->resize(conv_pack_N(c), 0.f);
+    *p = conv_matrix(w->v.data(), s.data(), c);
+    return JG_OK;
+}
+
+int pack_conv(jg_handle* h, int model_id, const std::string& conv, const std::string& bn, const ConvPack& c, int kind, PackedLayer* out) {
+    std::vector<float> p, shift;
+    RET(fold_conv(h, conv, bn, c, &p, &shift));
+    *out = pack_host(h, model_id, p.data(), shift.data(), conv_pack_N(c), conv_pack_K(c), kind, false, false, h->conv_round_diffuse ? c.slot : 0);
+    return JG_OK;
 }
 
 int make_conv(jg_handle* h, Model& m, const std::string& conv, const std::string& bn, int O, int I, int KT, int KH, int KW,
               int slot, int kpad, Lin* L, int SH, int SW, bool reorder, int Opad, int kind) {
-    const HostTensor *w, *b;
-    RET(need(h, conv + ".weight", (int64_t)O * I * KT * KH * KW, &w));
-    RET(need(h, conv + ".bias", O, &b));
-    std::vector<float> s(O, 1.f), shift(b->v);
-    if (!bn.empty()) {
-        const HostTensor *g, *be, *mu, *var;
-        RET(need(h, bn + ".weight", O, &g));
-        RET(need(h, bn + ".bias", O, &be));
-        RET(need(h, bn + ".running_mean", O, &mu));
-        RET(need(h, bn + ".running_var", O, &var));
-        for (int o = 0; o < O; ++o) {
-            s[o] = g->v[o] / std::sqrt(var->v[o] + 1e-5f);
-            shift[o] = (b->v[o] - mu->v[o]) * s[o] + be->v[o];
-        }
-    }
-    const int K = kpad > 0 ? kpad : KH * KW * slot;
-    const int N = Opad > O ? Opad : O;
-    shift.resize(N, 0.f);
-    std::vector<float> p((size_t)N * K, 0.f);
-    const auto order = tap_order(KH, KW, SH, SW, reorder);
-    for (int o = 0; o < O; ++o)
-        for (int c = 0; c < I; ++c)
-            for (int kt = 0; kt < KT; ++kt)
-                for (size_t t = 0; t < order.size(); ++t) {
-                    const int kh = order[t].first, kw = order[t].second;
-                    const float v = w->v[((((size_t)o * I + c) * KT + kt) * KH + kh) * KW + kw] * s[o];
-                    p[(size_t)o * K + t * slot + kt * I + c] = v;
-                }
-    return pack_matrix(h, m, p, shift, N, K, kind, L, false, false, h->conv_round_diffuse ? slot : 0);
+    PackedLayer p;
+    RET(pack_conv(h, m.id, conv, bn, {O, I, KT, KH, KW, slot, kpad, Opad, SH, SW, reorder}, kind, &p));
+    return upload_layer(h, m, std::move(p), L);
 }
 
 int make_annotated_layer(jg_handle* h, Model& m, const std::string& p, int D, int Dff, EncLayer* L, int kind) {
@@ -390,13 +324,7 @@ static int apply_bias_corrections(jg_handle* h, int models) {
             mu.resize(L->K);
             HIPCHK(h, hipMemcpy(mu.data(), c.mu, sizeof(float) * L->K, hipMemcpyDeviceToHost));
             std::vector<float> nb(L->N);
-            const double inv = 1.0 / (double)c.mu_rows;
-            for (int n = 0; n < L->N; ++n) {
-                double acc = 0.0;
-                const float* wr = &c.w32[(size_t)n * L->K];
-                for (int k = 0; k < L->K; ++k) acc += (double)(wr[k] - (float)(f16)wr[k]) * ((double)mu[k] * inv);
-                nb[n] = c.b32[n] + (float)acc;
-            }
+            bias_correction(c.w32.data(), c.b32.data(), mu.data(), c.mu_rows, L->N, L->K, nb.data());
             HIPCHK(h, hipMemcpy(L->bias, nb.data(), sizeof(float) * L->N, hipMemcpyHostToDevice));
             c.mu_rows = 0;
             L->uncalibrated = false;          // calibrated: single fp16 + corrected bias from here on

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <cstdio>
+#include "conv1_panel.h"
 
 // op 0: conv2 (the count itself); op 1: conv3 (3x3, stride 2, pad 1: rows whose window ends above s2); op 2: conv4 and op 3: conv5
 // (3x3, vertical stride 1, pad 1: one row fewer each)
@@ -66,21 +67,7 @@ static_assert(mfma32_row(0, 0) == 0 && mfma32_row(5, 1) == 13 && mfma32_row(15, 
 __host__ __device__ __forceinline__ constexpr long ln_part_index(long row, int nblk, int blk) { return 2 * (row * nblk + blk); }
 static_assert(ln_part_index(0, 12, 1) == 2 && ln_part_index(3, 12, 5) == 82, "LayerNorm partial sums");
 
-// conv1's weight panel Wd[slot][ch][16] (49 pixel slots (kh, kw), 64 output channels, 16 halves: 5 frames x 3 colours and the pad
-// lane CONV1_BIAS_LANE, which the kernel feeds 1.0): the BN-folded weights, and on the pad lane of slots 0 / 1 the hi / lo halves
-// of the channel's bias.
-// The pixels reach the MFMA as the fp16 subnormals n 2^-24; the pad lane's "1.0" is 2^-14 (CONV1_BIAS_ONE, the smallest NORMAL fp16)
-// and the pair holds 255 shift 2^-10 (CONV1_BIAS_PAIR_SCALE), so the product is 255 shift 2^-24 as it must be.  Not 2^-24 times
-// 255 shift: the MFMA aligns the products of a k-step by their operands' exponent FIELDS and keeps 24 bits below the largest; a
-// subnormal 2^-24 has the field of 2^-14, the product with a bias of 2^7 sat ten bits above its value and pushed the low bits of
-// the step's pixel products out of the window (tests/test_gpu_conv1_fp64.py, tier B: up to 20 % of a channel's outputs one fp16 ulp
-// off, none with a zero bias).
-constexpr int CONV1_BIAS_LANE = 15;
-constexpr unsigned CONV1_BIAS_ONE_BITS = 0x0400u;              // fp16 2^-14
-constexpr float CONV1_BIAS_ONE = 6.103515625e-05f;            // 2^-14
-constexpr float CONV1_BIAS_PAIR_SCALE = 9.765625e-04f;        // 2^-10 = 2^-24 / CONV1_BIAS_ONE
-__host__ __device__ __forceinline__ constexpr long conv1_wd_index(int slot, int ch, int e) { return (long)(slot * 64 + ch) * 16 + e; }
-static_assert(conv1_wd_index(0, 0, CONV1_BIAS_LANE) == 15 && conv1_wd_index(1, 2, 3) == 1059 && conv1_wd_index(48, 63, 15) == 49 * 64 * 16 - 1, "conv1 weight panel");
+// conv1's weight panel Wd[slot][ch][16], conv1_wd_index and the CONV1_BIAS_* constants: conv1_panel.h (shared with the HIP-free packing unit)
 
 // conv1's zero-scan scratch (launch_conv1_scan writes it; launch_conv1_direct and the conv stack behind it read it), in 32-bit words:
 //   header of CONV1_ZHDR_WORDS: words 0..31 zconst (64 values of the 16-bit type: what conv1 gives over an all-zero patch), word

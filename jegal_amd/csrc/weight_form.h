@@ -1,6 +1,6 @@
 // The precision contract of libjegal_hip in one place: which weights a packed layer's GEMM runs with.
 //
-// weight_form() decides once, when a matrix is packed (pack_matrix, linear.hip), from the handle's precision mode, the layer's kind and
+// weight_form() decides once, when a matrix is packed (pack_host, linear.hip), from the handle's precision mode, the layer's kind and
 // the model; runs_with_lo() answers at every launch whether the GEMM takes the lo half as a second operand.  The host units ask these
 // two (through run_lo, engine.h) instead of reading pointers, and jg_debug_weight_form / jg_debug_gemm_runs_lo (checks.hip) show the
 // answers on a machine without a GPU.  Pure: no HIP, no handle, no pointer, no state.

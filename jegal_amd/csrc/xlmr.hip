@@ -29,7 +29,7 @@ int finalize_xlmr(jg_handle* h) {
     RET(upload(h, m, t->v, &xl.type));
     RET(make_ln(h, m, "xlmr.embeddings.LayerNorm.weight", "xlmr.embeddings.LayerNorm.bias", D, &xl.emb_ln));
     // Implicit LayerNorm (xlmr_encode_folded): the Linear BEHIND a LayerNorm(gamma, beta) is packed as W diag(gamma) with bias
-    // b + W beta (fold_consumer), the Linear whose output is ADDED to that LayerNorm's output takes beta into its bias (the
+    // b + W beta (fold_ln_consumer, weight_pack.h), the Linear whose output is ADDED to that LayerNorm's output takes beta into its bias (the
     // gamma (x - mean) rstd part is recomputed from the un-normalised stream in its epilogue).
     // (the implicit-LayerNorm epilogues exist in the LDS-DMA kernel only -- plan_gemm, gemm_plan.hip; the option is the policy here, the
     // packing happens before any shape is known.  The fp32 audit path runs the explicit LayerNorms on the un-folded matrices, so audit
@@ -38,23 +38,12 @@ int finalize_xlmr(jg_handle* h) {
     const HostTensor *pg, *pb;          // the LayerNorm in front of the current sub-layer
     RET(need(h, "xlmr.embeddings.LayerNorm.weight", D, &pg));
     RET(need(h, "xlmr.embeddings.LayerNorm.bias", D, &pb));
-    auto fold_consumer = [](std::vector<float>& w, std::vector<float>& b, int N, int K, const std::vector<float>& g, const std::vector<float>& be) {
-        for (int n = 0; n < N; ++n) {
-            double acc = 0.0;
-            float* wr = &w[(size_t)n * K];
-            for (int k = 0; k < K; ++k) {
-                acc += (double)wr[k] * (double)be[k];
-                wr[k] *= g[k];
-            }
-            b[n] = (float)((double)b[n] + acc);
-        }
-    };
     auto make_producer = [&](const std::string& wname, const std::string& bname, int N, int K, const std::vector<float>& be, Lin* Lo) -> int {
         const HostTensor *w, *b;
         RET(need(h, wname, (int64_t)N * K, &w));
         RET(need(h, bname, N, &b));
         std::vector<float> bb = b->v;
-        for (int n = 0; n < N; ++n) bb[n] += be[n];
+        fold_ln_producer(bb.data(), N, be.data());
         return pack_matrix(h, m, w->v, bb, N, K, LK_XLMR, Lo);
     };
     int nl = 0;
@@ -82,7 +71,7 @@ int finalize_xlmr(jg_handle* h) {
             RET(make_ln(h, m, p + ".output.LayerNorm.weight", p + ".output.LayerNorm.bias", D, &L->n2));
             continue;
         }
-        fold_consumer(w, b, 3 * D, D, pg->v, pb->v);
+        fold_ln_consumer(w.data(), b.data(), 3 * D, D, pg->v.data(), pb->v.data());
         RET(pack_matrix(h, m, w, b, 3 * D, D, LK_XLMR, &L->qkv, true));
         RET(make_producer(p + ".attention.output.dense.weight", p + ".attention.output.dense.bias", D, D, pb->v, &L->out));
         RET(make_ln(h, m, p + ".attention.output.LayerNorm.weight", p + ".attention.output.LayerNorm.bias", D, &L->n1));
@@ -93,7 +82,7 @@ int finalize_xlmr(jg_handle* h) {
             RET(need(h, p + ".intermediate.dense.weight", (int64_t)DFF * D, &w1));
             RET(need(h, p + ".intermediate.dense.bias", DFF, &b1));
             std::vector<float> wf = w1->v, bf1 = b1->v;
-            fold_consumer(wf, bf1, DFF, D, pg->v, pb->v);
+            fold_ln_consumer(wf.data(), bf1.data(), DFF, D, pg->v.data(), pb->v.data());
             RET(pack_matrix(h, m, wf, bf1, DFF, D, LK_XLMR, &L->ff1, true));
         }
         RET(make_producer(p + ".output.dense.weight", p + ".output.dense.bias", D, DFF, pb->v, &L->ff2));
