@@ -302,6 +302,14 @@ int jg_debug_conv_rowmaps(jg_handle* h, const int32_t* s2_host, int NF, const in
 /* fp32 GEMM of the audit mode (launch_gemm32): out = act(A W^T * scale + bias + res[m % res_mod]), act 0 / 1 ReLU / 2 exact GELU. */
 int jg_debug_gemm32(jg_handle* h, const float* A, int64_t lda, const float* W, int64_t ldw, int M, int N, int K, const float* scale,
                     const float* bias, const float* res, int64_t ldr, int res_mod, int act, float* out, int64_t ldc);
+/* fp32 implicit-GEMM convolution of the audit mode (launch_gemm32 with conv = 1; tests/test_gpu_audit32_fp64.py): ONE launch, the geometry
+ * built by engine::geom, M = nimg * OH * OW output pixels.
+ *   out[(img, oh, ow)][n] = act( sum_{t, c} in[img][oh SH - PH + kh_t][ow SW - PW + kw_t][c] W[n][t C + c] * scale[n] + bias[n] )
+ * in [nimg][H][W][C] fp32 NHWC, W [N][ldw] fp32 with the taps t in ConvGeom's order (as jg_debug_conv_check), scale / bias per n or NULL,
+ * act 0 / 1 ReLU / 2 exact GELU, out [M][ldc].  C: any power of two >= 1 (the launcher's rule).  Refused up front: null pointers, sizes <= 0,
+ * KH or KW > 15, ldw < KH KW C, ldc < N, a kernel larger than the padded image, M >= 2^31. */
+int jg_debug_conv32(jg_handle* h, const float* in, int nimg, int H, int W, int C, int KH, int KW, int SH, int SW, int PH, int PW, int reorder,
+                    const float* W_, int64_t ldw, int N, const float* scale, const float* bias, int act, float* out, int64_t ldc);
 /* Split-operand GEMM (launch_gemm_x3, option jegal_fp32_ends): fp32 A, fp16 Wh + Wl, fp32 out = relu?(A W^T + bias + res[m % res_mod]).
  * fp16 weights in every precision mode.  K % 256 == 0, N % 128 == 0. */
 int jg_debug_gemm_x3(jg_handle* h, const float* A, int64_t lda, const void* Wh, const void* Wl, int64_t ldw, int M, int N, int K,
@@ -364,6 +372,14 @@ int jg_debug_broadcast_channels(jg_handle* h, const void* v, int C, void* out, i
 int jg_debug_col_sum(jg_handle* h, const void* A, int64_t lda, int M, int K, float* scratch, int64_t scratch_elems, float* out, const float* stats);
 int jg_debug_rc_bias(jg_handle* h, const void* A, int64_t lda, int64_t a_elems, int tiled, int nclips, int rpc, const int32_t* valid_host, int n_valid,
                      const void* lo, const float* bias, int N, int K, float* scratch, int64_t scratch_elems, float* out);
+/* The fp32 clones of the audit mode (jegal_amd/csrc/audit32.hip; tests/test_gpu_audit32_fp64.py): the same operations, arguments and
+ * refusals as jg_debug_stack_frames / jg_debug_maxpool (without a row skip) / jg_debug_group_mean / jg_debug_zero_tail on fp32 tensors.
+ * 16-byte aligned pointers; C % 4, D % 4, row_elems % 4 and L <= 0 are refused up front. */
+int jg_debug_stack_frames32(jg_handle* h, const void* src, int src_is_u8, int64_t sb, int64_t st, int64_t sh, int64_t sw, int64_t sc, int64_t src_elems,
+                            int B, int T, int pad, int H, int W, float* dst);
+int jg_debug_maxpool32(jg_handle* h, const float* in, int nimg, int H, int W, int C, float* out);
+int jg_debug_group_mean32(jg_handle* h, const float* in, int groups, int L, int D, float* out);
+int jg_debug_zero_tail32(jg_handle* h, float* x, const int32_t* valid_host, int n_valid, int halvings, int B, int H, int64_t row_elems);
 /* Name of the kernel instance the last check point launched, with its template arguments (e.g. "gemm_glds_kernel<1,0,4,4,2,0,0,0,0>";
  * empty if it launched nothing).  Host only, no synchronisation. */
 int jg_debug_last_kernel(jg_handle* h, char* buf, int len);

@@ -79,6 +79,7 @@ _SIGS = {
     "jg_debug_conv1_panel": [_P, _P, _P],
     "jg_debug_bias_correction": [_P, _P, _P, _L, _I, _I, _P],
     "jg_debug_gemm32": [_P, _P, _L, _P, _L, _I, _I, _I, _P, _P, _P, _L, _I, _I, _P, _L],
+    "jg_debug_conv32": [_P, _P] + [_I] * 11 + [_P, _L, _I, _P, _P, _I, _P, _L],
     "jg_debug_gemm_x3": [_P, _P, _L, _P, _P, _L, _I, _I, _I, _P, _P, _L, _I, _I, _P, _L],
     "jg_debug_attention": [_P, _P, _P, _I, _I, _I, _I, _P],
     "jg_debug_attention_gather": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
@@ -91,6 +92,10 @@ _SIGS = {
     "jg_debug_cast": [_P, _P, _P, _L],
     "jg_debug_audio_conv0": [_P, _P, _I, _I, _I, _P, _P, _P, _P, ctypes.POINTER(ctypes.c_int32), _I],
     "jg_debug_zero_tail": [_P, _P, ctypes.POINTER(ctypes.c_int32), _I, _I, _I, _I, _L],
+    "jg_debug_stack_frames32": [_P, _P, _I, _L, _L, _L, _L, _L, _L, _I, _I, _I, _I, _I, _P],
+    "jg_debug_maxpool32": [_P, _P, _I, _I, _I, _I, _P],
+    "jg_debug_group_mean32": [_P, _P, _I, _I, _I, _P],
+    "jg_debug_zero_tail32": [_P, _P, ctypes.POINTER(ctypes.c_int32), _I, _I, _I, _I, _L],
     "jg_debug_xlmr_embed": [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P],
     "jg_debug_xlmr_embed_planes": [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P],
     "jg_debug_ln_stats": [_P, _P, _I, _I, _P],
@@ -552,6 +557,12 @@ class Engine:
         self._ck(self.lib.jg_debug_gemm32(self.h, _ptr(A), lda, _ptr(W), ldw, M, N, K, _ptr(scale), _ptr(bias), _ptr(res), ldr, res_mod, act,
                                           _ptr(out), ldc))
 
+    def debug_conv32(self, x, nimg, H, W, C, KH, KW, SH, SW, PH, PW, reorder, Wt, ldw, N, out, ldc, scale=None, bias=None, act=0):
+        """fp32 implicit-GEMM convolution (launch_gemm32, conv): x (nimg,H,W,C) fp32 NHWC, Wt [N][ldw] fp32 in ConvGeom's tap order."""
+        self._bind_stream()
+        self._ck(self.lib.jg_debug_conv32(self.h, _ptr(x), nimg, H, W, C, KH, KW, SH, SW, PH, PW, int(reorder), _ptr(Wt), ldw, N, _ptr(scale),
+                                          _ptr(bias), act, _ptr(out), ldc))
+
     def debug_gemm_x3(self, A, lda, Wh, Wl, ldw, M, N, K, out, ldc, bias=None, res=None, ldr=0, res_mod=0, relu=0):
         self._bind_stream()
         self._ck(self.lib.jg_debug_gemm_x3(self.h, _ptr(A), lda, _ptr(Wh), _ptr(Wl), ldw, M, N, K, _ptr(bias), _ptr(res), ldr, res_mod, relu,
@@ -613,6 +624,28 @@ class Engine:
         self._bind_stream()
         v, n = self._valid_arg(valid)
         self._ck(self.lib.jg_debug_zero_tail(self.h, _ptr(x), v, n, halvings, B, H, row_elems))
+
+    # the fp32 clones of the audit mode (audit32.hip)
+    def debug_stack_frames32(self, src, strides, B, T, pad, H, W, dst):
+        self._bind_stream()
+        sb, st, sh, sw, sc = (int(x) for x in strides)
+        u8, elems = (int(src.dtype == torch.uint8), src.numel()) if src is not None else (0, 0)
+        self._ck(self.lib.jg_debug_stack_frames32(self.h, _ptr(src), u8, sb, st, sh, sw, sc, elems, B, T, pad, H, W, _ptr(dst)))
+
+    def debug_maxpool32(self, x, out):
+        """x (nimg,H,W,C) fp32 NHWC -> out (nimg,(H-3)//2+1,(W-3)//2+1,C), written in place."""
+        self._bind_stream()
+        nimg, H, W, C = x.shape
+        self._ck(self.lib.jg_debug_maxpool32(self.h, _ptr(x), nimg, H, W, C, _ptr(out)))
+
+    def debug_group_mean32(self, x, groups, L, D, out):
+        self._bind_stream()
+        self._ck(self.lib.jg_debug_group_mean32(self.h, _ptr(x), groups, L, D, _ptr(out)))
+
+    def debug_zero_tail32(self, x, valid, halvings, B, H, row_elems):
+        self._bind_stream()
+        v, n = self._valid_arg(valid)
+        self._ck(self.lib.jg_debug_zero_tail32(self.h, _ptr(x), v, n, halvings, B, H, row_elems))
 
     def debug_xlmr_embed(self, ids, B, L, D, pad_id, vocab, maxpos, word, pos, type_, out):
         self._bind_stream()

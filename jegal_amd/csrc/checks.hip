@@ -392,6 +392,26 @@ int jg_debug_gemm32(jg_handle* h, const float* A, int64_t lda, const float* W, i
     return check_result(h, launch_gemm32(a, h->stream, h->kname), "launch_gemm32");
 }
 
+// The conv form of launch_gemm32 (the fp32 implicit GEMM of the audit mode; tests/test_gpu_audit32_fp64.py).  C is any power of two >= 1 --
+// the launcher's own rule, so another C comes back through check_result; everything else that could leave the caller's buffers is refused here.
+int jg_debug_conv32(jg_handle* h, const float* in, int nimg, int H, int W, int C, int KH, int KW, int SH, int SW, int PH, int PW, int reorder,
+                    const float* Wt, int64_t ldw, int N, const float* scale, const float* bias, int act, float* out, int64_t ldc) {
+    ENTER(h);
+    h->kname[0] = 0;
+    if (!in || !Wt || !out || nimg <= 0 || H <= 0 || W <= 0 || C <= 0 || KH <= 0 || KW <= 0 || KH > 15 || KW > 15 || SH <= 0 || SW <= 0 || PH < 0 ||
+        PW < 0 || H + 2 * PH < KH || W + 2 * PW < KW || N <= 0 || (long)KH * KW * C >= (1L << 31) || ldw < (long)KH * KW * C || ldc < N || act < 0 ||
+        act > 2)
+        JG_FAIL(h, JG_ERR_ARG, "jg_debug_conv32: bad arguments (KH, KW <= 15, the kernel inside the padded image, ldw >= KH KW C, ldc >= N, act 0..2)");
+    const ConvGeom g = geom(H, W, C, KH, KW, SH, SW, PH, PW, reorder != 0);
+    const long M = (long)nimg * g.OH * g.OW;
+    if (M >= (1L << 31)) JG_FAIL(h, JG_ERR_ARG, "jg_debug_conv32: too many output pixels");
+    Gemm32Args a;
+    std::memset(&a, 0, sizeof(a));
+    a.A = in; a.g = g; a.conv = 1; a.W = Wt; a.ldw = ldw; a.M = (int)M; a.N = N; a.K = KH * KW * C;
+    a.scale = scale; a.bias = bias; a.out = out; a.ldc = ldc; a.act = act;
+    return check_result(h, launch_gemm32(a, h->stream, h->kname), "launch_gemm32");
+}
+
 int jg_debug_gemm_x3(jg_handle* h, const float* A, int64_t lda, const void* Wh, const void* Wl, int64_t ldw, int M, int N, int K,
                      const float* bias, const float* res, int64_t ldr, int res_mod, int relu, float* out, int64_t ldc) {
     ENTER(h);
@@ -530,6 +550,54 @@ int jg_debug_zero_tail(jg_handle* h, void* x, const int32_t* valid_host, int n_v
     const int rc = check_result(h, LAUNCH(h, launch_zero_tail, static_cast<f16*>(x), static_cast<const int*>(valid), halvings, B, H, (long)row_elems, h->stream),
                                 "launch_zero_tail");
     if (rc == JG_OK) record_kernel(h->kname, "%s", "zero_tail_kernel");
+    return rc;
+}
+
+// ---- the fp32 clones of the audit mode (audit32.hip; tests/test_gpu_audit32_fp64.py): the 16-bit entries' arguments and refusals, with the
+// 16-byte rules of the fp32 kernels (C % 4, D % 4, row_elems % 4) refused up front as well
+int jg_debug_stack_frames32(jg_handle* h, const void* src, int src_is_u8, int64_t sb, int64_t st, int64_t sh, int64_t sw, int64_t sc, int64_t src_elems,
+                            int B, int T, int pad, int H, int W, float* dst) {
+    ENTER(h);
+    h->kname[0] = 0;
+    if (!src || !dst || B <= 0 || T <= 0 || H <= 0 || W <= 0 || pad < 0 || T + 2 * pad < 5 || sb < 0 || st < 0 || sh < 0 || sw < 0 || sc < 0 ||
+        (src_is_u8 != 0 && src_is_u8 != 1) || !al(dst, 16) || (!src_is_u8 && !al(src, 4)) ||
+        (B - 1) * sb + (T - 1) * st + (H - 1) * sh + (W - 1) * sw + 2 * sc >= src_elems)
+        JG_FAIL(h, JG_ERR_ARG, "jg_debug_stack_frames32: bad arguments (T + 2 pad >= 5, strides >= 0 and inside src_elems, dst 16-byte aligned)");
+    const int rc = check_result(h, launch_stack_frames32(src, src_is_u8, (long)sb, (long)st, (long)sh, (long)sw, (long)sc, B, T, pad, H, W, dst, h->stream),
+                                "launch_stack_frames32");
+    if (rc == JG_OK) record_kernel(h->kname, "stack_frames32_kernel<%s>", src_is_u8 ? "uint8_t" : "float");
+    return rc;
+}
+
+int jg_debug_maxpool32(jg_handle* h, const float* in, int nimg, int H, int W, int C, float* out) {
+    ENTER(h);
+    h->kname[0] = 0;
+    if (!in || !out || nimg <= 0 || H < 3 || W < 3 || C <= 0 || C % 4 || !al(in, 16) || !al(out, 16))
+        JG_FAIL(h, JG_ERR_ARG, "jg_debug_maxpool32: bad arguments (C %% 4 == 0, H, W >= 3, 16-byte aligned images)");
+    const int rc = check_result(h, launch_maxpool3x3s2_32(in, out, nimg, H, W, C, h->stream), "launch_maxpool3x3s2_32");
+    if (rc == JG_OK) record_kernel(h->kname, "%s", "maxpool32_kernel");
+    return rc;
+}
+
+int jg_debug_group_mean32(jg_handle* h, const float* in, int groups, int L, int D, float* out) {
+    ENTER(h);
+    h->kname[0] = 0;
+    if (!in || !out || groups <= 0 || L <= 0 || D <= 0 || D % 4 || !al(in, 16) || !al(out, 16))
+        JG_FAIL(h, JG_ERR_ARG, "jg_debug_group_mean32: bad arguments (L > 0, D %% 4 == 0, 16-byte aligned rows)");
+    const int rc = check_result(h, launch_group_mean32(in, groups, L, D, out, h->stream), "launch_group_mean32");
+    if (rc == JG_OK) record_kernel(h->kname, "%s", "group_mean32_kernel");
+    return rc;
+}
+
+int jg_debug_zero_tail32(jg_handle* h, float* x, const int32_t* valid_host, int n_valid, int halvings, int B, int H, int64_t row_elems) {
+    ENTER(h);
+    h->kname[0] = 0;
+    if (!x || !valid_host || B <= 0 || H <= 0 || n_valid != B || halvings < 0 || halvings > 30 || row_elems <= 0 || row_elems % 4 || !al(x, 16))
+        JG_FAIL(h, JG_ERR_ARG, "jg_debug_zero_tail32: bad arguments (valid_host: one entry per clip; row_elems %% 4 == 0)");
+    int32_t* valid;
+    RET(upload_valid(h, valid_host, B, &valid));
+    const int rc = check_result(h, launch_zero_tail32(x, static_cast<const int*>(valid), halvings, B, H, (long)row_elems, h->stream), "launch_zero_tail32");
+    if (rc == JG_OK) record_kernel(h->kname, "%s", "zero_tail32_kernel");
     return rc;
 }
 
