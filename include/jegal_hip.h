@@ -643,11 +643,48 @@ int jg_asd_windows(jg_handle* h, const float* gesture, const int32_t* g_offsets,
  * Cost: ONE workgroup (one CU) walks a clip's video rows in blocks of 32, in order -- that is what keeps the per-shift sums in
  * ascending t without scratch -- so the parallelism comes from n_clips.  A batch of many short clips is the intended use (4000 clips of
  * 150 rows, D = 1024, R = 15: 3.7 ms on MI355X); a single clip of 8192 rows is 256 blocks on one CU -- 16.6 ms at D = 1024, R = 15 and
- * 31 ms at R = 64, measured, while the rest of the device idles: cut a long recording into clips (with max_shift rows of overlap) if
- * its offset is wanted quickly. */
+ * 31 ms at R = 64, measured, while the rest of the device idles: jg_sync_offset_windows (below) spreads a long track over every CU,
+ * takes tracks beyond 8192 rows and gives the same bits for one window over all rows. */
 int jg_sync_offset(jg_handle* h, const float* vid, const int32_t* v_offsets, const float* aud, const int32_t* a_offsets,
                    int n_clips, int D, int max_shift, int min_overlap,
                    float* curve /* may be NULL */, int32_t* offset, float* conf);
+
+/* The audio-visual offset as a function of time, of tracks of any length, and of several video tracks against one audio track.  All
+ * pointers are device pointers.
+ *   Clip i is video track i: rows v_offsets[i] .. v_offsets[i + 1] - 1 of vid (Tv of them; vid has n_vid_rows rows).  Its audio track is
+ *   a_of[i], or track i when a_of is NULL (then n_aud must equal n_clips); audio track j owns rows a_offsets[j] .. a_offsets[j + 1] - 1 of
+ *   aud (Ta).  Many clips may name the same audio track (which face is in sync with this audio) without copying it.
+ * Band (the sync heat map): band[(v0 + t)][d + R] = <v_t, a_{t+d}> / max(|v_t| |a_{t+d}|, 1e-8) for d = -R .. R (R = max_shift), NaN where
+ *   t + d is outside 0 .. Ta - 1; fp32 [n_vid_rows][2R + 1], indexed by the GLOBAL video row v0 + t.  Optional output: with band == NULL the
+ *   same array (n_vid_rows (2R + 1) floats) is taken from the handle's workspace, and the results are the same bits.  A cosine has the bits
+ *   jg_sync_offset computes for the same two rows, and depends on its two rows alone.
+ * Windows: window j of clip i covers video rows lo = j hop .. hi = min(lo + win, Tv) - 1; win == 0: one window over all rows (hop ignored).
+ *   Clip i owns the result rows w_offsets[i] .. w_offsets[i + 1] - 1, the number of windows being the caller's choice (to cover a track:
+ *   Tv <= win ? 1 : ceil((Tv - win) / hop) + 1); max_windows >= every count sizes the grid.  For a shift d the pairs are (t, t + d) with
+ *   lo <= t <= hi and 0 <= t + d < Ta, n_d of them; curve[d + R] = the sum of the band entries over those t in ascending t (with the
+ *   compensation term jg_sync_offset uses) / n_d, NaN when n_d < min_overlap; offset and conf from the curve exactly as in jg_sync_offset.
+ * Outputs: curve fp32 [w_offsets[n_clips]][2R + 1] (may be NULL), offset int32 and conf fp32 [w_offsets[n_clips]].
+ * Determinism: a window's result is a function of its own rows -- not of hop, j, the clip's place in the batch or the other clips.  The same
+ *   [lo, hi] reached through different (hop, j) gives the same bits; win == 0, or win >= Tv with j = 0, gives jg_sync_offset's bits for the
+ *   same clip (Tv, Ta within that entry's limits, a_of NULL); clips that share a video row set and an audio track give bit-equal results.
+ * Limits: tracks of 1..max_rows rows, max_rows 1..2^20; max_windows 1..2^20; max_shift, min_overlap, D and alignment as for jg_sync_offset;
+ *   win >= 0, hop >= 1 when win > 0, n_vid_rows >= 0, n_vid_rows (2R + 1) < 2^40.  A violated limit or a null buffer returns JG_ERR_ARG
+ *   before anything is enqueued; n_clips == 0 returns JG_OK and launches nothing.  The offsets are device arrays: a clip with Tv or Ta
+ *   outside 1..max_rows, v0 + Tv > n_vid_rows, an a_of entry outside 0..n_aud-1, or more than max_windows windows is UNDECIDED in all its
+ *   windows (offset 0, conf NaN, NaN curve rows): none of its rows is read, none of its band rows is written, the other clips are
+ *   unaffected.  A window with lo >= Tv, or without a non-NaN shift, is undecided alone.  Nothing outside the described elements is written.
+ * Cost: the band is computed once by a (clip, block of 32 rows) grid, so one long track uses every CU; the windows then read
+ *   n_windows win (2R + 1) band entries -- hop = 1 with win = 8192 is the caller's choice -- each window's sum in order, so ONE window
+ *   over a long track is a sequential walk (8192 rows: 0.3 ms).  For batches of short clips the band is an extra write and read (74 MB
+ *   for 4000 clips of 150 rows at R = 15) and, with band == NULL, workspace: jg_sync_offset, which needs neither, remains the entry for
+ *   those (measured on MI355X the two are within 20 % of each other there; one clip of 8192 rows: 0.42 ms here, 19.6 ms there).
+ *   Asynchronous. */
+int jg_sync_offset_windows(jg_handle* h,
+        const float* vid, const int32_t* v_offsets, int n_clips, int64_t n_vid_rows, int max_rows,
+        const float* aud, const int32_t* a_offsets, int n_aud, const int32_t* a_of /* device [n_clips] or NULL */,
+        int D, int max_shift, int min_overlap, int win, int hop,
+        const int32_t* w_offsets /* device [n_clips + 1] */, int max_windows,
+        float* band /* may be NULL */, float* curve /* may be NULL */, int32_t* offset, float* conf);
 
 /* ---- multi-GPU exchange.  The reference is single-process (its only parallelism is the --rank / --nshard file-list split of
  *      preprocess/extract_gestsync_feats.py:366-370); clips shard with no data-path collective, and the ONE exchange of the path is the

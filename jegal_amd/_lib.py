@@ -61,6 +61,7 @@ _SIGS = {
     "jg_debug_gsa_conv1_pool": [_P, _P, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_int32), _P, _P, _P, _I],
     "jg_debug_maxpool_2x3": [_P, _P, _I, _I, _I, _I, _P, _I],
     "jg_sync_offset": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P],
+    "jg_sync_offset_windows": [_P, _P, _P, _I, _L, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P],
     "jg_debug_conv1_pool": [_P, _P, _I, _I, _I, _P],
     "jg_debug_gemm": [_P, _I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_double)],
     "jg_debug_gemm_ex": [_P, _P, _P, _I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_double)],
@@ -1191,6 +1192,74 @@ class Engine:
             return offset, conf, curve
         self._ck(self.lib.jg_sync_offset(self.h, _ptr(v), _ptr(vo), _ptr(a), _ptr(ao), n, vs[1], R, mo, _ptr(curve), _ptr(offset), _ptr(conf)))
         return offset, conf, curve
+
+    @staticmethod
+    def sync_window_counts(Tv, win, hop):
+        """windows that cover tracks of Tv rows: Tv <= win ? 1 : ceil((Tv - win) / hop) + 1 (win == 0: one)"""
+        Tv = np.asarray(Tv, np.int64)
+        if not win:
+            return np.ones_like(Tv)
+        return np.where(Tv <= win, 1, -(-(Tv - win) // hop) + 1)
+
+    def sync_offset_windows(self, vid, aud, v_offsets, a_offsets, a_of=None, max_shift=15, min_overlap=1, win=0, hop=1, n_windows=None,
+                            want_curve=True, want_band=False):
+        """jg_sync_offset_windows: the audio-visual offset over time.  Clip i is video track i (rows v_offsets[i] : v_offsets[i + 1] of vid)
+        against audio track a_of[i] (default: i; rows a_offsets[j] : a_offsets[j + 1] of aud; several clips may name one track); all offsets
+        are HOST arrays.  Window j of a clip covers its video rows j hop .. min(j hop + win, Tv) - 1; win == 0: one window over all rows
+        (jg_sync_offset's bits).  Clip i gets n_windows[i] windows (default: the count that covers it, sync_window_counts).
+        Returns (offset, conf, curve | None, w_offsets, band | None): clip i's windows are the rows w_offsets[i] : w_offsets[i + 1] of
+        offset (int32), conf (fp32) and curve (·, 2 max_shift + 1); band (rows of vid, 2 max_shift + 1) holds every cosine (NaN where the
+        audio row does not exist), with want_band; device tensors, w_offsets host int64.  A window that begins behind its track or has no
+        shift with min_overlap pairs: offset 0, conf NaN.  Tracks may have up to 2^20 rows."""
+        R, mo, win, hop = int(max_shift), int(min_overlap), int(win), int(hop)
+        if not 0 <= R <= 64 or mo < 1:
+            raise ValueError("jg_sync_offset_windows limits: max_shift 0..64, min_overlap >= 1")
+        if win < 0 or win >= 2 ** 31 or (win and not 1 <= hop < 2 ** 31):
+            raise ValueError("jg_sync_offset_windows limits: win >= 0 (0: one window over all rows), hop >= 1")
+        vs, as_ = tuple(vid.shape), tuple(aud.shape)
+        if len(vs) != 2 or len(as_) != 2 or vs[1] != as_[1] or vs[1] % 64 or not 0 < vs[1] <= 1024:
+            raise ValueError("vid / aud must be (rows, D) with the same D, a multiple of 64, at most 1024")
+        voh, aoh = (np.asarray(a, np.int64).reshape(-1) for a in (v_offsets, a_offsets))
+        n, n_aud = voh.size - 1, aoh.size - 1
+        if n < 0 or n_aud < 0:
+            raise ValueError("v_offsets / a_offsets need clips + 1 / audio tracks + 1 entries")
+        if a_of is None:
+            if n_aud != n:
+                raise ValueError("without a_of clip i takes audio track i: as many audio tracks as clips")
+            aof = np.arange(n, dtype=np.int64)
+        else:
+            aof = np.asarray(a_of, np.int64).reshape(-1)
+            if aof.size != n or (n and (aof.min() < 0 or aof.max() >= n_aud)):
+                raise ValueError("a_of needs one entry per clip, inside 0 .. audio tracks - 1")
+        Tv, Ta = np.diff(voh), np.diff(aoh)
+        if voh[0] < 0 or aoh[0] < 0 or voh[-1] > vs[0] or aoh[-1] > as_[0] or max(voh[-1], aoh[-1]) >= 2 ** 31:
+            raise ValueError("offsets must lie inside vid / aud (and be int32)")
+        if n and (Tv.min() < 1 or Tv.max() > 2 ** 20 or Ta[aof].min() < 1 or Ta[aof].max() > 2 ** 20):
+            raise ValueError("jg_sync_offset_windows limits: tracks of 1..2^20 rows")
+        if vs[0] * (2 * R + 1) >= 2 ** 40:
+            raise ValueError("jg_sync_offset_windows limits: rows of vid x (2 max_shift + 1) < 2^40")
+        nw = self.sync_window_counts(Tv, win, hop) if n_windows is None else np.asarray(n_windows, np.int64).reshape(-1)
+        if nw.size != n or (n and (nw.min() < 1 or nw.max() > 2 ** 20)):
+            raise ValueError("jg_sync_offset_windows limits: 1..2^20 windows per clip, one count per clip")
+        w_off = np.zeros(n + 1, np.int64)
+        w_off[1:] = np.cumsum(nw)
+        if w_off[-1] >= 2 ** 31:
+            raise ValueError("more than 2^31 windows in one call")
+        self._bind_stream()
+        nwin, W = int(w_off[-1]), 2 * R + 1
+        offset = torch.zeros((nwin,), dtype=torch.int32, device=self.device)
+        conf = torch.full((nwin,), float("nan"), dtype=torch.float32, device=self.device)
+        curve = torch.full((nwin, W), float("nan"), dtype=torch.float32, device=self.device) if want_curve else None
+        band = torch.full((vs[0], W), float("nan"), dtype=torch.float32, device=self.device) if want_band else None
+        if n == 0:
+            return offset, conf, curve, w_off, band
+        v, a = self._f32(vid), self._f32(aud)
+        vo, ao, wo = (self._i32(x) for x in (voh, aoh, w_off))
+        af = None if a_of is None else self._i32(aof)
+        self._ck(self.lib.jg_sync_offset_windows(self.h, _ptr(v), _ptr(vo), n, vs[0], int(max(Tv.max(), Ta[aof].max())), _ptr(a), _ptr(ao),
+                                                 n_aud, _ptr(af), vs[1], R, mo, win, hop, _ptr(wo), int(nw.max()), _ptr(band), _ptr(curve),
+                                                 _ptr(offset), _ptr(conf)))
+        return offset, conf, curve, w_off, band
 
     def asd(self, query, cand, c_offsets, temp=0.07):
         qs, cs = _shape(query), _shape(cand)

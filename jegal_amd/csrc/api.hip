@@ -623,6 +623,35 @@ int jg_sync_offset(jg_handle* h, const float* vid, const int32_t* v_offsets, con
     });
 }
 
+int jg_sync_offset_windows(jg_handle* h, const float* vid, const int32_t* v_offsets, int n_clips, int64_t n_vid_rows, int max_rows,
+                           const float* aud, const int32_t* a_offsets, int n_aud, const int32_t* a_of, int D, int max_shift, int min_overlap,
+                           int win, int hop, const int32_t* w_offsets, int max_windows, float* band, float* curve, int32_t* offset,
+                           float* conf) {
+    ENTER(h);
+    if (!vid || !v_offsets || !aud || !a_offsets || !w_offsets || !offset || !conf) JG_FAIL(h, JG_ERR_ARG, "null buffer");
+    if (n_clips < 0 || n_aud < 0 || n_vid_rows < 0) JG_FAIL(h, JG_ERR_ARG, "n_clips, n_aud and n_vid_rows must be >= 0");
+    if (!a_of && n_aud != n_clips) JG_FAIL(h, JG_ERR_ARG, "without a_of clip i takes audio track i: n_aud must equal n_clips");
+    if (D <= 0 || D % 64 || D > SYNC_MAX_D) JG_FAIL(h, JG_ERR_ARG, "D must be a positive multiple of 64, at most %d", SYNC_MAX_D);
+    if (max_shift < 0 || max_shift > SYNC_MAX_R) JG_FAIL(h, JG_ERR_ARG, "max_shift must be 0..%d", SYNC_MAX_R);
+    if (min_overlap < 1) JG_FAIL(h, JG_ERR_ARG, "min_overlap must be >= 1");
+    if (max_rows < 1 || max_rows > SYNCW_MAX_T) JG_FAIL(h, JG_ERR_ARG, "max_rows must be 1..%d", SYNCW_MAX_T);
+    if (max_windows < 1 || max_windows > SYNCW_MAX_WINDOWS) JG_FAIL(h, JG_ERR_ARG, "max_windows must be 1..%d", SYNCW_MAX_WINDOWS);
+    if (win < 0 || (win > 0 && hop < 1)) JG_FAIL(h, JG_ERR_ARG, "win must be >= 0 (0: one window over all rows) and hop >= 1");
+    const int64_t band_elems = n_vid_rows * (2 * max_shift + 1);
+    if (n_vid_rows >= (int64_t)1 << 40 || band_elems >= (int64_t)1 << 40) JG_FAIL(h, JG_ERR_ARG, "the band (n_vid_rows x (2 max_shift + 1)) must stay below 2^40 entries");
+    if ((reinterpret_cast<uintptr_t>(vid) | reinterpret_cast<uintptr_t>(aud)) & 15) JG_FAIL(h, JG_ERR_ARG, "vid / aud must be 16-byte aligned");
+    if (n_clips == 0) return JG_OK;
+    if (n_aud == 0) JG_FAIL(h, JG_ERR_ARG, "clips need an audio track: n_aud must be >= 1");
+    if (!band) {                 // the band is scratch of this call: one pass, like jg_attn_matrix's keys
+        RET(begin_pass(h));
+        RET(wsalloc(h, (size_t)(band_elems > 0 ? band_elems : 1), &band));
+    }
+    return timed(h, JG_ST_MISC, [&] {
+        return launch_sync_offset_windows(vid, v_offsets, n_clips, (long)n_vid_rows, max_rows, aud, a_offsets, n_aud, a_of, D, max_shift,
+                                          min_overlap, win, hop, w_offsets, max_windows, band, curve, offset, conf, h->stream);
+    });
+}
+
 int jg_asd(jg_handle* h, const float* q, const float* cand, const int32_t* coff, int n, int D, float temp, int32_t* pred) {
     ENTER(h);
     if (!q || !cand || !coff || !pred) JG_FAIL(h, JG_ERR_ARG, "null buffer");

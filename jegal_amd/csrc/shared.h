@@ -207,6 +207,16 @@ hipError_t launch_asd(const float* q, const float* cand, const int32_t* coff, in
 constexpr int SYNC_MAX_R = 64, SYNC_MAX_T = 8192, SYNC_MAX_D = 1024;
 hipError_t launch_sync_offset(const float* vid, const int32_t* voff, const float* aud, const int32_t* aoff, int n, int D, int R, int min_overlap,
                               float* curve, int32_t* offset, float* conf, hipStream_t s);
+// The same over time (metrics.hip: sync_band_kernel + sync_windows_kernel): clip i = video track i against audio track a_of[i] (nullptr: i),
+// window j of it = video rows j hop .. min(j hop + win, Tv) - 1 (win == 0: all rows) -> curve (optional) / offset / conf rows woff[i] + j.
+// band [n_vid_rows][2R + 1] (required here: the caller's, or scratch of that size) receives every cosine once, NaN where the audio row does
+// not exist.  A clip outside the limits (tracks of 1..max_rows rows inside the arrays, a_of inside 0..n_aud-1, 1..max_windows windows) gets
+// offset 0, conf NaN and NaN curve rows in all of its windows and none of its band rows is written.
+constexpr int SYNCW_MAX_T = 1 << 20, SYNCW_MAX_WINDOWS = 1 << 20;
+hipError_t launch_sync_offset_windows(const float* vid, const int32_t* voff, int n, long n_vid_rows, int max_rows, const float* aud,
+                                      const int32_t* aoff, int n_aud, const int32_t* a_of, int D, int R, int min_overlap, int win, int hop,
+                                      const int32_t* woff, int max_windows, float* band, float* curve, int32_t* offset, float* conf,
+                                      hipStream_t s);
 // GestSync's audio stream (gsa_kernels.hip).  conv1 + BatchNorm + ReLU + max-pool of windows n0 .. n0 + nwin - 1 -> out [nwin][19][24][64]
 // (fp16, or fp32 with out32): clip_form 0: src = x (N, 1, 80, 100); 1: src = mel (B, Tm, 80), window n = b * T + t reads mel rows
 // clamp(4 (t - 12) + 0..99, 0, valid[b] - 1) (valid: device [B] or nullptr = Tm).  w [64][9] (BatchNorm scale folded), shift [64]: fp32

@@ -11,6 +11,7 @@
     python -m jegal_amd.drivers search --path D --query F.pkl [--level word|phrase]   # which clips gesture a word, and at which frame (-> search_<F>.npz)
     python -m jegal_amd.drivers asd --path D --file avs_asd.csv [--win N --hop M]   # the detection evaluate_asd.py grades (-> asd.npz)
     python -m jegal_amd.drivers sync_offset --checkpoint_path_gestsync CKPT --frames F.npy --wav F.wav [--mel F.npy] [--max_shift 15]   # audio-visual offset of a clip (-> <name>.sync.npz)
+        [--win 125 --hop 25]   # the offset over time (start, offset_t, conf_t, curve_t);  several --frames: which track is in sync with the audio, per window
     python -m jegal_amd.drivers embed_tracks --checkpoint_path_jegal CKPT --feature_dir D --result_dir R [--win 120 --ctx 50]   # gesture embeddings of tracks of any length (-> R/v/<vid>__<track>.pkl)
 
 Same flags, file naming and on-disk formats as the reference.  What is upstream of the hot path is
@@ -679,39 +680,22 @@ SYNC_OFFSET_NOTE = ("The released GestSync checkpoint was trained on its authors
                     "authors' mel with --mel for a real checkpoint.  Parity of the network itself is pinned (GestSync.forward_aud).")
 
 
-def cmd_sync_offset(argv, engine=None, gestsync=None):
-    """Audio-visual offset of one clip: the thin composition of GestSync.extract_clip_feats (frames -> (T,1024)), the log-mel front end
-    (--wav, Engine.logmel) or a caller's mel (--mel: (4T,80) fp32, time-major, 4 mel steps per frame), GestSync.extract_clip_audio_feats
-    (mel -> (T,1024)) and metrics.sync_offset.  Prints the offset in frames (d > 0: the audio matching frame t is found d frames later,
-    i.e. the audio track lags) and the confidence; writes ``<res_dir>/<name>.sync.npz`` = {offset, conf, curve (2 max_shift + 1,),
-    shifts}."""
+def _sync_streams(args, engine, gestsync):
+    """What both forms of sync_offset start from: the synthetic-weights warning, the models, the (T,1024) video rows of every --frames
+    file and the (Ta,1024) audio rows of the one --wav / --mel -> (engine, [video rows], audio rows), on the device."""
     from . import audio as jaudio
-    from . import metrics as M
-    p = argparse.ArgumentParser(prog="sync_offset", epilog=SYNC_OFFSET_NOTE)
-    p.add_argument("--checkpoint_path_gestsync", required=True,
-                   help="GestSync checkpoint with its audio stream; 'synthetic' = the seeded test weights, whose embeddings carry NO sync "
-                        "signal (the result then only shows that the path runs)")
-    p.add_argument("--frames", required=True, help=".npy of masked uint8 crops (T,270,480,3)")
-    p.add_argument("--wav", default=None, help="16 kHz mono .wav of the clip (log-mel on the GPU). " + SYNC_OFFSET_NOTE)
-    p.add_argument("--mel", default=None, help=".npy (Tm,80) fp32 time-major mel of the clip, 4 steps per frame: used instead of --wav")
-    p.add_argument("--max_shift", type=int, default=15)
-    p.add_argument("--min_overlap", type=int, default=1)
-    p.add_argument("--res_dir", default=".")
-    _add_precision_args(p)
-    args = p.parse_args(argv)
-    if (args.wav is None) == (args.mel is None):
-        raise SystemExit("sync_offset: give --wav or --mel (one of them)")
     if args.checkpoint_path_gestsync == "synthetic":
         print("WARNING: synthetic GestSync weights: their window embeddings are 0.93-0.996 correlated whatever the input, so the offset "
               "and confidence below are MEANINGLESS as a sync measurement; pass a trained checkpoint.")
     if gestsync is None:
         engine, gestsync, _ = _models(args, need_gestsync=True)
     eng = engine if engine is not None else gestsync.engine
-    frames = np.load(args.frames)
-    if frames.ndim != 4 or tuple(frames.shape[1:]) != (270, 480, 3) or frames.dtype != np.uint8:
-        raise ValueError("--frames must hold (T,270,480,3) uint8 masked crops")
-    T = frames.shape[0]
-    vid = gestsync.extract_clip_feats(torch.from_numpy(frames).to(eng.device))[0]
+    vids = []
+    for path in args.frames:
+        frames = np.load(path)
+        if frames.ndim != 4 or tuple(frames.shape[1:]) != (270, 480, 3) or frames.dtype != np.uint8:
+            raise ValueError("--frames must hold (T,270,480,3) uint8 masked crops")
+        vids.append(gestsync.extract_clip_feats(torch.from_numpy(frames).to(eng.device))[0])
     if args.mel is not None:
         mel = torch.from_numpy(np.load(args.mel).astype(np.float32))
         if mel.dim() != 2 or mel.shape[1] != 80 or mel.shape[0] < 1:
@@ -720,10 +704,88 @@ def cmd_sync_offset(argv, engine=None, gestsync=None):
     else:
         wav = torch.from_numpy(np.asarray(jaudio.load_wav(args.wav)).astype(np.float32))
         mel = jaudio.wav2filterbanks(wav[None].to(eng.device), engine=eng)[0]
+    T = max(int(v.shape[0]) for v in vids)
     Ta = max(1, min(T, -(-int(mel.shape[1]) // 4)))            # audio windows: one per frame the mel covers
-    aud = gestsync.extract_clip_audio_feats(mel, Ta)[0]
+    return eng, vids, gestsync.extract_clip_audio_feats(mel, Ta)[0]
+
+
+def _sync_offset_over_time(args, engine, gestsync):
+    """sync_offset with --win (the offset as a function of time: metrics.sync_timeline) and / or several --frames (which track is in sync
+    with the audio: metrics.sync_speaker); every track's ``<name>.sync.npz`` gains start, offset_t, conf_t, curve_t beside the clip-level
+    offset, conf, curve, shifts."""
+    from . import metrics as M
+    eng, vids, aud = _sync_streams(args, engine, gestsync)
+    hop = args.hop if args.hop > 0 else max(1, args.win // 5)
+    Ta = int(aud.shape[0])
+    n = len(vids)
+    clip = M.sync_timeline(vids, [aud], win=0, max_shift=args.max_shift, min_overlap=args.min_overlap, audio_of=[0] * n, engine=eng)
+    line = M.sync_timeline(vids, [aud], win=args.win, hop=hop, max_shift=args.max_shift, min_overlap=args.min_overlap, audio_of=[0] * n,
+                           engine=eng)
+    os.makedirs(args.res_dir, exist_ok=True)
+    shifts = np.arange(-args.max_shift, args.max_shift + 1, dtype=np.int32)
+    for f, v, c, t in zip(args.frames, vids, clip, line):
+        name = os.path.basename(f).rsplit(".", 1)[0]
+        out = os.path.join(args.res_dir, name + ".sync.npz")
+        np.savez(out, offset=c["offset"][0], conf=c["conf"][0], curve=c["curve"][0], shifts=shifts, start=t["start"], offset_t=t["offset"],
+                 conf_t=t["conf"], curve_t=t["curve"])
+        print("AV offset: {} frames   confidence: {:.4f}   ({} video / {} audio windows) -> {}".format(
+            int(c["offset"][0]), float(c["conf"][0]), int(v.shape[0]), Ta, out))
+        ok = ~np.isnan(t["conf"])
+        if ok.any():                    # confident: at least half the best window's confidence
+            ok &= np.nan_to_num(t["conf"], nan=-np.inf) >= 0.5 * np.nanmax(t["conf"])
+        if ok.any():
+            o = t["offset"][ok]
+            step = np.abs(np.diff(t["offset"].astype(np.int64))) if len(t["offset"]) > 1 else np.zeros(0, np.int64)
+            at = int(t["start"][1 + int(np.argmax(step))]) if step.size and step.max() > 0 else -1
+            print("  over time (win {} hop {}, {} windows): median offset {:g}, min {} / max {} over the {} confident windows{}".format(
+                args.win, hop, len(t["offset"]), float(np.median(o)), int(o.min()), int(o.max()), int(ok.sum()),
+                ", largest change at frame {}".format(at) if at >= 0 else ", no change"))
+        else:
+            print("  over time (win {} hop {}): no window with a shift".format(args.win, hop))
+    if n > 1:
+        speaker, conf = M.sync_speaker(vids, aud, win=args.win, hop=hop, max_shift=args.max_shift, min_overlap=args.min_overlap, engine=eng)
+        names = [os.path.basename(f).rsplit(".", 1)[0] for f in args.frames]
+        for j, s in enumerate(speaker):
+            print("  window {} (frame {}): in sync: {}".format(j, j * hop if args.win else 0, names[s] if s >= 0 else "-"))
+        np.savez(os.path.join(args.res_dir, "sync_speaker.npz"), tracks=np.asarray(names), speaker=speaker, conf=conf,
+                 start=(np.arange(len(speaker)) * (hop if args.win else 0)).astype(np.int32))
+    return 0
+
+
+def cmd_sync_offset(argv, engine=None, gestsync=None):
+    """Audio-visual offset of one clip: the thin composition of GestSync.extract_clip_feats (frames -> (T,1024)), the log-mel front end
+    (--wav, Engine.logmel) or a caller's mel (--mel: (4T,80) fp32, time-major, 4 mel steps per frame), GestSync.extract_clip_audio_feats
+    (mel -> (T,1024)) and metrics.sync_offset.  Prints the offset in frames (d > 0: the audio matching frame t is found d frames later,
+    i.e. the audio track lags) and the confidence; writes ``<res_dir>/<name>.sync.npz`` = {offset, conf, curve (2 max_shift + 1,),
+    shifts}.  --win N [--hop M]: the offset over time as well (_sync_offset_over_time: metrics.sync_timeline); --frames given several
+    times: candidate tracks against the one audio, the in-sync track per window (metrics.sync_speaker).  Without either: the output of
+    before, byte for byte."""
+    from . import metrics as M
+    p = argparse.ArgumentParser(prog="sync_offset", epilog=SYNC_OFFSET_NOTE)
+    p.add_argument("--checkpoint_path_gestsync", required=True,
+                   help="GestSync checkpoint with its audio stream; 'synthetic' = the seeded test weights, whose embeddings carry NO sync "
+                        "signal (the result then only shows that the path runs)")
+    p.add_argument("--frames", required=True, action="append",
+                   help=".npy of masked uint8 crops (T,270,480,3); several --frames: candidate tracks of one scene against the one --wav / --mel")
+    p.add_argument("--wav", default=None, help="16 kHz mono .wav of the clip (log-mel on the GPU). " + SYNC_OFFSET_NOTE)
+    p.add_argument("--mel", default=None, help=".npy (Tm,80) fp32 time-major mel of the clip, 4 steps per frame: used instead of --wav")
+    p.add_argument("--max_shift", type=int, default=15)
+    p.add_argument("--min_overlap", type=int, default=1)
+    p.add_argument("--win", type=int, default=0, help="frames per window of the offset timeline (0: one offset for the clip)")
+    p.add_argument("--hop", type=int, default=0, help="frames between window starts (default: win / 5)")
+    p.add_argument("--res_dir", default=".")
+    _add_precision_args(p)
+    args = p.parse_args(argv)
+    if (args.wav is None) == (args.mel is None):
+        raise SystemExit("sync_offset: give --wav or --mel (one of them)")
+    if args.win < 0 or args.hop < 0:
+        raise SystemExit("sync_offset: --win and --hop must be >= 0")
+    if args.win > 0 or len(args.frames) > 1:
+        return _sync_offset_over_time(args, engine, gestsync)
+    eng, (vid,), aud = _sync_streams(args, engine, gestsync)
+    T, Ta = int(vid.shape[0]), int(aud.shape[0])
     off, conf, curve = M.sync_offset([vid], [aud], args.max_shift, args.min_overlap, engine=eng)
-    name = os.path.basename(args.frames).rsplit(".", 1)[0]
+    name = os.path.basename(args.frames[0]).rsplit(".", 1)[0]
     os.makedirs(args.res_dir, exist_ok=True)
     out = os.path.join(args.res_dir, name + ".sync.npz")
     np.savez(out, offset=off[0], conf=conf[0], curve=curve[0], shifts=np.arange(-args.max_shift, args.max_shift + 1, dtype=np.int32))

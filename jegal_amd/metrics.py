@@ -290,6 +290,58 @@ def sync_offset(vid_feats, aud_feats, max_shift=15, min_overlap=1, engine=None):
     return _host(off), _host(conf), _host(curve)
 
 
+def _rows(mats):
+    """host arrays, or tensors already on the device (the extractors' outputs) -> one (sum rows, D) tensor"""
+    return torch.cat([m.to(torch.float32) for m in mats], 0) if isinstance(mats[0], torch.Tensor) else _cat(mats)
+
+
+def sync_timeline(vid_feats, aud_feats, win=125, hop=25, max_shift=15, min_overlap=1, audio_of=None, engine=None):
+    """The audio-visual offset as a function of time: vid_feats / aud_feats are lists of per-track (Tv, D) / (Ta, D) arrays (host arrays or
+    device tensors, as for sync_offset; tracks of any length up to 2^20 rows).  Clip i is video track i against audio track audio_of[i]
+    (default: i; several clips may name one audio track).  Window j of a clip covers its frames j hop .. j hop + win - 1 (cut at the
+    track's end), Tv <= win ? 1 : ceil((Tv - win) / hop) + 1 windows per clip; win = 0: one window over the whole track.  One
+    jg_sync_offset_windows call.
+    Returns per clip a dict(start (n_win,) int32: the first frame of each window; offset (n_win,) int32; conf (n_win,) float32; curve
+    (n_win, 2 max_shift + 1) float32), each as in sync_offset but over the window's frames.  A window without a shift of min_overlap
+    pairs: offset 0, conf NaN."""
+    n = len(vid_feats)
+    if (len(aud_feats) != n) if audio_of is None else (len(audio_of) != n):
+        raise ValueError("one audio array per video array, or one audio_of entry per video array")
+    if n == 0:
+        return []
+    if not len(aud_feats):
+        raise ValueError("no audio track")
+    eng = engine or Engine.get()
+    off, conf, curve, w_off, _ = eng.sync_offset_windows(_rows(vid_feats), _rows(aud_feats), _offsets(vid_feats), _offsets(aud_feats),
+                                                        a_of=audio_of, max_shift=max_shift, min_overlap=min_overlap, win=win, hop=hop)
+    off, conf, curve = _host(off), _host(conf), _host(curve)
+    out = []
+    for i in range(n):
+        lo, hi = int(w_off[i]), int(w_off[i + 1])
+        out.append(dict(start=(np.arange(hi - lo) * (hop if win else 0)).astype(np.int32), offset=off[lo:hi], conf=conf[lo:hi], curve=curve[lo:hi]))
+    return out
+
+
+def sync_speaker(tracks, audio, win=125, hop=25, max_shift=15, min_overlap=1, engine=None):
+    """Which face is in sync with this audio, and when: every video track of `tracks` (a list of (Tv_p, D) arrays, co-temporal: frame t of
+    each is the same instant) against the ONE audio track `audio` (Ta, D), per window of `win` frames, `hop` apart (win = 0: one window
+    over everything).  One jg_sync_offset_windows call; the audio is not copied per track.
+    Returns (speaker (n_win,) int32: per window the track with the largest confidence, the first on ties, -1 where every confidence is
+    NaN; conf (n_win, n_tracks) float32).  n_win covers the longest track; a track that has ended reads NaN."""
+    P = len(tracks)
+    if P == 0:
+        return np.zeros(0, np.int32), np.zeros((0, 0), np.float32)
+    eng = engine or Engine.get()
+    n_win = int(eng.sync_window_counts([max(int(t.shape[0]) for t in tracks)], int(win), int(hop))[0])
+    _, conf, _, _, _ = eng.sync_offset_windows(_rows(tracks), _rows([audio]), _offsets(tracks), _offsets([audio]), a_of=np.zeros(P, np.int64),
+                                                 max_shift=max_shift, min_overlap=min_overlap, win=win, hop=hop, n_windows=[n_win] * P,
+                                                 want_curve=False)
+    conf = _host(conf).reshape(P, n_win).T.copy()
+    none = np.isnan(conf).all(axis=1)
+    speaker = np.where(none, -1, np.argmax(np.where(np.isnan(conf), -np.inf, conf), axis=1)).astype(np.int32)
+    return speaker, conf
+
+
 def asd_counts(pred):
     """[correct for 2, 4, 6 speakers, queries] from jg_asd's (n,3) argmax indices: the positive is candidate 0 (evaluate_asd.py:101-113)."""
     pred = np.asarray(pred).reshape(-1, 3)
