@@ -10,6 +10,8 @@ import os
 import numpy as np
 import torch  # imported first so libamdhip64.so.7 resolves to the runtime torch already loaded
 
+from ._metric_entries import MetricEntries, _ptr, _shape
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libjegal_hip.so")
 
@@ -320,17 +322,9 @@ def track_windows(lengths, win, ctx):
     return table, smax.value
 
 
-def _ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-def _shape(x):
-    """The shape of a tensor, an array or nested lists, without moving anything."""
-    return tuple(x.shape) if hasattr(x, "shape") else np.shape(x)
-
-
-class Engine:
-    """One jg_handle on one GPU.  Not thread-safe; one per process/GPU."""
+class Engine(MetricEntries):
+    """One jg_handle on one GPU.  Not thread-safe; one per process/GPU.  The metric entries (pool_mean .. asd_windows) are
+    MetricEntries' (_metric_entries.py)."""
 
     _cache = {}
 
@@ -975,369 +969,6 @@ class Engine:
         D = x.shape[-1]
         self._ck(self.lib.jg_l2norm(self.h, _ptr(x), _ptr(out), x.numel() // D, D))
         return out
-
-    # ---- metrics
-    @staticmethod
-    def _check_row_offsets(offsets, rows, n=None):
-        """Row offsets of the ragged entries -> number of blocks.  What needs no sync is checked: the count (n + 1 entries when the caller
-        knows n), and for a host array that it is a non-decreasing partition inside 0 .. rows; a tensor's values stay on the device."""
-        if isinstance(offsets, torch.Tensor):
-            if offsets.ndim != 1 or offsets.numel() < 1 or offsets.dtype not in (torch.int32, torch.int64):
-                raise ValueError("offsets must be a 1-d integer tensor of blocks + 1 entries")
-            count = offsets.numel()
-        else:
-            off = np.asarray(offsets)
-            if off.ndim != 1 or off.size < 1 or not np.issubdtype(off.dtype, np.integer):
-                raise ValueError("offsets must be a 1-d integer array of blocks + 1 entries")
-            if off[0] < 0 or off[-1] > rows or np.any(np.diff(off.astype(np.int64)) < 0):
-                raise ValueError("offsets must be non-decreasing and lie inside 0 .. rows")
-            count = off.size
-        if n is not None and count != n + 1:
-            raise ValueError(f"offsets need {n + 1} entries (blocks + 1), not {count}")
-        return count - 1
-
-    def pool_mean(self, x, offsets):
-        xs = _shape(x)
-        if len(xs) != 2 or xs[1] < 1:
-            raise ValueError("x must be (rows, D)")
-        self._check_row_offsets(offsets, xs[0])
-        self._bind_stream()
-        x = self._f32(x)
-        off = self._i32(offsets)
-        n = off.numel() - 1
-        out = torch.empty((n, x.shape[-1]), dtype=torch.float32, device=self.device)
-        self._ck(self.lib.jg_pool_mean(self.h, _ptr(x), _ptr(off), n, x.shape[-1], _ptr(out)))
-        return out
-
-    def sim_rank(self, e1, e2, row_offset=0):
-        s1, s2 = _shape(e1), _shape(e2)
-        if len(s1) != 2 or len(s2) != 2 or s1[1] != s2[1] or s1[1] <= 0 or s1[1] % 64:
-            raise ValueError("e1 / e2 must be (rows, D) with the same D, a positive multiple of 64")
-        row_offset = int(row_offset)
-        if row_offset < 0 or row_offset + s1[0] > s2[0]:
-            raise ValueError("row_offset must be >= 0 and row_offset + rows of e1 <= rows of e2")
-        self._bind_stream()
-        e1, e2 = self._f32(e1), self._f32(e2)
-        n_local, D = e1.shape
-        rank = torch.empty(n_local, dtype=torch.int32, device=self.device)
-        ties = torch.empty(n_local, dtype=torch.int32, device=self.device)
-        self._ck(self.lib.jg_sim_rank(self.h, _ptr(e1), _ptr(e2), n_local, e2.shape[0], row_offset, D, _ptr(rank), _ptr(ties)))
-        return rank, ties
-
-    def _sim_topk_args(self, entry, queries, gallery, k, gallery_offset, merge_into, g_offsets=None):
-        """What sim_topk and sim_topk_grouped (`entry`; the latter passes g_offsets) share: the checks of the shapes, k, gallery_offset,
-        the group offsets and merge_into, then the stream, and the result to fill: merge_into's pair, or an empty one (-1 / -inf).
-        Returns (rows of queries, rows of gallery, D, k, gallery_offset, groups or None, idx, score)."""
-        qs, gs = tuple(queries.shape), tuple(gallery.shape)
-        if len(qs) != 2 or len(gs) != 2 or qs[1] != gs[1] or qs[1] <= 0 or qs[1] % 64:
-            raise ValueError("queries / gallery must be (rows, D) with the same D, a positive multiple of 64")
-        k, gallery_offset = int(k), int(gallery_offset)
-        if not 1 <= k <= 128:
-            raise ValueError(f"jg_{entry} limit: 1 <= k <= 128")
-        if gallery_offset < 0 or gallery_offset + gs[0] > 2 ** 31 - 1:
-            raise ValueError("gallery_offset must be >= 0 and gallery_offset + gallery rows <= INT32_MAX")
-        n_groups = None if g_offsets is None else self._check_group_offsets(g_offsets, gs[0])
-        if merge_into is not None:
-            if not isinstance(merge_into, (tuple, list)) or len(merge_into) != 2 or not all(isinstance(t, torch.Tensor) for t in merge_into):
-                raise ValueError(f"merge_into must be the (idx, score) pair of an earlier {entry} call")
-            idx, score = merge_into
-            if (tuple(idx.shape) != (qs[0], k) or tuple(score.shape) != (qs[0], k) or idx.dtype != torch.int32 or score.dtype != torch.float32
-                    or not idx.is_contiguous() or not score.is_contiguous()):
-                raise ValueError(f"merge_into must be contiguous (idx int32, score float32) tensors of shape ({qs[0]}, {k})")
-            if idx.device != self.device or score.device != self.device:
-                raise ValueError(f"merge_into must be on {self.device}")
-        self._bind_stream()
-        if merge_into is None:
-            idx = torch.full((qs[0], k), -1, dtype=torch.int32, device=self.device)
-            score = torch.full((qs[0], k), float("-inf"), dtype=torch.float32, device=self.device)
-        return qs[0], gs[0], qs[1], k, gallery_offset, n_groups, idx, score
-
-    def sim_topk(self, queries, gallery, k, gallery_offset=0, merge_into=None):
-        """jg_sim_topk: per query row the k gallery rows with the largest <q_i, g_j> (rows as stored: normalise first, as for sim_rank), best
-        first; on equal scores the smaller gallery row first.  queries (n, D) / gallery (m, D), D % 64 == 0, 1 <= k <= 128.
-        Returns (idx (n, k) int32 = gallery_offset + j, score (n, k) float32) as device tensors; slots beyond the candidates are -1 / -inf.
-        merge_into = (idx, score) of an earlier call with the same queries and k on OTHER gallery rows: the two are updated in place to the
-        best k of the union and returned (a gallery too large for the device goes through in pieces, each with its gallery_offset)."""
-        n, m, D, k, gallery_offset, _, idx, score = self._sim_topk_args("sim_topk", queries, gallery, k, gallery_offset, merge_into)
-        q, g = self._f32(queries), self._f32(gallery)
-        if n and m:                                    # (no gallery row: nothing to merge, or the empty result)
-            self._ck(self.lib.jg_sim_topk(self.h, _ptr(q), _ptr(g), n, m, D, k, gallery_offset, int(merge_into is not None), _ptr(idx), _ptr(score)))
-        return idx, score
-
-    @staticmethod
-    def _check_group_offsets(g_offsets, rows):
-        """g_offsets of the grouped entries -> number of groups.  A host array is checked (a non-decreasing partition inside 0 .. rows); a
-        tensor is taken as it is, as the C entry takes it: only its shape and type are looked at."""
-        if isinstance(g_offsets, torch.Tensor):
-            if g_offsets.ndim != 1 or g_offsets.numel() < 1 or g_offsets.dtype not in (torch.int32, torch.int64):
-                raise ValueError("g_offsets must be a 1-d integer tensor of groups + 1 entries")
-            return g_offsets.numel() - 1
-        off = np.asarray(g_offsets)
-        if off.ndim != 1 or off.size < 1 or not np.issubdtype(off.dtype, np.integer):
-            raise ValueError("g_offsets must be a 1-d integer array of groups + 1 entries")
-        if off[0] < 0 or (rows is not None and off[-1] > rows) or off[-1] > 2 ** 31 - 1 or np.any(np.diff(off.astype(np.int64)) < 0):
-            raise ValueError("g_offsets must be non-decreasing and lie inside 0 .. gallery rows")
-        return off.size - 1
-
-    def sim_topk_grouped(self, queries, gallery, g_offsets, k, gallery_offset=0, merge_into=None):
-        """jg_sim_topk_grouped: the gallery rows are cut into contiguous groups (group i = rows g_offsets[i] .. g_offsets[i + 1] - 1 of
-        `gallery`; a host array or a tensor of groups + 1 entries), a group scores as its best row, and per query row the k best groups come
-        back, each as the row that earned the score: (idx (n, k) int32 = gallery_offset + row, score (n, k) float32), device tensors, best
-        first, on equal scores the smaller row; never two rows of one group; -1 / -inf where fewer than k groups have a row.  Scores are
-        those of sim_topk / sim_rank bit for bit.  merge_into = (idx, score) of an earlier call with the same queries and k on OTHER
-        gallery rows, cut at group boundaries: updated in place to the best k of the union and returned."""
-        n, m, D, k, gallery_offset, n_groups, idx, score = self._sim_topk_args("sim_topk_grouped", queries, gallery, k, gallery_offset,
-                                                                               merge_into, g_offsets)
-        q, g, off = self._f32(queries), self._f32(gallery), self._i32(g_offsets)
-        if n and m and n_groups:                       # (no gallery row, no group: nothing to merge, or the empty result)
-            self._ck(self.lib.jg_sim_topk_grouped(self.h, _ptr(q), _ptr(g), n, m, D, k, _ptr(off), n_groups, gallery_offset,
-                                                  int(merge_into is not None), _ptr(idx), _ptr(score)))
-        return idx, score
-
-    def group_of_rows(self, idx, g_offsets, gallery_offset=0):
-        """jg_group_of_rows: the rows sim_topk_grouped returned (an int32 tensor of any shape) -> (grp, pos) int32 device tensors of that
-        shape: the group whose range holds idx - gallery_offset and the row's place inside it; -1 / -1 for idx < 0 or a row in no group.
-        After merged calls: the offsets of the whole gallery with gallery_offset = 0."""
-        if not isinstance(idx, torch.Tensor) or idx.dtype != torch.int32:
-            raise ValueError("idx must be an int32 tensor (the idx of sim_topk_grouped)")
-        gallery_offset = int(gallery_offset)
-        if not 0 <= gallery_offset <= 2 ** 31 - 1:
-            raise ValueError("gallery_offset must be 0 .. INT32_MAX")
-        n_groups = self._check_group_offsets(g_offsets, None)
-        self._bind_stream()
-        rows, off = self._i32(idx), self._i32(g_offsets)
-        grp, pos = torch.full_like(rows, -1), torch.full_like(rows, -1)
-        if rows.numel():
-            self._ck(self.lib.jg_group_of_rows(self.h, _ptr(rows), rows.numel(), _ptr(off), n_groups, gallery_offset, _ptr(grp), _ptr(pos)))
-        return grp, pos
-
-    def spot(self, gesture, content, g_offsets, c_offsets, targets, temp=0.07):
-        self._bind_stream()
-        g, c = self._f32(gesture), self._f32(content)
-        goh, coh, tgh = (np.asarray(a, np.int64) for a in (g_offsets, c_offsets, targets))
-        n = tgh.size
-        if goh.size != n + 1 or coh.size != n + 1:
-            raise ValueError("g_offsets / c_offsets need one entry more than targets")
-        T, W = np.diff(goh), np.diff(coh)
-        if n and (T.min() <= 0 or T.max() > 8192 or W.min() <= 0 or W.max() > 1024 or (tgh < 0).any() or (tgh >= W).any()):
-            raise ValueError("jg_spot limits: 1..8192 frames and 1..1024 words per clip, 0 <= target < words")
-        go, co, tg = self._i32(g_offsets), self._i32(c_offsets), self._i32(targets)
-        pred = torch.empty(n, dtype=torch.int32, device=self.device)
-        score = torch.empty(n, dtype=torch.float32, device=self.device)
-        self._ck(self.lib.jg_spot(self.h, _ptr(g), _ptr(c), _ptr(go), _ptr(co), _ptr(tg), n, g.shape[-1], temp, _ptr(pred), _ptr(score)))
-        return pred, score
-
-    def attn_matrix(self, gesture, content, g_offsets, c_offsets, temp=0.07, normalize=True, want_matrix=True):
-        """jg_attn_matrix: per clip A_i = softmax((G_i C_i^T) / temp, dim=1)^T (W_i, T_i) and, for every word, its first arg-max frame and
-        that probability.  gesture (sum T, D) / content (sum W, D); g_offsets / c_offsets: HOST arrays of n + 1 entries.
-        Returns (A_flat | None, a_offsets, best_frame, best_score): clip i's matrix is A_flat[a_offsets[i] : a_offsets[i + 1]].reshape(W_i, T_i)
-        (a_offsets: host int64, n + 1 entries), best_* are device tensors indexed like content's rows (c_offsets[-1] entries: clip i's words
-        are best_*[c_offsets[i] : c_offsets[i + 1]]; entries no clip covers are -1 / NaN).  want_matrix=False: no matrix is written."""
-        goh, coh = (np.asarray(a, np.int64).reshape(-1) for a in (g_offsets, c_offsets))
-        n = goh.size - 1
-        if n < 0 or coh.size != n + 1:
-            raise ValueError("g_offsets / c_offsets need the same number of entries (clips + 1)")
-        T, W = np.diff(goh), np.diff(coh)
-        if n and (T.min() <= 0 or T.max() > 8192 or W.min() <= 0 or W.max() > 1024):
-            raise ValueError("jg_attn_matrix limits: 1..8192 frames and 1..1024 words per clip")
-        if not temp > 0:
-            raise ValueError("temp must be positive")
-        gs, cs = tuple(gesture.shape), tuple(content.shape)
-        if len(gs) != 2 or len(cs) != 2 or gs[1] != cs[1] or gs[1] % 64:
-            raise ValueError("gesture / content must be (rows, D) with the same D, a multiple of 64")
-        if goh[0] < 0 or coh[0] < 0 or gs[0] < goh[-1] or cs[0] < coh[-1]:
-            raise ValueError("offsets must lie inside gesture / content")
-        a_off = np.zeros(n + 1, np.int64)
-        a_off[1:] = np.cumsum(T * W)
-        self._bind_stream()
-        g, c = self._f32(gesture), self._f32(content)
-        A = torch.empty(int(a_off[-1]), dtype=torch.float32, device=self.device) if want_matrix else None
-        best_frame = torch.full((int(coh[-1]),), -1, dtype=torch.int32, device=self.device)
-        best_score = torch.full((int(coh[-1]),), float("nan"), dtype=torch.float32, device=self.device)
-        if n == 0:
-            return A, a_off, best_frame, best_score
-        go, co = self._i32(goh), self._i32(coh)
-        ao = torch.as_tensor(a_off[:-1].copy(), device=self.device) if want_matrix else None
-        self._ck(self.lib.jg_attn_matrix(self.h, _ptr(g), _ptr(c), _ptr(go), _ptr(co), n, gs[1], int(T.max()), float(temp),
-                                         int(bool(normalize)), _ptr(A), _ptr(ao), _ptr(best_frame), _ptr(best_score)))
-        return A, a_off, best_frame, best_score
-
-    def sync_offset(self, vid, aud, v_offsets, a_offsets, max_shift=15, min_overlap=1, want_curve=True):
-        """jg_sync_offset: per clip the audio-visual offset (frames; d > 0: audio row t + d matches video row t), its confidence
-        (max - median of the curve) and the curve of mean cosines over the shifts -max_shift .. max_shift.  vid (sum Tv, D) / aud (sum Ta, D)
-        rows as stored; v_offsets / a_offsets: n + 1 row offsets each (host arrays or device int32 tensors).
-        Returns device tensors (offset (n,) int32, conf (n,) fp32, curve (n, 2 max_shift + 1) fp32 or None).  A clip with no rows, more than
-        8192 rows, or no shift with min_overlap pairs: offset 0, conf NaN, NaN curve."""
-        R, mo = int(max_shift), int(min_overlap)
-        if not 0 <= R <= 64 or mo < 1:
-            raise ValueError("jg_sync_offset limits: max_shift 0..64, min_overlap >= 1")
-        vs, as_ = tuple(vid.shape), tuple(aud.shape)
-        if len(vs) != 2 or len(as_) != 2 or vs[1] != as_[1] or vs[1] % 64 or not 0 < vs[1] <= 1024:
-            raise ValueError("vid / aud must be (rows, D) with the same D, a multiple of 64, at most 1024")
-        n = int(v_offsets.shape[0] if hasattr(v_offsets, "shape") else len(v_offsets)) - 1
-        n_a = int(a_offsets.shape[0] if hasattr(a_offsets, "shape") else len(a_offsets)) - 1
-        if n < 0 or n_a != n:
-            raise ValueError("v_offsets / a_offsets need the same number of entries (clips + 1)")
-        if not isinstance(v_offsets, torch.Tensor):
-            voh, aoh = np.asarray(v_offsets, np.int64), np.asarray(a_offsets, np.int64)
-            if voh[0] < 0 or aoh[0] < 0 or np.any(np.diff(voh) < 0) or np.any(np.diff(aoh) < 0) or voh[-1] > vs[0] or aoh[-1] > as_[0]:
-                raise ValueError("offsets must ascend and lie inside vid / aud")
-        self._bind_stream()
-        v, a = self._f32(vid), self._f32(aud)
-        vo, ao = self._i32(v_offsets), self._i32(a_offsets)
-        offset = torch.zeros((n,), dtype=torch.int32, device=self.device)
-        conf = torch.full((n,), float("nan"), dtype=torch.float32, device=self.device)
-        curve = torch.full((n, 2 * R + 1), float("nan"), dtype=torch.float32, device=self.device) if want_curve else None
-        if n == 0 or vs[0] == 0 or as_[0] == 0:          # (no rows at all: every clip is outside the limits)
-            return offset, conf, curve
-        self._ck(self.lib.jg_sync_offset(self.h, _ptr(v), _ptr(vo), _ptr(a), _ptr(ao), n, vs[1], R, mo, _ptr(curve), _ptr(offset), _ptr(conf)))
-        return offset, conf, curve
-
-    @staticmethod
-    def sync_window_counts(Tv, win, hop):
-        """windows that cover tracks of Tv rows: Tv <= win ? 1 : ceil((Tv - win) / hop) + 1 (win == 0: one)"""
-        Tv = np.asarray(Tv, np.int64)
-        if not win:
-            return np.ones_like(Tv)
-        return np.where(Tv <= win, 1, -(-(Tv - win) // hop) + 1)
-
-    def sync_offset_windows(self, vid, aud, v_offsets, a_offsets, a_of=None, max_shift=15, min_overlap=1, win=0, hop=1, n_windows=None,
-                            want_curve=True, want_band=False):
-        """jg_sync_offset_windows: the audio-visual offset over time.  Clip i is video track i (rows v_offsets[i] : v_offsets[i + 1] of vid)
-        against audio track a_of[i] (default: i; rows a_offsets[j] : a_offsets[j + 1] of aud; several clips may name one track); all offsets
-        are HOST arrays.  Window j of a clip covers its video rows j hop .. min(j hop + win, Tv) - 1; win == 0: one window over all rows
-        (jg_sync_offset's bits).  Clip i gets n_windows[i] windows (default: the count that covers it, sync_window_counts).
-        Returns (offset, conf, curve | None, w_offsets, band | None): clip i's windows are the rows w_offsets[i] : w_offsets[i + 1] of
-        offset (int32), conf (fp32) and curve (·, 2 max_shift + 1); band (rows of vid, 2 max_shift + 1) holds every cosine (NaN where the
-        audio row does not exist), with want_band; device tensors, w_offsets host int64.  A window that begins behind its track or has no
-        shift with min_overlap pairs: offset 0, conf NaN.  Tracks may have up to 2^20 rows."""
-        R, mo, win, hop = int(max_shift), int(min_overlap), int(win), int(hop)
-        if not 0 <= R <= 64 or mo < 1:
-            raise ValueError("jg_sync_offset_windows limits: max_shift 0..64, min_overlap >= 1")
-        if win < 0 or win >= 2 ** 31 or (win and not 1 <= hop < 2 ** 31):
-            raise ValueError("jg_sync_offset_windows limits: win >= 0 (0: one window over all rows), hop >= 1")
-        vs, as_ = tuple(vid.shape), tuple(aud.shape)
-        if len(vs) != 2 or len(as_) != 2 or vs[1] != as_[1] or vs[1] % 64 or not 0 < vs[1] <= 1024:
-            raise ValueError("vid / aud must be (rows, D) with the same D, a multiple of 64, at most 1024")
-        voh, aoh = (np.asarray(a, np.int64).reshape(-1) for a in (v_offsets, a_offsets))
-        n, n_aud = voh.size - 1, aoh.size - 1
-        if n < 0 or n_aud < 0:
-            raise ValueError("v_offsets / a_offsets need clips + 1 / audio tracks + 1 entries")
-        if a_of is None:
-            if n_aud != n:
-                raise ValueError("without a_of clip i takes audio track i: as many audio tracks as clips")
-            aof = np.arange(n, dtype=np.int64)
-        else:
-            aof = np.asarray(a_of, np.int64).reshape(-1)
-            if aof.size != n or (n and (aof.min() < 0 or aof.max() >= n_aud)):
-                raise ValueError("a_of needs one entry per clip, inside 0 .. audio tracks - 1")
-        Tv, Ta = np.diff(voh), np.diff(aoh)
-        if voh[0] < 0 or aoh[0] < 0 or voh[-1] > vs[0] or aoh[-1] > as_[0] or max(voh[-1], aoh[-1]) >= 2 ** 31:
-            raise ValueError("offsets must lie inside vid / aud (and be int32)")
-        if n and (Tv.min() < 1 or Tv.max() > 2 ** 20 or Ta[aof].min() < 1 or Ta[aof].max() > 2 ** 20):
-            raise ValueError("jg_sync_offset_windows limits: tracks of 1..2^20 rows")
-        if vs[0] * (2 * R + 1) >= 2 ** 40:
-            raise ValueError("jg_sync_offset_windows limits: rows of vid x (2 max_shift + 1) < 2^40")
-        nw = self.sync_window_counts(Tv, win, hop) if n_windows is None else np.asarray(n_windows, np.int64).reshape(-1)
-        if nw.size != n or (n and (nw.min() < 1 or nw.max() > 2 ** 20)):
-            raise ValueError("jg_sync_offset_windows limits: 1..2^20 windows per clip, one count per clip")
-        w_off = np.zeros(n + 1, np.int64)
-        w_off[1:] = np.cumsum(nw)
-        if w_off[-1] >= 2 ** 31:
-            raise ValueError("more than 2^31 windows in one call")
-        self._bind_stream()
-        nwin, W = int(w_off[-1]), 2 * R + 1
-        offset = torch.zeros((nwin,), dtype=torch.int32, device=self.device)
-        conf = torch.full((nwin,), float("nan"), dtype=torch.float32, device=self.device)
-        curve = torch.full((nwin, W), float("nan"), dtype=torch.float32, device=self.device) if want_curve else None
-        band = torch.full((vs[0], W), float("nan"), dtype=torch.float32, device=self.device) if want_band else None
-        if n == 0:
-            return offset, conf, curve, w_off, band
-        v, a = self._f32(vid), self._f32(aud)
-        vo, ao, wo = (self._i32(x) for x in (voh, aoh, w_off))
-        af = None if a_of is None else self._i32(aof)
-        self._ck(self.lib.jg_sync_offset_windows(self.h, _ptr(v), _ptr(vo), n, vs[0], int(max(Tv.max(), Ta[aof].max())), _ptr(a), _ptr(ao),
-                                                 n_aud, _ptr(af), vs[1], R, mo, win, hop, _ptr(wo), int(nw.max()), _ptr(band), _ptr(curve),
-                                                 _ptr(offset), _ptr(conf)))
-        return offset, conf, curve, w_off, band
-
-    def asd(self, query, cand, c_offsets, temp=0.07):
-        qs, cs = _shape(query), _shape(cand)
-        if len(qs) != 2 or len(cs) != 2 or qs[1] != cs[1] or qs[1] < 1:
-            raise ValueError("query / cand must be (rows, D) with the same D")
-        self._check_row_offsets(c_offsets, cs[0], qs[0])
-        self._bind_stream()
-        q, c = self._f32(query), self._f32(cand)
-        co = self._i32(c_offsets)
-        n = q.shape[0]
-        pred = torch.empty((n, 3), dtype=torch.int32, device=self.device)
-        self._ck(self.lib.jg_asd(self.h, _ptr(q), _ptr(c), _ptr(co), n, q.shape[-1], temp, _ptr(pred)))
-        return pred
-
-    def asd_windows(self, gesture, g_offsets, content, c_offsets, trk, s_offsets, win=0, hop=1, n_windows=None, word_start=None,
-                    word_end=None, temp=0.07, want_cos=False):
-        """jg_asd_windows: per scene and time window the probability that each candidate track gestures to the utterance, and the winner.
-        gesture (sum T, D): frame rows of the tracks, g_offsets their n_tracks + 1 row offsets; content (sum W, D): word rows of the scenes'
-        utterances, c_offsets (n + 1); trk / s_offsets (n + 1): scene i's candidates are the tracks trk[s_offsets[i] : s_offsets[i + 1]]; all
-        offsets are HOST arrays.  win == 0: one window per scene over every frame and word (clip-level ASD).  win > 0: window j covers frames
-        j hop .. j hop + win - 1, word_start / word_end (sum W) are the words' inclusive frame bounds, and scene i gets n_windows[i]
-        windows (default: ceil(its longest candidate track / hop)).
-        Returns (prob, p_offsets, pred, w_offsets, cosv | None): scene i's probabilities are prob[p_offsets[i] : p_offsets[i + 1]].reshape(
-        n_win_i, P_i) (cosv likewise, with want_cos), its winners pred[w_offsets[i] : w_offsets[i + 1]]; prob / cosv / pred are device tensors,
-        the offsets host int64.  A window without a word or without a frame of any candidate reads pred -1 and NaN; a candidate without
-        a frame in a decided window prob 0 and cosv NaN."""
-        goh, coh, soh = (np.asarray(a, np.int64).reshape(-1) for a in (g_offsets, c_offsets, s_offsets))
-        tk = np.asarray(trk, np.int64).reshape(-1)
-        n, n_tracks = soh.size - 1, goh.size - 1
-        if n < 0 or n_tracks < 0 or coh.size != n + 1:
-            raise ValueError("c_offsets / s_offsets need the same number of entries (scenes + 1), g_offsets tracks + 1")
-        win, hop = int(win), int(hop)
-        if not 0 <= win <= 8192 or (win and hop < 1):
-            raise ValueError("jg_asd_windows limits: win 0 (clip level) or 1..8192 frames, hop >= 1")
-        if not temp > 0:
-            raise ValueError("temp must be positive")
-        gs, cs = tuple(gesture.shape), tuple(content.shape)
-        if len(gs) != 2 or len(cs) != 2 or gs[1] != cs[1] or gs[1] <= 0 or gs[1] % 64 or gs[1] > 1024:
-            raise ValueError("gesture / content must be (rows, D) with the same D, a positive multiple of 64, at most 1024")
-        T, W, P = np.diff(goh), np.diff(coh), np.diff(soh)
-        if goh[0] < 0 or coh[0] < 0 or soh[0] < 0 or gs[0] < goh[-1] or cs[0] < coh[-1] or tk.size < soh[-1]:
-            raise ValueError("offsets must lie inside gesture / content / trk")
-        if n and (P.min() < 1 or P.max() > 64 or W.min() < 1 or W.max() > 1024):
-            raise ValueError("jg_asd_windows limits: 1..64 candidates and 1..1024 words per scene")
-        used = tk[soh[0]:soh[-1]]
-        if used.size and (used.min() < 0 or used.max() >= n_tracks or T[used].min() < 1 or T[used].max() > 8192):
-            raise ValueError("jg_asd_windows limits: candidates must be existing tracks of 1..8192 frames")
-        if win:
-            if word_start is None or word_end is None:
-                raise ValueError("windows need word_start / word_end")
-            wsh, weh = (np.asarray(a, np.int64).reshape(-1) for a in (word_start, word_end))
-            if wsh.size < coh[-1] or weh.size != wsh.size or (n and max(np.abs(wsh).max(), np.abs(weh).max()) >= 2 ** 31):
-                raise ValueError("word_start / word_end need one int32 entry per content row")
-            if n_windows is None:
-                n_windows = [-(-int(T[tk[soh[i]:soh[i + 1]]].max()) // hop) for i in range(n)]
-        elif n_windows is None:
-            n_windows = np.ones(n, np.int64)
-        nw = np.asarray(n_windows, np.int64).reshape(-1)
-        if nw.size != n or (n and (nw.min() < 1 or nw.max() > 8192)):
-            raise ValueError("jg_asd_windows limits: 1..8192 windows per scene, one count per scene")
-        w_off, p_off = np.zeros(n + 1, np.int64), np.zeros(n + 1, np.int64)
-        w_off[1:], p_off[1:] = np.cumsum(nw), np.cumsum(nw * P)
-        if w_off[-1] >= 2 ** 31:
-            raise ValueError("more than 2^31 windows in one call")
-        self._bind_stream()
-        prob = torch.full((int(p_off[-1]),), float("nan"), dtype=torch.float32, device=self.device)
-        cosv = torch.full((int(p_off[-1]),), float("nan"), dtype=torch.float32, device=self.device) if want_cos else None
-        pred = torch.full((int(w_off[-1]),), -1, dtype=torch.int32, device=self.device)
-        if n == 0:
-            return prob, p_off, pred, w_off, cosv
-        g, c = self._f32(gesture), self._f32(content)
-        go, co, so, tr, wo = (self._i32(a) for a in (goh, coh, soh, tk, w_off))
-        ws = self._i32(wsh) if win else None
-        we = self._i32(weh) if win else None
-        po = torch.as_tensor(p_off[:-1].copy(), device=self.device)
-        self._ck(self.lib.jg_asd_windows(self.h, _ptr(g), _ptr(go), n_tracks, _ptr(c), _ptr(co), _ptr(ws), _ptr(we), _ptr(tr), _ptr(so), n,
-                                         gs[1], win, hop, _ptr(wo), _ptr(po), int(nw.max()), float(temp), _ptr(prob), _ptr(cosv), _ptr(pred)))
-        return prob, p_off, pred, w_off, cosv
 
     # ---- profiling
     # ---- multi-GPU exchange on RCCL through the C ABI (jegal_amd/dist.py uses torch.distributed for the same exchange)

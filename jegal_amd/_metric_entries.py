@@ -1,0 +1,360 @@
+"""The metric entries of the engine (jg_pool_mean .. jg_asd_windows) as a class that Engine (_lib.py) inherits from, with the one set of
+argument rules they share.  Every check comes before the wrapper touches its handle or the device."""
+import ctypes
+
+import numpy as np
+import torch
+
+# The limits the C entries refuse on, named as in csrc/shared.h (tests/test_metric_entries_cpu.py keeps the two equal).
+SIM_TOPK_MAX_K = 128
+SPOT_MAX_W, SPOT_MAX_T = 1024, 8192
+SYNC_MAX_R, SYNC_MAX_T, SYNC_MAX_D = 64, 8192, 1024
+SYNCW_MAX_T, SYNCW_MAX_WINDOWS, SYNCW_MAX_BAND_LOG2 = 1 << 20, 1 << 20, 40
+ASDW_MAX_D, ASDW_MAX_P, ASDW_MAX_WIN = 1024, 64, 8192
+LIMITS = {k: v for k, v in globals().items() if k.isupper()}
+INT32_MAX = 2 ** 31 - 1
+
+
+def _ptr(t):
+    return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def _shape(x):
+    """The shape of a tensor, an array or nested lists, without moving anything."""
+    return tuple(x.shape) if hasattr(x, "shape") else np.shape(x)
+
+
+def _row_pair(a, b, names, multiple=64, max_D=None):
+    """Two (rows, D) operands with the same D >= 1, a multiple of `multiple` and at most max_D -> their shapes."""
+    sa, sb = _shape(a), _shape(b)
+    if len(sa) != 2 or len(sb) != 2 or sa[1] != sb[1] or sa[1] < 1 or sa[1] % multiple or (max_D and sa[1] > max_D):
+        raise ValueError(f"{names} must be (rows, D) with the same D" + (f", a positive multiple of {multiple}" if multiple > 1 else "")
+                         + (f", at most {max_D}" if max_D else ""))
+    return sa, sb
+
+
+def _offsets(offsets, rows, name, n=None, host=True):
+    """Row offsets of `name` -> int64 host array: 1-d integers, n + 1 entries when the caller knows n, a non-decreasing partition inside
+    0 .. rows (rows None: any end), int32 range.  host=False: the entry also takes a tensor, whose values are not read (no sync): only its
+    shape and type are looked at, as the C entry takes it, and it comes back as it is.  Blocks = len(result) - 1."""
+    dev = not host and isinstance(offsets, torch.Tensor)
+    off = offsets if dev else np.asarray(offsets)
+    if off.ndim != 1 or len(off) < 1 or not (off.dtype in (torch.int32, torch.int64) if dev else np.issubdtype(off.dtype, np.integer)):
+        raise ValueError(f"{name} must be 1-d integers, blocks + 1 entries")
+    if n is not None and len(off) != n + 1:
+        raise ValueError(f"{name} needs {n + 1} entries (blocks + 1), not {len(off)}")
+    if dev:
+        return off
+    off = off.astype(np.int64)
+    if off[0] < 0 or off[-1] > (INT32_MAX if rows is None else min(rows, INT32_MAX)) or np.any(np.diff(off) < 0):
+        raise ValueError(f"{name} must be non-decreasing and lie inside 0 .. rows (int32)")
+    return off
+
+
+def _within(lens, lo, hi, what):
+    """Block lengths (or counts), each within lo .. hi -> the same."""
+    if lens.size and (lens.min() < lo or lens.max() > hi):
+        raise ValueError(f"{what}: {lo}..{hi} each")
+    return lens
+
+
+def _ragged(counts, what=None):
+    """Counts -> the int64 offsets of their ragged blocks (one entry more); with `what` (the device takes them as int32): int32 range."""
+    off = np.zeros(len(counts) + 1, np.int64)
+    off[1:] = np.cumsum(counts)
+    if what and off[-1] > INT32_MAX:
+        raise ValueError(f"more than 2^31 {what} in one call")
+    return off
+
+
+def _ints(a):
+    return np.asarray(a, np.int64).reshape(-1)
+
+
+class MetricEntries:
+    """Engine's metric methods.  Uses Engine's handle (lib, h, device) and helpers (_ck, _bind_stream, _f32, _i32)."""
+
+    def pool_mean(self, x, offsets):
+        xs = _shape(x)
+        if len(xs) != 2 or xs[1] < 1:
+            raise ValueError("x must be (rows, D)")
+        n = len(_offsets(offsets, xs[0], "offsets", host=False)) - 1
+        self._bind_stream()
+        x, off = self._f32(x), self._i32(offsets)
+        out = torch.empty((n, x.shape[-1]), dtype=torch.float32, device=self.device)
+        self._ck(self.lib.jg_pool_mean(self.h, _ptr(x), _ptr(off), n, x.shape[-1], _ptr(out)))
+        return out
+
+    def sim_rank(self, e1, e2, row_offset=0):
+        s1, s2 = _row_pair(e1, e2, "e1 / e2")
+        row_offset = int(row_offset)
+        if row_offset < 0 or row_offset + s1[0] > s2[0]:
+            raise ValueError("row_offset must be >= 0 and row_offset + rows of e1 <= rows of e2")
+        self._bind_stream()
+        e1, e2 = self._f32(e1), self._f32(e2)
+        n_local, D = e1.shape
+        rank, ties = (torch.empty(n_local, dtype=torch.int32, device=self.device) for _ in range(2))
+        self._ck(self.lib.jg_sim_rank(self.h, _ptr(e1), _ptr(e2), n_local, e2.shape[0], row_offset, D, _ptr(rank), _ptr(ties)))
+        return rank, ties
+
+    def _sim_topk_args(self, entry, queries, gallery, k, gallery_offset, merge_into, g_offsets=None):
+        """What sim_topk and sim_topk_grouped (`entry`; the latter passes g_offsets) share: the checks of the shapes, k, gallery_offset,
+        the group offsets and merge_into, then the stream, and the result to fill: merge_into's pair, or an empty one (-1 / -inf).
+        Returns (rows of queries, rows of gallery, D, k, gallery_offset, groups or None, idx, score)."""
+        qs, gs = _row_pair(queries, gallery, "queries / gallery")
+        k, gallery_offset = int(k), int(gallery_offset)
+        if not 1 <= k <= SIM_TOPK_MAX_K:
+            raise ValueError(f"jg_{entry} limit: 1 <= k <= {SIM_TOPK_MAX_K}")
+        if gallery_offset < 0 or gallery_offset + gs[0] > INT32_MAX:
+            raise ValueError("gallery_offset must be >= 0 and gallery_offset + gallery rows <= INT32_MAX")
+        n_groups = None if g_offsets is None else len(_offsets(g_offsets, gs[0], "g_offsets", host=False)) - 1
+        if merge_into is not None:
+            if not isinstance(merge_into, (tuple, list)) or len(merge_into) != 2 or not all(isinstance(t, torch.Tensor) for t in merge_into):
+                raise ValueError(f"merge_into must be the (idx, score) pair of an earlier {entry} call")
+            idx, score = merge_into
+            if (tuple(idx.shape) != (qs[0], k) or tuple(score.shape) != (qs[0], k) or idx.dtype != torch.int32 or score.dtype != torch.float32
+                    or not idx.is_contiguous() or not score.is_contiguous()):
+                raise ValueError(f"merge_into must be contiguous (idx int32, score float32) tensors of shape ({qs[0]}, {k})")
+            if idx.device != self.device or score.device != self.device:
+                raise ValueError(f"merge_into must be on {self.device}")
+        self._bind_stream()
+        if merge_into is None:
+            idx = torch.full((qs[0], k), -1, dtype=torch.int32, device=self.device)
+            score = torch.full((qs[0], k), float("-inf"), dtype=torch.float32, device=self.device)
+        return qs[0], gs[0], qs[1], k, gallery_offset, n_groups, idx, score
+
+    def sim_topk(self, queries, gallery, k, gallery_offset=0, merge_into=None):
+        """jg_sim_topk: per query row the k gallery rows with the largest <q_i, g_j> (rows as stored: normalise first, as for sim_rank), best
+        first; on equal scores the smaller gallery row first.  queries (n, D) / gallery (m, D), D % 64 == 0, 1 <= k <= 128.
+        Returns (idx (n, k) int32 = gallery_offset + j, score (n, k) float32) as device tensors; slots beyond the candidates are -1 / -inf.
+        merge_into = (idx, score) of an earlier call with the same queries and k on OTHER gallery rows: the two are updated in place to the
+        best k of the union and returned (a gallery too large for the device goes through in pieces, each with its gallery_offset)."""
+        n, m, D, k, gallery_offset, _, idx, score = self._sim_topk_args("sim_topk", queries, gallery, k, gallery_offset, merge_into)
+        q, g = self._f32(queries), self._f32(gallery)
+        if n and m:                                    # (no gallery row: nothing to merge, or the empty result)
+            self._ck(self.lib.jg_sim_topk(self.h, _ptr(q), _ptr(g), n, m, D, k, gallery_offset, int(merge_into is not None), _ptr(idx), _ptr(score)))
+        return idx, score
+
+    def sim_topk_grouped(self, queries, gallery, g_offsets, k, gallery_offset=0, merge_into=None):
+        """jg_sim_topk_grouped: the gallery rows are cut into contiguous groups (group i = rows g_offsets[i] .. g_offsets[i + 1] - 1 of
+        `gallery`; a host array or a tensor of groups + 1 entries), a group scores as its best row, and per query row the k best groups come
+        back, each as the row that earned the score: (idx (n, k) int32 = gallery_offset + row, score (n, k) float32), device tensors, best
+        first, on equal scores the smaller row; never two rows of one group; -1 / -inf where fewer than k groups have a row.  Scores are
+        those of sim_topk / sim_rank bit for bit.  merge_into = (idx, score) of an earlier call with the same queries and k on OTHER
+        gallery rows, cut at group boundaries: updated in place to the best k of the union and returned."""
+        n, m, D, k, gallery_offset, n_groups, idx, score = self._sim_topk_args("sim_topk_grouped", queries, gallery, k, gallery_offset,
+                                                                               merge_into, g_offsets)
+        q, g, off = self._f32(queries), self._f32(gallery), self._i32(g_offsets)
+        if n and m and n_groups:                       # (no gallery row, no group: nothing to merge, or the empty result)
+            self._ck(self.lib.jg_sim_topk_grouped(self.h, _ptr(q), _ptr(g), n, m, D, k, _ptr(off), n_groups, gallery_offset,
+                                                  int(merge_into is not None), _ptr(idx), _ptr(score)))
+        return idx, score
+
+    def group_of_rows(self, idx, g_offsets, gallery_offset=0):
+        """jg_group_of_rows: the rows sim_topk_grouped returned (an int32 tensor of any shape) -> (grp, pos) int32 device tensors of that
+        shape: the group whose range holds idx - gallery_offset and the row's place inside it; -1 / -1 for idx < 0 or a row in no group.
+        After merged calls: the offsets of the whole gallery with gallery_offset = 0."""
+        if not isinstance(idx, torch.Tensor) or idx.dtype != torch.int32:
+            raise ValueError("idx must be an int32 tensor (the idx of sim_topk_grouped)")
+        gallery_offset = int(gallery_offset)
+        if not 0 <= gallery_offset <= INT32_MAX:
+            raise ValueError("gallery_offset must be 0 .. INT32_MAX")
+        n_groups = len(_offsets(g_offsets, None, "g_offsets", host=False)) - 1
+        self._bind_stream()
+        rows, off = self._i32(idx), self._i32(g_offsets)
+        grp, pos = torch.full_like(rows, -1), torch.full_like(rows, -1)
+        if rows.numel():
+            self._ck(self.lib.jg_group_of_rows(self.h, _ptr(rows), rows.numel(), _ptr(off), n_groups, gallery_offset, _ptr(grp), _ptr(pos)))
+        return grp, pos
+
+    def spot(self, gesture, content, g_offsets, c_offsets, targets, temp=0.07):
+        gs, cs = _row_pair(gesture, content, "gesture / content", multiple=1)
+        tgh = _ints(targets)
+        n = tgh.size
+        goh, coh = _offsets(g_offsets, gs[0], "g_offsets", n), _offsets(c_offsets, cs[0], "c_offsets", n)
+        _within(np.diff(goh), 1, SPOT_MAX_T, "jg_spot limits: frames per clip")
+        W = _within(np.diff(coh), 1, SPOT_MAX_W, "jg_spot limits: words per clip")
+        if (tgh < 0).any() or (tgh >= W).any():
+            raise ValueError("jg_spot limits: 0 <= target < words")
+        self._bind_stream()
+        g, c = self._f32(gesture), self._f32(content)
+        go, co, tg = self._i32(goh), self._i32(coh), self._i32(tgh)
+        pred = torch.empty(n, dtype=torch.int32, device=self.device)
+        score = torch.empty(n, dtype=torch.float32, device=self.device)
+        self._ck(self.lib.jg_spot(self.h, _ptr(g), _ptr(c), _ptr(go), _ptr(co), _ptr(tg), n, gs[1], temp, _ptr(pred), _ptr(score)))
+        return pred, score
+
+    def attn_matrix(self, gesture, content, g_offsets, c_offsets, temp=0.07, normalize=True, want_matrix=True):
+        """jg_attn_matrix: per clip A_i = softmax((G_i C_i^T) / temp, dim=1)^T (W_i, T_i) and, for every word, its first arg-max frame and
+        that probability.  gesture (sum T, D) / content (sum W, D); g_offsets / c_offsets: HOST arrays of n + 1 entries.
+        Returns (A_flat | None, a_offsets, best_frame, best_score): clip i's matrix is A_flat[a_offsets[i] : a_offsets[i + 1]].reshape(W_i, T_i)
+        (a_offsets: host int64, n + 1 entries), best_* are device tensors indexed like content's rows (c_offsets[-1] entries: clip i's words
+        are best_*[c_offsets[i] : c_offsets[i + 1]]; entries no clip covers are -1 / NaN).  want_matrix=False: no matrix is written."""
+        gs, cs = _row_pair(gesture, content, "gesture / content")
+        goh = _offsets(g_offsets, gs[0], "g_offsets")
+        n = goh.size - 1
+        coh = _offsets(c_offsets, cs[0], "c_offsets", n)
+        T = _within(np.diff(goh), 1, SPOT_MAX_T, "jg_attn_matrix limits: frames per clip")
+        W = _within(np.diff(coh), 1, SPOT_MAX_W, "jg_attn_matrix limits: words per clip")
+        if not temp > 0:
+            raise ValueError("temp must be positive")
+        a_off = _ragged(T * W)
+        self._bind_stream()
+        g, c = self._f32(gesture), self._f32(content)
+        A = torch.empty(int(a_off[-1]), dtype=torch.float32, device=self.device) if want_matrix else None
+        best_frame = torch.full((int(coh[-1]),), -1, dtype=torch.int32, device=self.device)
+        best_score = torch.full((int(coh[-1]),), float("nan"), dtype=torch.float32, device=self.device)
+        if n == 0:
+            return A, a_off, best_frame, best_score
+        go, co = self._i32(goh), self._i32(coh)
+        ao = torch.as_tensor(a_off[:-1].copy(), device=self.device) if want_matrix else None
+        self._ck(self.lib.jg_attn_matrix(self.h, _ptr(g), _ptr(c), _ptr(go), _ptr(co), n, gs[1], int(T.max()), float(temp),
+                                         int(bool(normalize)), _ptr(A), _ptr(ao), _ptr(best_frame), _ptr(best_score)))
+        return A, a_off, best_frame, best_score
+
+    def sync_offset(self, vid, aud, v_offsets, a_offsets, max_shift=15, min_overlap=1, want_curve=True):
+        """jg_sync_offset: per clip the audio-visual offset (frames; d > 0: audio row t + d matches video row t), its confidence
+        (max - median of the curve) and the curve of mean cosines over the shifts -max_shift .. max_shift.  vid (sum Tv, D) / aud (sum Ta, D)
+        rows as stored; v_offsets / a_offsets: n + 1 row offsets each (host arrays or device int32 tensors).
+        Returns device tensors (offset (n,) int32, conf (n,) fp32, curve (n, 2 max_shift + 1) fp32 or None).  A clip with no rows, more than
+        8192 rows, or no shift with min_overlap pairs: offset 0, conf NaN, NaN curve."""
+        R, mo = int(max_shift), int(min_overlap)
+        if not 0 <= R <= SYNC_MAX_R or mo < 1:
+            raise ValueError(f"jg_sync_offset limits: max_shift 0..{SYNC_MAX_R}, min_overlap >= 1")
+        vs, as_ = _row_pair(vid, aud, "vid / aud", max_D=SYNC_MAX_D)
+        n = len(_offsets(v_offsets, vs[0], "v_offsets", host=False)) - 1
+        _offsets(a_offsets, as_[0], "a_offsets", n, host=False)
+        self._bind_stream()
+        v, a = self._f32(vid), self._f32(aud)
+        vo, ao = self._i32(v_offsets), self._i32(a_offsets)
+        offset = torch.zeros((n,), dtype=torch.int32, device=self.device)
+        conf = torch.full((n,), float("nan"), dtype=torch.float32, device=self.device)
+        curve = torch.full((n, 2 * R + 1), float("nan"), dtype=torch.float32, device=self.device) if want_curve else None
+        if n == 0 or vs[0] == 0 or as_[0] == 0:          # (no rows at all: every clip is outside the limits)
+            return offset, conf, curve
+        self._ck(self.lib.jg_sync_offset(self.h, _ptr(v), _ptr(vo), _ptr(a), _ptr(ao), n, vs[1], R, mo, _ptr(curve), _ptr(offset), _ptr(conf)))
+        return offset, conf, curve
+
+    @staticmethod
+    def sync_window_counts(Tv, win, hop):
+        """windows that cover tracks of Tv rows: Tv <= win ? 1 : ceil((Tv - win) / hop) + 1 (win == 0: one)"""
+        Tv = np.asarray(Tv, np.int64)
+        if not win:
+            return np.ones_like(Tv)
+        return np.where(Tv <= win, 1, -(-(Tv - win) // hop) + 1)
+
+    def sync_offset_windows(self, vid, aud, v_offsets, a_offsets, a_of=None, max_shift=15, min_overlap=1, win=0, hop=1, n_windows=None,
+                            want_curve=True, want_band=False):
+        """jg_sync_offset_windows: the audio-visual offset over time.  Clip i is video track i (rows v_offsets[i] : v_offsets[i + 1] of vid)
+        against audio track a_of[i] (default: i; rows a_offsets[j] : a_offsets[j + 1] of aud; several clips may name one track); all offsets
+        are HOST arrays.  Window j of a clip covers its video rows j hop .. min(j hop + win, Tv) - 1; win == 0: one window over all rows
+        (jg_sync_offset's bits).  Clip i gets n_windows[i] windows (default: the count that covers it, sync_window_counts).
+        Returns (offset, conf, curve | None, w_offsets, band | None): clip i's windows are the rows w_offsets[i] : w_offsets[i + 1] of
+        offset (int32), conf (fp32) and curve (·, 2 max_shift + 1); band (rows of vid, 2 max_shift + 1) holds every cosine (NaN where the
+        audio row does not exist), with want_band; device tensors, w_offsets host int64.  A window that begins behind its track or has no
+        shift with min_overlap pairs: offset 0, conf NaN.  Tracks may have up to 2^20 rows."""
+        R, mo, win, hop = int(max_shift), int(min_overlap), int(win), int(hop)
+        if not 0 <= R <= SYNC_MAX_R or mo < 1:
+            raise ValueError(f"jg_sync_offset_windows limits: max_shift 0..{SYNC_MAX_R}, min_overlap >= 1")
+        if not 0 <= win <= INT32_MAX or (win and not 1 <= hop <= INT32_MAX):
+            raise ValueError("jg_sync_offset_windows limits: win >= 0 (0: one window over all rows), hop >= 1")
+        vs, as_ = _row_pair(vid, aud, "vid / aud", max_D=SYNC_MAX_D)
+        voh, aoh = _offsets(v_offsets, vs[0], "v_offsets"), _offsets(a_offsets, as_[0], "a_offsets")
+        n, n_aud = voh.size - 1, aoh.size - 1
+        if a_of is None:
+            if n_aud != n:
+                raise ValueError("without a_of clip i takes audio track i: as many audio tracks as clips")
+            aof = np.arange(n, dtype=np.int64)
+        else:
+            aof = _ints(a_of)
+            if aof.size != n or (n and (aof.min() < 0 or aof.max() >= n_aud)):
+                raise ValueError("a_of needs one entry per clip, inside 0 .. audio tracks - 1")
+        Tv = _within(np.diff(voh), 1, SYNCW_MAX_T, "jg_sync_offset_windows limits: rows per video track")
+        Ta = _within(np.diff(aoh)[aof], 1, SYNCW_MAX_T, "jg_sync_offset_windows limits: rows per audio track of a clip")
+        if vs[0] * (2 * R + 1) >= 2 ** SYNCW_MAX_BAND_LOG2:
+            raise ValueError(f"jg_sync_offset_windows limits: rows of vid x (2 max_shift + 1) < 2^{SYNCW_MAX_BAND_LOG2}")
+        nw = self.sync_window_counts(Tv, win, hop) if n_windows is None else _ints(n_windows)
+        if nw.size != n or (n and (nw.min() < 1 or nw.max() > SYNCW_MAX_WINDOWS)):
+            raise ValueError(f"jg_sync_offset_windows limits: 1..{SYNCW_MAX_WINDOWS} windows per clip, one count per clip")
+        w_off = _ragged(nw, "windows")
+        self._bind_stream()
+        nwin, W = int(w_off[-1]), 2 * R + 1
+        offset = torch.zeros((nwin,), dtype=torch.int32, device=self.device)
+        conf = torch.full((nwin,), float("nan"), dtype=torch.float32, device=self.device)
+        curve = torch.full((nwin, W), float("nan"), dtype=torch.float32, device=self.device) if want_curve else None
+        band = torch.full((vs[0], W), float("nan"), dtype=torch.float32, device=self.device) if want_band else None
+        if n == 0:
+            return offset, conf, curve, w_off, band
+        v, a = self._f32(vid), self._f32(aud)
+        vo, ao, wo = (self._i32(x) for x in (voh, aoh, w_off))
+        af = None if a_of is None else self._i32(aof)
+        self._ck(self.lib.jg_sync_offset_windows(self.h, _ptr(v), _ptr(vo), n, vs[0], int(max(Tv.max(), Ta.max())), _ptr(a), _ptr(ao),
+                                                 n_aud, _ptr(af), vs[1], R, mo, win, hop, _ptr(wo), int(nw.max()), _ptr(band), _ptr(curve),
+                                                 _ptr(offset), _ptr(conf)))
+        return offset, conf, curve, w_off, band
+
+    def asd(self, query, cand, c_offsets, temp=0.07):
+        qs, cs = _row_pair(query, cand, "query / cand", multiple=1)
+        _offsets(c_offsets, cs[0], "c_offsets", qs[0], host=False)
+        self._bind_stream()
+        q, c, co = self._f32(query), self._f32(cand), self._i32(c_offsets)
+        n = q.shape[0]
+        pred = torch.empty((n, 3), dtype=torch.int32, device=self.device)
+        self._ck(self.lib.jg_asd(self.h, _ptr(q), _ptr(c), _ptr(co), n, q.shape[-1], temp, _ptr(pred)))
+        return pred
+
+    def asd_windows(self, gesture, g_offsets, content, c_offsets, trk, s_offsets, win=0, hop=1, n_windows=None, word_start=None,
+                    word_end=None, temp=0.07, want_cos=False):
+        """jg_asd_windows: per scene and time window the probability that each candidate track gestures to the utterance, and the winner.
+        gesture (sum T, D): frame rows of the tracks, g_offsets their n_tracks + 1 row offsets; content (sum W, D): word rows of the scenes'
+        utterances, c_offsets (n + 1); trk / s_offsets (n + 1): scene i's candidates are the tracks trk[s_offsets[i] : s_offsets[i + 1]]; all
+        offsets are HOST arrays.  win == 0: one window per scene over every frame and word (clip-level ASD).  win > 0: window j covers frames
+        j hop .. j hop + win - 1, word_start / word_end (sum W) are the words' inclusive frame bounds, and scene i gets n_windows[i]
+        windows (default: ceil(its longest candidate track / hop)).
+        Returns (prob, p_offsets, pred, w_offsets, cosv | None): scene i's probabilities are prob[p_offsets[i] : p_offsets[i + 1]].reshape(
+        n_win_i, P_i) (cosv likewise, with want_cos), its winners pred[w_offsets[i] : w_offsets[i + 1]]; prob / cosv / pred are device tensors,
+        the offsets host int64.  A window without a word or without a frame of any candidate reads pred -1 and NaN; a candidate without
+        a frame in a decided window prob 0 and cosv NaN."""
+        win, hop = int(win), int(hop)
+        if not 0 <= win <= ASDW_MAX_WIN or (win and hop < 1):
+            raise ValueError(f"jg_asd_windows limits: win 0 (clip level) or 1..{ASDW_MAX_WIN} frames, hop >= 1")
+        if not temp > 0:
+            raise ValueError("temp must be positive")
+        gs, cs = _row_pair(gesture, content, "gesture / content", max_D=ASDW_MAX_D)
+        tk = _ints(trk)
+        goh, soh = _offsets(g_offsets, gs[0], "g_offsets"), _offsets(s_offsets, tk.size, "s_offsets")
+        n, n_tracks = soh.size - 1, goh.size - 1
+        coh = _offsets(c_offsets, cs[0], "c_offsets", n)
+        T = np.diff(goh)
+        P = _within(np.diff(soh), 1, ASDW_MAX_P, "jg_asd_windows limits: candidates per scene")
+        _within(np.diff(coh), 1, SPOT_MAX_W, "jg_asd_windows limits: words per scene")
+        used = tk[soh[0]:soh[-1]]
+        if used.size and (used.min() < 0 or used.max() >= n_tracks or T[used].min() < 1 or T[used].max() > SPOT_MAX_T):
+            raise ValueError(f"jg_asd_windows limits: candidates must be existing tracks of 1..{SPOT_MAX_T} frames")
+        if win:
+            if word_start is None or word_end is None:
+                raise ValueError("windows need word_start / word_end")
+            wsh, weh = _ints(word_start), _ints(word_end)
+            if wsh.size < coh[-1] or weh.size != wsh.size or (n and max(np.abs(wsh).max(), np.abs(weh).max()) > INT32_MAX):
+                raise ValueError("word_start / word_end need one int32 entry per content row")
+            if n_windows is None:
+                n_windows = [-(-int(T[tk[soh[i]:soh[i + 1]]].max()) // hop) for i in range(n)]
+        elif n_windows is None:
+            n_windows = np.ones(n, np.int64)
+        nw = _ints(n_windows)
+        if nw.size != n or (n and (nw.min() < 1 or nw.max() > ASDW_MAX_WIN)):
+            raise ValueError(f"jg_asd_windows limits: 1..{ASDW_MAX_WIN} windows per scene, one count per scene")
+        w_off, p_off = _ragged(nw, "windows"), _ragged(nw * P)
+        self._bind_stream()
+        prob = torch.full((int(p_off[-1]),), float("nan"), dtype=torch.float32, device=self.device)
+        cosv = torch.full((int(p_off[-1]),), float("nan"), dtype=torch.float32, device=self.device) if want_cos else None
+        pred = torch.full((int(w_off[-1]),), -1, dtype=torch.int32, device=self.device)
+        if n == 0:
+            return prob, p_off, pred, w_off, cosv
+        g, c = self._f32(gesture), self._f32(content)
+        go, co, so, tr, wo = (self._i32(a) for a in (goh, coh, soh, tk, w_off))
+        ws, we = (self._i32(wsh), self._i32(weh)) if win else (None, None)
+        po = torch.as_tensor(p_off[:-1].copy(), device=self.device)
+        self._ck(self.lib.jg_asd_windows(self.h, _ptr(g), _ptr(go), n_tracks, _ptr(c), _ptr(co), _ptr(ws), _ptr(we), _ptr(tr), _ptr(so), n,
+                                         gs[1], win, hop, _ptr(wo), _ptr(po), int(nw.max()), float(temp), _ptr(prob), _ptr(cosv), _ptr(pred)))
+        return prob, p_off, pred, w_off, cosv

@@ -128,6 +128,10 @@ int engine::upload_i32_async(jg_handle* h, const int32_t* src, size_t n, int32_t
     return JG_OK;
 }
 
+// what a metric entry ends in: one launch on the handle's stream, timed as the MISC stage -- launcher(args..., h->stream)
+template <class F, class... A>
+static int misc_launch(jg_handle* h, F launcher, A... args) { return timed(h, JG_ST_MISC, [&] { return launcher(args..., h->stream); }); }
+
 // ======================================================================================= C ABI
 extern "C" {
 
@@ -525,10 +529,11 @@ int jg_extract_gesture(jg_handle* h, const void* frames, int dtype, int B, int T
     return run_in_lanes(h, B, T, run_part);
 }
 
+// ---- the metric entries
 int jg_pool_mean(jg_handle* h, const float* x, const int32_t* off, int n, int D, float* out) {
     ENTER(h);
     if (!x || !off || !out) JG_FAIL(h, JG_ERR_ARG, "null buffer");
-    return timed(h, JG_ST_MISC, [&] { return launch_ragged_mean(x, off, n, D, out, h->stream); });
+    return misc_launch(h, launch_ragged_mean, x, off, n, D, out);
 }
 
 int jg_sim_rank(jg_handle* h, const float* e1, const float* e2, int n_local, int n_total, int row_offset, int D,
@@ -536,18 +541,29 @@ int jg_sim_rank(jg_handle* h, const float* e1, const float* e2, int n_local, int
     ENTER(h);
     if (!e1 || !e2 || !rank || !ties) JG_FAIL(h, JG_ERR_ARG, "null buffer");
     if (D % 64 || row_offset < 0 || row_offset + n_local > n_total) JG_FAIL(h, JG_ERR_ARG, "bad sim_rank geometry");
-    return timed(h, JG_ST_MISC, [&] { return launch_sim_rank(e1, e2, n_local, n_total, row_offset, D, rank, ties, h->stream); });
+    return misc_launch(h, launch_sim_rank, e1, e2, n_local, n_total, row_offset, D, rank, ties);
 }
 
+// The checks that several entries make, each written once.  Two row operands (`names` for the message): D a positive multiple of 64, at
+// most max_D where the entry has a maximum (0: none), both 16-byte aligned
+static int row_pair_check(jg_handle* h, const char* names, const float* a, const float* b, int D, int max_D = 0) {
+    if (max_D && (D <= 0 || D % 64 || D > max_D)) JG_FAIL(h, JG_ERR_ARG, "D must be a positive multiple of 64, at most %d", max_D);
+    if (D <= 0 || D % 64) JG_FAIL(h, JG_ERR_ARG, "D must be a positive multiple of 64");
+    if ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15) JG_FAIL(h, JG_ERR_ARG, "%s must be 16-byte aligned", names);
+    return JG_OK;
+}
+static int shift_check(jg_handle* h, int max_shift, int min_overlap) {
+    if (max_shift < 0 || max_shift > SYNC_MAX_R) JG_FAIL(h, JG_ERR_ARG, "max_shift must be 0..%d", SYNC_MAX_R);
+    if (min_overlap < 1) JG_FAIL(h, JG_ERR_ARG, "min_overlap must be >= 1");
+    return JG_OK;
+}
 // the arguments jg_sim_topk and jg_sim_topk_grouped share (`entry` names the caller in the geometry message; n_groups: 0 for the former)
 static int sim_topk_check(jg_handle* h, const char* entry, const float* queries, const float* gallery, int n_queries, int n_gallery, int D,
                           int k, int n_groups, int gallery_offset) {
     if (k < 1 || k > SIM_TOPK_MAX_K) JG_FAIL(h, JG_ERR_ARG, "k must be 1..%d", SIM_TOPK_MAX_K);
-    if (D <= 0 || D % 64) JG_FAIL(h, JG_ERR_ARG, "D must be a positive multiple of 64");
     if (n_queries < 0 || n_gallery < 0 || n_groups < 0 || gallery_offset < 0 || gallery_offset > INT32_MAX - n_gallery)
         JG_FAIL(h, JG_ERR_ARG, "bad %s geometry (counts and gallery_offset >= 0, gallery_offset + n_gallery <= INT32_MAX)", entry);
-    if ((reinterpret_cast<uintptr_t>(queries) | reinterpret_cast<uintptr_t>(gallery)) & 15) JG_FAIL(h, JG_ERR_ARG, "queries / gallery must be 16-byte aligned");
-    return JG_OK;
+    return row_pair_check(h, "queries / gallery", queries, gallery, D);
 }
 
 int jg_sim_topk(jg_handle* h, const float* queries, const float* gallery, int n_queries, int n_gallery, int D, int k,
@@ -556,9 +572,7 @@ int jg_sim_topk(jg_handle* h, const float* queries, const float* gallery, int n_
     if (!queries || !gallery || !idx || !score) JG_FAIL(h, JG_ERR_ARG, "null buffer");
     RET(sim_topk_check(h, "sim_topk", queries, gallery, n_queries, n_gallery, D, k, 0, gallery_offset));
     if (n_queries == 0) return JG_OK;
-    return timed(h, JG_ST_MISC, [&] {
-        return launch_sim_topk(queries, gallery, n_queries, n_gallery, D, k, gallery_offset, merge, idx, score, h->stream);
-    });
+    return misc_launch(h, launch_sim_topk, queries, gallery, n_queries, n_gallery, D, k, gallery_offset, merge, idx, score);
 }
 
 int jg_sim_topk_grouped(jg_handle* h, const float* queries, const float* gallery, int n_queries, int n_gallery, int D, int k,
@@ -567,10 +581,8 @@ int jg_sim_topk_grouped(jg_handle* h, const float* queries, const float* gallery
     if (!queries || !gallery || !idx || !score || (n_groups > 0 && !g_offsets)) JG_FAIL(h, JG_ERR_ARG, "null buffer");
     RET(sim_topk_check(h, "sim_topk_grouped", queries, gallery, n_queries, n_gallery, D, k, n_groups, gallery_offset));
     if (n_queries == 0) return JG_OK;
-    return timed(h, JG_ST_MISC, [&] {
-        return launch_sim_topk_grouped(queries, gallery, n_queries, n_gallery, D, k, g_offsets, n_groups, gallery_offset, merge, idx, score,
-                                       h->stream);
-    });
+    return misc_launch(h, launch_sim_topk_grouped, queries, gallery, n_queries, n_gallery, D, k, g_offsets, n_groups, gallery_offset, merge, idx,
+                       score);
 }
 
 int jg_group_of_rows(jg_handle* h, const int32_t* idx, int64_t n, const int32_t* g_offsets, int n_groups, int gallery_offset,
@@ -579,14 +591,14 @@ int jg_group_of_rows(jg_handle* h, const int32_t* idx, int64_t n, const int32_t*
     if (!idx || !grp || !pos || (n_groups > 0 && !g_offsets)) JG_FAIL(h, JG_ERR_ARG, "null buffer");
     if (n < 0 || n_groups < 0 || gallery_offset < 0) JG_FAIL(h, JG_ERR_ARG, "n, n_groups and gallery_offset must be >= 0");
     if (n == 0) return JG_OK;
-    return timed(h, JG_ST_MISC, [&] { return launch_group_of_rows(idx, (long)n, g_offsets, n_groups, gallery_offset, grp, pos, h->stream); });
+    return misc_launch(h, launch_group_of_rows, idx, (long)n, g_offsets, n_groups, gallery_offset, grp, pos);
 }
 
 int jg_spot(jg_handle* h, const float* g, const float* c, const int32_t* goff, const int32_t* coff, const int32_t* target,
             int n, int D, float temp, int32_t* pred, float* score) {
     ENTER(h);
     if (!g || !c || !goff || !coff || !target || !pred || !score) JG_FAIL(h, JG_ERR_ARG, "null buffer");
-    return timed(h, JG_ST_MISC, [&] { return launch_spot(g, c, goff, coff, target, n, D, temp, pred, score, h->stream); });
+    return misc_launch(h, launch_spot, g, c, goff, coff, target, n, D, temp, pred, score);
 }
 
 int jg_attn_matrix(jg_handle* h, const float* g, const float* c, const int32_t* goff, const int32_t* coff, int n, int D, int max_frames,
@@ -595,17 +607,14 @@ int jg_attn_matrix(jg_handle* h, const float* g, const float* c, const int32_t* 
     if (!g || !c || !goff || !coff) JG_FAIL(h, JG_ERR_ARG, "null buffer");
     if (A && !aoff) JG_FAIL(h, JG_ERR_ARG, "A needs a_offsets");
     if (!A && !best_frame && !best_score) JG_FAIL(h, JG_ERR_ARG, "no output: A, best_frame and best_score are all NULL");
-    if (n < 0 || max_frames < 1 || max_frames > 8192) JG_FAIL(h, JG_ERR_ARG, "max_frames must be 1..8192 (and n_clips >= 0)");
-    if (D <= 0 || D % 64) JG_FAIL(h, JG_ERR_ARG, "D must be a positive multiple of 64");
+    if (n < 0 || max_frames < 1 || max_frames > SPOT_MAX_T) JG_FAIL(h, JG_ERR_ARG, "max_frames must be 1..%d (and n_clips >= 0)", SPOT_MAX_T);
     if (!(temp > 0.f)) JG_FAIL(h, JG_ERR_ARG, "temp must be positive");
-    if ((reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(c)) & 15) JG_FAIL(h, JG_ERR_ARG, "gesture / content must be 16-byte aligned");
+    RET(row_pair_check(h, "gesture / content", g, c, D));
     if (n == 0) return JG_OK;
     unsigned long long* keys = nullptr;          // per-word arg-max keys, combined across the frame blocks of a clip
     RET(begin_pass(h));
     if (best_frame || best_score) RET(wsalloc(h, attn_matrix_key_elems(n), &keys));
-    return timed(h, JG_ST_MISC, [&] {
-        return launch_attn_matrix(g, c, goff, coff, n, D, max_frames, temp, normalize, A, aoff, keys, best_frame, best_score, h->stream);
-    });
+    return misc_launch(h, launch_attn_matrix, g, c, goff, coff, n, D, max_frames, temp, normalize, A, aoff, keys, best_frame, best_score);
 }
 
 int jg_sync_offset(jg_handle* h, const float* vid, const int32_t* v_offsets, const float* aud, const int32_t* a_offsets, int n_clips, int D,
@@ -613,14 +622,10 @@ int jg_sync_offset(jg_handle* h, const float* vid, const int32_t* v_offsets, con
     ENTER(h);
     if (!vid || !v_offsets || !aud || !a_offsets || !offset || !conf) JG_FAIL(h, JG_ERR_ARG, "null buffer");
     if (n_clips < 0) JG_FAIL(h, JG_ERR_ARG, "n_clips must be >= 0");
-    if (D <= 0 || D % 64 || D > SYNC_MAX_D) JG_FAIL(h, JG_ERR_ARG, "D must be a positive multiple of 64, at most %d", SYNC_MAX_D);
-    if (max_shift < 0 || max_shift > SYNC_MAX_R) JG_FAIL(h, JG_ERR_ARG, "max_shift must be 0..%d", SYNC_MAX_R);
-    if (min_overlap < 1) JG_FAIL(h, JG_ERR_ARG, "min_overlap must be >= 1");
-    if ((reinterpret_cast<uintptr_t>(vid) | reinterpret_cast<uintptr_t>(aud)) & 15) JG_FAIL(h, JG_ERR_ARG, "vid / aud must be 16-byte aligned");
+    RET(shift_check(h, max_shift, min_overlap));
+    RET(row_pair_check(h, "vid / aud", vid, aud, D, SYNC_MAX_D));
     if (n_clips == 0) return JG_OK;
-    return timed(h, JG_ST_MISC, [&] {
-        return launch_sync_offset(vid, v_offsets, aud, a_offsets, n_clips, D, max_shift, min_overlap, curve, offset, conf, h->stream);
-    });
+    return misc_launch(h, launch_sync_offset, vid, v_offsets, aud, a_offsets, n_clips, D, max_shift, min_overlap, curve, offset, conf);
 }
 
 int jg_sync_offset_windows(jg_handle* h, const float* vid, const int32_t* v_offsets, int n_clips, int64_t n_vid_rows, int max_rows,
@@ -631,31 +636,27 @@ int jg_sync_offset_windows(jg_handle* h, const float* vid, const int32_t* v_offs
     if (!vid || !v_offsets || !aud || !a_offsets || !w_offsets || !offset || !conf) JG_FAIL(h, JG_ERR_ARG, "null buffer");
     if (n_clips < 0 || n_aud < 0 || n_vid_rows < 0) JG_FAIL(h, JG_ERR_ARG, "n_clips, n_aud and n_vid_rows must be >= 0");
     if (!a_of && n_aud != n_clips) JG_FAIL(h, JG_ERR_ARG, "without a_of clip i takes audio track i: n_aud must equal n_clips");
-    if (D <= 0 || D % 64 || D > SYNC_MAX_D) JG_FAIL(h, JG_ERR_ARG, "D must be a positive multiple of 64, at most %d", SYNC_MAX_D);
-    if (max_shift < 0 || max_shift > SYNC_MAX_R) JG_FAIL(h, JG_ERR_ARG, "max_shift must be 0..%d", SYNC_MAX_R);
-    if (min_overlap < 1) JG_FAIL(h, JG_ERR_ARG, "min_overlap must be >= 1");
+    RET(shift_check(h, max_shift, min_overlap));
     if (max_rows < 1 || max_rows > SYNCW_MAX_T) JG_FAIL(h, JG_ERR_ARG, "max_rows must be 1..%d", SYNCW_MAX_T);
     if (max_windows < 1 || max_windows > SYNCW_MAX_WINDOWS) JG_FAIL(h, JG_ERR_ARG, "max_windows must be 1..%d", SYNCW_MAX_WINDOWS);
     if (win < 0 || (win > 0 && hop < 1)) JG_FAIL(h, JG_ERR_ARG, "win must be >= 0 (0: one window over all rows) and hop >= 1");
-    const int64_t band_elems = n_vid_rows * (2 * max_shift + 1);
-    if (n_vid_rows >= (int64_t)1 << 40 || band_elems >= (int64_t)1 << 40) JG_FAIL(h, JG_ERR_ARG, "the band (n_vid_rows x (2 max_shift + 1)) must stay below 2^40 entries");
-    if ((reinterpret_cast<uintptr_t>(vid) | reinterpret_cast<uintptr_t>(aud)) & 15) JG_FAIL(h, JG_ERR_ARG, "vid / aud must be 16-byte aligned");
+    const int64_t band_max = (int64_t)1 << SYNCW_MAX_BAND_LOG2, band_elems = n_vid_rows * (2 * max_shift + 1);
+    if (n_vid_rows >= band_max || band_elems >= band_max) JG_FAIL(h, JG_ERR_ARG, "the band (n_vid_rows x (2 max_shift + 1)) must stay below 2^%d entries", SYNCW_MAX_BAND_LOG2);
+    RET(row_pair_check(h, "vid / aud", vid, aud, D, SYNC_MAX_D));
     if (n_clips == 0) return JG_OK;
     if (n_aud == 0) JG_FAIL(h, JG_ERR_ARG, "clips need an audio track: n_aud must be >= 1");
     if (!band) {                 // the band is scratch of this call: one pass, like jg_attn_matrix's keys
         RET(begin_pass(h));
         RET(wsalloc(h, (size_t)(band_elems > 0 ? band_elems : 1), &band));
     }
-    return timed(h, JG_ST_MISC, [&] {
-        return launch_sync_offset_windows(vid, v_offsets, n_clips, (long)n_vid_rows, max_rows, aud, a_offsets, n_aud, a_of, D, max_shift,
-                                          min_overlap, win, hop, w_offsets, max_windows, band, curve, offset, conf, h->stream);
-    });
+    return misc_launch(h, launch_sync_offset_windows, vid, v_offsets, n_clips, (long)n_vid_rows, max_rows, aud, a_offsets, n_aud, a_of, D, max_shift,
+                       min_overlap, win, hop, w_offsets, max_windows, band, curve, offset, conf);
 }
 
 int jg_asd(jg_handle* h, const float* q, const float* cand, const int32_t* coff, int n, int D, float temp, int32_t* pred) {
     ENTER(h);
     if (!q || !cand || !coff || !pred) JG_FAIL(h, JG_ERR_ARG, "null buffer");
-    return timed(h, JG_ST_MISC, [&] { return launch_asd(q, cand, coff, n, D, temp, pred, h->stream); });
+    return misc_launch(h, launch_asd, q, cand, coff, n, D, temp, pred);
 }
 
 int jg_asd_windows(jg_handle* h, const float* gesture, const int32_t* g_offsets, int n_tracks, const float* content, const int32_t* c_offsets,
@@ -666,18 +667,15 @@ int jg_asd_windows(jg_handle* h, const float* gesture, const int32_t* g_offsets,
     if (!gesture || !g_offsets || !content || !c_offsets || !trk || !s_offsets || !w_offsets || !p_offsets || !prob || !pred)
         JG_FAIL(h, JG_ERR_ARG, "null buffer");
     if (n_scenes < 0 || n_tracks < 0) JG_FAIL(h, JG_ERR_ARG, "n_scenes and n_tracks must be >= 0");
-    if (D <= 0 || D % 64 || D > ASDW_MAX_D) JG_FAIL(h, JG_ERR_ARG, "D must be a positive multiple of 64, at most %d", ASDW_MAX_D);
-    if (win < 0 || win > 8192) JG_FAIL(h, JG_ERR_ARG, "win must be 0 (one window over everything) or 1..8192 frames");
+    if (win < 0 || win > ASDW_MAX_WIN) JG_FAIL(h, JG_ERR_ARG, "win must be 0 (one window over everything) or 1..%d frames", ASDW_MAX_WIN);
     if (win > 0 && hop < 1) JG_FAIL(h, JG_ERR_ARG, "hop must be >= 1");
     if (win > 0 && (!word_start || !word_end)) JG_FAIL(h, JG_ERR_ARG, "windows need word_start and word_end");
     if (!(temp > 0.f)) JG_FAIL(h, JG_ERR_ARG, "temp must be positive");
-    if (max_windows < 1 || max_windows > 8192) JG_FAIL(h, JG_ERR_ARG, "max_windows must be 1..8192");
-    if ((reinterpret_cast<uintptr_t>(gesture) | reinterpret_cast<uintptr_t>(content)) & 15) JG_FAIL(h, JG_ERR_ARG, "gesture / content must be 16-byte aligned");
+    if (max_windows < 1 || max_windows > ASDW_MAX_WIN) JG_FAIL(h, JG_ERR_ARG, "max_windows must be 1..%d", ASDW_MAX_WIN);
+    RET(row_pair_check(h, "gesture / content", gesture, content, D, ASDW_MAX_D));
     if (n_scenes == 0) return JG_OK;
-    return timed(h, JG_ST_MISC, [&] {
-        return launch_asd_windows(gesture, g_offsets, n_tracks, content, c_offsets, word_start, word_end, trk, s_offsets, n_scenes, D, win, hop,
-                                  w_offsets, p_offsets, max_windows, temp, prob, cosv, pred, h->stream);
-    });
+    return misc_launch(h, launch_asd_windows, gesture, g_offsets, n_tracks, content, c_offsets, word_start, word_end, trk, s_offsets, n_scenes, D, win,
+                       hop, w_offsets, p_offsets, max_windows, temp, prob, cosv, pred);
 }
 
 // ---- multi-GPU exchange on RCCL: one communicator per handle = per rank = per GPU

@@ -1,0 +1,312 @@
+// Retrieval kernels (gfx950): rank counting, top-k and grouped top-k on exact-fp32 MFMA, and the group of a returned row.
+#include "metric_parts.h"
+
+// ---------------------------------------------------------------------------------------------
+// Retrieval (evaluate_retrieval.py:38-65).  For each local query row i (global index gi =
+// row_offset + i):  d = <e1[i], e2[gi]>,  rank[i] = #{j : <e1[i],e2[j]> > d},
+// ties[i] = #{j : <e1[i],e2[j]> == d} (includes j = gi).  The reference's `ind` entries for the row
+// are rank .. rank+ties-1.  The N x N similarity matrix is never written to HBM.
+//
+// v_mfma_f32_32x32x2_f32: exact fp32, a k-ordered fmaf chain per element, so an element's value
+// depends only on its two vectors -- duplicate gallery rows give bitwise-equal scores, i.e. exact
+// ties like the reference.  Block = 4 waves = 64 query rows x 64 gallery rows per tile (each wave a
+// 32x32 accumulator), K staged through LDS in 64-wide chunks stored [k][row] so the one-float
+// fragment reads (lane -> row l&31, k l>>5) are bank-conflict free.
+// The tile is written once (sim_tile) and so is an element's k order: a score has the same bits in jg_sim_rank, jg_sim_topk and
+// jg_sim_topk_grouped, whatever tile of whichever call it falls in.
+
+__global__ __launch_bounds__(256) void sim_rank_kernel(const float* __restrict__ e1, const float* __restrict__ e2,
+                                                       int n_local, int n_total, int row_offset, int D,
+                                                       int32_t* __restrict__ rank, int32_t* __restrict__ ties) {
+    __shared__ float sA[64][64];   // [k][query row]
+    __shared__ float sB[64][64];   // [k][gallery row]
+    __shared__ float sDiag[64];
+    __shared__ int sRank[64], sTies[64];
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int i0 = blockIdx.x * 64;
+    if (tid < 64) { sRank[tid] = 0; sTies[tid] = 0; }
+
+    int cnt_gt[16], cnt_eq[16];
+#pragma unroll
+    for (int x = 0; x < 16; ++x) { cnt_gt[x] = 0; cnt_eq[x] = 0; }
+
+    const int ntiles = (n_total + 63) / 64;
+    // tile -1 is the diagonal tile (gallery rows row_offset+i0 ..), then all gallery tiles.
+    for (int tile = -1; tile < ntiles; ++tile) {
+        const int j0 = tile < 0 ? row_offset + i0 : tile * 64;
+        const f32x16 acc = sim_tile(e1, e2, i0, j0, n_local, n_total, D, sA, sB, tid);
+        if (tile < 0) {
+#pragma unroll
+            for (int x = 0; x < 16; ++x) {
+                const int row = sim_tile_row(x, tid);
+                if (row == sim_tile_col(tid)) sDiag[row] = acc[x];
+            }
+            __syncthreads();
+        } else {
+            const bool jok = j0 + sim_tile_col(tid) < n_total;
+#pragma unroll
+            for (int x = 0; x < 16; ++x) {
+                const float d = sDiag[sim_tile_row(x, tid)];
+                cnt_gt[x] += (jok && acc[x] > d) ? 1 : 0;
+                cnt_eq[x] += (jok && acc[x] == d) ? 1 : 0;
+            }
+        }
+    }
+    // reduce over the 32 lanes that share a row, then across the two column waves
+#pragma unroll
+    for (int x = 0; x < 16; ++x) {
+        int g = cnt_gt[x], e = cnt_eq[x];
+#pragma unroll
+        for (int o = 16; o > 0; o >>= 1) { g += __shfl_xor(g, o, 64); e += __shfl_xor(e, o, 64); }
+        if ((lane & 31) == 0) {
+            atomicAdd(&sRank[sim_tile_row(x, tid)], g);
+            atomicAdd(&sTies[sim_tile_row(x, tid)], e);
+        }
+    }
+    __syncthreads();
+    if (tid < 64 && i0 + tid < n_local) {
+        rank[i0 + tid] = sRank[tid];
+        ties[i0 + tid] = sTies[tid];
+    }
+}
+
+hipError_t launch_sim_rank(const float* e1, const float* e2, int n_local, int n_total, int row_offset, int D,
+                           int32_t* rank, int32_t* ties, hipStream_t s) {
+    if (n_local <= 0) return hipSuccess;
+    if (D % 64) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(sim_rank_kernel, dim3((n_local + 63) / 64), dim3(256), 0, s, e1, e2, n_local, n_total, row_offset, D, rank, ties);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
+// Top-k retrieval: for each query row the k gallery rows with the largest <q_i, g_j>, best first, without the similarity matrix.
+// A candidate is the 64-bit key (order-preserving bits of the score << 32) | ~index:
+// keys of distinct gallery rows are distinct and totally ordered (larger score first, then the smaller index), so "the k largest keys of
+// a set" does not depend on the order of arrival, nor on how the gallery is cut into calls.  Key 0 = empty slot (no number has it).
+//
+// Per query row in LDS: LCAP >= k keys sorted descending (sL), the k-th of them as the threshold (sThr), and a queue of this tile's
+// survivors (sQ, 64 slots = the tile's 64 columns, so it cannot overflow; it lies over the staging buffers, which are dead between the
+// last MFMA of a tile and the staging of the next).  After every tile a wave takes 16 rows and inserts the queued keys of each one by one:
+// the list lives in the wave's registers (position = lane, lane + 64), an insertion is one compare and a shift by one lane.
+//
+// Grouped top-k (GROUPED): the gallery rows are partitioned into contiguous groups (goff[g] .. goff[g + 1] - 1, local rows), a group
+// scores as its best row (its champion: the largest key of its rows, so on equal scores the first row), and per query the k best champions
+// are kept, each with its row.  What this adds is the invariant AT MOST ONE LIST ENTRY PER GROUP: an insertion first looks for the
+// entry of the candidate's group; if that entry beats the candidate the candidate is dropped, else the entry is removed and the candidate
+// inserted -- one pass, since the candidate lands at or before the entry it replaces: the positions behind that entry keep their keys.
+// Entries only ever move towards the end of the list, and replacing an entry by a larger one can only raise the k-th key, so the
+// threshold stays monotone: what is below a threshold that ever held is below the final k-th champion.
+//
+// Groups are contiguous, so "same group" is a range test on the row half of a key against the candidate's [goff[g], goff[g + 1]); the
+// list needs no second array.  The range comes from a wave-uniform binary search over goff when the candidate is broadcast, and is kept
+// for the candidates behind it: the queue of a tile holds 64 consecutive rows, mostly of one or two groups.  Entries seeded by merge lie
+// outside this call's rows and never match.  goff is a device array that nobody has checked: it is only ever read at 0 .. n_groups
+// (the search is bounded by n_groups, not by what it reads) and its values are only compared with row numbers, never used as addresses.
+using u64 = unsigned long long;
+__device__ __forceinline__ unsigned topk_ord(float s) {          // fp32 -> unsigned, order-preserving; -0.0 counts as +0.0
+    const unsigned b = __float_as_uint(s);
+    return b == 0x80000000u ? 0x80000000u : (b & 0x80000000u) ? ~b : b | 0x80000000u;
+}
+__device__ __forceinline__ float topk_score(u64 key) {
+    const unsigned o = (unsigned)(key >> 32);
+    return key ? __uint_as_float((o & 0x80000000u) ? o ^ 0x80000000u : ~o) : -INFINITY;
+}
+__device__ __forceinline__ int32_t topk_index(u64 key) { return key ? (int32_t)(0xffffffffu - (unsigned)key) : -1; }
+__device__ __forceinline__ u64 topk_key(float s, unsigned index) { return ((u64)topk_ord(s) << 32) | (0xffffffffu - index); }
+__device__ __forceinline__ u64 topk_readlane(u64 v, int src) {   // src: wave-uniform
+    const unsigned lo = __builtin_amdgcn_readlane((int)(unsigned)v, src), hi = __builtin_amdgcn_readlane((int)(unsigned)(v >> 32), src);
+    return ((u64)hi << 32) | lo;
+}
+
+// the group that holds local row j, and its rows [lo, hi), given goff[0] <= j < goff[n_groups] (else: some group and range)
+__device__ __forceinline__ int group_range(const int32_t* __restrict__ goff, int n_groups, int j, int& lo, int& hi) {
+    int a = 0, b = n_groups;
+    lo = goff[0];
+    hi = goff[n_groups];
+    while (b - a > 1) {                                          // goff[a] <= j < goff[b]
+        const int mid = (a + b) >> 1, v = goff[mid];
+        if (v <= j) { a = mid; lo = v; } else { b = mid; hi = v; }
+    }
+    return a;
+}
+
+// the wave's 16 rows: queued keys into the sorted lists (GROUPED: one entry per group), new thresholds, queues emptied
+template <int LCAP, bool GROUPED>
+__device__ __forceinline__ void topk_flush(u64 (*sL)[LCAP], const u64 (*sQ)[64], int* sCnt, u64* sThr, int k, int wave, int lane,
+                                           const int32_t* __restrict__ goff, int n_groups, unsigned gallery_offset) {
+    unsigned first = 0u, len = 0u;                               // global rows first .. first + len - 1: the group searched last
+    for (int rr = 0; rr < 16; ++rr) {
+        const int row = wave * 16 + rr;
+        const int n = __builtin_amdgcn_readfirstlane(sCnt[row]);
+        if (n == 0) continue;
+        const u64 cand = lane < n ? sQ[row][lane] : 0ull;
+        u64 e0 = sL[row][lane], e1 = 0ull;
+        if constexpr (LCAP == 128) e1 = sL[row][64 + lane];
+        u64 kth = sThr[row];
+        for (int i = 0; i < n; ++i) {
+            const u64 c = topk_readlane(cand, i);
+            // an earlier insertion of this tile has raised the threshold past it (GROUPED: below the k-th champion, its group's entry, if
+            // any, beats it as well)
+            if (c < kth) continue;
+            int m = LCAP;                                        // GROUPED: the positions behind m keep their keys
+            if constexpr (GROUPED) {
+                const unsigned gi = 0xffffffffu - (unsigned)c;
+                if (gi - first >= len) {
+                    int lo, hi;
+                    group_range(goff, n_groups, (int)(gi - gallery_offset), lo, hi);
+                    first = gallery_offset + (unsigned)lo;
+                    len = (unsigned)hi - (unsigned)lo;
+                }
+                // m: the position of the group's entry (the first one, should hostile offsets give several), LCAP when it has none
+                const unsigned long long hit0 = __ballot(e0 != 0ull && 0xffffffffu - (unsigned)e0 - first < len);
+                m = hit0 ? __builtin_ctzll(hit0) : LCAP;
+                if constexpr (LCAP == 128) {
+                    const unsigned long long hit1 = __ballot(e1 != 0ull && 0xffffffffu - (unsigned)e1 - first < len);
+                    if (!hit0 && hit1) m = 64 + __builtin_ctzll(hit1);
+                }
+                if (m < LCAP && topk_readlane(m < 64 ? e0 : e1, m & 63) > c) continue;   // the group's champion stays
+            }
+            // up to m: position p keeps its key if that beats c, else it takes c if the key before it beats c, else the key before it
+            // (GROUPED: the entry at m is below c, so it is the one that leaves)
+            u64 p0 = __shfl_up(e0, 1, 64);
+            if (lane == 0) p0 = ~0ull;
+            if constexpr (LCAP == 128) {
+                u64 p1 = __shfl_up(e1, 1, 64);
+                const u64 last0 = topk_readlane(e0, 63);
+                if (lane == 0) p1 = last0;
+                e1 = ((GROUPED && 64 + lane > m) || e1 > c) ? e1 : (p1 > c ? c : p1);
+            }
+            e0 = ((GROUPED && lane > m) || e0 > c) ? e0 : (p0 > c ? c : p0);
+            kth = topk_readlane(LCAP == 128 && k > 64 ? e1 : e0, (k - 1) & 63);
+        }
+        sL[row][lane] = e0;
+        if constexpr (LCAP == 128) sL[row][64 + lane] = e1;
+        if (lane == 0) { sThr[row] = kth; sCnt[row] = 0; }
+    }
+}
+
+// jg_sim_topk (GROUPED = false: goff and n_groups are not looked at) and jg_sim_topk_grouped
+template <int LCAP, bool GROUPED>
+__global__ __launch_bounds__(256) void sim_topk_kernel(const float* __restrict__ e1, const float* __restrict__ e2, int n_queries,
+                                                       int n_gallery, int D, int k, const int32_t* __restrict__ goff, int n_groups,
+                                                       int gallery_offset, int merge, int32_t* __restrict__ idx,
+                                                       float* __restrict__ score) {
+    __shared__ __attribute__((aligned(16))) u64 sStage[64 * 64];       // staging (sA, sB) during a tile's k loop, the queues after it
+    __shared__ u64 sL[64][LCAP];
+    __shared__ u64 sThr[64];
+    __shared__ int sCnt[64];
+    float (*sA)[64] = reinterpret_cast<float (*)[64]>(sStage);         // [k][query row]
+    float (*sB)[64] = sA + 64;                                         // [k][gallery row]
+    u64 (*sQ)[64] = reinterpret_cast<u64 (*)[64]>(sStage);             // [query row][slot]
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int i0 = blockIdx.x * 64;
+
+    // the lists start empty, or (merge) from the caller's earlier result: sorted, empty slots (idx < 0) last
+    for (int rr = 0; rr < 16; ++rr) {
+        const int row = wave * 16 + rr;
+        const long base = (long)(i0 + row) * k;
+        u64 kth = 0ull;
+#pragma unroll
+        for (int p = lane; p < LCAP; p += 64) {
+            u64 key = 0ull;
+            if (merge && p < k && i0 + row < n_queries) {
+                const int32_t j = idx[base + p];
+                const float s = score[base + p];
+                if (j >= 0 && s == s) key = topk_key(s, (unsigned)j);
+            }
+            sL[row][p] = key;
+            if (p == k - 1) kth = key;
+        }
+        if (lane == ((k - 1) & 63)) sThr[row] = kth;
+        if (lane == 0) sCnt[row] = 0;
+    }
+
+    int grp_lo = 0, grp_hi = 0, ntiles = (n_gallery + 63) / 64;
+    if constexpr (GROUPED) {
+        // rows below goff[0] or from goff[n_groups] on belong to no group; without a group there is no candidate and no tile to walk
+        grp_lo = n_groups > 0 ? goff[0] : 0;
+        grp_hi = n_groups > 0 ? goff[n_groups] : 0;
+        if (n_groups <= 0) ntiles = 0;
+    }
+    for (int tile = 0; tile < ntiles; ++tile) {
+        const int j0 = tile * 64;
+        const f32x16 acc = sim_tile(e1, e2, i0, j0, n_queries, n_gallery, D, sA, sB, tid);
+        __syncthreads();                                         // the staging buffers become the queues
+        const int j = j0 + sim_tile_col(tid);
+        const bool jok = j < n_gallery && (!GROUPED || (j >= grp_lo && j < grp_hi));
+        const unsigned gj = (unsigned)gallery_offset + (unsigned)j;
+#pragma unroll
+        for (int x = 0; x < 16; ++x) {
+            const int row = sim_tile_row(x, tid);
+            const u64 key = topk_key(acc[x], gj);
+            if (jok && acc[x] == acc[x] && i0 + row < n_queries && key > sThr[row])      // a NaN is never a candidate
+                sQ[row][atomicAdd(&sCnt[row], 1)] = key;
+        }
+        __syncthreads();
+        topk_flush<LCAP, GROUPED>(sL, sQ, sCnt, sThr, k, wave, lane, goff, n_groups, (unsigned)gallery_offset);
+    }
+    // a wave stores the lists of the rows it seeded and flushed itself, each row as one contiguous run
+    for (int rr = 0; rr < 16; ++rr) {
+        const int row = wave * 16 + rr;
+        if (i0 + row >= n_queries) break;
+        const long base = (long)(i0 + row) * k;
+        for (int p = lane; p < k; p += 64) {
+            const u64 key = sL[row][p];
+            idx[base + p] = topk_index(key);
+            score[base + p] = topk_score(key);
+        }
+    }
+}
+
+template <bool GROUPED>
+static hipError_t launch_topk(const float* queries, const float* gallery, int n_queries, int n_gallery, int D, int k, const int32_t* g_offsets,
+                              int n_groups, int gallery_offset, int merge, int32_t* idx, float* score, hipStream_t s) {
+    if (n_queries <= 0) return hipSuccess;
+    if (D <= 0 || D % 64 || k < 1 || k > SIM_TOPK_MAX_K || n_gallery < 0 || (GROUPED && (n_groups < 0 || (n_groups > 0 && !g_offsets))) ||
+        gallery_offset < 0 || gallery_offset > INT32_MAX - n_gallery)
+        return hipErrorInvalidValue;
+    const auto kernel = k <= 64 ? sim_topk_kernel<64, GROUPED> : sim_topk_kernel<128, GROUPED>;
+    hipLaunchKernelGGL(kernel, dim3((n_queries + 63) / 64), dim3(256), 0, s, queries, gallery, n_queries, n_gallery, D, k, g_offsets, n_groups,
+                       gallery_offset, merge, idx, score);
+    return hipGetLastError();
+}
+
+hipError_t launch_sim_topk(const float* queries, const float* gallery, int n_queries, int n_gallery, int D, int k, int gallery_offset,
+                           int merge, int32_t* idx, float* score, hipStream_t s) {
+    return launch_topk<false>(queries, gallery, n_queries, n_gallery, D, k, nullptr, 0, gallery_offset, merge, idx, score, s);
+}
+
+hipError_t launch_sim_topk_grouped(const float* queries, const float* gallery, int n_queries, int n_gallery, int D, int k,
+                                   const int32_t* g_offsets, int n_groups, int gallery_offset, int merge, int32_t* idx, float* score,
+                                   hipStream_t s) {
+    return launch_topk<true>(queries, gallery, n_queries, n_gallery, D, k, g_offsets, n_groups, gallery_offset, merge, idx, score, s);
+}
+
+// rows (as jg_sim_topk_grouped returns them) -> group and position inside it: an element-wise binary search; -1 / -1 for idx < 0 or a row
+// in no group.  Hostile offsets give some group and position, nothing else.
+__global__ void group_of_rows_kernel(const int32_t* __restrict__ idx, long n, const int32_t* __restrict__ goff, int n_groups,
+                                     int gallery_offset, int32_t* __restrict__ grp, int32_t* __restrict__ pos) {
+    for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long)gridDim.x * blockDim.x) {
+        const long j = (long)idx[e] - gallery_offset;
+        int g = -1, p = -1;
+        if (idx[e] >= 0 && n_groups > 0 && j >= goff[0] && j < goff[n_groups]) {
+            int lo, hi;
+            g = group_range(goff, n_groups, (int)j, lo, hi);
+            p = (int)(j - goff[g]);
+        }
+        grp[e] = g;
+        pos[e] = p;
+    }
+}
+
+hipError_t launch_group_of_rows(const int32_t* idx, long n, const int32_t* g_offsets, int n_groups, int gallery_offset, int32_t* grp,
+                                int32_t* pos, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    if (n_groups < 0 || (n_groups > 0 && !g_offsets)) return hipErrorInvalidValue;
+    const long blocks = (n + 255) / 256;
+    hipLaunchKernelGGL(group_of_rows_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, s, idx, n, g_offsets, n_groups,
+                       gallery_offset, grp, pos);
+    return hipGetLastError();
+}

@@ -1,7 +1,8 @@
 // Build-independent declarations of libjegal_hip (gfx950 only): everything that does not depend on the 16-bit operand type.
 // Included once, global namespace, by both kernel builds (common.h includes it).  The rule of the two builds is in common.h:
-// a kernel with no 16-bit operand is compiled once (elementwise_f32.hip, metrics.hip) and its launcher is declared here; so are the
-// launchers of gsa_kernels.hip, whose output type (fp16 / fp32) is a run-time flag and which no bf16 handle reaches.
+// a kernel with no 16-bit operand is compiled once (elementwise_f32.hip and the metric units retrieval.hip, spotting.hip, asd.hip,
+// sync_offset.hip) and its launcher is declared here, with every limit its entry refuses on beside it; so are the launchers of
+// gsa_kernels.hip, whose output type (fp16 / fp32) is a run-time flag and which no bf16 handle reaches.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -191,6 +192,9 @@ hipError_t launch_sim_topk_grouped(const float* queries, const float* gallery, i
 // grp / pos [n]: the group that holds row idx[e] - gallery_offset and the row's place inside it; -1 / -1 for idx[e] < 0 or a row in no group
 hipError_t launch_group_of_rows(const int32_t* idx, long n, const int32_t* g_offsets, int n_groups, int gallery_offset, int32_t* grp,
                                 int32_t* pos, hipStream_t s);
+// per clip at most SPOT_MAX_W words and SPOT_MAX_T frames (spot, attention matrices and ASD windows size LDS arrays with them); a clip
+// outside them, or with a target outside its words, gets pred = -1, score = NaN
+constexpr int SPOT_MAX_W = 1024, SPOT_MAX_T = 8192;
 hipError_t launch_spot(const float* g, const float* c, const int32_t* goff, const int32_t* coff, const int32_t* target,
                        int n, int D, float temp, int32_t* pred, float* score, hipStream_t s);
 // A (optional; with aoff, int64 element offsets per clip) and / or best_frame / best_score (optional; they need keys: attn_matrix_key_elems(n)
@@ -201,18 +205,19 @@ hipError_t launch_attn_matrix(const float* g, const float* c, const int32_t* gof
                               int32_t* best_frame, float* best_score, hipStream_t s);
 hipError_t launch_asd(const float* q, const float* cand, const int32_t* coff, int n, int D, float temp,
                       int32_t* pred2, hipStream_t s);
-// Audio-visual offset per clip (metrics.hip: sync_offset_kernel): mean cosine of the row pairs (t, t + d) for d = -R .. R -> curve
+// Audio-visual offset per clip (sync_offset.hip: sync_offset_kernel): mean cosine of the row pairs (t, t + d) for d = -R .. R -> curve
 // (optional, [n][2R + 1]; NaN where fewer than min_overlap pairs exist), offset = first arg-max, conf = max - median.  A clip outside
 // the limits (1..SYNC_MAX_T video and audio rows, one shift with enough pairs) gets offset 0, conf NaN, a NaN curve row.  No scratch.
 constexpr int SYNC_MAX_R = 64, SYNC_MAX_T = 8192, SYNC_MAX_D = 1024;
 hipError_t launch_sync_offset(const float* vid, const int32_t* voff, const float* aud, const int32_t* aoff, int n, int D, int R, int min_overlap,
                               float* curve, int32_t* offset, float* conf, hipStream_t s);
-// The same over time (metrics.hip: sync_band_kernel + sync_windows_kernel): clip i = video track i against audio track a_of[i] (nullptr: i),
+// The same over time (sync_offset.hip: sync_band_kernel + sync_windows_kernel): clip i = video track i against audio track a_of[i] (nullptr: i),
 // window j of it = video rows j hop .. min(j hop + win, Tv) - 1 (win == 0: all rows) -> curve (optional) / offset / conf rows woff[i] + j.
 // band [n_vid_rows][2R + 1] (required here: the caller's, or scratch of that size) receives every cosine once, NaN where the audio row does
 // not exist.  A clip outside the limits (tracks of 1..max_rows rows inside the arrays, a_of inside 0..n_aud-1, 1..max_windows windows) gets
 // offset 0, conf NaN and NaN curve rows in all of its windows and none of its band rows is written.
 constexpr int SYNCW_MAX_T = 1 << 20, SYNCW_MAX_WINDOWS = 1 << 20;
+constexpr int SYNCW_MAX_BAND_LOG2 = 40;      // n_vid_rows and the band's n_vid_rows (2R + 1) entries stay below 2^40
 hipError_t launch_sync_offset_windows(const float* vid, const int32_t* voff, int n, long n_vid_rows, int max_rows, const float* aud,
                                       const int32_t* aoff, int n_aud, const int32_t* a_of, int D, int R, int min_overlap, int win, int hop,
                                       const int32_t* woff, int max_windows, float* band, float* curve, int32_t* offset, float* conf,
@@ -224,10 +229,12 @@ hipError_t launch_gsa_conv1_pool(const float* src, int clip_form, int n0, int nw
                                  const float* shift, void* out, int out32, hipStream_t s, char* kname = nullptr);
 // NHWC max-pool, window (2, 3), stride (2, 2): (N, H, W, C) -> (N, (H - 2) / 2 + 1, (W - 3) / 2 + 1, C), fp16 or (f32) fp32 elements; C % 8 == 0
 hipError_t launch_maxpool_2x3_s2(const void* in, void* out, int N, int H, int W, int C, int f32, hipStream_t s, char* kname = nullptr);
-// ASD per time window (metrics.hip: asd_windows_kernel): prob / cosv (optional) (n_win_i, P_i) at poff[i], pred [woff[n_scenes]].  A scene
+// ASD per time window (asd.hip: asd_windows_kernel): prob / cosv (optional) (n_win_i, P_i) at poff[i], pred [woff[n_scenes]].  A scene
 // outside the limits (1..64 candidates, 1..1024 words, 1..max_windows windows, tracks of 1..8192 frames inside 0..n_tracks-1) gets
 // pred = -1 and NaN rows in all of its windows.  No scratch.
 constexpr int ASDW_MAX_D = 1024;
+constexpr int ASDW_MAX_P = 64;               // candidates per scene: one lane each in the softmax
+constexpr int ASDW_MAX_WIN = 8192;           // windows per scene, and frames per window
 hipError_t launch_asd_windows(const float* g, const int32_t* goff, int n_tracks, const float* c, const int32_t* coff, const int32_t* wstart,
                               const int32_t* wend, const int32_t* trk, const int32_t* soff, int n_scenes, int D, int win, int hop,
                               const int32_t* woff, const int64_t* poff, int max_windows, float temp, float* prob, float* cosv,

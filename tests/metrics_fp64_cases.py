@@ -1,4 +1,4 @@
-"""Cases, float64 references and derived bounds for the first-generation metric entries jg_sim_rank, jg_spot and jg_asd (jegal_amd/csrc/metrics.hip).
+"""Cases, float64 references and derived bounds for the first-generation metric entries jg_sim_rank, jg_spot and jg_asd (jegal_amd/csrc/retrieval.hip, spotting.hip, asd.hip).
 
 Imports without a GPU: tests/test_gpu_metrics_fp64.py feeds the cases to the public C ABI, tests/test_metrics_cases_cpu.py feeds them to plain
 float32 numpy statements of the kernels' arithmetic and to planted defects, so that references, bounds and margin conditions are checked

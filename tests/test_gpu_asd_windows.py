@@ -18,7 +18,7 @@ from jegal_amd import synth
 
 pytestmark = pytest.mark.gpu
 TEMP = 0.07
-WB = 16                    # ASDW_WB of jegal_amd/csrc/metrics.hip: windows per workgroup
+WB = 16                    # ASDW_WB of jegal_amd/csrc/asd.hip: windows per workgroup
 NAN_BITS = 0x7FC0BEEF      # a quiet NaN with a payload, as int32
 FLOOR = 8 * 2.0 ** -23
 PTR = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())

@@ -24,7 +24,7 @@ from jegal_amd import synth
 
 pytestmark = pytest.mark.gpu
 TEMP = 0.07
-REG_W = 128          # AM_REG_W of jegal_amd/csrc/metrics.hip: widest clip of the in-register form
+REG_W = 128          # AM_REG_W of jegal_amd/csrc/spotting.hip: widest clip of the in-register form
 FRAME_BLOCK = 128    # AM_FB: frames per workgroup
 
 
