@@ -380,8 +380,12 @@ int jg_debug_stack_frames32(jg_handle* h, const void* src, int src_is_u8, int64_
 int jg_debug_maxpool32(jg_handle* h, const float* in, int nimg, int H, int W, int C, float* out);
 int jg_debug_group_mean32(jg_handle* h, const float* in, int groups, int L, int D, float* out);
 int jg_debug_zero_tail32(jg_handle* h, float* x, const int32_t* valid_host, int n_valid, int halvings, int B, int H, int64_t row_elems);
-/* Name of the kernel instance the last check point launched, with its template arguments (e.g. "gemm_glds_kernel<1,0,4,4,2,0,0,0,0>";
- * empty if it launched nothing).  Host only, no synchronisation. */
+/* Name of the kernel instance the last kernel check point on this handle launched, with its template arguments (e.g.
+ * "gemm_glds_kernel<1,0,4,4,2,0,0,0,0>"; "a_kernel+b_kernel" for a launcher of two kernels).  The launcher itself writes the name, where
+ * it picks the instance and directly in front of the launch; the check point only lends it the handle's slot.  A check point that makes
+ * several launches (jg_debug_conv_check with s2_host, jg_debug_conv1_pool) reports the last one.  Empty after any error: a call the
+ * check point or the launcher refused, or a HIP failure, never leaves an earlier call's name.  jg_debug_gemm / jg_debug_gemm_ex time
+ * launches and leave the name alone.  Host only, no synchronisation. */
 int jg_debug_last_kernel(jg_handle* h, char* buf, int len);
 /* Check point for "conv2_row_skip": the MINIMUM over the positions of the last conv stack of the leading conv2 output rows that
  * were read from the const chain instead of computed (every position skips its own count: jg_debug_conv_rows);

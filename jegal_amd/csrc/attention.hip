@@ -604,12 +604,14 @@ __global__ __launch_bounds__(512) void attn_mfma_flash_kernel(const f16* __restr
 template <int DK>
 static hipError_t launch_attn_flash(const f16* qkv, const float* keymask, long npairs, int S, int H, f16* out, hipStream_t s) {
     const int nq = S < 256 ? S : 256;
+    record_kernel("attn_mfma_flash_kernel<%d>", DK);
     hipLaunchKernelGGL((attn_mfma_flash_kernel<DK>), dim3((unsigned)npairs, (unsigned)((S + 255) / 256)), dim3(64 * ((nq + 31) / 32)), 0, s, qkv, keymask, S, H, out);
     return hipGetLastError();
 }
 
 template <int NB>
 static hipError_t launch_attn_mfma(const f16* qkv, const float* keymask, long npairs, int S, int H, f16* out, hipStream_t s) {
+    record_kernel("attn_mfma_kernel<%d>", NB);
     hipLaunchKernelGGL((attn_mfma_kernel<NB>), dim3((unsigned)npairs), dim3(64 * NB), 0, s, qkv, keymask, S, H, out);
     return hipGetLastError();
 }
@@ -617,11 +619,12 @@ static hipError_t launch_attn_mfma(const f16* qkv, const float* keymask, long np
 // The attn_mfma_s32_kernel instance for S <= 32: OR = 24 where the sequence fits, four pairs per workgroup; the gather form
 // rounds the grid up to whole rounds of the eight XCDs (its block -> XCD deal).
 template <bool GATHER>
-static hipError_t launch_attn_s32(const f16* qkv, const AttnGather& g, long npairs, int S, int H, f16* out, hipStream_t s, char* kname) {
+static hipError_t launch_attn_s32(const f16* qkv, const AttnGather& g, long npairs, int S, int H, f16* out, hipStream_t s) {
     unsigned blocks = (unsigned)((npairs + 3) / 4);
     if (GATHER) blocks = (blocks + 7) / 8 * 8;
-    record_kernel(kname, "attn_mfma_s32_kernel<%d,%d>", (int)GATHER, S <= 24 ? 24 : 32);
-    const auto kernel = S <= 24 ? attn_mfma_s32_kernel<GATHER, 24> : attn_mfma_s32_kernel<GATHER, 32>;
+    const bool or24 = S <= 24;
+    const auto kernel = or24 ? attn_mfma_s32_kernel<GATHER, 24> : attn_mfma_s32_kernel<GATHER, 32>;
+    record_kernel("attn_mfma_s32_kernel<%d,%d>", (int)GATHER, or24 ? 24 : 32);
     hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, s, qkv, (int)npairs, S, H, out, g);
     return hipGetLastError();
 }
@@ -629,11 +632,11 @@ static hipError_t launch_attn_s32(const f16* qkv, const AttnGather& g, long npai
 #ifndef JG_BF16      // fp16 only (declared in common.h's fp16-only block): a bf16 handle never has the tiled token stream this path needs
 // Layer-0 attention of the GestSync transformer from per-position projections (see attn_mfma_s32_kernel<true>):
 // B = windows (nclip * g.Twin), S <= 32 tokens, dk = 64.
-hipError_t launch_attention_gather(const f16* qkv_pos, const AttnGather& g, int B, int S, int H, f16* out, hipStream_t s, char* kname) {
+hipError_t launch_attention_gather(const f16* qkv_pos, const AttnGather& g, int B, int S, int H, f16* out, hipStream_t s) {
     if (B <= 0 || S <= 0) return hipSuccess;
     const long npairs = (long)B * H;
     if (S > 32 || npairs >= (1L << 31) || g.Twin <= 0 || g.P <= 0 || !g.pe_qkv) return hipErrorInvalidValue;
-    return launch_attn_s32<true>(qkv_pos, g, npairs, S, H, out, s, kname);
+    return launch_attn_s32<true>(qkv_pos, g, npairs, S, H, out, s);
 }
 #endif
 
@@ -641,17 +644,14 @@ hipError_t launch_attention(const f16* qkv, const float* keymask, int B, int S, 
     if (B <= 0 || S <= 0) return hipSuccess;
     const long npairs = (long)B * H;
     if (o.attn_mfma && S <= 32 && dk == 64 && !keymask && npairs < (1L << 31))
-        return launch_attn_s32<false>(qkv, AttnGather{}, npairs, S, H, out, s, o.kname);
+        return launch_attn_s32<false>(qkv, AttnGather{}, npairs, S, H, out, s);
     if (o.attn_mfma && S <= 160 && dk == 64 && npairs < (1L << 31)) {      // S <= 32 with a key mask: one query block
         static constexpr decltype(&launch_attn_mfma<1>) by_nb[5] = {launch_attn_mfma<1>, launch_attn_mfma<2>, launch_attn_mfma<3>, launch_attn_mfma<4>,
                                                                     launch_attn_mfma<5>};
-        const int nb = (S + 31) / 32;
-        record_kernel(o.kname, "attn_mfma_kernel<%d>", nb);
-        return by_nb[nb - 1](qkv, keymask, npairs, S, H, out, s);
+        return by_nb[(S + 31) / 32 - 1](qkv, keymask, npairs, S, H, out, s);
     }
     // everything else on the matrix cores too: dk = 64 beyond 160 keys, dk = 96 (text encoder) at any length
     if (o.attn_mfma && npairs < (1L << 31) && (dk == 64 || dk == 96)) {
-        record_kernel(o.kname, "attn_mfma_flash_kernel<%d>", dk);
         if (dk == 64) return launch_attn_flash<64>(qkv, keymask, npairs, S, H, out, s);
         if (dk == 96) return launch_attn_flash<96>(qkv, keymask, npairs, S, H, out, s);
     }
@@ -666,10 +666,13 @@ hipError_t launch_attention(const f16* qkv, const float* keymask, int B, int S, 
         grid = dim3((unsigned)npairs, (S + 255) / 256);
         block = dim3(256);
     }
-    if (dk == 64 || dk == 96) record_kernel(o.kname, "attn_kernel<%d>", dk);
-    if (dk == 64) hipLaunchKernelGGL(attn_kernel<64>, grid, block, 0, s, qkv, keymask, B, S, H, G, out);
-    else if (dk == 96) hipLaunchKernelGGL(attn_kernel<96>, grid, block, 0, s, qkv, keymask, B, S, H, G, out);
-    else return hipErrorInvalidValue;
+    if (dk == 64) {
+        record_kernel("attn_kernel<64>");
+        hipLaunchKernelGGL(attn_kernel<64>, grid, block, 0, s, qkv, keymask, B, S, H, G, out);
+    } else if (dk == 96) {
+        record_kernel("attn_kernel<96>");
+        hipLaunchKernelGGL(attn_kernel<96>, grid, block, 0, s, qkv, keymask, B, S, H, G, out);
+    } else return hipErrorInvalidValue;
     return hipGetLastError();
 }
 

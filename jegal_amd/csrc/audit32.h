@@ -27,11 +27,11 @@ struct Gemm32Args {
     long ldc;
     int act;              // 0 none, 1 ReLU, 2 exact GELU
 };
-hipError_t launch_gemm32(const Gemm32Args& a, hipStream_t s, char* kname = nullptr);     // kname: EngineOpts::kname
+hipError_t launch_gemm32(const Gemm32Args& a, hipStream_t s);
 
 // softmax(q k^T / sqrt(dk) masked_fill(mask == 0, -1e9)) v per (sequence, head): qkv [B*S][3*H*dk] fp32 (q | k | v), keymask (B,S) fp32 or
 // nullptr, out [B*S][H*dk].  dk = 64 or 96.
-hipError_t launch_attention32(const float* qkv, const float* keymask, int B, int S, int H, int dk, float* out, hipStream_t s, char* kname = nullptr);
+hipError_t launch_attention32(const float* qkv, const float* keymask, int B, int S, int H, int dk, float* out, hipStream_t s);
 
 // S[b][p][h][w][16] = frame(clamp(p + dt - pad))[h][w][c] (dt < 5, c < 3; slot 15 zero); u8 sources are divided by 255 in fp32 like
 // inference_embs.py:282

@@ -306,42 +306,49 @@ __global__ __launch_bounds__(256) void zero_tail32_kernel(float* __restrict__ x,
 }  // namespace
 
 template <int BT>
-static hipError_t launch_gemm32_bt(const Gemm32Args& a, hipStream_t s, char* kname) {
+static hipError_t launch_gemm32_bt(const Gemm32Args& a, hipStream_t s) {
     const long mt = (a.M + BT - 1) / BT, nt = (a.N + BT - 1) / BT;
     const dim3 grid((unsigned)(mt * nt)), block(256);
     const bool walign = (a.ldw & 3) == 0 && ((uintptr_t)a.W & 15) == 0 && ((uintptr_t)a.A & 15) == 0;
     if (a.conv) {
         if ((1 << a.g.cshift) != a.g.C || a.g.rowmap || a.g.const_in) return hipErrorInvalidValue;
-        const bool v4 = walign && (a.g.C & 3) == 0;
-        record_kernel(kname, "gemm32_kernel<1,%d,%d>", (int)v4, BT);
-        if (v4) hipLaunchKernelGGL((gemm32_kernel<true, true, BT>), grid, block, 0, s, a);
-        else hipLaunchKernelGGL((gemm32_kernel<true, false, BT>), grid, block, 0, s, a);
+        if (walign && (a.g.C & 3) == 0) {
+            record_kernel("gemm32_kernel<1,1,%d>", BT);
+            hipLaunchKernelGGL((gemm32_kernel<true, true, BT>), grid, block, 0, s, a);
+        } else {
+            record_kernel("gemm32_kernel<1,0,%d>", BT);
+            hipLaunchKernelGGL((gemm32_kernel<true, false, BT>), grid, block, 0, s, a);
+        }
+    } else if (walign && (a.lda & 3) == 0 && (a.K & 3) == 0) {
+        record_kernel("gemm32_kernel<0,1,%d>", BT);
+        hipLaunchKernelGGL((gemm32_kernel<false, true, BT>), grid, block, 0, s, a);
     } else {
-        const bool v4 = walign && (a.lda & 3) == 0 && (a.K & 3) == 0;
-        record_kernel(kname, "gemm32_kernel<0,%d,%d>", (int)v4, BT);
-        if (v4) hipLaunchKernelGGL((gemm32_kernel<false, true, BT>), grid, block, 0, s, a);
-        else hipLaunchKernelGGL((gemm32_kernel<false, false, BT>), grid, block, 0, s, a);
+        record_kernel("gemm32_kernel<0,0,%d>", BT);
+        hipLaunchKernelGGL((gemm32_kernel<false, false, BT>), grid, block, 0, s, a);
     }
     return hipGetLastError();
 }
 
-hipError_t launch_gemm32(const Gemm32Args& a, hipStream_t s, char* kname) {
+hipError_t launch_gemm32(const Gemm32Args& a, hipStream_t s) {
     if (a.M <= 0 || a.N <= 0) return hipSuccess;
     if (a.K <= 0 || !a.A || !a.W || !a.out) return hipErrorInvalidValue;
     // fewer than ~1.5 rounds of 128 x 128 tiles on 256 CUs: 64 x 64 tiles (the small-M launches of the JEGAL branch)
     const long tiles128 = (long)((a.M + 127) / 128) * ((a.N + 127) / 128);
-    if (tiles128 < 384) return launch_gemm32_bt<64>(a, s, kname);
-    return launch_gemm32_bt<128>(a, s, kname);
+    if (tiles128 < 384) return launch_gemm32_bt<64>(a, s);
+    return launch_gemm32_bt<128>(a, s);
 }
 
-hipError_t launch_attention32(const float* qkv, const float* keymask, int B, int S, int H, int dk, float* out, hipStream_t s, char* kname) {
+hipError_t launch_attention32(const float* qkv, const float* keymask, int B, int S, int H, int dk, float* out, hipStream_t s) {
     if (B <= 0 || S <= 0) return hipSuccess;
     const int threads = S >= 256 ? 256 : (S + 63) / 64 * 64;
     const dim3 grid((unsigned)(B * H), (unsigned)((S + threads - 1) / threads));
-    if (dk == 64 || dk == 96) record_kernel(kname, "attention32_kernel<%d>", dk);
-    if (dk == 64) hipLaunchKernelGGL(attention32_kernel<64>, grid, dim3(threads), 0, s, qkv, keymask, S, H, out);
-    else if (dk == 96) hipLaunchKernelGGL(attention32_kernel<96>, grid, dim3(threads), 0, s, qkv, keymask, S, H, out);
-    else return hipErrorInvalidValue;
+    if (dk == 64) {
+        record_kernel("attention32_kernel<64>");
+        hipLaunchKernelGGL(attention32_kernel<64>, grid, dim3(threads), 0, s, qkv, keymask, S, H, out);
+    } else if (dk == 96) {
+        record_kernel("attention32_kernel<96>");
+        hipLaunchKernelGGL(attention32_kernel<96>, grid, dim3(threads), 0, s, qkv, keymask, S, H, out);
+    } else return hipErrorInvalidValue;
     return hipGetLastError();
 }
 
@@ -349,10 +356,13 @@ hipError_t launch_stack_frames32(const void* src, int src_is_u8, long sb, long s
                                  float* dst, hipStream_t s) {
     const long total = (long)B * (T + 2 * pad - 4) * H * W;
     if (total <= 0) return hipSuccess;
-    if (src_is_u8)
+    if (src_is_u8) {
+        record_kernel("stack_frames32_kernel<uint8_t>");
         hipLaunchKernelGGL(stack_frames32_kernel<uint8_t>, dim3(grid_for(total)), dim3(256), 0, s, (const uint8_t*)src, sb, st, sh, sw, sc, B, T, pad, H, W, dst);
-    else
+    } else {
+        record_kernel("stack_frames32_kernel<float>");
         hipLaunchKernelGGL(stack_frames32_kernel<float>, dim3(grid_for(total)), dim3(256), 0, s, (const float*)src, sb, st, sh, sw, sc, B, T, pad, H, W, dst);
+    }
     return hipGetLastError();
 }
 
@@ -361,6 +371,7 @@ hipError_t launch_maxpool3x3s2_32(const float* in, float* out, int N, int H, int
     const int OH = (H - 3) / 2 + 1, OW = (W - 3) / 2 + 1;
     const long total = (long)N * OH * OW * (C / 4);
     if (total <= 0) return hipSuccess;
+    record_kernel("maxpool32_kernel");
     hipLaunchKernelGGL(maxpool32_kernel, dim3(grid_for(total)), dim3(256), 0, s, in, out, N, H, W, C, OH, OW);
     return hipGetLastError();
 }
@@ -369,6 +380,7 @@ hipError_t launch_group_mean32(const float* in, int groups, int L, int D, float*
     if (D % 4) return hipErrorInvalidValue;
     const long total = (long)groups * (D / 4);
     if (total <= 0) return hipSuccess;
+    record_kernel("group_mean32_kernel");
     hipLaunchKernelGGL(group_mean32_kernel, dim3(grid_for(total)), dim3(256), 0, s, in, groups, L, D, out);
     return hipGetLastError();
 }
@@ -376,6 +388,7 @@ hipError_t launch_group_mean32(const float* in, int groups, int L, int D, float*
 hipError_t launch_zero_tail32(float* x, const int* valid, int halvings, int B, int H, long row_elems, hipStream_t s) {
     if (B <= 0 || H <= 0 || !valid) return hipSuccess;
     if (row_elems % 4) return hipErrorInvalidValue;
+    record_kernel("zero_tail32_kernel");
     hipLaunchKernelGGL(zero_tail32_kernel, dim3((unsigned)(B * H)), dim3(256), 0, s, x, valid, halvings, H, (int)(row_elems / 4));
     return hipGetLastError();
 }

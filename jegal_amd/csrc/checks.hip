@@ -6,10 +6,31 @@ using namespace engine;
 // ---- kernel check points: one launch of a production launcher on the caller's operands, with the handle's options (which pick
 // the instance exactly as in production) and the handle's build (fp16 or bf16).  The launcher's own shape rules decide what is
 // valid: its hipErrorInvalidValue comes back as JG_ERR_ARG, and nothing was launched then.  (Handle internals and LAUNCH: engine.h.)
+// Which instance ran is the launcher's word, not this file's: a check point begins with ENTER_CHECK, which makes the handle's name slot
+// the sink of record_kernel (shared.h) for the length of the call, and the launcher writes the name where it picks the instance.  No
+// kernel is named here.  A check point of several launches reports the last one; one that is refused, here or by the launcher, or that
+// fails reports "" (check_result).  jg_debug_gemm / jg_debug_gemm_ex only time launches and open no sink.
 // jg_debug_gemm_plan asks the GEMM planner (gemm_plan.h) the same question without a handle, a device or a launch, and
 // jg_debug_weight_form / jg_debug_gemm_runs_lo show which weights a layer's GEMM runs with (weight_form.h) in the same way.
 namespace {
+// the handle's name slot, emptied, as this thread's record_kernel sink until the check point returns
+struct KernelNameScope {
+    char* const prev = kernel_name_sink();
+    explicit KernelNameScope(char* slot) { slot[0] = 0; kernel_name_sink() = slot; }
+    ~KernelNameScope() { kernel_name_sink() = prev; }
+    KernelNameScope(const KernelNameScope&) = delete;
+};
+#define ENTER_CHECK(h) if (!(h)) return JG_ERR_ARG; const KernelNameScope _kn((h)->kname); ENTER(h)
+// option debug_lanes: the handle's options read as inside a two-lane batch (EngineOpts::lanes_active) until the check point returns.
+// Only the check points whose launchers read the flag take it: launch_gemm (plan_gemm) and, through gs_conv1_stage, launch_conv1_direct.
+struct DebugLanes {
+    jg_handle* const h;
+    explicit DebugLanes(jg_handle* h_) : h(h_) { h->opts.lanes_active = h->debug_lanes; }
+    ~DebugLanes() { h->opts.lanes_active = false; }
+    DebugLanes(const DebugLanes&) = delete;
+};
 int check_result(jg_handle* h, hipError_t e, const char* what) {
+    if (e != hipSuccess) h->kname[0] = 0;       // a refusal comes from in front of the launcher's record, a HIP failure may come from behind it
     if (e == hipErrorInvalidValue) JG_FAIL(h, JG_ERR_ARG, "%s: the launcher rejects this shape / argument set", what);
     if (e != hipSuccess) JG_FAIL(h, JG_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
     return JG_OK;
@@ -68,16 +89,16 @@ int jg_debug_conv_rows(jg_handle* h, int64_t* computed, int64_t* full) {
 }
 
 int jg_debug_conv1_pool(jg_handle* h, const void* frames_u8, int B, int T, int pad, void* out_f16) {
-    ENTER(h);
+    ENTER_CHECK(h);
     if (!h->gs.m.ready) JG_FAIL(h, JG_ERR_STATE, "GestSync weights not finalized");
     if (!frames_u8 || !out_f16 || B <= 0 || pad < 0 || pad > 12 || T + 2 * pad < 5)      // conv1's skip-mask area is sized for pad <= 12
         JG_FAIL(h, JG_ERR_ARG, "bad arguments (need 0 <= pad <= 12 and T + 2*pad >= 5)");
     RET(begin_pass(h));
     const long sw = 3, sh = (long)FW * 3, st = (long)FH * FW * 3, sb = (long)T * st;
     unsigned* zscr;
-    h->opts.lanes_active = h->debug_lanes;
+    const DebugLanes lanes(h);
     const int rc = gs_conv1_stage(h, frames_u8, 1, sb, st, sh, sw, 1, B, T, pad, static_cast<f16*>(out_f16), true, &zscr);
-    h->opts.lanes_active = false;
+    if (rc != JG_OK) h->kname[0] = 0;
     return rc;
 }
 
@@ -149,25 +170,21 @@ int jg_debug_gemm_ex(jg_handle* h, const void* a16, const void* w16, int M, int 
 }
 
 int jg_debug_gemm_check(jg_handle* h, const jg_gemm_check* c) {
-    ENTER(h);
-    h->kname[0] = 0;
+    ENTER_CHECK(h);
     if (!c || !c->A || !c->Wh || c->M <= 0 || c->N <= 0 || c->K <= 0 || c->lda < c->K || c->ldw < c->K || (!c->out32 && !c->out16) ||
         ((c->out32 || (c->out16 && !c->ln_w)) && c->ldc < c->N) || (c->res && (c->ldr < c->N || c->res_mod < 0)) ||
         (c->bias_clip && (c->rpc <= 0 || c->nclips <= 0)) || c->relu < 0 || c->relu > 2 || c->ln_mode < 0 || c->ln_mode > 2)
         JG_FAIL(h, JG_ERR_ARG, "jg_debug_gemm_check: bad arguments");
     const GemmArgs a = gemm_check_args(c);
-    EngineOpts o = h->opts;
-    o.kname = h->kname;          // the name slot the launchers write
-    o.lanes_active = h->debug_lanes;
-    return check_result(h, LAUNCH(h, launch_gemm, a, false, o, h->stream), "launch_gemm");
+    const DebugLanes lanes(h);
+    return check_result(h, LAUNCH(h, launch_gemm, a, false, h->opts, h->stream), "launch_gemm");
 }
 
 // One conv launch of launch_gemm.  With s2_host the launch runs as layer `op` of the row-skipping chain does in gs_conv_stack: the production
 // launch_conv_rowmaps builds the layer's compacted map in the workspace in front of the GEMM.  The planner is asked before anything is
 // enqueued, so a rejected argument set launches nothing at all.
 int jg_debug_conv_check(jg_handle* h, const jg_conv_check* c) {
-    ENTER(h);
-    h->kname[0] = 0;
+    ENTER_CHECK(h);
     if (!c || !c->in || !c->Wh || c->nimg <= 0 || c->H <= 0 || c->W <= 0 || c->C < 8 || (c->C & (c->C - 1)) || c->KH <= 0 || c->KW <= 0 || c->KH > 15 ||
         c->KW > 15 || c->SH <= 0 || c->SW <= 0 || c->PH < 0 || c->PW < 0 || c->H + 2 * c->PH < c->KH || c->W + 2 * c->PW < c->KW || c->N <= 0 ||
         (long)c->KH * c->KW * c->C != c->K || c->ldw < c->K || (!c->out32 && !c->out16) || c->ldc < c->N || c->relu < 0 || c->relu > 1 || c->op < 0 ||
@@ -188,14 +205,12 @@ int jg_debug_conv_check(jg_handle* h, const jg_conv_check* c) {
     a.M = (int)M; a.N = c->N; a.K = c->K;
     a.scale = c->scale; a.bias = c->bias; a.relu = c->relu;
     a.out32 = c->out32; a.out16 = static_cast<f16*>(c->out16); a.ldc = c->ldc;
-    EngineOpts o = h->opts;
-    o.kname = h->kname;          // the name slot the launchers write
-    o.lanes_active = h->debug_lanes;
+    const DebugLanes lanes(h);
     if (c->s2_host) {
         GemmShape q = gemm_shape(a, false);
         q.set_geom(g);
         q.rowmap = true; q.const_in = c->const_in != nullptr;
-        if (!plan_gemm(q, o).ok()) JG_FAIL(h, JG_ERR_ARG, "launch_gemm: the launcher rejects this shape / argument set");
+        if (!plan_gemm(q, h->opts).ok()) JG_FAIL(h, JG_ERR_ARG, "launch_gemm: the launcher rejects this shape / argument set");
         RET(begin_pass(h));
         int32_t* s2;
         ConvRowMap rm;
@@ -203,16 +218,14 @@ int jg_debug_conv_check(jg_handle* h, const jg_conv_check* c) {
         RET(wsalloc(h, (size_t)c->nimg, &s2));
         RET(rowmap_chain(h, c->nimg, 1, &g.OH, &g.OW, c->op, &rm, &g, &cin));
         RET(upload_i32_async(h, c->s2_host, (size_t)c->nimg, s2));
-        const int rc = check_result(h, launch_conv_rowmaps(s2, c->nimg, &rm, 1, h->stream), "launch_conv_rowmaps");
-        if (rc != JG_OK) return rc;
+        RET(check_result(h, launch_conv_rowmaps(s2, c->nimg, &rm, 1, h->stream), "launch_conv_rowmaps"));
     }
     a.g = g;
-    return check_result(h, LAUNCH(h, launch_gemm, a, true, o, h->stream), "launch_gemm");
+    return check_result(h, LAUNCH(h, launch_gemm, a, true, h->opts, h->stream), "launch_gemm");
 }
 
 int jg_debug_maxpool(jg_handle* h, const void* in, int nimg, int H, int W, int C, const int32_t* s2_host, int in_op, const void* const_in, void* out) {
-    ENTER(h);
-    h->kname[0] = 0;
+    ENTER_CHECK(h);
     if (!in || !out || nimg <= 0 || H < 3 || W < 3 || C <= 0 || C % 8 || (s2_host != nullptr) != (const_in != nullptr) || in_op < 0 || in_op > 3)
         JG_FAIL(h, JG_ERR_ARG, "jg_debug_maxpool: bad arguments (C %% 8 == 0, H, W >= 3, s2_host and const_in together, in_op 0..3)");
     int32_t* s2 = nullptr;
@@ -224,36 +237,31 @@ int jg_debug_maxpool(jg_handle* h, const void* in, int nimg, int H, int W, int C
         RET(wsalloc(h, (size_t)nimg, &s2));
         RET(upload_i32_async(h, s2_host, (size_t)nimg, s2));
     }
-    const int rc = check_result(h, LAUNCH(h, launch_maxpool3x3s2, static_cast<const f16*>(in), static_cast<f16*>(out), nimg, H, W, C, h->stream,
-                                          static_cast<const int*>(s2), in_op, static_cast<const f16*>(const_in)), "launch_maxpool3x3s2");
-    if (rc == JG_OK) record_kernel(h->kname, "%s", "maxpool_kernel");
-    return rc;
+    return check_result(h, LAUNCH(h, launch_maxpool3x3s2, static_cast<const f16*>(in), static_cast<f16*>(out), nimg, H, W, C, h->stream,
+                                  static_cast<const int*>(s2), in_op, static_cast<const f16*>(const_in)), "launch_maxpool3x3s2");
 }
 
 int jg_debug_gsa_conv1_pool(jg_handle* h, const float* src, int clip_form, int B, int Tm, int T, const int32_t* valid_host, const float* w,
                             const float* shift, void* out, int out_f32) {
-    ENTER(h);
-    h->kname[0] = 0;
+    ENTER_CHECK(h);
     if (!src || !w || !shift || !out || B <= 0 || T <= 0 || (clip_form && Tm <= 0) || (!clip_form && (T != 1 || valid_host)) || !al(out, 16))
         JG_FAIL(h, JG_ERR_ARG, "jg_debug_gsa_conv1_pool: bad arguments (window form: T = 1 and no valid_host)");
     for (int b = 0; valid_host && b < B; ++b)
         if (valid_host[b] < 1 || valid_host[b] > Tm) JG_FAIL(h, JG_ERR_ARG, "jg_debug_gsa_conv1_pool: valid[%d] = %d outside 1..Tm = %d", b, valid_host[b], Tm);
     int32_t* valid = nullptr;
     if (valid_host) RET(upload_valid(h, valid_host, B, &valid));
-    return check_result(h, launch_gsa_conv1_pool(src, clip_form, 0, B * T, T, Tm, valid, w, shift, out, out_f32, h->stream, h->kname), "launch_gsa_conv1_pool");
+    return check_result(h, launch_gsa_conv1_pool(src, clip_form, 0, B * T, T, Tm, valid, w, shift, out, out_f32, h->stream), "launch_gsa_conv1_pool");
 }
 
 int jg_debug_maxpool_2x3(jg_handle* h, const void* in, int nimg, int H, int W, int C, void* out, int f32) {
-    ENTER(h);
-    h->kname[0] = 0;
+    ENTER_CHECK(h);
     if (!in || !out || nimg <= 0) JG_FAIL(h, JG_ERR_ARG, "jg_debug_maxpool_2x3: bad arguments");
-    return check_result(h, launch_maxpool_2x3_s2(in, out, nimg, H, W, C, f32, h->stream, h->kname), "launch_maxpool_2x3_s2");
+    return check_result(h, launch_maxpool_2x3_s2(in, out, nimg, H, W, C, f32, h->stream), "launch_maxpool_2x3_s2");
 }
 
 int jg_debug_conv_rowmaps(jg_handle* h, const int32_t* s2_host, int NF, const int* OH, const int* OW, int nlayers, int32_t* const* map_host,
                           int32_t* const* base_host, int32_t* total_host) {
-    ENTER(h);
-    h->kname[0] = 0;
+    ENTER_CHECK(h);
     if (!s2_host || !OH || !OW || !map_host || !base_host || !total_host || NF <= 0) JG_FAIL(h, JG_ERR_ARG, "jg_debug_conv_rowmaps: bad arguments");
     if (nlayers < 1 || nlayers > 4) JG_FAIL(h, JG_ERR_ARG, "launch_conv_rowmaps: the launcher rejects this shape / argument set");
     for (int l = 0; l < nlayers; ++l) {
@@ -270,9 +278,7 @@ int jg_debug_conv_rowmaps(jg_handle* h, const int32_t* s2_host, int NF, const in
     RET(upload_i32_async(h, s2_host, (size_t)NF, s2));
     for (int l = 0; l < nlayers; ++l)      // the caller's fill: the launch writes the first *total entries only (on the stream: behind the pass's poison)
         HIPCHK(h, hipMemcpyAsync(rm[l].map, map_host[l], (size_t)NF * OH[l] * OW[l] * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    const int rc = check_result(h, launch_conv_rowmaps(s2, NF, rm, nlayers, h->stream), "launch_conv_rowmaps");
-    if (rc != JG_OK) return rc;
-    record_kernel(h->kname, "%s", "conv_rowmap_scan_kernel+conv_rowmap_fill_kernel");
+    RET(check_result(h, launch_conv_rowmaps(s2, NF, rm, nlayers, h->stream), "launch_conv_rowmaps"));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     for (int l = 0; l < nlayers; ++l) {
         HIPCHK(h, hipMemcpy(map_host[l], rm[l].map, (size_t)NF * OH[l] * OW[l] * sizeof(int), hipMemcpyDeviceToHost));
@@ -381,23 +387,21 @@ int jg_debug_bias_correction(const float* w32, const float* b32, const float* mu
 
 int jg_debug_gemm32(jg_handle* h, const float* A, int64_t lda, const float* W, int64_t ldw, int M, int N, int K, const float* scale,
                     const float* bias, const float* res, int64_t ldr, int res_mod, int act, float* out, int64_t ldc) {
-    ENTER(h);
-    h->kname[0] = 0;
+    ENTER_CHECK(h);
     if (!A || !W || !out || M <= 0 || N <= 0 || K <= 0 || lda < K || ldw < K || ldc < N || (res && (ldr < N || res_mod < 0)) || act < 0 || act > 2)
         JG_FAIL(h, JG_ERR_ARG, "jg_debug_gemm32: bad arguments");
     Gemm32Args a;
     std::memset(&a, 0, sizeof(a));
     a.A = A; a.lda = lda; a.W = W; a.ldw = ldw; a.M = M; a.N = N; a.K = K;
     a.scale = scale; a.bias = bias; a.res = res; a.ldr = ldr; a.res_mod = res_mod; a.out = out; a.ldc = ldc; a.act = act;
-    return check_result(h, launch_gemm32(a, h->stream, h->kname), "launch_gemm32");
+    return check_result(h, launch_gemm32(a, h->stream), "launch_gemm32");
 }
 
 // The conv form of launch_gemm32 (the fp32 implicit GEMM of the audit mode; tests/test_gpu_audit32_fp64.py).  C is any power of two >= 1 --
 // the launcher's own rule, so another C comes back through check_result; everything else that could leave the caller's buffers is refused here.
 int jg_debug_conv32(jg_handle* h, const float* in, int nimg, int H, int W, int C, int KH, int KW, int SH, int SW, int PH, int PW, int reorder,
                     const float* Wt, int64_t ldw, int N, const float* scale, const float* bias, int act, float* out, int64_t ldc) {
-    ENTER(h);
-    h->kname[0] = 0;
+    ENTER_CHECK(h);
     if (!in || !Wt || !out || nimg <= 0 || H <= 0 || W <= 0 || C <= 0 || KH <= 0 || KW <= 0 || KH > 15 || KW > 15 || SH <= 0 || SW <= 0 || PH < 0 ||
         PW < 0 || H + 2 * PH < KH || W + 2 * PW < KW || N <= 0 || (long)KH * KW * C >= (1L << 31) || ldw < (long)KH * KW * C || ldc < N || act < 0 ||
         act > 2)
@@ -409,13 +413,12 @@ int jg_debug_conv32(jg_handle* h, const float* in, int nimg, int H, int W, int C
     std::memset(&a, 0, sizeof(a));
     a.A = in; a.g = g; a.conv = 1; a.W = Wt; a.ldw = ldw; a.M = (int)M; a.N = N; a.K = KH * KW * C;
     a.scale = scale; a.bias = bias; a.out = out; a.ldc = ldc; a.act = act;
-    return check_result(h, launch_gemm32(a, h->stream, h->kname), "launch_gemm32");
+    return check_result(h, launch_gemm32(a, h->stream), "launch_gemm32");
 }
 
 int jg_debug_gemm_x3(jg_handle* h, const float* A, int64_t lda, const void* Wh, const void* Wl, int64_t ldw, int M, int N, int K,
                      const float* bias, const float* res, int64_t ldr, int res_mod, int relu, float* out, int64_t ldc) {
-    ENTER(h);
-    h->kname[0] = 0;
+    ENTER_CHECK(h);
     if (!A || !Wh || !Wl || !out || M <= 0 || N <= 0 || K <= 0 || lda < K || ldw < K || ldc < N || (res && (ldr < N || res_mod < 0)) ||
         relu < 0 || relu > 1)
         JG_FAIL(h, JG_ERR_ARG, "jg_debug_gemm_x3: bad arguments");
@@ -423,35 +426,30 @@ int jg_debug_gemm_x3(jg_handle* h, const float* A, int64_t lda, const void* Wh, 
     std::memset(&a, 0, sizeof(a));
     a.A = A; a.lda = lda; a.Wh = static_cast<const f16*>(Wh); a.Wl = static_cast<const f16*>(Wl); a.ldw = ldw; a.M = M; a.N = N; a.K = K;
     a.bias = bias; a.res = res; a.ldr = ldr; a.res_mod = res_mod; a.out = out; a.ldc = ldc; a.relu = relu;
-    return check_result(h, launch_gemm_x3(a, h->stream, h->kname), "launch_gemm_x3");
+    return check_result(h, launch_gemm_x3(a, h->stream), "launch_gemm_x3");
 }
 
 int jg_debug_attention(jg_handle* h, const void* qkv, const float* keymask, int B, int S, int H, int dk, void* out) {
-    ENTER(h);
-    h->kname[0] = 0;
+    ENTER_CHECK(h);
     if (!qkv || !out || B <= 0 || S <= 0 || H <= 0 || (dk != 64 && dk != 96)) JG_FAIL(h, JG_ERR_ARG, "jg_debug_attention: bad arguments");
-    EngineOpts o = h->opts;
-    o.kname = h->kname;          // the name slot the launchers write
-    return check_result(h, LAUNCH(h, launch_attention, static_cast<const f16*>(qkv), keymask, B, S, H, dk, static_cast<f16*>(out), o, h->stream),
+    return check_result(h, LAUNCH(h, launch_attention, static_cast<const f16*>(qkv), keymask, B, S, H, dk, static_cast<f16*>(out), h->opts, h->stream),
                         "launch_attention");
 }
 
 int jg_debug_attention_gather(jg_handle* h, const void* qkv_pos, const void* pe_qkv, int Twin, int P, int shift, int B, int S, int H, void* out) {
-    ENTER(h);
-    h->kname[0] = 0;
+    ENTER_CHECK(h);
     if (!qkv_pos || !pe_qkv || !out || B <= 0 || S <= 0 || H <= 0 || Twin <= 0 || P <= 0 || B % Twin)
         JG_FAIL(h, JG_ERR_ARG, "jg_debug_attention_gather: bad arguments (B must be a multiple of Twin)");
     if (h->bf16) JG_FAIL(h, JG_ERR_STATE, "jg_debug_attention_gather: the gather form is an fp16-build kernel (the clip path's layer 0)");
     const AttnGather g{static_cast<const f16*>(pe_qkv), Twin, P, shift};
-    return check_result(h, launch_attention_gather(static_cast<const f16*>(qkv_pos), g, B, S, H, static_cast<f16*>(out), h->stream, h->kname),
+    return check_result(h, launch_attention_gather(static_cast<const f16*>(qkv_pos), g, B, S, H, static_cast<f16*>(out), h->stream),
                         "launch_attention_gather");
 }
 
 int jg_debug_attention32(jg_handle* h, const float* qkv, const float* keymask, int B, int S, int H, int dk, float* out) {
-    ENTER(h);
-    h->kname[0] = 0;
+    ENTER_CHECK(h);
     if (!qkv || !out || B <= 0 || S <= 0 || H <= 0) JG_FAIL(h, JG_ERR_ARG, "jg_debug_attention32: bad arguments");
-    return check_result(h, launch_attention32(qkv, keymask, B, S, H, dk, out, h->stream, h->kname), "launch_attention32");
+    return check_result(h, launch_attention32(qkv, keymask, B, S, H, dk, out, h->stream), "launch_attention32");
 }
 
 // ---- the element-wise and reduction launchers (elementwise.hip, elementwise_f32.hip, elementwise_fp16.hip; tests/test_gpu_elementwise_fp64.py).
@@ -460,237 +458,176 @@ int jg_debug_attention32(jg_handle* h, const float* qkv, const float* keymask, i
 // length); the shape rules the launcher itself carries come back through check_result.  Nothing is enqueued in either case.
 int jg_debug_stack_frames(jg_handle* h, const void* src, int src_is_u8, int64_t sb, int64_t st, int64_t sh, int64_t sw, int64_t sc, int64_t src_elems,
                           int B, int T, int pad, int H, int W, void* dst) {
-    ENTER(h);
-    h->kname[0] = 0;
+    ENTER_CHECK(h);
     if (!src || !dst || B <= 0 || T <= 0 || H <= 0 || W <= 0 || pad < 0 || T + 2 * pad < 5 || sb < 0 || st < 0 || sh < 0 || sw < 0 || sc < 0 ||
         (src_is_u8 != 0 && src_is_u8 != 1) || !al(dst, 16) || (!src_is_u8 && !al(src, 4)) ||
         (B - 1) * sb + (T - 1) * st + (H - 1) * sh + (W - 1) * sw + 2 * sc >= src_elems)
         JG_FAIL(h, JG_ERR_ARG, "jg_debug_stack_frames: bad arguments (T + 2 pad >= 5, strides >= 0 and inside src_elems, dst 16-byte aligned)");
-    const int rc = check_result(h, LAUNCH(h, launch_stack_frames, src, src_is_u8, (long)sb, (long)st, (long)sh, (long)sw, (long)sc, B, T, pad, H, W,
-                                          static_cast<f16*>(dst), h->stream), "launch_stack_frames");
-    if (rc == JG_OK) record_kernel(h->kname, "stack_frames_kernel<%s>", src_is_u8 ? "uint8_t" : "float");
-    return rc;
+    return check_result(h, LAUNCH(h, launch_stack_frames, src, src_is_u8, (long)sb, (long)st, (long)sh, (long)sw, (long)sc, B, T, pad, H, W,
+                                  static_cast<f16*>(dst), h->stream), "launch_stack_frames");
 }
 
 int jg_debug_window_gather(jg_handle* h, const float* conv, const float* pe, int B, int P, int Twin, int L, int D, int shift, int tiled, float* x32,
                            void* x16) {
-    ENTER(h);
-    h->kname[0] = 0;
+    ENTER_CHECK(h);
     if (!conv || !pe || B <= 0 || D <= 0 || shift < 0 || (tiled ? !x16 : !x32) || !al(conv, 16) || !al(pe, 16) || !al(x32, 16) || !al(x16, 8))
         JG_FAIL(h, JG_ERR_ARG, "jg_debug_window_gather: bad arguments (tiled: x16, row-major: x32; 16-byte aligned fp32 rows)");
-    const int rc = check_result(h, LAUNCH(h, launch_window_gather, conv, pe, B, P, Twin, L, D, shift, tiled != 0, x32, static_cast<f16*>(x16), h->stream),
-                                "launch_window_gather");
-    if (rc == JG_OK) record_kernel(h->kname, "%s", tiled ? "window_gather_tiled_kernel" : "window_gather_kernel");
-    return rc;
+    return check_result(h, LAUNCH(h, launch_window_gather, conv, pe, B, P, Twin, L, D, shift, tiled != 0, x32, static_cast<f16*>(x16), h->stream),
+                        "launch_window_gather");
 }
 
 int jg_debug_layernorm(jg_handle* h, const float* in, const float* w, const float* b, int rows, int D, int flavour, int relu, float* out32, void* out16) {
-    ENTER(h);
-    h->kname[0] = 0;
+    ENTER_CHECK(h);
     if (!in || !w || !b || rows <= 0 || D <= 0 || (!out32 && !out16) || (flavour != LN_STD && flavour != LN_ANNOTATED) || relu < 0 || relu > 1 ||
         !al(in, 16) || !al(w, 16) || !al(b, 16) || !al(out32, 16) || !al(out16, 8))
         JG_FAIL(h, JG_ERR_ARG, "jg_debug_layernorm: bad arguments (flavour 0 / 1, relu 0 / 1, out32 and / or out16, 16-byte aligned rows)");
-    const int rc = check_result(h, LAUNCH(h, launch_layernorm, in, w, b, rows, D, flavour, relu, out32, static_cast<f16*>(out16), h->stream), "launch_layernorm");
-    if (rc == JG_OK) record_kernel(h->kname, "layernorm_kernel<%d>", D / 256);
-    return rc;
+    return check_result(h, LAUNCH(h, launch_layernorm, in, w, b, rows, D, flavour, relu, out32, static_cast<f16*>(out16), h->stream), "launch_layernorm");
 }
 
 int jg_debug_layernorm_planes(jg_handle* h, const void* hi, const void* lo, const float* w, const float* b, int rows, int D, float* out32) {
-    ENTER(h);
-    h->kname[0] = 0;
+    ENTER_CHECK(h);
     if (!hi || !lo || !w || !b || !out32 || rows <= 0 || D <= 0 || !al(hi, 8) || !al(lo, 8) || !al(w, 16) || !al(b, 16) || !al(out32, 16))
         JG_FAIL(h, JG_ERR_ARG, "jg_debug_layernorm_planes: bad arguments");
-    const int rc = check_result(h, LAUNCH(h, launch_layernorm_planes, static_cast<const f16*>(hi), static_cast<const f16*>(lo), w, b, rows, D, out32, h->stream),
-                                "launch_layernorm_planes");
-    if (rc == JG_OK) record_kernel(h->kname, "layernorm_planes_kernel<%d>", D / 256);
-    return rc;
+    return check_result(h, LAUNCH(h, launch_layernorm_planes, static_cast<const f16*>(hi), static_cast<const f16*>(lo), w, b, rows, D, out32, h->stream),
+                        "launch_layernorm_planes");
 }
 
 int jg_debug_group_mean(jg_handle* h, const void* in, int groups, int L, int D, void* out) {
-    ENTER(h);
-    h->kname[0] = 0;
+    ENTER_CHECK(h);
     if (!in || !out || groups <= 0 || D <= 0 || !al(in, 16) || !al(out, 16)) JG_FAIL(h, JG_ERR_ARG, "jg_debug_group_mean: bad arguments");
-    const int rc = check_result(h, LAUNCH(h, launch_group_mean, static_cast<const f16*>(in), groups, L, D, static_cast<f16*>(out), h->stream), "launch_group_mean");
-    if (rc == JG_OK) record_kernel(h->kname, "%s", "group_mean_kernel");
-    return rc;
+    return check_result(h, LAUNCH(h, launch_group_mean, static_cast<const f16*>(in), groups, L, D, static_cast<f16*>(out), h->stream), "launch_group_mean");
 }
 
 int jg_debug_cast(jg_handle* h, const float* in, void* out, int64_t n) {
-    ENTER(h);
-    h->kname[0] = 0;
+    ENTER_CHECK(h);
     if (!in || !out || n <= 0 || !al(in, 16) || !al(out, 8)) JG_FAIL(h, JG_ERR_ARG, "jg_debug_cast: bad arguments");
-    const int rc = check_result(h, LAUNCH(h, launch_cast_f32_f16, in, static_cast<f16*>(out), (long)n, h->stream), "launch_cast_f32_f16");
-    if (rc == JG_OK) record_kernel(h->kname, "%s", "cast_kernel");
-    return rc;
+    return check_result(h, LAUNCH(h, launch_cast_f32_f16, in, static_cast<f16*>(out), (long)n, h->stream), "launch_cast_f32_f16");
 }
 
 int jg_debug_audio_conv0(jg_handle* h, const float* mel, int B, int Tm, int F, const void* wh, const void* wl, const float* bias, void* out,
                          const int32_t* valid_host, int n_valid) {
-    ENTER(h);
-    h->kname[0] = 0;
+    ENTER_CHECK(h);
     if (!mel || !wh || !bias || !out || B <= 0 || Tm <= 0 || F <= 0 || !al(out, 16) || (valid_host ? n_valid != B : n_valid != 0))
         JG_FAIL(h, JG_ERR_ARG, "jg_debug_audio_conv0: bad arguments (valid_host: one entry per clip)");
     if (F > 80) JG_FAIL(h, JG_ERR_ARG, "launch_audio_conv0: the launcher rejects this shape / argument set");      // before the upload: nothing enqueued
     int32_t* valid = nullptr;
     if (valid_host) RET(upload_valid(h, valid_host, B, &valid));
-    const int rc = check_result(h, LAUNCH(h, launch_audio_conv0, mel, B, Tm, F, static_cast<const f16*>(wh), static_cast<const f16*>(wl), bias,
-                                          static_cast<f16*>(out), static_cast<const int*>(valid), h->stream), "launch_audio_conv0");
-    if (rc == JG_OK) record_kernel(h->kname, "%s", "audio_conv0_kernel");
-    return rc;
+    return check_result(h, LAUNCH(h, launch_audio_conv0, mel, B, Tm, F, static_cast<const f16*>(wh), static_cast<const f16*>(wl), bias,
+                                  static_cast<f16*>(out), static_cast<const int*>(valid), h->stream), "launch_audio_conv0");
 }
 
 int jg_debug_zero_tail(jg_handle* h, void* x, const int32_t* valid_host, int n_valid, int halvings, int B, int H, int64_t row_elems) {
-    ENTER(h);
-    h->kname[0] = 0;
+    ENTER_CHECK(h);
     if (!x || !valid_host || B <= 0 || H <= 0 || n_valid != B || halvings < 0 || halvings > 30 || row_elems <= 0 || !al(x, 16))
         JG_FAIL(h, JG_ERR_ARG, "jg_debug_zero_tail: bad arguments (valid_host: one entry per clip)");
     if (row_elems % 8) JG_FAIL(h, JG_ERR_ARG, "launch_zero_tail: the launcher rejects this shape / argument set");     // before the upload: nothing enqueued
     int32_t* valid;
     RET(upload_valid(h, valid_host, B, &valid));
-    const int rc = check_result(h, LAUNCH(h, launch_zero_tail, static_cast<f16*>(x), static_cast<const int*>(valid), halvings, B, H, (long)row_elems, h->stream),
-                                "launch_zero_tail");
-    if (rc == JG_OK) record_kernel(h->kname, "%s", "zero_tail_kernel");
-    return rc;
+    return check_result(h, LAUNCH(h, launch_zero_tail, static_cast<f16*>(x), static_cast<const int*>(valid), halvings, B, H, (long)row_elems, h->stream),
+                        "launch_zero_tail");
 }
 
 // ---- the fp32 clones of the audit mode (audit32.hip; tests/test_gpu_audit32_fp64.py): the 16-bit entries' arguments and refusals, with the
 // 16-byte rules of the fp32 kernels (C % 4, D % 4, row_elems % 4) refused up front as well
 int jg_debug_stack_frames32(jg_handle* h, const void* src, int src_is_u8, int64_t sb, int64_t st, int64_t sh, int64_t sw, int64_t sc, int64_t src_elems,
                             int B, int T, int pad, int H, int W, float* dst) {
-    ENTER(h);
-    h->kname[0] = 0;
+    ENTER_CHECK(h);
     if (!src || !dst || B <= 0 || T <= 0 || H <= 0 || W <= 0 || pad < 0 || T + 2 * pad < 5 || sb < 0 || st < 0 || sh < 0 || sw < 0 || sc < 0 ||
         (src_is_u8 != 0 && src_is_u8 != 1) || !al(dst, 16) || (!src_is_u8 && !al(src, 4)) ||
         (B - 1) * sb + (T - 1) * st + (H - 1) * sh + (W - 1) * sw + 2 * sc >= src_elems)
         JG_FAIL(h, JG_ERR_ARG, "jg_debug_stack_frames32: bad arguments (T + 2 pad >= 5, strides >= 0 and inside src_elems, dst 16-byte aligned)");
-    const int rc = check_result(h, launch_stack_frames32(src, src_is_u8, (long)sb, (long)st, (long)sh, (long)sw, (long)sc, B, T, pad, H, W, dst, h->stream),
-                                "launch_stack_frames32");
-    if (rc == JG_OK) record_kernel(h->kname, "stack_frames32_kernel<%s>", src_is_u8 ? "uint8_t" : "float");
-    return rc;
+    return check_result(h, launch_stack_frames32(src, src_is_u8, (long)sb, (long)st, (long)sh, (long)sw, (long)sc, B, T, pad, H, W, dst, h->stream),
+                        "launch_stack_frames32");
 }
 
 int jg_debug_maxpool32(jg_handle* h, const float* in, int nimg, int H, int W, int C, float* out) {
-    ENTER(h);
-    h->kname[0] = 0;
+    ENTER_CHECK(h);
     if (!in || !out || nimg <= 0 || H < 3 || W < 3 || C <= 0 || C % 4 || !al(in, 16) || !al(out, 16))
         JG_FAIL(h, JG_ERR_ARG, "jg_debug_maxpool32: bad arguments (C %% 4 == 0, H, W >= 3, 16-byte aligned images)");
-    const int rc = check_result(h, launch_maxpool3x3s2_32(in, out, nimg, H, W, C, h->stream), "launch_maxpool3x3s2_32");
-    if (rc == JG_OK) record_kernel(h->kname, "%s", "maxpool32_kernel");
-    return rc;
+    return check_result(h, launch_maxpool3x3s2_32(in, out, nimg, H, W, C, h->stream), "launch_maxpool3x3s2_32");
 }
 
 int jg_debug_group_mean32(jg_handle* h, const float* in, int groups, int L, int D, float* out) {
-    ENTER(h);
-    h->kname[0] = 0;
+    ENTER_CHECK(h);
     if (!in || !out || groups <= 0 || L <= 0 || D <= 0 || D % 4 || !al(in, 16) || !al(out, 16))
         JG_FAIL(h, JG_ERR_ARG, "jg_debug_group_mean32: bad arguments (L > 0, D %% 4 == 0, 16-byte aligned rows)");
-    const int rc = check_result(h, launch_group_mean32(in, groups, L, D, out, h->stream), "launch_group_mean32");
-    if (rc == JG_OK) record_kernel(h->kname, "%s", "group_mean32_kernel");
-    return rc;
+    return check_result(h, launch_group_mean32(in, groups, L, D, out, h->stream), "launch_group_mean32");
 }
 
 int jg_debug_zero_tail32(jg_handle* h, float* x, const int32_t* valid_host, int n_valid, int halvings, int B, int H, int64_t row_elems) {
-    ENTER(h);
-    h->kname[0] = 0;
+    ENTER_CHECK(h);
     if (!x || !valid_host || B <= 0 || H <= 0 || n_valid != B || halvings < 0 || halvings > 30 || row_elems <= 0 || row_elems % 4 || !al(x, 16))
         JG_FAIL(h, JG_ERR_ARG, "jg_debug_zero_tail32: bad arguments (valid_host: one entry per clip; row_elems %% 4 == 0)");
     int32_t* valid;
     RET(upload_valid(h, valid_host, B, &valid));
-    const int rc = check_result(h, launch_zero_tail32(x, static_cast<const int*>(valid), halvings, B, H, (long)row_elems, h->stream), "launch_zero_tail32");
-    if (rc == JG_OK) record_kernel(h->kname, "%s", "zero_tail32_kernel");
-    return rc;
+    return check_result(h, launch_zero_tail32(x, static_cast<const int*>(valid), halvings, B, H, (long)row_elems, h->stream), "launch_zero_tail32");
 }
 
 int jg_debug_xlmr_embed(jg_handle* h, const int32_t* ids, int B, int L, int D, int pad_id, int vocab, int maxpos, const float* word, const float* pos,
                         const float* type, float* out) {
-    ENTER(h);
-    h->kname[0] = 0;
+    ENTER_CHECK(h);
     if (!ids || !word || !pos || !type || !out || B <= 0 || L <= 0 || D <= 0 || vocab <= 0 || maxpos <= 0 || pad_id < 0 || pad_id >= maxpos ||
         !al(word, 16) || !al(pos, 16) || !al(type, 16) || !al(out, 16))
         JG_FAIL(h, JG_ERR_ARG, "jg_debug_xlmr_embed: bad arguments (0 <= pad_id < maxpos)");
-    const int rc = check_result(h, launch_xlmr_embed(ids, B, L, D, pad_id, vocab, maxpos, word, pos, type, out, h->stream), "launch_xlmr_embed");
-    if (rc == JG_OK) record_kernel(h->kname, "%s", "xlmr_embed_kernel");
-    return rc;
+    return check_result(h, launch_xlmr_embed(ids, B, L, D, pad_id, vocab, maxpos, word, pos, type, out, h->stream), "launch_xlmr_embed");
 }
 
 int jg_debug_xlmr_embed_planes(jg_handle* h, const int32_t* ids, int B, int L, int D, int pad_id, int vocab, int maxpos, const float* word,
                                const float* pos, const float* type, void* hi, void* lo, float* part) {
-    ENTER(h);
-    h->kname[0] = 0;
+    ENTER_CHECK(h);
     if (!ids || !word || !pos || !type || !hi || !lo || !part || B <= 0 || L <= 0 || D <= 0 || vocab <= 0 || maxpos <= 0 || pad_id < 0 || pad_id >= maxpos ||
         !al(word, 16) || !al(pos, 16) || !al(type, 16) || !al(hi, 8) || !al(lo, 8) || !al(part, 8))
         JG_FAIL(h, JG_ERR_ARG, "jg_debug_xlmr_embed_planes: bad arguments (0 <= pad_id < maxpos)");
-    const int rc = check_result(h, LAUNCH(h, launch_xlmr_embed_planes, ids, B, L, D, pad_id, vocab, maxpos, word, pos, type, static_cast<f16*>(hi),
-                                          static_cast<f16*>(lo), part, h->stream), "launch_xlmr_embed_planes");
-    if (rc == JG_OK) record_kernel(h->kname, "%s", "xlmr_embed_planes_kernel");
-    return rc;
+    return check_result(h, LAUNCH(h, launch_xlmr_embed_planes, ids, B, L, D, pad_id, vocab, maxpos, word, pos, type, static_cast<f16*>(hi),
+                                  static_cast<f16*>(lo), part, h->stream), "launch_xlmr_embed_planes");
 }
 
 int jg_debug_ln_stats(jg_handle* h, const float* part, int rows, int P, float* stats) {
-    ENTER(h);
-    h->kname[0] = 0;
+    ENTER_CHECK(h);
     if (!part || !stats || rows <= 0 || P <= 0 || !al(part, 8) || !al(stats, 8)) JG_FAIL(h, JG_ERR_ARG, "jg_debug_ln_stats: bad arguments");
-    const int rc = check_result(h, launch_ln_stats(part, rows, P, stats, h->stream), "launch_ln_stats");
-    if (rc == JG_OK) record_kernel(h->kname, "%s", "ln_stats_kernel");
-    return rc;
+    return check_result(h, launch_ln_stats(part, rows, P, stats, h->stream), "launch_ln_stats");
 }
 
 int jg_debug_mask_i32_f32(jg_handle* h, const int32_t* in, float* out, int64_t n) {
-    ENTER(h);
-    h->kname[0] = 0;
+    ENTER_CHECK(h);
     if (!in || !out || n <= 0) JG_FAIL(h, JG_ERR_ARG, "jg_debug_mask_i32_f32: bad arguments");
-    const int rc = check_result(h, launch_mask_i32_f32(in, out, (long)n, h->stream), "launch_mask_i32_f32");
-    if (rc == JG_OK) record_kernel(h->kname, "%s", "mask_i32_f32_kernel");
-    return rc;
+    return check_result(h, launch_mask_i32_f32(in, out, (long)n, h->stream), "launch_mask_i32_f32");
 }
 
 int jg_debug_transpose_tokens(jg_handle* h, const float* in, int N, int L, int D, float* out) {
-    ENTER(h);
-    h->kname[0] = 0;
+    ENTER_CHECK(h);
     if (!in || !out || N <= 0 || L <= 0 || D <= 0 || N > 65535 || (L + 31) / 32 > 65535)
         JG_FAIL(h, JG_ERR_ARG, "jg_debug_transpose_tokens: bad arguments (N and L / 32 are grid dimensions: <= 65535)");
-    const int rc = check_result(h, launch_transpose_tokens(in, N, L, D, out, h->stream), "launch_transpose_tokens");
-    if (rc == JG_OK) record_kernel(h->kname, "%s", "transpose_tokens_kernel");
-    return rc;
+    return check_result(h, launch_transpose_tokens(in, N, L, D, out, h->stream), "launch_transpose_tokens");
 }
 
 int jg_debug_pe_project(jg_handle* h, const float* pe, int S, const void* Wh, const void* Wl, const float* bias, int N, int K, void* out) {
-    ENTER(h);
-    h->kname[0] = 0;
+    ENTER_CHECK(h);
     if (!pe || !Wh || !out || S <= 0 || N <= 0 || K <= 0 || (long)S * N >= (1L << 31)) JG_FAIL(h, JG_ERR_ARG, "jg_debug_pe_project: bad arguments");
     FP16_ONLY(h, "jg_debug_pe_project");
-    const int rc = check_result(h, launch_pe_project(pe, S, static_cast<const f16*>(Wh), static_cast<const f16*>(Wl), bias, N, K, static_cast<f16*>(out), h->stream),
-                                "launch_pe_project");
-    if (rc == JG_OK) record_kernel(h->kname, "%s", "pe_project_kernel");
-    return rc;
+    return check_result(h, launch_pe_project(pe, S, static_cast<const f16*>(Wh), static_cast<const f16*>(Wl), bias, N, K, static_cast<f16*>(out), h->stream),
+                        "launch_pe_project");
 }
 
 int jg_debug_broadcast_channels(jg_handle* h, const void* v, int C, void* out, int64_t pixels) {
-    ENTER(h);
-    h->kname[0] = 0;
+    ENTER_CHECK(h);
     if (!v || !out || C <= 0 || pixels <= 0) JG_FAIL(h, JG_ERR_ARG, "jg_debug_broadcast_channels: bad arguments");
     FP16_ONLY(h, "jg_debug_broadcast_channels");
-    const int rc = check_result(h, launch_broadcast_channels(static_cast<const f16*>(v), C, static_cast<f16*>(out), (long)pixels, h->stream),
-                                "launch_broadcast_channels");
-    if (rc == JG_OK) record_kernel(h->kname, "%s", "broadcast_channels_kernel");
-    return rc;
+    return check_result(h, launch_broadcast_channels(static_cast<const f16*>(v), C, static_cast<f16*>(out), (long)pixels, h->stream),
+                        "launch_broadcast_channels");
 }
 
 int jg_debug_col_sum(jg_handle* h, const void* A, int64_t lda, int M, int K, float* scratch, int64_t scratch_elems, float* out, const float* stats) {
-    ENTER(h);
-    h->kname[0] = 0;
+    ENTER_CHECK(h);
     if (!A || !scratch || !out || M <= 0 || K <= 0 || lda < K || lda % 8 || !al(A, 16) || scratch_elems < (int64_t)col_sum_scratch_elems(K))
         JG_FAIL(h, JG_ERR_ARG, "jg_debug_col_sum: bad arguments (lda >= K, lda %% 8 == 0, A 16-byte aligned, scratch of 64 K floats)");
     FP16_ONLY(h, "jg_debug_col_sum");
-    const int rc = check_result(h, launch_col_sum(static_cast<const f16*>(A), (long)lda, M, K, scratch, out, h->stream, stats), "launch_col_sum");
-    if (rc == JG_OK) record_kernel(h->kname, "%s", "col_sum_kernel+col_sum_finish_kernel");
-    return rc;
+    return check_result(h, launch_col_sum(static_cast<const f16*>(A), (long)lda, M, K, scratch, out, h->stream, stats), "launch_col_sum");
 }
 
 int jg_debug_rc_bias(jg_handle* h, const void* A, int64_t lda, int64_t a_elems, int tiled, int nclips, int rpc, const int32_t* valid_host, int n_valid,
                      const void* lo, const float* bias, int N, int K, float* scratch, int64_t scratch_elems, float* out) {
-    ENTER(h);
-    h->kname[0] = 0;
+    ENTER_CHECK(h);
     if (!A || !lo || !scratch || !out || nclips <= 0 || rpc <= 0 || N <= 0 || K <= 0 || !al(A, 16) || !al(lo, 16) || !al(scratch, 16) ||
         (valid_host ? n_valid != nclips : n_valid != 0) || (long)nclips * rpc >= (1L << 31) || scratch_elems < (int64_t)rc_scratch_elems(nclips, K))
         JG_FAIL(h, JG_ERR_ARG, "jg_debug_rc_bias: bad arguments (valid_host: one entry per clip; scratch of nclips K floats)");
@@ -701,32 +638,24 @@ int jg_debug_rc_bias(jg_handle* h, const void* A, int64_t lda, int64_t a_elems, 
     if (!rc_bias_ok(N, K, tiled)) JG_FAIL(h, JG_ERR_ARG, "launch_rc_bias: the launcher rejects this shape / argument set");      // before the upload: nothing enqueued
     int32_t* valid = nullptr;
     if (valid_host) RET(upload_valid(h, valid_host, nclips, &valid));
-    const int rc = check_result(h, launch_rc_bias(static_cast<const f16*>(A), (long)lda, tiled, nclips, rpc, static_cast<const int*>(valid),
-                                                  static_cast<const f16*>(lo), bias, N, K, scratch, out, h->stream), "launch_rc_bias");
-    if (rc == JG_OK) record_kernel(h->kname, "%s", "rc_col_mean_kernel+rc_gemv_kernel");
-    return rc;
+    return check_result(h, launch_rc_bias(static_cast<const f16*>(A), (long)lda, tiled, nclips, rpc, static_cast<const int*>(valid),
+                                          static_cast<const f16*>(lo), bias, N, K, scratch, out, h->stream), "launch_rc_bias");
 }
 
 int jg_debug_span_gather(jg_handle* h, const float* p32, const float* pe, const int32_t* table_dev, int n_windows, int span_max, int D, float* x32,
                          float* mask) {
-    ENTER(h);
-    h->kname[0] = 0;
+    ENTER_CHECK(h);
     if (!p32 || !pe || !table_dev || !x32 || !mask || n_windows < 1 || span_max < 1 || span_max > TRACK_SPAN_MAX || D <= 0 || !al(p32, 16) ||
         !al(pe, 16) || !al(table_dev, 16) || !al(x32, 16) || !al(mask, 4))
         JG_FAIL(h, JG_ERR_ARG, "jg_debug_span_gather: bad arguments (span_max 1..%d, 16-byte aligned fp32 rows and table)", TRACK_SPAN_MAX);
-    const int rc = check_result(h, launch_span_gather(p32, pe, table_dev, n_windows, span_max, D, x32, mask, h->stream), "launch_span_gather");
-    if (rc == JG_OK) record_kernel(h->kname, "%s", "span_gather_kernel");
-    return rc;
+    return check_result(h, launch_span_gather(p32, pe, table_dev, n_windows, span_max, D, x32, mask, h->stream), "launch_span_gather");
 }
 
 int jg_debug_core_compact(jg_handle* h, const void* in, int elem_bytes, const int32_t* table_dev, int n_windows, int span_max, int D, void* out) {
-    ENTER(h);
-    h->kname[0] = 0;
+    ENTER_CHECK(h);
     if (!in || !table_dev || !out || n_windows < 1 || span_max < 1 || D <= 0 || D % 4 || !al(in, 16) || !al(table_dev, 16) || !al(out, 16))
         JG_FAIL(h, JG_ERR_ARG, "jg_debug_core_compact: bad arguments (D %% 4 == 0, 16-byte aligned rows and table)");
-    const int rc = check_result(h, launch_core_compact(in, elem_bytes, table_dev, n_windows, span_max, D, out, h->stream), "launch_core_compact");
-    if (rc == JG_OK) record_kernel(h->kname, "%s", "core_compact_kernel");
-    return rc;
+    return check_result(h, launch_core_compact(in, elem_bytes, table_dev, n_windows, span_max, D, out, h->stream), "launch_core_compact");
 }
 
 int jg_debug_last_kernel(jg_handle* h, char* buf, int len) {

@@ -194,7 +194,7 @@ hipError_t launch_conv1_direct(const uint8_t* src, int nclip, int T, int pad, co
 hipError_t launch_conv1_edge_fix(f16* out_pooled, const f16* edge, long positions, hipStream_t s);
 // the 64 per-channel values relu(bias) that conv1 produces over an all-zero patch, as the kernel rounds them (-> const chain)
 hipError_t launch_conv1_zconst(const f16* Wd, float scale, f16* zconst, hipStream_t s);
-hipError_t launch_attention_gather(const f16* qkv_pos, const AttnGather& g, int B, int S, int H, f16* out, hipStream_t s, char* kname = nullptr);
+hipError_t launch_attention_gather(const f16* qkv_pos, const AttnGather& g, int B, int S, int H, f16* out, hipStream_t s);
 // pe_qkv[j][n] = sum_k W[n][k] pe[j][k] + bias[n]  (W = Wh (+ Wl), [N][K] fp16; pe [S][K] fp32): 21 x 1536 outputs
 hipError_t launch_pe_project(const float* pe, int S, const f16* Wh, const f16* Wl, const float* bias, int N, int K, f16* out, hipStream_t s);
 hipError_t launch_broadcast_channels(const f16* v, int C, f16* out, long pixels, hipStream_t s);

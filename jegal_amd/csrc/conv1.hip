@@ -859,6 +859,7 @@ hipError_t launch_conv1_scan(const uint8_t* src, int nclip, int T, int pad, cons
     if (nclip * T <= 0) return hipSuccess;
     const int P = T + 2 * pad - 4;
     const Conv1Scan z = conv1_scan_view(zscratch, nclip, T, pad);
+    record_kernel("conv1_zero_scan_kernel+conv1_skip_mask_kernel");
     hipLaunchKernelGGL(conv1_zero_scan_kernel, dim3((unsigned)(nclip * T)), dim3(256), 0, s, src, z.frame_mask(), Wd, scale * 16777216.0f,
                        static_cast<f16*>(z.zconst()));
     hipLaunchKernelGGL(conv1_skip_mask_kernel, dim3((unsigned)((nclip * P + 255) / 256)), dim3(256), 0, s, z.frame_mask(), nclip, T, pad, P,
@@ -919,14 +920,20 @@ hipError_t launch_conv1_direct(const uint8_t* src, int nclip, int T, int pad, co
     // XCD range rule (conv1_strips): XCD x = blockIdx.x & 7 owns strips [x * per, (x + 1) * per) -- under 8 workgroups some ranges have none
     if (wgs < 8 && a.nstrips > wgs) return hipErrorInvalidValue;
     const unsigned grid = (unsigned)grid_wgs;
-    if (o.conv1_mfma16) hipLaunchKernelGGL((conv1_direct_kernel<true>), dim3(grid), dim3(512), LDS_BYTES, s, a);
-    else hipLaunchKernelGGL((conv1_direct_kernel<false>), dim3(grid), dim3(512), LDS_BYTES, s, a);
+    if (o.conv1_mfma16) {
+        record_kernel("conv1_direct_kernel<1>");
+        hipLaunchKernelGGL((conv1_direct_kernel<true>), dim3(grid), dim3(512), LDS_BYTES, s, a);
+    } else {
+        record_kernel("conv1_direct_kernel<0>");
+        hipLaunchKernelGGL((conv1_direct_kernel<false>), dim3(grid), dim3(512), LDS_BYTES, s, a);
+    }
     return hipGetLastError();
 }
 
 hipError_t launch_conv1_edge_fix(f16* out_pooled, const f16* edge, long positions, hipStream_t s) {
     const long n = positions * PH * 4 * 8;
     if (n <= 0) return hipSuccess;
+    record_kernel("conv1_edge_fix_kernel");
     hipLaunchKernelGGL(conv1_edge_fix_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, out_pooled, edge, n);
     return hipGetLastError();
 }

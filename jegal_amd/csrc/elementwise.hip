@@ -42,10 +42,13 @@ hipError_t launch_stack_frames(const void* src, int src_is_u8, long sb, long st,
                                int B, int T, int pad, int H, int W, f16* dst, hipStream_t s) {
     const long total = (long)B * (T + 2 * pad - 4) * H * W;
     const int grid = grid_for(total);
-    if (src_is_u8)
+    if (src_is_u8) {
+        record_kernel("stack_frames_kernel<uint8_t>");
         hipLaunchKernelGGL(stack_frames_kernel<uint8_t>, dim3(grid), dim3(256), 0, s, (const uint8_t*)src, sb, st, sh, sw, sc, B, T, pad, H, W, dst);
-    else
+    } else {
+        record_kernel("stack_frames_kernel<float>");
         hipLaunchKernelGGL(stack_frames_kernel<float>, dim3(grid), dim3(256), 0, s, (const float*)src, sb, st, sh, sw, sc, B, T, pad, H, W, dst);
+    }
     return hipGetLastError();
 }
 
@@ -86,6 +89,7 @@ hipError_t launch_maxpool3x3s2(const f16* in, f16* out, int N, int H, int W, int
     const int OH = (H - 3) / 2 + 1, OW = (W - 3) / 2 + 1;
     const long total = (long)N * OH * OW * (C / 8);
     const int grid = grid_for(total);
+    record_kernel("maxpool_kernel");
     hipLaunchKernelGGL(maxpool_kernel, dim3(grid), dim3(256), 0, s, in, out, N, H, W, C, OH, OW, s2, in_op, const_in);
     return hipGetLastError();
 }
@@ -161,11 +165,13 @@ hipError_t launch_window_gather(const float* conv, const float* pe, int B, int P
     if (tiled) {
         if ((long)B * Twin * L >= (1L << 31)) return hipErrorInvalidValue;
         const long nblk = (((long)B * Twin * L + 15) >> 4) * 8;
+        record_kernel("window_gather_tiled_kernel");
         hipLaunchKernelGGL(window_gather_tiled_kernel, dim3((unsigned)((nblk + 3) / 4)), dim3(256), 0, s, conv, pe, B, P, Twin, L, shift, x16);
         return hipGetLastError();
     }
     const long total = (long)B * Twin * L * (D / 4);
     const int grid = grid_for(total);
+    record_kernel("window_gather_kernel");
     hipLaunchKernelGGL(window_gather_kernel, dim3(grid), dim3(256), 0, s, conv, pe, B, P, Twin, L, D, shift, x32, x16);
     return hipGetLastError();
 }
@@ -220,9 +226,13 @@ hipError_t launch_layernorm(const float* in, const float* w, const float* b, int
                             int relu, float* out32, f16* out16, hipStream_t s) {
     if (rows <= 0) return hipSuccess;
     const int grid = (rows + 3) / 4;
-    if (D == 512) hipLaunchKernelGGL(layernorm_kernel<2>, dim3(grid), dim3(256), 0, s, in, w, b, rows, flavour, relu, out32, out16);
-    else if (D == 768) hipLaunchKernelGGL(layernorm_kernel<3>, dim3(grid), dim3(256), 0, s, in, w, b, rows, flavour, relu, out32, out16);
-    else return hipErrorInvalidValue;
+    if (D == 512) {
+        record_kernel("layernorm_kernel<2>");
+        hipLaunchKernelGGL(layernorm_kernel<2>, dim3(grid), dim3(256), 0, s, in, w, b, rows, flavour, relu, out32, out16);
+    } else if (D == 768) {
+        record_kernel("layernorm_kernel<3>");
+        hipLaunchKernelGGL(layernorm_kernel<3>, dim3(grid), dim3(256), 0, s, in, w, b, rows, flavour, relu, out32, out16);
+    } else return hipErrorInvalidValue;
     return hipGetLastError();
 }
 
@@ -253,6 +263,7 @@ hipError_t launch_group_mean(const f16* in, int groups, int L, int D, f16* out, 
     if (D % 8 || L <= 0) return hipErrorInvalidValue;      // eight columns per thread; the mean of no rows
     const long total = (long)groups * (D / 8);
     if (total <= 0) return hipSuccess;
+    record_kernel("group_mean_kernel");
     hipLaunchKernelGGL(group_mean_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, in, groups, L, D, out);
     return hipGetLastError();
 }
@@ -270,6 +281,7 @@ hipError_t launch_cast_f32_f16(const float* in, f16* out, long n, hipStream_t s)
     if (n % 4) return hipErrorInvalidValue;      // four elements per thread
     const long n4 = n / 4;
     const int grid = grid_for(n4);
+    record_kernel("cast_kernel");
     hipLaunchKernelGGL(cast_kernel, dim3(grid), dim3(256), 0, s, in, out, n4);
     return hipGetLastError();
 }
@@ -338,6 +350,7 @@ hipError_t launch_audio_conv0(const float* mel, int B, int Tm, int F, const f16*
                               hipStream_t s) {
     if (B <= 0 || Tm <= 0) return hipSuccess;
     if (F < 1 || F > 80 || 3 * F > 256) return hipErrorInvalidValue;
+    record_kernel("audio_conv0_kernel");
     hipLaunchKernelGGL(audio_conv0_kernel, dim3((unsigned)(B * ((Tm + 2) / 3))), dim3(256), 0, s, mel, B, Tm, F, wh, wl, bias, out, valid);
     return hipGetLastError();
 }
@@ -360,6 +373,7 @@ __global__ __launch_bounds__(256) void zero_tail_kernel(f16* __restrict__ x, con
 hipError_t launch_zero_tail(f16* x, const int* valid, int halvings, int B, int H, long row_elems, hipStream_t s) {
     if (B <= 0 || H <= 0 || !valid) return hipSuccess;
     if (row_elems % 8) return hipErrorInvalidValue;
+    record_kernel("zero_tail_kernel");
     hipLaunchKernelGGL(zero_tail_kernel, dim3((unsigned)(B * H)), dim3(256), 0, s, x, valid, halvings, H, (int)(row_elems / 8));
     return hipGetLastError();
 }
@@ -430,6 +444,7 @@ __global__ __launch_bounds__(256) void xlmr_embed_planes_kernel(const int32_t* _
 hipError_t launch_xlmr_embed_planes(const int32_t* ids, int B, int L, int D, int pad_id, int vocab, int maxpos, const float* word, const float* pos,
                                     const float* type, f16* hi, f16* lo, float* part, hipStream_t s) {
     if (D % 256) return hipErrorInvalidValue;
+    record_kernel("xlmr_embed_planes_kernel");
     hipLaunchKernelGGL(xlmr_embed_planes_kernel, dim3((unsigned)(((long)B * L + 3) / 4)), dim3(256), 0, s, ids, B, L, D, pad_id, vocab, maxpos, word, pos, type,
                        hi, lo, part);
     return hipGetLastError();
@@ -467,6 +482,7 @@ __global__ void layernorm_planes_kernel(const f16* __restrict__ hi, const f16* _
 hipError_t launch_layernorm_planes(const f16* hi, const f16* lo, const float* w, const float* b, int rows, int D, float* out32, hipStream_t s) {
     if (rows <= 0) return hipSuccess;
     if (D != 768) return hipErrorInvalidValue;
+    record_kernel("layernorm_planes_kernel<3>");
     hipLaunchKernelGGL(layernorm_planes_kernel<3>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, hi, lo, w, b, rows, out32);
     return hipGetLastError();
 }

@@ -21,6 +21,7 @@ __global__ void transpose_tokens_kernel(const float* __restrict__ in, int L, int
 
 hipError_t launch_transpose_tokens(const float* in, int N, int L, int D, float* out, hipStream_t s) {
     if (N <= 0) return hipSuccess;
+    record_kernel("transpose_tokens_kernel");
     hipLaunchKernelGGL(transpose_tokens_kernel, dim3((D + 31) / 32, (L + 31) / 32, N), dim3(32, 8), 0, s, in, L, D, out);
     return hipGetLastError();
 }
@@ -84,6 +85,7 @@ hipError_t launch_span_gather(const float* p32, const float* pe, const int32_t* 
     if (n_windows <= 0) return hipSuccess;
     if (span_max < 1 || D <= 0 || D % 4 || (long)n_windows * span_max >= (1L << 31)) return hipErrorInvalidValue;
     const unsigned rows = (unsigned)n_windows * (unsigned)span_max;
+    record_kernel("span_gather_kernel");
     hipLaunchKernelGGL(span_gather_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, p32, pe, reinterpret_cast<const i32x4_t*>(table), rows,
                        (unsigned)span_max, D, x32, mask);
     return hipGetLastError();
@@ -106,6 +108,7 @@ hipError_t launch_core_compact(const void* in, int elem_bytes, const int32_t* ta
     if (span_max < 1 || D <= 0 || (elem_bytes != 2 && elem_bytes != 4) || (long)D * elem_bytes % 16 || (long)n_windows * span_max >= (1L << 31))
         return hipErrorInvalidValue;
     const unsigned rows = (unsigned)n_windows * (unsigned)span_max;
+    record_kernel("core_compact_kernel");
     hipLaunchKernelGGL(core_compact_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, static_cast<const uint4*>(in), reinterpret_cast<const i32x4_t*>(table),
                        rows, (unsigned)span_max, (int)((long)D * elem_bytes / 16), static_cast<uint4*>(out));
     return hipGetLastError();
@@ -153,6 +156,7 @@ __global__ __launch_bounds__(256) void xlmr_embed_kernel(const int32_t* __restri
 hipError_t launch_xlmr_embed(const int32_t* ids, int B, int L, int D, int pad_id, int vocab, int maxpos, const float* word, const float* pos,
                              const float* type, float* out, hipStream_t s) {
     if (D % 4) return hipErrorInvalidValue;
+    record_kernel("xlmr_embed_kernel");
     hipLaunchKernelGGL(xlmr_embed_kernel, dim3((unsigned)(((long)B * L + 3) / 4)), dim3(256), 0, s, ids, B, L, D, pad_id, vocab, maxpos, word, pos, type, out);
     return hipGetLastError();
 }
@@ -173,6 +177,7 @@ __global__ void ln_stats_kernel(const float* __restrict__ part, int rows, int P,
 }
 hipError_t launch_ln_stats(const float* part, int rows, int P, float* stats, hipStream_t s) {
     if (rows <= 0) return hipSuccess;
+    record_kernel("ln_stats_kernel");
     hipLaunchKernelGGL(ln_stats_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, part, rows, P, stats);
     return hipGetLastError();
 }
@@ -182,6 +187,7 @@ __global__ void mask_i32_f32_kernel(const int32_t* __restrict__ in, float* __res
     if (i < n) out[i] = in[i] != 0 ? 1.f : 0.f;
 }
 hipError_t launch_mask_i32_f32(const int32_t* in, float* out, long n, hipStream_t s) {
+    record_kernel("mask_i32_f32_kernel");
     hipLaunchKernelGGL(mask_i32_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, in, out, n);
     return hipGetLastError();
 }
@@ -546,6 +552,7 @@ hipError_t launch_conv_rowmaps(const int* s2, int NF, const ConvRowMap* layers, 
         a.L[l] = layers[l < nlayers ? l : nlayers - 1];
         if ((long)NF * a.L[l].OH * a.L[l].OW >= ROWMAP_MAX_ROWS) return hipErrorInvalidValue;      // the row index of a map entry
     }
+    record_kernel("conv_rowmap_scan_kernel+conv_rowmap_fill_kernel");
     hipLaunchKernelGGL(conv_rowmap_scan_kernel, dim3(1), dim3(1024), 0, s, a);
     hipLaunchKernelGGL(conv_rowmap_fill_kernel, dim3((unsigned)NF), dim3(256), 0, s, a);
     return hipGetLastError();

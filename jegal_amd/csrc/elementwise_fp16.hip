@@ -20,6 +20,7 @@ __global__ __launch_bounds__(256) void pe_project_kernel(const float* __restrict
 }
 
 hipError_t launch_pe_project(const float* pe, int S, const f16* Wh, const f16* Wl, const float* bias, int N, int K, f16* out, hipStream_t s) {
+    record_kernel("pe_project_kernel");
     hipLaunchKernelGGL(pe_project_kernel, dim3((unsigned)((S * N + 3) / 4)), dim3(256), 0, s, pe, S, Wh, Wl, bias, N, K, out);
     return hipGetLastError();
 }
@@ -30,6 +31,7 @@ __global__ void broadcast_channels_kernel(const f16* __restrict__ v, int C, f16*
 }
 hipError_t launch_broadcast_channels(const f16* v, int C, f16* out, long pixels, hipStream_t s) {
     const long total = pixels * C;
+    record_kernel("broadcast_channels_kernel");
     hipLaunchKernelGGL(broadcast_channels_kernel, dim3((unsigned)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096)), dim3(256), 0, s, v, C, out, total);
     return hipGetLastError();
 }
@@ -70,6 +72,7 @@ hipError_t launch_col_sum(const f16* A, long lda, int M, int K, float* scratch, 
     if (K % 8) return hipErrorInvalidValue;      // eight columns per thread
     const int cols = K / 8;
     const int gy = M < 64 ? M : 64;
+    record_kernel("col_sum_kernel+col_sum_finish_kernel");
     hipLaunchKernelGGL(col_sum_kernel, dim3((cols + 63) / 64, gy), dim3(64), 0, s, A, lda, M, K, scratch, stats);
     hipLaunchKernelGGL(col_sum_finish_kernel, dim3((K + 255) / 256), dim3(256), 0, s, scratch, gy, K, out);
     return hipGetLastError();
@@ -194,6 +197,7 @@ hipError_t launch_rc_bias(const f16* A, long lda, int tiled, int nclips, int rpc
     if (nclips <= 0 || rpc <= 0) return hipSuccess;
     if (!rc_bias_ok(N, K, tiled)) return hipErrorInvalidValue;
     f16* mean16 = reinterpret_cast<f16*>(scratch);
+    record_kernel("rc_col_mean_kernel+rc_gemv_kernel");
     hipLaunchKernelGGL(rc_col_mean_kernel, dim3(nclips, K / 64), dim3(256), 0, s, A, lda, tiled, rpc, valid_rows, K, mean16);
     hipLaunchKernelGGL(rc_gemv_kernel, dim3(N / 32, (nclips + 31) / 32), dim3(256), 0, s, mean16, lo, bias, nclips, N, K, out);
     return hipGetLastError();

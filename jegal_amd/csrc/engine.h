@@ -178,7 +178,8 @@ struct jg_handle {
     engine::ConvReport conv_report;
     std::map<std::string, engine::HostTensor> host;
     EngineOpts opts;               // per-handle tuning switches + per-device resources (shared.h)
-    char kname[KNAME_LEN] = {0};   // instance the last kernel check point launched (jg_debug_last_kernel)
+    char kname[KNAME_LEN] = {0};   // jg_debug_last_kernel: what the launcher of the last kernel check point's last launch recorded (record_kernel,
+                                   // shared.h; the slot is that sink while a check point runs, checks.hip); "" after a refusal or a failure
     engine::Arena ws;
     bool prof = false;
     int prof_only = -1;            // >= 0: only this stage is bracketed with events (jg_profile_enable(h, 2 + stage))

@@ -1120,7 +1120,7 @@ static hipError_t run_glds(const GemmArgs& a, const GemmPlan& p, const EngineOpt
         attr_set[o.device] = true;
     }
     if (!o.zeros) return hipErrorInvalidValue;
-    record_kernel(o.kname, "%s", p.name);
+    record_kernel(p.name);
     hipLaunchKernelGGL((gemm_glds_kernel<W2, CONV, MI, WM, WN, LNF, SPR, XE, C32>), dim3(p.grid), dim3(512), p.lds, s, a, p.n_tiles, p.total_tiles,
                        static_cast<const f16*>(o.zeros), o.gemm_counted | (p.stagger << 8));
     return hipGetLastError();
@@ -1128,7 +1128,7 @@ static hipError_t run_glds(const GemmArgs& a, const GemmPlan& p, const EngineOpt
 
 template <int WM, int WN, bool CONV, bool W2>
 static hipError_t run_staged(const GemmArgs& a, const GemmPlan& p, const EngineOpts& o, hipStream_t s) {
-    record_kernel(o.kname, "%s", p.name);
+    record_kernel(p.name);
     hipLaunchKernelGGL((gemm_kernel<WM, WN, CONV, W2>), dim3(p.grid), dim3(256), p.lds, s, a);
     return hipGetLastError();
 }

@@ -32,7 +32,7 @@
     X(4, 1, 0, 0) X(4, 1, 0, 1) X(2, 2, 0, 0) X(2, 2, 0, 1) X(4, 1, 1, 0) X(4, 1, 1, 1) X(2, 2, 1, 0) X(2, 2, 1, 1)
 
 struct GemmInstance {
-    const char* name;       // what record_kernel writes (jg_debug_last_kernel)
+    const char* name;       // what the instance's launch thunk (gemm.hip) hands to record_kernel: jg_debug_last_kernel reads exactly this
     int key[10];            // {LDS-DMA kernel (512 threads) or register-staged (256), W2, CONV, MI, WM, WN, LNF, SPR, XE, C32}
 };
 constexpr GemmInstance GEMM_INSTANCES[] = {
@@ -136,7 +136,7 @@ inline GemmShape gemm_shape(const Args& a, bool conv) {
 // with its launch figures.
 struct GemmPlan {
     int instance = -1;
-    const char* name = "rejected";
+    const char* name = "rejected";              // GEMM_INSTANCES[instance].name: jg_debug_gemm_plan shows it, the launch thunk records it
     unsigned grid = 0;
     size_t lds = 0;
     int n_tiles = 0, total_tiles = 0;           // tiles along n / in all (the LDS-DMA kernels' arguments)

@@ -1,5 +1,5 @@
 // libjegal_hip: the GEMM planner (gemm_plan.h) -- every admission rule and every tile choice of launch_gemm -- and the EngineOpts
-// it reads (engine_opts_set / init / release).  Host code only, one copy for both kernel builds.
+// it reads (engine_opts_set / init / release), and the per-thread sink of record_kernel.  Host code only, one copy for both kernel builds.
 #include "gemm_plan.h"
 
 #include <algorithm>
@@ -208,4 +208,10 @@ hipError_t engine_opts_init(EngineOpts& o, int device) {
 void engine_opts_release(EngineOpts& o) {
     if (o.zeros) (void)hipFree(const_cast<void*>(o.zeros));
     o.zeros = nullptr;
+}
+
+// where record_kernel (shared.h) writes on this thread: a check point's name slot while its call runs, nullptr otherwise
+char*& kernel_name_sink() {
+    static thread_local char* sink = nullptr;
+    return sink;
 }

@@ -21,4 +21,4 @@ struct GemmX3Args {
     long ldc;
     int relu;
 };
-hipError_t launch_gemm_x3(const GemmX3Args& a, hipStream_t s, char* kname = nullptr);
+hipError_t launch_gemm_x3(const GemmX3Args& a, hipStream_t s);

@@ -121,13 +121,13 @@ __global__ __launch_bounds__(256) void gemm_x3_kernel(GemmX3Args a) {
 
 }  // namespace
 
-hipError_t launch_gemm_x3(const GemmX3Args& a, hipStream_t s, char* kname) {
+hipError_t launch_gemm_x3(const GemmX3Args& a, hipStream_t s) {
     if (a.M <= 0) return hipSuccess;
     if (!a.A || !a.Wh || !a.Wl || !a.out || a.K <= 0 || a.K % 256 || a.N <= 0 || a.N % 128 || (a.lda & 3) || (a.ldw & 7) || (a.ldc & 3) || (a.res && (a.ldr & 3)) ||
         ((uintptr_t)a.A & 15))
         return hipErrorInvalidValue;
     const long tiles = (long)((a.M + 31) / 32) * (a.N / 128);
-    record_kernel(kname, "%s", "gemm_x3_kernel");
+    record_kernel("gemm_x3_kernel");
     hipLaunchKernelGGL(gemm_x3_kernel, dim3((unsigned)tiles), dim3(256), 0, s, a);
     return hipGetLastError();
 }

@@ -88,14 +88,17 @@ __global__ __launch_bounds__(256) void gsa_conv1_pool_kernel(const float* __rest
 }
 
 hipError_t launch_gsa_conv1_pool(const float* src, int clip_form, int n0, int nwin, int T, int Tm, const int* valid, const float* w,
-                                 const float* shift, void* out, int out32, hipStream_t s, char* kname) {
+                                 const float* shift, void* out, int out32, hipStream_t s) {
     if (nwin <= 0) return hipSuccess;
     if (!src || !w || !shift || !out || n0 < 0 || (clip_form && (T <= 0 || Tm <= 0)) || (reinterpret_cast<uintptr_t>(out) & 15)) return hipErrorInvalidValue;
-    if (out32)
+    const char* const form = clip_form ? "clip" : "windows";
+    if (out32) {
+        record_kernel("gsa_conv1_pool_kernel<float> %s", form);
         hipLaunchKernelGGL(gsa_conv1_pool_kernel<float>, dim3(nwin), dim3(256), 0, s, src, clip_form, n0, T, Tm, valid, w, shift, static_cast<float*>(out));
-    else
+    } else {
+        record_kernel("gsa_conv1_pool_kernel<f16> %s", form);
         hipLaunchKernelGGL(gsa_conv1_pool_kernel<f16>, dim3(nwin), dim3(256), 0, s, src, clip_form, n0, T, Tm, valid, w, shift, static_cast<f16*>(out));
-    record_kernel(kname, "gsa_conv1_pool_kernel<%s> %s", out32 ? "float" : "f16", clip_form ? "clip" : "windows");
+    }
     return hipGetLastError();
 }
 
@@ -127,17 +130,19 @@ __global__ __launch_bounds__(256) void maxpool_2x3_s2_kernel(const ET* __restric
     }
 }
 
-hipError_t launch_maxpool_2x3_s2(const void* in, void* out, int N, int H, int W, int C, int f32, hipStream_t s, char* kname) {
+hipError_t launch_maxpool_2x3_s2(const void* in, void* out, int N, int H, int W, int C, int f32, hipStream_t s) {
     if (N <= 0) return hipSuccess;
     if (!in || !out || H < 2 || W < 3 || C <= 0 || C % 8 || ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15)) return hipErrorInvalidValue;
     const int OH = (H - 2) / 2 + 1, OW = (W - 3) / 2 + 1;
     const long total = (long)N * OH * OW * (C / (f32 ? 4 : 8));
-    if (f32)
+    if (f32) {
+        record_kernel("maxpool_2x3_s2_kernel<float>");
         hipLaunchKernelGGL(maxpool_2x3_s2_kernel<float>, dim3(grid_for(total)), dim3(256), 0, s, static_cast<const float*>(in), static_cast<float*>(out), H, W,
                            C, OH, OW, total);
-    else
+    } else {
+        record_kernel("maxpool_2x3_s2_kernel<f16>");
         hipLaunchKernelGGL(maxpool_2x3_s2_kernel<f16>, dim3(grid_for(total)), dim3(256), 0, s, static_cast<const f16*>(in), static_cast<f16*>(out), H, W, C, OH,
                            OW, total);
-    record_kernel(kname, "maxpool_2x3_s2_kernel<%s>", f32 ? "float" : "f16");
+    }
     return hipGetLastError();
 }

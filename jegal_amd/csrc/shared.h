@@ -126,16 +126,21 @@ struct EngineOpts {
     bool attn_mfma = true;
     bool conv1_zero_skip = true;
     bool conv1_mfma16 = true;            // conv1_direct_kernel's MFMA waves on 16x16x32 MFMAs (false: 32x32x16, the round-1/2 form)
-    char* kname = nullptr;               // kernel check points (jg_debug_last_kernel): the launchers write the name of the instance they
-                                         // launch here, with its template arguments (KNAME_LEN bytes; nullptr: not recorded)
 };
 constexpr int LANE_WALK_MAX = 4;
+
+// ---- which kernel a launcher launched (jg_debug_last_kernel) ---------------------------------------------------
+// Every launcher a kernel check point reaches calls record_kernel where it chooses its instance, directly in front of the launch and
+// behind its last refusal: the name with its template arguments, or "a_kernel+b_kernel" for a launcher of two kernels.  The name goes to
+// the calling thread's sink: KNAME_LEN bytes that a check point opens for the length of its call (checks.hip: KernelNameScope) and
+// nullptr, nothing recorded, everywhere else.  One sink per thread, defined once (gemm_plan.hip), for both kernel builds.
 constexpr int KNAME_LEN = 96;
-// printf-style into kname (if any): host side of a launcher
+char*& kernel_name_sink();
 template <class... T>
-inline void record_kernel(char* kname, const char* fmt, T... v) {
-    if (kname) snprintf(kname, KNAME_LEN, fmt, v...);
+inline void record_kernel(const char* fmt, T... v) {
+    if (char* const sink = kernel_name_sink()) snprintf(sink, KNAME_LEN, fmt, v...);
 }
+inline void record_kernel(const char* name) { record_kernel("%s", name); }
 hipError_t engine_opts_init(EngineOpts& o, int device);      // queries the CU count, allocates the zero page (current device = `device`)
 void engine_opts_release(EngineOpts& o);
 
@@ -226,9 +231,9 @@ hipError_t launch_sync_offset_windows(const float* vid, const int32_t* voff, int
 // (fp16, or fp32 with out32): clip_form 0: src = x (N, 1, 80, 100); 1: src = mel (B, Tm, 80), window n = b * T + t reads mel rows
 // clamp(4 (t - 12) + 0..99, 0, valid[b] - 1) (valid: device [B] or nullptr = Tm).  w [64][9] (BatchNorm scale folded), shift [64]: fp32
 hipError_t launch_gsa_conv1_pool(const float* src, int clip_form, int n0, int nwin, int T, int Tm, const int* valid, const float* w,
-                                 const float* shift, void* out, int out32, hipStream_t s, char* kname = nullptr);
+                                 const float* shift, void* out, int out32, hipStream_t s);
 // NHWC max-pool, window (2, 3), stride (2, 2): (N, H, W, C) -> (N, (H - 2) / 2 + 1, (W - 3) / 2 + 1, C), fp16 or (f32) fp32 elements; C % 8 == 0
-hipError_t launch_maxpool_2x3_s2(const void* in, void* out, int N, int H, int W, int C, int f32, hipStream_t s, char* kname = nullptr);
+hipError_t launch_maxpool_2x3_s2(const void* in, void* out, int N, int H, int W, int C, int f32, hipStream_t s);
 // ASD per time window (asd.hip: asd_windows_kernel): prob / cosv (optional) (n_win_i, P_i) at poff[i], pred [woff[n_scenes]].  A scene
 // outside the limits (1..64 candidates, 1..1024 words, 1..max_windows windows, tracks of 1..8192 frames inside 0..n_tracks-1) gets
 // pred = -1 and NaN rows in all of its windows.  No scratch.

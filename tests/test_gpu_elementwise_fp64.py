@@ -348,6 +348,22 @@ def test_layernorm(bf, D):
     report("layernorm_fp32", fails)
 
 
+def test_a_refused_check_point_does_not_keep_the_previous_name():
+    """The name belongs to one call: after a launch that recorded its instance, a call of ANOTHER check point that the check point itself
+    refuses (max-pool with C = 4: no launcher is reached) reads "", not the earlier call's name."""
+    e = eng()
+    c = C.ln_input(C.LN_FAMILIES[0], 4, 512)
+    o32 = guarded(4, 512, torch.float32)
+    e.debug_layernorm(framed(c["x"]), framed(c["w"]), framed(c["b"]), 4, 512, C.LN_STD, 0, out32=o32)
+    launched(e, "layernorm_kernel<2>")
+    img = torch.zeros(1, 5, 5, 4, dtype=torch.float16, device=DEV)
+    out = guarded(4, 4, torch.float16)
+    assert rejects(e.debug_maxpool, img, out)
+    assert e.debug_last_kernel() == ""
+    torch.cuda.synchronize()
+    assert guards_intact(out, 0, 0), "a refused launch wrote to its output"
+
+
 @BUILDS
 def test_layernorm_planes(bf):
     e, d16 = eng(bf), dt16(bf)

@@ -92,6 +92,29 @@ def test_every_gemm_instance_has_a_kernel_level_case():
     assert all(n.split("<")[1].split(",")[1 if n.startswith("gemm_glds") else 2] == "1" for n in CONV_INSTANCES)
 
 
+def test_kernel_names_come_from_the_launchers_alone():
+    """jg_debug_last_kernel reports what the launcher recorded (record_kernel, jegal_amd/csrc/shared.h): the check points name no kernel
+    themselves, and no name slot travels through a parameter or through EngineOpts."""
+    csrc = os.path.join(ROOT, "jegal_amd", "csrc")
+    src = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".h", ".hip"))}
+    assert len(src) > 20 and "checks.hip" in src and "shared.h" in src
+    checks = src["checks.hip"]
+    assert "record_kernel(" not in checks
+    literals = re.findall(r'"(?:[^"\\\n]|\\.)*"', checks)
+    assert len(literals) > 100 and '"launch_layernorm"' in literals
+    assert [s for s in literals if "_kernel" in s] == []
+    for f, text in src.items():
+        assert not re.search(r"[(,][^(),;{}]*[\s*&]kname\s*(?:=[^(),;]*)?[,)]", text), f"{f}: a parameter named kname"
+        assert "EngineOpts::kname" not in text, f
+    opts = re.search(r"\nstruct EngineOpts \{\n(.*?)\n\};", src["shared.h"], re.S)
+    assert opts and "lanes_active" in opts.group(1) and not re.search(r"\bkname\b", opts.group(1))
+    # ... and the launchers do record: the sink has one definition, and a launcher of each unit a check point reaches writes to it
+    assert sum(len(re.findall(r"^char\*& kernel_name_sink\(\) \{", t, re.M)) for t in src.values()) == 1
+    for f in ("gemm.hip", "attention.hip", "elementwise.hip", "elementwise_f32.hip", "elementwise_fp16.hip", "audit32.hip", "gemm_x3.hip", "gsa_kernels.hip",
+              "conv1.hip"):
+        assert "record_kernel(" in src[f], f
+
+
 def test_weight_forms_match_the_recorded_rule(golden_dir):
     """Which weights a layer's GEMM runs with (jegal_amd/csrc/weight_form.h, asked through jg_debug_weight_form / jg_debug_gemm_runs_lo: no
     handle, no device) against what pack_matrix and gemm() decided BEFORE the rule moved there: all 7 precision modes x 4 layer kinds x
