@@ -217,7 +217,12 @@ int jg_debug_conv1_pool(jg_handle* h, const void* frames_u8, int B, int T, int p
  *   out[m][n] = act( sum_k A[m][k] (Wh[n][k] + Wl[n][k]) * scale[n] + bias[n] + res[m % res_mod][n] ),  act: relu 0 none / 1 ReLU / 2 GELU;
  *   bias_clip [nclips][N]: row m takes bias_clip[min(m / rpc, nclips - 1)] instead of bias (fp16 out16 alone);
  *   ln_w != NULL: residual + LayerNorm fused (N = 512, M >= 1024): out16 = LN(acc + bias + res16) in the tiled token order;
- *   ln_mode 1 / 2: the implicit-LayerNorm consumer / producer epilogues (ln_stats, xres_hi / xres_lo, out_lo, stat_out as in GemmArgs). */
+ *     out16 may be res16 (the fused transformer runs it in place);
+ *   ln_mode 1 / 2: the implicit-LayerNorm consumer / producer epilogues (ln_stats, xres_hi / xres_lo, out_lo, stat_out as in GemmArgs);
+ *     with ln_mode 2, out16 / out_lo may be xres_hi / xres_lo (the token stream is updated in place);
+ *   a_tiled != 0: A is the tiled token plane of jegal_amd/csrc/shared.h (x16t_index) instead of [M][lda]: K = 512, whole 128-row tiles,
+ *     lda is not used for addressing, and the caller owns ceil(M / 128) * 65536 elements.  An fp16-build route (no bf16 handle reaches
+ *     it): JG_ERR_STATE on a bf16 handle. */
 typedef struct jg_gemm_check {
     const void* A; int64_t lda;                   /* [M][lda] 16-bit */
     const void* Wh; const void* Wl; int64_t ldw;  /* [N][ldw] 16-bit; Wl NULL: single weights */
@@ -229,12 +234,13 @@ typedef struct jg_gemm_check {
     float* out32; void* out16; int64_t ldc;       /* either or both */
     const float* ln_w; const float* ln_b; const void* res16;
     int ln_mode; const float* ln_stats; const void* xres_hi; const void* xres_lo; void* out_lo; float* stat_out;
+    int a_tiled;                                  /* A is the tiled token plane (above) */
 } jg_gemm_check;
 int jg_debug_gemm_check(jg_handle* h, const jg_gemm_check* c);
 /* The GEMM planner's answer for an argument set, without a handle, a device or a launch: which kernel instance launch_gemm would run
  * (jegal_amd/csrc/gemm_plan.h).  Of `c` only the sizes and the null-ness of the pointers are read.  conv (optional): the launch is an
  * implicit-GEMM convolution of this geometry (rowmap / const_in: whether ConvGeom's pointers are set).  a_tiled: the A operand is the
- * tiled token plane.  num_cu: compute units of the device; lanes_active: the launch is part of a two-lane batch.  opt_names / opt_values:
+ * tiled token plane (this parameter or c->a_tiled non-zero: the planner then plans exactly what jg_debug_gemm_check launches for c).  num_cu: compute units of the device; lanes_active: the launch is part of a two-lane batch.  opt_names / opt_values:
  * n_opts options as for jg_set_option ("gemm_*", "lane_walk*"; the built-in defaults otherwise, every walk factor 1).  name receives the instance as jg_debug_last_kernel reports it,
  * or "rejected" (launch_gemm would return an error and launch nothing; grid = lds = stagger = 0 then); grid = workgroups, lds = dynamic
  * LDS bytes, stagger = de-phasing delay in 10-ns ticks.  Returns JG_ERR_ARG for bad arguments or an unknown option. */

@@ -32,7 +32,8 @@ class GemmCheck(ctypes.Structure):
                 ("scale", _P), ("bias", _P), ("bias_clip", _P), ("rpc", _I), ("nclips", _I),
                 ("res", _P), ("ldr", _L), ("res_mod", _I), ("relu", _I), ("out32", _P), ("out16", _P), ("ldc", _L),
                 ("ln_w", _P), ("ln_b", _P), ("res16", _P),
-                ("ln_mode", _I), ("ln_stats", _P), ("xres_hi", _P), ("xres_lo", _P), ("out_lo", _P), ("stat_out", _P)]
+                ("ln_mode", _I), ("ln_stats", _P), ("xres_hi", _P), ("xres_lo", _P), ("out_lo", _P), ("stat_out", _P),
+                ("a_tiled", _I)]
 class ConvCheck(ctypes.Structure):
     """struct jg_conv_check (include/jegal_hip.h): operands of one jg_debug_conv_check launch."""
     _fields_ = [("in_", _P)] + [(k, _I) for k in ("nimg", "H", "W", "C", "KH", "KW", "SH", "SW", "PH", "PW", "reorder")] + [
@@ -179,7 +180,8 @@ def load_library():
 def gemm_plan(num_cu=256, lanes_active=False, opts=None, conv=None, a_tiled=False, **fields):
     """The GEMM planner's answer (jg_debug_gemm_plan) -> (instance name or "rejected", grid, lds bytes, stagger).  Needs no Engine and no
     GPU.  fields: those of jg_gemm_check, as for Engine.debug_gemm_check; of a pointer field only its presence counts, so a tensor or
-    True stands for "set" (None / False / 0: NULL).  opts: engine options (gemm_*, lane_walk*; "num_cu" overrides num_cu, "debug_lanes" overrides
+    True stands for "set" (None / False / 0: NULL).  a_tiled: A is the tiled token plane (debug_gemm_check's a_tiled field, passed with the
+    other fields, lands here: the planner plans exactly what that call launches).  opts: engine options (gemm_*, lane_walk*; "num_cu" overrides num_cu, "debug_lanes" overrides
     lanes_active, as the handle options of those names do for the check points); conv: dict of the jg_conv_shape fields."""
     lib = load_library()
     c = GemmCheck()

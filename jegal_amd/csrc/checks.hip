@@ -51,6 +51,7 @@ GemmArgs gemm_check_args(const jg_gemm_check* c) {
     a.ln_mode = c->ln_mode; a.ln_stats = c->ln_stats;
     a.xres_hi = static_cast<const f16*>(c->xres_hi); a.xres_lo = static_cast<const f16*>(c->xres_lo);
     a.out_lo = static_cast<f16*>(c->out_lo); a.stat_out = c->stat_out;
+    a.a_tiled = c->a_tiled != 0;
     return a;
 }
 bool al(const void* p, unsigned bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
@@ -175,6 +176,7 @@ int jg_debug_gemm_check(jg_handle* h, const jg_gemm_check* c) {
         ((c->out32 || (c->out16 && !c->ln_w)) && c->ldc < c->N) || (c->res && (c->ldr < c->N || c->res_mod < 0)) ||
         (c->bias_clip && (c->rpc <= 0 || c->nclips <= 0)) || c->relu < 0 || c->relu > 2 || c->ln_mode < 0 || c->ln_mode > 2)
         JG_FAIL(h, JG_ERR_ARG, "jg_debug_gemm_check: bad arguments");
+    if (c->a_tiled) { FP16_ONLY(h, "jg_debug_gemm_check with a_tiled"); }
     const GemmArgs a = gemm_check_args(c);
     const DebugLanes lanes(h);
     return check_result(h, LAUNCH(h, launch_gemm, a, false, h->opts, h->stream), "launch_gemm");
@@ -294,7 +296,7 @@ int jg_debug_gemm_plan(const jg_gemm_check* c, const jg_conv_shape* conv, int a_
         !grid || !lds || !stagger)
         return JG_ERR_ARG;
     GemmShape s = gemm_shape(gemm_check_args(c), false);
-    s.a_tiled = a_tiled != 0;
+    s.a_tiled = a_tiled != 0 || c->a_tiled != 0;
     if (conv) {
         s.conv = true;
         s.H = conv->H; s.W = conv->W; s.C = conv->C; s.KH = conv->KH; s.KW = conv->KW; s.PH = conv->PH; s.PW = conv->PW;

@@ -34,6 +34,7 @@ DEV = "cuda"
 GUARD_ROWS = 128
 SENT16 = 0x7D5A            # fp16 / bf16 NaN bit pattern: a value no kernel computes
 SENT32 = 0x7FBADBAD
+NAN16 = 0x7E00             # the fp16 quiet NaN: what the parts of a tiled plane that no launch may read hold
 RATIOS = {}                # family -> worst observed / bound (printed at the end of each test)
 
 
@@ -138,9 +139,11 @@ def planned(kw, opts=None):
 
 
 def gemm_case(name, M, N, K, *, w2=False, out="f32", lda=None, ldw=None, ldc=None, scale=False, bias=True, res=False, res_mod=0,
-              relu=0, bias_clip=None, bf=False, opts=None, seed=0):
-    """One plain / per-clip-bias Linear launch vs float64.  bias_clip = (rpc, nclips)."""
+              relu=0, bias_clip=None, bf=False, opts=None, seed=0, tiled=False):
+    """One plain / per-clip-bias Linear launch vs float64.  bias_clip = (rpc, nclips).  tiled: A is handed over as the tiled token plane
+    (a_tiled; K = 512) of whole 128-row tiles plus one guard tile, with NaN bits in the rows >= M of the last tile and in the guard tile."""
     g = torch.Generator().manual_seed(seed)
+    assert not tiled or (K == 512 and lda in (None, 512)), "the tiled token plane has 512 columns"
     lda, ldw = lda or K, ldw or K
     ldc = ldc or N + 8                                  # guard columns
     d16 = dt16(bf)
@@ -158,12 +161,18 @@ def gemm_case(name, M, N, K, *, w2=False, out="f32", lda=None, ldw=None, ldc=Non
         rpc, ncl = bias_clip
         bc = (urnd(g, (ncl, N), -2, 2)).float()          # O(1) differences between the clips' vectors
     e = engine(prec=4 if bf else None, **(opts or {}))
-    A = operand(a, lda, d16)
+    if tiled:
+        from elementwise_fp64_cases import tiled_plane          # (imports this module: not at the top)
+        A = tiled_plane(a.to(d16), (M + 127) // 128 * 65536 + 65536, NAN16).view(d16).to(DEV)
+    else:
+        A = operand(a, lda, d16)
     Wh = operand(wh, ldw, d16)
     Wl = operand(wl, ldw, d16) if w2 else None
     o32 = guarded(M, ldc, torch.float32) if out in ("f32", "both") else None
     o16 = guarded(M, ldc, d16) if out in ("f16", "both") else None
     kw = dict(A=A, lda=lda, Wh=Wh, ldw=ldw, M=M, N=N, K=K, relu=relu, ldc=ldc)
+    if tiled:
+        kw["a_tiled"] = 1
     if w2:
         kw["Wl"] = Wl
     if sc is not None:
@@ -261,8 +270,10 @@ GEMM_CASES = [
 ]
 
 
-def ln_fused_case(M, clip=None, seed=1):
-    """Residual + LayerNorm fused (N = 512): the token plane in the tiled order of common.h, built here from that description."""
+def ln_fused_case(M, clip=None, seed=1, inplace=False):
+    """Residual + LayerNorm fused (N = 512): the token plane in the tiled order of common.h, built here from that description.
+    inplace: out16 is the res16 plane itself, as the fused transformer passes it; the reference keeps the host copy of the plane, the guard
+    tile must keep the bits it was given, rows >= M inside the last 128-row tile are unspecified afterwards."""
     N, K = 512, 512
     g = torch.Generator().manual_seed(seed)
     e = engine()
@@ -283,7 +294,8 @@ def ln_fused_case(M, clip=None, seed=1):
     plane16[R * 65536:] = float("nan")
     kw = dict(A=operand(a, K, torch.float16), lda=K, Wh=operand(wh, K, torch.float16), ldw=K, M=M, N=N, K=K, bias=bias.to(DEV),
               ln_w=gam.to(DEV), ln_b=bet.to(DEV), res16=plane16.to(DEV))
-    out16 = torch.full((R * 65536 + 65536,), SENT16, dtype=torch.int16, device=DEV).view(torch.float16)
+    out16 = kw["res16"] if inplace else torch.full((R * 65536 + 65536,), SENT16, dtype=torch.int16, device=DEV).view(torch.float16)
+    guard_bits = plane16.view(torch.int16)[R * 65536:].clone() if inplace else torch.full((65536,), SENT16, dtype=torch.int16)
     kw["out16"] = out16
     rows = torch.arange(M)
     if clip:
@@ -312,17 +324,20 @@ def ln_fused_case(M, clip=None, seed=1):
     got = o16[torch.from_numpy(off16[:M].ravel())].view(M, N).double()
     ratio = float(((got - y).abs() / (ey + ulp16(y))).max()) if got.isfinite().all() else float("inf")
     fails = []
-    if not bool((o16.view(torch.int16)[R * 65536:] == SENT16).all()):
+    if not torch.equal(o16.view(torch.int16)[R * 65536:], guard_bits):
         fails.append("ln_fused: guard tile of out16 overwritten")
     note("ln_fused", ratio)
-    print(f"ln_fused M={M} clip={clip} {kname} observed/bound {ratio:.3f}")
+    print(f"ln_fused M={M} clip={clip}{' in place' if inplace else ''} {kname} observed/bound {ratio:.3f}")
     if ratio > 1:
-        fails.append(f"ln_fused M={M} clip={clip}: observed/bound {ratio:.3f}")
+        fails.append(f"ln_fused M={M} clip={clip}{' in place' if inplace else ''}: observed/bound {ratio:.3f}")
     return fails
 
 
-def implicit_ln_case(mode, M, N, K, w2, tile, seed=2):
-    """ln_mode 1 (consumer) / 2 (producer) of the implicit-LayerNorm token stream (GemmArgs::ln_mode, common.h)."""
+def implicit_ln_case(mode, M, N, K, w2, tile, seed=2, inplace=False):
+    """ln_mode 1 (consumer) / 2 (producer) of the implicit-LayerNorm token stream (GemmArgs::ln_mode, common.h).
+    inplace (ln_mode 2): out16 is the xres_hi buffer and out_lo the xres_lo buffer, as engine::gemm passes them; their guard rows and guard
+    columns must keep the (NaN) bits they were given, compared with a clone taken before the launch."""
+    assert mode == 2 or not inplace
     g = torch.Generator().manual_seed(seed)
     e = engine(gemm_tile=tile)
     a = (urnd(g, (M, K)) + 0.5).half().double()              # un-normalised rows with a mean of their own
@@ -355,10 +370,15 @@ def implicit_ln_case(mode, M, N, K, w2, tile, seed=2):
         mean = xp.mean(1).float()
         rstd = (1 / (xp.var(1, unbiased=False) + 1e-5).sqrt()).float()
         gam = urnd(g, (N,), 0.5, 1.5).float()
-        lo = guarded(M, ldc, torch.float16)
+        xres_hi = operand(xh.double(), ldc, torch.float16, extra_rows=GUARD_ROWS if inplace else 16)
+        xres_lo = operand(xl.double(), ldc, torch.float16, extra_rows=GUARD_ROWS if inplace else 16)
+        if inplace:
+            before = (xres_hi.clone(), xres_lo.clone())
+            out16 = kw["out16"] = xres_hi
+        lo = xres_lo if inplace else guarded(M, ldc, torch.float16)
         stat = guarded(M, N // 64 * 2, torch.float32)
-        kw.update(scale=gam.to(DEV), ln_stats=torch.stack([mean, rstd], 1).contiguous().to(DEV), xres_hi=operand(xh.double(), ldc, torch.float16),
-                  xres_lo=operand(xl.double(), ldc, torch.float16), out_lo=lo, stat_out=stat)
+        kw.update(scale=gam.to(DEV), ln_stats=torch.stack([mean, rstd], 1).contiguous().to(DEV), xres_hi=xres_hi, xres_lo=xres_lo, out_lo=lo,
+                  stat_out=stat)
         nrm = gam.double() * rstd.double()[:, None] * (xp - mean.double()[:, None])
         v = acc + bias.double() + nrm
         eb = 2 * K * U * (mag + bias.double().abs() + nrm.abs())
@@ -369,7 +389,10 @@ def implicit_ln_case(mode, M, N, K, w2, tile, seed=2):
     SEEN.add(kname)
     hi = out16[:M, :N].double().cpu()
     ratio = float(((hi - v).abs() / (eb + ulp16(v))).max()) if hi.isfinite().all() else float("inf")
-    if not guards_intact(out16, M, N):
+    def guards_kept(buf, was):          # in place: the rows >= M and the columns >= N hold what they held before the launch
+        b, w = buf.view(torch.int16).cpu(), was.view(torch.int16).cpu()
+        return torch.equal(b[M:], w[M:]) and torch.equal(b[:M, N:], w[:M, N:])
+    if not (guards_kept(out16, before[0]) if inplace else guards_intact(out16, M, N)):
         fails.append(f"ln_mode {mode}: out16 guard overwritten")
     if mode == 2:
         got = hi + lo[:M, :N].double().cpu()
@@ -382,12 +405,12 @@ def implicit_ln_case(mode, M, N, K, w2, tile, seed=2):
         b1 = (eb64 + 64 * U * av).sum(2)
         b2 = (2 * av * eb64 + 64 * U * av * av).sum(2)
         ratio = max(ratio, float(((gs[..., 0] - s1).abs() / b1).max()), float(((gs[..., 1] - s2).abs() / b2).max()))
-        if not guards_intact(lo, M, N) or not guards_intact(stat, M, N // 64 * 2):
+        if not (guards_kept(lo, before[1]) if inplace else guards_intact(lo, M, N)) or not guards_intact(stat, M, N // 64 * 2):
             fails.append("ln_mode 2: out_lo / stat_out guard overwritten")
     note(f"ln_mode{mode}", ratio)
-    print(f"ln_mode={mode} M={M} N={N} K={K} w2={w2} tile={tile} {kname} observed/bound {ratio:.3f}")
+    print(f"ln_mode={mode} M={M} N={N} K={K} w2={w2} tile={tile}{' in place' if inplace else ''} {kname} observed/bound {ratio:.3f}")
     if not ratio <= 1:
-        fails.append(f"ln_mode {mode} M={M} N={N} w2={w2} tile={tile}: observed/bound {ratio:.3f} ({kname})")
+        fails.append(f"ln_mode {mode} M={M} N={N} w2={w2} tile={tile}{' in place' if inplace else ''}: observed/bound {ratio:.3f} ({kname})")
     return fails
 
 
