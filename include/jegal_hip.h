@@ -600,6 +600,39 @@ int jg_attn_matrix(jg_handle* h, const float* gesture, const float* content, con
                    int n_clips, int D, int max_frames, float temp, int normalize,
                    float* A, const int64_t* a_offsets,          /* A may be NULL: no matrix is written (one pass over G, the spot-every-word mode) */
                    int32_t* best_frame, float* best_score);     /* [sum W], in c_offsets order; both may be NULL when A is not */
+/* The gesture-word heat map along whole talks: jg_attn_matrix's softmax runs over the words of a clip of at most 220 frames, the length
+ * the model was trained on; here every frame sees the words a clip of 2 reach + 1 frames centred on it would contain.  All pointers are
+ * device pointers.
+ *   gesture (n_rows, D) fp32: frame rows of n_tracks tracks, g_offsets [n_tracks + 1] their row offsets (T frames each);
+ *   content (n_words, D) fp32: word rows, c_offsets [n_tracks + 1]: track i's words, in transcript order; word_start / word_end [n_words]:
+ *     every word's inclusive frame bounds on ITS track's frame axis, non-decreasing along a track, start <= end.
+ * Word w is IN REACH of frame f iff start_w - reach <= f <= end_w + reach.  For a frame f in 0..T-1 and a word w in reach of it
+ *   P[w][f] = exp(x_wf - m_f) / sum over the words w' in reach of f of exp(x_w'f - m_f),  x_wf = <c_w, g_f> / temp,  m_f = max x_w'f over them;
+ * normalize != 0: both rows F.normalize'd first, as in jg_attn_matrix.  With reach >= T every word is in reach of every frame and P is
+ * jg_attn_matrix's A.
+ * Outputs, each optional (NULL), at least one required; every element of each is written and nothing else is:
+ *   band fp32 [n_words][band_pitch]: band[w][j] = P[w][f] for f = start_w - reach + j; NaN where f is outside 0..T-1, beyond end_w + reach,
+ *     or undecided.  A word whose range is longer than band_pitch keeps its first band_pitch frames; its best_* still cover the whole range;
+ *   best_frame int32 / best_score fp32 [n_words]: the first arg-max of P[w][.] over the word's decided frames (on the track's frame axis)
+ *     and that probability, the band entry bit for bit; -1 / NaN when the word has none;
+ *   frame_word int32 / frame_prob fp32 [n_rows]: the arg-max word of the frame, counted from the track's first word, the smaller index on
+ *     ties, and its probability; -1 / NaN when no word is in reach, and in undecided frames.
+ * The work is cut into blocks of 128 frames, aligned to the track's first frame; a block's candidates are the words in reach of any of its
+ * frames (one contiguous range: the bounds are non-decreasing), and a block with more than 128 candidates is UNDECIDED in all its frames:
+ * lower reach.  The logits run on exact-fp32 MFMAs and have the bits jg_attn_matrix gives the same two rows; for a track of at most 128
+ * words with reach >= T, band entries, best_frame and best_score equal jg_attn_matrix's bit for bit.  Determinism: a track's results are
+ * a function of its own rows, words and reach, not of the other tracks or of its place in the batch; duplicate frames give bit-equal columns.
+ * Limits: tracks of 0..max_frames frames, max_frames 1..2^20 (it sizes the grid); reach 0..1024; n_words * band_pitch < 2^31; D % 64 == 0;
+ * gesture / content 16-byte aligned.  A violated limit, a null operand, temp <= 0, band with band_pitch < 1 or no output at all returns
+ * JG_ERR_ARG before anything is enqueued; n_tracks == 0 returns JG_OK and launches nothing.  The offsets and bounds are device arrays: a
+ * track longer than max_frames, or with rows or words outside the arrays, is undecided as a whole, none of its rows is read, and the other
+ * tracks are unaffected.  Bounds that are not non-decreasing, or start > end, give unspecified values for that track and no access outside
+ * the operands (every index taken from the search is clamped to the track's words).  Words outside the track are legal and have no frames.
+ * Workspace: with best_frame or best_score, n_words 64-bit arg-max keys.  Asynchronous, on the handle's stream. */
+int jg_attn_talk(jg_handle* h, const float* gesture, const int32_t* g_offsets, int n_tracks, int64_t n_rows, int max_frames,
+                 const float* content, const int32_t* c_offsets, int n_words, const int32_t* word_start, const int32_t* word_end,
+                 int D, int reach, float temp, int normalize,
+                 float* band, int band_pitch, int32_t* best_frame, float* best_score, int32_t* frame_word, float* frame_prob);
 /* evaluate_asd.py:43-51,94-100: pred (n,3) = argmax over the first 2/4/6 candidates */
 int jg_asd(jg_handle* h, const float* query, const float* cand, const int32_t* c_offsets, int n, int D, float temp, int32_t* pred);
 

@@ -137,6 +137,7 @@ _SIGS = {
     "jg_group_of_rows": [_P, _P, _L, _P, _I, _I, _P, _P],
     "jg_spot": [_P, _P, _P, _P, _P, _P, _I, _I, ctypes.c_float, _P, _P],
     "jg_attn_matrix": [_P, _P, _P, _P, _P, _I, _I, _I, ctypes.c_float, _I, _P, _P, _P, _P],
+    "jg_attn_talk": [_P, _P, _P, _I, _L, _I, _P, _P, _I, _P, _P, _I, _I, ctypes.c_float, _I, _P, _I, _P, _P, _P, _P],
     "jg_asd": [_P, _P, _P, _P, _I, _I, ctypes.c_float, _P],
     "jg_asd_windows": [_P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _I, ctypes.c_float, _P, _P, _P],
     "jg_comm_get_unique_id": [ctypes.c_char_p],

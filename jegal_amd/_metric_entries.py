@@ -11,8 +11,10 @@ SPOT_MAX_W, SPOT_MAX_T = 1024, 8192
 SYNC_MAX_R, SYNC_MAX_T, SYNC_MAX_D = 64, 8192, 1024
 SYNCW_MAX_T, SYNCW_MAX_WINDOWS, SYNCW_MAX_BAND_LOG2 = 1 << 20, 1 << 20, 40
 ASDW_MAX_D, ASDW_MAX_P, ASDW_MAX_WIN = 1024, 64, 8192
+TALK_MAX_T, TALK_MAX_REACH, TALK_MAX_BLOCK_W = 1 << 20, 1024, 128
 LIMITS = {k: v for k, v in globals().items() if k.isupper()}
 INT32_MAX = 2 ** 31 - 1
+TALK_FB = 128        # frames per block of jg_attn_talk (csrc/spotting.hip), aligned to the track's first frame
 
 
 def _ptr(t):
@@ -211,6 +213,70 @@ class MetricEntries:
         self._ck(self.lib.jg_attn_matrix(self.h, _ptr(g), _ptr(c), _ptr(go), _ptr(co), n, gs[1], int(T.max()), float(temp),
                                          int(bool(normalize)), _ptr(A), _ptr(ao), _ptr(best_frame), _ptr(best_score)))
         return A, a_off, best_frame, best_score
+
+    @staticmethod
+    def talk_block_candidates(T, start, end, reach):
+        """jg_attn_talk's candidates per block of 128 frames of ONE track of T frames whose words have the inclusive bounds start / end
+        (non-decreasing): the number of words in reach of any frame of the block, as the kernel's two searches count them."""
+        start, end = np.asarray(start, np.int64), np.asarray(end, np.int64)
+        f0 = np.arange(0, max(int(T), 0), TALK_FB, dtype=np.int64)
+        last = np.minimum(f0 + TALK_FB, T) - 1
+        lo = np.searchsorted(end + reach, f0, side="left")
+        hi = np.searchsorted(start - reach, last, side="right")
+        return np.maximum(hi - lo, 0)
+
+    def attn_talk(self, gesture, content, g_offsets, c_offsets, word_start, word_end, reach=110, temp=0.07, normalize=True, want_band=True,
+                  want_best=True, want_frames=True):
+        """jg_attn_talk: the gesture-word heat map along whole tracks.  gesture (sum T, D) / content (sum W, D); g_offsets / c_offsets: HOST
+        arrays of n + 1 entries; word_start / word_end: one inclusive frame bound per content row, on the frame axis of the word's track,
+        non-decreasing along a track.  Word w is in reach of frame f iff start_w - reach <= f <= end_w + reach, and every frame's softmax
+        runs over the words in reach of it.
+        Returns device tensors (band (sum W, 2 reach + longest word) | None, best_frame, best_score (sum W,) | None, frame_word, frame_prob
+        (sum T,) | None): band[w][j] is the word's probability at frame start_w - reach + j (NaN outside the track or beyond end_w + reach),
+        best_* its first arg-max frame and that probability (-1 / NaN without a frame), frame_* the frame's arg-max word counted from
+        the track's first word and its probability (-1 / NaN when no word is in reach).  Content rows no track covers read NaN / -1."""
+        reach = int(reach)
+        if not 0 <= reach <= TALK_MAX_REACH:
+            raise ValueError(f"jg_attn_talk limits: reach 0..{TALK_MAX_REACH}")
+        if not temp > 0:
+            raise ValueError("temp must be positive")
+        if not (want_band or want_best or want_frames):
+            raise ValueError("no output asked for")
+        gs, cs = _row_pair(gesture, content, "gesture / content")
+        goh = _offsets(g_offsets, gs[0], "g_offsets")
+        n = goh.size - 1
+        coh = _offsets(c_offsets, cs[0], "c_offsets", n)
+        T = _within(np.diff(goh), 0, TALK_MAX_T, "jg_attn_talk limits: frames per track")
+        wsh, weh = _ints(word_start), _ints(word_end)
+        if wsh.size != cs[0] or weh.size != cs[0] or (cs[0] and max(np.abs(wsh).max(), np.abs(weh).max()) > INT32_MAX):
+            raise ValueError("word_start / word_end need one int32 entry per content row")
+        if (wsh > weh).any():
+            raise ValueError("word_start must be <= word_end")
+        for i in range(n):
+            s, e = wsh[coh[i]:coh[i + 1]], weh[coh[i]:coh[i + 1]]
+            if (np.diff(s) < 0).any() or (np.diff(e) < 0).any():
+                raise ValueError(f"track {i}: word_start / word_end must be non-decreasing (transcript order)")
+            cand = self.talk_block_candidates(T[i], s, e, reach)
+            if cand.size and cand.max() > TALK_MAX_BLOCK_W:
+                raise ValueError(f"track {i}: {int(cand.max())} words in reach of the {TALK_FB} frames from {int(cand.argmax()) * TALK_FB}; "
+                                 f"jg_attn_talk decides at most {TALK_MAX_BLOCK_W} per block: lower reach")
+        pitch = 2 * reach + (int((weh - wsh).max()) + 1 if cs[0] else 1)
+        if want_band and cs[0] * pitch > INT32_MAX:
+            raise ValueError("jg_attn_talk limits: content rows x (2 reach + longest word) < 2^31")
+        self._bind_stream()
+        nan = float("nan")
+        band = torch.full((cs[0], pitch), nan, dtype=torch.float32, device=self.device) if want_band else None
+        best_frame = torch.full((cs[0],), -1, dtype=torch.int32, device=self.device) if want_best else None
+        best_score = torch.full((cs[0],), nan, dtype=torch.float32, device=self.device) if want_best else None
+        frame_word = torch.full((gs[0],), -1, dtype=torch.int32, device=self.device) if want_frames else None
+        frame_prob = torch.full((gs[0],), nan, dtype=torch.float32, device=self.device) if want_frames else None
+        if n and gs[0] and cs[0]:                      # (no frame or no word at all: every output is the undecided value already)
+            g, c = self._f32(gesture), self._f32(content)
+            go, co, ws, we = (self._i32(a) for a in (goh, coh, wsh, weh))
+            self._ck(self.lib.jg_attn_talk(self.h, _ptr(g), _ptr(go), n, gs[0], max(int(T.max()), 1), _ptr(c), _ptr(co), cs[0], _ptr(ws), _ptr(we),
+                                           gs[1], reach, float(temp), int(bool(normalize)), _ptr(band), pitch, _ptr(best_frame),
+                                           _ptr(best_score), _ptr(frame_word), _ptr(frame_prob)))
+        return band, best_frame, best_score, frame_word, frame_prob
 
     def sync_offset(self, vid, aud, v_offsets, a_offsets, max_shift=15, min_overlap=1, want_curve=True):
         """jg_sync_offset: per clip the audio-visual offset (frames; d > 0: audio row t + d matches video row t), its confidence

@@ -617,6 +617,31 @@ int jg_attn_matrix(jg_handle* h, const float* g, const float* c, const int32_t* 
     return misc_launch(h, launch_attn_matrix, g, c, goff, coff, n, D, max_frames, temp, normalize, A, aoff, keys, best_frame, best_score);
 }
 
+int jg_attn_talk(jg_handle* h, const float* gesture, const int32_t* g_offsets, int n_tracks, int64_t n_rows, int max_frames,
+                 const float* content, const int32_t* c_offsets, int n_words, const int32_t* word_start, const int32_t* word_end, int D,
+                 int reach, float temp, int normalize, float* band, int band_pitch, int32_t* best_frame, float* best_score,
+                 int32_t* frame_word, float* frame_prob) {
+    ENTER(h);
+    if (!gesture || !g_offsets || !content || !c_offsets || !word_start || !word_end) JG_FAIL(h, JG_ERR_ARG, "null buffer");
+    if (!band && !best_frame && !best_score && !frame_word && !frame_prob)
+        JG_FAIL(h, JG_ERR_ARG, "no output: band, best_frame, best_score, frame_word and frame_prob are all NULL");
+    if (n_tracks < 0 || n_rows < 0 || n_rows > INT32_MAX || n_words < 0) JG_FAIL(h, JG_ERR_ARG, "n_tracks, n_rows (int32) and n_words must be >= 0");
+    if (max_frames < 1 || max_frames > TALK_MAX_T) JG_FAIL(h, JG_ERR_ARG, "max_frames must be 1..%d", TALK_MAX_T);
+    if (reach < 0 || reach > TALK_MAX_REACH) JG_FAIL(h, JG_ERR_ARG, "reach must be 0..%d", TALK_MAX_REACH);
+    if (!(temp > 0.f)) JG_FAIL(h, JG_ERR_ARG, "temp must be positive");
+    if (band && (band_pitch < 1 || (int64_t)n_words * band_pitch > INT32_MAX))
+        JG_FAIL(h, JG_ERR_ARG, "band needs band_pitch >= 1 and n_words x band_pitch < 2^31");
+    RET(row_pair_check(h, "gesture / content", gesture, content, D));
+    if (n_tracks == 0) return JG_OK;
+    unsigned long long* keys = nullptr;          // per-word arg-max keys, combined across the frame blocks of a track
+    if (best_frame || best_score) {
+        RET(begin_pass(h));
+        RET(wsalloc(h, (size_t)(n_words > 0 ? n_words : 1), &keys));
+    }
+    return misc_launch(h, launch_attn_talk, gesture, g_offsets, n_tracks, (long)n_rows, max_frames, content, c_offsets, n_words, word_start, word_end,
+                       D, reach, temp, normalize, band, band_pitch, keys, best_frame, best_score, frame_word, frame_prob);
+}
+
 int jg_sync_offset(jg_handle* h, const float* vid, const int32_t* v_offsets, const float* aud, const int32_t* a_offsets, int n_clips, int D,
                    int max_shift, int min_overlap, float* curve, int32_t* offset, float* conf) {
     ENTER(h);

@@ -208,6 +208,17 @@ size_t attn_matrix_key_elems(int n_clips);
 hipError_t launch_attn_matrix(const float* g, const float* c, const int32_t* goff, const int32_t* coff, int n, int D, int max_frames,
                               float temp, int normalize, float* A, const int64_t* aoff, unsigned long long* keys,
                               int32_t* best_frame, float* best_score, hipStream_t s);
+// The heat map along whole talks (spotting.hip: attn_talk_kernel): track i = frame rows goff[i] .. goff[i + 1] - 1 of g (n_rows rows) and
+// word rows coff[i] .. coff[i + 1] - 1 of c (n_words rows), wstart / wend [n_words] the words' inclusive bounds on the track's frame axis.
+// band (optional) [n_words][band_pitch], best_* (optional; they need keys: n_words words of scratch) [n_words], frame_* (optional) [n_rows];
+// every element of each is written.  A track outside the limits (0..max_frames frames and its words inside the arrays) is UNDECIDED as
+// a whole, a block of TALK_FB frames with more than TALK_MAX_BLOCK_W words in reach in all its frames: NaN / -1.
+constexpr int TALK_MAX_T = 1 << 20, TALK_MAX_REACH = 1024;
+constexpr int TALK_MAX_BLOCK_W = 128;        // words in reach of a block of 128 frames: the in-register form of the attention matrix
+hipError_t launch_attn_talk(const float* g, const int32_t* goff, int n_tracks, long n_rows, int max_frames, const float* c,
+                            const int32_t* coff, int n_words, const int32_t* wstart, const int32_t* wend, int D, int reach, float temp,
+                            int normalize, float* band, int band_pitch, unsigned long long* keys, int32_t* best_frame, float* best_score,
+                            int32_t* frame_word, float* frame_prob, hipStream_t s);
 hipError_t launch_asd(const float* q, const float* cand, const int32_t* coff, int n, int D, float temp,
                       int32_t* pred2, hipStream_t s);
 // Audio-visual offset per clip (sync_offset.hip: sync_offset_kernel): mean cosine of the row pairs (t, t + d) for d = -R .. R -> curve

@@ -335,3 +335,222 @@ hipError_t launch_attn_matrix(const float* g, const float* c, const int32_t* gof
     if (keys) hipLaunchKernelGGL(attn_best_kernel, dim3(n), dim3(256), 0, s, goff, coff, max_frames, keys, best_frame, best_score);
     return hipGetLastError();
 }
+
+// ---------------------------------------------------------------------------------------------
+// The heat map along a whole talk (jg_attn_talk).  A track has T frame rows and W word rows in transcript order with inclusive frame
+// bounds [start_w, end_w]; word w is IN REACH of frame f iff start_w - reach <= f <= end_w + reach, and
+//   P[w][f] = exp(x_wf - m_f) / sum over the words in reach of f of exp(x_w'f - m_f),  x = <c_w, g_f> / temp,  m_f = the max over those words:
+// every frame sees the words a clip of 2 reach + 1 frames centred on it would contain.  Built from the parts of attn_matrix_kernel<false>:
+// grid = (track, block of TALK_FB frames, aligned to the track's first frame); the block's CANDIDATES are the words in reach of any of
+// its frames -- the bounds are non-decreasing, so they are one contiguous range [lo, hi) found by two binary searches on block-uniform
+// values -- staged with am_stage as the A operand; a wave owns 32 frames and all candidates (am_mfma, am_fold: a logit has the bits
+// jg_attn_matrix gives the same two rows); talk_finish is am_finish with every entry masked by the reach predicate: a masked entry adds
+// exactly 0 to the sum and takes no part in the maximum, so with every word in reach the probabilities are jg_attn_matrix's bit for bit.
+// A block with more than TALK_MAX_BLOCK_W candidates is UNDECIDED in all its frames.  attn_talk_fill_kernel writes the undecided values
+// (NaN band, -1 / NaN frames, zero keys) everywhere first; the blocks overwrite what they decide; attn_talk_best_kernel decodes the keys.
+constexpr int TALK_FB = 128;                 // frames per workgroup
+
+// the track's rows and words, or false = the track is UNDECIDED as a whole (nothing of it is read)
+__device__ __forceinline__ bool talk_track(int trk, const int32_t* __restrict__ goff, long n_rows, int max_frames,
+                                           const int32_t* __restrict__ coff, int n_words, int& t0, int& T, int& w0, int& W) {
+    t0 = goff[trk]; w0 = coff[trk];
+    const long Tl = (long)goff[trk + 1] - t0, Wl = (long)coff[trk + 1] - w0;
+    const bool ok = t0 >= 0 && Tl >= 0 && Tl <= max_frames && t0 + Tl <= n_rows && w0 >= 0 && Wl >= 0 && w0 + Wl <= n_words;
+    T = ok ? (int)Tl : 0; W = ok ? (int)Wl : 0;
+    return ok;
+}
+// the first w in [first, W) with v[w] + add >= bound, W when there is none (v non-decreasing; whatever v holds, the result is in [first, W])
+__device__ __forceinline__ int talk_lower_bound(const int32_t* __restrict__ v, int first, int W, long add, long bound) {
+    int a = first, b = W;
+    while (a < b) {
+        const int m = a + ((b - a) >> 1);
+        if ((long)v[m] + add >= bound) b = m; else a = m + 1;
+    }
+    return a;
+}
+
+// am_finish for a block of a talk: the wave's 32 frames (frame0 ..) against the block's NC candidates, entry (word, frame) taking part iff
+// sLo[word] <= frame <= sHi[word] (an empty interval beyond the candidates).  bandw / kw / fw / fp: the outputs (any may be null) at
+// the block's first candidate / the track's first frame; lo = the first candidate's index inside the track.
+__device__ __forceinline__ void talk_finish(f32x16 (&acc)[4], int NC, int T, int frame0, float temp, const int* sLo, const int* sHi,
+                                            float* __restrict__ bandw, int pitch, unsigned long long* __restrict__ kw,
+                                            int32_t* __restrict__ fw, float* __restrict__ fp, int lo, int lane) {
+    const int h = lane >> 5, l31 = lane & 31;
+    const int frame = frame0 + l31;
+    const bool fok = frame < T;
+    unsigned in[4];                              // bit x of in[i]: accumulator i, register x is a word in reach of the lane's frame
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        in[i] = 0u;
+#pragma unroll
+        for (int x = 0; x < 16; ++x) {
+            const int word = i * 32 + mfma32_row(x, 0) + 4 * h;
+            if (fok && sLo[word] <= frame && frame <= sHi[word]) in[i] |= 1u << x;
+        }
+    }
+    float mx = -INFINITY;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int x = 0; x < 16; ++x) {
+            acc[i][x] = acc[i][x] / temp;
+            if (in[i] >> x & 1) mx = fmaxf(mx, acc[i][x]);
+        }
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    float sum = 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int x = 0; x < 16; ++x) {
+            const float e = (in[i] >> x & 1) ? expf(acc[i][x] - mx) : 0.f;
+            acc[i][x] = e;
+            sum += e;
+        }
+    sum += __shfl_xor(sum, 32, 64);
+    float bp = -1.f;                             // the lane's best word so far: registers come in ascending word order, > keeps the first
+    int bi = 0x7fffffff;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        if (i * 32 < NC) {                                               // wave-uniform: the tile holds a candidate
+            const int word0 = i * 32 + 4 * h;
+#pragma unroll
+            for (int x = 0; x < 16; ++x) {
+                const int word = word0 + mfma32_row(x, 0);
+                const bool inb = in[i] >> x & 1;
+                const float p = acc[i][x] / sum;
+                if (inb && p > bp) { bp = p; bi = word; }
+                if (bandw && inb) {
+                    const long j = (long)frame - sLo[word];                  // >= 0: the word is in reach
+                    if (j < pitch) bandw[(long)word * pitch + j] = p;        // n_words * pitch < 2^31
+                }
+                if (kw) {
+                    // first frame of the 32 with the largest probability: max over the lane half, then the lowest lane that holds it
+                    float m = inb ? p : -1.f;
+#pragma unroll
+                    for (int o = 16; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+                    const unsigned long long bal = __ballot(inb && p == m);
+                    const unsigned mine = (unsigned)(bal >> (32 * h));
+                    if (l31 == 0 && word < NC && mine) {
+                        const unsigned first = frame0 + __ffs(mine) - 1;
+                        atomicMax(&kw[word], ARGMAX_KEY(m, first));
+                    }
+                }
+            }
+        }
+    }
+    if (fw || fp) {
+        const float op = __shfl_xor(bp, 32, 64);
+        const int oi = __shfl_xor(bi, 32, 64);
+        if (op > bp || (op == bp && oi < bi)) { bp = op; bi = oi; }
+        if (h == 0 && fok && bi != 0x7fffffff) {                         // (no word in reach: the frame keeps -1 / NaN)
+            if (fw) fw[frame] = lo + bi;
+            if (fp) fp[frame] = bp;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void attn_talk_kernel(const float* __restrict__ g, const int32_t* __restrict__ goff, long n_rows,
+                                                        int max_frames, const float* __restrict__ c, const int32_t* __restrict__ coff,
+                                                        int n_words, const int32_t* __restrict__ wstart, const int32_t* __restrict__ wend,
+                                                        int D, int reach, float temp, int normalize, float* __restrict__ band, int pitch,
+                                                        unsigned long long* __restrict__ keys, int32_t* __restrict__ frame_word,
+                                                        float* __restrict__ frame_prob) {
+    __shared__ float sC[32 * TALK_MAX_BLOCK_W];      // content chunk [k][candidate]
+    __shared__ float sG[32 * TALK_FB];               // gesture chunk [k][frame]
+    __shared__ float sCn[TALK_MAX_BLOCK_W];          // 1 / max(||c_w||, eps), or 1
+    __shared__ float sGn[TALK_FB];
+    __shared__ int sLo[TALK_MAX_BLOCK_W], sHi[TALK_MAX_BLOCK_W];      // start - reach / end + reach per candidate; empty beyond them
+    const int trk = blockIdx.x, f0 = blockIdx.y * TALK_FB;
+    int t0, T, w0, W;
+    if (!talk_track(trk, goff, n_rows, max_frames, coff, n_words, t0, T, w0, W) || f0 >= T) return;       // block-uniform
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int nf = T - f0 < TALK_FB ? T - f0 : TALK_FB;
+    // candidates [lo, hi): end_w + reach >= f0 and start_w - reach <= f0 + nf - 1; both searches stay inside the track's words
+    const int lo = talk_lower_bound(wend + w0, 0, W, reach, f0);
+    const int hi = talk_lower_bound(wstart + w0, lo, W, -(long)reach, (long)f0 + nf);
+    const int NC = hi - lo;
+    if (NC <= 0 || NC > TALK_MAX_BLOCK_W) return;                        // no word in reach of any frame | UNDECIDED
+    const float* crow = c + (long)(w0 + lo) * D;
+    const float* grow = g + (long)(t0 + f0) * D;
+    for (int w = wave; w < NC; w += 4) {
+        const float rn = normalize ? row_rnorm(crow + (long)w * D, D, lane) : 1.f;
+        if (lane == 0) sCn[w] = rn;
+    }
+    for (int f = wave; f < nf; f += 4) {
+        const float rn = normalize ? row_rnorm(grow + (long)f * D, D, lane) : 1.f;
+        if (lane == 0) sGn[f] = rn;
+    }
+    if (tid < TALK_MAX_BLOCK_W) {
+        // clamped to int32: frames are < 2^20, so neither comparison changes, and a band index taken from a clamped bound is >= 2^31 - 1
+        long a = 0x7fffffffL, b = -0x80000000L;
+        if (tid < NC) { a = (long)wstart[w0 + lo + tid] - reach; b = (long)wend[w0 + lo + tid] + reach; }
+        sLo[tid] = (int)(a < -0x7fffffffL ? -0x7fffffffL : a > 0x7fffffffL ? 0x7fffffffL : a);
+        sHi[tid] = (int)(b < -0x80000000L ? -0x80000000L : b > 0x7fffffffL ? 0x7fffffffL : b);
+    }
+    const int ntile = (NC + 31) >> 5;
+    f32x16 acc[4], tot[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int x = 0; x < 16; ++x) { acc[i][x] = 0.f; tot[i][x] = 0.f; }
+    const bool active = wave * 32 < nf;
+    for (int k0 = 0; k0 < D; k0 += 32) {
+        __syncthreads();
+        if (tid < 128) am_stage<32>(crow, D, k0, NC, ntile * 32, sCn, sC, TALK_MAX_BLOCK_W, tid, 128);
+        else am_stage<32>(grow, D, k0, nf, (nf + 31) & ~31, sGn, sG, TALK_FB, tid - 128, 128);
+        __syncthreads();
+        if (active) am_mfma<4, 1, 32, TALK_MAX_BLOCK_W, TALK_FB>(sC, sG, 0, ntile, wave * 32, lane, acc);
+        if ((k0 + 32) % AM_KSPLIT == 0 || k0 + 32 == D) am_fold<4>(acc, tot);
+    }
+    if (active)
+        talk_finish(tot, NC, T, f0 + wave * 32, temp, sLo, sHi, band ? band + (long)(w0 + lo) * pitch : nullptr, pitch,
+                    keys ? keys + w0 + lo : nullptr, frame_word ? frame_word + t0 : nullptr, frame_prob ? frame_prob + t0 : nullptr, lo, lane);
+}
+
+// the undecided values, everywhere (each output may be null)
+__global__ void attn_talk_fill_kernel(float* __restrict__ band, long band_elems, unsigned long long* __restrict__ keys, int n_words,
+                                      int32_t* __restrict__ frame_word, float* __restrict__ frame_prob, long n_rows) {
+    const long step = (long)gridDim.x * blockDim.x, first = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const float nan = __builtin_nanf("");
+    if (band)
+        for (long e = first; e < band_elems; e += step) band[e] = nan;
+    if (keys)
+        for (long e = first; e < n_words; e += step) keys[e] = 0ull;
+    for (long e = first; e < n_rows; e += step) {
+        if (frame_word) frame_word[e] = -1;
+        if (frame_prob) frame_prob[e] = nan;
+    }
+}
+
+// keys -> best_frame / best_score (either may be null); a word without a decided frame reads -1 / NaN
+__global__ void attn_talk_best_kernel(const unsigned long long* __restrict__ keys, int n_words, int32_t* __restrict__ best_frame,
+                                      float* __restrict__ best_score) {
+    for (long w = (long)blockIdx.x * blockDim.x + threadIdx.x; w < n_words; w += (long)gridDim.x * blockDim.x) {
+        const unsigned long long key = keys[w];
+        if (best_frame) best_frame[w] = key ? argmax_key_frame(key) : -1;
+        if (best_score) best_score[w] = key ? argmax_key_prob(key) : __builtin_nanf("");
+    }
+}
+
+hipError_t launch_attn_talk(const float* g, const int32_t* goff, int n_tracks, long n_rows, int max_frames, const float* c,
+                            const int32_t* coff, int n_words, const int32_t* wstart, const int32_t* wend, int D, int reach, float temp,
+                            int normalize, float* band, int band_pitch, unsigned long long* keys, int32_t* best_frame, float* best_score,
+                            int32_t* frame_word, float* frame_prob, hipStream_t s) {
+    if (n_tracks <= 0) return hipSuccess;
+    const long band_elems = band ? (long)n_words * band_pitch : 0;
+    if (D <= 0 || D % 64 || max_frames < 1 || max_frames > TALK_MAX_T || reach < 0 || reach > TALK_MAX_REACH || n_rows < 0 || n_words < 0 ||
+        !(temp > 0.f) || (band && (band_pitch < 1 || band_elems > 0x7fffffffL)) || ((best_frame || best_score) && !keys) ||
+        (!band && !keys && !frame_word && !frame_prob))
+        return hipErrorInvalidValue;
+    record_kernel("attn_talk_fill_kernel+attn_talk_kernel+attn_talk_best_kernel");
+    long most = band_elems > n_rows ? band_elems : n_rows;
+    most = most > n_words ? most : n_words;
+    if (most > 0)
+        hipLaunchKernelGGL(attn_talk_fill_kernel, dim3(grid_for(most)), dim3(256), 0, s, band, band_elems, keys, n_words, frame_word, frame_prob,
+                           n_rows);
+    hipLaunchKernelGGL(attn_talk_kernel, dim3(n_tracks, (max_frames + TALK_FB - 1) / TALK_FB), dim3(256), 0, s, g, goff, n_rows, max_frames, c,
+                       coff, n_words, wstart, wend, D, reach, temp, normalize, band, band_pitch, keys, frame_word, frame_prob);
+    if (keys && n_words > 0)
+        hipLaunchKernelGGL(attn_talk_best_kernel, dim3(grid_for(n_words)), dim3(256), 0, s, keys, n_words, best_frame, best_score);
+    return hipGetLastError();
+}

@@ -797,7 +797,7 @@ def cmd_embed_tracks(argv, engine=None, jegal=None):
     """Gesture embeddings of whole tracks, however long: reads the ``<feature_dir>/<vid>/<track>.npy`` (T,1024) GestSync features that
     extract_gestsync_feats writes, runs JEGAL.forward_gesture_tracks on them (windows of --win emitted frames with --ctx frames of context
     on both sides: include/jegal_hip.h, jg_jegal_gesture_tracks) and writes ``<result_dir>/v/<vid>__<track>.pkl`` = {"gesture_emb": (T,512)
-    unit rows, "content_emb": None, "info": {"fname", "win", "ctx"}} -- the file search, asd and attn_matrix read.  Tracks are packed into
+    unit rows, "content_emb": None, "info": {"fname", "win", "ctx"}} -- the file search, asd and spot_talk read.  Tracks are packed into
     engine calls of at most --rows_per_call frames (a longer track goes alone); a track's rows do not depend on what it is packed with.
     engine / jegal: an Engine and a loaded JEGAL to run on (default: this process's, loaded from --checkpoint_path_jegal)."""
     p = argparse.ArgumentParser(prog="embed_tracks")
@@ -882,7 +882,67 @@ def cmd_embed_tracks(argv, engine=None, jegal=None):
     return 0
 
 
+SPOT_TALK_NOTE = ("--reach 110 is half the longest clip of the training lists (220 frames): every frame sees the words a clip of that length "
+                  "centred on it would contain.  It is a choice, not a measured optimum: no trained checkpoint was available to tune it on.")
+
+
+def cmd_spot_talk(argv, engine=None):
+    """The gesture-word heat map of a whole talk, and its word spotting: --gesture is the track's .pkl as embed_tracks writes it (gesture_emb
+    (T,512), any T up to 2^20); the words come from --content, one feature .pkl whose content_emb rows and info["word_boundaries"] are on
+    the track's frame axis, or from --utterances, a csv with the columns filename and start_frame: every row names an utterance-level
+    feature .pkl under --path (``a/b`` -> ``a__b.pkl``, as extract_jegal_embs names them; inference_embs --modalities ta writes the same
+    from wav and text alone) and the frame of the talk at which it begins (metrics.talk_words).  One jg_attn_talk call.  Writes
+    ``<res_dir>/<name>.talk.npz`` = {words (W,), word_start, word_end (W,) int32, first_frame (W,) int32, band (W, 2 reach + longest word)
+    float32: band[w][j] = the probability of word w at frame first_frame[w] + j, NaN outside the track or its reach; best_frame (W,) int32,
+    best_score (W,) float32; frame_word (T,) int32, frame_prob (T,) float32}; --band 0 leaves first_frame and band out.  <name> is the
+    gesture .pkl's own name.  engine: the Engine to run on (default: this process's)."""
+    from . import metrics as M
+    p = argparse.ArgumentParser(prog="spot_talk", description=SPOT_TALK_NOTE)
+    p.add_argument("--gesture", required=True, help="the track's .pkl (embed_tracks): gesture_emb (T,512)")
+    p.add_argument("--content", default=None, help="a feature .pkl with content_emb (W,512) and word boundaries on the track's frame axis")
+    p.add_argument("--utterances", default=None, help="a csv (filename, start_frame) of utterance-level feature .pkl files under --path")
+    p.add_argument("--path", default=None, help="the directory of the --utterances files")
+    p.add_argument("--reach", type=int, default=110, help="frames around a word within which it competes for a frame.  " + SPOT_TALK_NOTE)
+    p.add_argument("--temp", type=float, default=0.07)
+    p.add_argument("--normalize", type=int, default=0, choices=[0, 1], help="1: re-normalise the rows first (evaluate_spotting.py:39-57)")
+    p.add_argument("--band", type=int, default=1, choices=[0, 1], help="0: best_* and frame_* only")
+    p.add_argument("--res_dir", default=".")
+    args = p.parse_args(argv)
+    if (args.content is None) == (args.utterances is None) or (args.utterances is not None and args.path is None):
+        raise SystemExit("spot_talk: give --content C.pkl, or --utterances LIST.csv with --path DIR")
+
+    def load(fn):
+        with open(fn, "rb") as f:
+            return pickle.load(f)
+
+    track = load(args.gesture)
+    if track.get("gesture_emb") is None:
+        raise SystemExit("{} holds no gesture_emb".format(args.gesture))
+    gesture = np.asarray(track["gesture_emb"], np.float32)
+    if args.content is not None:
+        ft = load(args.content)
+        if ft.get("content_emb") is None:
+            raise SystemExit("{} holds no content_emb".format(args.content))
+        content, bounds = M.talk_words([ft], [0])
+    else:
+        import pandas as pd
+        df = pd.read_csv(args.utterances)
+        stem = lambda fname: "__".join(str(fname).split("/")) + ("" if str(fname).endswith(".pkl") else ".pkl")
+        content, bounds = M.talk_words([load(os.path.join(args.path, stem(f))) for f in df.filename], [int(s) for s in df.start_frame])
+    eng = engine if engine is not None else _models(args)[0]
+    call = M.talk_heatmap if args.band else M.spot_talk
+    r = call(gesture, content, bounds, reach=args.reach, temp=args.temp, normalize=bool(args.normalize), engine=eng)
+    os.makedirs(args.res_dir, exist_ok=True)
+    name = os.path.basename(args.gesture).rsplit(".", 1)[0]
+    out = os.path.join(args.res_dir, name + ".talk.npz")
+    np.savez(out, words=np.asarray([b[0] for b in bounds]), word_start=np.asarray([b[1] for b in bounds], np.int32),
+             word_end=np.asarray([b[2] for b in bounds], np.int32), **r)
+    print("Talk heat map: {} frames, {} words, reach {} -> {}".format(gesture.shape[0], len(bounds), args.reach, out))
+    return 0
+
+
 COMMANDS = {
+    "spot_talk": cmd_spot_talk,
     "embed_tracks": cmd_embed_tracks,
     "sync_offset": cmd_sync_offset,
     "attn_matrix": cmd_attn_matrix,

@@ -423,3 +423,83 @@ def asd_timeline(contents, word_boundaries, tracks, win=25, hop=5, temp=0.07, en
         out.append(dict(start=(np.arange(n_win) * hop).astype(np.int32), prob=prob[p_off[i]:p_off[i + 1]].reshape(n_win, len(scene)),
                         pred=pred[w_off[i]:w_off[i + 1]]))
     return out[0] if single else out
+
+
+def _talk_call(gesture, content, word_boundaries, reach, temp, normalize, engine, want_band):
+    """One Engine.attn_talk call for a track or a list of tracks -> per track a dict of host arrays"""
+    single = not isinstance(gesture, (list, tuple))
+    if single:
+        gesture, content, word_boundaries = [gesture], [content], [word_boundaries]
+    if not (len(gesture) == len(content) == len(word_boundaries)):
+        raise ValueError("one content array and one list of word boundaries per track")
+    if not len(gesture):
+        return []
+    se = [_bounds(wb) for wb in word_boundaries]
+    for (s, _), c in zip(se, content):
+        if len(s) != len(c):
+            raise ValueError("{} word boundaries for {} content rows".format(len(s), len(c)))
+    eng = engine or Engine.get()
+    goff, coff = _offsets(gesture).astype(np.int64), _offsets(content).astype(np.int64)
+    start, end = np.concatenate([s for s, _ in se]), np.concatenate([e for _, e in se])
+    band, bf, bs, fw, fp = eng.attn_talk(_rows(gesture), _rows(content), goff, coff, start, end, reach=reach, temp=temp, normalize=normalize,
+                                         want_band=want_band)
+    bf, bs, fw, fp = _host(bf), _host(bs), _host(fw), _host(fp)
+    band = _host(band) if want_band else None
+    out = []
+    for i in range(len(gesture)):
+        w, f = slice(int(coff[i]), int(coff[i + 1])), slice(int(goff[i]), int(goff[i + 1]))
+        d = dict(best_frame=bf[w], best_score=bs[w], frame_word=fw[f], frame_prob=fp[f])
+        if want_band:
+            d.update(first_frame=(start[w] - int(reach)).astype(np.int32), band=band[w])
+        out.append(d)
+    return out[0] if single else out
+
+
+def talk_heatmap(gesture, content, word_boundaries, reach=110, temp=0.07, normalize=True, engine=None):
+    """The gesture-word heat map along a whole talk: a track's frame rows (T, D) -- embed_tracks' gesture_emb, of any length up to 2^20 --
+    against the W word rows of its transcript, word_boundaries = [word, start, end] triplets (or (start, end) pairs) with inclusive
+    frames on the track's axis, in transcript order.  Word w is in reach of frame f iff start_w - reach <= f <= end_w + reach, and the
+    softmax of a frame runs over the words in reach of it: every frame sees the words a clip of 2 reach + 1 frames centred on it would
+    contain (the clip form, attention_matrices, runs its softmax over all words of a clip of at most 220 frames, which is what the
+    model was trained on; reach = 110 is half of that, a choice and not a measured optimum).  One track, or lists of tracks (-> a
+    list); one jg_attn_talk call for the batch.
+    Returns per track a dict of host arrays: band (W, 2 reach + longest word) float32 with band[w][j] = the probability of word w at
+    frame first_frame[w] + j (NaN outside the track, beyond end_w + reach, or undecided); first_frame (W,) int32 = start_w - reach;
+    best_frame (W,) int32 / best_score (W,) float32: the word's first arg-max frame and that probability (-1 / NaN without a frame);
+    frame_word (T,) int32 / frame_prob (T,) float32: the frame's most probable word and its probability (-1 / NaN when no word is in
+    reach).  More than 128 words in reach of a block of 128 frames is refused (ValueError): lower reach."""
+    return _talk_call(gesture, content, word_boundaries, reach, temp, normalize, engine, True)
+
+
+def spot_talk(gesture, content, word_boundaries, reach=110, temp=0.07, normalize=True, engine=None):
+    """talk_heatmap without the band: every word of a talk localised (best_frame, best_score) and every frame labelled (frame_word,
+    frame_prob); the band is not written (jg_attn_talk with band = NULL)."""
+    return _talk_call(gesture, content, word_boundaries, reach, temp, normalize, engine, False)
+
+
+def talk_words(utterances, starts):
+    """The word rows of a talk from its utterances: `utterances` are feature dicts {"content_emb" (W_i, 512), "info": {word_boundaries}} as
+    extract_jegal_embs / inference_embs --modalities ta write them from wav and text alone (the utterance is the unit the content encoders
+    were trained on), `starts` the first frame of each utterance on the talk's frame axis.  Returns (content (sum W, 512) float32, bounds =
+    [[word, start, end]] on the talk's axis), utterances in the order of their starts.  Raises ValueError when the shifted boundaries are
+    not in order (utterances that overlap out of order), or when an utterance's boundaries do not match its content rows."""
+    starts = np.asarray(starts, np.int64).reshape(-1)
+    if len(utterances) != starts.size:
+        raise ValueError("one start frame per utterance")
+    rows, bounds = [], []
+    for i in np.argsort(starts, kind="stable"):
+        u = utterances[int(i)]
+        if u.get("content_emb") is None:
+            raise ValueError("utterance {} holds no content_emb".format(int(i)))
+        c = np.asarray(u["content_emb"], np.float32)
+        wb = u["info"]["word_boundaries"]
+        wb = ast.literal_eval(wb) if isinstance(wb, str) else wb
+        if len(wb) != len(c):
+            raise ValueError("utterance {}: {} word boundaries for {} content rows".format(int(i), len(wb), len(c)))
+        rows.append(c)
+        bounds += [[str(b[0]), int(b[-2]) + int(starts[i]), int(b[-1]) + int(starts[i])] for b in wb]
+    s, e = np.asarray([b[1] for b in bounds], np.int64), np.asarray([b[2] for b in bounds], np.int64)
+    if (np.diff(s) < 0).any() or (np.diff(e) < 0).any() or (s > e).any():
+        raise ValueError("the utterances overlap out of order: the shifted word boundaries are not non-decreasing")
+    content = np.concatenate(rows, 0) if rows else np.zeros((0, 512), np.float32)
+    return content, bounds
