@@ -256,12 +256,7 @@ __global__ __launch_bounds__(256) void asd_windows_kernel(const float* __restric
         const float pr = e / wave_sum(e);
         float best = present ? pr : -1.f;
         int bi = lane;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ob = __shfl_xor(best, o, 64);
-            const int oi = __shfl_xor(bi, o, 64);
-            if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-        }
+        wave_best_first(best, bi);
         if (cand) {
             prob[row + lane] = pr;
             if (cosv) cosv[row + lane] = present ? cs : nan;

@@ -45,6 +45,18 @@ __device__ __forceinline__ float wmax(float v) {
     return v;
 }
 
+// (best, bi) <- the pair with the larger `best`, on equal ones the lower index, among the lanes that differ from this one in the lane bits
+// 32 .. LAST.  LAST = 1: over the wave, the same pair in every lane; LAST = 32: over the lane and its partner in the other half.
+template <int LAST = 1>
+__device__ __forceinline__ void wave_best_first(float& best, int& bi) {
+#pragma unroll
+    for (int o = 32; o >= LAST; o >>= 1) {
+        const float ob = __shfl_xor(best, o, 64);
+        const int oi = __shfl_xor(bi, o, 64);
+        if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+    }
+}
+
 // ||row||; the same bits in every lane
 __device__ __forceinline__ float row_norm(const float* __restrict__ row, int D, int lane) {
     float sq = 0.f;

@@ -62,12 +62,7 @@ __global__ __launch_bounds__(256) void spot_kernel(const float* __restrict__ g, 
             const float a = sA[t];
             if (a > best) { best = a; bi = t; }      // strided scan keeps the first index per lane
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ob = __shfl_xor(best, o, 64);
-            const int oi = __shfl_xor(bi, o, 64);
-            if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-        }
+        wave_best_first(best, bi);
         if (lane == 0) { pred[clip] = bi; score[clip] = best; }
     }
 }
@@ -97,20 +92,51 @@ hipError_t launch_spot(const float* g, const float* c, const int32_t* goff, cons
 // The per-word arg-max is combined across waves and frame blocks by a 64-bit atomicMax on (probability bits, ~frame):
 // order-independent, and on equal probabilities the smaller frame wins (np.argmax's first index).  attn_keys_init_kernel
 // zeroes the keys of the clips inside the limits, attn_best_kernel decodes them (and marks the clips outside).
+//
+// The parts, each defined once and shared with the talk form below (jg_attn_talk), whose logits, softmax and keys therefore have the
+// bits these kernels give the same rows:
+//   am_row_scales                the staging factors of the content and gesture rows
+//   am_stage, am_mfma, am_fold   one k chunk into LDS, its MFMAs, the cut of the k-ordered chains
+//   am_reg_logits                the in-register form's k loop over those three: the logits of 128 words x the wave's 32 frames
+//   am_softmax                   exp(x / temp - max) and its sum over the entries a mask admits
+//   am_key_max                   a word's best frame among the wave's 32 into its key; argmax_key_decode reads a key back
+// attn_matrix_kernel<false> = am_row_scales, am_reg_logits, am_finish<4, 1>; attn_matrix_kernel<true> = am_row_scales, then per frame
+// tile its own k loop (8 k at a time over all words) and am_finish<8, 4>.  am_finish = am_softmax over the words that exist, the stores
+// into the (W, T) matrix, am_key_max.
 constexpr int AM_FB = 128;                   // frames per workgroup
 constexpr int AM_REG_W = 128;                // widest clip of the in-register form
 constexpr int AM_KEY_PITCH = SPOT_MAX_W;     // keys[clip][word]: the host cannot know sum W (the offsets are device arrays)
 
 size_t attn_matrix_key_elems(int n_clips) { return (size_t)n_clips * AM_KEY_PITCH; }
 // The arg-max key of a word: (fp32 bits of the probability << 32) | ~frame, so that a 64-bit max prefers the larger probability and then
-// the smaller frame; 0 = no frame yet.  (The pack is a macro: as a function, inlined or not, it changes the register allocation of both
-// attn_matrix_kernel instances.)
-#define ARGMAX_KEY(prob, frame) (((unsigned long long)__float_as_uint(prob) << 32) | (0xffffffffu - (frame)))
+// the smaller frame; 0 = no frame yet.
+__device__ __forceinline__ unsigned long long argmax_key(float prob, unsigned frame) {
+    return ((unsigned long long)__float_as_uint(prob) << 32) | (0xffffffffu - frame);
+}
 __device__ __forceinline__ int32_t argmax_key_frame(unsigned long long key) { return (int32_t)(0xffffffffu - (unsigned)key); }
 __device__ __forceinline__ float argmax_key_prob(unsigned long long key) { return __uint_as_float((unsigned)(key >> 32)); }
+// key -> best_frame[at] / best_score[at] (either may be null); no frame: -1 / NaN
+__device__ __forceinline__ void argmax_key_decode(unsigned long long key, int32_t* __restrict__ best_frame, float* __restrict__ best_score,
+                                                  long at) {
+    if (best_frame) best_frame[at] = key ? argmax_key_frame(key) : -1;
+    if (best_score) best_score[at] = key ? argmax_key_prob(key) : __builtin_nanf("");
+}
 
 __device__ __forceinline__ bool attn_clip_ok(int T, int W, int max_frames) {
     return T > 0 && T <= SPOT_MAX_T && T <= max_frames && W > 0 && W <= SPOT_MAX_W;
+}
+
+// sCn[w] / sGn[f] = the factor that content row w < nw / gesture row f < nf is staged with: 1 / max(||row||, 1e-12), or 1
+__device__ __forceinline__ void am_row_scales(const float* __restrict__ crow, int nw, const float* __restrict__ grow, int nf, int D,
+                                              int normalize, float* sCn, float* sGn, int lane, int wave) {
+    for (int w = wave; w < nw; w += 4) {
+        const float rn = normalize ? row_rnorm(crow + (long)w * D, D, lane) : 1.f;
+        if (lane == 0) sCn[w] = rn;
+    }
+    for (int f = wave; f < nf; f += 4) {
+        const float rn = normalize ? row_rnorm(grow + (long)f * D, D, lane) : 1.f;
+        if (lane == 0) sGn[f] = rn;
+    }
 }
 
 // rows r0, r0 + rstep, .. < npad of `rows`, columns k0 .. k0 + KC - 1, scaled by rinv[r], into dst[k][r] (pitch floats per k);
@@ -160,26 +186,44 @@ __device__ __forceinline__ void am_fold(f32x16 (&acc)[NT], f32x16 (&tot)[NT]) {
         for (int x = 0; x < 16; ++x) { tot[i][x] += acc[i][x]; acc[i][x] = 0.f; }
 }
 
-// Softmax over the clip's words for the wave's 32 frames (frame0 ..), as torch evaluates it: exp(x - max) / sum exp(x - max); then the
-// stores and the arg-max keys.  Accumulator layout: frame = lane & 31, word = 32 tile + mfma32_row(x, lane >> 5).
-// TSTEP > 1: the four waves hold different words of the SAME frames and every wave of the workgroup makes this call.
-template <int NT, int TSTEP>
-__device__ __forceinline__ void am_finish(f32x16 (&acc)[NT], int tbase, int W, int T, int frame0, float temp, float* __restrict__ Aclip,
-                                          unsigned long long* __restrict__ kclip, float (*sRed)[4][32], int lane, int wave) {
-    // Everything below that depends only on W, T and the lane is invariant in the wide form's frame-tile loop; hoisted out of it, the
-    // word predicates and store offsets of 128 registers spill.  An empty asm keeps them inside.
-    asm volatile("" : "+s"(W), "+s"(T));
+// The in-register form's logits: tot = <content row, gesture row> over all of D for the nw <= 128 words at crow against the wave's 32 of
+// the nf <= 128 frames at grow.  sC / sG: 32 k of [k][word] / [k][frame] staging with pitches CP / GP.
+template <int CP, int GP>
+__device__ __forceinline__ void am_reg_logits(const float* __restrict__ crow, int nw, const float* __restrict__ grow, int nf, int D,
+                                              const float* sCn, const float* sGn, float* sC, float* sG, int tid, f32x16 (&tot)[4]) {
+    const int lane = tid & 63, wave = tid >> 6;
+    const int ntile = (nw + 31) >> 5;
+    f32x16 acc[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int x = 0; x < 16; ++x) { acc[i][x] = 0.f; tot[i][x] = 0.f; }
+    const bool active = wave * 32 < nf;
+    for (int k0 = 0; k0 < D; k0 += 32) {
+        __syncthreads();
+        if (tid < 128) am_stage<32>(crow, D, k0, nw, ntile * 32, sCn, sC, CP, tid, 128);
+        else am_stage<32>(grow, D, k0, nf, (nf + 31) & ~31, sGn, sG, GP, tid - 128, 128);
+        __syncthreads();
+        if (active) am_mfma<4, 1, 32, CP, GP>(sC, sG, 0, ntile, wave * 32, lane, acc);
+        if ((k0 + 32) % AM_KSPLIT == 0 || k0 + 32 == D) am_fold<4>(acc, tot);
+    }
+}
+
+// The softmax over the words of the lane's frame as torch evaluates it, exp(x - max) / sum exp(x - max), up to the division:
+// acc[i][x] <- in(i, x) ? exp(acc[i][x] / temp - max) : 0, returns the sum.  in(i, x): accumulator i, register x takes part; the same value
+// at every call.  An entry outside adds exactly 0 to the sum and takes no part in the maximum.  Accumulator layout: frame = lane & 31,
+// word = 32 tile + mfma32_row(x, lane >> 5).  TSTEP > 1: the four waves hold different words of the SAME frames, every wave of the
+// workgroup makes this call, and max and sum cross the waves through sRed in a fixed order (TSTEP == 1 reads neither sRed nor wave).
+template <int NT, int TSTEP, class In>
+__device__ __forceinline__ float am_softmax(f32x16 (&acc)[NT], float temp, In in, float (*sRed)[4][32], int lane, int wave) {
     const int h = lane >> 5, l31 = lane & 31;
-    const int frame = frame0 + l31;
-    const bool fok = frame < T;
-    const int wl = W - 4 * h - tbase * 32;           // accumulator i, register x holds a word of the clip iff roff(x) < wl - 32 i TSTEP
     float mx = -INFINITY;
 #pragma unroll
     for (int i = 0; i < NT; ++i)
 #pragma unroll
         for (int x = 0; x < 16; ++x) {
             acc[i][x] = acc[i][x] / temp;
-            if (mfma32_row(x, 0) < wl - i * TSTEP * 32) mx = fmaxf(mx, acc[i][x]);
+            if (in(i, x)) mx = fmaxf(mx, acc[i][x]);
         }
     mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
     if constexpr (TSTEP > 1) {
@@ -192,7 +236,7 @@ __device__ __forceinline__ void am_finish(f32x16 (&acc)[NT], int tbase, int W, i
     for (int i = 0; i < NT; ++i)
 #pragma unroll
         for (int x = 0; x < 16; ++x) {
-            const float e = mfma32_row(x, 0) < wl - i * TSTEP * 32 ? expf(acc[i][x] - mx) : 0.f;
+            const float e = in(i, x) ? expf(acc[i][x] - mx) : 0.f;
             acc[i][x] = e;
             sum += e;
         }
@@ -202,6 +246,35 @@ __device__ __forceinline__ void am_finish(f32x16 (&acc)[NT], int tbase, int W, i
         __syncthreads();
         sum = ((sRed[1][0][l31] + sRed[1][1][l31]) + sRed[1][2][l31]) + sRed[1][3][l31];
     }
+    return sum;
+}
+
+// A word's first frame with the largest probability among the wave's 32 (frame0 ..) into its key at `slot`: max over the lane half (lanes
+// without `valid` count as -1), then the lowest lane that holds it.  Every lane of the wave makes the call with its own p of the same word;
+// word_ok: the half's word exists.
+__device__ __forceinline__ void am_key_max(unsigned long long* slot, float p, bool valid, bool word_ok, int frame0, int lane) {
+    const int h = lane >> 5, l31 = lane & 31;
+    float m = valid ? p : -1.f;
+#pragma unroll
+    for (int o = 16; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    const unsigned long long bal = __ballot(valid && p == m);
+    const unsigned mine = (unsigned)(bal >> (32 * h));
+    if (l31 == 0 && word_ok && mine) atomicMax(slot, argmax_key(m, frame0 + __ffs(mine) - 1));
+}
+
+// The clip form's end for the wave's 32 frames (frame0 ..): the softmax over the clip's words, the stores into the (W, T) matrix and the
+// arg-max keys.  Accumulator i is word tile tbase + i * TSTEP.
+template <int NT, int TSTEP>
+__device__ __forceinline__ void am_finish(f32x16 (&acc)[NT], int tbase, int W, int T, int frame0, float temp, float* __restrict__ Aclip,
+                                          unsigned long long* __restrict__ kclip, float (*sRed)[4][32], int lane, int wave) {
+    // Everything below that depends only on W, T and the lane is invariant in the wide form's frame-tile loop; hoisted out of it, the
+    // word predicates and store offsets of 128 registers spill.  An empty asm keeps them inside.
+    asm volatile("" : "+s"(W), "+s"(T));
+    const int h = lane >> 5, l31 = lane & 31;
+    const int frame = frame0 + l31;
+    const bool fok = frame < T;
+    const int wl = W - 4 * h - tbase * 32;           // accumulator i, register x holds a word of the clip iff roff(x) < wl - 32 i TSTEP
+    const float sum = am_softmax<NT, TSTEP>(acc, temp, [&](int i, int x) { return mfma32_row(x, 0) < wl - i * TSTEP * 32; }, sRed, lane, wave);
 #pragma unroll
     for (int i = 0; i < NT; ++i) {
         const int tile = tbase + i * TSTEP;
@@ -214,18 +287,7 @@ __device__ __forceinline__ void am_finish(f32x16 (&acc)[NT], int tbase, int W, i
                 const bool wok = roff < wl - i * TSTEP * 32;
                 const float p = acc[i][x] / sum;
                 if (Aclip && fok && wok) Arow[roff * T] = p;          // W T <= 2^23 elements per clip
-                if (kclip) {
-                    // first frame of the 32 with the largest probability: max over the lane half, then the lowest lane that holds it
-                    float m = fok ? p : -1.f;
-#pragma unroll
-                    for (int o = 16; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-                    const unsigned long long bal = __ballot(fok && p == m);
-                    const unsigned mine = (unsigned)(bal >> (32 * h));
-                    if (l31 == 0 && wok && mine) {
-                        const unsigned first = frame0 + __ffs(mine) - 1;
-                        atomicMax(&kclip[word0 + roff], ARGMAX_KEY(m, first));
-                    }
-                }
+                if (kclip) am_key_max(&kclip[word0 + roff], p, fok, wok, frame0, lane);
             }
         }
     }
@@ -249,35 +311,16 @@ __global__ __launch_bounds__(256) void attn_matrix_kernel(const float* __restric
     const int nf = T - f0 < AM_FB ? T - f0 : AM_FB;
     const float* crow = c + (long)w0 * D;
     const float* grow = g + (long)(t0 + f0) * D;
-    for (int w = wave; w < W; w += 4) {
-        const float rn = normalize ? row_rnorm(crow + (long)w * D, D, lane) : 1.f;
-        if (lane == 0) sCn[w] = rn;
-    }
-    for (int f = wave; f < nf; f += 4) {
-        const float rn = normalize ? row_rnorm(grow + (long)f * D, D, lane) : 1.f;
-        if (lane == 0) sGn[f] = rn;
-    }
+    am_row_scales(crow, W, grow, nf, D, normalize, sCn, sGn, lane, wave);
     float* Aclip = A ? A + aoff[clip] : nullptr;
     unsigned long long* kclip = keys ? keys + (size_t)clip * AM_KEY_PITCH : nullptr;
-    const int ntile = (W + 31) >> 5;
 
     if constexpr (!WIDE) {
-        f32x16 acc[4], tot[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int x = 0; x < 16; ++x) { acc[i][x] = 0.f; tot[i][x] = 0.f; }
-        const bool active = wave * 32 < nf;
-        for (int k0 = 0; k0 < D; k0 += 32) {
-            __syncthreads();
-            if (tid < 128) am_stage<32>(crow, D, k0, W, ntile * 32, sCn, sC, 128, tid, 128);
-            else am_stage<32>(grow, D, k0, nf, (nf + 31) & ~31, sGn, sG, AM_FB, tid - 128, 128);
-            __syncthreads();
-            if (active) am_mfma<4, 1, 32, 128, AM_FB>(sC, sG, 0, ntile, wave * 32, lane, acc);
-            if ((k0 + 32) % AM_KSPLIT == 0 || k0 + 32 == D) am_fold<4>(acc, tot);
-        }
-        if (active) am_finish<4, 1>(tot, 0, W, T, f0 + wave * 32, temp, Aclip, kclip, sRed, lane, wave);
+        f32x16 tot[4];
+        am_reg_logits<128, AM_FB>(crow, W, grow, nf, D, sCn, sGn, sC, sG, tid, tot);
+        if (wave * 32 < nf) am_finish<4, 1>(tot, 0, W, T, f0 + wave * 32, temp, Aclip, kclip, sRed, lane, wave);
     } else {
+        const int ntile = (W + 31) >> 5;
         for (int ft = 0; ft * 32 < nf; ++ft) {
             f32x16 acc[8], tot[8];
 #pragma unroll
@@ -314,11 +357,8 @@ __global__ void attn_best_kernel(const int32_t* __restrict__ goff, const int32_t
     const int T = goff[clip + 1] - goff[clip];
     const int w0 = coff[clip], W = coff[clip + 1] - w0;
     const bool ok = attn_clip_ok(T, W, max_frames);
-    for (int w = threadIdx.x; w < W; w += blockDim.x) {
-        const unsigned long long key = ok ? keys[(size_t)clip * AM_KEY_PITCH + w] : 0ull;
-        if (best_frame) best_frame[w0 + w] = key ? argmax_key_frame(key) : -1;
-        if (best_score) best_score[w0 + w] = key ? argmax_key_prob(key) : __builtin_nanf("");
-    }
+    for (int w = threadIdx.x; w < W; w += blockDim.x)
+        argmax_key_decode(ok ? keys[(size_t)clip * AM_KEY_PITCH + w] : 0ull, best_frame, best_score, w0 + w);
 }
 
 hipError_t launch_attn_matrix(const float* g, const float* c, const int32_t* goff, const int32_t* coff, int n, int D, int max_frames,
@@ -340,12 +380,13 @@ hipError_t launch_attn_matrix(const float* g, const float* c, const int32_t* gof
 // The heat map along a whole talk (jg_attn_talk).  A track has T frame rows and W word rows in transcript order with inclusive frame
 // bounds [start_w, end_w]; word w is IN REACH of frame f iff start_w - reach <= f <= end_w + reach, and
 //   P[w][f] = exp(x_wf - m_f) / sum over the words in reach of f of exp(x_w'f - m_f),  x = <c_w, g_f> / temp,  m_f = the max over those words:
-// every frame sees the words a clip of 2 reach + 1 frames centred on it would contain.  Built from the parts of attn_matrix_kernel<false>:
-// grid = (track, block of TALK_FB frames, aligned to the track's first frame); the block's CANDIDATES are the words in reach of any of
+// every frame sees the words a clip of 2 reach + 1 frames centred on it would contain.
+// Grid = (track, block of TALK_FB frames, aligned to the track's first frame); the block's CANDIDATES are the words in reach of any of
 // its frames -- the bounds are non-decreasing, so they are one contiguous range [lo, hi) found by two binary searches on block-uniform
-// values -- staged with am_stage as the A operand; a wave owns 32 frames and all candidates (am_mfma, am_fold: a logit has the bits
-// jg_attn_matrix gives the same two rows); talk_finish is am_finish with every entry masked by the reach predicate: a masked entry adds
-// exactly 0 to the sum and takes no part in the maximum, so with every word in reach the probabilities are jg_attn_matrix's bit for bit.
+// values.  attn_talk_kernel = the two searches, am_row_scales and am_reg_logits with the candidates as the words (a wave owns 32 frames
+// and all candidates), talk_finish.  talk_finish = am_softmax over the words in reach of the lane's frame, the stores into the band rows,
+// am_key_max, and the frame's best word.  With every word in reach the mask is am_finish's, so the probabilities, best frames and best
+// scores are jg_attn_matrix's bit for bit.
 // A block with more than TALK_MAX_BLOCK_W candidates is UNDECIDED in all its frames.  attn_talk_fill_kernel writes the undecided values
 // (NaN band, -1 / NaN frames, zero keys) everywhere first; the blocks overwrite what they decide; attn_talk_best_kernel decodes the keys.
 constexpr int TALK_FB = 128;                 // frames per workgroup
@@ -369,14 +410,14 @@ __device__ __forceinline__ int talk_lower_bound(const int32_t* __restrict__ v, i
     return a;
 }
 
-// am_finish for a block of a talk: the wave's 32 frames (frame0 ..) against the block's NC candidates, entry (word, frame) taking part iff
+// The talk form's end for the wave's 32 frames (frame0 ..) against the block's NC candidates, entry (word, frame) taking part iff
 // sLo[word] <= frame <= sHi[word] (an empty interval beyond the candidates).  bandw / kw / fw / fp: the outputs (any may be null) at
 // the block's first candidate / the track's first frame; lo = the first candidate's index inside the track.
 __device__ __forceinline__ void talk_finish(f32x16 (&acc)[4], int NC, int T, int frame0, float temp, const int* sLo, const int* sHi,
                                             float* __restrict__ bandw, int pitch, unsigned long long* __restrict__ kw,
                                             int32_t* __restrict__ fw, float* __restrict__ fp, int lo, int lane) {
-    const int h = lane >> 5, l31 = lane & 31;
-    const int frame = frame0 + l31;
+    const int h = lane >> 5;
+    const int frame = frame0 + (lane & 31);
     const bool fok = frame < T;
     unsigned in[4];                              // bit x of in[i]: accumulator i, register x is a word in reach of the lane's frame
 #pragma unroll
@@ -388,25 +429,7 @@ __device__ __forceinline__ void talk_finish(f32x16 (&acc)[4], int NC, int T, int
             if (fok && sLo[word] <= frame && frame <= sHi[word]) in[i] |= 1u << x;
         }
     }
-    float mx = -INFINITY;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int x = 0; x < 16; ++x) {
-            acc[i][x] = acc[i][x] / temp;
-            if (in[i] >> x & 1) mx = fmaxf(mx, acc[i][x]);
-        }
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    float sum = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int x = 0; x < 16; ++x) {
-            const float e = (in[i] >> x & 1) ? expf(acc[i][x] - mx) : 0.f;
-            acc[i][x] = e;
-            sum += e;
-        }
-    sum += __shfl_xor(sum, 32, 64);
+    const float sum = am_softmax<4, 1>(acc, temp, [&](int i, int x) { return (in[i] >> x & 1) != 0; }, nullptr, lane, 0);
     float bp = -1.f;                             // the lane's best word so far: registers come in ascending word order, > keeps the first
     int bi = 0x7fffffff;
 #pragma unroll
@@ -423,25 +446,12 @@ __device__ __forceinline__ void talk_finish(f32x16 (&acc)[4], int NC, int T, int
                     const long j = (long)frame - sLo[word];                  // >= 0: the word is in reach
                     if (j < pitch) bandw[(long)word * pitch + j] = p;        // n_words * pitch < 2^31
                 }
-                if (kw) {
-                    // first frame of the 32 with the largest probability: max over the lane half, then the lowest lane that holds it
-                    float m = inb ? p : -1.f;
-#pragma unroll
-                    for (int o = 16; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-                    const unsigned long long bal = __ballot(inb && p == m);
-                    const unsigned mine = (unsigned)(bal >> (32 * h));
-                    if (l31 == 0 && word < NC && mine) {
-                        const unsigned first = frame0 + __ffs(mine) - 1;
-                        atomicMax(&kw[word], ARGMAX_KEY(m, first));
-                    }
-                }
+                if (kw) am_key_max(&kw[word], p, inb, word < NC, frame0, lane);
             }
         }
     }
     if (fw || fp) {
-        const float op = __shfl_xor(bp, 32, 64);
-        const int oi = __shfl_xor(bi, 32, 64);
-        if (op > bp || (op == bp && oi < bi)) { bp = op; bi = oi; }
+        wave_best_first<32>(bp, bi);                                     // the two halves hold different words of the same frame
         if (h == 0 && fok && bi != 0x7fffffff) {                         // (no word in reach: the frame keeps -1 / NaN)
             if (fw) fw[frame] = lo + bi;
             if (fp) fp[frame] = bp;
@@ -472,14 +482,7 @@ __global__ __launch_bounds__(256) void attn_talk_kernel(const float* __restrict_
     if (NC <= 0 || NC > TALK_MAX_BLOCK_W) return;                        // no word in reach of any frame | UNDECIDED
     const float* crow = c + (long)(w0 + lo) * D;
     const float* grow = g + (long)(t0 + f0) * D;
-    for (int w = wave; w < NC; w += 4) {
-        const float rn = normalize ? row_rnorm(crow + (long)w * D, D, lane) : 1.f;
-        if (lane == 0) sCn[w] = rn;
-    }
-    for (int f = wave; f < nf; f += 4) {
-        const float rn = normalize ? row_rnorm(grow + (long)f * D, D, lane) : 1.f;
-        if (lane == 0) sGn[f] = rn;
-    }
+    am_row_scales(crow, NC, grow, nf, D, normalize, sCn, sGn, lane, wave);
     if (tid < TALK_MAX_BLOCK_W) {
         // clamped to int32: frames are < 2^20, so neither comparison changes, and a band index taken from a clamped bound is >= 2^31 - 1
         long a = 0x7fffffffL, b = -0x80000000L;
@@ -487,22 +490,9 @@ __global__ __launch_bounds__(256) void attn_talk_kernel(const float* __restrict_
         sLo[tid] = (int)(a < -0x7fffffffL ? -0x7fffffffL : a > 0x7fffffffL ? 0x7fffffffL : a);
         sHi[tid] = (int)(b < -0x80000000L ? -0x80000000L : b > 0x7fffffffL ? 0x7fffffffL : b);
     }
-    const int ntile = (NC + 31) >> 5;
-    f32x16 acc[4], tot[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int x = 0; x < 16; ++x) { acc[i][x] = 0.f; tot[i][x] = 0.f; }
-    const bool active = wave * 32 < nf;
-    for (int k0 = 0; k0 < D; k0 += 32) {
-        __syncthreads();
-        if (tid < 128) am_stage<32>(crow, D, k0, NC, ntile * 32, sCn, sC, TALK_MAX_BLOCK_W, tid, 128);
-        else am_stage<32>(grow, D, k0, nf, (nf + 31) & ~31, sGn, sG, TALK_FB, tid - 128, 128);
-        __syncthreads();
-        if (active) am_mfma<4, 1, 32, TALK_MAX_BLOCK_W, TALK_FB>(sC, sG, 0, ntile, wave * 32, lane, acc);
-        if ((k0 + 32) % AM_KSPLIT == 0 || k0 + 32 == D) am_fold<4>(acc, tot);
-    }
-    if (active)
+    f32x16 tot[4];
+    am_reg_logits<TALK_MAX_BLOCK_W, TALK_FB>(crow, NC, grow, nf, D, sCn, sGn, sC, sG, tid, tot);
+    if (wave * 32 < nf)
         talk_finish(tot, NC, T, f0 + wave * 32, temp, sLo, sHi, band ? band + (long)(w0 + lo) * pitch : nullptr, pitch,
                     keys ? keys + w0 + lo : nullptr, frame_word ? frame_word + t0 : nullptr, frame_prob ? frame_prob + t0 : nullptr, lo, lane);
 }
@@ -525,11 +515,8 @@ __global__ void attn_talk_fill_kernel(float* __restrict__ band, long band_elems,
 // keys -> best_frame / best_score (either may be null); a word without a decided frame reads -1 / NaN
 __global__ void attn_talk_best_kernel(const unsigned long long* __restrict__ keys, int n_words, int32_t* __restrict__ best_frame,
                                       float* __restrict__ best_score) {
-    for (long w = (long)blockIdx.x * blockDim.x + threadIdx.x; w < n_words; w += (long)gridDim.x * blockDim.x) {
-        const unsigned long long key = keys[w];
-        if (best_frame) best_frame[w] = key ? argmax_key_frame(key) : -1;
-        if (best_score) best_score[w] = key ? argmax_key_prob(key) : __builtin_nanf("");
-    }
+    for (long w = (long)blockIdx.x * blockDim.x + threadIdx.x; w < n_words; w += (long)gridDim.x * blockDim.x)
+        argmax_key_decode(keys[w], best_frame, best_score, w);
 }
 
 hipError_t launch_attn_talk(const float* g, const int32_t* goff, int n_tracks, long n_rows, int max_frames, const float* c,

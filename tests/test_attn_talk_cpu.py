@@ -227,7 +227,9 @@ def test_library_exports_the_entry_and_its_kernels_do_not_spill():
     res = kernel_resources()
     mine = {k: v for k, v in res.items() if "attn_talk" in k}
     assert len(mine) == 3 and sum("attn_talk_kernel" in k for k in mine) == 1
-    for name, r in mine.items():
+    clips = {k: v for k, v in res.items() if "attn_matrix_kernel<" in k}        # the clip form shares the talk kernel's parts
+    assert len(clips) == 2
+    for name, r in {**mine, **clips}.items():
         assert r["spill"] == 0 and r["scratch"] == 0, (name, r)
     talk = next(v for k, v in mine.items() if "attn_talk_kernel" in k)
     clip = next(v for k, v in res.items() if "attn_matrix_kernel<false>" in k)

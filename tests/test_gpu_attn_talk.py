@@ -143,10 +143,16 @@ def dense_of(band, start, reach, T):
     return np.stack([band[w, reach - int(start[w]):reach - int(start[w]) + T] for w in range(band.shape[0])])
 
 
+# d = 64 is one k chunk pair below the chain cut of 128 terms, d = 192 ends its second chain off a cut; T = 33 / W = 33 put one frame and one
+# word past a 32-lane half and a 32-word tile; (160, 96) is two frame blocks, the second partial, against three full word tiles.
+# (The first two cases keep the ids they had before d became a parameter.)
 @pytest.mark.parametrize("normalize", [1, 0])
-@pytest.mark.parametrize("T,W,span,gap,reach", [(300, 37, 6, 2, 400), (129, 128, 1, 0, 200)])
-def test_full_reach_gives_the_bits_of_attn_matrix(eng, T, W, span, gap, reach, normalize):
-    g, c, s, e = C.planted_talk(5, T, W, span, gap)
+@pytest.mark.parametrize("T,W,span,gap,reach,d", [pytest.param(300, 37, 6, 2, 400, 512, id="300-37-6-2-400"),
+                                                  pytest.param(129, 128, 1, 0, 200, 512, id="129-128-1-0-200"),
+                                                  (33, 33, 1, 0, 64, 64), (160, 96, 2, 1, 300, 192)])
+def test_full_reach_gives_the_bits_of_attn_matrix(eng, T, W, span, gap, reach, d, normalize):
+    g, c, s, e = C.planted_talk(5, T, W, span, gap, d)
+    assert C.reach_mask(T, s, e, reach).all()                      # what the test is about: every word in reach of every frame
     r = call(eng, [(g, c, s, e)], reach, normalize)["tracks"][0]
     clip = clip_call(eng, [g], [c], normalize)
     A = dense_of(r["band"], s, reach, T)
