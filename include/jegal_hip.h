@@ -571,6 +571,38 @@ int jg_sim_topk(jg_handle* h, const float* queries, const float* gallery, int n_
 int jg_sim_topk_grouped(jg_handle* h, const float* queries, const float* gallery, int n_queries, int n_gallery, int D, int k,
                         const int32_t* g_offsets /* device, [n_groups + 1] */, int n_groups,
                         int gallery_offset, int merge, int32_t* idx, float* score);
+/* Search of a corpus: jg_sim_topk (g_offsets == NULL, n_groups == 0) or jg_sim_topk_grouped (g_offsets != NULL) over a gallery that may be
+ * stored in 16 bits and that every CU walks a part of.
+ * Contract: let G32 be the gallery widened to fp32 (exact for fp16).  The call leaves in idx / score exactly what jg_sim_topk_grouped -- or
+ * jg_sim_topk when g_offsets == NULL -- leaves for G32, bit for bit, for every value of `slices`, with and without merge.  Everything
+ * those two entries document carries over: equal scores order by the smaller row, -0.0 counts as +0.0, a NaN score is never a candidate,
+ * empty slots hold -1 / -inf, a group has at most one entry, gallery_offset and merge mean the same, nothing outside the n_queries * k
+ * entries of idx and score is written, and g_offsets (a device array nobody has checked) is only read at 0 .. n_groups and only ever
+ * compared with row numbers.
+ * gallery: [n_gallery][D] rows of gallery_dtype, JG_F32 or JG_F16 (IEEE binary16; a 16-bit corpus is searched as stored: the scores are
+ * exact fp32 chains over the stored values).
+ * Slices: the gallery is cut into S slices of whole 64-row tiles, slice s = rows [s R, min((s + 1) R, n_gallery)), R % 64 == 0, none
+ * empty.  One workgroup per (64 query rows, slice) walks its tiles as the plain entries walk all of them and writes its sorted list of k
+ * candidate keys to the workspace; a second launch on the same stream seeds each row's list from idx / score (merge), passes the S k keys
+ * of the row through the same insertion -- one entry per group when grouped -- and stores idx / score.  The k best champions of a set do
+ * not depend on how the set is cut (a key is (score, row), totally ordered; the true champion of a group is the best row of the group in
+ * its own slice and can miss that slice's list only when k other groups beat it there, so the group is not among the k best; a weaker part
+ * of the group that survives in another slice is replaced by the champion in the reduction, or is beaten by the k groups that beat the
+ * champion).  S == 1 is one launch straight into idx / score and uses no workspace.
+ * slices: 0 = the library chooses (jg_debug_search_plan: one slice when the query blocks alone fill the device, else enough slices for
+ * about two workgroups per CU, each of at least four tiles); > 0 = that many, at most one per tile.
+ * Limits as for jg_sim_topk / jg_sim_topk_grouped, and 0 <= slices <= 1024 with lists of S n_queries k 8 bytes <= 64 MiB when S > 1.  A
+ * violated limit, a null operand (g_offsets == NULL with n_groups != 0 included) or another gallery_dtype returns JG_ERR_ARG before
+ * anything is enqueued.  n_queries == 0 returns JG_OK and launches nothing; n_gallery == 0, or g_offsets != NULL with n_groups == 0, fills
+ * -1 / -inf without merge and keeps the list with it.  jg_debug_last_kernel names what the call launched ("a+b" for two launches).
+ * Asynchronous. */
+int jg_sim_search(jg_handle* h, const float* queries, int n_queries, const void* gallery, int gallery_dtype /* JG_F32 | JG_F16 */,
+                  int n_gallery, int D, int k, const int32_t* g_offsets /* device [n_groups + 1], or NULL: ungrouped */, int n_groups,
+                  int gallery_offset, int merge, int slices /* 0: the library chooses */, int32_t* idx, float* score);
+/* The cut jg_sim_search makes on a device of num_cu CUs: no handle, no device.  slices_in as jg_sim_search's `slices`.  -> *slices = S,
+ * *rows_per_slice = R, *ws_bytes = S n_queries k 8 (0 when S == 1: one slice writes no lists).  JG_ERR_ARG where jg_sim_search refuses
+ * the counts (negative ones, k outside 1..128, slices_in > 1024, lists beyond 64 MiB). */
+int jg_debug_search_plan(int n_queries, int n_gallery, int k, int num_cu, int slices_in, int* slices, int* rows_per_slice, int64_t* ws_bytes);
 /* The rows jg_sim_topk_grouped returns, back to (group, position inside the group), on the device: grp[e] = the group whose range holds
  * idx[e] - gallery_offset, pos[e] = the row's offset inside it; both -1 for idx[e] < 0 or a row in no group.  An element-wise binary
  * search over g_offsets (device, [n_groups + 1]); a caller of merged calls passes its global offsets with gallery_offset = 0.  n, n_groups,

@@ -134,6 +134,8 @@ _SIGS = {
     "jg_sim_rank": [_P, _P, _P, _I, _I, _I, _I, _P, _P],
     "jg_sim_topk": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P],
     "jg_sim_topk_grouped": [_P, _P, _P, _I, _I, _I, _I, _P, _I, _I, _I, _P, _P],
+    "jg_sim_search": [_P, _P, _I, _P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _P, _P],
+    "jg_debug_search_plan": [_I, _I, _I, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(ctypes.c_int64)],
     "jg_group_of_rows": [_P, _P, _L, _P, _I, _I, _P, _P],
     "jg_spot": [_P, _P, _P, _P, _P, _P, _I, _I, ctypes.c_float, _P, _P],
     "jg_attn_matrix": [_P, _P, _P, _P, _P, _I, _I, _I, ctypes.c_float, _I, _P, _P, _P, _P],
@@ -206,7 +208,18 @@ def gemm_plan(num_cu=256, lanes_active=False, opts=None, conv=None, a_tiled=Fals
     return name.value.decode(), grid.value, lds.value, stagger.value
 
 
-WEIGHT_FORMS = ["single", "split", "bias_corrected", "runtime_corrected"]       # enum WeightForm (jegal_amd/csrc/weight_form.h)
+def search_plan(n_queries, n_gallery, k, num_cu=256, slices=0):
+    """The cut jg_sim_search makes (jg_debug_search_plan) -> (slices, rows per slice, bytes of the slices' lists).  Needs no Engine and no
+    GPU; JegalError where jg_sim_search refuses the counts."""
+    s, r, b = _I(), _I(), ctypes.c_int64()
+    rc = load_library().jg_debug_search_plan(int(n_queries), int(n_gallery), int(k), int(num_cu), int(slices), ctypes.byref(s), ctypes.byref(r),
+                                             ctypes.byref(b))
+    if rc != 0:
+        raise JegalError(f"jg_debug_search_plan: bad arguments ({rc})", rc)
+    return s.value, r.value, b.value
+
+
+WEIGHT_FORMS = ["single", "split", "bias_corrected", "runtime_corrected"]      # enum WeightForm (jegal_amd/csrc/weight_form.h)
 
 
 def weight_form(precision, kind, model, keep32=False):

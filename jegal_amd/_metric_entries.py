@@ -7,6 +7,7 @@ import torch
 
 # The limits the C entries refuse on, named as in csrc/shared.h (tests/test_metric_entries_cpu.py keeps the two equal).
 SIM_TOPK_MAX_K = 128
+SIM_SEARCH_MAX_SLICES, SIM_SEARCH_MAX_WS = 1024, 64 << 20
 SPOT_MAX_W, SPOT_MAX_T = 1024, 8192
 SYNC_MAX_R, SYNC_MAX_T, SYNC_MAX_D = 64, 8192, 1024
 SYNCW_MAX_T, SYNCW_MAX_WINDOWS, SYNCW_MAX_BAND_LOG2 = 1 << 20, 1 << 20, 40
@@ -150,6 +151,34 @@ class MetricEntries:
         if n and m and n_groups:                       # (no gallery row, no group: nothing to merge, or the empty result)
             self._ck(self.lib.jg_sim_topk_grouped(self.h, _ptr(q), _ptr(g), n, m, D, k, _ptr(off), n_groups, gallery_offset,
                                                   int(merge_into is not None), _ptr(idx), _ptr(score)))
+        return idx, score
+
+    def sim_search(self, queries, gallery, k, g_offsets=None, gallery_offset=0, merge_into=None, slices=0):
+        """jg_sim_search: sim_topk (g_offsets None) or sim_topk_grouped over a gallery of float32 or float16 rows (a tensor or an array; a
+        float16 gallery is searched as stored and gives the bits of the call on gallery.float()) that the device walks in `slices` slices at
+        once, one workgroup per 64 query rows and slice (0: the library chooses, search_plan in _lib.py); the bits do not depend on the
+        slices.  The other arguments and the (idx, score) result are those of the two entries; a gallery that is a contiguous tensor on
+        the engine's device is used where it lies."""
+        dtype = getattr(gallery, "dtype", None)
+        if dtype not in (torch.float32, torch.float16, np.dtype(np.float32), np.dtype(np.float16)):
+            raise ValueError("gallery must be a float32 or float16 tensor or array")
+        slices = int(slices)
+        if not 0 <= slices <= SIM_SEARCH_MAX_SLICES:
+            raise ValueError(f"jg_sim_search limit: 0 <= slices <= {SIM_SEARCH_MAX_SLICES} (0: the library chooses)")
+        qs, gs = _shape(queries), _shape(gallery)
+        if slices and len(qs) == 2 and len(gs) == 2 and 1 <= int(k) <= SIM_TOPK_MAX_K and gs[0] <= INT32_MAX:
+            from ._lib import JegalError, search_plan      # (the planner is a host function of the library: no handle, no device)
+            try:
+                search_plan(qs[0], gs[0], int(k), slices=slices)
+            except JegalError:
+                raise ValueError(f"jg_sim_search limit: {slices} slices of {qs[0]} x {int(k)} keys exceed {SIM_SEARCH_MAX_WS} bytes") from None
+        n, m, D, k, gallery_offset, n_groups, idx, score = self._sim_topk_args("sim_search", queries, gallery, k, gallery_offset, merge_into,
+                                                                               g_offsets)
+        q, g = self._f32(queries), torch.as_tensor(gallery, device=self.device).contiguous()
+        off = None if g_offsets is None else self._i32(g_offsets)
+        if n and m and n_groups != 0:                  # (no gallery row, no group: nothing to merge, or the empty result)
+            self._ck(self.lib.jg_sim_search(self.h, _ptr(q), n, _ptr(g), 1 if g.dtype == torch.float16 else 0, m, D, k, _ptr(off), n_groups or 0,
+                                            gallery_offset, int(merge_into is not None), slices, _ptr(idx), _ptr(score)))
         return idx, score
 
     def group_of_rows(self, idx, g_offsets, gallery_offset=0):

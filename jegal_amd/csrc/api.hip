@@ -585,6 +585,33 @@ int jg_sim_topk_grouped(jg_handle* h, const float* queries, const float* gallery
                        score);
 }
 
+int jg_sim_search(jg_handle* h, const float* queries, int n_queries, const void* gallery, int gallery_dtype, int n_gallery, int D, int k,
+                  const int32_t* g_offsets, int n_groups, int gallery_offset, int merge, int slices, int32_t* idx, float* score) {
+    if (!h) return JG_ERR_ARG;
+    const KernelNameScope kn(h->kname);          // the launch depends on the plan: jg_debug_last_kernel shows which one it was
+    ENTER(h);
+    if (!queries || !gallery || !idx || !score) JG_FAIL(h, JG_ERR_ARG, "null buffer");
+    if (!g_offsets && n_groups != 0) JG_FAIL(h, JG_ERR_ARG, "g_offsets == NULL means ungrouped: n_groups must be 0");
+    if (gallery_dtype != JG_F32 && gallery_dtype != JG_F16) JG_FAIL(h, JG_ERR_ARG, "gallery_dtype must be JG_F32 or JG_F16");
+    RET(sim_topk_check(h, "sim_search", queries, static_cast<const float*>(gallery), n_queries, n_gallery, D, k, n_groups, gallery_offset));
+    // no gallery row, or grouped without a group: no tile to walk; one launch seeds and stores the lists as the plain entries do
+    const bool no_rows = n_gallery == 0 || (g_offsets && n_groups == 0);
+    SimSearchPlan plan;
+    if (!sim_search_plan(n_queries, no_rows ? 0 : n_gallery, k, h->opts.num_cu, slices, plan))
+        JG_FAIL(h, JG_ERR_ARG, "slices must be 0 (the library chooses) .. %d, and the slices' lists (slices x n_queries x k x 8 bytes) at most %d bytes",
+                SIM_SEARCH_MAX_SLICES, SIM_SEARCH_MAX_WS);
+    if (n_queries == 0) return JG_OK;
+    unsigned long long* keys = nullptr;          // the slices' lists: scratch of this call, one pass
+    if (plan.slices > 1) {
+        RET(begin_pass(h));
+        RET(wsalloc(h, (size_t)(plan.ws_bytes / 8), &keys));
+    }
+    const int rc = misc_launch(h, launch_sim_search, queries, gallery, gallery_dtype == JG_F16, n_queries, n_gallery, D, k, g_offsets, n_groups,
+                               gallery_offset, merge, idx, score, plan.slices, plan.slice_rows, keys);
+    if (rc != JG_OK) h->kname[0] = 0;            // (a failure may come from behind the launcher's record)
+    return rc;
+}
+
 int jg_group_of_rows(jg_handle* h, const int32_t* idx, int64_t n, const int32_t* g_offsets, int n_groups, int gallery_offset,
                      int32_t* grp, int32_t* pos) {
     ENTER(h);

@@ -13,13 +13,6 @@ using namespace engine;
 // jg_debug_gemm_plan asks the GEMM planner (gemm_plan.h) the same question without a handle, a device or a launch, and
 // jg_debug_weight_form / jg_debug_gemm_runs_lo show which weights a layer's GEMM runs with (weight_form.h) in the same way.
 namespace {
-// the handle's name slot, emptied, as this thread's record_kernel sink until the check point returns
-struct KernelNameScope {
-    char* const prev = kernel_name_sink();
-    explicit KernelNameScope(char* slot) { slot[0] = 0; kernel_name_sink() = slot; }
-    ~KernelNameScope() { kernel_name_sink() = prev; }
-    KernelNameScope(const KernelNameScope&) = delete;
-};
 #define ENTER_CHECK(h) if (!(h)) return JG_ERR_ARG; const KernelNameScope _kn((h)->kname); ENTER(h)
 // option debug_lanes: the handle's options read as inside a two-lane batch (EngineOpts::lanes_active) until the check point returns.
 // Only the check points whose launchers read the flag take it: launch_gemm (plan_gemm) and, through gs_conv1_stage, launch_conv1_direct.
@@ -658,6 +651,15 @@ int jg_debug_core_compact(jg_handle* h, const void* in, int elem_bytes, const in
     if (!in || !table_dev || !out || n_windows < 1 || span_max < 1 || D <= 0 || D % 4 || !al(in, 16) || !al(table_dev, 16) || !al(out, 16))
         JG_FAIL(h, JG_ERR_ARG, "jg_debug_core_compact: bad arguments (D %% 4 == 0, 16-byte aligned rows and table)");
     return check_result(h, launch_core_compact(in, elem_bytes, table_dev, n_windows, span_max, D, out, h->stream), "launch_core_compact");
+}
+
+int jg_debug_search_plan(int n_queries, int n_gallery, int k, int num_cu, int slices_in, int* slices, int* rows_per_slice, int64_t* ws_bytes) {
+    SimSearchPlan p;
+    if (!slices || !rows_per_slice || !ws_bytes || !sim_search_plan(n_queries, n_gallery, k, num_cu, slices_in, p)) return JG_ERR_ARG;
+    *slices = p.slices;
+    *rows_per_slice = p.slice_rows;
+    *ws_bytes = p.ws_bytes;
+    return JG_OK;
 }
 
 int jg_debug_last_kernel(jg_handle* h, char* buf, int len) {

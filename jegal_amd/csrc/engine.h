@@ -261,6 +261,14 @@ struct DeviceGuard {
     }
     ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
 };
+// the handle's name slot, emptied, as this thread's record_kernel sink (shared.h) until the scope ends: the kernel check points
+// (checks.hip: ENTER_CHECK) and jg_sim_search, whose launch depends on a plan
+struct KernelNameScope {
+    char* const prev = kernel_name_sink();
+    explicit KernelNameScope(char* slot) { slot[0] = 0; kernel_name_sink() = slot; }
+    ~KernelNameScope() { kernel_name_sink() = prev; }
+    KernelNameScope(const KernelNameScope&) = delete;
+};
 #define ENTER(h) if (!(h)) return JG_ERR_ARG; engine::DeviceGuard _dg((h)->device); if (!_dg.ok) JG_FAIL(h, JG_ERR_HIP, "hipSetDevice(%d) failed", (h)->device)
 
 // env JG_DEBUG_SYNC, read once per process: synchronise (and report) after every launch

@@ -5,7 +5,16 @@
 // One 64 x 64 tile <e1[i0 ..], e2[j0 ..]> over all of D: the calling wave's 32 x 32 part of it.  sA / sB: [k][query row] / [k][gallery
 // row] staging, 64 x 64 floats each; rows from n_rows / n_cols on are zero.  Begins with a barrier, so the buffers may hold anything that
 // every wave has finished reading; the last chunk's reads are NOT fenced from what the caller writes there next.
-__device__ __forceinline__ f32x16 sim_tile(const float* __restrict__ e1, const float* __restrict__ e2, int i0, int j0, int n_rows, int n_cols,
+// GT: the element type of e2's rows as stored, float or _Float16 (sim_row4: widened on the way into sB, which is exact, so the MFMA chain
+// and with it every bit of the result are those of the widened rows).
+__device__ __forceinline__ f32x4 sim_row4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
+__device__ __forceinline__ f32x4 sim_row4(const _Float16* p) {
+    typedef _Float16 h16x4 __attribute__((ext_vector_type(4)));
+    const h16x4 v = *reinterpret_cast<const h16x4*>(p);
+    return f32x4{(float)v.x, (float)v.y, (float)v.z, (float)v.w};
+}
+template <class GT = float>
+__device__ __forceinline__ f32x16 sim_tile(const float* __restrict__ e1, const GT* __restrict__ e2, int i0, int j0, int n_rows, int n_cols,
                                            int D, float (*sA)[64], float (*sB)[64], int tid) {
     const int lane = tid & 63, wave = tid >> 6;
     const int wr = wave & 1, wc = wave >> 1;
@@ -20,7 +29,7 @@ __device__ __forceinline__ f32x16 sim_tile(const float* __restrict__ e1, const f
             const int k = kq * 16 + q * 4;
             f32x4 va = {0.f, 0.f, 0.f, 0.f}, vb = va;
             if (i0 + r < n_rows) va = *reinterpret_cast<const f32x4*>(e1 + (long)(i0 + r) * D + k0 + k);
-            if (j0 + r < n_cols) vb = *reinterpret_cast<const f32x4*>(e2 + (long)(j0 + r) * D + k0 + k);
+            if (j0 + r < n_cols) vb = sim_row4(e2 + (long)(j0 + r) * D + k0 + k);
             sA[k][r] = va.x; sA[k + 1][r] = va.y; sA[k + 2][r] = va.z; sA[k + 3][r] = va.w;
             sB[k][r] = vb.x; sB[k + 1][r] = vb.y; sB[k + 2][r] = vb.z; sB[k + 3][r] = vb.w;
         }

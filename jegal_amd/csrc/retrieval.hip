@@ -1,4 +1,5 @@
-// Retrieval kernels (gfx950): rank counting, top-k and grouped top-k on exact-fp32 MFMA, and the group of a returned row.
+// Retrieval kernels (gfx950): rank counting, top-k and grouped top-k on exact-fp32 MFMA -- in one walk or in slices over an fp32 or fp16
+// gallery -- and the group of a returned row.
 #include "metric_parts.h"
 
 // ---------------------------------------------------------------------------------------------
@@ -103,6 +104,12 @@ hipError_t launch_sim_rank(const float* e1, const float* e2, int n_local, int n_
 // for the candidates behind it: the queue of a tile holds 64 consecutive rows, mostly of one or two groups.  Entries seeded by merge lie
 // outside this call's rows and never match.  goff is a device array that nobody has checked: it is only ever read at 0 .. n_groups
 // (the search is bounded by n_groups, not by what it reads) and its values are only compared with row numbers, never used as addresses.
+//
+// Slices (jg_sim_search): the same walk over a part of the gallery's tiles per workgroup, the sorted lists written out as keys, and a second
+// kernel that passes every slice's keys through the same insertion (sim_topk_reduce_kernel).  The k best keys of a set do not depend
+// on how the set is cut; grouped, a group's true champion is the best row of the group in its own slice, so it misses that slice's list
+// only if k other groups beat it there (the group is not in the result then), and a weaker part of the group that another slice kept is
+// replaced by the champion in the reduction, or beaten by the k groups that beat the champion.
 using u64 = unsigned long long;
 __device__ __forceinline__ unsigned topk_ord(float s) {          // fp32 -> unsigned, order-preserving; -0.0 counts as +0.0
     const unsigned b = __float_as_uint(s);
@@ -186,24 +193,10 @@ __device__ __forceinline__ void topk_flush(u64 (*sL)[LCAP], const u64 (*sQ)[64],
     }
 }
 
-// jg_sim_topk (GROUPED = false: goff and n_groups are not looked at) and jg_sim_topk_grouped
-template <int LCAP, bool GROUPED>
-__global__ __launch_bounds__(256) void sim_topk_kernel(const float* __restrict__ e1, const float* __restrict__ e2, int n_queries,
-                                                       int n_gallery, int D, int k, const int32_t* __restrict__ goff, int n_groups,
-                                                       int gallery_offset, int merge, int32_t* __restrict__ idx,
-                                                       float* __restrict__ score) {
-    __shared__ __attribute__((aligned(16))) u64 sStage[64 * 64];       // staging (sA, sB) during a tile's k loop, the queues after it
-    __shared__ u64 sL[64][LCAP];
-    __shared__ u64 sThr[64];
-    __shared__ int sCnt[64];
-    float (*sA)[64] = reinterpret_cast<float (*)[64]>(sStage);         // [k][query row]
-    float (*sB)[64] = sA + 64;                                         // [k][gallery row]
-    u64 (*sQ)[64] = reinterpret_cast<u64 (*)[64]>(sStage);             // [query row][slot]
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int i0 = blockIdx.x * 64;
-
-    // the lists start empty, or (merge) from the caller's earlier result: sorted, empty slots (idx < 0) last
+// the wave's 16 rows: the lists start empty, or (merge) from the caller's earlier result: sorted, empty slots (idx < 0) last
+template <int LCAP>
+__device__ __forceinline__ void topk_seed(u64 (*sL)[LCAP], int* sCnt, u64* sThr, int k, int wave, int lane, int i0, int n_queries, int merge,
+                                          const int32_t* idx, const float* score) {
     for (int rr = 0; rr < 16; ++rr) {
         const int row = wave * 16 + rr;
         const long base = (long)(i0 + row) * k;
@@ -222,6 +215,45 @@ __global__ __launch_bounds__(256) void sim_topk_kernel(const float* __restrict__
         if (lane == ((k - 1) & 63)) sThr[row] = kth;
         if (lane == 0) sCnt[row] = 0;
     }
+}
+// ... and the lists to where they go: idx / score, each row as one contiguous run
+template <int LCAP>
+__device__ __forceinline__ void topk_store(const u64 (*sL)[LCAP], int k, int wave, int lane, int i0, int n_queries, int32_t* __restrict__ idx,
+                                           float* __restrict__ score) {
+    for (int rr = 0; rr < 16; ++rr) {
+        const int row = wave * 16 + rr;
+        if (i0 + row >= n_queries) break;
+        const long base = (long)(i0 + row) * k;
+        for (int p = lane; p < k; p += 64) {
+            const u64 key = sL[row][p];
+            idx[base + p] = topk_index(key);
+            score[base + p] = topk_score(key);
+        }
+    }
+}
+
+// jg_sim_topk (GROUPED = false: goff and n_groups are not looked at), jg_sim_topk_grouped and the first kernel of jg_sim_search.
+// GT: the gallery's element type (sim_tile).  Workgroup (x, y) walks the tiles of the gallery rows [y slice_rows, (y + 1) slice_rows) for
+// the query rows 64 x ..; slice_rows is a multiple of 64, and one slice over all rows (gridDim.y == 1) is the walk of the two plain entries.
+// keys == nullptr: the lists go to idx / score.  keys != nullptr (jg_sim_search with more than one slice; merge == 0): the sorted keys
+// themselves go to keys[y][query row][0 .. k - 1], every slot written, 0 = empty, and idx / score are not touched.
+template <class GT, int LCAP, bool GROUPED>
+__global__ __launch_bounds__(256) void sim_topk_kernel(const float* __restrict__ e1, const GT* __restrict__ e2, int n_queries,
+                                                       int n_gallery, int D, int k, const int32_t* __restrict__ goff, int n_groups,
+                                                       int gallery_offset, int merge, int32_t* __restrict__ idx,
+                                                       float* __restrict__ score, int slice_rows, u64* __restrict__ keys) {
+    __shared__ __attribute__((aligned(16))) u64 sStage[64 * 64];       // staging (sA, sB) during a tile's k loop, the queues after it
+    __shared__ u64 sL[64][LCAP];
+    __shared__ u64 sThr[64];
+    __shared__ int sCnt[64];
+    float (*sA)[64] = reinterpret_cast<float (*)[64]>(sStage);         // [k][query row]
+    float (*sB)[64] = sA + 64;                                         // [k][gallery row]
+    u64 (*sQ)[64] = reinterpret_cast<u64 (*)[64]>(sStage);             // [query row][slot]
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int i0 = blockIdx.x * 64;
+
+    topk_seed<LCAP>(sL, sCnt, sThr, k, wave, lane, i0, n_queries, merge, idx, score);
 
     int grp_lo = 0, grp_hi = 0, ntiles = (n_gallery + 63) / 64;
     if constexpr (GROUPED) {
@@ -230,7 +262,9 @@ __global__ __launch_bounds__(256) void sim_topk_kernel(const float* __restrict__
         grp_hi = n_groups > 0 ? goff[n_groups] : 0;
         if (n_groups <= 0) ntiles = 0;
     }
-    for (int tile = 0; tile < ntiles; ++tile) {
+    const int slice_tiles = slice_rows >> 6, tile0 = blockIdx.y * slice_tiles;
+    if (ntiles - tile0 > slice_tiles) ntiles = tile0 + slice_tiles;
+    for (int tile = tile0; tile < ntiles; ++tile) {
         const int j0 = tile * 64;
         const f32x16 acc = sim_tile(e1, e2, i0, j0, n_queries, n_gallery, D, sA, sB, tid);
         __syncthreads();                                         // the staging buffers become the queues
@@ -247,41 +281,120 @@ __global__ __launch_bounds__(256) void sim_topk_kernel(const float* __restrict__
         __syncthreads();
         topk_flush<LCAP, GROUPED>(sL, sQ, sCnt, sThr, k, wave, lane, goff, n_groups, (unsigned)gallery_offset);
     }
-    // a wave stores the lists of the rows it seeded and flushed itself, each row as one contiguous run
-    for (int rr = 0; rr < 16; ++rr) {
-        const int row = wave * 16 + rr;
-        if (i0 + row >= n_queries) break;
-        const long base = (long)(i0 + row) * k;
-        for (int p = lane; p < k; p += 64) {
-            const u64 key = sL[row][p];
-            idx[base + p] = topk_index(key);
-            score[base + p] = topk_score(key);
+    // a wave stores the lists of the rows it seeded and flushed itself
+    if (keys) {
+        for (int rr = 0; rr < 16; ++rr) {
+            const int row = wave * 16 + rr;
+            if (i0 + row >= n_queries) break;
+            const long base = ((long)blockIdx.y * n_queries + i0 + row) * k;
+            for (int p = lane; p < k; p += 64) keys[base + p] = sL[row][p];
         }
+    } else {
+        topk_store<LCAP>(sL, k, wave, lane, i0, n_queries, idx, score);
     }
 }
 
-template <bool GROUPED>
-static hipError_t launch_topk(const float* queries, const float* gallery, int n_queries, int n_gallery, int D, int k, const int32_t* g_offsets,
-                              int n_groups, int gallery_offset, int merge, int32_t* idx, float* score, hipStream_t s) {
+// The second kernel of jg_sim_search: the per-slice lists keys[n_slices][n_queries][k] (sim_topk_kernel) -> idx / score.  Organised as
+// sim_topk_kernel's flush: a wave owns 16 query rows, seeds their lists as that kernel does (merge), streams the rows' n_slices k keys
+// through topk_flush 64 at a time -- the queue's size; flat position e of a row is key e % k of slice e / k -- and stores the lists.  A key
+// of a slice's list is a candidate like a tile's: GROUPED, the champion of a group that several slices hold a part of replaces the parts
+// wherever they meet.  A wave touches the LDS rows of its own 16 query rows only: no barrier.  The next 64 keys are on their way while
+// the current ones are inserted.
+template <int LCAP, bool GROUPED>
+__global__ __launch_bounds__(256) void sim_topk_reduce_kernel(const u64* __restrict__ keys, int n_slices, int n_queries, int k,
+                                                              const int32_t* __restrict__ goff, int n_groups, int gallery_offset, int merge,
+                                                              int32_t* __restrict__ idx, float* __restrict__ score) {
+    __shared__ u64 sQ[64][64];
+    __shared__ u64 sL[64][LCAP];
+    __shared__ u64 sThr[64];
+    __shared__ int sCnt[64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int i0 = blockIdx.x * 64;
+    topk_seed<LCAP>(sL, sCnt, sThr, k, wave, lane, i0, n_queries, merge, idx, score);
+
+    const int per_row = n_slices * k;                                    // (at most 65535 slices of 128 keys: the launcher's limits)
+    const long slice_pitch = (long)n_queries * k;
+    auto fetch = [&](int e0, u64 (&v)[16]) {
+        const int e = e0 + lane;
+        const long at = e < per_row ? (e / k) * slice_pitch + e % k : -1;
+#pragma unroll
+        for (int rr = 0; rr < 16; ++rr) {
+            const int q = i0 + wave * 16 + rr;
+            v[rr] = at >= 0 && q < n_queries ? keys[at + (long)q * k] : 0ull;
+        }
+    };
+    u64 cur[16], nxt[16];
+    fetch(0, nxt);
+    for (int e0 = 0; e0 < per_row; e0 += 64) {
+#pragma unroll
+        for (int rr = 0; rr < 16; ++rr) cur[rr] = nxt[rr];
+        if (e0 + 64 < per_row) fetch(e0 + 64, nxt);
+#pragma unroll
+        for (int rr = 0; rr < 16; ++rr) {
+            const int row = wave * 16 + rr;
+            const bool in = cur[rr] > sThr[row];                         // (0, the empty slot, beats no threshold)
+            const unsigned long long live = __ballot(in);
+            if (in) sQ[row][__popcll(live & ((1ull << lane) - 1ull))] = cur[rr];
+            if (lane == 0) sCnt[row] = __popcll(live);
+        }
+        topk_flush<LCAP, GROUPED>(sL, sQ, sCnt, sThr, k, wave, lane, goff, n_groups, (unsigned)gallery_offset);
+    }
+    topk_store<LCAP>(sL, k, wave, lane, i0, n_queries, idx, score);
+}
+
+template <class GT, bool GROUPED>
+static hipError_t launch_topk(const float* queries, const GT* gallery, int n_queries, int n_gallery, int D, int k, const int32_t* g_offsets,
+                              int n_groups, int gallery_offset, int merge, int32_t* idx, float* score, int slices, int slice_rows,
+                              unsigned long long* keys, hipStream_t s) {
     if (n_queries <= 0) return hipSuccess;
     if (D <= 0 || D % 64 || k < 1 || k > SIM_TOPK_MAX_K || n_gallery < 0 || (GROUPED && (n_groups < 0 || (n_groups > 0 && !g_offsets))) ||
-        gallery_offset < 0 || gallery_offset > INT32_MAX - n_gallery)
+        gallery_offset < 0 || gallery_offset > INT32_MAX - n_gallery || slices < 1 || slices > 65535 || slice_rows < 64 || slice_rows % 64 ||
+        (slices > 1 && (!keys || (long)(slices - 1) * slice_rows >= n_gallery)))
         return hipErrorInvalidValue;
-    const auto kernel = k <= 64 ? sim_topk_kernel<64, GROUPED> : sim_topk_kernel<128, GROUPED>;
-    hipLaunchKernelGGL(kernel, dim3((n_queries + 63) / 64), dim3(256), 0, s, queries, gallery, n_queries, n_gallery, D, k, g_offsets, n_groups,
-                       gallery_offset, merge, idx, score);
+    const char* const gt = sizeof(GT) == 2 ? "_Float16" : "float";
+    const int L = k <= 64 ? 64 : 128, qblocks = (n_queries + 63) / 64;
+    const auto kernel = k <= 64 ? sim_topk_kernel<GT, 64, GROUPED> : sim_topk_kernel<GT, 128, GROUPED>;
+    if (slices == 1) {                               // one slice: its list is the result
+        record_kernel("sim_topk_kernel<%s,%d,%d>", gt, L, (int)GROUPED);
+        hipLaunchKernelGGL(kernel, dim3(qblocks), dim3(256), 0, s, queries, gallery, n_queries, n_gallery, D, k, g_offsets, n_groups,
+                           gallery_offset, merge, idx, score, slice_rows, (u64*)nullptr);
+        return hipGetLastError();
+    }
+    // two launches on one stream: the kernel boundary is what makes the slices' lists visible to the reduction
+    record_kernel("sim_topk_kernel<%s,%d,%d>+sim_topk_reduce_kernel<%d,%d>", gt, L, (int)GROUPED, L, (int)GROUPED);
+    hipLaunchKernelGGL(kernel, dim3(qblocks, slices), dim3(256), 0, s, queries, gallery, n_queries, n_gallery, D, k, g_offsets, n_groups,
+                       gallery_offset, 0, idx, score, slice_rows, keys);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const auto reduce = k <= 64 ? sim_topk_reduce_kernel<64, GROUPED> : sim_topk_reduce_kernel<128, GROUPED>;
+    hipLaunchKernelGGL(reduce, dim3(qblocks), dim3(256), 0, s, keys, slices, n_queries, k, g_offsets, n_groups, gallery_offset, merge, idx, score);
     return hipGetLastError();
 }
+constexpr int ONE_SLICE = INT32_MAX & ~63;           // slice_rows of a walk over the whole gallery
 
 hipError_t launch_sim_topk(const float* queries, const float* gallery, int n_queries, int n_gallery, int D, int k, int gallery_offset,
                            int merge, int32_t* idx, float* score, hipStream_t s) {
-    return launch_topk<false>(queries, gallery, n_queries, n_gallery, D, k, nullptr, 0, gallery_offset, merge, idx, score, s);
+    return launch_topk<float, false>(queries, gallery, n_queries, n_gallery, D, k, nullptr, 0, gallery_offset, merge, idx, score, 1, ONE_SLICE,
+                                     nullptr, s);
 }
 
 hipError_t launch_sim_topk_grouped(const float* queries, const float* gallery, int n_queries, int n_gallery, int D, int k,
                                    const int32_t* g_offsets, int n_groups, int gallery_offset, int merge, int32_t* idx, float* score,
                                    hipStream_t s) {
-    return launch_topk<true>(queries, gallery, n_queries, n_gallery, D, k, g_offsets, n_groups, gallery_offset, merge, idx, score, s);
+    return launch_topk<float, true>(queries, gallery, n_queries, n_gallery, D, k, g_offsets, n_groups, gallery_offset, merge, idx, score, 1,
+                                    ONE_SLICE, nullptr, s);
+}
+
+hipError_t launch_sim_search(const float* queries, const void* gallery, bool gallery_f16, int n_queries, int n_gallery, int D, int k,
+                             const int32_t* g_offsets, int n_groups, int gallery_offset, int merge, int32_t* idx, float* score, int slices,
+                             int slice_rows, unsigned long long* keys, hipStream_t s) {
+    const float* const g32 = static_cast<const float*>(gallery);
+    const _Float16* const g16 = static_cast<const _Float16*>(gallery);
+#define SEARCH(GT, G, GROUPED) launch_topk<GT, GROUPED>(queries, G, n_queries, n_gallery, D, k, g_offsets, n_groups, gallery_offset, merge, idx, \
+                                                        score, slices, slice_rows, keys, s)
+    if (g_offsets) return gallery_f16 ? SEARCH(_Float16, g16, true) : SEARCH(float, g32, true);
+    return gallery_f16 ? SEARCH(_Float16, g16, false) : SEARCH(float, g32, false);
+#undef SEARCH
 }
 
 // rows (as jg_sim_topk_grouped returns them) -> group and position inside it: an element-wise binary search; -1 / -1 for idx < 0 or a row

@@ -132,7 +132,7 @@ constexpr int LANE_WALK_MAX = 4;
 // ---- which kernel a launcher launched (jg_debug_last_kernel) ---------------------------------------------------
 // Every launcher a kernel check point reaches calls record_kernel where it chooses its instance, directly in front of the launch and
 // behind its last refusal: the name with its template arguments, or "a_kernel+b_kernel" for a launcher of two kernels.  The name goes to
-// the calling thread's sink: KNAME_LEN bytes that a check point opens for the length of its call (checks.hip: KernelNameScope) and
+// the calling thread's sink: KNAME_LEN bytes that a check point opens for the length of its call (engine.h: KernelNameScope; jg_sim_search opens one too) and
 // nullptr, nothing recorded, everywhere else.  One sink per thread, defined once (gemm_plan.hip), for both kernel builds.
 constexpr int KNAME_LEN = 96;
 char*& kernel_name_sink();
@@ -194,6 +194,46 @@ hipError_t launch_sim_topk(const float* queries, const float* gallery, int n_que
 hipError_t launch_sim_topk_grouped(const float* queries, const float* gallery, int n_queries, int n_gallery, int D, int k,
                                    const int32_t* g_offsets, int n_groups, int gallery_offset, int merge, int32_t* idx, float* score,
                                    hipStream_t s);
+// jg_sim_search: either of the two above (g_offsets == nullptr: ungrouped) over a gallery of fp32 or fp16 rows cut into `slices` slices of
+// slice_rows rows (whole 64-row tiles, none empty: a SimSearchPlan), one workgroup per query block and slice, and a second kernel that
+// reduces the slices' lists (keys: slices x n_queries x k words of scratch, every one written) into idx / score.  slices == 1 is one
+// launch straight into idx / score and needs no keys.  The bits do not depend on the cut.
+constexpr int SIM_SEARCH_MAX_SLICES = 1024;  // slices of one call, asked for or chosen
+constexpr int SIM_SEARCH_MAX_WS = 64 << 20;  // bytes of the slices' lists
+constexpr int SIM_SEARCH_WG_PER_CU = 2;      // workgroups per CU the chosen cut aims at: what fits a CU's LDS at k <= 64
+constexpr int SIM_SEARCH_MIN_TILES = 4;      // ... and the fewest tiles a chosen slice walks
+struct SimSearchPlan {
+    int slices, slice_rows;
+    long long ws_bytes;                      // slices n_queries k 8: the lists; 0 with one slice, which writes none
+};
+// The cut of a call, a pure function (jg_debug_search_plan shows it).  slices_in == 0: as many slices as bring the launch to
+// SIM_SEARCH_WG_PER_CU workgroups per CU -- one when the query blocks alone fill the device -- of at least SIM_SEARCH_MIN_TILES tiles, at
+// most SIM_SEARCH_MAX_SLICES, with lists inside SIM_SEARCH_MAX_WS.  slices_in > 0: that many, at most one per tile.  The tiles are then
+// dealt out evenly, which may leave fewer slices than asked for, none of them empty.  false: a count the entry refuses.
+inline bool sim_search_plan(int n_queries, int n_gallery, int k, int num_cu, int slices_in, SimSearchPlan& p) {
+    if (n_queries < 0 || n_gallery < 0 || k < 1 || k > SIM_TOPK_MAX_K || num_cu < 1 || slices_in < 0 || slices_in > SIM_SEARCH_MAX_SLICES)
+        return false;
+    const long long tiles = ((long long)n_gallery + 63) / 64, qblocks = ((long long)n_queries + 63) / 64, list = (long long)n_queries * k * 8;
+    long long s = slices_in;
+    if (!slices_in) {
+        s = qblocks >= num_cu || !qblocks ? 1 : ((long long)SIM_SEARCH_WG_PER_CU * num_cu + qblocks - 1) / qblocks;
+        if (s > tiles / SIM_SEARCH_MIN_TILES) s = tiles / SIM_SEARCH_MIN_TILES;
+        if (s > SIM_SEARCH_MAX_SLICES) s = SIM_SEARCH_MAX_SLICES;
+        if (list && s > SIM_SEARCH_MAX_WS / list) s = SIM_SEARCH_MAX_WS / list;
+    }
+    if (s > tiles) s = tiles;
+    if (s < 1) s = 1;
+    const long long per = tiles ? (tiles + s - 1) / s : 1;       // tiles per slice
+    s = tiles ? (tiles + per - 1) / per : 1;
+    if (s > 1 && s * list > SIM_SEARCH_MAX_WS) return false;
+    p.slices = (int)s;
+    p.slice_rows = (int)(per * 64 < INT32_MAX ? per * 64 : INT32_MAX & ~63);
+    p.ws_bytes = s > 1 ? s * list : 0;
+    return true;
+}
+hipError_t launch_sim_search(const float* queries, const void* gallery, bool gallery_f16, int n_queries, int n_gallery, int D, int k,
+                             const int32_t* g_offsets, int n_groups, int gallery_offset, int merge, int32_t* idx, float* score, int slices,
+                             int slice_rows, unsigned long long* keys, hipStream_t s);
 // grp / pos [n]: the group that holds row idx[e] - gallery_offset and the row's place inside it; -1 / -1 for idx[e] < 0 or a row in no group
 hipError_t launch_group_of_rows(const int32_t* idx, long n, const int32_t* g_offsets, int n_groups, int gallery_offset, int32_t* grp,
                                 int32_t* pos, hipStream_t s);

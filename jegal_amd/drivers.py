@@ -540,6 +540,37 @@ def cmd_retrieve(argv, engine=None):
     return 0
 
 
+def _corpus_clips(path):
+    """the corpus under `path`: (names (N,): the .pkl base names in sorted order = the clip numbering, [gesture_emb (T_i, D) float32])"""
+    files, feats = _load_pkls(path)
+    feats = [(fn, ft) for fn, ft in zip(files, feats) if ft.get("gesture_emb") is not None]
+    if not feats:
+        raise SystemExit("no .pkl with gesture_emb under {}".format(path))
+    return (np.asarray([os.path.basename(fn)[:-len(".pkl")] for fn, _ in feats]),
+            [np.asarray(ft["gesture_emb"], np.float32) for _, ft in feats])
+
+
+def cmd_index(argv, engine=None):
+    """Prepare a corpus for search --index: every gesture_emb of the .pkl files under --path (names and clip numbering as search --path
+    has them), the rows L2-normalised (--normalize 1) and rounded to --dtype, written as one .npz (metrics.Corpus).  float16 halves the
+    file, the upload and the device memory; the search then scores the rows as stored.  engine: the Engine to run on."""
+    from . import metrics as M
+    p = argparse.ArgumentParser(prog="index")
+    p.add_argument("--path", required=True, help="a directory of JEGAL feature .pkl files: the corpus")
+    p.add_argument("--out", required=True, help="the corpus file to write (.npz)")
+    p.add_argument("--dtype", default="float16", choices=["float16", "float32"])
+    p.add_argument("--normalize", type=int, default=1, choices=[0, 1], help="1: unit rows (cosine similarity); 0: the rows as stored")
+    args = p.parse_args(argv)
+    names, clips = _corpus_clips(args.path)
+    eng = engine if engine is not None else (_models(args)[0] if args.normalize else None)
+    corpus = M.Corpus.build(clips, names=names, dtype=args.dtype, normalize=bool(args.normalize), engine=eng)
+    out = args.out if args.out.endswith(".npz") else args.out + ".npz"
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    corpus.save(out)
+    print("index: {} clips, {} rows x {} {} -> {}".format(len(names), corpus.rows.shape[0], corpus.rows.shape[1], args.dtype, out))
+    return 0
+
+
 def cmd_search(argv, engine=None):
     """For this word, or this phrase, which clips of a corpus gesture it, and at which frame: the query rows are the --query .pkl's
     content_emb rows (--level word: one query per word) or their mean (--level phrase: one query), the gallery is every gesture_emb row of
@@ -547,10 +578,12 @@ def cmd_search(argv, engine=None):
     score on their own, so a long clip can come back with several moments.  Writes ``<res_dir>/search_<query name>.npz`` = {words (Q,): the
     query's words (phrase: the words joined), names (N,): the .pkl base names = the clip numbering, clip (Q,K) int32, frame (Q,K) int32:
     the frame inside the clip, score (Q,K) float32; -1 / -1 / -inf where fewer than K groups exist} and prints one line per query row.
-    engine: the Engine to run on (default: this process's)."""
+    --index FILE instead of --path: the corpus is one written by the index command (metrics.Corpus, jg_sim_search): prepared once, maybe
+    in 16 bits, the same output.  engine: the Engine to run on (default: this process's)."""
     from . import metrics as M
     p = argparse.ArgumentParser(prog="search", description="Single process: sharding over ranks is not built for this command.")
-    p.add_argument("--path", required=True, help="a directory of JEGAL feature .pkl files: the corpus")
+    p.add_argument("--path", default=None, help="a directory of JEGAL feature .pkl files: the corpus (or --index)")
+    p.add_argument("--index", default=None, help="a corpus written by the index command, instead of --path: prepared once, maybe in 16 bits")
     p.add_argument("--query", required=True, help="a JEGAL feature .pkl whose content_emb rows are the query")
     p.add_argument("--level", default="word", choices=["word", "phrase"])
     p.add_argument("--topk", type=int, default=10, help="clips (or segments) kept per query row (1..128)")
@@ -563,6 +596,8 @@ def cmd_search(argv, engine=None):
         raise SystemExit("--topk must be 1..128")
     if args.segment < 0:
         raise SystemExit("--segment must be >= 0")
+    if (args.path is None) == (args.index is None):
+        raise SystemExit("exactly one of --path and --index")
     with open(args.query, "rb") as f:
         qf = pickle.load(f)
     if qf.get("content_emb") is None:
@@ -576,14 +611,17 @@ def cmd_search(argv, engine=None):
         raise ValueError("{}: {} word boundaries for {} content rows".format(args.query, len(words), len(queries)))
     if args.level == "phrase":
         queries, words = queries.mean(axis=0, keepdims=True), [" ".join(words)]
-    files, feats = _load_pkls(args.path)
-    feats = [(fn, ft) for fn, ft in zip(files, feats) if ft.get("gesture_emb") is not None]
-    if not feats:
-        raise SystemExit("no .pkl with gesture_emb under {}".format(args.path))
-    names = np.asarray([os.path.basename(fn)[:-len(".pkl")] for fn, _ in feats])
-    eng = engine if engine is not None else _models(args)[0]
-    clip, frame, score = M.search(queries, [np.asarray(ft["gesture_emb"], np.float32) for _, ft in feats], k=args.topk, segment=args.segment,
-                                  normalize=bool(args.normalize), engine=eng, max_rows=args.max_rows)
+    if args.index is not None:                   # (its rows were normalised, or not, when it was built: --normalize is about the query)
+        corpus = M.Corpus.load(args.index)
+        names = corpus.names
+        eng = engine if engine is not None else _models(args)[0]
+        clip, frame, score = corpus.search(queries, k=args.topk, segment=args.segment, normalize=bool(args.normalize), engine=eng,
+                                           max_rows=args.max_rows)
+    else:
+        names, clips = _corpus_clips(args.path)
+        eng = engine if engine is not None else _models(args)[0]
+        clip, frame, score = M.search(queries, clips, k=args.topk, segment=args.segment, normalize=bool(args.normalize), engine=eng,
+                                      max_rows=args.max_rows)
     os.makedirs(args.res_dir, exist_ok=True)
     qname = os.path.basename(args.query).rsplit(".", 1)[0]
     out = os.path.join(args.res_dir, "search_{}.npz".format(qname))
@@ -948,6 +986,7 @@ COMMANDS = {
     "attn_matrix": cmd_attn_matrix,
     "retrieve": cmd_retrieve,
     "search": cmd_search,
+    "index": cmd_index,
     "asd": cmd_asd,
     "extract_gestsync_feats": cmd_extract_gestsync_feats,
     "extract_jegal_embs": cmd_extract_jegal_embs,

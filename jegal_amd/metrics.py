@@ -161,6 +161,119 @@ def search(queries, clips, k=10, segment=0, normalize=True, engine=None, max_row
     return clip, frame, score
 
 
+class Corpus:
+    """The frame rows of many clips, prepared once and searched many times: what search() does with a list of clips on every call --
+    concatenate, normalise, upload -- happens in build(), and the rows may be kept in 16 bits, as the reference's CUDA path writes them
+    (half the bytes on disk, in the upload and on the device; jg_sim_search reads them as they are).
+    rows (sum T, D) float16 or float32, lengths (N,) int64 frames per clip, names (N,) str, normalized: whether build() L2-normalised the
+    rows.  A 16-bit corpus is searched AS STORED: a score is the exact fp32 chain over the stored rows, the one search() computes for
+    rows.astype(float32).  Against the float32 corpus of the same clips a score differs by at most sum_d |q_d| (2^-11 |g_d| + 2^-25) --
+    fp16 rounds to nearest even with a relative error of 2^-11 on normal values and an absolute one of 2^-25 below 2^-14 -- plus the two
+    fp32 chain bounds D 2^-24 sum_d |q_d g_d| (derived from the formats, not measured)."""
+    VERSION = 1
+    CHUNK = 1 << 18              # rows that build() normalises at a time
+
+    def __init__(self, rows, lengths, names, normalized):
+        self.rows = np.ascontiguousarray(rows)
+        self.lengths = np.asarray(lengths, np.int64).reshape(-1)
+        self.names = np.asarray(names, dtype=str).reshape(-1)
+        self.normalized = bool(normalized)
+        if self.rows.dtype not in (np.float16, np.float32) or self.rows.ndim != 2:
+            raise ValueError("rows must be a (sum T, D) float16 or float32 array")
+        if (self.lengths < 0).any() or int(self.lengths.sum()) != self.rows.shape[0] or len(self.names) != len(self.lengths):
+            raise ValueError("lengths must be >= 0 and add up to the rows, with one name per clip")
+        if self.rows.shape[0] > 2 ** 31 - 1:
+            raise ValueError("more than INT32_MAX gallery rows")
+        self._dev = None         # (engine, the rows on its device): kept between searches
+
+    @classmethod
+    def build(cls, clips, names=None, dtype="float16", normalize=True, engine=None):
+        """clips: a list of (T_i, D) frame-level arrays; names: one per clip (default: "0", "1", ..).  normalize: the rows are L2-normalised in
+        fp32 (engine.l2norm, as search() does); then they are rounded to dtype ("float16" or "float32") to nearest even, the bits of
+        numpy.astype."""
+        dtype = np.dtype(dtype)
+        if dtype not in (np.float16, np.float32):
+            raise ValueError("dtype must be float16 or float32")
+        clips = [_host(c).astype(np.float32, copy=False) if isinstance(c, torch.Tensor) else np.asarray(c, np.float32) for c in clips]
+        D = clips[0].shape[1] if clips and clips[0].ndim == 2 else 0
+        if any(c.ndim != 2 or c.shape[1] != D for c in clips):
+            raise ValueError("every clip must be (T_i, D) with one D")
+        names = [str(i) for i in range(len(clips))] if names is None else list(names)
+        if len(names) != len(clips):
+            raise ValueError("names needs one entry per clip")
+        rows = np.concatenate(clips, 0) if clips else np.zeros((0, 0), np.float32)
+        if normalize and rows.shape[0]:
+            eng = engine or Engine.get()
+            rows = np.concatenate([_host(eng.l2norm(torch.from_numpy(rows[a:a + cls.CHUNK]))).astype(np.float32, copy=False)
+                                   for a in range(0, rows.shape[0], cls.CHUNK)], 0)
+        return cls(rows.astype(dtype), [c.shape[0] for c in clips], names, normalize)
+
+    def save(self, path):
+        """one uncompressed .npz: rows, lengths, names, normalized, version"""
+        np.savez(path, rows=self.rows, lengths=self.lengths, names=self.names, normalized=np.asarray(self.normalized), version=np.asarray(self.VERSION))
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path, allow_pickle=False) as z:
+            if int(z["version"]) != cls.VERSION:
+                raise ValueError("{}: corpus version {}, this package reads {}".format(path, int(z["version"]), cls.VERSION))
+            return cls(z["rows"], z["lengths"], z["names"], bool(z["normalized"]))
+
+    def _device_rows(self, eng, r0, r1, keep):
+        """rows r0 .. r1 - 1 on the engine's device, in their stored type; keep: the whole corpus, uploaded once per engine"""
+        if not keep:
+            return torch.from_numpy(self.rows[r0:r1]).to(eng.device)
+        if self._dev is None or self._dev[0] is not eng:
+            self._dev = (eng, torch.from_numpy(self.rows).to(eng.device))
+        return self._dev[1]
+
+    def search(self, queries, k=10, segment=0, normalize=True, engine=None, max_rows=None):
+        """search() over the prepared rows: the same (clip, frame, score) triple, the same groups (segment) and the same piece-wise merging at
+        group boundaries under max_rows, through jg_sim_search, which spreads the rows over every CU.  normalize: the QUERY rows are
+        L2-normalised first (the corpus rows are what build() made them).  Without max_rows the rows stay on the engine's device between
+        calls: repeated searches upload the queries only."""
+        k, segment = int(k), int(segment)
+        if not 1 <= k <= 128:
+            raise ValueError("k must be 1..128")
+        if segment < 0:
+            raise ValueError("segment must be >= 0 (0: one group per clip)")
+        q = _tensor(queries)
+        if q.ndim != 2 or (self.rows.shape[0] and q.shape[1] != self.rows.shape[1]):
+            raise ValueError("queries must be (Q, {})".format(self.rows.shape[1]))
+        Q = int(q.shape[0])
+        goff, gclip, gstart = search_groups(self.lengths, segment)
+        n_groups = len(gclip)
+        sizes = np.diff(goff)
+        if max_rows is not None and (int(max_rows) < 1 or (n_groups and sizes.max() > int(max_rows))):
+            raise ValueError("max_rows must hold the largest group ({} rows): groups are never split; use segment".format(int(sizes.max()) if n_groups else 0))
+        empty = (np.full((Q, k), -1, np.int32), np.full((Q, k), -1, np.int32), np.full((Q, k), -np.inf, np.float32))
+        if Q == 0 or goff[-1] == 0:
+            return empty
+        eng = engine or Engine.get()
+        if normalize:
+            q = eng.l2norm(q)
+        res, g0 = None, 0
+        while g0 < n_groups:                             # pieces = runs of whole groups of at most max_rows rows, as in search()
+            g1 = n_groups
+            if max_rows is not None:
+                g1 = g0 + 1
+                while g1 < n_groups and goff[g1 + 1] - goff[g0] <= int(max_rows):
+                    g1 += 1
+            r0, r1 = int(goff[g0]), int(goff[g1])
+            if r1 > r0:
+                res = eng.sim_search(q, self._device_rows(eng, r0, r1, max_rows is None), k, g_offsets=goff[g0:g1 + 1] - r0, gallery_offset=r0,
+                                     merge_into=res)
+            g0 = g1
+        if res is None:
+            return empty
+        grp, pos = eng.group_of_rows(res[0], goff, 0)
+        grp, pos, score = _host(grp).astype(np.int64), _host(pos).astype(np.int32), _host(res[1]).astype(np.float32)
+        found = grp >= 0
+        clip = np.where(found, gclip[np.maximum(grp, 0)], -1).astype(np.int32)
+        frame = np.where(found, gstart[np.maximum(grp, 0)] + pos, -1).astype(np.int32)
+        return clip, frame, score
+
+
 def partner_ranks(emb1, emb2, engine=None):
     """jg_sim_rank's rank of every query's own partner (row i of emb1 belongs to row i of emb2), the number retrieval_metrics turns into
     R@K: host int32 (N,), over all ranks' rows in rank order when sharded."""
