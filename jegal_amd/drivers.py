@@ -24,7 +24,6 @@ Run under ``torchrun`` to shard over GPUs (contiguous blocks, extract_gestsync_f
 import argparse
 import ast
 import glob
-import math
 import os
 import pickle
 import sys
@@ -33,6 +32,8 @@ import numpy as np
 import torch
 
 from . import dist as jdist
+from . import extract
+from . import metrics as M
 from . import synth
 
 
@@ -102,6 +103,82 @@ def _models(args, need_gestsync=False, need_jegal=False):
     return eng, gs, jg
 
 
+def _engine(engine, args):
+    """the Engine a command runs on: the caller's, or this process's"""
+    return engine if engine is not None else _models(args)[0]
+
+
+# --------------------------------------------------------------------------- feature files
+def _load_pkl(fn):
+    with open(fn, "rb") as f:
+        return pickle.load(f)
+
+
+def _base_name(fn):
+    """a file's name without its directory and its extension"""
+    return os.path.basename(fn).rsplit(".", 1)[0]
+
+
+def _feature_words(ft):
+    """the words of a feature dict, from its info (the csv row, a pandas Series, or inference_embs' {fname, word_boundaries, text}); None where
+    it holds no boundaries"""
+    info = ft.get("info")
+    return M.word_bounds(info["word_boundaries"])[0] if info is not None and "word_boundaries" in info else None
+
+
+def _check_topk(topk):
+    if not 1 <= topk <= 128:
+        raise SystemExit("--topk must be 1..128")
+
+
+def _gesture_content(out, has_visual, has_content):
+    """JEGAL.forward_inference's return value -> (gesture | None, content | None): both when it was given frames and text or audio"""
+    if has_visual and has_content:
+        return out
+    return (out, None) if has_visual else (None, out)
+
+
+def _wav_mel(wav_fn, eng):
+    """a 16 kHz mono .wav -> its (1, Tm, 80) log-mel on the engine's device (jg_logmel)"""
+    from . import audio as jaudio
+    wav = torch.from_numpy(np.asarray(jaudio.load_wav(wav_fn)).astype(np.float32))
+    return jaudio.wav2filterbanks(wav[None].to(eng.device), engine=eng)[0]
+
+
+def _run_groups(groups, run_group, save, label):
+    """Run every group of items in one call of run_group(group) -> one result per item; a group that raises is run again item by item, so
+    that one bad file does not take its neighbours down (a group of one is not retried).  save(result, item) stores one result, under its
+    own try (per-file try/except as in the reference, extract_gestsync_feats.py:347-351).  Every failure prints ``Error: <e> | <label>:
+    <item[1]>``.  -> (saved, err)"""
+    saved = err = 0
+    for group in groups:
+        try:
+            results = run_group(group)
+        except Exception as e:
+            if len(group) == 1:
+                err += 1
+                print("Error: ", e, " | {}: ".format(label), group[0][1])
+                continue
+            results = []
+            for item in group:
+                try:
+                    results.append(run_group([item])[0])
+                except Exception as e1:
+                    results.append(None)
+                    err += 1
+                    print("Error: ", e1, " | {}: ".format(label), item[1])
+        for result, item in zip(results, group):
+            if result is None:
+                continue
+            try:
+                save(result, item)
+                saved += 1
+            except Exception as e:
+                err += 1
+                print("Error: ", e, " | {}: ".format(label), item[1])
+    return saved, err
+
+
 # --------------------------------------------------------------------------- extract_gestsync_feats
 def cmd_extract_gestsync_feats(argv):
     p = argparse.ArgumentParser(prog="extract_gestsync_feats")
@@ -161,43 +238,20 @@ def cmd_extract_gestsync_feats(argv):
         feats = gs.extract_clip_feats(torch.from_numpy(batch).to(eng.device), lengths=[t for t, _, _ in group]).cpu().numpy()
         return [feats[i, :t] for i, (t, _, _) in enumerate(group)]
 
-    def save_one(feat, out):
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        np.save(out, feat)
+    def save_one(feat, item):
+        os.makedirs(os.path.dirname(item[2]), exist_ok=True)
+        np.save(item[2], feat)
 
     nb, fmax = max(1, args.clips_per_batch), max(1, args.frames_per_batch)
-    s0 = 0
+    groups, s0 = [], 0
     while s0 < len(sized):
         s1 = s0 + 1                                   # sorted by length: the last clip of a group is its longest
         while s1 < len(sized) and s1 - s0 < nb and (s1 - s0 + 1) * sized[s1][0] <= fmax:
             s1 += 1
-        group = sized[s0:s1]
+        groups.append(sized[s0:s1])
         s0 = s1
-        try:
-            feats = run_group(group)
-        except Exception as e:                       # one bad file must not take its neighbours down: retry the group clip by clip
-            if len(group) == 1:
-                err += 1
-                print("Error: ", e, " | Video file: ", group[0][1])
-                continue
-            feats = []
-            for item in group:
-                try:
-                    feats.append(run_group([item])[0])
-                except Exception as e1:              # per-file try/except as in the reference (:347-351)
-                    feats.append(None)
-                    err += 1
-                    print("Error: ", e1, " | Video file: ", item[1])
-        for feat, (t, f, out) in zip(feats, group):
-            if feat is None:
-                continue
-            try:
-                save_one(feat, out)
-                saved += 1
-            except Exception as e:
-                err += 1
-                print("Error: ", e, " | Video file: ", f)
-    print("No of files saved = {} | Err = {}".format(saved, err))
+    done, failed = _run_groups(groups, run_group, save_one, "Video file")
+    print("No of files saved = {} | Err = {}".format(saved + done, err + failed))
     return 0
 
 
@@ -275,9 +329,7 @@ def cmd_extract_jegal_embs(argv):
                     item["mel"] = np.load(fn).astype(np.float32)
                 elif os.path.exists(wav_fn):
                     try:
-                        from . import audio as jaudio
-                        wav = torch.from_numpy(np.asarray(jaudio.load_wav(wav_fn)).astype(np.float32))
-                        item["mel"] = jaudio.wav2filterbanks(wav[None].to(eng.device), engine=eng)[0][0].cpu().numpy()
+                        item["mel"] = _wav_mel(wav_fn, eng)[0].cpu().numpy()
                     except Exception:                      # dataset.py:296-298: a wav that cannot be read drops the sample
                         print("Error loading audio, check the file: ", wav_fn)
                         continue
@@ -301,7 +353,7 @@ def cmd_extract_jegal_embs(argv):
             continue
         n = len(batch)
         vis = mask = audio = text = None
-        wbs = [ast.literal_eval(it["row"].word_boundaries) for it in batch] if mod != "v" else None
+        wbs = [M.boundary_list(it["row"].word_boundaries) for it in batch] if mod != "v" else None
         if "v" in mod:                                # pad_sequence + mask (dataset.py:336-340)
             T = max(it["feats"].shape[0] for it in batch)
             vis = torch.zeros((n, T, 1024))
@@ -342,21 +394,14 @@ def cmd_extract_jegal_embs(argv):
         # count and the audio conv stack sees every clip's own zero padding (jegal_amd/jegal.py, jg_jegal_audio_ragged)
         out = jg.forward_inference(visual_feats=vis, visual_mask=mask, text=text, audio=audio, audio_mask=am, word_boundaries=wbs,
                                    audio_lens=alens, per_clip=True)
-        gesture = content = None
-        if vis is not None and (text is not None or audio is not None):
-            gesture, content = out
-        elif vis is not None:
-            gesture = out
-        else:
-            content = out
+        gesture, content = _gesture_content(out, vis is not None, text is not None or audio is not None)
         for i, it in enumerate(batch):
             g = c = None
             if gesture is not None:                   # strip padded query rows
                 g = eng.l2norm(gesture[i, :it["feats"].shape[0]]).cpu().numpy()
             if content is not None:                   # strip padded word rows
                 c = eng.l2norm(content[i, :len(wbs[i])]).cpu().numpy()
-            parts = it["file"].split("/")
-            with open(os.path.join(res_dir, parts[0] + "__" + parts[1] + ".pkl"), "wb") as f:
+            with open(extract.pkl_name(res_dir, it["file"]), "wb") as f:
                 pickle.dump({"gesture_emb": g, "content_emb": c, "info": it["row"]}, f)
             saved += 1
     print("Saved {} files".format(saved))
@@ -368,15 +413,10 @@ def cmd_extract_jegal_embs(argv):
 def _load_pkls(path):
     files = sorted(glob.glob("{}/*.pkl".format(path)))
     print("No of files = ", len(files))
-    feats = []
-    for fn in files:
-        with open(fn, "rb") as f:
-            feats.append(pickle.load(f))
-    return files, feats
+    return files, [_load_pkl(fn) for fn in files]
 
 
 def cmd_evaluate_retrieval(argv):
-    from . import metrics as M
     p = argparse.ArgumentParser(prog="evaluate_retrieval")
     p.add_argument("--path", required=True)
     args = p.parse_args(argv)
@@ -397,7 +437,6 @@ def cmd_evaluate_retrieval(argv):
 
 
 def cmd_evaluate_spotting(argv):
-    from . import metrics as M
     p = argparse.ArgumentParser(prog="evaluate_spotting")
     p.add_argument("--path", required=True)
     p.add_argument("--threshold", type=float, default=0.5)
@@ -409,7 +448,7 @@ def cmd_evaluate_spotting(argv):
     feats = feats[lo:hi]
     acc = M.spotting_accuracy([f["gesture_emb"] for f in feats], [f["content_emb"] for f in feats],
                               [f["info"]["word_boundaries"] for f in feats],
-                              [f["info"]["target_word_boundary"] if not hasattr(f["info"], "target_word_boundary") else f["info"].target_word_boundary for f in feats],
+                              [f["info"]["target_word_boundary"] for f in feats],
                               thresh=args.threshold, frame_thresh=args.frame_threshold, engine=eng)
     if jdist.rank() == 0:
         print("Word Spotting Accuracy: {}".format(acc))
@@ -418,7 +457,6 @@ def cmd_evaluate_spotting(argv):
 
 def cmd_evaluate_asd(argv):
     import pandas as pd
-    from . import metrics as M
     p = argparse.ArgumentParser(prog="evaluate_asd")
     p.add_argument("--path", required=True)
     p.add_argument("--file", required=True)
@@ -428,11 +466,8 @@ def cmd_evaluate_asd(argv):
     print("Total files: {}".format(len(df)))
 
     def load(fname):
-        fn = os.path.join(args.path, fname.split("/")[0] + "__" + fname.split("/")[1] + ".pkl")
-        if not os.path.exists(fn):
-            return None
-        with open(fn, "rb") as f:
-            return pickle.load(f)
+        fn = extract.pkl_name(args.path, fname)
+        return _load_pkl(fn) if os.path.exists(fn) else None
 
     queries, cands = [], []
     lo, hi = jdist.shard_range(len(df))           # queries sharded over the ranks (contiguous blocks), counters all-reduced
@@ -463,7 +498,6 @@ def cmd_attn_matrix(argv, engine=None):
     best_frame (W,) int32, best_score (W,) float32}; <name> is --fname for a single file (plot_heatmap's flag), the .pkl's own name
     otherwise.  --normalize 0 (default) is what plot_heatmap.py computes on the stored, already normalised embeddings; 1 re-normalises the
     rows first (evaluate_spotting.py:39-57).  engine: the Engine to run on (default: this process's)."""
-    from . import metrics as M
     p = argparse.ArgumentParser(prog="attn_matrix")
     p.add_argument("--path", required=True, help="a JEGAL feature .pkl, or a directory of them")
     p.add_argument("--fname", default=None, help="name of the output for a single .pkl (default: the .pkl's name)")
@@ -473,27 +507,20 @@ def cmd_attn_matrix(argv, engine=None):
     args = p.parse_args(argv)
     if os.path.isdir(args.path):
         files, feats = _load_pkls(args.path)
-        names = [os.path.basename(f)[:-len(".pkl")] for f in files]
+        names = [_base_name(f) for f in files]
     else:
-        with open(args.path, "rb") as f:
-            feats = [pickle.load(f)]
-        names = [args.fname or os.path.basename(args.path).rsplit(".", 1)[0]]
+        feats = [_load_pkl(args.path)]
+        names = [args.fname or _base_name(args.path)]
     if not feats:
         raise SystemExit("no .pkl under {}".format(args.path))
-    words = []
-    for ft in feats:
-        wb = ft["info"]["word_boundaries"]          # info: the csv row (a pandas Series) or inference_embs' {fname, word_boundaries, text}
-        if isinstance(wb, str):
-            wb = ast.literal_eval(wb)
-        words.append([str(b[0]) for b in wb])
-    eng = engine if engine is not None else _models(args)[0]
-    mats, best = M._attn_call([np.asarray(ft["gesture_emb"], np.float32) for ft in feats],
-                              [np.asarray(ft["content_emb"], np.float32) for ft in feats],
-                              args.temp, bool(args.normalize), eng, None, True)          # matrices and best_* from ONE call
+    words = [_feature_words(ft) for ft in feats]
+    eng = _engine(engine, args)
+    mats, best = M.attn_call([np.asarray(ft["gesture_emb"], np.float32) for ft in feats],
+                             [np.asarray(ft["content_emb"], np.float32) for ft in feats],
+                             args.temp, bool(args.normalize), eng, None, True)          # matrices and best_* from ONE call
     os.makedirs(args.res_dir, exist_ok=True)
     for name, a, w, (bf, bs) in zip(names, mats, words, best):
-        if len(w) != a.shape[0]:
-            raise ValueError("{}: {} word boundaries for {} content rows".format(name, len(w), a.shape[0]))
+        M.check_word_count(len(w), a.shape[0], name)
         out = os.path.join(args.res_dir, name + ".attn.npz")
         np.savez(out, attn=a, words=np.asarray(w), best_frame=bf, best_score=bs)
         print("Attn mtx: ", a.shape, " -> ", out)
@@ -509,20 +536,18 @@ def cmd_retrieve(argv, engine=None):
     the .pkl base names = the gallery order, idx (N,K) int32 gallery rows best first (-1 where N < K), score (N,K) float32, rank (N,)
     int32: jg_sim_rank's rank of the clip's own partner from the same normalised rows}.  engine: the Engine to run on (default: this
     process's)."""
-    from . import metrics as M
     p = argparse.ArgumentParser(prog="retrieve")
     p.add_argument("--path", required=True, help="a directory of JEGAL feature .pkl files")
     p.add_argument("--topk", type=int, default=10, help="gallery clips kept per query (1..128)")
     p.add_argument("--direction", default="both", choices=["c2g", "g2c", "both"])
     p.add_argument("--res_dir", default=".")
     args = p.parse_args(argv)
-    if not 1 <= args.topk <= 128:
-        raise SystemExit("--topk must be 1..128")
-    eng = engine if engine is not None else _models(args)[0]
+    _check_topk(args.topk)
+    eng = _engine(engine, args)
     files, feats = _load_pkls(args.path)
     if not feats:
         raise SystemExit("no .pkl under {}".format(args.path))
-    names = np.asarray([os.path.basename(f)[:-len(".pkl")] for f in files])
+    names = np.asarray([_base_name(f) for f in files])
     lo, hi = jdist.shard_range(len(feats))
     pooled = {key: M.video_level(eng, [f[key] for f in feats[lo:hi]]) for key in ("gesture_emb", "content_emb")}
     res = {}
@@ -546,7 +571,7 @@ def _corpus_clips(path):
     feats = [(fn, ft) for fn, ft in zip(files, feats) if ft.get("gesture_emb") is not None]
     if not feats:
         raise SystemExit("no .pkl with gesture_emb under {}".format(path))
-    return (np.asarray([os.path.basename(fn)[:-len(".pkl")] for fn, _ in feats]),
+    return (np.asarray([_base_name(fn) for fn, _ in feats]),
             [np.asarray(ft["gesture_emb"], np.float32) for _, ft in feats])
 
 
@@ -554,7 +579,6 @@ def cmd_index(argv, engine=None):
     """Prepare a corpus for search --index: every gesture_emb of the .pkl files under --path (names and clip numbering as search --path
     has them), the rows L2-normalised (--normalize 1) and rounded to --dtype, written as one .npz (metrics.Corpus).  float16 halves the
     file, the upload and the device memory; the search then scores the rows as stored.  engine: the Engine to run on."""
-    from . import metrics as M
     p = argparse.ArgumentParser(prog="index")
     p.add_argument("--path", required=True, help="a directory of JEGAL feature .pkl files: the corpus")
     p.add_argument("--out", required=True, help="the corpus file to write (.npz)")
@@ -562,7 +586,7 @@ def cmd_index(argv, engine=None):
     p.add_argument("--normalize", type=int, default=1, choices=[0, 1], help="1: unit rows (cosine similarity); 0: the rows as stored")
     args = p.parse_args(argv)
     names, clips = _corpus_clips(args.path)
-    eng = engine if engine is not None else (_models(args)[0] if args.normalize else None)
+    eng = _engine(engine, args) if engine is not None or args.normalize else None
     corpus = M.Corpus.build(clips, names=names, dtype=args.dtype, normalize=bool(args.normalize), engine=eng)
     out = args.out if args.out.endswith(".npz") else args.out + ".npz"
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
@@ -580,7 +604,6 @@ def cmd_search(argv, engine=None):
     the frame inside the clip, score (Q,K) float32; -1 / -1 / -inf where fewer than K groups exist} and prints one line per query row.
     --index FILE instead of --path: the corpus is one written by the index command (metrics.Corpus, jg_sim_search): prepared once, maybe
     in 16 bits, the same output.  engine: the Engine to run on (default: this process's)."""
-    from . import metrics as M
     p = argparse.ArgumentParser(prog="search", description="Single process: sharding over ranks is not built for this command.")
     p.add_argument("--path", default=None, help="a directory of JEGAL feature .pkl files: the corpus (or --index)")
     p.add_argument("--index", default=None, help="a corpus written by the index command, instead of --path: prepared once, maybe in 16 bits")
@@ -592,39 +615,34 @@ def cmd_search(argv, engine=None):
     p.add_argument("--max_rows", type=int, default=None, help="gallery rows on the device at a time (default: all)")
     p.add_argument("--res_dir", default=".")
     args = p.parse_args(argv)
-    if not 1 <= args.topk <= 128:
-        raise SystemExit("--topk must be 1..128")
+    _check_topk(args.topk)
     if args.segment < 0:
         raise SystemExit("--segment must be >= 0")
     if (args.path is None) == (args.index is None):
         raise SystemExit("exactly one of --path and --index")
-    with open(args.query, "rb") as f:
-        qf = pickle.load(f)
+    qf = _load_pkl(args.query)
     if qf.get("content_emb") is None:
         raise SystemExit("{} holds no content_emb".format(args.query))
     queries = np.asarray(qf["content_emb"], np.float32)
-    wb = qf["info"]["word_boundaries"] if qf.get("info") is not None and "word_boundaries" in qf["info"] else None
-    if isinstance(wb, str):
-        wb = ast.literal_eval(wb)
-    words = [str(b[0]) for b in wb] if wb is not None else ["word{}".format(i) for i in range(len(queries))]
-    if len(words) != len(queries):
-        raise ValueError("{}: {} word boundaries for {} content rows".format(args.query, len(words), len(queries)))
+    words = _feature_words(qf)
+    if words is None:
+        words = ["word{}".format(i) for i in range(len(queries))]
+    M.check_word_count(len(words), len(queries), args.query)
     if args.level == "phrase":
         queries, words = queries.mean(axis=0, keepdims=True), [" ".join(words)]
     if args.index is not None:                   # (its rows were normalised, or not, when it was built: --normalize is about the query)
         corpus = M.Corpus.load(args.index)
         names = corpus.names
-        eng = engine if engine is not None else _models(args)[0]
+        eng = _engine(engine, args)
         clip, frame, score = corpus.search(queries, k=args.topk, segment=args.segment, normalize=bool(args.normalize), engine=eng,
                                            max_rows=args.max_rows)
     else:
         names, clips = _corpus_clips(args.path)
-        eng = engine if engine is not None else _models(args)[0]
+        eng = _engine(engine, args)
         clip, frame, score = M.search(queries, clips, k=args.topk, segment=args.segment, normalize=bool(args.normalize), engine=eng,
                                       max_rows=args.max_rows)
     os.makedirs(args.res_dir, exist_ok=True)
-    qname = os.path.basename(args.query).rsplit(".", 1)[0]
-    out = os.path.join(args.res_dir, "search_{}.npz".format(qname))
+    out = os.path.join(args.res_dir, "search_{}.npz".format(_base_name(args.query)))
     np.savez(out, words=np.asarray(words), names=names, clip=clip, frame=frame, score=score)
     for i, w in enumerate(words):
         hits = ["{}@{} ({:.3f})".format(names[c], f, s) for c, f, s in zip(clip[i][:3], frame[i][:3], score[i][:3]) if c >= 0]
@@ -642,7 +660,6 @@ def cmd_asd(argv, engine=None):
     int32, prob (n_win, P) float32, pred (n_win,) int32}: windows of --win frames, --hop apart, on the query's word boundaries.  A clip
     that is a candidate of many queries is on the device once.  engine: the Engine to run on (default: this process's)."""
     import pandas as pd
-    from . import metrics as M
     p = argparse.ArgumentParser(prog="asd", description="Single process: sharding over ranks is not built for this command.")
     p.add_argument("--path", required=True, help="a directory of JEGAL feature .pkl files")
     p.add_argument("--file", required=True, help="the csv of evaluate_asd: filename, neg_files")
@@ -655,16 +672,15 @@ def cmd_asd(argv, engine=None):
         raise SystemExit("--win must be 1..8192 and --hop >= 1")
     df = pd.read_csv(args.file)
     print("Total files: {}".format(len(df)))
-    stem = lambda fname: fname.split("/")[0] + "__" + fname.split("/")[1]
+    stem = lambda fname: _base_name(extract.pkl_name("", fname))
     feats, track_of, tracks = {}, {}, []
 
     def load(fname):
         if fname not in feats:
-            fn = os.path.join(args.path, stem(fname) + ".pkl")
+            fn = extract.pkl_name(args.path, fname)
             feats[fname] = None
             if os.path.exists(fn):
-                with open(fn, "rb") as f:
-                    feats[fname] = pickle.load(f)
+                feats[fname] = _load_pkl(fn)
                 track_of[fname] = len(tracks)
                 tracks.append(np.asarray(feats[fname]["gesture_emb"], np.float32))
         return feats[fname]
@@ -686,29 +702,27 @@ def cmd_asd(argv, engine=None):
         s_off.append(len(trk))
     if not names:
         raise SystemExit("no query of {} has a .pkl under {}".format(args.file, args.path))
-    eng = engine if engine is not None else _models(args)[0]
-    g, c = M._cat(tracks), M._cat(contents)
-    goff, coff = M._offsets(tracks), M._offsets(contents)
+    eng = _engine(engine, args)
+    g, c = M.cat_rows(tracks), M.cat_rows(contents)
+    goff, coff = M.offsets_of(tracks), M.offsets_of(contents)
     prob, _, pred, _, _ = eng.asd_windows(g, goff, c, coff, trk, s_off, win=0, temp=args.temp)
     os.makedirs(args.res_dir, exist_ok=True)
     out = os.path.join(args.res_dir, "asd.npz")
-    pred = M._host(pred).astype(np.int32)
+    pred = M.to_host(pred).astype(np.int32)
     np.savez(out, names=np.asarray(names), cand_names=np.asarray([c for cs in cand_names for c in cs]), cand_offsets=np.asarray(s_off, np.int64),
-             prob=M._host(prob), pred=pred)
+             prob=M.to_host(prob), pred=pred)
     print("ASD: {} queries, own clip chosen for {} -> {}".format(len(names), int(np.sum(pred == 0)), out))
     if args.win is not None:
-        se = [M._bounds(wb) for wb in bounds]
-        for name, (s, _), ct in zip(names, se, contents):
-            if len(s) != len(ct):
-                raise ValueError("{}: {} word boundaries for {} content rows".format(name, len(s), len(ct)))
+        start, end = M.batch_bounds(bounds, contents, names)
         prob, p_off, pred, w_off, _ = eng.asd_windows(g, goff, c, coff, trk, s_off, win=args.win, hop=args.hop, temp=args.temp,
-                                                      word_start=np.concatenate([s for s, _ in se]), word_end=np.concatenate([e for _, e in se]))
-        prob, pred = M._host(prob), M._host(pred)
+                                                      word_start=start, word_end=end)
+        prob, pred = M.to_host(prob), M.to_host(pred)
         for i, name in enumerate(names):
-            n_win = int(w_off[i + 1] - w_off[i])
+            w = M.span(w_off, i)
+            n_win = w.stop - w.start
             np.savez(os.path.join(args.res_dir, name + ".asd.npz"), candidates=np.asarray(cand_names[i]),
-                     start=(np.arange(n_win) * args.hop).astype(np.int32), prob=prob[p_off[i]:p_off[i + 1]].reshape(n_win, len(cand_names[i])),
-                     pred=pred[w_off[i]:w_off[i + 1]].astype(np.int32))
+                     start=M.window_starts(n_win, args.win, args.hop), prob=prob[M.span(p_off, i)].reshape(n_win, len(cand_names[i])),
+                     pred=pred[w].astype(np.int32))
         print("ASD timelines: win {} hop {} -> {}/<name>.asd.npz".format(args.win, args.hop, args.res_dir))
     return 0
 
@@ -721,7 +735,6 @@ SYNC_OFFSET_NOTE = ("The released GestSync checkpoint was trained on its authors
 def _sync_streams(args, engine, gestsync):
     """What both forms of sync_offset start from: the synthetic-weights warning, the models, the (T,1024) video rows of every --frames
     file and the (Ta,1024) audio rows of the one --wav / --mel -> (engine, [video rows], audio rows), on the device."""
-    from . import audio as jaudio
     if args.checkpoint_path_gestsync == "synthetic":
         print("WARNING: synthetic GestSync weights: their window embeddings are 0.93-0.996 correlated whatever the input, so the offset "
               "and confidence below are MEANINGLESS as a sync measurement; pass a trained checkpoint.")
@@ -740,8 +753,7 @@ def _sync_streams(args, engine, gestsync):
             raise ValueError("--mel must hold (Tm,80) mel rows")
         mel = mel[None].to(eng.device)
     else:
-        wav = torch.from_numpy(np.asarray(jaudio.load_wav(args.wav)).astype(np.float32))
-        mel = jaudio.wav2filterbanks(wav[None].to(eng.device), engine=eng)[0]
+        mel = _wav_mel(args.wav, eng)
     T = max(int(v.shape[0]) for v in vids)
     Ta = max(1, min(T, -(-int(mel.shape[1]) // 4)))            # audio windows: one per frame the mel covers
     return eng, vids, gestsync.extract_clip_audio_feats(mel, Ta)[0]
@@ -751,7 +763,6 @@ def _sync_offset_over_time(args, engine, gestsync):
     """sync_offset with --win (the offset as a function of time: metrics.sync_timeline) and / or several --frames (which track is in sync
     with the audio: metrics.sync_speaker); every track's ``<name>.sync.npz`` gains start, offset_t, conf_t, curve_t beside the clip-level
     offset, conf, curve, shifts."""
-    from . import metrics as M
     eng, vids, aud = _sync_streams(args, engine, gestsync)
     hop = args.hop if args.hop > 0 else max(1, args.win // 5)
     Ta = int(aud.shape[0])
@@ -762,8 +773,7 @@ def _sync_offset_over_time(args, engine, gestsync):
     os.makedirs(args.res_dir, exist_ok=True)
     shifts = np.arange(-args.max_shift, args.max_shift + 1, dtype=np.int32)
     for f, v, c, t in zip(args.frames, vids, clip, line):
-        name = os.path.basename(f).rsplit(".", 1)[0]
-        out = os.path.join(args.res_dir, name + ".sync.npz")
+        out = os.path.join(args.res_dir, _base_name(f) + ".sync.npz")
         np.savez(out, offset=c["offset"][0], conf=c["conf"][0], curve=c["curve"][0], shifts=shifts, start=t["start"], offset_t=t["offset"],
                  conf_t=t["conf"], curve_t=t["curve"])
         print("AV offset: {} frames   confidence: {:.4f}   ({} video / {} audio windows) -> {}".format(
@@ -782,11 +792,11 @@ def _sync_offset_over_time(args, engine, gestsync):
             print("  over time (win {} hop {}): no window with a shift".format(args.win, hop))
     if n > 1:
         speaker, conf = M.sync_speaker(vids, aud, win=args.win, hop=hop, max_shift=args.max_shift, min_overlap=args.min_overlap, engine=eng)
-        names = [os.path.basename(f).rsplit(".", 1)[0] for f in args.frames]
+        names = [_base_name(f) for f in args.frames]
+        start = M.window_starts(len(speaker), args.win, hop)
         for j, s in enumerate(speaker):
-            print("  window {} (frame {}): in sync: {}".format(j, j * hop if args.win else 0, names[s] if s >= 0 else "-"))
-        np.savez(os.path.join(args.res_dir, "sync_speaker.npz"), tracks=np.asarray(names), speaker=speaker, conf=conf,
-                 start=(np.arange(len(speaker)) * (hop if args.win else 0)).astype(np.int32))
+            print("  window {} (frame {}): in sync: {}".format(j, start[j], names[s] if s >= 0 else "-"))
+        np.savez(os.path.join(args.res_dir, "sync_speaker.npz"), tracks=np.asarray(names), speaker=speaker, conf=conf, start=start)
     return 0
 
 
@@ -798,7 +808,6 @@ def cmd_sync_offset(argv, engine=None, gestsync=None):
     shifts}.  --win N [--hop M]: the offset over time as well (_sync_offset_over_time: metrics.sync_timeline); --frames given several
     times: candidate tracks against the one audio, the in-sync track per window (metrics.sync_speaker).  Without either: the output of
     before, byte for byte."""
-    from . import metrics as M
     p = argparse.ArgumentParser(prog="sync_offset", epilog=SYNC_OFFSET_NOTE)
     p.add_argument("--checkpoint_path_gestsync", required=True,
                    help="GestSync checkpoint with its audio stream; 'synthetic' = the seeded test weights, whose embeddings carry NO sync "
@@ -823,9 +832,8 @@ def cmd_sync_offset(argv, engine=None, gestsync=None):
     eng, (vid,), aud = _sync_streams(args, engine, gestsync)
     T, Ta = int(vid.shape[0]), int(aud.shape[0])
     off, conf, curve = M.sync_offset([vid], [aud], args.max_shift, args.min_overlap, engine=eng)
-    name = os.path.basename(args.frames[0]).rsplit(".", 1)[0]
     os.makedirs(args.res_dir, exist_ok=True)
-    out = os.path.join(args.res_dir, name + ".sync.npz")
+    out = os.path.join(args.res_dir, _base_name(args.frames[0]) + ".sync.npz")
     np.savez(out, offset=off[0], conf=conf[0], curve=curve[0], shifts=np.arange(-args.max_shift, args.max_shift + 1, dtype=np.int32))
     print("AV offset: {} frames   confidence: {:.4f}   ({} video / {} audio windows) -> {}".format(int(off[0]), float(conf[0]), T, Ta, out))
     return 0
@@ -864,7 +872,7 @@ def cmd_embed_tracks(argv, engine=None, jegal=None):
     todo = []
     for f in files[lo:hi]:
         fname = f.split("/")[-2] + "/" + os.path.basename(f)[:-len(".npy")]
-        out = os.path.join(res_dir, fname.replace("/", "__") + ".pkl")
+        out = extract.pkl_name(res_dir, fname)
         if os.path.exists(out):                      # resume: skip-if-exists, as extract_gestsync_feats
             saved += 1
             continue
@@ -881,41 +889,21 @@ def cmd_embed_tracks(argv, engine=None, jegal=None):
         embs = jegal.forward_gesture_tracks([torch.from_numpy(ft) for ft, _, _ in group], win=args.win, ctx=args.ctx, normalize=True)
         return [e.cpu().numpy() for e in embs]
 
+    def save_one(emb, item):
+        with open(item[2], "wb") as f:
+            pickle.dump({"gesture_emb": emb, "content_emb": None, "info": {"fname": item[1], "win": args.win, "ctx": args.ctx}}, f)
+
     cap = max(1, args.rows_per_call)
-    s0 = 0
+    groups, s0 = [], 0
     while s0 < len(todo):
         s1, rows = s0 + 1, todo[s0][0].shape[0]
         while s1 < len(todo) and rows + todo[s1][0].shape[0] <= cap:
             rows += todo[s1][0].shape[0]
             s1 += 1
-        group = todo[s0:s1]
+        groups.append(todo[s0:s1])
         s0 = s1
-        try:
-            embs = run_group(group)
-        except Exception as e:                       # one bad track must not take its neighbours down: retry the group track by track
-            if len(group) == 1:
-                err += 1
-                print("Error: ", e, " | Track: ", group[0][1])
-                continue
-            embs = []
-            for item in group:
-                try:
-                    embs.append(run_group([item])[0])
-                except Exception as e1:
-                    embs.append(None)
-                    err += 1
-                    print("Error: ", e1, " | Track: ", item[1])
-        for emb, (_, fname, out) in zip(embs, group):
-            if emb is None:
-                continue
-            try:
-                with open(out, "wb") as f:
-                    pickle.dump({"gesture_emb": emb, "content_emb": None, "info": {"fname": fname, "win": args.win, "ctx": args.ctx}}, f)
-                saved += 1
-            except Exception as e:
-                err += 1
-                print("Error: ", e, " | Track: ", fname)
-    print("No of files saved = {} | Err = {}".format(saved, err))
+    done, failed = _run_groups(groups, run_group, save_one, "Track")
+    print("No of files saved = {} | Err = {}".format(saved + done, err + failed))
     print("Saved JEGAL gesture embeddings at: ", res_dir)
     return 0
 
@@ -934,7 +922,6 @@ def cmd_spot_talk(argv, engine=None):
     float32: band[w][j] = the probability of word w at frame first_frame[w] + j, NaN outside the track or its reach; best_frame (W,) int32,
     best_score (W,) float32; frame_word (T,) int32, frame_prob (T,) float32}; --band 0 leaves first_frame and band out.  <name> is the
     gesture .pkl's own name.  engine: the Engine to run on (default: this process's)."""
-    from . import metrics as M
     p = argparse.ArgumentParser(prog="spot_talk", description=SPOT_TALK_NOTE)
     p.add_argument("--gesture", required=True, help="the track's .pkl (embed_tracks): gesture_emb (T,512)")
     p.add_argument("--content", default=None, help="a feature .pkl with content_emb (W,512) and word boundaries on the track's frame axis")
@@ -949,16 +936,12 @@ def cmd_spot_talk(argv, engine=None):
     if (args.content is None) == (args.utterances is None) or (args.utterances is not None and args.path is None):
         raise SystemExit("spot_talk: give --content C.pkl, or --utterances LIST.csv with --path DIR")
 
-    def load(fn):
-        with open(fn, "rb") as f:
-            return pickle.load(f)
-
-    track = load(args.gesture)
+    track = _load_pkl(args.gesture)
     if track.get("gesture_emb") is None:
         raise SystemExit("{} holds no gesture_emb".format(args.gesture))
     gesture = np.asarray(track["gesture_emb"], np.float32)
     if args.content is not None:
-        ft = load(args.content)
+        ft = _load_pkl(args.content)
         if ft.get("content_emb") is None:
             raise SystemExit("{} holds no content_emb".format(args.content))
         content, bounds = M.talk_words([ft], [0])
@@ -966,13 +949,12 @@ def cmd_spot_talk(argv, engine=None):
         import pandas as pd
         df = pd.read_csv(args.utterances)
         stem = lambda fname: "__".join(str(fname).split("/")) + ("" if str(fname).endswith(".pkl") else ".pkl")
-        content, bounds = M.talk_words([load(os.path.join(args.path, stem(f))) for f in df.filename], [int(s) for s in df.start_frame])
-    eng = engine if engine is not None else _models(args)[0]
+        content, bounds = M.talk_words([_load_pkl(os.path.join(args.path, stem(f))) for f in df.filename], [int(s) for s in df.start_frame])
+    eng = _engine(engine, args)
     call = M.talk_heatmap if args.band else M.spot_talk
     r = call(gesture, content, bounds, reach=args.reach, temp=args.temp, normalize=bool(args.normalize), engine=eng)
     os.makedirs(args.res_dir, exist_ok=True)
-    name = os.path.basename(args.gesture).rsplit(".", 1)[0]
-    out = os.path.join(args.res_dir, name + ".talk.npz")
+    out = os.path.join(args.res_dir, _base_name(args.gesture) + ".talk.npz")
     np.savez(out, words=np.asarray([b[0] for b in bounds]), word_start=np.asarray([b[1] for b in bounds], np.int32),
              word_end=np.asarray([b[2] for b in bounds], np.int32), **r)
     print("Talk heat map: {} frames, {} words, reach {} -> {}".format(gesture.shape[0], len(bounds), args.reach, out))
@@ -1012,8 +994,6 @@ def cmd_inference_embs(argv):
 
     All seven --modalities work (the reference unpacks two return values and indexes word_boundaries[0] unconditionally, so only
     'vta' / 'vt' / 'va' survive there): outputs follow JEGAL.forward_inference's own return convention (:377-415)."""
-    from . import audio as jaudio
-    from . import extract
     p = argparse.ArgumentParser(prog="inference_embs")
     p.add_argument("--checkpoint_path_gestsync", required=True)
     p.add_argument("--checkpoint_path_jegal", required=True)
@@ -1090,8 +1070,6 @@ def audit_against_fp32(args, mod, gesture, content):
 def _inference_embs_clip(args, mod, eng, gs, jg, verbose=True):
     """frames / wav / text of one clip -> (gesture (T,512) | None, content (W,512) | None, fname, word boundaries, text): extract_embs of
     inference_embs.py:526-646 on `eng`."""
-    from . import audio as jaudio
-    from . import extract
     say = print if verbose else (lambda *a, **k: None)
     vis = mask = text = audio = am = wbs = None
     fname = None
@@ -1119,8 +1097,7 @@ def _inference_embs_clip(args, mod, eng, gs, jg, verbose=True):
             fname = os.path.basename(args.text_path).split(".")[0]
     if args.audio_path is not None and "a" in mod:
         say("Loading audio...")
-        wav = torch.from_numpy(np.asarray(jaudio.load_wav(args.audio_path)).astype(np.float32))
-        audio = jaudio.wav2filterbanks(wav[None].to(eng.device), engine=eng)[0]       # load_audio (:440-475)
+        audio = _wav_mel(args.audio_path, eng)                               # load_audio (:440-475)
         say("Input audio mel: ", tuple(audio.shape))
         am = torch.ones((1, audio.shape[1] // 4), device=eng.device)
     if fname is None and args.audio_path is not None:
@@ -1139,13 +1116,7 @@ def _inference_embs_clip(args, mod, eng, gs, jg, verbose=True):
     say("------------------------------------------------")
     out = jg.forward_inference(visual_feats=vis, visual_mask=mask, text=text, audio=audio, audio_mask=am,
                                word_boundaries=wbs if mod != "v" else None)
-    gesture = content = None
-    if vis is not None and (text is not None or audio is not None):
-        gesture, content = out
-    elif vis is not None:
-        gesture = out
-    else:
-        content = out
+    gesture, content = _gesture_content(out, vis is not None, text is not None or audio is not None)
     if gesture is not None:
         gesture = eng.l2norm(gesture[0]).cpu().numpy()                       # F.normalize(p=2, dim=-1), [0], .cpu().numpy() (:629-637)
         say("Extracted gesture embeddings: ", gesture.shape)

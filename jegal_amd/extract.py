@@ -71,7 +71,7 @@ def extract_embs(gestsync, jegal, frames, text=None, audio=None, word_boundaries
 
 
 def pkl_name(res_dir, filename):
-    """<res_dir>/<vid>__<track>.pkl (extract_jegal_embs.py:120)."""
+    """<res_dir>/<vid>__<track>.pkl (extract_jegal_embs.py:120, evaluate_asd.py:65,80): the one place that names a feature file."""
     parts = filename.split("/")
     return os.path.join(res_dir, parts[0] + "__" + parts[1] + ".pkl")
 

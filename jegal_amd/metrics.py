@@ -7,7 +7,6 @@ across ranks (contiguous blocks, the --rank/--nshard rule of extract_gestsync_fe
 the gallery is assembled with one all-gather (RCCL over xGMI on MI355X).
 """
 import ast
-import math
 
 import numpy as np
 import torch
@@ -16,20 +15,64 @@ from ._lib import Engine
 from . import dist as jdist
 
 
-def _tensor(x):
-    return x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x, np.float32))
+def cat_rows(x):
+    """One float32 (rows, D) tensor from a ragged batch -- a list of per-item (n_i, D) arrays or tensors -- or from one (n, D) array or
+    tensor.  Host arrays: one np.concatenate to float32 and one CPU tensor (the engine entry that takes it uploads it, once); tensors: the
+    torch.cat of the float32 parts where they lie (the extractors' outputs stay on the device).  One matrix is not copied."""
+    if isinstance(x, torch.Tensor):
+        return x.to(torch.float32)
+    if not isinstance(x, (list, tuple)) or (len(x) and np.ndim(x[0]) < 2):          # (a list of plain rows is one matrix)
+        return torch.as_tensor(np.asarray(x, np.float32))
+    if len(x) and isinstance(x[0], torch.Tensor):
+        return torch.cat([torch.as_tensor(m).to(torch.float32) for m in x], 0)
+    return torch.as_tensor(np.concatenate([np.asarray(m, np.float32) for m in x], 0))
 
 
-def _offsets(mats):
+def offsets_of(mats):
+    """the (n + 1,) int32 row offsets of a ragged batch in cat_rows' order"""
     off = np.zeros(len(mats) + 1, np.int32)
     off[1:] = np.cumsum([m.shape[0] for m in mats])
     return off
 
 
+def to_host(x):
+    return x.cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+
+
+_offsets, _host = offsets_of, to_host          # (the names these two had before they were public)
+
+
+def span(off, i):
+    """the rows of item i in a flat result laid out by the offsets `off`"""
+    return slice(int(off[i]), int(off[i + 1]))
+
+
+def window_starts(n, win, hop):
+    """the first frame of each of n windows, `hop` apart (win == 0: the one window over everything starts at 0) -> (n,) int32"""
+    return (np.arange(n) * (hop if win else 0)).astype(np.int32)
+
+
+def boundary_list(wb):
+    """the word boundaries of one clip as a list: the list itself, or its repr as the csv rows hold it"""
+    return ast.literal_eval(wb) if isinstance(wb, str) else wb
+
+
+def word_bounds(wb):
+    """word boundaries of one clip -> (words [str], start (W,) int64, end (W,) int64): [word, start, end] triplets, (start, end) pairs (no
+    word: the first entry stands in) or the repr of either"""
+    wb = boundary_list(wb)
+    return [str(b[0]) for b in wb], np.asarray([b[-2] for b in wb], np.int64), np.asarray([b[-1] for b in wb], np.int64)
+
+
+def check_word_count(n_bounds, n_rows, name=None):
+    """every content row needs its boundary; name: what the message is about (a file, "utterance 3")"""
+    if n_bounds != n_rows:
+        raise ValueError("{}{} word boundaries for {} content rows".format("" if name is None else "{}: ".format(name), n_bounds, n_rows))
+
+
 def video_level(engine, mats):
     """Temporal mean per clip (evaluate_retrieval.py:30-31): list of (T_i,512) -> (N,512) device."""
-    cat = torch.as_tensor(np.concatenate([np.asarray(m, np.float32) for m in mats], 0))
-    return engine.pool_mean(cat, _offsets(mats))
+    return engine.pool_mean(cat_rows(mats), offsets_of(mats))
 
 
 def metrics_from_ranks(rank, ties):
@@ -43,17 +86,20 @@ def metrics_from_ranks(rank, ties):
     return out
 
 
+def _normalised_and_gathered(eng, queries, gallery):
+    """What retrieval_metrics, retrieve and partner_ranks start from: both sets L2-normalised, the gallery all-gathered over the ranks (a
+    single process: the rows themselves) -> (queries, gallery, the row of the gallery at which this rank's block begins)"""
+    q = eng.l2norm(cat_rows(queries))
+    g, row_offset = jdist.all_gather_rows(eng.l2norm(cat_rows(gallery)))
+    return q, g, row_offset
+
+
 def retrieval_metrics(emb1, emb2, engine=None):
     """get_similarity_matrix + compute_metrics (evaluate_retrieval.py:38-65) for query set emb1
     against gallery emb2 (both (N,512), un-normalised video-level means).  Sharded over ranks when
     torch.distributed is initialised: every rank passes ITS contiguous block of rows."""
     eng = engine or Engine.get()
-    e1 = eng.l2norm(_tensor(emb1))
-    e2 = eng.l2norm(_tensor(emb2))
-    if jdist.world_size() > 1:
-        gallery, row_offset = jdist.all_gather_rows(e2)
-    else:
-        gallery, row_offset = e2, 0
+    e1, gallery, row_offset = _normalised_and_gathered(eng, emb1, emb2)
     rank, ties = eng.sim_rank(e1, gallery, row_offset)
     if jdist.world_size() > 1:
         rank, _ = jdist.all_gather_rows(rank.to(torch.int32).reshape(-1, 1))
@@ -69,13 +115,11 @@ def retrieve(emb_q, emb_g, k=10, engine=None):
     all-gathered, each rank runs its queries and the results are gathered in rank order.
     Returns host arrays (idx (N,k) int32: global gallery rows, -1 where the gallery has fewer than k; score (N,k) float32)."""
     eng = engine or Engine.get()
-    q = eng.l2norm(_tensor(emb_q))
-    g = eng.l2norm(_tensor(emb_g))
-    g, _ = jdist.all_gather_rows(g)                  # (a single process: the rows themselves)
+    q, g, _ = _normalised_and_gathered(eng, emb_q, emb_g)
     idx, score = eng.sim_topk(q, g, k)
     idx, _ = jdist.all_gather_rows(idx)
     score, _ = jdist.all_gather_rows(score)
-    return _host(idx), _host(score)
+    return to_host(idx), to_host(score)
 
 
 def search_groups(lengths, segment=0):
@@ -94,28 +138,23 @@ def search_groups(lengths, segment=0):
     return off, np.asarray(clip, np.int32), np.asarray(start, np.int32)
 
 
-def search(queries, clips, k=10, segment=0, normalize=True, engine=None, max_rows=None):
-    """For each query row (a word, a phrase: (Q, D), the space of the content embeddings), the k clips of a corpus that gesture it and the
-    frame at which they do: clips is a list of (T_i, D) frame-level gesture arrays; a clip scores as its best frame (jg_sim_topk_grouped:
-    no pooling, no Q x sum T matrix, scores as jg_sim_topk computes them).  segment > 0: the groups are runs of `segment` frames of a clip
-    instead of whole clips, so a long track can come back with several moments.  normalize: rows are L2-normalised first (cosine
-    similarity); False: the rows as stored.  max_rows: the gallery goes to the device in pieces of at most that many rows, cut at group
-    boundaries and merged -- the same result, for corpora larger than device memory.
-    Returns host arrays (clip (Q, k) int32, frame (Q, k) int32: the frame inside the clip, score (Q, k) float32), best first, ties to the
-    earlier clip and frame; -1 / -1 / -inf where fewer than k groups exist."""
+def _search_walk(queries, dim, corpus, k, segment, normalize, engine, max_rows):
+    """The walk of search() and Corpus.search(): check the arguments, cut the clips into groups (search_groups) and the groups into pieces
+    of at most max_rows rows, score piece after piece into one merged top-k list, and decode its gallery rows into (clip, frame, score).
+    corpus(q) checks the (Q, D) query tensor against the gallery and returns (the frames of every clip, score_piece); score_piece(eng, q,
+    r0, r1, c0, c1, g_offsets, res) brings the gallery rows r0 .. r1 - 1 (of the clips c0 .. c1 - 1) to the device and scores them with the
+    caller's entry, merging into res.  dim: what a message calls the queries' D."""
     k, segment = int(k), int(segment)
     if not 1 <= k <= 128:
         raise ValueError("k must be 1..128")
     if segment < 0:
         raise ValueError("segment must be >= 0 (0: one group per clip)")
-    q = _tensor(queries)
+    q = cat_rows(queries)
     if q.ndim != 2:
-        raise ValueError("queries must be (Q, D)")
-    Q, D = int(q.shape[0]), int(q.shape[1])
-    clips = [c if isinstance(c, torch.Tensor) else np.asarray(c, np.float32) for c in clips]
-    if any(c.ndim != 2 or c.shape[1] != D for c in clips):
-        raise ValueError("every clip must be (T_i, {}) like the queries".format(D))
-    goff, gclip, gstart = search_groups([c.shape[0] for c in clips], segment)
+        raise ValueError("queries must be (Q, {})".format(dim))
+    Q = int(q.shape[0])
+    lengths, score_piece = corpus(q)
+    goff, gclip, gstart = search_groups(lengths, segment)
     n_groups = len(gclip)
     if goff[-1] > 2 ** 31 - 1:
         raise ValueError("more than INT32_MAX gallery rows")
@@ -128,37 +167,50 @@ def search(queries, clips, k=10, segment=0, normalize=True, engine=None, max_row
     eng = engine or Engine.get()
     if normalize:
         q = eng.l2norm(q)
-    # pieces = runs of whole groups of at most max_rows rows
-    cuts, g0 = [], 0
-    while g0 < n_groups:
-        g1 = g0 + 1
-        if max_rows is None:
-            g1 = n_groups
-        else:
+    res, g0 = None, 0
+    while g0 < n_groups:                             # pieces = runs of whole groups of at most max_rows rows
+        g1 = n_groups
+        if max_rows is not None:
+            g1 = g0 + 1
             while g1 < n_groups and goff[g1 + 1] - goff[g0] <= int(max_rows):
                 g1 += 1
-        cuts.append((g0, g1))
-        g0 = g1
-    first_clip = np.concatenate([[0], np.cumsum([c.shape[0] for c in clips])])
-    res = None
-    for g0, g1 in cuts:
         r0, r1 = int(goff[g0]), int(goff[g1])
-        if r1 == r0:
-            continue
-        c0, c1 = int(gclip[g0]), int(gclip[g1 - 1]) + 1                      # the clips the piece's rows come from
-        rows = [torch.as_tensor(c) for c in clips[c0:c1]]
-        rows = torch.cat(rows, 0)[r0 - int(first_clip[c0]):r1 - int(first_clip[c0])].to(torch.float32)
-        if normalize:
-            rows = eng.l2norm(rows)
-        res = eng.sim_topk_grouped(q, rows, goff[g0:g1 + 1] - r0, k, gallery_offset=r0, merge_into=res)
+        if r1 > r0:
+            res = score_piece(eng, q, r0, r1, int(gclip[g0]), int(gclip[g1 - 1]) + 1, goff[g0:g1 + 1] - r0, res)
+        g0 = g1
     if res is None:
         return empty
     grp, pos = eng.group_of_rows(res[0], goff, 0)
-    grp, pos, score = _host(grp).astype(np.int64), _host(pos).astype(np.int32), _host(res[1]).astype(np.float32)
+    grp, pos, score = to_host(grp).astype(np.int64), to_host(pos).astype(np.int32), to_host(res[1]).astype(np.float32)
     found = grp >= 0
     clip = np.where(found, gclip[np.maximum(grp, 0)], -1).astype(np.int32)
     frame = np.where(found, gstart[np.maximum(grp, 0)] + pos, -1).astype(np.int32)
     return clip, frame, score
+
+
+def search(queries, clips, k=10, segment=0, normalize=True, engine=None, max_rows=None):
+    """For each query row (a word, a phrase: (Q, D), the space of the content embeddings), the k clips of a corpus that gesture it and the
+    frame at which they do: clips is a list of (T_i, D) frame-level gesture arrays; a clip scores as its best frame (jg_sim_topk_grouped:
+    no pooling, no Q x sum T matrix, scores as jg_sim_topk computes them).  segment > 0: the groups are runs of `segment` frames of a clip
+    instead of whole clips, so a long track can come back with several moments.  normalize: rows are L2-normalised first (cosine
+    similarity); False: the rows as stored.  max_rows: the gallery goes to the device in pieces of at most that many rows, cut at group
+    boundaries and merged -- the same result, for corpora larger than device memory.
+    Returns host arrays (clip (Q, k) int32, frame (Q, k) int32: the frame inside the clip, score (Q, k) float32), best first, ties to the
+    earlier clip and frame; -1 / -1 / -inf where fewer than k groups exist."""
+    def corpus(q):
+        D = int(q.shape[1])
+        mats = [c if isinstance(c, torch.Tensor) else np.asarray(c, np.float32) for c in clips]
+        if any(c.ndim != 2 or c.shape[1] != D for c in mats):
+            raise ValueError("every clip must be (T_i, {}) like the queries".format(D))
+        first_row = np.concatenate([[0], np.cumsum([c.shape[0] for c in mats])])
+
+        def score_piece(eng, q, r0, r1, c0, c1, g_offsets, res):        # the rows of the piece come from the clips c0 .. c1 - 1
+            rows = cat_rows(mats[c0:c1])[r0 - int(first_row[c0]):r1 - int(first_row[c0])]
+            if normalize:
+                rows = eng.l2norm(rows)
+            return eng.sim_topk_grouped(q, rows, g_offsets, int(k), gallery_offset=r0, merge_into=res)
+        return [c.shape[0] for c in mats], score_piece
+    return _search_walk(queries, "D", corpus, k, segment, normalize, engine, max_rows)
 
 
 class Corpus:
@@ -194,7 +246,7 @@ class Corpus:
         dtype = np.dtype(dtype)
         if dtype not in (np.float16, np.float32):
             raise ValueError("dtype must be float16 or float32")
-        clips = [_host(c).astype(np.float32, copy=False) if isinstance(c, torch.Tensor) else np.asarray(c, np.float32) for c in clips]
+        clips = [to_host(c).astype(np.float32, copy=False) if isinstance(c, torch.Tensor) else np.asarray(c, np.float32) for c in clips]
         D = clips[0].shape[1] if clips and clips[0].ndim == 2 else 0
         if any(c.ndim != 2 or c.shape[1] != D for c in clips):
             raise ValueError("every clip must be (T_i, D) with one D")
@@ -204,7 +256,7 @@ class Corpus:
         rows = np.concatenate(clips, 0) if clips else np.zeros((0, 0), np.float32)
         if normalize and rows.shape[0]:
             eng = engine or Engine.get()
-            rows = np.concatenate([_host(eng.l2norm(torch.from_numpy(rows[a:a + cls.CHUNK]))).astype(np.float32, copy=False)
+            rows = np.concatenate([to_host(eng.l2norm(torch.from_numpy(rows[a:a + cls.CHUNK]))).astype(np.float32, copy=False)
                                    for a in range(0, rows.shape[0], cls.CHUNK)], 0)
         return cls(rows.astype(dtype), [c.shape[0] for c in clips], names, normalize)
 
@@ -232,57 +284,25 @@ class Corpus:
         group boundaries under max_rows, through jg_sim_search, which spreads the rows over every CU.  normalize: the QUERY rows are
         L2-normalised first (the corpus rows are what build() made them).  Without max_rows the rows stay on the engine's device between
         calls: repeated searches upload the queries only."""
-        k, segment = int(k), int(segment)
-        if not 1 <= k <= 128:
-            raise ValueError("k must be 1..128")
-        if segment < 0:
-            raise ValueError("segment must be >= 0 (0: one group per clip)")
-        q = _tensor(queries)
-        if q.ndim != 2 or (self.rows.shape[0] and q.shape[1] != self.rows.shape[1]):
-            raise ValueError("queries must be (Q, {})".format(self.rows.shape[1]))
-        Q = int(q.shape[0])
-        goff, gclip, gstart = search_groups(self.lengths, segment)
-        n_groups = len(gclip)
-        sizes = np.diff(goff)
-        if max_rows is not None and (int(max_rows) < 1 or (n_groups and sizes.max() > int(max_rows))):
-            raise ValueError("max_rows must hold the largest group ({} rows): groups are never split; use segment".format(int(sizes.max()) if n_groups else 0))
-        empty = (np.full((Q, k), -1, np.int32), np.full((Q, k), -1, np.int32), np.full((Q, k), -np.inf, np.float32))
-        if Q == 0 or goff[-1] == 0:
-            return empty
-        eng = engine or Engine.get()
-        if normalize:
-            q = eng.l2norm(q)
-        res, g0 = None, 0
-        while g0 < n_groups:                             # pieces = runs of whole groups of at most max_rows rows, as in search()
-            g1 = n_groups
-            if max_rows is not None:
-                g1 = g0 + 1
-                while g1 < n_groups and goff[g1 + 1] - goff[g0] <= int(max_rows):
-                    g1 += 1
-            r0, r1 = int(goff[g0]), int(goff[g1])
-            if r1 > r0:
-                res = eng.sim_search(q, self._device_rows(eng, r0, r1, max_rows is None), k, g_offsets=goff[g0:g1 + 1] - r0, gallery_offset=r0,
-                                     merge_into=res)
-            g0 = g1
-        if res is None:
-            return empty
-        grp, pos = eng.group_of_rows(res[0], goff, 0)
-        grp, pos, score = _host(grp).astype(np.int64), _host(pos).astype(np.int32), _host(res[1]).astype(np.float32)
-        found = grp >= 0
-        clip = np.where(found, gclip[np.maximum(grp, 0)], -1).astype(np.int32)
-        frame = np.where(found, gstart[np.maximum(grp, 0)] + pos, -1).astype(np.int32)
-        return clip, frame, score
+        def corpus(q):
+            if self.rows.shape[0] and q.shape[1] != self.rows.shape[1]:
+                raise ValueError("queries must be (Q, {})".format(self.rows.shape[1]))
+
+            def score_piece(eng, q, r0, r1, c0, c1, g_offsets, res):
+                return eng.sim_search(q, self._device_rows(eng, r0, r1, max_rows is None), int(k), g_offsets=g_offsets, gallery_offset=r0,
+                                      merge_into=res)
+            return self.lengths, score_piece
+        return _search_walk(queries, self.rows.shape[1], corpus, k, segment, normalize, engine, max_rows)
 
 
 def partner_ranks(emb1, emb2, engine=None):
     """jg_sim_rank's rank of every query's own partner (row i of emb1 belongs to row i of emb2), the number retrieval_metrics turns into
     R@K: host int32 (N,), over all ranks' rows in rank order when sharded."""
     eng = engine or Engine.get()
-    e1 = eng.l2norm(_tensor(emb1))
-    gallery, row_offset = jdist.all_gather_rows(eng.l2norm(_tensor(emb2)))
+    e1, gallery, row_offset = _normalised_and_gathered(eng, emb1, emb2)
     rank, _ = eng.sim_rank(e1, gallery, row_offset)
     rank, _ = jdist.all_gather_rows(rank.to(torch.int32).reshape(-1, 1))
-    return _host(rank).reshape(-1).astype(np.int32)
+    return to_host(rank).reshape(-1).astype(np.int32)
 
 
 def reduce_counts(counts, device=None):
@@ -315,7 +335,7 @@ def spotting_accuracy(gestures, contents, word_boundaries, targets, thresh=0.5, 
     gestures / contents: lists of per-clip (T_i,512) / (W_i,512) arrays as the evaluators load them from the .pkl files, or -- with
     ``offsets=(g_offsets, c_offsets)`` -- the already concatenated (sum T,512) / (sum W,512) tensors (device-resident galleries)."""
     eng = engine or Engine.get()
-    wbs = [ast.literal_eval(w) if isinstance(w, str) else w for w in word_boundaries]
+    wbs = [boundary_list(w) for w in word_boundaries]
     tidx = []
     for wb, t in zip(wbs, targets):
         if isinstance(t, str):
@@ -326,9 +346,7 @@ def spotting_accuracy(gestures, contents, word_boundaries, targets, thresh=0.5, 
         if offsets is not None:
             g, c, (goff, coff) = gestures, contents, offsets
         else:
-            g = torch.as_tensor(np.concatenate([np.asarray(x, np.float32) for x in gestures], 0))
-            c = torch.as_tensor(np.concatenate([np.asarray(x, np.float32) for x in contents], 0))
-            goff, coff = _offsets(gestures), _offsets(contents)
+            g, c, goff, coff = cat_rows(gestures), cat_rows(contents), offsets_of(gestures), offsets_of(contents)
         pred, score = eng.spot(g, c, goff, coff, tidx)
         correct, _ = spotting_counts(pred.cpu().numpy(), score.cpu().numpy(), wbs, tidx, thresh, frame_thresh)
     correct, total = reduce_counts([correct, len(wbs)], eng.device)
@@ -342,16 +360,10 @@ def _ragged_inputs(gestures, contents, offsets):
         return gestures, contents, goff.astype(np.int64), coff.astype(np.int64)
     if not len(gestures):
         return None, None, np.zeros(1, np.int64), np.zeros(1, np.int64)
-    g = torch.as_tensor(np.concatenate([np.asarray(x, np.float32) for x in gestures], 0))
-    c = torch.as_tensor(np.concatenate([np.asarray(x, np.float32) for x in contents], 0))
-    return g, c, _offsets(gestures).astype(np.int64), _offsets(contents).astype(np.int64)
+    return cat_rows(gestures), cat_rows(contents), offsets_of(gestures).astype(np.int64), offsets_of(contents).astype(np.int64)
 
 
-def _host(x):
-    return x.cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
-
-
-def _attn_call(gestures, contents, temp, normalize, engine, offsets, want_matrix):
+def attn_call(gestures, contents, temp, normalize, engine, offsets, want_matrix):
     """One Engine.attn_matrix call for the batch -> (matrices | None, [(frames, scores)]) per clip, on the host"""
     g, c, goff, coff = _ragged_inputs(gestures, contents, offsets)
     n = len(goff) - 1
@@ -362,10 +374,10 @@ def _attn_call(gestures, contents, temp, normalize, engine, offsets, want_matrix
     T, W = np.diff(goff), np.diff(coff)
     mats = None
     if want_matrix:
-        A = _host(A)
-        mats = [A[aoff[i]:aoff[i + 1]].reshape(W[i], T[i]) for i in range(n)]
-    bf, bs = _host(bf), _host(bs)
-    return mats, [(bf[coff[i]:coff[i + 1]], bs[coff[i]:coff[i + 1]]) for i in range(n)]
+        A = to_host(A)
+        mats = [A[span(aoff, i)].reshape(W[i], T[i]) for i in range(n)]
+    bf, bs = to_host(bf), to_host(bs)
+    return mats, [(bf[span(coff, i)], bs[span(coff, i)]) for i in range(n)]
 
 
 def attention_matrices(gestures, contents, temp=0.07, normalize=True, engine=None, offsets=None):
@@ -373,14 +385,14 @@ def attention_matrices(gestures, contents, temp=0.07, normalize=True, engine=Non
     evaluate_spotting.py:39-57 (normalize=True: rows L2-normalised first) or of utils/plot_heatmap.py:34-59 (normalize=False: rows as stored).
     Inputs as for spotting_accuracy: lists of per-clip (T_i,512) / (W_i,512) arrays, or the concatenated tensors with
     ``offsets=(g_offsets, c_offsets)``.  One jg_attn_matrix call for the whole batch."""
-    return _attn_call(gestures, contents, temp, normalize, engine, offsets, True)[0]
+    return attn_call(gestures, contents, temp, normalize, engine, offsets, True)[0]
 
 
 def spot_words(gestures, contents, temp=0.07, normalize=True, engine=None, offsets=None):
     """Every word of every clip localised (evaluate_spotting.py:72-73 applied to each row of the attention matrix): per clip
     (frames int32 (W_i,), scores float32 (W_i,)) = first arg-max frame of the word's row and its probability.  The matrix itself is
     not written (jg_attn_matrix with A = NULL)."""
-    return _attn_call(gestures, contents, temp, normalize, engine, offsets, False)[1]
+    return attn_call(gestures, contents, temp, normalize, engine, offsets, False)[1]
 
 
 def sync_offset(vid_feats, aud_feats, max_shift=15, min_overlap=1, engine=None):
@@ -397,15 +409,8 @@ def sync_offset(vid_feats, aud_feats, max_shift=15, min_overlap=1, engine=None):
     if n == 0:
         return np.zeros(0, np.int32), np.zeros(0, np.float32), np.zeros((0, W), np.float32)
     eng = engine or Engine.get()
-    def rows(mats):          # host arrays, or tensors already on the device (the extractors' outputs)
-        return torch.cat([m.to(torch.float32) for m in mats], 0) if isinstance(mats[0], torch.Tensor) else _cat(mats)
-    off, conf, curve = eng.sync_offset(rows(vid_feats), rows(aud_feats), _offsets(vid_feats), _offsets(aud_feats), max_shift, min_overlap)
-    return _host(off), _host(conf), _host(curve)
-
-
-def _rows(mats):
-    """host arrays, or tensors already on the device (the extractors' outputs) -> one (sum rows, D) tensor"""
-    return torch.cat([m.to(torch.float32) for m in mats], 0) if isinstance(mats[0], torch.Tensor) else _cat(mats)
+    off, conf, curve = eng.sync_offset(cat_rows(vid_feats), cat_rows(aud_feats), offsets_of(vid_feats), offsets_of(aud_feats), max_shift, min_overlap)
+    return to_host(off), to_host(conf), to_host(curve)
 
 
 def sync_timeline(vid_feats, aud_feats, win=125, hop=25, max_shift=15, min_overlap=1, audio_of=None, engine=None):
@@ -425,13 +430,13 @@ def sync_timeline(vid_feats, aud_feats, win=125, hop=25, max_shift=15, min_overl
     if not len(aud_feats):
         raise ValueError("no audio track")
     eng = engine or Engine.get()
-    off, conf, curve, w_off, _ = eng.sync_offset_windows(_rows(vid_feats), _rows(aud_feats), _offsets(vid_feats), _offsets(aud_feats),
+    off, conf, curve, w_off, _ = eng.sync_offset_windows(cat_rows(vid_feats), cat_rows(aud_feats), offsets_of(vid_feats), offsets_of(aud_feats),
                                                         a_of=audio_of, max_shift=max_shift, min_overlap=min_overlap, win=win, hop=hop)
-    off, conf, curve = _host(off), _host(conf), _host(curve)
+    off, conf, curve = to_host(off), to_host(conf), to_host(curve)
     out = []
     for i in range(n):
-        lo, hi = int(w_off[i]), int(w_off[i + 1])
-        out.append(dict(start=(np.arange(hi - lo) * (hop if win else 0)).astype(np.int32), offset=off[lo:hi], conf=conf[lo:hi], curve=curve[lo:hi]))
+        w = span(w_off, i)
+        out.append(dict(start=window_starts(w.stop - w.start, win, hop), offset=off[w], conf=conf[w], curve=curve[w]))
     return out
 
 
@@ -446,10 +451,10 @@ def sync_speaker(tracks, audio, win=125, hop=25, max_shift=15, min_overlap=1, en
         return np.zeros(0, np.int32), np.zeros((0, 0), np.float32)
     eng = engine or Engine.get()
     n_win = int(eng.sync_window_counts([max(int(t.shape[0]) for t in tracks)], int(win), int(hop))[0])
-    _, conf, _, _, _ = eng.sync_offset_windows(_rows(tracks), _rows([audio]), _offsets(tracks), _offsets([audio]), a_of=np.zeros(P, np.int64),
+    _, conf, _, _, _ = eng.sync_offset_windows(cat_rows(tracks), cat_rows([audio]), offsets_of(tracks), offsets_of([audio]), a_of=np.zeros(P, np.int64),
                                                  max_shift=max_shift, min_overlap=min_overlap, win=win, hop=hop, n_windows=[n_win] * P,
                                                  want_curve=False)
-    conf = _host(conf).reshape(P, n_win).T.copy()
+    conf = to_host(conf).reshape(P, n_win).T.copy()
     none = np.isnan(conf).all(axis=1)
     speaker = np.where(none, -1, np.argmax(np.where(np.isnan(conf), -np.inf, conf), axis=1)).astype(np.int32)
     return speaker, conf
@@ -468,15 +473,10 @@ def asd_accuracy(query_content, candidate_gestures, engine=None):
     eng = engine or Engine.get()
     counts = [0, 0, 0, 0]
     if len(candidate_gestures):
-        cand = torch.cat([_tensor(c).to(eng.device) for c in candidate_gestures], 0)
-        counts = asd_counts(eng.asd(_tensor(query_content), cand, _offsets(candidate_gestures)).cpu().numpy())
+        counts = asd_counts(eng.asd(cat_rows(query_content), cat_rows(candidate_gestures), offsets_of(candidate_gestures)).cpu().numpy())
     c2, c4, c6, n = reduce_counts(counts, eng.device)
     n = max(1, n)
     return c2 / n, c4 / n, c6 / n
-
-
-def _cat(mats):
-    return torch.as_tensor(np.concatenate([np.asarray(m, np.float32) for m in mats], 0))
 
 
 def asd_scores(contents, candidates, temp=0.07, engine=None):
@@ -491,18 +491,19 @@ def asd_scores(contents, candidates, temp=0.07, engine=None):
     tracks = [t for cands in candidates for t in cands]
     s_off = np.zeros(len(candidates) + 1, np.int64)
     s_off[1:] = np.cumsum([len(cands) for cands in candidates])
-    prob, p_off, pred, _, _ = eng.asd_windows(_cat(tracks), _offsets(tracks), _cat(contents), _offsets(contents), np.arange(len(tracks)),
+    prob, p_off, pred, _, _ = eng.asd_windows(cat_rows(tracks), offsets_of(tracks), cat_rows(contents), offsets_of(contents), np.arange(len(tracks)),
                                               s_off, win=0, temp=temp)
-    prob, pred = _host(prob), _host(pred)
-    return [(prob[p_off[i]:p_off[i + 1]], int(pred[i])) for i in range(len(contents))]
+    prob, pred = to_host(prob), to_host(pred)
+    return [(prob[span(p_off, i)], int(pred[i])) for i in range(len(contents))]
 
 
-def _bounds(wb):
-    """word boundaries of one scene -> (start, end) int arrays: [word, start, end] triplets (or their repr, as the csv rows hold them)
-    or (start, end) pairs"""
-    wb = ast.literal_eval(wb) if isinstance(wb, str) else wb
-    se = [(b[-2], b[-1]) for b in wb]
-    return np.asarray([b[0] for b in se], np.int64), np.asarray([b[1] for b in se], np.int64)
+def batch_bounds(word_boundaries, contents, names=None):
+    """the word boundaries of every item of a batch, each checked against its content rows (names: what to call the items in the message)
+    -> the concatenated (start, end)"""
+    se = [word_bounds(wb)[1:] for wb in word_boundaries]
+    for i, ((s, _), c) in enumerate(zip(se, contents)):
+        check_word_count(len(s), len(c), None if names is None else names[i])
+    return np.concatenate([s for s, _ in se]), np.concatenate([e for _, e in se])
 
 
 def asd_timeline(contents, word_boundaries, tracks, win=25, hop=5, temp=0.07, engine=None):
@@ -522,19 +523,15 @@ def asd_timeline(contents, word_boundaries, tracks, win=25, hop=5, temp=0.07, en
     flat = [t for scene in tracks for t in scene]
     s_off = np.zeros(len(tracks) + 1, np.int64)
     s_off[1:] = np.cumsum([len(scene) for scene in tracks])
-    se = [_bounds(wb) for wb in word_boundaries]
-    for (s, _), c in zip(se, contents):
-        if len(s) != len(c):
-            raise ValueError("{} word boundaries for {} content rows".format(len(s), len(c)))
-    prob, p_off, pred, w_off, _ = eng.asd_windows(_cat(flat), _offsets(flat), _cat(contents), _offsets(contents), np.arange(len(flat)), s_off,
-                                                  win=win, hop=hop, word_start=np.concatenate([s for s, _ in se]),
-                                                  word_end=np.concatenate([e for _, e in se]), temp=temp)
-    prob, pred = _host(prob), _host(pred)
+    start, end = batch_bounds(word_boundaries, contents)
+    prob, p_off, pred, w_off, _ = eng.asd_windows(cat_rows(flat), offsets_of(flat), cat_rows(contents), offsets_of(contents), np.arange(len(flat)), s_off,
+                                                  win=win, hop=hop, word_start=start, word_end=end, temp=temp)
+    prob, pred = to_host(prob), to_host(pred)
     out = []
     for i, scene in enumerate(tracks):
-        n_win = int(w_off[i + 1] - w_off[i])
-        out.append(dict(start=(np.arange(n_win) * hop).astype(np.int32), prob=prob[p_off[i]:p_off[i + 1]].reshape(n_win, len(scene)),
-                        pred=pred[w_off[i]:w_off[i + 1]]))
+        w = span(w_off, i)
+        n_win = w.stop - w.start
+        out.append(dict(start=window_starts(n_win, win, hop), prob=prob[span(p_off, i)].reshape(n_win, len(scene)), pred=pred[w]))
     return out[0] if single else out
 
 
@@ -547,20 +544,16 @@ def _talk_call(gesture, content, word_boundaries, reach, temp, normalize, engine
         raise ValueError("one content array and one list of word boundaries per track")
     if not len(gesture):
         return []
-    se = [_bounds(wb) for wb in word_boundaries]
-    for (s, _), c in zip(se, content):
-        if len(s) != len(c):
-            raise ValueError("{} word boundaries for {} content rows".format(len(s), len(c)))
+    start, end = batch_bounds(word_boundaries, content)
     eng = engine or Engine.get()
-    goff, coff = _offsets(gesture).astype(np.int64), _offsets(content).astype(np.int64)
-    start, end = np.concatenate([s for s, _ in se]), np.concatenate([e for _, e in se])
-    band, bf, bs, fw, fp = eng.attn_talk(_rows(gesture), _rows(content), goff, coff, start, end, reach=reach, temp=temp, normalize=normalize,
+    goff, coff = offsets_of(gesture).astype(np.int64), offsets_of(content).astype(np.int64)
+    band, bf, bs, fw, fp = eng.attn_talk(cat_rows(gesture), cat_rows(content), goff, coff, start, end, reach=reach, temp=temp, normalize=normalize,
                                          want_band=want_band)
-    bf, bs, fw, fp = _host(bf), _host(bs), _host(fw), _host(fp)
-    band = _host(band) if want_band else None
+    bf, bs, fw, fp = to_host(bf), to_host(bs), to_host(fw), to_host(fp)
+    band = to_host(band) if want_band else None
     out = []
     for i in range(len(gesture)):
-        w, f = slice(int(coff[i]), int(coff[i + 1])), slice(int(goff[i]), int(goff[i + 1]))
+        w, f = span(coff, i), span(goff, i)
         d = dict(best_frame=bf[w], best_score=bs[w], frame_word=fw[f], frame_prob=fp[f])
         if want_band:
             d.update(first_frame=(start[w] - int(reach)).astype(np.int32), band=band[w])
@@ -605,12 +598,10 @@ def talk_words(utterances, starts):
         if u.get("content_emb") is None:
             raise ValueError("utterance {} holds no content_emb".format(int(i)))
         c = np.asarray(u["content_emb"], np.float32)
-        wb = u["info"]["word_boundaries"]
-        wb = ast.literal_eval(wb) if isinstance(wb, str) else wb
-        if len(wb) != len(c):
-            raise ValueError("utterance {}: {} word boundaries for {} content rows".format(int(i), len(wb), len(c)))
+        words, s, e = word_bounds(u["info"]["word_boundaries"])
+        check_word_count(len(words), len(c), "utterance {}".format(int(i)))
         rows.append(c)
-        bounds += [[str(b[0]), int(b[-2]) + int(starts[i]), int(b[-1]) + int(starts[i])] for b in wb]
+        bounds += [[w, int(a) + int(starts[i]), int(b) + int(starts[i])] for w, a, b in zip(words, s, e)]
     s, e = np.asarray([b[1] for b in bounds], np.int64), np.asarray([b[2] for b in bounds], np.int64)
     if (np.diff(s) < 0).any() or (np.diff(e) < 0).any() or (s > e).any():
         raise ValueError("the utterances overlap out of order: the shifted word boundaries are not non-decreasing")

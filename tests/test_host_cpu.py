@@ -578,3 +578,33 @@ def test_importing_the_package_does_not_touch_the_environment():
             "os.environ['GPU_MAX_HW_QUEUES'] = '1'; assert jegal_amd.want_hw_queues() == '1'; print('ok')")
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, cwd=ROOT, timeout=120)
     assert r.returncode == 0 and r.stdout.strip() == "ok", r.stderr
+
+
+def test_run_groups_retries_a_failed_group_item_by_item(capsys):
+    """The loop extract_gestsync_feats and embed_tracks share (drivers._run_groups), without an engine: a group that raises is run again
+    item by item, so the neighbours of a bad item are saved and the bad item is counted once; a group of one that fails is counted and not
+    run again; a save that raises is counted and the loop goes on."""
+    from jegal_amd.drivers import _run_groups
+    items = {name: (i, name, name + ".out") for i, name in enumerate(["a", "b", "BAD", "c", "ALONE", "d", "UNSAVABLE", "e"])}
+    groups = [[items[n] for n in g] for g in (["a", "b", "BAD", "c"], ["ALONE"], ["d", "UNSAVABLE", "e"])]
+    calls, saves = [], {}
+
+    def run_group(group):
+        calls.append([name for _, name, _ in group])
+        if any(name in ("BAD", "ALONE") for _, name, _ in group):
+            raise RuntimeError("cannot run " + "+".join(calls[-1]))
+        return [name.upper() for _, name, _ in group]
+
+    def save(result, item):
+        if item[1] == "UNSAVABLE":
+            raise OSError("disk full")
+        saves[item[2]] = result
+
+    saved, err = _run_groups(groups, run_group, save, "Thing")
+    assert (saved, err) == (5, 3)
+    assert saves == {"a.out": "A", "b.out": "B", "c.out": "C", "d.out": "D", "e.out": "E"}          # the neighbours of every bad item
+    assert calls == [["a", "b", "BAD", "c"], ["a"], ["b"], ["BAD"], ["c"],          # the group, then its items: BAD raises once more, counted once
+                     ["ALONE"],                                                      # a group of one is not retried
+                     ["d", "UNSAVABLE", "e"]]                                        # a failed save does not run anything again
+    lines = [l for l in capsys.readouterr().out.splitlines() if l.startswith("Error: ")]
+    assert lines == ["Error:  cannot run BAD  | Thing:  BAD", "Error:  cannot run ALONE  | Thing:  ALONE", "Error:  disk full  | Thing:  UNSAVABLE"]
