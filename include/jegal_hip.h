@@ -603,6 +603,39 @@ int jg_sim_search(jg_handle* h, const float* queries, int n_queries, const void*
  * *rows_per_slice = R, *ws_bytes = S n_queries k 8 (0 when S == 1: one slice writes no lists).  JG_ERR_ARG where jg_sim_search refuses
  * the counts (negative ones, k outside 1..128, slices_in > 1024, lists beyond 64 MiB). */
 int jg_debug_search_plan(int n_queries, int n_gallery, int k, int num_cu, int slices_in, int* slices, int* rows_per_slice, int64_t* ws_bytes);
+/* Coupling (late interaction, MaxSim): rank groups of gallery rows (clips of frames) for queries of several word rows, every word by its
+ * best row in the group, without the (all words) x (all rows) matrix.
+ * words [n_words][D] fp32; w_offsets_host [n_queries + 1], a HOST array: query q owns word rows w_offsets[q] .. w_offsets[q + 1] - 1.
+ * gallery [n_gallery][D] of gallery_dtype (JG_F32 | JG_F16, as jg_sim_search); g_offsets [n_groups + 1], a DEVICE array with the meaning and
+ * the safety rule of jg_sim_topk_grouped: read at 0 .. n_groups only, only ever compared with row numbers, the gallery is never addressed
+ * through it; offsets that are no non-decreasing partition give an unspecified result, never an access outside the operands.
+ * The score: s(w, t) = <words[w], gallery[t]> with the bits jg_sim_topk gives for the gallery widened to fp32; -0.0 counts as +0.0; a NaN s
+ * is skipped.  m(w, g) = the max of the non-NaN s(w, t) over the rows of group g, none if there is no such row.  score(q, g): none if any
+ * word of q has no m (NaN in `pair`, never a candidate); else the m(w, g) added in fp32 in ascending word order, one sequential chain,
+ * divided by (float)W_q with a correctly rounded fp32 division.  A score depends on the rows of its query and its group only: not on
+ * slices, tiles, k or what else is in the call.
+ * idx / score [n_queries][k]: group_offset + g, best first: the larger score, on equal scores the smaller group; -1 / -inf where there are
+ * fewer.  merge as for jg_sim_topk_grouped: pieces cut at group boundaries with disjoint group_offset ranges leave, in any order, the bits
+ * of one call.
+ * pair (optional, NULL to skip): the dense scores, GROUP-major: pair[g * pair_ld + q], pair_ld >= n_queries, g a local group of this call.
+ * The entry first fills pair[g][0 .. n_queries) with NaN for every local group (a launch of its own on the handle's stream); the kernel
+ * stores the pairs that have a score.  Nothing outside those entries and the n_queries * k entries of idx / score is written.
+ * slices as for jg_sim_search (jg_debug_coupling_plan): a slice owns the groups that BEGIN in its rows and walks on until the last ends.
+ * Limits: 1..64 word rows per query; 1 <= k <= 128; D > 0, D % 64 == 0; words and gallery 16-byte aligned; w_offsets_host[0] == 0 and
+ * non-decreasing; counts >= 0; group_offset >= 0, group_offset + n_groups <= INT32_MAX; 0 <= slices <= 1024, the lists (S n_queries k 8
+ * bytes) at most 64 MiB when S > 1.  A violated limit, a null buffer or another dtype returns JG_ERR_ARG before anything is enqueued or
+ * written.  n_queries == 0 returns JG_OK and launches nothing; n_gallery == 0 or n_groups == 0 fills -1 / -inf without merge and keeps the
+ * lists with it, pair stays NaN.  The two host tables go to this call's workspace pass.  jg_debug_last_kernel names the coupling launch
+ * ("a+b" with the reduction of more than one slice; the NaN fill is not named).  Asynchronous. */
+int jg_sim_coupling(jg_handle* h, const float* words, const int32_t* w_offsets_host, int n_queries, const void* gallery,
+                    int gallery_dtype /* JG_F32 | JG_F16 */, int n_gallery, int D, int k, const int32_t* g_offsets /* device */, int n_groups,
+                    int group_offset, int merge, int slices /* 0: the library chooses */, int32_t* idx, float* score,
+                    float* pair /* optional */, int64_t pair_ld);
+/* The plan jg_sim_coupling makes: no handle, no device.  Queries are packed in order into tiles of at most 64 word rows, never split;
+ * tile_first_query (room for n_queries + 1) [i] = first query of tile i, [*n_tiles] = n_queries.  The cut is jg_debug_search_plan's with the
+ * query tiles in place of the query blocks; *ws_bytes = S n_queries k 8 (0 when S == 1).  JG_ERR_ARG where jg_sim_coupling refuses. */
+int jg_debug_coupling_plan(const int32_t* w_offsets_host, int n_queries, int n_gallery, int k, int num_cu, int slices_in,
+                           int32_t* tile_first_query, int* n_tiles, int* slices, int* rows_per_slice, int64_t* ws_bytes);
 /* The rows jg_sim_topk_grouped returns, back to (group, position inside the group), on the device: grp[e] = the group whose range holds
  * idx[e] - gallery_offset, pos[e] = the row's offset inside it; both -1 for idx[e] < 0 or a row in no group.  An element-wise binary
  * search over g_offsets (device, [n_groups + 1]); a caller of merged calls passes its global offsets with gallery_offset = 0.  n, n_groups,

@@ -136,6 +136,8 @@ _SIGS = {
     "jg_sim_topk_grouped": [_P, _P, _P, _I, _I, _I, _I, _P, _I, _I, _I, _P, _P],
     "jg_sim_search": [_P, _P, _I, _P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _P, _P],
     "jg_debug_search_plan": [_I, _I, _I, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(ctypes.c_int64)],
+    "jg_sim_coupling": [_P, _P, _P, _I, _P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _P, _P, _P, ctypes.c_int64],
+    "jg_debug_coupling_plan": [_P, _I, _I, _I, _I, _I, _P, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(ctypes.c_int64)],
     "jg_group_of_rows": [_P, _P, _L, _P, _I, _I, _P, _P],
     "jg_spot": [_P, _P, _P, _P, _P, _P, _I, _I, ctypes.c_float, _P, _P],
     "jg_attn_matrix": [_P, _P, _P, _P, _P, _I, _I, _I, ctypes.c_float, _I, _P, _P, _P, _P],
@@ -217,6 +219,22 @@ def search_plan(n_queries, n_gallery, k, num_cu=256, slices=0):
     if rc != 0:
         raise JegalError(f"jg_debug_search_plan: bad arguments ({rc})", rc)
     return s.value, r.value, b.value
+
+
+def coupling_plan(w_offsets, n_gallery, k, num_cu=256, slices=0):
+    """The plan jg_sim_coupling makes (jg_debug_coupling_plan) for queries of the word rows w_offsets (queries + 1 host entries) ->
+    (tile_first_query: int32 array of tiles + 1 entries, slices, rows per slice, bytes of the slices' lists).  Needs no Engine and no
+    GPU; JegalError where jg_sim_coupling refuses the offsets or the counts."""
+    import numpy as np
+    off = np.ascontiguousarray(np.asarray(w_offsets).reshape(-1), np.int32)
+    tfq = np.zeros(max(off.size, 1), np.int32)
+    t, s, r, b = _I(), _I(), _I(), ctypes.c_int64()
+    rc = load_library().jg_debug_coupling_plan(off.ctypes.data_as(_P) if off.size else None, off.size - 1, int(n_gallery), int(k), int(num_cu),
+                                               int(slices), tfq.ctypes.data_as(_P), ctypes.byref(t), ctypes.byref(s), ctypes.byref(r),
+                                               ctypes.byref(b))
+    if rc != 0:
+        raise JegalError(f"jg_debug_coupling_plan: bad arguments ({rc})", rc)
+    return tfq[:t.value + 1].copy(), s.value, r.value, b.value
 
 
 WEIGHT_FORMS = ["single", "split", "bias_corrected", "runtime_corrected"]      # enum WeightForm (jegal_amd/csrc/weight_form.h)

@@ -8,6 +8,7 @@ import torch
 # The limits the C entries refuse on, named as in csrc/shared.h (tests/test_metric_entries_cpu.py keeps the two equal).
 SIM_TOPK_MAX_K = 128
 SIM_SEARCH_MAX_SLICES, SIM_SEARCH_MAX_WS = 1024, 64 << 20
+COUPLING_MAX_W = 64
 SPOT_MAX_W, SPOT_MAX_T = 1024, 8192
 SYNC_MAX_R, SYNC_MAX_T, SYNC_MAX_D = 64, 8192, 1024
 SYNCW_MAX_T, SYNCW_MAX_WINDOWS, SYNCW_MAX_BAND_LOG2 = 1 << 20, 1 << 20, 40
@@ -180,6 +181,47 @@ class MetricEntries:
             self._ck(self.lib.jg_sim_search(self.h, _ptr(q), n, _ptr(g), 1 if g.dtype == torch.float16 else 0, m, D, k, _ptr(off), n_groups or 0,
                                             gallery_offset, int(merge_into is not None), slices, _ptr(idx), _ptr(score)))
         return idx, score
+
+    def sim_coupling(self, words, w_offsets, gallery, g_offsets, k, group_offset=0, merge_into=None, slices=0, want_matrix=False):
+        """jg_sim_coupling (late interaction): query q = the word rows w_offsets[q] .. w_offsets[q + 1] - 1 of `words` (a HOST array of
+        queries + 1 entries, 1..64 rows each), group g = the rows g_offsets[g] .. g_offsets[g + 1] - 1 of `gallery` (float32 or float16 rows;
+        a host array or a tensor of groups + 1 entries).  A group scores as the mean over the query's words of each word's best row in it
+        (rows as stored: normalise first); per query the k best groups come back: (idx (n, k) int32 = group_offset + g, score (n, k)
+        float32), device tensors, best first, on equal scores the smaller group, -1 / -inf where fewer groups have a score.  A score's bits
+        depend on its query's and its group's rows only.  merge_into = (idx, score) of an earlier call with the same queries and k on OTHER
+        groups (group_offset): updated in place to the best k of the union.  slices as for sim_search.  want_matrix: also the
+        (n, groups) matrix of all scores of this call (NaN where a pair has none), a transposed view of the group-major buffer."""
+        dtype = getattr(gallery, "dtype", None)
+        if dtype not in (torch.float32, torch.float16, np.dtype(np.float32), np.dtype(np.float16)):
+            raise ValueError("gallery must be a float32 or float16 tensor or array")
+        slices, group_offset = int(slices), int(group_offset)
+        if not 0 <= slices <= SIM_SEARCH_MAX_SLICES:
+            raise ValueError(f"jg_sim_coupling limit: 0 <= slices <= {SIM_SEARCH_MAX_SLICES} (0: the library chooses)")
+        ws, gs = _row_pair(words, gallery, "words / gallery")
+        woh = _offsets(w_offsets, ws[0], "w_offsets")
+        if woh[0] != 0:
+            raise ValueError("w_offsets must start at 0")
+        _within(np.diff(woh), 1, COUPLING_MAX_W, "jg_sim_coupling limits: word rows per query")
+        n = woh.size - 1
+        n_groups = len(_offsets(g_offsets, gs[0], "g_offsets", host=False)) - 1
+        if group_offset < 0 or group_offset + n_groups > INT32_MAX:
+            raise ValueError("group_offset must be >= 0 and group_offset + groups <= INT32_MAX")
+        if slices and 1 <= int(k) <= SIM_TOPK_MAX_K and gs[0] <= INT32_MAX:
+            from ._lib import JegalError, coupling_plan    # (the planner is a host function of the library: no handle, no device)
+            try:
+                coupling_plan(woh, gs[0], int(k), slices=slices)
+            except JegalError:
+                raise ValueError(f"jg_sim_coupling limit: {slices} slices of {n} x {int(k)} keys exceed {SIM_SEARCH_MAX_WS} bytes") from None
+        # k and merge_into as the top-k entries check them, with one row of the result per QUERY: (n, D) stands for the queries
+        _, m, D, k, _, _, idx, score = self._sim_topk_args("sim_coupling", np.broadcast_to(np.float32(0), (n, ws[1])), gallery, k, 0, merge_into)
+        w, g, off = self._f32(words), torch.as_tensor(gallery, device=self.device).contiguous(), self._i32(g_offsets)
+        pair = torch.full((n_groups, n), float("nan"), dtype=torch.float32, device=self.device) if want_matrix else None
+        if n and m and n_groups:                       # (no gallery row, no group: nothing to merge, or the empty result)
+            wo = np.ascontiguousarray(woh, np.int32)
+            self._ck(self.lib.jg_sim_coupling(self.h, _ptr(w), wo.ctypes.data_as(ctypes.c_void_p), n, _ptr(g),
+                                              1 if g.dtype == torch.float16 else 0, m, D, k, _ptr(off), n_groups, group_offset,
+                                              int(merge_into is not None), slices, _ptr(idx), _ptr(score), _ptr(pair), n))
+        return (idx, score, pair.t()) if want_matrix else (idx, score)
 
     def group_of_rows(self, idx, g_offsets, gallery_offset=0):
         """jg_group_of_rows: the rows sim_topk_grouped returned (an int32 tensor of any shape) -> (grp, pos) int32 device tensors of that

@@ -612,6 +612,41 @@ int jg_sim_search(jg_handle* h, const float* queries, int n_queries, const void*
     return rc;
 }
 
+int jg_sim_coupling(jg_handle* h, const float* words, const int32_t* w_offsets_host, int n_queries, const void* gallery, int gallery_dtype,
+                    int n_gallery, int D, int k, const int32_t* g_offsets, int n_groups, int group_offset, int merge, int slices, int32_t* idx,
+                    float* score, float* pair, int64_t pair_ld) {
+    if (!h) return JG_ERR_ARG;
+    const KernelNameScope kn(h->kname);          // the launch depends on the plan, as in jg_sim_search
+    ENTER(h);
+    if (!words || !w_offsets_host || !gallery || !idx || !score || (n_groups > 0 && !g_offsets)) JG_FAIL(h, JG_ERR_ARG, "null buffer");
+    if (gallery_dtype != JG_F32 && gallery_dtype != JG_F16) JG_FAIL(h, JG_ERR_ARG, "gallery_dtype must be JG_F32 or JG_F16");
+    // (the check of the top-k entries, with the groups as what group_offset numbers)
+    RET(sim_topk_check(h, "sim_coupling", words, static_cast<const float*>(gallery), n_queries, n_gallery, D, k, n_groups, 0));
+    if (group_offset < 0 || group_offset > INT32_MAX - n_groups) JG_FAIL(h, JG_ERR_ARG, "group_offset >= 0, group_offset + n_groups <= INT32_MAX");
+    if (pair && (pair_ld < n_queries || (reinterpret_cast<uintptr_t>(pair) & 3))) JG_FAIL(h, JG_ERR_ARG, "pair needs pair_ld >= n_queries");
+    const bool no_rows = n_gallery == 0 || n_groups == 0;
+    std::vector<int32_t> tables((size_t)n_queries * 2 + 2);      // w_offsets [n_queries + 1], then tile_first_query [n_tiles + 1]
+    int32_t* const tfq_host = tables.data() + n_queries + 1;
+    CouplingPlan plan;
+    if (!sim_coupling_plan(w_offsets_host, n_queries, no_rows ? 0 : n_gallery, k, h->opts.num_cu, slices, tfq_host, plan))
+        JG_FAIL(h, JG_ERR_ARG, "w_offsets must start at 0 and give every query 1..%d word rows; slices must be 0 (the library chooses) .. %d, and "
+                "the slices' lists (slices x n_queries x k x 8 bytes) at most %d bytes", COUPLING_MAX_W, SIM_SEARCH_MAX_SLICES, SIM_SEARCH_MAX_WS);
+    if (n_queries == 0) return JG_OK;
+    std::memcpy(tables.data(), w_offsets_host, ((size_t)n_queries + 1) * sizeof(int32_t));
+    RET(begin_pass(h));
+    int32_t* tables_dev = nullptr;
+    unsigned long long* keys = nullptr;
+    RET(wsalloc(h, tables.size(), &tables_dev));
+    if (plan.cut.slices > 1) RET(wsalloc(h, (size_t)(plan.cut.ws_bytes / 8), &keys));
+    RET(upload_i32_async(h, tables.data(), (size_t)n_queries + 1 + plan.n_tiles + 1, tables_dev));
+    if (pair) RET(misc_launch(h, launch_coupling_fill, pair, (long)pair_ld, n_queries, n_groups));
+    const int rc = misc_launch(h, launch_sim_coupling, words, tables_dev, tables_dev + n_queries + 1, plan.n_tiles, gallery, gallery_dtype == JG_F16,
+                               n_queries, n_gallery, D, k, g_offsets, n_groups, group_offset, merge, idx, score, pair, (long)pair_ld,
+                               plan.cut.slices, plan.cut.slice_rows, keys);
+    if (rc != JG_OK) h->kname[0] = 0;
+    return rc;
+}
+
 int jg_group_of_rows(jg_handle* h, const int32_t* idx, int64_t n, const int32_t* g_offsets, int n_groups, int gallery_offset,
                      int32_t* grp, int32_t* pos) {
     ENTER(h);

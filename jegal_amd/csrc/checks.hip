@@ -662,6 +662,19 @@ int jg_debug_search_plan(int n_queries, int n_gallery, int k, int num_cu, int sl
     return JG_OK;
 }
 
+int jg_debug_coupling_plan(const int32_t* w_offsets_host, int n_queries, int n_gallery, int k, int num_cu, int slices_in, int32_t* tile_first_query,
+                           int* n_tiles, int* slices, int* rows_per_slice, int64_t* ws_bytes) {
+    CouplingPlan p;
+    if (!n_tiles || !slices || !rows_per_slice || !ws_bytes ||
+        !sim_coupling_plan(w_offsets_host, n_queries, n_gallery, k, num_cu, slices_in, tile_first_query, p))
+        return JG_ERR_ARG;
+    *n_tiles = p.n_tiles;
+    *slices = p.cut.slices;
+    *rows_per_slice = p.cut.slice_rows;
+    *ws_bytes = p.cut.ws_bytes;
+    return JG_OK;
+}
+
 int jg_debug_last_kernel(jg_handle* h, char* buf, int len) {
     if (!h || !buf || len <= 0) return JG_ERR_ARG;
     snprintf(buf, (size_t)len, "%s", h->kname);

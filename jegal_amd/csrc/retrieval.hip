@@ -397,6 +397,191 @@ hipError_t launch_sim_search(const float* queries, const void* gallery, bool gal
 #undef SEARCH
 }
 
+// ---------------------------------------------------------------------------------------------
+// Coupling (late interaction, jg_sim_coupling): query q = word rows woff[q] .. woff[q + 1] - 1, group g = gallery rows goff[g] ..
+// goff[g + 1] - 1; m(w, g) = the largest non-NaN <word w, row t> over the group's rows (-0.0 as +0.0), score(q, g) = (the m(w, g) added in
+// word order, one fp32 chain) / W_q, and per query the k best groups.  A pair with a word that has no m has no score.  The max is exact and
+// the chain's order is fixed, so a score depends on the rows of its query and its group alone, not on tiles, slices or the rest of the call.
+//
+// Workgroup (x, y): query tile x (tfq[x] .. tfq[x + 1] - 1: whole queries, at most 64 word rows together -- sim_coupling_plan) and the
+// groups whose first row lies in slice y = [y slice_rows, (y + 1) slice_rows).  It walks the 64-row-aligned gallery tiles that hold a column
+// of such a group, on past the slice's end until the last of them ends: a group is never split between workgroups, and the tiles are the
+// same for every cut.  Inside a tile a group's columns are one segment [b, e): every thread masks its column, 5 shuffle / max steps leave a
+// row's max over a wave's 32 columns in the row's first lane, the two column waves meet in sPart, and sRun keeps the max per word row while
+// the group goes on into the next tile.  NaN stands for "none" throughout: fmaxf returns the other operand.  When a group ends, thread
+// i < (queries of the tile) adds the maxima of query i's rows, divides, stores the pair and queues the key for topk_flush with "row" =
+// query of the tile.  The segments of a tile are disjoint (`pos`: the first column not yet consumed, whatever the offsets hold) and only a
+// group with a column queues a key, so at most 64 keys per query and tile: the queue cannot overflow.
+// goff is only read at 0 .. n_groups and only compared with row numbers; hostile offsets give some result and nothing else.
+__global__ void coupling_fill_kernel(float* __restrict__ pair, long pair_ld, int n_queries, int n_groups) {
+    const long n = (long)n_queries * n_groups;
+    for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long)gridDim.x * blockDim.x)
+        pair[(e / n_queries) * pair_ld + e % n_queries] = __uint_as_float(0x7fc00000u);
+}
+
+template <class GT, int LCAP>
+__global__ __launch_bounds__(256) void sim_coupling_kernel(const float* __restrict__ words, const int32_t* __restrict__ woff,
+                                                           const int32_t* __restrict__ tfq, const GT* __restrict__ gallery, int n_queries,
+                                                           int n_gallery, int D, int k, const int32_t* __restrict__ goff, int n_groups,
+                                                           int group_offset, int merge, int32_t* __restrict__ idx, float* __restrict__ score,
+                                                           float* __restrict__ pair, long pair_ld, int slice_rows, u64* __restrict__ keys) {
+    __shared__ __attribute__((aligned(16))) u64 sStage[64 * 64];       // staging (sA, sB) during a tile's k loop, the queues after it
+    __shared__ u64 sL[64][LCAP];
+    __shared__ u64 sThr[64];
+    __shared__ int sCnt[64];
+    __shared__ float sPart[2][64];                                     // a segment's max per word row, of either column wave
+    __shared__ float sRun[64];                                         // the open group's max per word row so far
+    __shared__ int sW[65];                                             // the tile's queries as word rows of the tile
+    float (*sA)[64] = reinterpret_cast<float (*)[64]>(sStage);
+    float (*sB)[64] = sA + 64;
+    u64 (*sQ)[64] = reinterpret_cast<u64 (*)[64]>(sStage);             // [query of the tile][slot]
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int q0 = tfq[blockIdx.x], q1 = tfq[blockIdx.x + 1], nq = q1 - q0;
+    const int row0 = woff[q0], row1 = woff[q1];
+    if (tid <= nq) sW[tid] = woff[q0 + tid] - row0;
+    topk_seed<LCAP>(sL, sCnt, sThr, k, wave, lane, q0, q1, merge, idx, score);
+
+    // the first group this slice owns (g, rows [lo, hi)); n_groups: none
+    const long lim_lo = (long)blockIdx.y * slice_rows, lim_hi = lim_lo + slice_rows;
+    int g = n_groups, lo = 0, hi = 0;
+    if (n_groups > 0 && lim_lo < n_gallery) {
+        if (lim_lo <= goff[0]) {
+            g = 0; lo = goff[0]; hi = goff[1];
+        } else if (lim_lo < goff[n_groups]) {
+            g = group_range(goff, n_groups, (int)lim_lo, lo, hi);
+            if (lo != lim_lo) { ++g; lo = hi; hi = g < n_groups ? goff[g + 1] : lo; }      // it began before the slice: another's
+        }
+    }
+    auto next_group = [&] { ++g; lo = hi; if (g < n_groups) hi = goff[g + 1]; };
+    auto flush = [&] {
+        __syncthreads();
+        topk_flush<LCAP, false>(sL, sQ, sCnt, sThr, k, wave, lane, nullptr, 0, 0u);
+    };
+
+    int pos = (int)(lim_lo < n_gallery ? lim_lo : n_gallery);      // columns below it are consumed (or another slice's)
+    int j0 = -64;                                                    // the tile in acc: none yet
+    bool queued = false;                                             // a group has ended in this tile
+    f32x16 acc;
+#pragma unroll
+    for (int x = 0; x < 16; ++x) acc[x] = 0.f;
+    __syncthreads();                                                 // sW and the seeded lists
+    for (;;) {
+        // the next owned group with a column; a group without one has no score
+        while (g < n_groups && lo < lim_hi && (hi < n_gallery ? hi : n_gallery) <= (lo > pos ? lo : pos)) next_group();
+        if (g >= n_groups || lo >= lim_hi) break;
+        int b = lo > pos ? lo : pos;
+        const int e = hi < n_gallery ? hi : n_gallery;               // its columns [b, e), b < e
+        bool first = true;
+        for (;;) {                                                   // its segments, one per tile
+            if (b >= (long)j0 + 64) {
+                if (queued) { flush(); queued = false; }
+                j0 = b & ~63;
+                acc = sim_tile(words, gallery, row0, j0, row1, n_gallery, D, sA, sB, tid);
+            }
+            const int se = e < (long)j0 + 64 ? e : j0 + 64;                  // (long: the last tile of 2^31 - 1 rows ends past INT32_MAX)
+            const long col = (long)j0 + sim_tile_col(tid);
+            const bool in = col >= b && col < se;
+#pragma unroll
+            for (int x = 0; x < 16; ++x) {
+                float v = in ? (acc[x] == 0.f ? 0.f : acc[x]) : __uint_as_float(0x7fc00000u);
+#pragma unroll
+                for (int o = 16; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+                if ((lane & 31) == 0) sPart[wave >> 1][sim_tile_row(x, tid)] = v;
+            }
+            __syncthreads();
+            if (tid < 64) {
+                const float m = fmaxf(sPart[0][tid], sPart[1][tid]);
+                sRun[tid] = first ? m : fmaxf(sRun[tid], m);
+            }
+            first = false;
+            b = se;
+            if (b >= e) break;
+        }
+        // the group has ended: query i of the tile, by thread i
+        __syncthreads();
+        if (tid < nq) {
+            const int w0 = sW[tid], w1 = sW[tid + 1];
+            float sum = 0.f;
+            bool all = true;
+            for (int r = w0; r < w1; ++r) {
+                const float m = sRun[r];
+                all = all && m == m;
+                sum += m;
+            }
+            const float sc = __fdiv_rn(sum, (float)(w1 - w0));
+            if (all) {
+                if (pair) pair[(long)g * pair_ld + q0 + tid] = sc;
+                const u64 key = topk_key(sc, (unsigned)group_offset + (unsigned)g);
+                if (sc == sc && key > sThr[tid]) sQ[tid][sCnt[tid]++] = key;
+            }
+        }
+        queued = true;
+        pos = e;
+        next_group();
+    }
+    if (queued) flush();
+    // a wave stores the lists of the queries it seeded and flushed itself
+    if (keys) {
+        for (int rr = 0; rr < 16; ++rr) {
+            const int row = wave * 16 + rr;
+            if (row >= nq) break;
+            const long base = ((long)blockIdx.y * n_queries + q0 + row) * k;
+            for (int p = lane; p < k; p += 64) keys[base + p] = sL[row][p];
+        }
+    } else {
+        topk_store<LCAP>(sL, k, wave, lane, q0, q1, idx, score);
+    }
+}
+
+hipError_t launch_coupling_fill(float* pair, long pair_ld, int n_queries, int n_groups, hipStream_t s) {
+    const long n = (long)n_queries * n_groups;
+    if (n <= 0) return hipSuccess;
+    if (!pair || pair_ld < n_queries) return hipErrorInvalidValue;
+    const long blocks = (n + 255) / 256;
+    hipLaunchKernelGGL(coupling_fill_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, s, pair, pair_ld, n_queries, n_groups);
+    return hipGetLastError();
+}
+
+template <class GT>
+static hipError_t launch_coupling(const float* words, const int32_t* woff, const int32_t* tfq, int n_tiles, const GT* gallery, int n_queries,
+                                  int n_gallery, int D, int k, const int32_t* g_offsets, int n_groups, int group_offset, int merge, int32_t* idx,
+                                  float* score, float* pair, long pair_ld, int slices, int slice_rows, u64* keys, hipStream_t s) {
+    const char* const gt = sizeof(GT) == 2 ? "_Float16" : "float";
+    const int L = k <= 64 ? 64 : 128;
+    const auto kernel = k <= 64 ? sim_coupling_kernel<GT, 64> : sim_coupling_kernel<GT, 128>;
+    if (slices == 1) {
+        record_kernel("sim_coupling_kernel<%s,%d>", gt, L);
+        hipLaunchKernelGGL(kernel, dim3(n_tiles), dim3(256), 0, s, words, woff, tfq, gallery, n_queries, n_gallery, D, k, g_offsets, n_groups,
+                           group_offset, merge, idx, score, pair, pair_ld, slice_rows, (u64*)nullptr);
+        return hipGetLastError();
+    }
+    record_kernel("sim_coupling_kernel<%s,%d>+sim_topk_reduce_kernel<%d,0>", gt, L, L);
+    hipLaunchKernelGGL(kernel, dim3(n_tiles, slices), dim3(256), 0, s, words, woff, tfq, gallery, n_queries, n_gallery, D, k, g_offsets, n_groups,
+                       group_offset, 0, idx, score, pair, pair_ld, slice_rows, keys);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const auto reduce = k <= 64 ? sim_topk_reduce_kernel<64, false> : sim_topk_reduce_kernel<128, false>;
+    hipLaunchKernelGGL(reduce, dim3((n_queries + 63) / 64), dim3(256), 0, s, keys, slices, n_queries, k, (const int32_t*)nullptr, 0, group_offset,
+                       merge, idx, score);
+    return hipGetLastError();
+}
+
+hipError_t launch_sim_coupling(const float* words, const int32_t* woff, const int32_t* tfq, int n_tiles, const void* gallery, bool gallery_f16,
+                               int n_queries, int n_gallery, int D, int k, const int32_t* g_offsets, int n_groups, int group_offset, int merge,
+                               int32_t* idx, float* score, float* pair, long pair_ld, int slices, int slice_rows, unsigned long long* keys,
+                               hipStream_t s) {
+    if (n_queries <= 0) return hipSuccess;
+    if (!words || !woff || !tfq || n_tiles < 1 || n_tiles > n_queries || D <= 0 || D % 64 || k < 1 || k > SIM_TOPK_MAX_K || n_gallery < 0 ||
+        n_groups < 0 || (n_groups > 0 && !g_offsets) || group_offset < 0 || group_offset > INT32_MAX - n_groups || (pair && pair_ld < n_queries) ||
+        slices < 1 || slices > 65535 || slice_rows < 64 || slice_rows % 64 || (slices > 1 && (!keys || (long)(slices - 1) * slice_rows >= n_gallery)))
+        return hipErrorInvalidValue;
+    return gallery_f16 ? launch_coupling(words, woff, tfq, n_tiles, static_cast<const _Float16*>(gallery), n_queries, n_gallery, D, k, g_offsets,
+                                         n_groups, group_offset, merge, idx, score, pair, pair_ld, slices, slice_rows, keys, s)
+                       : launch_coupling(words, woff, tfq, n_tiles, static_cast<const float*>(gallery), n_queries, n_gallery, D, k, g_offsets,
+                                         n_groups, group_offset, merge, idx, score, pair, pair_ld, slices, slice_rows, keys, s);
+}
+
 // rows (as jg_sim_topk_grouped returns them) -> group and position inside it: an element-wise binary search; -1 / -1 for idx < 0 or a row
 // in no group.  Hostile offsets give some group and position, nothing else.
 __global__ void group_of_rows_kernel(const int32_t* __restrict__ idx, long n, const int32_t* __restrict__ goff, int n_groups,

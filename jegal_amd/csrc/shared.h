@@ -210,10 +210,9 @@ struct SimSearchPlan {
 // SIM_SEARCH_WG_PER_CU workgroups per CU -- one when the query blocks alone fill the device -- of at least SIM_SEARCH_MIN_TILES tiles, at
 // most SIM_SEARCH_MAX_SLICES, with lists inside SIM_SEARCH_MAX_WS.  slices_in > 0: that many, at most one per tile.  The tiles are then
 // dealt out evenly, which may leave fewer slices than asked for, none of them empty.  false: a count the entry refuses.
-inline bool sim_search_plan(int n_queries, int n_gallery, int k, int num_cu, int slices_in, SimSearchPlan& p) {
-    if (n_queries < 0 || n_gallery < 0 || k < 1 || k > SIM_TOPK_MAX_K || num_cu < 1 || slices_in < 0 || slices_in > SIM_SEARCH_MAX_SLICES)
-        return false;
-    const long long tiles = ((long long)n_gallery + 63) / 64, qblocks = ((long long)n_queries + 63) / 64, list = (long long)n_queries * k * 8;
+// (n_blocks workgroups per slice and lists of `list` bytes per slice: jg_sim_search's query blocks, jg_sim_coupling's query tiles)
+inline bool sim_slice_cut(long long n_blocks, long long list, int n_gallery, int num_cu, int slices_in, SimSearchPlan& p) {
+    const long long tiles = ((long long)n_gallery + 63) / 64, qblocks = n_blocks;
     long long s = slices_in;
     if (!slices_in) {
         s = qblocks >= num_cu || !qblocks ? 1 : ((long long)SIM_SEARCH_WG_PER_CU * num_cu + qblocks - 1) / qblocks;
@@ -231,9 +230,47 @@ inline bool sim_search_plan(int n_queries, int n_gallery, int k, int num_cu, int
     p.ws_bytes = s > 1 ? s * list : 0;
     return true;
 }
+inline bool sim_search_plan(int n_queries, int n_gallery, int k, int num_cu, int slices_in, SimSearchPlan& p) {
+    if (n_queries < 0 || n_gallery < 0 || k < 1 || k > SIM_TOPK_MAX_K || num_cu < 1 || slices_in < 0 || slices_in > SIM_SEARCH_MAX_SLICES)
+        return false;
+    return sim_slice_cut(((long long)n_queries + 63) / 64, (long long)n_queries * k * 8, n_gallery, num_cu, slices_in, p);
+}
 hipError_t launch_sim_search(const float* queries, const void* gallery, bool gallery_f16, int n_queries, int n_gallery, int D, int k,
                              const int32_t* g_offsets, int n_groups, int gallery_offset, int merge, int32_t* idx, float* score, int slices,
                              int slice_rows, unsigned long long* keys, hipStream_t s);
+// jg_sim_coupling (late interaction): query q = word rows w_offsets[q] .. w_offsets[q + 1] - 1 (1 .. COUPLING_MAX_W of them), a group scores
+// as the mean over the query's words of each word's best row in the group, per query the k best groups (retrieval.hip).
+constexpr int COUPLING_MAX_W = 64;           // word rows of one query: a query lives in one 64-row tile
+struct CouplingPlan {
+    int n_tiles;                             // query tiles: whole queries in order, at most 64 word rows each
+    SimSearchPlan cut;                       // sim_search_plan's rule with the query tiles in place of the query blocks
+};
+// The plan of a call, a pure host function (jg_debug_coupling_plan shows it).  Queries are packed in order into tiles of at most 64 word
+// rows; a query is never split, one that does not fit the rest of a tile starts the next.  tile_first_query (n_queries + 1 entries of
+// room): [i] = the first query of tile i, [n_tiles] = n_queries.  false: offsets or counts the entry refuses.
+inline bool sim_coupling_plan(const int32_t* w_offsets, int n_queries, int n_gallery, int k, int num_cu, int slices_in, int32_t* tile_first_query,
+                              CouplingPlan& p) {
+    if (!w_offsets || !tile_first_query || n_queries < 0 || n_gallery < 0 || k < 1 || k > SIM_TOPK_MAX_K || num_cu < 1 || slices_in < 0 ||
+        slices_in > SIM_SEARCH_MAX_SLICES || w_offsets[0] != 0)
+        return false;
+    int n_tiles = 0, used = 64;              // word rows in the open tile (64: none is open)
+    for (int q = 0; q < n_queries; ++q) {
+        const long long W = (long long)w_offsets[q + 1] - w_offsets[q];
+        if (W < 1 || W > COUPLING_MAX_W) return false;
+        if (used + W > 64) { tile_first_query[n_tiles++] = q; used = 0; }
+        used += (int)W;
+    }
+    tile_first_query[n_tiles] = n_queries;
+    p.n_tiles = n_tiles;
+    return sim_slice_cut(n_tiles, (long long)n_queries * k * 8, n_gallery, num_cu, slices_in, p.cut);
+}
+// woff [n_queries + 1] and tfq [n_tiles + 1]: the two tables above on the device.  pair (optional) [n_groups][pair_ld]: only pairs with a
+// score are stored (launch_coupling_fill first: NaN everywhere).  keys as for launch_sim_search.
+hipError_t launch_coupling_fill(float* pair, long pair_ld, int n_queries, int n_groups, hipStream_t s);
+hipError_t launch_sim_coupling(const float* words, const int32_t* woff, const int32_t* tfq, int n_tiles, const void* gallery, bool gallery_f16,
+                               int n_queries, int n_gallery, int D, int k, const int32_t* g_offsets, int n_groups, int group_offset, int merge,
+                               int32_t* idx, float* score, float* pair, long pair_ld, int slices, int slice_rows, unsigned long long* keys,
+                               hipStream_t s);
 // grp / pos [n]: the group that holds row idx[e] - gallery_offset and the row's place inside it; -1 / -1 for idx[e] < 0 or a row in no group
 hipError_t launch_group_of_rows(const int32_t* idx, long n, const int32_t* g_offsets, int n_groups, int gallery_offset, int32_t* grp,
                                 int32_t* pos, hipStream_t s);

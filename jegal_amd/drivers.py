@@ -8,7 +8,7 @@
     python -m jegal_amd.drivers inference_embs ...            # inference_embs.py (single clip -> <fname>.pkl)
     python -m jegal_amd.drivers attn_matrix --path F|D        # utils/plot_heatmap.py without the rendering (-> <name>.attn.npz)
     python -m jegal_amd.drivers retrieve --path D [--topk 10] # the retrieval evaluate_retrieval.py grades (-> retrieve_<direction>.npz)
-    python -m jegal_amd.drivers search --path D --query F.pkl [--level word|phrase]   # which clips gesture a word, and at which frame (-> search_<F>.npz)
+    python -m jegal_amd.drivers search --path D --query F.pkl [--level word|phrase|coupling]   # which clips gesture a word, and at which frame (-> search_<F>.npz)
     python -m jegal_amd.drivers asd --path D --file avs_asd.csv [--win N --hop M]   # the detection evaluate_asd.py grades (-> asd.npz)
     python -m jegal_amd.drivers sync_offset --checkpoint_path_gestsync CKPT --frames F.npy --wav F.wav [--mel F.npy] [--max_shift 15]   # audio-visual offset of a clip (-> <name>.sync.npz)
         [--win 125 --hop 25]   # the offset over time (start, offset_t, conf_t, curve_t);  several --frames: which track is in sync with the audio, per window
@@ -35,6 +35,7 @@ from . import dist as jdist
 from . import extract
 from . import metrics as M
 from . import synth
+from ._metric_entries import COUPLING_MAX_W
 
 
 def load_checkpoint(path, kind):
@@ -416,12 +417,29 @@ def _load_pkls(path):
     return files, [_load_pkl(fn) for fn in files]
 
 
-def cmd_evaluate_retrieval(argv):
+_RETRIEVAL_LINE = "R@1: {:.2f} - R@5: {:.2f} - R@10: {:.2f} - R@25: {:.2f} - R@50: {:.2f} | Median R: {:.1f}"
+
+
+def cmd_evaluate_retrieval(argv, engine=None):
+    """evaluate_retrieval.py.  --score coupling: the same two lines with the late-interaction score (every word's best frame in the clip,
+    metrics.coupling_retrieval_metrics) in place of the cosine of the pooled vectors; one process only.  engine: the Engine to run on
+    (default: this process's)."""
     p = argparse.ArgumentParser(prog="evaluate_retrieval")
     p.add_argument("--path", required=True)
+    p.add_argument("--score", default="pooled", choices=["pooled", "coupling"],
+                   help="pooled: the cosine of the clip-level means, as the reference; coupling: every word's best frame (late interaction)")
     args = p.parse_args(argv)
-    eng, _, _ = _models(args)
+    eng = _engine(engine, args)
+    if args.score == "coupling" and jdist.world_size() > 1:
+        raise SystemExit("--score coupling runs in one process: it is not sharded over ranks")
     _, feats = _load_pkls(args.path)
+    if args.score == "coupling":
+        both = M.coupling_retrieval_metrics([f["content_emb"] for f in feats], [f["gesture_emb"] for f in feats], engine=eng)
+        res = {"Content to Gesture": both["c2g"], "Gesture to Content": both["g2c"]}
+        for name, m in res.items():
+            print("{} Retrieval scores:".format(name))
+            print(_RETRIEVAL_LINE.format(m["R1"] * 100, m["R5"] * 100, m["R10"] * 100, m["R25"] * 100, m["R50"] * 100, m["MR"]))
+        return res
     lo, hi = jdist.shard_range(len(feats))
     g = M.video_level(eng, [f["gesture_emb"] for f in feats[lo:hi]])
     c = M.video_level(eng, [f["content_emb"] for f in feats[lo:hi]])
@@ -431,8 +449,7 @@ def cmd_evaluate_retrieval(argv):
         res[name] = m
         if jdist.rank() == 0:
             print("{} Retrieval scores:".format(name))
-            print("R@1: {:.2f} - R@5: {:.2f} - R@10: {:.2f} - R@25: {:.2f} - R@50: {:.2f} | Median R: {:.1f}".format(
-                m["R1"] * 100, m["R5"] * 100, m["R10"] * 100, m["R25"] * 100, m["R50"] * 100, m["MR"]))
+            print(_RETRIEVAL_LINE.format(m["R1"] * 100, m["R5"] * 100, m["R10"] * 100, m["R25"] * 100, m["R50"] * 100, m["MR"]))
     return res
 
 
@@ -603,12 +620,15 @@ def cmd_search(argv, engine=None):
     query's words (phrase: the words joined), names (N,): the .pkl base names = the clip numbering, clip (Q,K) int32, frame (Q,K) int32:
     the frame inside the clip, score (Q,K) float32; -1 / -1 / -inf where fewer than K groups exist} and prints one line per query row.
     --index FILE instead of --path: the corpus is one written by the index command (metrics.Corpus, jg_sim_search): prepared once, maybe
-    in 16 bits, the same output.  engine: the Engine to run on (default: this process's)."""
+    in 16 bits, the same output.  --level coupling: the query's words stay separate rows of ONE query of at most 64 words, and a clip (or
+    segment) scores as the mean over the words of each word's best frame in it (metrics.search_phrases, jg_sim_coupling); the .npz also
+    holds start (1,K) = the first frame of the returned group inside its clip, and `frame` repeats it.  engine: the Engine to run on
+    (default: this process's)."""
     p = argparse.ArgumentParser(prog="search", description="Single process: sharding over ranks is not built for this command.")
     p.add_argument("--path", default=None, help="a directory of JEGAL feature .pkl files: the corpus (or --index)")
     p.add_argument("--index", default=None, help="a corpus written by the index command, instead of --path: prepared once, maybe in 16 bits")
     p.add_argument("--query", required=True, help="a JEGAL feature .pkl whose content_emb rows are the query")
-    p.add_argument("--level", default="word", choices=["word", "phrase"])
+    p.add_argument("--level", default="word", choices=["word", "phrase", "coupling"])
     p.add_argument("--topk", type=int, default=10, help="clips (or segments) kept per query row (1..128)")
     p.add_argument("--segment", type=int, default=0, help="frames per group; 0: a clip is one group")
     p.add_argument("--normalize", type=int, default=1, choices=[0, 1], help="1: cosine similarity (rows re-normalised); 0: the rows as stored")
@@ -630,20 +650,28 @@ def cmd_search(argv, engine=None):
     M.check_word_count(len(words), len(queries), args.query)
     if args.level == "phrase":
         queries, words = queries.mean(axis=0, keepdims=True), [" ".join(words)]
+    coupling = args.level == "coupling"
+    if coupling:                                 # the words stay separate rows of ONE query
+        if not 1 <= len(queries) <= COUPLING_MAX_W:
+            raise SystemExit("--level coupling takes a query of 1..{} words, not {}".format(COUPLING_MAX_W, len(queries)))
+        queries, words = [queries], [" ".join(words)]
     if args.index is not None:                   # (its rows were normalised, or not, when it was built: --normalize is about the query)
         corpus = M.Corpus.load(args.index)
         names = corpus.names
         eng = _engine(engine, args)
-        clip, frame, score = corpus.search(queries, k=args.topk, segment=args.segment, normalize=bool(args.normalize), engine=eng,
+        clip, frame, score = (corpus.search_phrases if coupling else corpus.search)(queries, k=args.topk, segment=args.segment, normalize=bool(args.normalize), engine=eng,
                                            max_rows=args.max_rows)
     else:
         names, clips = _corpus_clips(args.path)
         eng = _engine(engine, args)
-        clip, frame, score = M.search(queries, clips, k=args.topk, segment=args.segment, normalize=bool(args.normalize), engine=eng,
+        clip, frame, score = (M.search_phrases if coupling else M.search)(queries, clips, k=args.topk, segment=args.segment, normalize=bool(args.normalize), engine=eng,
                                       max_rows=args.max_rows)
     os.makedirs(args.res_dir, exist_ok=True)
     out = os.path.join(args.res_dir, "search_{}.npz".format(_base_name(args.query)))
-    np.savez(out, words=np.asarray(words), names=names, clip=clip, frame=frame, score=score)
+    if coupling:                                 # a group comes back, not a frame: `frame` is its first one, under both names
+        np.savez(out, words=np.asarray(words), names=names, clip=clip, start=frame, frame=frame, score=score)
+    else:
+        np.savez(out, words=np.asarray(words), names=names, clip=clip, frame=frame, score=score)
     for i, w in enumerate(words):
         hits = ["{}@{} ({:.3f})".format(names[c], f, s) for c, f, s in zip(clip[i][:3], frame[i][:3], score[i][:3]) if c >= 0]
         print("search: \"{}\" -> {} of {} clips: {}".format(w, int(np.sum(clip[i] >= 0)), len(names), ", ".join(hits) or "nothing"))

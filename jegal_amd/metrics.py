@@ -138,12 +138,14 @@ def search_groups(lengths, segment=0):
     return off, np.asarray(clip, np.int32), np.asarray(start, np.int32)
 
 
-def _search_walk(queries, dim, corpus, k, segment, normalize, engine, max_rows):
-    """The walk of search() and Corpus.search(): check the arguments, cut the clips into groups (search_groups) and the groups into pieces
+def _search_walk(queries, dim, corpus, k, segment, normalize, engine, max_rows, phrases=False):
+    """The walk of search() and Corpus.search(), and (phrases) of their search_phrases: check the arguments, cut the clips into groups (search_groups) and the groups into pieces
     of at most max_rows rows, score piece after piece into one merged top-k list, and decode its gallery rows into (clip, frame, score).
     corpus(q) checks the (Q, D) query tensor against the gallery and returns (the frames of every clip, score_piece); score_piece(eng, q,
     r0, r1, c0, c1, g_offsets, res) brings the gallery rows r0 .. r1 - 1 (of the clips c0 .. c1 - 1) to the device and scores them with the
-    caller's entry, merging into res.  dim: what a message calls the queries' D."""
+    caller's entry, merging into res.  dim: what a message calls the queries' D.
+    phrases: `queries` is a list of (W_i, D) word matrices, each ONE query (q: their rows, Q: their number); score_piece gets the piece's
+    first group as a ninth argument and returns GROUPS (Engine.sim_coupling), and `frame` is the first frame of the returned group."""
     k, segment = int(k), int(segment)
     if not 1 <= k <= 128:
         raise ValueError("k must be 1..128")
@@ -152,7 +154,7 @@ def _search_walk(queries, dim, corpus, k, segment, normalize, engine, max_rows):
     q = cat_rows(queries)
     if q.ndim != 2:
         raise ValueError("queries must be (Q, {})".format(dim))
-    Q = int(q.shape[0])
+    Q = len(queries) if phrases else int(q.shape[0])
     lengths, score_piece = corpus(q)
     goff, gclip, gstart = search_groups(lengths, segment)
     n_groups = len(gclip)
@@ -176,11 +178,11 @@ def _search_walk(queries, dim, corpus, k, segment, normalize, engine, max_rows):
                 g1 += 1
         r0, r1 = int(goff[g0]), int(goff[g1])
         if r1 > r0:
-            res = score_piece(eng, q, r0, r1, int(gclip[g0]), int(gclip[g1 - 1]) + 1, goff[g0:g1 + 1] - r0, res)
+            res = score_piece(eng, q, r0, r1, int(gclip[g0]), int(gclip[g1 - 1]) + 1, goff[g0:g1 + 1] - r0, res, *([g0] if phrases else []))
         g0 = g1
     if res is None:
         return empty
-    grp, pos = eng.group_of_rows(res[0], goff, 0)
+    grp, pos = (res[0], torch.zeros_like(res[0])) if phrases else eng.group_of_rows(res[0], goff, 0)
     grp, pos, score = to_host(grp).astype(np.int64), to_host(pos).astype(np.int32), to_host(res[1]).astype(np.float32)
     found = grp >= 0
     clip = np.where(found, gclip[np.maximum(grp, 0)], -1).astype(np.int32)
@@ -211,6 +213,83 @@ def search(queries, clips, k=10, segment=0, normalize=True, engine=None, max_row
             return eng.sim_topk_grouped(q, rows, g_offsets, int(k), gallery_offset=r0, merge_into=res)
         return [c.shape[0] for c in mats], score_piece
     return _search_walk(queries, "D", corpus, k, segment, normalize, engine, max_rows)
+
+
+def _phrase_list(queries):
+    """search_phrases' queries: a list of (W_i, D) word matrices of 1..64 rows each -> (the list as float32 arrays or tensors, w_offsets)"""
+    mats = [m.to(torch.float32) if isinstance(m, torch.Tensor) else np.asarray(m, np.float32) for m in queries]
+    if any(m.ndim != 2 for m in mats) or len({int(m.shape[1]) for m in mats}) > 1:
+        raise ValueError("queries must be a list of (W_i, D) word matrices with one D")
+    if any(not 1 <= m.shape[0] <= 64 for m in mats):
+        raise ValueError("a query must have 1..64 word rows")
+    return mats, offsets_of(mats)
+
+
+def _no_phrases(k):
+    if not 1 <= int(k) <= 128:
+        raise ValueError("k must be 1..128")
+    return np.zeros((0, int(k)), np.int32), np.zeros((0, int(k)), np.int32), np.zeros((0, int(k)), np.float32)
+
+
+def search_phrases(queries, clips, k=10, segment=0, normalize=True, engine=None, max_rows=None):
+    """search() for queries of several words that keeps the word-to-frame structure (late interaction, jg_sim_coupling): queries is a list
+    of (W_i, D) word matrices (1..64 rows each), each ONE query; a group of frames (a clip, or a run of `segment` frames of it) scores as
+    the mean over the query's words of each word's best frame in the group -- no pooling of the words or the frames, no (words) x (frames)
+    matrix.  clips, segment, normalize and max_rows as for search(); pieces are cut at group boundaries and merged, the same result.
+    Returns host arrays (clip (Q, k) int32, start (Q, k) int32: the first frame of the returned group inside its clip (search_groups),
+    score (Q, k) float32), best first, ties to the earlier group; -1 / -1 / -inf where fewer than k groups have a score."""
+    mats_q, w_off = _phrase_list(queries)
+    if not mats_q:
+        return _no_phrases(k)
+
+    def corpus(q):
+        D = int(q.shape[1])
+        mats = [c if isinstance(c, torch.Tensor) else np.asarray(c, np.float32) for c in clips]
+        if any(c.ndim != 2 or c.shape[1] != D for c in mats):
+            raise ValueError("every clip must be (T_i, {}) like the queries".format(D))
+        first_row = np.concatenate([[0], np.cumsum([c.shape[0] for c in mats])])
+
+        def score_piece(eng, q, r0, r1, c0, c1, g_offsets, res, g0):
+            rows = cat_rows(mats[c0:c1])[r0 - int(first_row[c0]):r1 - int(first_row[c0])]
+            if normalize:
+                rows = eng.l2norm(rows)
+            return eng.sim_coupling(q, w_off, rows, g_offsets, int(k), group_offset=g0, merge_into=res)
+        return [c.shape[0] for c in mats], score_piece
+    return _search_walk(mats_q, "D", corpus, k, segment, normalize, engine, max_rows, phrases=True)
+
+
+def coupling_matrix(contents, gestures, normalize=True, engine=None):
+    """The late-interaction score of every utterance against every clip: contents is a list of (W_i, D) word matrices (1..64 rows each),
+    gestures a list of (T_j, D) frame matrices; entry (i, j) is the mean over utterance i's words of each word's largest product with a
+    frame of clip j (normalize: rows L2-normalised first, so cosines).  One jg_sim_coupling call; the (words) x (frames) matrix is never
+    written.  Returns the (N_c, N_g) float32 matrix on the engine's device; NaN where a pair has no score (an empty clip)."""
+    eng = engine or Engine.get()
+    mats_c, w_off = _phrase_list(contents)
+    if not mats_c or not len(gestures):
+        return torch.full((len(mats_c), len(gestures)), float("nan"), dtype=torch.float32, device=eng.device)
+    w, g = cat_rows(mats_c), cat_rows(gestures)
+    if normalize:
+        w, g = eng.l2norm(w), eng.l2norm(g)
+    return eng.sim_coupling(w, w_off, g, offsets_of(gestures), 1, want_matrix=True)[2]
+
+
+def coupling_retrieval_metrics(contents, gestures, engine=None):
+    """R@K and the median rank of evaluate_retrieval with the late-interaction score in place of the cosine of the pooled vectors:
+    {"c2g": .., "g2c": ..}, each in metrics_from_ranks' form, both from the one coupling_matrix (utterance i belongs to clip i).  The rank
+    of a partner is the number of strictly larger entries in its row (c2g) or its column (g2c), ties counted as jg_sim_rank counts them.
+    g2c here ranks the UTTERANCES for a clip by the same word -> frame score (every word of the utterance looks for its best frame in the
+    clip); it is not a second, frame -> word score.  Counted with torch on the device matrix.  Single process only."""
+    if jdist.world_size() > 1:
+        raise RuntimeError("coupling_retrieval_metrics runs in one process: it is not sharded over ranks")
+    if len(contents) != len(gestures):
+        raise ValueError("one clip per utterance")
+    M = coupling_matrix(contents, gestures, engine=engine)
+    d = M.diagonal()
+    out = {}
+    for name, part, own in (("c2g", M, d[:, None]), ("g2c", M.t(), d[:, None])):
+        rank, ties = (part > own).sum(1), (part == own).sum(1)
+        out[name] = metrics_from_ranks(to_host(rank), to_host(ties))
+    return out
 
 
 class Corpus:
@@ -293,6 +372,23 @@ class Corpus:
                                       merge_into=res)
             return self.lengths, score_piece
         return _search_walk(queries, self.rows.shape[1], corpus, k, segment, normalize, engine, max_rows)
+
+    def search_phrases(self, queries, k=10, segment=0, normalize=True, engine=None, max_rows=None):
+        """search_phrases() over the prepared rows, 16- or 32-bit as stored: the same (clip, start, score) triple through jg_sim_coupling;
+        the rest as for search()."""
+        mats_q, w_off = _phrase_list(queries)
+        if not mats_q:
+            return _no_phrases(k)
+
+        def corpus(q):
+            if self.rows.shape[0] and q.shape[1] != self.rows.shape[1]:
+                raise ValueError("queries must be (W_i, {})".format(self.rows.shape[1]))
+
+            def score_piece(eng, q, r0, r1, c0, c1, g_offsets, res, g0):
+                return eng.sim_coupling(q, w_off, self._device_rows(eng, r0, r1, max_rows is None), g_offsets, int(k), group_offset=g0,
+                                        merge_into=res)
+            return self.lengths, score_piece
+        return _search_walk(mats_q, self.rows.shape[1], corpus, k, segment, normalize, engine, max_rows, phrases=True)
 
 
 def partner_ranks(emb1, emb2, engine=None):
