@@ -10,150 +10,26 @@ import os
 import numpy as np
 import torch  # imported first so libamdhip64.so.7 resolves to the runtime torch already loaded
 
+from . import _abi
+from ._check_entries import CheckPoints, ConvCheck, ConvShape, GemmCheck
 from ._metric_entries import MetricEntries, _ptr, _shape
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libjegal_hip.so")
 
-JG_F32, JG_F16, JG_I64, JG_U8 = 0, 1, 2, 3
-PREC_FP16, PREC_FP16_W2, PREC_FP16_W2_ALL, PREC_FP16_BC, PREC_BF16, PREC_FP16_RC, PREC_FP32 = 0, 1, 2, 3, 4, 5, 6
-AUDIT_CONV, AUDIT_GESTSYNC, AUDIT_JEGAL, AUDIT_CONTENT, AUDIT_XLMR = 1, 2, 4, 8, 16      # option audit_stages (include/jegal_hip.h)
-STAGES = ["stack_frames", "conv1", "maxpool", "conv2-fc6+audio_cnn", "gemm", "attention", "layernorm", "misc", "conv1_aux"]
-
+# include/jegal_hip.h is the only declaration of the ABI: signatures, structs and enum values come from _abi's parse of it
 _P = ctypes.c_void_p
 _I = ctypes.c_int
 _L = ctypes.c_int64
-JG_ERR_ARG = -1
+JG_F32, JG_F16, JG_I64, JG_U8, JG_ERR_ARG = (_abi.CONSTANTS[k] for k in ("JG_F32", "JG_F16", "JG_I64", "JG_U8", "JG_ERR_ARG"))
+PREC_FP16, PREC_FP16_W2, PREC_FP16_W2_ALL, PREC_FP16_BC, PREC_BF16, PREC_FP16_RC, PREC_FP32 = (
+    _abi.CONSTANTS["JG_PREC_" + k] for k in ("FP16", "FP16_W2", "FP16_W2_ALL", "FP16_BC", "BF16", "FP16_RC", "FP32"))
+AUDIT_CONV, AUDIT_GESTSYNC, AUDIT_JEGAL, AUDIT_CONTENT, AUDIT_XLMR = 1, 2, 4, 8, 16      # option audit_stages (include/jegal_hip.h)
+STAGES = ["stack_frames", "conv1", "maxpool", "conv2-fc6+audio_cnn", "gemm", "attention", "layernorm", "misc", "conv1_aux"]
+assert len(STAGES) == _abi.CONSTANTS["JG_ST_COUNT"], "STAGES needs one label per JG_ST_* stage of include/jegal_hip.h"
 
-
-class GemmCheck(ctypes.Structure):
-    """struct jg_gemm_check (include/jegal_hip.h): operands of one jg_debug_gemm_check launch."""
-    _fields_ = [("A", _P), ("lda", _L), ("Wh", _P), ("Wl", _P), ("ldw", _L), ("M", _I), ("N", _I), ("K", _I),
-                ("scale", _P), ("bias", _P), ("bias_clip", _P), ("rpc", _I), ("nclips", _I),
-                ("res", _P), ("ldr", _L), ("res_mod", _I), ("relu", _I), ("out32", _P), ("out16", _P), ("ldc", _L),
-                ("ln_w", _P), ("ln_b", _P), ("res16", _P),
-                ("ln_mode", _I), ("ln_stats", _P), ("xres_hi", _P), ("xres_lo", _P), ("out_lo", _P), ("stat_out", _P),
-                ("a_tiled", _I)]
-class ConvCheck(ctypes.Structure):
-    """struct jg_conv_check (include/jegal_hip.h): operands of one jg_debug_conv_check launch."""
-    _fields_ = [("in_", _P)] + [(k, _I) for k in ("nimg", "H", "W", "C", "KH", "KW", "SH", "SW", "PH", "PW", "reorder")] + [
-        ("Wh", _P), ("Wl", _P), ("ldw", _L), ("N", _I), ("K", _I), ("scale", _P), ("bias", _P), ("relu", _I),
-        ("out32", _P), ("out16", _P), ("ldc", _L), ("s2_host", ctypes.POINTER(ctypes.c_int32)), ("op", _I), ("const_in", _P)]
-class ConvShape(ctypes.Structure):
-    """struct jg_conv_shape (include/jegal_hip.h): the part of a conv geometry the GEMM planner reads."""
-    _fields_ = [(k, _I) for k in ("H", "W", "C", "KH", "KW", "PH", "PW", "tap_table", "rowmap", "const_in")]
-
-
-_SIGS = {
-    "jg_create": [_I, ctypes.POINTER(_P)],
-    "jg_destroy": [_P],
-    "jg_set_stream": [_P, _P],
-    "jg_set_precision": [_P, _I],
-    "jg_set_chunk": [_P, _I],
-    "jg_set_option": [_P, ctypes.c_char_p, _I],
-    "jg_sync": [_P],
-    "jg_load_tensor": [_P, ctypes.c_char_p, _P, ctypes.POINTER(ctypes.c_int64), _I, _I],
-    "jg_finalize_weights": [_P, _I],
-    "jg_clear_staged_tensors": [_P],
-    "jg_calibrate_gesture": [_P, _P, _I, _I, _I],
-    "jg_gestsync_clip": [_P, _P, _I, _I, _I, _P],
-    "jg_gestsync_clip_ragged": [_P, _P, _I, _I, _I, ctypes.POINTER(ctypes.c_int32), _P],
-    "jg_gestsync_windows": [_P, _P, _I, _P, _P],
-    "jg_gestsync_audio_windows": [_P, _P, _I, _P],
-    "jg_gestsync_audio_clip": [_P, _P, _I, _I, _I, ctypes.POINTER(ctypes.c_int32), _P],
-    "jg_debug_gsa_conv1_pool": [_P, _P, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_int32), _P, _P, _P, _I],
-    "jg_debug_maxpool_2x3": [_P, _P, _I, _I, _I, _I, _P, _I],
-    "jg_sync_offset": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P],
-    "jg_sync_offset_windows": [_P, _P, _P, _I, _L, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P],
-    "jg_debug_conv1_pool": [_P, _P, _I, _I, _I, _P],
-    "jg_debug_gemm": [_P, _I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_double)],
-    "jg_debug_gemm_ex": [_P, _P, _P, _I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_double)],
-    "jg_debug_conv2_rowskip": [_P, ctypes.POINTER(ctypes.c_int)],
-    "jg_debug_gemm_check": [_P, _P],
-    "jg_debug_conv_check": [_P, _P],
-    "jg_debug_maxpool": [_P, _P, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_int32), _I, _P, _P],
-    "jg_debug_conv_rowmaps": [_P, ctypes.POINTER(ctypes.c_int32), _I, ctypes.POINTER(_I), ctypes.POINTER(_I), _I, ctypes.POINTER(_P), ctypes.POINTER(_P),
-                              ctypes.POINTER(ctypes.c_int32)],
-    "jg_debug_gemm_plan": [_P, _P, _I, _I, _I, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(_I), _I, ctypes.c_char_p, _I,
-                           ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I)],
-    "jg_debug_weight_form": [_I, _I, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I)],
-    "jg_debug_gemm_runs_lo": [_I, _I, _I, _I, ctypes.POINTER(_I)],
-    "jg_debug_pack_conv": [_P] * 6 + [_I] * 13 + [_P, _P],
-    "jg_debug_pack_round": [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I] + [_P] * 7,
-    "jg_debug_conv1_panel": [_P, _P, _P],
-    "jg_debug_bias_correction": [_P, _P, _P, _L, _I, _I, _P],
-    "jg_debug_gemm32": [_P, _P, _L, _P, _L, _I, _I, _I, _P, _P, _P, _L, _I, _I, _P, _L],
-    "jg_debug_conv32": [_P, _P] + [_I] * 11 + [_P, _L, _I, _P, _P, _I, _P, _L],
-    "jg_debug_gemm_x3": [_P, _P, _L, _P, _P, _L, _I, _I, _I, _P, _P, _L, _I, _I, _P, _L],
-    "jg_debug_attention": [_P, _P, _P, _I, _I, _I, _I, _P],
-    "jg_debug_attention_gather": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
-    "jg_debug_attention32": [_P, _P, _P, _I, _I, _I, _I, _P],
-    "jg_debug_stack_frames": [_P, _P, _I, _L, _L, _L, _L, _L, _L, _I, _I, _I, _I, _I, _P],
-    "jg_debug_window_gather": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P],
-    "jg_debug_layernorm": [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P],
-    "jg_debug_layernorm_planes": [_P, _P, _P, _P, _P, _I, _I, _P],
-    "jg_debug_group_mean": [_P, _P, _I, _I, _I, _P],
-    "jg_debug_cast": [_P, _P, _P, _L],
-    "jg_debug_audio_conv0": [_P, _P, _I, _I, _I, _P, _P, _P, _P, ctypes.POINTER(ctypes.c_int32), _I],
-    "jg_debug_zero_tail": [_P, _P, ctypes.POINTER(ctypes.c_int32), _I, _I, _I, _I, _L],
-    "jg_debug_stack_frames32": [_P, _P, _I, _L, _L, _L, _L, _L, _L, _I, _I, _I, _I, _I, _P],
-    "jg_debug_maxpool32": [_P, _P, _I, _I, _I, _I, _P],
-    "jg_debug_group_mean32": [_P, _P, _I, _I, _I, _P],
-    "jg_debug_zero_tail32": [_P, _P, ctypes.POINTER(ctypes.c_int32), _I, _I, _I, _I, _L],
-    "jg_debug_xlmr_embed": [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P],
-    "jg_debug_xlmr_embed_planes": [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P],
-    "jg_debug_ln_stats": [_P, _P, _I, _I, _P],
-    "jg_debug_mask_i32_f32": [_P, _P, _P, _L],
-    "jg_debug_transpose_tokens": [_P, _P, _I, _I, _I, _P],
-    "jg_debug_pe_project": [_P, _P, _I, _P, _P, _P, _I, _I, _P],
-    "jg_debug_broadcast_channels": [_P, _P, _I, _P, _L],
-    "jg_debug_col_sum": [_P, _P, _L, _I, _I, _P, _L, _P, _P],
-    "jg_debug_rc_bias": [_P, _P, _L, _L, _I, _I, _I, ctypes.POINTER(ctypes.c_int32), _I, _P, _P, _I, _I, _P, _L, _P],
-    "jg_debug_last_kernel": [_P, ctypes.c_char_p, _I],
-    "jg_debug_conv_rows": [_P, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)],
-    "jg_jegal_gestures": [_P, _P, _P, _I, _I, _I, _P],
-    "jg_track_windows": [ctypes.POINTER(ctypes.c_int32), _I, _I, _I, ctypes.POINTER(ctypes.c_int32), _I, ctypes.POINTER(_I), ctypes.POINTER(_I)],
-    "jg_jegal_gesture_tracks": [_P, _P, ctypes.POINTER(ctypes.c_int32), _I, _I, _I, _I, _I, _P],
-    "jg_debug_span_gather": [_P, _P, _P, _P, _I, _I, _I, _P, _P],
-    "jg_debug_core_compact": [_P, _P, _I, _P, _I, _I, _I, _P],
-    "jg_jegal_audio": [_P, _P, _I, _I, _P],
-    "jg_jegal_audio_ragged": [_P, _P, _I, _I, ctypes.POINTER(ctypes.c_int32), _P],
-    "jg_audio_len": [_I],
-    "jg_logmel": [_P, _P, _I, _I, _P, _P],
-    "jg_mask_resize": [_P, _P, _I, _I, _I, _P, _P],
-    "jg_unpack_masked": [_P, _P, ctypes.c_int64, _P, _P, _I, _P],
-    "jg_mask_resize_packed": [_P, _P, ctypes.c_int64, _P, _I, _I, _I, _P, _P],
-    "jg_jegal_text": [_P, _P, _P, _I, _I, _P],
-    "jg_xlmr_encode": [_P, _P, _P, _I, _I, _P],
-    "jg_calibrate_xlmr": [_P, _P, _P, _I, _I],
-    "jg_word_pool": [_P, _P, _I, _P, _I, _P, _I, _I],
-    "jg_fuse_content": [_P, _P, _I, _P],
-    "jg_l2norm": [_P, _P, _P, _I, _I],
-    "jg_extract_gesture": [_P, _P, _I, _I, _I, _P],
-    "jg_pool_mean": [_P, _P, _P, _I, _I, _P],
-    "jg_sim_rank": [_P, _P, _P, _I, _I, _I, _I, _P, _P],
-    "jg_sim_topk": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P],
-    "jg_sim_topk_grouped": [_P, _P, _P, _I, _I, _I, _I, _P, _I, _I, _I, _P, _P],
-    "jg_sim_search": [_P, _P, _I, _P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _P, _P],
-    "jg_debug_search_plan": [_I, _I, _I, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(ctypes.c_int64)],
-    "jg_sim_coupling": [_P, _P, _P, _I, _P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _P, _P, _P, ctypes.c_int64],
-    "jg_debug_coupling_plan": [_P, _I, _I, _I, _I, _I, _P, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(ctypes.c_int64)],
-    "jg_group_of_rows": [_P, _P, _L, _P, _I, _I, _P, _P],
-    "jg_spot": [_P, _P, _P, _P, _P, _P, _I, _I, ctypes.c_float, _P, _P],
-    "jg_attn_matrix": [_P, _P, _P, _P, _P, _I, _I, _I, ctypes.c_float, _I, _P, _P, _P, _P],
-    "jg_attn_talk": [_P, _P, _P, _I, _L, _I, _P, _P, _I, _P, _P, _I, _I, ctypes.c_float, _I, _P, _I, _P, _P, _P, _P],
-    "jg_asd": [_P, _P, _P, _P, _I, _I, ctypes.c_float, _P],
-    "jg_asd_windows": [_P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _I, ctypes.c_float, _P, _P, _P],
-    "jg_comm_get_unique_id": [ctypes.c_char_p],
-    "jg_comm_init": [_P, ctypes.c_char_p, _I, _I],
-    "jg_comm_destroy": [_P],
-    "jg_allgather": [_P, _P, _P, ctypes.c_int64],
-    "jg_allreduce_sum_i64": [_P, _P, _I],
-    "jg_profile_enable": [_P, _I],
-    "jg_profile_get": [_P, _I, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)],
-    "jg_profile_reset": [_P],
-}
-EXPORTS = sorted(list(_SIGS) + ["jg_last_error", "jg_stage_name", "jg_workspace_bytes"])
+_SIGS = {name: args for name, (res, args) in _abi.FUNCTIONS.items() if res is _I}      # the entries that return a status
+EXPORTS = sorted(_abi.FUNCTIONS)
 
 _lib = None
 
@@ -168,16 +44,10 @@ def load_library():
             f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or `make -C jegal_amd/csrc`).  jegal_amd has no CPU/PyTorch fallback.")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, args in _SIGS.items():
+    for name, (res, args) in _abi.FUNCTIONS.items():
         fn = getattr(lib, name)
         fn.argtypes = args
-        fn.restype = _I
-    lib.jg_last_error.argtypes = [_P]
-    lib.jg_last_error.restype = ctypes.c_char_p
-    lib.jg_stage_name.argtypes = [_I]
-    lib.jg_stage_name.restype = ctypes.c_char_p
-    lib.jg_workspace_bytes.argtypes = [_P]
-    lib.jg_workspace_bytes.restype = ctypes.c_int64
+        fn.restype = res
     _lib = lib
     return lib
 
@@ -349,16 +219,16 @@ def track_windows(lengths, win, ctx):
     if rc != 0:
         raise JegalError(f"jg_track_windows: bad arguments (need win >= 1, ctx >= 0, win + 2 ctx <= 500) ({rc})", rc)
     table = np.zeros((n.value, 4), np.int32)
-    rc = lib.jg_track_windows(off, len(off) - 1, int(win), int(ctx), table.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), n.value,
+    rc = lib.jg_track_windows(off, len(off) - 1, int(win), int(ctx), table.ctypes.data, n.value,
                               ctypes.byref(n), ctypes.byref(smax))
     if rc != 0:
         raise JegalError(f"jg_track_windows failed ({rc})", rc)
     return table, smax.value
 
 
-class Engine(MetricEntries):
+class Engine(MetricEntries, CheckPoints):
     """One jg_handle on one GPU.  Not thread-safe; one per process/GPU.  The metric entries (pool_mean .. asd_windows) are
-    MetricEntries' (_metric_entries.py)."""
+    MetricEntries' (_metric_entries.py), the kernel check points (debug_*) CheckPoints' (_check_entries.py)."""
 
     _cache = {}
 
@@ -402,6 +272,11 @@ class Engine(MetricEntries):
 
     def _bind_stream(self):
         self._ck(self.lib.jg_set_stream(self.h, _P(torch.cuda.current_stream(self.device).cuda_stream)))
+
+    def _call(self, name, *args):
+        """One entry on the current stream: tensors go by device pointer, None and scalars as they are; a status other than 0 raises."""
+        self._bind_stream()
+        self._ck(getattr(self.lib, name)(self.h, *[_ptr(a) if isinstance(a, torch.Tensor) else a for a in args]))
 
     # ---- weights
     def set_precision(self, mode):
@@ -507,241 +382,6 @@ class Engine(MetricEntries):
         self._ck(self.lib.jg_gestsync_clip_ragged(self.h, _ptr(frames), code, B, T, (ctypes.c_int32 * B)(*v), _ptr(out)))
         return out
 
-    def debug_gemm(self, M, N, K, mode=0, iters=10, a16=None, w16=None):
-        """ms per launch of the production GEMM; a16 (M,K) / w16 (N,K): optional fp16 cuda operands (else constant fill)."""
-        self._bind_stream()
-        ms = ctypes.c_double()
-        for t, shp in ((a16, (M, K)), (w16, (N, K))):
-            if t is not None and (t.dtype != torch.float16 or tuple(t.shape) != shp or not t.is_contiguous() or t.device != self.device):
-                raise ValueError(f"debug_gemm operand must be a contiguous fp16 {shp} tensor on {self.device}")
-        self._ck(self.lib.jg_debug_gemm_ex(self.h, _ptr(a16), _ptr(w16), M, N, K, mode, iters, ctypes.byref(ms)))
-        return ms.value
-
-    # ---- kernel check points (include/jegal_hip.h): one production launch on caller-owned device tensors, asynchronous on the
-    # engine's stream; a shape the launcher rejects raises JegalError with .code == JG_ERR_ARG.  debug_last_kernel() names the instance.
-    def debug_gemm_check(self, **kw):
-        """Linear GEMM (launch_gemm): keyword arguments are the fields of jg_gemm_check; tensors are passed by pointer."""
-        self._bind_stream()
-        c = GemmCheck()
-        for k, v in kw.items():
-            if isinstance(v, torch.Tensor):
-                if v.device != self.device:
-                    raise ValueError(f"debug_gemm_check: {k} must be on {self.device}")
-                v = v.data_ptr()
-            setattr(c, k, v)
-        self._ck(self.lib.jg_debug_gemm_check(self.h, ctypes.byref(c)))
-
-    def debug_conv_check(self, **kw):
-        """Implicit-GEMM convolution (launch_gemm, conv): keyword arguments are the fields of jg_conv_check (`in_` for its `in`); tensors are
-        passed by pointer, s2_host is a sequence of nimg ints (or None)."""
-        self._bind_stream()
-        c = ConvCheck()
-        s2 = kw.pop("s2_host", None)
-        for k, v in kw.items():
-            if isinstance(v, torch.Tensor):
-                if v.device != self.device:
-                    raise ValueError(f"debug_conv_check: {k} must be on {self.device}")
-                v = v.data_ptr()
-            setattr(c, "in_" if k == "in" else k, v)
-        if s2 is not None:
-            s2 = [int(x) for x in s2]
-            if len(s2) != c.nimg:
-                raise ValueError("debug_conv_check: s2_host needs one entry per image")
-            keep = (ctypes.c_int32 * len(s2))(*s2)
-            c.s2_host = ctypes.cast(keep, ctypes.POINTER(ctypes.c_int32))
-        self._ck(self.lib.jg_debug_conv_check(self.h, ctypes.byref(c)))
-
-    def debug_maxpool(self, x, out, s2_host=None, in_op=0, const_in=None):
-        """3x3 / stride 2 max-pool (launch_maxpool3x3s2): x (nimg,H,W,C) 16-bit NHWC -> out (nimg,(H-3)//2+1,(W-3)//2+1,C), written in place.
-        s2_host (nimg ints) / in_op / const_in (H,W,C): input rows below conv_skip_decode(s2, in_op) come from const_in."""
-        self._bind_stream()
-        nimg, H, W, C = x.shape
-        s2 = None
-        if s2_host is not None:
-            s2 = [int(v) for v in s2_host]
-            if len(s2) != nimg:
-                raise ValueError("debug_maxpool: s2_host needs one entry per image")
-            s2 = (ctypes.c_int32 * nimg)(*s2)
-        self._ck(self.lib.jg_debug_maxpool(self.h, _ptr(x), nimg, H, W, C, s2, int(in_op), _ptr(const_in), _ptr(out)))
-
-    def debug_conv_rowmaps(self, s2_host, layers, fill=-1):
-        """Compaction maps of conv layers op = 0 .. len(layers)-1 (launch_conv_rowmaps) for the per-image counts s2_host; layers: (OH, OW) per layer.
-        -> per layer (map int32 [NF*OH*OW], prefilled with `fill`: only the first `total` entries are written; base int32 [NF+1]; total)."""
-        self._bind_stream()
-        s2 = np.ascontiguousarray(np.asarray(s2_host, np.int32))
-        NF, nl = int(s2.size), len(layers)
-        maps = [np.full(NF * oh * ow, fill, np.int32) for oh, ow in layers]
-        bases = [np.full(NF + 1, fill, np.int32) for _ in layers]
-        totals = np.full(max(nl, 1), fill, np.int32)
-        i32p = ctypes.POINTER(ctypes.c_int32)
-        OH = (_I * max(nl, 1))(*[oh for oh, _ in layers])
-        OW = (_I * max(nl, 1))(*[ow for _, ow in layers])
-        mp = (_P * max(nl, 1))(*[m.ctypes.data for m in maps])
-        bp = (_P * max(nl, 1))(*[b.ctypes.data for b in bases])
-        self._ck(self.lib.jg_debug_conv_rowmaps(self.h, s2.ctypes.data_as(i32p), NF, OH, OW, nl, mp, bp, totals.ctypes.data_as(i32p)))
-        return [(maps[l], bases[l], int(totals[l])) for l in range(nl)]
-
-    def debug_gemm32(self, A, lda, W, ldw, M, N, K, out, ldc, scale=None, bias=None, res=None, ldr=0, res_mod=0, act=0):
-        self._bind_stream()
-        self._ck(self.lib.jg_debug_gemm32(self.h, _ptr(A), lda, _ptr(W), ldw, M, N, K, _ptr(scale), _ptr(bias), _ptr(res), ldr, res_mod, act,
-                                          _ptr(out), ldc))
-
-    def debug_conv32(self, x, nimg, H, W, C, KH, KW, SH, SW, PH, PW, reorder, Wt, ldw, N, out, ldc, scale=None, bias=None, act=0):
-        """fp32 implicit-GEMM convolution (launch_gemm32, conv): x (nimg,H,W,C) fp32 NHWC, Wt [N][ldw] fp32 in ConvGeom's tap order."""
-        self._bind_stream()
-        self._ck(self.lib.jg_debug_conv32(self.h, _ptr(x), nimg, H, W, C, KH, KW, SH, SW, PH, PW, int(reorder), _ptr(Wt), ldw, N, _ptr(scale),
-                                          _ptr(bias), act, _ptr(out), ldc))
-
-    def debug_gemm_x3(self, A, lda, Wh, Wl, ldw, M, N, K, out, ldc, bias=None, res=None, ldr=0, res_mod=0, relu=0):
-        self._bind_stream()
-        self._ck(self.lib.jg_debug_gemm_x3(self.h, _ptr(A), lda, _ptr(Wh), _ptr(Wl), ldw, M, N, K, _ptr(bias), _ptr(res), ldr, res_mod, relu,
-                                           _ptr(out), ldc))
-
-    def debug_attention(self, qkv, keymask, B, S, H, dk, out):
-        self._bind_stream()
-        self._ck(self.lib.jg_debug_attention(self.h, _ptr(qkv), _ptr(keymask), B, S, H, dk, _ptr(out)))
-
-    def debug_attention_gather(self, qkv_pos, pe_qkv, Twin, P, shift, B, S, H, out):
-        self._bind_stream()
-        self._ck(self.lib.jg_debug_attention_gather(self.h, _ptr(qkv_pos), _ptr(pe_qkv), Twin, P, shift, B, S, H, _ptr(out)))
-
-    def debug_attention32(self, qkv, keymask, B, S, H, dk, out):
-        self._bind_stream()
-        self._ck(self.lib.jg_debug_attention32(self.h, _ptr(qkv), _ptr(keymask), B, S, H, dk, _ptr(out)))
-
-    # ---- check points of the element-wise and reduction launchers (include/jegal_hip.h): device tensors by pointer, sizes as given -- the
-    # library validates them and raises JegalError(.code == JG_ERR_ARG) before anything is enqueued; `valid`: a sequence of host ints or None
-    @staticmethod
-    def _valid_arg(valid):
-        if valid is None:
-            return None, 0
-        v = [int(x) for x in valid]
-        return (ctypes.c_int32 * max(len(v), 1))(*v), len(v)
-
-    def debug_stack_frames(self, src, strides, B, T, pad, H, W, dst):
-        """strides = (sb, st, sh, sw, sc) in elements of src (uint8 or float32)."""
-        self._bind_stream()
-        sb, st, sh, sw, sc = (int(x) for x in strides)
-        self._ck(self.lib.jg_debug_stack_frames(self.h, _ptr(src), int(src.dtype == torch.uint8), sb, st, sh, sw, sc, src.numel(), B, T, pad, H, W, _ptr(dst)))
-
-    def debug_window_gather(self, conv, pe, B, P, Twin, L, D, shift, tiled, x32, x16):
-        self._bind_stream()
-        self._ck(self.lib.jg_debug_window_gather(self.h, _ptr(conv), _ptr(pe), B, P, Twin, L, D, shift, int(bool(tiled)), _ptr(x32), _ptr(x16)))
-
-    def debug_layernorm(self, x, w, b, rows, D, flavour, relu, out32=None, out16=None):
-        self._bind_stream()
-        self._ck(self.lib.jg_debug_layernorm(self.h, _ptr(x), _ptr(w), _ptr(b), rows, D, flavour, relu, _ptr(out32), _ptr(out16)))
-
-    def debug_layernorm_planes(self, hi, lo, w, b, rows, D, out32):
-        self._bind_stream()
-        self._ck(self.lib.jg_debug_layernorm_planes(self.h, _ptr(hi), _ptr(lo), _ptr(w), _ptr(b), rows, D, _ptr(out32)))
-
-    def debug_group_mean(self, x, groups, L, D, out):
-        self._bind_stream()
-        self._ck(self.lib.jg_debug_group_mean(self.h, _ptr(x), groups, L, D, _ptr(out)))
-
-    def debug_cast(self, x, out, n):
-        self._bind_stream()
-        self._ck(self.lib.jg_debug_cast(self.h, _ptr(x), _ptr(out), n))
-
-    def debug_audio_conv0(self, mel, B, Tm, F, wh, wl, bias, out, valid=None):
-        self._bind_stream()
-        v, n = self._valid_arg(valid)
-        self._ck(self.lib.jg_debug_audio_conv0(self.h, _ptr(mel), B, Tm, F, _ptr(wh), _ptr(wl), _ptr(bias), _ptr(out), v, n))
-
-    def debug_zero_tail(self, x, valid, halvings, B, H, row_elems):
-        self._bind_stream()
-        v, n = self._valid_arg(valid)
-        self._ck(self.lib.jg_debug_zero_tail(self.h, _ptr(x), v, n, halvings, B, H, row_elems))
-
-    # the fp32 clones of the audit mode (audit32.hip)
-    def debug_stack_frames32(self, src, strides, B, T, pad, H, W, dst):
-        self._bind_stream()
-        sb, st, sh, sw, sc = (int(x) for x in strides)
-        u8, elems = (int(src.dtype == torch.uint8), src.numel()) if src is not None else (0, 0)
-        self._ck(self.lib.jg_debug_stack_frames32(self.h, _ptr(src), u8, sb, st, sh, sw, sc, elems, B, T, pad, H, W, _ptr(dst)))
-
-    def debug_maxpool32(self, x, out):
-        """x (nimg,H,W,C) fp32 NHWC -> out (nimg,(H-3)//2+1,(W-3)//2+1,C), written in place."""
-        self._bind_stream()
-        nimg, H, W, C = x.shape
-        self._ck(self.lib.jg_debug_maxpool32(self.h, _ptr(x), nimg, H, W, C, _ptr(out)))
-
-    def debug_group_mean32(self, x, groups, L, D, out):
-        self._bind_stream()
-        self._ck(self.lib.jg_debug_group_mean32(self.h, _ptr(x), groups, L, D, _ptr(out)))
-
-    def debug_zero_tail32(self, x, valid, halvings, B, H, row_elems):
-        self._bind_stream()
-        v, n = self._valid_arg(valid)
-        self._ck(self.lib.jg_debug_zero_tail32(self.h, _ptr(x), v, n, halvings, B, H, row_elems))
-
-    def debug_xlmr_embed(self, ids, B, L, D, pad_id, vocab, maxpos, word, pos, type_, out):
-        self._bind_stream()
-        self._ck(self.lib.jg_debug_xlmr_embed(self.h, _ptr(ids), B, L, D, pad_id, vocab, maxpos, _ptr(word), _ptr(pos), _ptr(type_), _ptr(out)))
-
-    def debug_xlmr_embed_planes(self, ids, B, L, D, pad_id, vocab, maxpos, word, pos, type_, hi, lo, part):
-        self._bind_stream()
-        self._ck(self.lib.jg_debug_xlmr_embed_planes(self.h, _ptr(ids), B, L, D, pad_id, vocab, maxpos, _ptr(word), _ptr(pos), _ptr(type_), _ptr(hi),
-                                                     _ptr(lo), _ptr(part)))
-
-    def debug_ln_stats(self, part, rows, P, stats):
-        self._bind_stream()
-        self._ck(self.lib.jg_debug_ln_stats(self.h, _ptr(part), rows, P, _ptr(stats)))
-
-    def debug_mask_i32_f32(self, x, out, n):
-        self._bind_stream()
-        self._ck(self.lib.jg_debug_mask_i32_f32(self.h, _ptr(x), _ptr(out), n))
-
-    def debug_transpose_tokens(self, x, N, L, D, out):
-        self._bind_stream()
-        self._ck(self.lib.jg_debug_transpose_tokens(self.h, _ptr(x), N, L, D, _ptr(out)))
-
-    def debug_pe_project(self, pe, S, Wh, Wl, bias, N, K, out):
-        self._bind_stream()
-        self._ck(self.lib.jg_debug_pe_project(self.h, _ptr(pe), S, _ptr(Wh), _ptr(Wl), _ptr(bias), N, K, _ptr(out)))
-
-    def debug_broadcast_channels(self, v, C, out, pixels):
-        self._bind_stream()
-        self._ck(self.lib.jg_debug_broadcast_channels(self.h, _ptr(v), C, _ptr(out), pixels))
-
-    def debug_col_sum(self, A, lda, M, K, scratch, out, stats=None):
-        self._bind_stream()
-        self._ck(self.lib.jg_debug_col_sum(self.h, _ptr(A), lda, M, K, _ptr(scratch), scratch.numel(), _ptr(out), _ptr(stats)))
-
-    def debug_rc_bias(self, A, lda, tiled, nclips, rpc, lo, bias, N, K, scratch, out, valid=None):
-        """scratch: float32, at least nclips * K elements; its first nclips * K fp16 values are the clip means afterwards."""
-        self._bind_stream()
-        v, n = self._valid_arg(valid)
-        self._ck(self.lib.jg_debug_rc_bias(self.h, _ptr(A), lda, A.numel(), int(bool(tiled)), nclips, rpc, v, n, _ptr(lo), _ptr(bias), N, K, _ptr(scratch),
-                                           scratch.numel(), _ptr(out)))
-
-    def debug_last_kernel(self):
-        buf = ctypes.create_string_buffer(128)
-        self._ck(self.lib.jg_debug_last_kernel(self.h, buf, 128))
-        return buf.value.decode()
-
-    def debug_conv2_rowskip(self):
-        """Leading conv2 output rows per image that the last conv stack copied instead of computing ("conv2_row_skip")."""
-        rows = ctypes.c_int()
-        self._ck(self.lib.jg_debug_conv2_rowskip(self.h, ctypes.byref(rows)))
-        return rows.value
-
-    def debug_conv_rows(self):
-        """(computed, full) output pixels of conv2 .. conv5 in the last conv stack (per-position row skip)."""
-        c, f = (ctypes.c_int64 * 4)(), (ctypes.c_int64 * 4)()
-        self._ck(self.lib.jg_debug_conv_rows(self.h, c, f))
-        return list(c), list(f)
-
-    def debug_conv1_pool(self, frames_u8, pad):
-        """conv1+BN+ReLU+maxpool only: (B,T,270,480,3) u8 -> (B*(T+2*pad-4),43,78,64) fp16 NHWC."""
-        self._bind_stream()
-        frames_u8 = frames_u8.to(self.device).contiguous()
-        B, T = frames_u8.shape[:2]
-        out = torch.empty((B * (T + 2 * pad - 4), 43, 78, 64), dtype=torch.float16, device=self.device)
-        self._ck(self.lib.jg_debug_conv1_pool(self.h, _ptr(frames_u8), B, T, pad, _ptr(out)))
-        return out
-
     def gestsync_windows(self, x, return_feats=False):
         self._bind_stream()
         x = self._f32(x)
@@ -782,22 +422,6 @@ class Engine(MetricEntries):
         out = torch.empty((B, int(T), 1024), dtype=torch.float32, device=self.device)
         self._ck(self.lib.jg_gestsync_audio_clip(self.h, _ptr(mel), B, Tm, int(T), v, _ptr(out)))
         return out
-
-    def debug_gsa_conv1_pool(self, src, w, shift, out, T=None, lengths=None):
-        """One launch of gsa_conv1_pool_kernel: src (N,1,80,100) (T None) or mel (B,Tm,80) with T windows per clip; w (64,9) / shift (64,) fp32
-        device tensors; out (windows,19,24,64) fp16 or fp32, written in place."""
-        self._bind_stream()
-        clip = T is not None
-        B, Tm = (src.shape[0], src.shape[1]) if clip else (src.shape[0], 0)
-        v = None if lengths is None else (ctypes.c_int32 * B)(*[int(x) for x in lengths])
-        self._ck(self.lib.jg_debug_gsa_conv1_pool(self.h, _ptr(src), int(clip), B, Tm, int(T) if clip else 1, v, _ptr(w), _ptr(shift), _ptr(out),
-                                                  int(out.dtype == torch.float32)))
-
-    def debug_maxpool_2x3(self, x, out):
-        """One launch of maxpool_2x3_s2_kernel: x (nimg,H,W,C) fp16 or fp32 NHWC -> out (nimg,(H-2)//2+1,(W-3)//2+1,C), written in place."""
-        self._bind_stream()
-        nimg, H, W, C = x.shape
-        self._ck(self.lib.jg_debug_maxpool_2x3(self.h, _ptr(x), nimg, H, W, C, _ptr(out), int(x.dtype == torch.float32)))
 
     def extract_gesture(self, frames, out=None):
         """frames -> unit-norm gesture embedding (B,T,512), one library call."""
@@ -854,15 +478,6 @@ class Engine(MetricEntries):
             raise ValueError(f"frames must be one track (T,270,480,3), got {tuple(frames.shape)}")
         feats = self.gestsync_clip(frames[None])[0]
         return self.jegal_gesture_tracks(feats, [feats.shape[0]], win=win, ctx=ctx, align=True, normalize=True)
-
-    def debug_span_gather(self, p32, pe, table, n_windows, span_max, D, x32, mask):
-        self._bind_stream()
-        self._ck(self.lib.jg_debug_span_gather(self.h, _ptr(p32), _ptr(pe), _ptr(table), n_windows, span_max, D, _ptr(x32), _ptr(mask)))
-
-    def debug_core_compact(self, x, table, n_windows, span_max, D, out):
-        """x (n_windows, span_max, D) of 2- or 4-byte elements; out rows of the same type, written in place."""
-        self._bind_stream()
-        self._ck(self.lib.jg_debug_core_compact(self.h, _ptr(x), x.element_size(), _ptr(table), n_windows, span_max, D, _ptr(out)))
 
     def audio_len(self, Tm):
         return int(self.lib.jg_audio_len(int(Tm)))

@@ -27,7 +27,8 @@ def test_library_exports_every_declared_symbol():
     lib = ctypes.CDLL(os.path.join(ROOT, "jegal_amd", "libjegal_hip.so"))
     for name in declared:
         assert hasattr(lib, name), f"{name} declared in include/jegal_hip.h but not exported"
-    from jegal_amd import _lib
+    from jegal_amd import _abi, _lib
+    assert set(_abi.FUNCTIONS) == set(declared)          # a prototype the binding's parser cannot read must not go missing quietly
     assert set(_lib.EXPORTS) == set(declared)
 
 
