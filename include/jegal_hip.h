@@ -636,6 +636,50 @@ int jg_sim_coupling(jg_handle* h, const float* words, const int32_t* w_offsets_h
  * query tiles in place of the query blocks; *ws_bytes = S n_queries k 8 (0 when S == 1).  JG_ERR_ARG where jg_sim_coupling refuses. */
 int jg_debug_coupling_plan(const int32_t* w_offsets_host, int n_queries, int n_gallery, int k, int num_cu, int slices_in,
                            int32_t* tile_first_query, int* n_tiles, int* slices, int* rows_per_slice, int64_t* ws_bytes);
+/* Ordered coupling: jg_sim_coupling with the words of a query assigned to rows of the group IN WORD ORDER (speech is ordered, and a gesture
+ * is time-locked to its word).  The parameter list, the operands and everything jg_sim_coupling documents carry over unchanged: the limits
+ * and the refusals before anything is enqueued or written, the HOST w_offsets and the DEVICE g_offsets with their safety rule (read at 0 ..
+ * n_groups only, only compared with row numbers), -0.0 as +0.0, idx = group_offset + g best first with ties to the smaller group and -1 /
+ * -inf where there are fewer, merge at group boundaries, the optional group-major pair (NaN-filled first), slices and the lists in the
+ * workspace (jg_debug_coupling_plan is the plan of this entry too), the two host tables, asynchronous execution.  Only the score differs.
+ * With s(w, t) as for jg_sim_coupling, a query's words w_1 .. w_W, and t counting the rows of the group [a, b) clamped to 0 .. n_gallery
+ * from a, T = b - a:
+ *   M_0(t) = +0.0 for all t;  for i = 1 .. W:  E_i(t) = M_(i-1)(t) + s(w_i, t), one fp32 add, NaN when either operand is;
+ *   M_i(t) = the max of the non-NaN E_i(t') over t' <= t, NaN when there is none;
+ *   score(q, g) = M_W(T - 1) / (float)W, a correctly rounded fp32 division; none (NaN in pair, never a candidate) when M_W(T - 1) is NaN
+ *   or the group has no row.
+ * That is the best mean of s(w_i, t_i) over the assignments t_1 <= t_2 <= .. <= t_W -- one row may serve consecutive words, so a query
+ * may have more words than the group has rows -- with the sum as one fp32 chain in word order and an exact max: a score depends on the
+ * rows of its query and its group only.  With W = 1 it is jg_sim_topk_grouped's score bit for bit; it never exceeds jg_sim_coupling's (fp32
+ * addition is monotone) and equals it bit for bit where the words' first arg-max rows are non-decreasing already.
+ * jg_debug_last_kernel names the launch ("a+b" with the reduction of more than one slice; the NaN fill is not named). */
+int jg_sim_ordered(jg_handle* h, const float* words, const int32_t* w_offsets_host, int n_queries, const void* gallery,
+                   int gallery_dtype /* JG_F32 | JG_F16 */, int n_gallery, int D, int k, const int32_t* g_offsets /* device */, int n_groups,
+                   int group_offset, int merge, int slices /* 0: the library chooses */, int32_t* idx, float* score,
+                   float* pair /* optional */, int64_t pair_ld);
+/* The rows behind a result of jg_sim_coupling (ordered == 0) or jg_sim_ordered (ordered != 0): for every returned (query, group) pair, the
+ * row each word took.  words .. group_offset: the operands of that call (this piece's, for merged pieces).  idx [n_queries][k], device: its
+ * result.  Slot (q, r) is handled iff group_offset <= idx[q][r] < group_offset + n_groups; a slot holding -1 or a group of another piece
+ * is not, and its entries of frames and score stay exactly as they were: a caller of merged pieces initialises the two to -1 / NaN and
+ * passes every piece with the final idx.
+ * A handled slot: frames[(q k + r) frames_ld + i] = the call's local gallery row a + t_i of word i for i < W_q, -1 for W_q <= i < frames_ld;
+ * score[q k + r] = the pair's score, bit for bit jg_sim_ordered's (ordered != 0) or jg_sim_coupling's (ordered == 0).
+ *   ordered: t_W = the first arg-max of E_W over [0, T); t_i = the first arg-max of E_i over [0, t_(i+1)] for i = W - 1 .. 1; the rows are
+ *   non-decreasing, and s at them, added in word order in fp32 and divided by W, is the score.
+ *   unordered: t_i = the first arg-max row of s(w_i, .) in the group, where jg_sim_coupling's m(w_i, g) comes from.
+ * A handled slot whose pair has no score, or whose group has more than 8192 rows (the limit of jg_spot and jg_attn_matrix), gets -1 in all
+ * frames_ld entries and NaN.
+ * One workgroup per slot recomputes the group's 64-row tiles for the query's words, keeps one bit per (word, row) -- did this row raise the
+ * word's running max -- and backtracks through the bits.  g_offsets is read at the slot's group and the next only, and only clamped and
+ * compared; idx is only compared.
+ * Limits as for jg_sim_coupling (words per query, k, D, alignment, w_offsets_host, counts, group_offset, dtype) and frames_ld >= the longest
+ * query; a violated limit or a null buffer returns JG_ERR_ARG before anything is enqueued or written.  n_queries == 0 returns JG_OK and
+ * launches nothing.  Nothing outside the n_queries * k * frames_ld entries of frames and the n_queries * k entries of score is written.
+ * The workspace pass holds the uploaded w_offsets only.  jg_debug_last_kernel names the launch.  Asynchronous. */
+int jg_sim_align(jg_handle* h, const float* words, const int32_t* w_offsets_host, int n_queries, const void* gallery,
+                 int gallery_dtype /* JG_F32 | JG_F16 */, int n_gallery, int D, const int32_t* g_offsets /* device */, int n_groups,
+                 int group_offset, const int32_t* idx /* device, [n_queries][k] */, int k, int ordered, int32_t* frames, int frames_ld,
+                 float* score);
 /* The rows jg_sim_topk_grouped returns, back to (group, position inside the group), on the device: grp[e] = the group whose range holds
  * idx[e] - gallery_offset, pos[e] = the row's offset inside it; both -1 for idx[e] < 0 or a row in no group.  An element-wise binary
  * search over g_offsets (device, [n_groups + 1]); a caller of merged calls passes its global offsets with gallery_offset = 0.  n, n_groups,

@@ -191,37 +191,91 @@ class MetricEntries:
         depend on its query's and its group's rows only.  merge_into = (idx, score) of an earlier call with the same queries and k on OTHER
         groups (group_offset): updated in place to the best k of the union.  slices as for sim_search.  want_matrix: also the
         (n, groups) matrix of all scores of this call (NaN where a pair has none), a transposed view of the group-major buffer."""
+        return self._sim_coupling("sim_coupling", words, w_offsets, gallery, g_offsets, k, group_offset, merge_into, slices, want_matrix)
+
+    def sim_ordered(self, words, w_offsets, gallery, g_offsets, k, group_offset=0, merge_into=None, slices=0, want_matrix=False):
+        """jg_sim_ordered: sim_coupling with the words of a query assigned to rows of the group in word order -- the score is the best mean
+        of <word i, row t_i> over t_1 <= t_2 <= .. <= t_W (one row may serve consecutive words), the sum one float32 chain in word order.
+        Arguments, checks and returns are sim_coupling's; a score never exceeds sim_coupling's and equals it where the words' best rows
+        are in order already."""
+        return self._sim_coupling("sim_ordered", words, w_offsets, gallery, g_offsets, k, group_offset, merge_into, slices, want_matrix)
+
+    def _phrase_operands(self, entry, words, w_offsets, gallery, g_offsets, group_offset):
+        """What sim_coupling, sim_ordered and sim_align check of their shared operands before anything else
+        -> (shape of words, shape of gallery, host w_offsets, queries, groups, group_offset)"""
         dtype = getattr(gallery, "dtype", None)
         if dtype not in (torch.float32, torch.float16, np.dtype(np.float32), np.dtype(np.float16)):
             raise ValueError("gallery must be a float32 or float16 tensor or array")
-        slices, group_offset = int(slices), int(group_offset)
-        if not 0 <= slices <= SIM_SEARCH_MAX_SLICES:
-            raise ValueError(f"jg_sim_coupling limit: 0 <= slices <= {SIM_SEARCH_MAX_SLICES} (0: the library chooses)")
+        group_offset = int(group_offset)
         ws, gs = _row_pair(words, gallery, "words / gallery")
         woh = _offsets(w_offsets, ws[0], "w_offsets")
         if woh[0] != 0:
             raise ValueError("w_offsets must start at 0")
-        _within(np.diff(woh), 1, COUPLING_MAX_W, "jg_sim_coupling limits: word rows per query")
-        n = woh.size - 1
+        _within(np.diff(woh), 1, COUPLING_MAX_W, f"jg_{entry} limits: word rows per query")
         n_groups = len(_offsets(g_offsets, gs[0], "g_offsets", host=False)) - 1
         if group_offset < 0 or group_offset + n_groups > INT32_MAX:
             raise ValueError("group_offset must be >= 0 and group_offset + groups <= INT32_MAX")
+        return ws, gs, woh, woh.size - 1, n_groups, group_offset
+
+    def _sim_coupling(self, entry, words, w_offsets, gallery, g_offsets, k, group_offset, merge_into, slices, want_matrix):
+        """The body of sim_coupling and sim_ordered (`entry`): the two differ in the C entry they call and in nothing else."""
+        if getattr(gallery, "dtype", None) is None:        # (first, as ever: _phrase_operands names the types)
+            raise ValueError("gallery must be a float32 or float16 tensor or array")
+        slices = int(slices)
+        if not 0 <= slices <= SIM_SEARCH_MAX_SLICES:
+            raise ValueError(f"jg_{entry} limit: 0 <= slices <= {SIM_SEARCH_MAX_SLICES} (0: the library chooses)")
+        ws, gs, woh, n, n_groups, group_offset = self._phrase_operands(entry, words, w_offsets, gallery, g_offsets, group_offset)
         if slices and 1 <= int(k) <= SIM_TOPK_MAX_K and gs[0] <= INT32_MAX:
             from ._lib import JegalError, coupling_plan    # (the planner is a host function of the library: no handle, no device)
             try:
                 coupling_plan(woh, gs[0], int(k), slices=slices)
             except JegalError:
-                raise ValueError(f"jg_sim_coupling limit: {slices} slices of {n} x {int(k)} keys exceed {SIM_SEARCH_MAX_WS} bytes") from None
+                raise ValueError(f"jg_{entry} limit: {slices} slices of {n} x {int(k)} keys exceed {SIM_SEARCH_MAX_WS} bytes") from None
         # k and merge_into as the top-k entries check them, with one row of the result per QUERY: (n, D) stands for the queries
-        _, m, D, k, _, _, idx, score = self._sim_topk_args("sim_coupling", np.broadcast_to(np.float32(0), (n, ws[1])), gallery, k, 0, merge_into)
+        _, m, D, k, _, _, idx, score = self._sim_topk_args(entry, np.broadcast_to(np.float32(0), (n, ws[1])), gallery, k, 0, merge_into)
         w, g, off = self._f32(words), torch.as_tensor(gallery, device=self.device).contiguous(), self._i32(g_offsets)
         pair = torch.full((n_groups, n), float("nan"), dtype=torch.float32, device=self.device) if want_matrix else None
         if n and m and n_groups:                       # (no gallery row, no group: nothing to merge, or the empty result)
             wo = np.ascontiguousarray(woh, np.int32)
-            self._ck(self.lib.jg_sim_coupling(self.h, _ptr(w), wo.ctypes.data_as(ctypes.c_void_p), n, _ptr(g),
-                                              1 if g.dtype == torch.float16 else 0, m, D, k, _ptr(off), n_groups, group_offset,
-                                              int(merge_into is not None), slices, _ptr(idx), _ptr(score), _ptr(pair), n))
+            self._ck(getattr(self.lib, "jg_" + entry)(self.h, _ptr(w), wo.ctypes.data_as(ctypes.c_void_p), n, _ptr(g),
+                                                      1 if g.dtype == torch.float16 else 0, m, D, k, _ptr(off), n_groups, group_offset,
+                                                      int(merge_into is not None), slices, _ptr(idx), _ptr(score), _ptr(pair), n))
         return (idx, score, pair.t()) if want_matrix else (idx, score)
+
+    def sim_align(self, words, w_offsets, gallery, g_offsets, idx, ordered, group_offset=0, into=None):
+        """jg_sim_align: the rows behind a result of sim_coupling (ordered False) or sim_ordered (True).  words .. g_offsets and group_offset:
+        the operands of that call; idx (n, k) int32 on the device: its result.  Returns device tensors (frames (n, k, Wmax) int32, score
+        (n, k) float32), Wmax = the longest query: frames[q, r, i] = the row of `gallery` that word i of query q took in the group idx[q, r]
+        (-1 behind the query's words, or where the pair has no score or the group more than 8192 rows), score the pair's score with the bits
+        of the call that made idx.  Only slots whose idx lies in group_offset .. group_offset + groups - 1 are written; the others keep -1
+        / NaN, or what `into` = (frames, score) of an earlier call held: merged pieces are aligned piece by piece with the final idx."""
+        ws, gs, woh, n, n_groups, group_offset = self._phrase_operands("sim_align", words, w_offsets, gallery, g_offsets, group_offset)
+        if not isinstance(idx, torch.Tensor) or idx.dtype != torch.int32 or idx.ndim != 2 or idx.shape[0] != n or not idx.is_contiguous():
+            raise ValueError(f"idx must be the contiguous int32 ({n}, k) tensor of sim_coupling or sim_ordered")
+        k = int(idx.shape[1])
+        if not 1 <= k <= SIM_TOPK_MAX_K:
+            raise ValueError(f"jg_sim_align limit: 1 <= k <= {SIM_TOPK_MAX_K}")
+        wmax = int(np.diff(woh).max()) if n else 1
+        if into is not None:
+            if not isinstance(into, (tuple, list)) or len(into) != 2 or not all(isinstance(t, torch.Tensor) for t in into):
+                raise ValueError("into must be the (frames, score) pair of an earlier sim_align call")
+            frames, score = into
+            if (tuple(frames.shape) != (n, k, wmax) or tuple(score.shape) != (n, k) or frames.dtype != torch.int32 or score.dtype != torch.float32
+                    or not frames.is_contiguous() or not score.is_contiguous()):
+                raise ValueError(f"into must be contiguous (frames int32 ({n}, {k}, {wmax}), score float32 ({n}, {k})) tensors")
+        if idx.device != self.device or (into is not None and (frames.device != self.device or score.device != self.device)):
+            raise ValueError(f"idx and into must be on {self.device}")
+        self._bind_stream()
+        if into is None:
+            frames = torch.full((n, k, wmax), -1, dtype=torch.int32, device=self.device)
+            score = torch.full((n, k), float("nan"), dtype=torch.float32, device=self.device)
+        w, g, off = self._f32(words), torch.as_tensor(gallery, device=self.device).contiguous(), self._i32(g_offsets)
+        if n and gs[0] and n_groups:
+            wo = np.ascontiguousarray(woh, np.int32)
+            self._ck(self.lib.jg_sim_align(self.h, _ptr(w), wo.ctypes.data_as(ctypes.c_void_p), n, _ptr(g), 1 if g.dtype == torch.float16 else 0,
+                                           gs[0], ws[1], _ptr(off), n_groups, group_offset, _ptr(idx), k, int(bool(ordered)), _ptr(frames), wmax,
+                                           _ptr(score)))
+        return frames, score
 
     def group_of_rows(self, idx, g_offsets, gallery_offset=0):
         """jg_group_of_rows: the rows sim_topk_grouped returned (an int32 tensor of any shape) -> (grp, pos) int32 device tensors of that

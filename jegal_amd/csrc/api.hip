@@ -612,16 +612,18 @@ int jg_sim_search(jg_handle* h, const float* queries, int n_queries, const void*
     return rc;
 }
 
-int jg_sim_coupling(jg_handle* h, const float* words, const int32_t* w_offsets_host, int n_queries, const void* gallery, int gallery_dtype,
-                    int n_gallery, int D, int k, const int32_t* g_offsets, int n_groups, int group_offset, int merge, int slices, int32_t* idx,
-                    float* score, float* pair, int64_t pair_ld) {
+// jg_sim_coupling and jg_sim_ordered: one entry, two launchers with one signature (`entry` names the caller in the geometry message)
+using CouplingLauncher = decltype(&launch_sim_coupling);
+static int coupling_entry(jg_handle* h, const char* entry, CouplingLauncher launcher, const float* words, const int32_t* w_offsets_host,
+                          int n_queries, const void* gallery, int gallery_dtype, int n_gallery, int D, int k, const int32_t* g_offsets,
+                          int n_groups, int group_offset, int merge, int slices, int32_t* idx, float* score, float* pair, int64_t pair_ld) {
     if (!h) return JG_ERR_ARG;
     const KernelNameScope kn(h->kname);          // the launch depends on the plan, as in jg_sim_search
     ENTER(h);
     if (!words || !w_offsets_host || !gallery || !idx || !score || (n_groups > 0 && !g_offsets)) JG_FAIL(h, JG_ERR_ARG, "null buffer");
     if (gallery_dtype != JG_F32 && gallery_dtype != JG_F16) JG_FAIL(h, JG_ERR_ARG, "gallery_dtype must be JG_F32 or JG_F16");
     // (the check of the top-k entries, with the groups as what group_offset numbers)
-    RET(sim_topk_check(h, "sim_coupling", words, static_cast<const float*>(gallery), n_queries, n_gallery, D, k, n_groups, 0));
+    RET(sim_topk_check(h, entry, words, static_cast<const float*>(gallery), n_queries, n_gallery, D, k, n_groups, 0));
     if (group_offset < 0 || group_offset > INT32_MAX - n_groups) JG_FAIL(h, JG_ERR_ARG, "group_offset >= 0, group_offset + n_groups <= INT32_MAX");
     if (pair && (pair_ld < n_queries || (reinterpret_cast<uintptr_t>(pair) & 3))) JG_FAIL(h, JG_ERR_ARG, "pair needs pair_ld >= n_queries");
     const bool no_rows = n_gallery == 0 || n_groups == 0;
@@ -640,9 +642,54 @@ int jg_sim_coupling(jg_handle* h, const float* words, const int32_t* w_offsets_h
     if (plan.cut.slices > 1) RET(wsalloc(h, (size_t)(plan.cut.ws_bytes / 8), &keys));
     RET(upload_i32_async(h, tables.data(), (size_t)n_queries + 1 + plan.n_tiles + 1, tables_dev));
     if (pair) RET(misc_launch(h, launch_coupling_fill, pair, (long)pair_ld, n_queries, n_groups));
-    const int rc = misc_launch(h, launch_sim_coupling, words, tables_dev, tables_dev + n_queries + 1, plan.n_tiles, gallery, gallery_dtype == JG_F16,
+    const int rc = misc_launch(h, launcher, words, tables_dev, tables_dev + n_queries + 1, plan.n_tiles, gallery, gallery_dtype == JG_F16,
                                n_queries, n_gallery, D, k, g_offsets, n_groups, group_offset, merge, idx, score, pair, (long)pair_ld,
                                plan.cut.slices, plan.cut.slice_rows, keys);
+    if (rc != JG_OK) h->kname[0] = 0;
+    return rc;
+}
+
+int jg_sim_coupling(jg_handle* h, const float* words, const int32_t* w_offsets_host, int n_queries, const void* gallery, int gallery_dtype,
+                    int n_gallery, int D, int k, const int32_t* g_offsets, int n_groups, int group_offset, int merge, int slices, int32_t* idx,
+                    float* score, float* pair, int64_t pair_ld) {
+    return coupling_entry(h, "sim_coupling", launch_sim_coupling, words, w_offsets_host, n_queries, gallery, gallery_dtype, n_gallery, D, k,
+                          g_offsets, n_groups, group_offset, merge, slices, idx, score, pair, pair_ld);
+}
+
+int jg_sim_ordered(jg_handle* h, const float* words, const int32_t* w_offsets_host, int n_queries, const void* gallery, int gallery_dtype,
+                   int n_gallery, int D, int k, const int32_t* g_offsets, int n_groups, int group_offset, int merge, int slices, int32_t* idx,
+                   float* score, float* pair, int64_t pair_ld) {
+    return coupling_entry(h, "sim_ordered", launch_sim_ordered, words, w_offsets_host, n_queries, gallery, gallery_dtype, n_gallery, D, k,
+                          g_offsets, n_groups, group_offset, merge, slices, idx, score, pair, pair_ld);
+}
+
+int jg_sim_align(jg_handle* h, const float* words, const int32_t* w_offsets_host, int n_queries, const void* gallery, int gallery_dtype,
+                 int n_gallery, int D, const int32_t* g_offsets, int n_groups, int group_offset, const int32_t* idx, int k, int ordered,
+                 int32_t* frames, int frames_ld, float* score) {
+    if (!h) return JG_ERR_ARG;
+    const KernelNameScope kn(h->kname);
+    ENTER(h);
+    if (!words || !w_offsets_host || !gallery || !idx || !frames || !score || (n_groups > 0 && !g_offsets)) JG_FAIL(h, JG_ERR_ARG, "null buffer");
+    if (gallery_dtype != JG_F32 && gallery_dtype != JG_F16) JG_FAIL(h, JG_ERR_ARG, "gallery_dtype must be JG_F32 or JG_F16");
+    RET(sim_topk_check(h, "sim_align", words, static_cast<const float*>(gallery), n_queries, n_gallery, D, k, n_groups, 0));
+    if (group_offset < 0 || group_offset > INT32_MAX - n_groups) JG_FAIL(h, JG_ERR_ARG, "group_offset >= 0, group_offset + n_groups <= INT32_MAX");
+    // the word offsets as jg_sim_coupling takes them: its plan is the check (one slice: no lists to size)
+    std::vector<int32_t> tfq((size_t)n_queries + 1);
+    CouplingPlan plan;
+    if (!sim_coupling_plan(w_offsets_host, n_queries, 0, k, h->opts.num_cu, 1, tfq.data(), plan))
+        JG_FAIL(h, JG_ERR_ARG, "w_offsets must start at 0 and give every query 1..%d word rows", COUPLING_MAX_W);
+    int longest = 0;
+    for (int q = 0; q < n_queries; ++q) longest = std::max(longest, (int)(w_offsets_host[q + 1] - w_offsets_host[q]));
+    if (frames_ld < longest || frames_ld < 1) JG_FAIL(h, JG_ERR_ARG, "frames_ld must hold the longest query (%d word rows)", longest);
+    if ((reinterpret_cast<uintptr_t>(frames) | reinterpret_cast<uintptr_t>(score) | reinterpret_cast<uintptr_t>(idx)) & 3)
+        JG_FAIL(h, JG_ERR_ARG, "idx, frames and score must be 4-byte aligned");
+    if (n_queries == 0) return JG_OK;
+    RET(begin_pass(h));
+    int32_t* woff_dev = nullptr;
+    RET(wsalloc(h, (size_t)n_queries + 1, &woff_dev));
+    RET(upload_i32_async(h, w_offsets_host, (size_t)n_queries + 1, woff_dev));
+    const int rc = misc_launch(h, launch_sim_align, words, woff_dev, gallery, gallery_dtype == JG_F16, n_queries, n_gallery, D, g_offsets, n_groups,
+                               group_offset, idx, k, ordered, frames, frames_ld, score);
     if (rc != JG_OK) h->kname[0] = 0;
     return rc;
 }

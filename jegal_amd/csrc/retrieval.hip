@@ -582,6 +582,308 @@ hipError_t launch_sim_coupling(const float* words, const int32_t* woff, const in
                                          n_groups, group_offset, merge, idx, score, pair, pair_ld, slices, slice_rows, keys, s);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Ordered coupling (jg_sim_ordered): the queries, groups, tiles, slices and lists of jg_sim_coupling, with the words of a query assigned to
+// frames of the group in word order.  With t counted from the group's first row and s(w, t) as above (-0.0 as +0.0):
+//   M_0(t) = +0.0;  E_i(t) = M_{i-1}(t) + s(w_i, t) (one fp32 add, NaN if either is);  M_i(t) = the max of the non-NaN E_i(t'), t' <= t
+// (NaN: none), and score(q, g) = M_W(T - 1) / W: the best mean of s(w_i, t_i) over t_1 <= t_2 <= .. <= t_W, the sum one fp32 chain in word
+// order.  Nothing in it depends on where a tile or a slice ends, so the bits do not either.
+//
+// The walk is sim_coupling_kernel's, unchanged.  What differs is a segment (the columns [b, e) of a group inside a tile): the tile's scores
+// go to LDS as sS[word row][column] once per tile, and every query of the tile is taken by one wave (query i by wave i & 3), lane = column.
+// The wave runs down the query's word rows: one LDS value, one add, an inclusive fmax prefix scan over the 64 lanes with the lanes outside
+// the segment as NaN (fmaxf returns the other operand), and an fmax with the word's carry sCarry[row] = M_i at the last column of the
+// tiles before -- M_i is non-decreasing in t, so that one value stands for all of them.  Lane 63 of the result is the new carry.  A query's
+// rows are touched by its own wave only; the barrier in front of a segment orders them against the tile's stores and against the threads
+// that read the last carries when the group before ended.  NaN propagates by itself: a word without a value leaves M_i NaN everywhere, so
+// every later E is NaN and so is M_W: the pair has no score.
+__device__ __forceinline__ float wave_fmax_scan(float v, int lane) {     // inclusive, over the lanes 0 .. lane; NaN = none
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const float u = __shfl_up(v, o, 64);
+        if (lane >= o) v = fmaxf(v, u);
+    }
+    return v;
+}
+// the tile in acc -> sS[word row][column], -0.0 as +0.0
+__device__ __forceinline__ void sim_tile_store(const f32x16& acc, float (*sS)[64], int tid) {
+    const int col = sim_tile_col(tid);
+#pragma unroll
+    for (int x = 0; x < 16; ++x) sS[sim_tile_row(x, tid)][col] = acc[x] == 0.f ? 0.f : acc[x];
+}
+
+template <class GT, int LCAP>
+__global__ __launch_bounds__(256) void sim_ordered_kernel(const float* __restrict__ words, const int32_t* __restrict__ woff,
+                                                          const int32_t* __restrict__ tfq, const GT* __restrict__ gallery, int n_queries,
+                                                          int n_gallery, int D, int k, const int32_t* __restrict__ goff, int n_groups,
+                                                          int group_offset, int merge, int32_t* __restrict__ idx, float* __restrict__ score,
+                                                          float* __restrict__ pair, long pair_ld, int slice_rows, u64* __restrict__ keys) {
+    __shared__ __attribute__((aligned(16))) u64 sStage[64 * 64];       // staging (sA, sB) during a tile's k loop, the queues after it
+    __shared__ u64 sL[64][LCAP];
+    __shared__ u64 sThr[64];
+    __shared__ int sCnt[64];
+    __shared__ float sS[64][64];                                       // the tile's scores, [word row][column]
+    __shared__ float sCarry[64];                                       // the open group's M_i at the last column so far, per word row
+    __shared__ int sW[65];                                             // the tile's queries as word rows of the tile
+    float (*sA)[64] = reinterpret_cast<float (*)[64]>(sStage);
+    float (*sB)[64] = sA + 64;
+    u64 (*sQ)[64] = reinterpret_cast<u64 (*)[64]>(sStage);             // [query of the tile][slot]
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int q0 = tfq[blockIdx.x], q1 = tfq[blockIdx.x + 1], nq = q1 - q0;
+    const int row0 = woff[q0], row1 = woff[q1];
+    if (tid <= nq) sW[tid] = woff[q0 + tid] - row0;
+    topk_seed<LCAP>(sL, sCnt, sThr, k, wave, lane, q0, q1, merge, idx, score);
+
+    // the first group this slice owns (g, rows [lo, hi)); n_groups: none
+    const long lim_lo = (long)blockIdx.y * slice_rows, lim_hi = lim_lo + slice_rows;
+    int g = n_groups, lo = 0, hi = 0;
+    if (n_groups > 0 && lim_lo < n_gallery) {
+        if (lim_lo <= goff[0]) {
+            g = 0; lo = goff[0]; hi = goff[1];
+        } else if (lim_lo < goff[n_groups]) {
+            g = group_range(goff, n_groups, (int)lim_lo, lo, hi);
+            if (lo != lim_lo) { ++g; lo = hi; hi = g < n_groups ? goff[g + 1] : lo; }      // it began before the slice: another's
+        }
+    }
+    auto next_group = [&] { ++g; lo = hi; if (g < n_groups) hi = goff[g + 1]; };
+    auto flush = [&] {
+        __syncthreads();
+        topk_flush<LCAP, false>(sL, sQ, sCnt, sThr, k, wave, lane, nullptr, 0, 0u);
+    };
+
+    int pos = (int)(lim_lo < n_gallery ? lim_lo : n_gallery);      // columns below it are consumed (or another slice's)
+    int j0 = -64;                                                    // the tile in sS: none yet
+    bool queued = false;                                             // a group has ended in this tile
+    __syncthreads();                                                 // sW and the seeded lists
+    for (;;) {
+        // the next owned group with a column; a group without one has no score
+        while (g < n_groups && lo < lim_hi && (hi < n_gallery ? hi : n_gallery) <= (lo > pos ? lo : pos)) next_group();
+        if (g >= n_groups || lo >= lim_hi) break;
+        int b = lo > pos ? lo : pos;
+        const int e = hi < n_gallery ? hi : n_gallery;               // its columns [b, e), b < e
+        bool first = true;
+        for (;;) {                                                   // its segments, one per tile
+            if (b >= (long)j0 + 64) {
+                if (queued) { flush(); queued = false; }
+                j0 = b & ~63;
+                // (the barriers inside sim_tile: every wave has finished the segments of the tile before, so sS may be written)
+                const f32x16 acc = sim_tile(words, gallery, row0, j0, row1, n_gallery, D, sA, sB, tid);
+                sim_tile_store(acc, sS, tid);
+            }
+            const int se = e < (long)j0 + 64 ? e : j0 + 64;                  // (long: the last tile of 2^31 - 1 rows ends past INT32_MAX)
+            const long col = (long)j0 + lane;
+            const bool in = col >= b && col < se;
+            __syncthreads();                                         // sS is whole, and the carries of the group before have been read
+            for (int i = wave; i < nq; i += 4) {
+                float m = 0.f;                                       // M_0
+                for (int r = sW[i]; r < sW[i + 1]; ++r) {
+                    const float ev = in ? m + sS[r][lane] : __uint_as_float(0x7fc00000u);
+                    m = wave_fmax_scan(ev, lane);
+                    if (!first) m = fmaxf(m, sCarry[r]);
+                    if (lane == 63) sCarry[r] = m;
+                }
+            }
+            first = false;
+            b = se;
+            if (b >= e) break;
+        }
+        // the group has ended: query i of the tile, by thread i
+        __syncthreads();
+        if (tid < nq) {
+            const int w0 = sW[tid], w1 = sW[tid + 1];
+            const float m = sCarry[w1 - 1];                          // M_W(T - 1)
+            const float sc = __fdiv_rn(m, (float)(w1 - w0));
+            if (m == m) {
+                if (pair) pair[(long)g * pair_ld + q0 + tid] = sc;
+                const u64 key = topk_key(sc, (unsigned)group_offset + (unsigned)g);
+                if (sc == sc && key > sThr[tid]) sQ[tid][sCnt[tid]++] = key;
+            }
+        }
+        queued = true;
+        pos = e;
+        next_group();
+    }
+    if (queued) flush();
+    // a wave stores the lists of the queries it seeded and flushed itself
+    if (keys) {
+        for (int rr = 0; rr < 16; ++rr) {
+            const int row = wave * 16 + rr;
+            if (row >= nq) break;
+            const long base = ((long)blockIdx.y * n_queries + q0 + row) * k;
+            for (int p = lane; p < k; p += 64) keys[base + p] = sL[row][p];
+        }
+    } else {
+        topk_store<LCAP>(sL, k, wave, lane, q0, q1, idx, score);
+    }
+}
+
+template <class GT>
+static hipError_t launch_ordered(const float* words, const int32_t* woff, const int32_t* tfq, int n_tiles, const GT* gallery, int n_queries,
+                                 int n_gallery, int D, int k, const int32_t* g_offsets, int n_groups, int group_offset, int merge, int32_t* idx,
+                                 float* score, float* pair, long pair_ld, int slices, int slice_rows, u64* keys, hipStream_t s) {
+    const char* const gt = sizeof(GT) == 2 ? "_Float16" : "float";
+    const int L = k <= 64 ? 64 : 128;
+    const auto kernel = k <= 64 ? sim_ordered_kernel<GT, 64> : sim_ordered_kernel<GT, 128>;
+    if (slices == 1) {
+        record_kernel("sim_ordered_kernel<%s,%d>", gt, L);
+        hipLaunchKernelGGL(kernel, dim3(n_tiles), dim3(256), 0, s, words, woff, tfq, gallery, n_queries, n_gallery, D, k, g_offsets, n_groups,
+                           group_offset, merge, idx, score, pair, pair_ld, slice_rows, (u64*)nullptr);
+        return hipGetLastError();
+    }
+    record_kernel("sim_ordered_kernel<%s,%d>+sim_topk_reduce_kernel<%d,0>", gt, L, L);
+    hipLaunchKernelGGL(kernel, dim3(n_tiles, slices), dim3(256), 0, s, words, woff, tfq, gallery, n_queries, n_gallery, D, k, g_offsets, n_groups,
+                       group_offset, 0, idx, score, pair, pair_ld, slice_rows, keys);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const auto reduce = k <= 64 ? sim_topk_reduce_kernel<64, false> : sim_topk_reduce_kernel<128, false>;
+    hipLaunchKernelGGL(reduce, dim3((n_queries + 63) / 64), dim3(256), 0, s, keys, slices, n_queries, k, (const int32_t*)nullptr, 0, group_offset,
+                       merge, idx, score);
+    return hipGetLastError();
+}
+
+hipError_t launch_sim_ordered(const float* words, const int32_t* woff, const int32_t* tfq, int n_tiles, const void* gallery, bool gallery_f16,
+                              int n_queries, int n_gallery, int D, int k, const int32_t* g_offsets, int n_groups, int group_offset, int merge,
+                              int32_t* idx, float* score, float* pair, long pair_ld, int slices, int slice_rows, unsigned long long* keys,
+                              hipStream_t s) {
+    if (n_queries <= 0) return hipSuccess;
+    if (!words || !woff || !tfq || n_tiles < 1 || n_tiles > n_queries || D <= 0 || D % 64 || k < 1 || k > SIM_TOPK_MAX_K || n_gallery < 0 ||
+        n_groups < 0 || (n_groups > 0 && !g_offsets) || group_offset < 0 || group_offset > INT32_MAX - n_groups || (pair && pair_ld < n_queries) ||
+        slices < 1 || slices > 65535 || slice_rows < 64 || slice_rows % 64 || (slices > 1 && (!keys || (long)(slices - 1) * slice_rows >= n_gallery)))
+        return hipErrorInvalidValue;
+    return gallery_f16 ? launch_ordered(words, woff, tfq, n_tiles, static_cast<const _Float16*>(gallery), n_queries, n_gallery, D, k, g_offsets,
+                                        n_groups, group_offset, merge, idx, score, pair, pair_ld, slices, slice_rows, keys, s)
+                       : launch_ordered(words, woff, tfq, n_tiles, static_cast<const float*>(gallery), n_queries, n_gallery, D, k, g_offsets,
+                                        n_groups, group_offset, merge, idx, score, pair, pair_ld, slices, slice_rows, keys, s);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Alignment (jg_sim_align): which frame every word of a returned (query, group) pair took.  One workgroup per slot (q, r) of idx; a slot
+// whose entry is not one of this call's groups is left alone.  The group's rows [a, b) (goff at the group and the next, clamped to the
+// gallery) are walked in 64-row-aligned tiles through sim_tile with the query's word rows alone as the 64-row operand, and wave 0 runs the
+// recurrence above per tile -- with M_{i-1} replaced by +0.0 when not ordered, which leaves E_i = s(w_i, .) and M_i the running max
+// jg_sim_coupling takes.  Nothing of E is kept but one bit per cell: sBit[word][tile] = the ballot of "this column strictly raised the word's
+// running max" (for a first value: "is not NaN").  The first arg-max of E_i over [0, c] is then the last set bit at or below c, so one wave
+// backtracks from word W down to 1: ordered, the limit c of a word is the frame of the word after it; unordered, it is T - 1 for every
+// word.  The score is M_W(T - 1) / W (ordered), or the M_i(T - 1) added in word order / W (unordered): the bits of the two scans.
+constexpr int ALIGN_MAX_T = SPOT_MAX_T;                                // rows of a group that is aligned
+constexpr int ALIGN_TILES = ALIGN_MAX_T / 64 + 1;                      // ... which lie in at most this many 64-row-aligned tiles
+
+template <class GT>
+__global__ __launch_bounds__(256) void sim_align_kernel(const float* __restrict__ words, const int32_t* __restrict__ woff,
+                                                        const GT* __restrict__ gallery, int n_gallery, int D,
+                                                        const int32_t* __restrict__ goff, int n_groups, int group_offset,
+                                                        const int32_t* __restrict__ idx, int k, int ordered, int32_t* __restrict__ frames,
+                                                        int frames_ld, float* __restrict__ score) {
+    __shared__ __attribute__((aligned(16))) float sA[64][64];          // [k][word row]
+    __shared__ __attribute__((aligned(16))) float sB[64][64];          // [k][gallery row]
+    __shared__ float sS[64][64];                                       // the tile's scores, [word row][column]
+    __shared__ u64 sBit[64][ALIGN_TILES];                              // [word row][tile]: the columns that raised the word's running max
+    __shared__ float sCarry[64];                                       // M_i at the last column so far
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long slot = blockIdx.x;                                      // q k + r
+    const int q = (int)(slot / k);
+    const int32_t entry = idx[slot];
+    const long gl = (long)entry - group_offset;
+    if (entry < 0 || gl < 0 || gl >= n_groups) return;                 // -1, or another piece's group: not this call's slot
+    const int g = (int)gl;
+    const int w0 = woff[q], W = woff[q + 1] - w0;
+    const int lo = goff[g], hi = goff[g + 1];
+    const int a = lo > 0 ? lo : 0, b = hi < n_gallery ? hi : n_gallery;
+    int32_t* const fr = frames + slot * frames_ld;
+    const bool none = b <= a || (long)b - a > ALIGN_MAX_T;             // no row, or more rows than are aligned
+    const int base = a & ~63;                                          // column c = gallery row base + c
+    const int ntiles = none ? 0 : (int)(((long)b - base + 63) >> 6);
+
+    if (tid < 64) sCarry[tid] = __uint_as_float(0x7fc00000u);
+    for (int tile = 0; tile < ntiles; ++tile) {
+        const int j0 = base + tile * 64;
+        const f32x16 acc = sim_tile(words, gallery, w0, j0, w0 + W, n_gallery, D, sA, sB, tid);
+        sim_tile_store(acc, sS, tid);
+        __syncthreads();
+        if (wave == 0) {
+            const long col = (long)j0 + lane;
+            const bool in = col >= a && col < b;
+            float m = 0.f;
+            for (int i = 0; i < W; ++i) {
+                const float ev = in ? (ordered ? m : 0.f) + sS[i][lane] : __uint_as_float(0x7fc00000u);
+                const float incl = wave_fmax_scan(ev, lane);
+                float before = __shfl_up(incl, 1, 64);               // the running max in front of this column
+                const float carry = sCarry[i];
+                before = lane == 0 ? carry : fmaxf(before, carry);
+                const u64 raised = __ballot(ev == ev && !(ev <= before));
+                m = fmaxf(incl, carry);
+                if (lane == 63) sCarry[i] = m;
+                if (lane == 0) sBit[i][tile] = raised;
+            }
+        }
+        // (the next tile's sim_tile begins with a barrier: wave 0 has read sS before it is written again)
+    }
+    __syncthreads();
+    if (wave != 0) return;
+    // the score, the same in every lane
+    float sum = 0.f;
+    bool all = !none;
+    if (ordered) {
+        sum = sCarry[W - 1];
+        all = all && sum == sum;
+    } else {
+        for (int i = 0; i < W; ++i) {
+            const float m = sCarry[i];
+            all = all && m == m;
+            sum += m;
+        }
+    }
+    // the backtrack: word i's frame = the last set bit of its row at or below `limit`
+    int mine = -1;                                                     // lane i keeps the frame of word i
+    int limit = all ? (int)((long)b - 1 - base) : -1;
+    for (int i = W - 1; i >= 0 && all; --i) {
+        int found = -1;
+        const int lt = limit >> 6;
+        for (int t0 = (lt >> 6) << 6; t0 >= 0 && found < 0; t0 -= 64) {
+            const int t = t0 + lane;
+            u64 bitsv = 0ull;
+            if (t <= lt) {
+                bitsv = sBit[i][t];
+                if (t == lt) bitsv &= ~0ull >> (63 - (limit & 63));
+            }
+            const u64 any = __ballot(bitsv != 0ull);
+            if (any) {
+                const int src = 63 - __builtin_clzll(any);
+                const u64 top = topk_readlane(bitsv, src);
+                found = (t0 + src) * 64 + 63 - __builtin_clzll(top);
+            }
+        }
+        if (found < 0) { all = false; break; }                         // (cannot be: a non-NaN M_i has a column that raised it)
+        if (lane == i) mine = base + found;
+        if (ordered) limit = found;
+    }
+    for (int i = lane; i < frames_ld; i += 64) fr[i] = all && i < W ? mine : -1;      // (W <= 64: word i is lane i's)
+    if (lane == 0) score[slot] = all ? __fdiv_rn(sum, (float)W) : __uint_as_float(0x7fc00000u);
+}
+
+hipError_t launch_sim_align(const float* words, const int32_t* woff, const void* gallery, bool gallery_f16, int n_queries, int n_gallery, int D,
+                            const int32_t* g_offsets, int n_groups, int group_offset, const int32_t* idx, int k, int ordered, int32_t* frames,
+                            int frames_ld, float* score, hipStream_t s) {
+    if (n_queries <= 0) return hipSuccess;
+    if (!words || !woff || !gallery || !idx || !frames || !score || D <= 0 || D % 64 || k < 1 || k > SIM_TOPK_MAX_K || n_gallery < 0 ||
+        n_groups < 0 || (n_groups > 0 && !g_offsets) || group_offset < 0 || group_offset > INT32_MAX - n_groups || frames_ld < 1 ||
+        (long)n_queries * k > INT32_MAX)
+        return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((long)n_queries * k));
+    if (gallery_f16) {
+        record_kernel("sim_align_kernel<_Float16>");
+        hipLaunchKernelGGL(sim_align_kernel<_Float16>, grid, dim3(256), 0, s, words, woff, static_cast<const _Float16*>(gallery), n_gallery, D,
+                           g_offsets, n_groups, group_offset, idx, k, ordered, frames, frames_ld, score);
+    } else {
+        record_kernel("sim_align_kernel<float>");
+        hipLaunchKernelGGL(sim_align_kernel<float>, grid, dim3(256), 0, s, words, woff, static_cast<const float*>(gallery), n_gallery, D,
+                           g_offsets, n_groups, group_offset, idx, k, ordered, frames, frames_ld, score);
+    }
+    return hipGetLastError();
+}
+
 // rows (as jg_sim_topk_grouped returns them) -> group and position inside it: an element-wise binary search; -1 / -1 for idx < 0 or a row
 // in no group.  Hostile offsets give some group and position, nothing else.
 __global__ void group_of_rows_kernel(const int32_t* __restrict__ idx, long n, const int32_t* __restrict__ goff, int n_groups,

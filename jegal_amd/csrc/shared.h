@@ -271,6 +271,17 @@ hipError_t launch_sim_coupling(const float* words, const int32_t* woff, const in
                                int n_queries, int n_gallery, int D, int k, const int32_t* g_offsets, int n_groups, int group_offset, int merge,
                                int32_t* idx, float* score, float* pair, long pair_ld, int slices, int slice_rows, unsigned long long* keys,
                                hipStream_t s);
+// jg_sim_ordered: launch_sim_coupling's arguments, plan and lists, with the words assigned to rows of the group in word order (retrieval.hip)
+hipError_t launch_sim_ordered(const float* words, const int32_t* woff, const int32_t* tfq, int n_tiles, const void* gallery, bool gallery_f16,
+                              int n_queries, int n_gallery, int D, int k, const int32_t* g_offsets, int n_groups, int group_offset, int merge,
+                              int32_t* idx, float* score, float* pair, long pair_ld, int slices, int slice_rows, unsigned long long* keys,
+                              hipStream_t s);
+// jg_sim_align: per slot of idx [n_queries][k] that names one of this call's groups, the row of every word (frames [n_queries k][frames_ld],
+// -1 behind the query's words) and the pair's score, ordered or not; other slots are not written.  woff on the device, frames_ld >= the
+// longest query (the entry checks it)
+hipError_t launch_sim_align(const float* words, const int32_t* woff, const void* gallery, bool gallery_f16, int n_queries, int n_gallery, int D,
+                            const int32_t* g_offsets, int n_groups, int group_offset, const int32_t* idx, int k, int ordered, int32_t* frames,
+                            int frames_ld, float* score, hipStream_t s);
 // grp / pos [n]: the group that holds row idx[e] - gallery_offset and the row's place inside it; -1 / -1 for idx[e] < 0 or a row in no group
 hipError_t launch_group_of_rows(const int32_t* idx, long n, const int32_t* g_offsets, int n_groups, int gallery_offset, int32_t* grp,
                                 int32_t* pos, hipStream_t s);

@@ -8,7 +8,7 @@
     python -m jegal_amd.drivers inference_embs ...            # inference_embs.py (single clip -> <fname>.pkl)
     python -m jegal_amd.drivers attn_matrix --path F|D        # utils/plot_heatmap.py without the rendering (-> <name>.attn.npz)
     python -m jegal_amd.drivers retrieve --path D [--topk 10] # the retrieval evaluate_retrieval.py grades (-> retrieve_<direction>.npz)
-    python -m jegal_amd.drivers search --path D --query F.pkl [--level word|phrase|coupling]   # which clips gesture a word, and at which frame (-> search_<F>.npz)
+    python -m jegal_amd.drivers search --path D --query F.pkl [--level word|phrase|coupling|ordered] [--align]   # which clips gesture a word, and at which frame (-> search_<F>.npz)
     python -m jegal_amd.drivers asd --path D --file avs_asd.csv [--win N --hop M]   # the detection evaluate_asd.py grades (-> asd.npz)
     python -m jegal_amd.drivers sync_offset --checkpoint_path_gestsync CKPT --frames F.npy --wav F.wav [--mel F.npy] [--max_shift 15]   # audio-visual offset of a clip (-> <name>.sync.npz)
         [--win 125 --hop 25]   # the offset over time (start, offset_t, conf_t, curve_t);  several --frames: which track is in sync with the audio, per window
@@ -422,19 +422,21 @@ _RETRIEVAL_LINE = "R@1: {:.2f} - R@5: {:.2f} - R@10: {:.2f} - R@25: {:.2f} - R@5
 
 def cmd_evaluate_retrieval(argv, engine=None):
     """evaluate_retrieval.py.  --score coupling: the same two lines with the late-interaction score (every word's best frame in the clip,
-    metrics.coupling_retrieval_metrics) in place of the cosine of the pooled vectors; one process only.  engine: the Engine to run on
-    (default: this process's)."""
+    metrics.coupling_retrieval_metrics) in place of the cosine of the pooled vectors; --score ordered: that score with the words taking
+    frames in word order (jg_sim_ordered); either in one process only.  engine: the Engine to run on (default: this process's)."""
     p = argparse.ArgumentParser(prog="evaluate_retrieval")
     p.add_argument("--path", required=True)
-    p.add_argument("--score", default="pooled", choices=["pooled", "coupling"],
-                   help="pooled: the cosine of the clip-level means, as the reference; coupling: every word's best frame (late interaction)")
+    p.add_argument("--score", default="pooled", choices=["pooled", "coupling", "ordered"],
+                   help="pooled: the cosine of the clip-level means, as the reference; coupling: every word's best frame (late interaction); "
+                        "ordered: the same with the words' frames in word order")
     args = p.parse_args(argv)
     eng = _engine(engine, args)
-    if args.score == "coupling" and jdist.world_size() > 1:
-        raise SystemExit("--score coupling runs in one process: it is not sharded over ranks")
+    if args.score != "pooled" and jdist.world_size() > 1:
+        raise SystemExit("--score {} runs in one process: it is not sharded over ranks".format(args.score))
     _, feats = _load_pkls(args.path)
-    if args.score == "coupling":
-        both = M.coupling_retrieval_metrics([f["content_emb"] for f in feats], [f["gesture_emb"] for f in feats], engine=eng)
+    if args.score != "pooled":
+        both = M.coupling_retrieval_metrics([f["content_emb"] for f in feats], [f["gesture_emb"] for f in feats], engine=eng,
+                                            **({"ordered": True} if args.score == "ordered" else {}))
         res = {"Content to Gesture": both["c2g"], "Gesture to Content": both["g2c"]}
         for name, m in res.items():
             print("{} Retrieval scores:".format(name))
@@ -622,13 +624,16 @@ def cmd_search(argv, engine=None):
     --index FILE instead of --path: the corpus is one written by the index command (metrics.Corpus, jg_sim_search): prepared once, maybe
     in 16 bits, the same output.  --level coupling: the query's words stay separate rows of ONE query of at most 64 words, and a clip (or
     segment) scores as the mean over the words of each word's best frame in it (metrics.search_phrases, jg_sim_coupling); the .npz also
-    holds start (1,K) = the first frame of the returned group inside its clip, and `frame` repeats it.  engine: the Engine to run on
-    (default: this process's)."""
+    holds start (1,K) = the first frame of the returned group inside its clip, and `frame` repeats it.  --level ordered: as coupling, with
+    the words taking frames of the group in word order (jg_sim_ordered).  --align (coupling and ordered): the .npz also holds word_frame
+    (1,K,W) int32, the frame inside the returned clip that every word took (jg_sim_align), and the printed line shows each word with its
+    frame.  engine: the Engine to run on (default: this process's)."""
     p = argparse.ArgumentParser(prog="search", description="Single process: sharding over ranks is not built for this command.")
     p.add_argument("--path", default=None, help="a directory of JEGAL feature .pkl files: the corpus (or --index)")
     p.add_argument("--index", default=None, help="a corpus written by the index command, instead of --path: prepared once, maybe in 16 bits")
     p.add_argument("--query", required=True, help="a JEGAL feature .pkl whose content_emb rows are the query")
-    p.add_argument("--level", default="word", choices=["word", "phrase", "coupling"])
+    p.add_argument("--level", default="word", choices=["word", "phrase", "coupling", "ordered"])
+    p.add_argument("--align", action="store_true", help="--level coupling / ordered: also the frame every word took in each returned clip")
     p.add_argument("--topk", type=int, default=10, help="clips (or segments) kept per query row (1..128)")
     p.add_argument("--segment", type=int, default=0, help="frames per group; 0: a clip is one group")
     p.add_argument("--normalize", type=int, default=1, choices=[0, 1], help="1: cosine similarity (rows re-normalised); 0: the rows as stored")
@@ -650,30 +655,41 @@ def cmd_search(argv, engine=None):
     M.check_word_count(len(words), len(queries), args.query)
     if args.level == "phrase":
         queries, words = queries.mean(axis=0, keepdims=True), [" ".join(words)]
-    coupling = args.level == "coupling"
+    coupling = args.level in ("coupling", "ordered")
+    if args.align and not coupling:
+        raise SystemExit("--align goes with --level coupling or --level ordered")
+    more = {}                                    # (keywords only where asked for: an engine or a corpus of before is called as before)
+    if args.level == "ordered":
+        more["order"] = True
+    if args.align:
+        more["align"] = True
+    word_list = list(words)
     if coupling:                                 # the words stay separate rows of ONE query
         if not 1 <= len(queries) <= COUPLING_MAX_W:
-            raise SystemExit("--level coupling takes a query of 1..{} words, not {}".format(COUPLING_MAX_W, len(queries)))
+            raise SystemExit("--level {} takes a query of 1..{} words, not {}".format(args.level, COUPLING_MAX_W, len(queries)))
         queries, words = [queries], [" ".join(words)]
     if args.index is not None:                   # (its rows were normalised, or not, when it was built: --normalize is about the query)
         corpus = M.Corpus.load(args.index)
         names = corpus.names
         eng = _engine(engine, args)
-        clip, frame, score = (corpus.search_phrases if coupling else corpus.search)(queries, k=args.topk, segment=args.segment, normalize=bool(args.normalize), engine=eng,
-                                           max_rows=args.max_rows)
+        clip, frame, score, *rest = (corpus.search_phrases if coupling else corpus.search)(
+            queries, k=args.topk, segment=args.segment, normalize=bool(args.normalize), engine=eng, max_rows=args.max_rows, **more)
     else:
         names, clips = _corpus_clips(args.path)
         eng = _engine(engine, args)
-        clip, frame, score = (M.search_phrases if coupling else M.search)(queries, clips, k=args.topk, segment=args.segment, normalize=bool(args.normalize), engine=eng,
-                                      max_rows=args.max_rows)
+        clip, frame, score, *rest = (M.search_phrases if coupling else M.search)(
+            queries, clips, k=args.topk, segment=args.segment, normalize=bool(args.normalize), engine=eng, max_rows=args.max_rows, **more)
     os.makedirs(args.res_dir, exist_ok=True)
     out = os.path.join(args.res_dir, "search_{}.npz".format(_base_name(args.query)))
     if coupling:                                 # a group comes back, not a frame: `frame` is its first one, under both names
-        np.savez(out, words=np.asarray(words), names=names, clip=clip, start=frame, frame=frame, score=score)
+        np.savez(out, words=np.asarray(words), names=names, clip=clip, start=frame, frame=frame, score=score,
+                 **({"word_frame": rest[0]} if args.align else {}))
     else:
         np.savez(out, words=np.asarray(words), names=names, clip=clip, frame=frame, score=score)
     for i, w in enumerate(words):
         hits = ["{}@{} ({:.3f})".format(names[c], f, s) for c, f, s in zip(clip[i][:3], frame[i][:3], score[i][:3]) if c >= 0]
+        if args.align:                           # ... and every word with the frame it took
+            hits = ["{} [{}]".format(h, " ".join("{}@{}".format(wd, t) for wd, t in zip(word_list, rest[0][i][r]))) for r, h in enumerate(hits)]
         print("search: \"{}\" -> {} of {} clips: {}".format(w, int(np.sum(clip[i] >= 0)), len(names), ", ".join(hits) or "nothing"))
     print("search: {} query rows x top-{} -> {}".format(len(words), args.topk, out))
     return 0

@@ -145,7 +145,11 @@ def _search_walk(queries, dim, corpus, k, segment, normalize, engine, max_rows, 
     r0, r1, c0, c1, g_offsets, res) brings the gallery rows r0 .. r1 - 1 (of the clips c0 .. c1 - 1) to the device and scores them with the
     caller's entry, merging into res.  dim: what a message calls the queries' D.
     phrases: `queries` is a list of (W_i, D) word matrices, each ONE query (q: their rows, Q: their number); score_piece gets the piece's
-    first group as a ninth argument and returns GROUPS (Engine.sim_coupling), and `frame` is the first frame of the returned group."""
+    first group as a ninth argument and returns GROUPS (Engine.sim_coupling), and `frame` is the first frame of the returned group.
+    align_piece (phrases only; corpus(q) may return it as a third value): align_piece(eng, q, r0, r1, c0, c1, g_offsets, g0, idx, into)
+    passes the piece once more with the FINAL idx (Engine.sim_align, which writes the slots of the piece's groups only) -> into =
+    (frames, score); a fourth array comes back, word_frame
+    (Q, k, Wmax) int32: the frame inside the returned clip of every word, -1 behind a query's words and where there is no result."""
     k, segment = int(k), int(segment)
     if not 1 <= k <= 128:
         raise ValueError("k must be 1..128")
@@ -155,7 +159,7 @@ def _search_walk(queries, dim, corpus, k, segment, normalize, engine, max_rows, 
     if q.ndim != 2:
         raise ValueError("queries must be (Q, {})".format(dim))
     Q = len(queries) if phrases else int(q.shape[0])
-    lengths, score_piece = corpus(q)
+    lengths, score_piece, align_piece = (tuple(corpus(q)) + (None,))[:3]
     goff, gclip, gstart = search_groups(lengths, segment)
     n_groups = len(gclip)
     if goff[-1] > 2 ** 31 - 1:
@@ -164,12 +168,14 @@ def _search_walk(queries, dim, corpus, k, segment, normalize, engine, max_rows, 
     if max_rows is not None and (int(max_rows) < 1 or (n_groups and sizes.max() > int(max_rows))):
         raise ValueError("max_rows must hold the largest group ({} rows): groups are never split; use segment".format(int(sizes.max()) if n_groups else 0))
     empty = (np.full((Q, k), -1, np.int32), np.full((Q, k), -1, np.int32), np.full((Q, k), -np.inf, np.float32))
+    if align_piece:
+        empty += (np.full((Q, k, max([int(m.shape[0]) for m in queries] or [0])), -1, np.int32),)
     if Q == 0 or goff[-1] == 0:
         return empty
     eng = engine or Engine.get()
     if normalize:
         q = eng.l2norm(q)
-    res, g0 = None, 0
+    res, g0, pieces = None, 0, []
     while g0 < n_groups:                             # pieces = runs of whole groups of at most max_rows rows
         g1 = n_groups
         if max_rows is not None:
@@ -179,15 +185,26 @@ def _search_walk(queries, dim, corpus, k, segment, normalize, engine, max_rows, 
         r0, r1 = int(goff[g0]), int(goff[g1])
         if r1 > r0:
             res = score_piece(eng, q, r0, r1, int(gclip[g0]), int(gclip[g1 - 1]) + 1, goff[g0:g1 + 1] - r0, res, *([g0] if phrases else []))
+            pieces.append((g0, g1, r0, r1))
         g0 = g1
     if res is None:
         return empty
+    word_frame = None
+    if align_piece:
+        # every piece once more, now that the lists are final: a piece fills the slots of its own groups with rows counted from its first
+        into, piece_row0 = None, np.zeros(n_groups, np.int64)
+        for g0, g1, r0, r1 in pieces:
+            into = align_piece(eng, q, r0, r1, int(gclip[g0]), int(gclip[g1 - 1]) + 1, goff[g0:g1 + 1] - r0, g0, res[0], into)
+            piece_row0[g0:g1] = r0
+        rows, grp = to_host(into[0]).astype(np.int64), np.maximum(to_host(res[0]).astype(np.int64), 0)
+        clip_row0 = np.concatenate([[0], np.cumsum(np.asarray(lengths, np.int64))])[gclip[grp]]
+        word_frame = np.where(rows >= 0, rows + (piece_row0[grp] - clip_row0)[:, :, None], -1).astype(np.int32)
     grp, pos = (res[0], torch.zeros_like(res[0])) if phrases else eng.group_of_rows(res[0], goff, 0)
     grp, pos, score = to_host(grp).astype(np.int64), to_host(pos).astype(np.int32), to_host(res[1]).astype(np.float32)
     found = grp >= 0
     clip = np.where(found, gclip[np.maximum(grp, 0)], -1).astype(np.int32)
     frame = np.where(found, gstart[np.maximum(grp, 0)] + pos, -1).astype(np.int32)
-    return clip, frame, score
+    return (clip, frame, score) if word_frame is None else (clip, frame, score, word_frame)
 
 
 def search(queries, clips, k=10, segment=0, normalize=True, engine=None, max_rows=None):
@@ -225,22 +242,40 @@ def _phrase_list(queries):
     return mats, offsets_of(mats)
 
 
-def _no_phrases(k):
+def _no_phrases(k, align=False):
     if not 1 <= int(k) <= 128:
         raise ValueError("k must be 1..128")
-    return np.zeros((0, int(k)), np.int32), np.zeros((0, int(k)), np.int32), np.zeros((0, int(k)), np.float32)
+    out = np.zeros((0, int(k)), np.int32), np.zeros((0, int(k)), np.int32), np.zeros((0, int(k)), np.float32)
+    return out + (np.zeros((0, int(k), 0), np.int32),) if align else out
 
 
-def search_phrases(queries, clips, k=10, segment=0, normalize=True, engine=None, max_rows=None):
+def _phrase_pieces(rows_of, w_off, k, order, align):
+    """score_piece and align_piece of the two search_phrases (_search_walk): rows_of(eng, r0, r1, c0, c1) brings a piece's rows to the
+    device; order: jg_sim_ordered instead of jg_sim_coupling (called only then)."""
+    def score_piece(eng, q, r0, r1, c0, c1, g_offsets, res, g0):
+        entry = eng.sim_ordered if order else eng.sim_coupling
+        return entry(q, w_off, rows_of(eng, r0, r1, c0, c1), g_offsets, int(k), group_offset=g0, merge_into=res)
+
+    def align_piece(eng, q, r0, r1, c0, c1, g_offsets, g0, idx, into):
+        return eng.sim_align(q, w_off, rows_of(eng, r0, r1, c0, c1), g_offsets, idx, bool(order), group_offset=g0, into=into)
+    return score_piece, align_piece if align else None
+
+
+def search_phrases(queries, clips, k=10, segment=0, normalize=True, engine=None, max_rows=None, order=False, align=False):
     """search() for queries of several words that keeps the word-to-frame structure (late interaction, jg_sim_coupling): queries is a list
     of (W_i, D) word matrices (1..64 rows each), each ONE query; a group of frames (a clip, or a run of `segment` frames of it) scores as
     the mean over the query's words of each word's best frame in the group -- no pooling of the words or the frames, no (words) x (frames)
     matrix.  clips, segment, normalize and max_rows as for search(); pieces are cut at group boundaries and merged, the same result.
     Returns host arrays (clip (Q, k) int32, start (Q, k) int32: the first frame of the returned group inside its clip (search_groups),
-    score (Q, k) float32), best first, ties to the earlier group; -1 / -1 / -inf where fewer than k groups have a score."""
+    score (Q, k) float32), best first, ties to the earlier group; -1 / -1 / -inf where fewer than k groups have a score.
+    order: the words are assigned to frames in word order (jg_sim_ordered): the score is the best mean over frames t_1 <= .. <= t_W, one
+    frame may serve consecutive words; it never exceeds the unordered score.
+    align: a fourth array, word_frame (Q, k, Wmax) int32: the frame inside the returned clip (counted from the clip's first frame, also
+    with segment > 0) that every word of the query took in the returned group (jg_sim_align); -1 behind a query's words and in empty
+    slots.  Under max_rows the pieces are passed a second time, after the lists are final."""
     mats_q, w_off = _phrase_list(queries)
     if not mats_q:
-        return _no_phrases(k)
+        return _no_phrases(k, align)
 
     def corpus(q):
         D = int(q.shape[1])
@@ -249,20 +284,19 @@ def search_phrases(queries, clips, k=10, segment=0, normalize=True, engine=None,
             raise ValueError("every clip must be (T_i, {}) like the queries".format(D))
         first_row = np.concatenate([[0], np.cumsum([c.shape[0] for c in mats])])
 
-        def score_piece(eng, q, r0, r1, c0, c1, g_offsets, res, g0):
+        def rows_of(eng, r0, r1, c0, c1):
             rows = cat_rows(mats[c0:c1])[r0 - int(first_row[c0]):r1 - int(first_row[c0])]
-            if normalize:
-                rows = eng.l2norm(rows)
-            return eng.sim_coupling(q, w_off, rows, g_offsets, int(k), group_offset=g0, merge_into=res)
-        return [c.shape[0] for c in mats], score_piece
+            return eng.l2norm(rows) if normalize else rows
+        return ([c.shape[0] for c in mats],) + _phrase_pieces(rows_of, w_off, k, order, align)
     return _search_walk(mats_q, "D", corpus, k, segment, normalize, engine, max_rows, phrases=True)
 
 
-def coupling_matrix(contents, gestures, normalize=True, engine=None):
+def coupling_matrix(contents, gestures, normalize=True, engine=None, ordered=False):
     """The late-interaction score of every utterance against every clip: contents is a list of (W_i, D) word matrices (1..64 rows each),
     gestures a list of (T_j, D) frame matrices; entry (i, j) is the mean over utterance i's words of each word's largest product with a
     frame of clip j (normalize: rows L2-normalised first, so cosines).  One jg_sim_coupling call; the (words) x (frames) matrix is never
-    written.  Returns the (N_c, N_g) float32 matrix on the engine's device; NaN where a pair has no score (an empty clip)."""
+    written.  Returns the (N_c, N_g) float32 matrix on the engine's device; NaN where a pair has no score (an empty clip).
+    ordered: the words take frames in word order (one jg_sim_ordered call instead), never more than the unordered entry."""
     eng = engine or Engine.get()
     mats_c, w_off = _phrase_list(contents)
     if not mats_c or not len(gestures):
@@ -270,20 +304,21 @@ def coupling_matrix(contents, gestures, normalize=True, engine=None):
     w, g = cat_rows(mats_c), cat_rows(gestures)
     if normalize:
         w, g = eng.l2norm(w), eng.l2norm(g)
-    return eng.sim_coupling(w, w_off, g, offsets_of(gestures), 1, want_matrix=True)[2]
+    return (eng.sim_ordered if ordered else eng.sim_coupling)(w, w_off, g, offsets_of(gestures), 1, want_matrix=True)[2]
 
 
-def coupling_retrieval_metrics(contents, gestures, engine=None):
+def coupling_retrieval_metrics(contents, gestures, engine=None, ordered=False):
     """R@K and the median rank of evaluate_retrieval with the late-interaction score in place of the cosine of the pooled vectors:
     {"c2g": .., "g2c": ..}, each in metrics_from_ranks' form, both from the one coupling_matrix (utterance i belongs to clip i).  The rank
     of a partner is the number of strictly larger entries in its row (c2g) or its column (g2c), ties counted as jg_sim_rank counts them.
     g2c here ranks the UTTERANCES for a clip by the same word -> frame score (every word of the utterance looks for its best frame in the
-    clip); it is not a second, frame -> word score.  Counted with torch on the device matrix.  Single process only."""
+    clip); it is not a second, frame -> word score.  Counted with torch on the device matrix.  Single process only.
+    ordered: from coupling_matrix(ordered=True), the score with the words in order."""
     if jdist.world_size() > 1:
         raise RuntimeError("coupling_retrieval_metrics runs in one process: it is not sharded over ranks")
     if len(contents) != len(gestures):
         raise ValueError("one clip per utterance")
-    M = coupling_matrix(contents, gestures, engine=engine)
+    M = coupling_matrix(contents, gestures, engine=engine, ordered=ordered)
     d = M.diagonal()
     out = {}
     for name, part, own in (("c2g", M, d[:, None]), ("g2c", M.t(), d[:, None])):
@@ -373,21 +408,20 @@ class Corpus:
             return self.lengths, score_piece
         return _search_walk(queries, self.rows.shape[1], corpus, k, segment, normalize, engine, max_rows)
 
-    def search_phrases(self, queries, k=10, segment=0, normalize=True, engine=None, max_rows=None):
-        """search_phrases() over the prepared rows, 16- or 32-bit as stored: the same (clip, start, score) triple through jg_sim_coupling;
-        the rest as for search()."""
+    def search_phrases(self, queries, k=10, segment=0, normalize=True, engine=None, max_rows=None, order=False, align=False):
+        """search_phrases() over the prepared rows, 16- or 32-bit as stored: the same (clip, start, score) triple through jg_sim_coupling,
+        or jg_sim_ordered with order, and word_frame with align; the rest as for search()."""
         mats_q, w_off = _phrase_list(queries)
         if not mats_q:
-            return _no_phrases(k)
+            return _no_phrases(k, align)
 
         def corpus(q):
             if self.rows.shape[0] and q.shape[1] != self.rows.shape[1]:
                 raise ValueError("queries must be (W_i, {})".format(self.rows.shape[1]))
 
-            def score_piece(eng, q, r0, r1, c0, c1, g_offsets, res, g0):
-                return eng.sim_coupling(q, w_off, self._device_rows(eng, r0, r1, max_rows is None), g_offsets, int(k), group_offset=g0,
-                                        merge_into=res)
-            return self.lengths, score_piece
+            def rows_of(eng, r0, r1, c0, c1):
+                return self._device_rows(eng, r0, r1, max_rows is None)
+            return (self.lengths,) + _phrase_pieces(rows_of, w_off, k, order, align)
         return _search_walk(mats_q, self.rows.shape[1], corpus, k, segment, normalize, engine, max_rows, phrases=True)
 
 
