@@ -71,8 +71,11 @@ def test_rc_result_of_a_clip_does_not_depend_on_the_batch(rc):
 
 @pytest.mark.parametrize("opt", ["fuse_ln", "gemm_glds", "qkv0_linear", "gemm_big_tile", "dual_stream"])
 def test_rc_options_fall_back_to_hi_lo_or_stay_within_tolerance(rc, opt):
-    """Where the per-clip epilogue is not available (unfused LayerNorm, register-staged GEMM) the run-time corrected layers run hi+lo:
-    never single fp16 without its correction."""
+    """Where the per-clip epilogue is not available (unfused LayerNorm, register-staged GEMM) the run-time corrected layers run hi+lo.
+    This test only holds each arrangement to the 1e-3 of the whole path, which single fp16 WITHOUT its correction would pass too
+    (6.6e-4).  "Never single fp16 without its correction" is checked where it can be seen:
+    tests/test_gpu_precision_budget.py::test_corrected_plan_was_taken counts the correction launches of the fused plan, and
+    ::test_runtime_correction_removes_the_weight_rounding_bias measures what they remove with the transformer alone in 16-bit."""
     gsd, jsd = O.tensors(synth.gestsync_state_dict(include_unused=False)), O.tensors(synth.jegal_state_dict())
     T = 60
     frames = synth.synth_frames(5150, 2, T)

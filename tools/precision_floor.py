@@ -17,12 +17,12 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 import jegal_oracle as O  # noqa: E402
 from jegal_amd import synth  # noqa: E402
 import jegal_amd._lib as L  # noqa: E402
-from jegal_amd.gestsync import GestSync  # noqa: E402
-from jegal_amd.jegal import JEGAL  # noqa: E402
+import precision_engine as PE  # noqa: E402
 
 
 def rel(a, b):
@@ -58,20 +58,10 @@ def main():
         extra = [tuple([kv.split("=")[0], int(kv.split("=")[1])]) for kv in args.opts.split(",") if kv]
 
         def run(tag, prec, aw=False, masks=(0,), opts=(), parts=(0,)):
-            e = L.Engine(0, precision=prec)
+            e = PE.open_engine(prec, gsd, jsd, audit_weights=aw, opts=opts)
             try:
-                if aw:
-                    e.set_option("audit_weights", 1)
-                for k, v in opts:
-                    e.set_option(k, v)
-                GestSync(engine=e).load_state_dict(gsd)
-                JEGAL(engine=e).load_state_dict(jsd)
                 for m, jp in [(m, jp) for m in masks for jp in parts]:
-                    if aw:
-                        e.set_option("audit_stages", m)
-                        e.set_option("audit_jegal_parts", jp)
-                    emb = e.extract_gesture(dev).cpu().numpy()
-                    feats = e.gestsync_clip(dev).cpu().numpy()
+                    emb, feats = PE.run(e, dev, m if aw else None, jp)
                     key = tag if not aw else f"{tag} stages={m}" + (f" jegal_parts={jp}" if jp else "")
                     rows[key] = {"gesture_rel": max(rel(emb[b], refs[b][1]) for b in range(B)),
                                  "gesture_maxabs": max(float(np.abs(emb[b] - refs[b][1]).max()) for b in range(B)),
